@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """Benchmark of the cut-scoring hot path (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--config c2|c4|c4-shard]
+    python bench.py --gpus N --steps K --warmup W [--config c2|c4|c4-shard] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, ms_per_step, the roofline of the score
+kernel from event pairs on a sample of the timed steps).  --full adds everything else the line can carry: the k = 2, 4, 5
+rates, the feasibility / optimality rounds, the cold round, c3 / c5 / mixed covers / triangle, the CPU baseline with the
+parity of the last timed round, and the per-phase times of the sharded step.  --dump-outputs DIR writes what the last timed
+step handed its caller (head ids, scores, lambda_min, cut rows, counters) as DIR/<name>.npy in float64.
 
 One "step" = one selection round over one batch of synthetic candidates whose index sets are
 resident in HBM, bracketed HOST TO HOST (SURVEY.md section 8 d): the LP point starts in a host
@@ -12,7 +18,7 @@ the round's results are back in host memory when the step ends.
 
   c2 (default)  BASELINE.json configs[1] per GPU: n = 100 dense, 1e6 random 3-variable index sets
                 (seed 7 + rank), weak scaling -- the configuration the metric is quoted on;
-                at N = 1 the line also carries the k = 2, 4, 5 rates as secondary fields.
+                at N = 1 a --full line also carries the k = 2, 4, 5 rates as secondary fields.
   c4            BASELINE.json configs[3]: n = 1000, 1e8 3-variable candidates IN TOTAL, generated on
                 the device by the counter-based Philox generator (candidate id -> index set), rank r
                 takes ids [r, r+1) * 1e8 / N: strong scaling.
@@ -21,7 +27,7 @@ the round's results are back in host memory when the step ends.
                 2/3/4-variable sets, enumerated on the device) at two LP points the reference's own trajectory recorded
                 (tests/golden/rounds_spar125_075_1_d4_s4.npz: round 2 = combined strategy, round 8 = feasibility), through
                 the fused C-ABI calls AND through the drop-in pair _sel_eigcut_by_ordering_on_measure + _gen_eigcuts_selected
-                (cut_select_qp.py:165-182).  The default (c2) run carries the same numbers as secondary.c3.
+                (cut_select_qp.py:165-182).  A --full c2 run carries the same numbers as secondary.c3.
 
 `value` = candidates scored per second over all ranks.  Rank 0 prints ONE JSON line.
 """
@@ -560,6 +566,54 @@ def bench_cold_round(make_scorer, K, n_local, vv_host, repeats=20):
     return out
 
 
+def _writable(path):
+    return os.access(path if os.path.exists(path) else os.path.dirname(path), os.W_OK)
+
+
+def checked_build(fn):
+    """fn() -- __graft_entry__.build, or the library build alone -- where this process may write the tree.  In a tree it cannot
+    write (built beforehand by another user), the same call in the build's no-compiler mode: objects and library are checked
+    against their sources and stamp, anything stale or missing raises, and nothing is written (the build rewrites its stamp
+    on every call that may compile)."""
+    from sdpcutsel_via_nn_amd import build as hip_build
+    if _writable(hip_build.STAMP):
+        return fn()
+    hipcc = hip_build.HIPCC
+    hip_build.HIPCC = os.path.join(os.devnull, "hipcc")
+    try:
+        return fn()
+    except RuntimeError as e:
+        raise RuntimeError("%s -- this process cannot write %s, so it does not compile: run build() first" % (e, hip_build.STAMP))
+    finally:
+        hip_build.HIPCC = hipcc
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(res, out_dir):
+    """--dump-outputs: the result of one round as its caller receives it -> out_dir/<name>.npy, float64 (ids, counts and flags
+    are exact in float64); scalars as 0-d arrays, the counters dict as counters_<name>.npy."""
+    arrays = {}
+    for name, v in res.items():
+        if isinstance(v, dict):
+            for k2, v2 in v.items():
+                arrays["%s_%s" % (name, k2)] = v2
+        else:
+            arrays[name] = v
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, v in sorted(arrays.items()):
+        if hasattr(v, "detach"):        # torch tensors of the sharded round
+            v = v.detach().cpu().numpy()
+        a = np.asarray(v, dtype=np.float64)
+        total += a.nbytes
+        if total > DUMP_LIMIT_BYTES:
+            raise RuntimeError("--dump-outputs: more than %d bytes" % DUMP_LIMIT_BYTES)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
+
+
 class _StdoutToStderr(object):
     """fd-level redirect: native libraries (RCCL prints a version banner when its first communicator
     comes up) must not put lines on stdout, which carries exactly one JSON line."""
@@ -628,7 +682,7 @@ def self_launch(n_ranks):
                          % (n_ranks, ", ".join(sorted(preload))))
         return 2
     from sdpcutsel_via_nn_amd import build as hip_build
-    hip_build.build(verbose=True)           # compile only: no dlopen, no GPU
+    checked_build(lambda: hip_build.build(verbose=True))           # compile only: no dlopen, no GPU
     # rendezvous port: a bound (never listening) SO_REUSEADDR socket keeps the number ours until the ranks are gone -- rank 0's
     # store binds the same port with SO_REUSEADDR, which Linux allows next to a non-listening holder, while a stranger's plain
     # bind() is refused (the bind-close-reuse of round 4 left a window)
@@ -701,7 +755,7 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--config", choices=sorted(CONFIGS) + ["c3"], default="c2")
-    ap.add_argument("--no-c3", action="store_true", help="skip secondary.c3 / c5 (the spar125-075-1 dim-4 rounds, the q_50 QCQP round) of the default run")
+    ap.add_argument("--no-c3", action="store_true", help="skip secondary.c3 / c5 (the spar125-075-1 dim-4 rounds, the q_50 QCQP round) of a --full run")
     ap.add_argument("--kernel", choices=["mfma", "simple", "valu"], default="mfma")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-cold", action="store_true", help="skip secondary.cold_round (rounds after 10 ms / 100 ms / 1 s of idle device: ~50 s)")
@@ -723,8 +777,17 @@ def main():
     ap.add_argument("--k", type=int, choices=[2, 3, 4, 5], default=None, help="candidate size (default: the config's, 3)")
     ap.add_argument("--time-every", type=int, default=8,
                     help="attach the HIP event pair to the score dispatch of every n-th step of the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary rates, c3 / c5 / mixed covers / triangle, the cold round, the CPU baseline with parity "
+                         "and the per-phase times of the sharded step (the --no-* options trim this)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0) as DIR/<name>.npy, float64")
     args = ap.parse_args()
+    if args.steps < 1:
+        sys.exit("--steps must be >= 1")
     if args.config == "c3":
+        if args.dump_outputs:
+            sys.exit("--dump-outputs: the c2, c4 and c4-shard configurations (c3 times several routes)")
         return main_c3(args)
     cfg = CONFIGS[args.config]
     if args.gpus < 1:
@@ -780,7 +843,7 @@ def main():
             else:
                 dist.init_process_group(backend)
         if rank == 0:
-            entry.build()
+            checked_build(entry.build)
         if use_dist:
             dist.barrier()          # the first collective: the communicator (and RCCL's banner) come up here
 
@@ -896,10 +959,13 @@ def main():
     if use_dist:
         dist.barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # before any other call on this handle: copy=False results are views of its pinned block
+        dump_outputs(last_res, args.dump_outputs)
     # the LAST round of the timed region, kept for the parity object of the line (compared with the ranking of the oracle's own
     # scores after everything is timed, cpu_baseline): ids / scores as returned, the device's score arrays of that round
     gpu_rounds = {}
-    if world == 1 and sel is None and not args.no_cpu_baseline:
+    if args.full and world == 1 and sel is None and not args.no_cpu_baseline:
         gpu_rounds[4] = gpu_round_record(sc, last_res, 4)
     rank_ms = None
     if use_dist:
@@ -915,7 +981,7 @@ def main():
         dt = float(t.item())
 
     phases = None
-    if sel is not None:
+    if args.full and sel is not None:
         # Where a sharded step goes (every rank runs the loop -- it contains the collective --, rank 0 reports): device
         # time between events on the stream the library and the collective share, host time around each call.  Untimed
         # extra steps after the measured region; the events cost the host a few microseconds each.
@@ -988,7 +1054,7 @@ def main():
         out["config"]["selection_fallbacks"] = sc.get_stat(_capi.STAT_SELECT_FALLBACKS)       # rounds answered by the full-sort path
         out["roofline"]["traffic_source"] = ("profiles/score_kernel_traffic.json (rocprofv3 --pmc passes of this kernel at "
                                              "this size; not re-measured in this run)") if traffic else None
-        if world == 1 and args.config == "c2" and not args.no_secondary:
+        if args.full and world == 1 and args.config == "c2" and not args.no_secondary:
             # SURVEY 8 d: "+ k = 2, 4, 5 single GPU as secondary" -- same round, same sizes, the other three networks
             sec = {}
             for k2 in (2, 4, 5):
@@ -1027,7 +1093,7 @@ def main():
                 out["secondary"]["c5"] = bench_c5(local_rank, max(20, args.steps // 4))
                 out["secondary"]["mixed_cover"] = bench_mixed_cover(local_rank, max(50, args.steps // 2))
                 out["secondary"]["triangle"] = bench_triangle(local_rank, max(20, args.steps // 4))
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             vv_host = np.array(vv_host)     # (detach from the handle's pinned buffer: worker processes pickle it)
             if sets_host is None:       # device-generated list: the numpy twin of the generator names the sample
                 m = min(args.cpu_sample, n_local)
@@ -1074,7 +1140,7 @@ def main_c3(args):
     torch.cuda.set_device(0)
     import __graft_entry__ as entry
     with _StdoutToStderr():
-        entry.build()
+        checked_build(entry.build)
     import gc
     gc.collect()
     gc.freeze()

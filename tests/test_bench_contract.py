@@ -32,7 +32,7 @@ def test_bench_names_the_baseline_metric():
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_roofline_and_cpu_baseline():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "1",
-                          "--cpu-sample", "20000"], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+                          "--cpu-sample", "20000", "--full"], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert out.returncode == 0, out.stderr.decode()[-3000:]
     lines = [ln for ln in out.stdout.decode().splitlines() if ln.strip()]
     assert len(lines) == 1, lines
@@ -65,7 +65,7 @@ def test_bench_prints_one_json_line_with_roofline_and_cpu_baseline():
 def test_bench_config_c4_shard():
     """BASELINE.json configs[3] on one GPU: one of the eight shards (1.25e7 candidates of the on-device generator)."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c4-shard", "--steps", "3", "--warmup", "1",
-                          "--cpu-sample", "20000"], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+                          "--cpu-sample", "20000", "--full"], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert out.returncode == 0, out.stderr.decode()[-3000:]
     lines = [ln for ln in out.stdout.decode().splitlines() if ln.strip()]
     assert len(lines) == 1, lines
@@ -156,7 +156,8 @@ def test_plain_bench_returns_the_worst_rank_exit_code_and_leaves_nobody_behind()
 def test_plain_bench_gpus_2_on_the_one_gpu_box(config, extra):
     """The exact form a SCALE run may use -- `python3 bench.py --gpus 2 --steps 5` -- on the one-GPU box: both ranks on cuda:0
     (SDPCUT_BENCH_ONE_DEVICE=1), the all-gather through gloo.  rc 0, one JSON line, n_gpus 2, phases and the 8-GPU budget on it."""
-    out = _plain(["--gpus", "2", "--steps", "5", "--warmup", "1", "--no-cpu-baseline", "--no-secondary", "--config", config] + extra,
+    out = _plain(["--gpus", "2", "--steps", "5", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-secondary", "--config", config]
+                 + extra,
                  {"SDPCUT_BENCH_ONE_DEVICE": "1", "SDPCUT_BENCH_BACKEND": "gloo"}, timeout=900)
     assert out.returncode == 0, out.stderr.decode()[-3000:]
     lines = [ln for ln in out.stdout.decode().splitlines() if ln.strip()]
@@ -168,3 +169,80 @@ def test_plain_bench_gpus_2_on_the_one_gpu_box(config, extra):
     assert abs(d["value"] - 2 * per_rank / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"] and d["value"] > 3e8
     assert set(d["phases"]["device_us"]) == {"score_and_head", "all_gather", "merge_and_rows"}
     assert "step_ms" in d["expected_8gpu"]
+
+
+def test_bench_options_full_and_dump_outputs():
+    """the plain run is lean; what it leaves out is behind --full, and --dump-outputs names where the last step's arrays go"""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], cwd=ROOT, stdout=subprocess.PIPE,
+                         stderr=subprocess.PIPE, timeout=120)
+    assert out.returncode == 0, out.stderr.decode()[-2000:]
+    text = out.stdout.decode()
+    assert "--full" in text and "--dump-outputs DIR" in text
+
+
+def test_dump_outputs_writes_float64_arrays(tmp_path):
+    """bench.dump_outputs on a round's result as select_round returns it: one float64 .npy per array, scalar and counter"""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    res = dict(idx=np.array([7, 3, 2**40], dtype=np.int64), score=np.array([-1.5, -0.25, 0.0]), lam=np.zeros(3),
+               coef=np.arange(12, dtype=np.float64).reshape(3, 4), rhs=np.ones(3), ks=np.array([3, 3, 3], dtype=np.int32),
+               n_total=10 ** 6, new_strat=4, counters=dict(nb_violated=5, strong=2, violated=3, nb_positive=0))
+    names = bench.dump_outputs(res, str(tmp_path / "d"))
+    assert sorted(os.listdir(tmp_path / "d")) == sorted(n + ".npy" for n in names)
+    assert "counters_strong" in names and "coef" in names
+    for n in names:
+        a = np.load(tmp_path / "d" / (n + ".npy"))
+        assert a.dtype == np.float64
+    assert np.load(tmp_path / "d" / "idx.npy").tolist() == [7, 3, 2 ** 40]
+    assert np.load(tmp_path / "d" / "coef.npy").shape == (3, 4) and float(np.load(tmp_path / "d" / "n_total.npy")) == 10 ** 6
+    assert float(np.load(tmp_path / "d" / "counters_strong.npy")) == 2
+
+
+@pytest.mark.gpu
+def test_plain_bench_is_lean_and_dumps_the_same_outputs_twice(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: one line with the headline fields, `steps` timed steps, none of
+    the --full legs; --dump-outputs of two runs with the same arguments: the same arrays, bit for bit"""
+    import numpy as np
+    dumps = []
+    for run in range(2):
+        d = tmp_path / ("run%d" % run)
+        out = _plain(["--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", str(d)], {})
+        assert out.returncode == 0, out.stderr.decode()[-3000:]
+        lines = [ln for ln in out.stdout.decode().splitlines() if ln.strip()]
+        assert len(lines) == 1, lines
+        r = json.loads(lines[0])
+        assert r["metric"] == _baseline()["metric"] and r["unit"] == "candidates/s" and r["higher_is_better"] is True
+        assert r["dtype"] == "f64" and r["steps"] == 7 and r["warmup"] == 2 and r["n_gpus"] == 1
+        assert abs(r["value"] - 10 ** 6 / (r["ms_per_step"] * 1e-3)) <= 1e-6 * r["value"]
+        assert not {"secondary", "eig_only", "cpu_baseline", "parity", "phases"} & set(r)
+        arrays = {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}
+        assert {"idx", "score", "lam", "coef", "rhs", "ks", "new_strat"} <= set(arrays)
+        assert all(a.dtype == np.float64 for a in arrays.values())
+        assert 0 < arrays["idx"].shape[0] <= 5000 and arrays["coef"].shape[0] == arrays["idx"].shape[0]
+        dumps.append(arrays)
+    assert set(dumps[0]) == set(dumps[1])
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name], dumps[1][name]), name
+
+
+def test_bench_build_step_writes_nothing_in_a_tree_it_cannot_write(monkeypatch):
+    """bench.py in a tree built beforehand by another user: the library is checked against its sources and stamp and loaded,
+    the stamp is not rewritten (the build rewrites it on every call that may compile), and the compiler setting is restored"""
+    sys.path.insert(0, ROOT)
+    import bench
+    import __graft_entry__ as entry
+    from sdpcutsel_via_nn_amd import build as hip_build
+    entry.build()
+    with open(hip_build.STAMP, "rb") as f:
+        before = f.read()
+    mtime = os.stat(hip_build.STAMP).st_mtime_ns
+    hipcc = hip_build.HIPCC
+    monkeypatch.setattr(bench, "_writable", lambda path: False)
+    seen = []
+    monkeypatch.setattr(hip_build, "_compiler_id", lambda real=hip_build._compiler_id: seen.append(hip_build.HIPCC) or real())
+    bench.checked_build(entry.build)
+    assert seen and all(not os.path.exists(h) for h in seen) and hip_build.HIPCC == hipcc
+    with open(hip_build.STAMP, "rb") as f:
+        assert f.read() == before
+    assert os.stat(hip_build.STAMP).st_mtime_ns == mtime

@@ -14,7 +14,7 @@ GROUPS3=("SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ
 case "$1" in
 a)
   step "bench c2 (driver form)"
-  python3 bench.py > $out/r05_bench.json 2> $out/r05_bench.err || { tail -5 $out/r05_bench.err; exit 1; }
+  python3 bench.py --full > $out/r05_bench.json 2> $out/r05_bench.err || { tail -5 $out/r05_bench.err; exit 1; }
   step "kernel stats + PMC + traffic of the bench command"
   tools/gpu_profile.sh r05_k3 > $out/r05_k3_profile.log 2>&1 || { tail -5 $out/r05_k3_profile.log; exit 1; }
   step "eigenvalue-only kernel PMC"
@@ -43,9 +43,9 @@ c)
   step "config 4 shard"
   python3 bench.py --config c4-shard --no-cpu-baseline --steps 50 > $out/r05_bench_c4_shard.json 2>/dev/null
   step "sharded code path at N = 1, one-rank RCCL, self-launched two ranks on one GPU"
-  SDPCUT_BENCH_FORCE_SHARDED=1 python3 bench.py --no-cpu-baseline --no-secondary > $out/r05_bench_forced_sharded.json 2>/dev/null
-  SDPCUT_FORCE_COLLECTIVES=1 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29671 bench.py --gpus 1 --no-cpu-baseline --no-secondary > $out/r05_bench_one_rank_rccl.json 2>/dev/null
-  SDPCUT_BENCH_ONE_DEVICE=1 SDPCUT_BENCH_BACKEND=gloo python3 bench.py --gpus 2 --steps 50 --no-cpu-baseline --no-secondary > $out/r05_bench_plain_gpus2_one_device.json 2> $out/r05_bench_plain_gpus2.err
+  SDPCUT_BENCH_FORCE_SHARDED=1 python3 bench.py --full --no-cpu-baseline --no-secondary > $out/r05_bench_forced_sharded.json 2>/dev/null
+  SDPCUT_FORCE_COLLECTIVES=1 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29671 bench.py --gpus 1 --full --no-cpu-baseline --no-secondary > $out/r05_bench_one_rank_rccl.json 2>/dev/null
+  SDPCUT_BENCH_ONE_DEVICE=1 SDPCUT_BENCH_BACKEND=gloo python3 bench.py --gpus 2 --steps 50 --full --no-cpu-baseline --no-secondary > $out/r05_bench_plain_gpus2_one_device.json 2> $out/r05_bench_plain_gpus2.err
   step "accuracy"
   python3 tools/accuracy.py > $out/r05_accuracy.txt 2>/dev/null
   python3 tools/compat_accuracy.py >> $out/r05_accuracy.txt 2>/dev/null
