@@ -5,6 +5,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "topk_route.h"
 
 static std::string g_create_err;
 static std::mutex g_mu;
@@ -917,7 +918,7 @@ static int round_end(sdpcut_ctx *h, const void **block, int64_t *cap_out, int64_
     }
     ++h->stat_rounds;
     bool resorted = false;      // the head in d_idx / d_sc was produced after the enqueued epilogue ran: launch it again
-    if (P.fast_tried && !have && strat == SDPCUT_STRAT_COMB && hdr[4] == 2 && hdr[6] == 4 /* TK_MODE_COMBALL */) {
+    if (P.fast_tried && !have && strat == SDPCUT_STRAT_COMB && hdr[4] == 2 && hdr[6] == TK_MODE_COMBALL) {
         // the threshold tie group of the every-entry-visited ranking does not fit the sort buffers (a structured LP vertex):
         // cut it by its secondary key with two more selections (topk.hip: topk_tie_split) instead of sorting the full list
         int64_t c7[7];

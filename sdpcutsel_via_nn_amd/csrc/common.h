@@ -10,10 +10,6 @@
 #define SDPCUT_NEG_EIGVAL (-1e-15) /* _THRES_NEG_EIGVAL, cut_select_qp.py:24 */
 #define SDPCUT_BIG_M 1000.0        /* _BIG_M, cut_select_qp.py:26 */
 
-// lists shorter than this do not count the fine histogram of their selection (topk_dev.h): their heads come from the one-workgroup
-// selections or from passes over a few thousand keys, and their epilogues are too small to zero 34 KB more
-#define SDPCUT_PF_MIN_N 32768
-
 #define MAX_HIDDEN 64
 #define MAX_LAYERS 5
 
@@ -107,7 +103,7 @@ struct sdpcut_ctx {
     double *d_Q = nullptr;      // [L]
     double *d_vars = nullptr;   // [L + n]
     // set by sdpcut_shard_head_device around its selection: the sort's last kernel also writes the
-    // record header and the padding (topk.hip, tk_mergerank_kernel)
+    // record header and the padding (topk_sort.hip, tk_mergerank_kernel)
     int64_t *shard_rec = nullptr;
     int64_t shard_rec_count = 0, shard_rec_len = -1;
     bool have_point = false;
@@ -192,7 +188,7 @@ void free_candidates(sdpcut_ctx *h);             // capi.hip: drop the handle's 
 // (ScoreArgs::tk): ws = zeroed TopkWs of the selection that follows (topk_begin).
 struct ScoreFuse {
     void *ws;
-    int mode;      // TK_MODE_FEAS / OPT / STRONG of topk_dev.h: whose keys to count
+    int mode;      // TK_MODE_FEAS / OPT / STRONG of topk_route.h: whose keys to count
     int64_t k;     // head size of the selection (the streaming prefilter's bound rises to the k-th largest key); 0: no fine histogram
 };
 // strong_out (optional, device, 8 int64 replicas): the launches add the number of candidates with

@@ -15,6 +15,7 @@
 
 #include "common.h"
 #include "keys.h"
+#include "topk_route.h"
 
 // counters: [0] nb_violated  [1] strong  [2] violated_in_scan  [3] nb_positive
 __global__ void keys_first_kernel(int strat, int64_t n, const double *eig, const double *obj, uint64_t *key,
@@ -197,18 +198,18 @@ int rank_fast_mode(sdpcut_ctx *h, int strat, int64_t sel_size, int64_t max_out, 
     const int64_t n = h->N;
     if (sel_size > n) sel_size = n;
     if (score_add) *score_add = 0.0;
-    if (!(n > 0 && max_out >= 1 && max_out <= 16384)) return 0;      // TK_MAXK (topk_dev.h)
-    if (max_out > 8192 && strat == SDPCUT_STRAT_COMB) return 0;     // big heads: plain rankings only (the device-resolved regime's sort keeps keys AND indices in LDS)
-    if (strat == SDPCUT_STRAT_FEAS) return 1;
-    if (strat == SDPCUT_STRAT_OPT) return 2;
-    if (strat == SDPCUT_PART_STRONG) return 3;
+    if (!(n > 0 && max_out >= 1 && max_out <= TK_MAXK)) return 0;
+    if (max_out > TK_LDSK && strat == SDPCUT_STRAT_COMB) return 0;     // big heads: plain rankings only (the device-resolved regime's sort keeps keys AND indices in LDS)
+    if (strat == SDPCUT_STRAT_FEAS) return TK_MODE_FEAS;
+    if (strat == SDPCUT_STRAT_OPT) return TK_MODE_OPT;
+    if (strat == SDPCUT_PART_STRONG) return TK_MODE_STRONG;
     if (strat == SDPCUT_STRAT_COMB && sel_size >= 1 && max_out <= sel_size) {
         // combined scan, common regime: at least sel_size candidates are positive AND violated.
         // The scan stops after sel_size of them; the re-sorted list starts with exactly those,
         // +BIG_M, in obj_improve order (cut_select_qp.py:606-625).  rank_fast_finish verifies
         // the regime through the class size.
         if (score_add) *score_add = SDPCUT_BIG_M;
-        return 3;
+        return TK_MODE_STRONG;
     }
     return 0;
 }
@@ -220,7 +221,7 @@ int rank_fast_enqueue(sdpcut_ctx *h, int strat, int64_t sel_size, int64_t max_ou
     int mode = rank_fast_mode(h, strat, sel_size, max_out, &add);
     if (!mode) return 0;
     int64_t sel = sel_size < h->N ? sel_size : h->N;
-    if (auto_regime && strat == SDPCUT_STRAT_COMB) mode = 5 /* TK_MODE_COMBAUTO */;
+    if (auto_regime && strat == SDPCUT_STRAT_COMB) mode = TK_MODE_COMBAUTO;
     int rc = topk_select_enqueue(h, mode, max_out, add, d_idx_out, d_score_out, d_c4, stage, sel);
     return rc ? rc : 1;
 }
@@ -236,7 +237,7 @@ int rank_fast_finish(sdpcut_ctx *h, int strat, int64_t sel_size, int64_t max_out
     if (sel_size > n) sel_size = n;
     const bool comb = strat == SDPCUT_STRAT_COMB;
     if (c4[4]) return 0;
-    const bool all_visited = comb && c4[6] == 4 /* TK_MODE_COMBALL: resolved on the device, strong < sel_size */;
+    const bool all_visited = comb && c4[6] == TK_MODE_COMBALL;      // resolved on the device, strong < sel_size
     if (comb && !all_visited && c4[0] < sel_size) return 0;
     const int64_t total = (strat == SDPCUT_STRAT_OPT || comb) ? n : c4[0];
     const int64_t w = total < max_out ? total : max_out;
@@ -286,9 +287,9 @@ int rank_on_device(sdpcut_ctx *h, int strat, int64_t sel_size, int64_t max_out, 
     // then a function of its own (obj_improve, eigmin) alone (cut_select_qp.py:606-623), and the head
     // of the re-sorted list is a top-k by (new score, obj_improve, index) -- radix select again, with
     // obj_improve as secondary key where new scores tie (second stable sort of :625).
-    if (strat == SDPCUT_STRAT_COMB && strong >= 0 && strong < sel_size && n > 0 && max_out >= 1 && max_out <= 16384) {
+    if (strat == SDPCUT_STRAT_COMB && strong >= 0 && strong < sel_size && n > 0 && max_out >= 1 && max_out <= TK_MAXK) {
         const int64_t *d_c4 = nullptr;
-        rc = topk_select_enqueue(h, 4 /* TK_MODE_COMBALL */, max_out, 0.0, d_idx_out, d_score_out, &d_c4);
+        rc = topk_select_enqueue(h, TK_MODE_COMBALL, max_out, 0.0, d_idx_out, d_score_out, &d_c4);
         if (rc) return rc;
         int64_t c4[5] = {0, 0, 0, 0, 0};
         HIP_TRY(h, hipMemcpyAsync(c4, d_c4, 5 * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));

@@ -13,6 +13,7 @@
 
 #include "common.h"
 #include "keys.h"
+#include "topk_route.h"
 
 #define SHARD_HDR 8
 
@@ -94,7 +95,7 @@ extern "C" int sdpcut_shard_head_device(sdpcut_handle h, int strat, int64_t coun
 {
     if (!h) return SDPCUT_EINVAL;
     SDPCUT_NO_PENDING(h);
-    if (count < 1 || count > 16384 || !d_record) return sdpcut_fail(h, SDPCUT_EINVAL, "shard head: count must be 1..16384");
+    if (count < 1 || count > TK_MAXK || !d_record) return sdpcut_fail(h, SDPCUT_EINVAL, "shard head: count must be 1.." + std::to_string(TK_MAXK));
     const bool comball = strat == SDPCUT_PART_COMBALL;
     if (strat != SDPCUT_STRAT_FEAS && strat != SDPCUT_STRAT_OPT && strat != SDPCUT_PART_STRONG && !comball)
         return sdpcut_fail(h, SDPCUT_EINVAL, "shard head: strategy must be 1, 2, SDPCUT_PART_STRONG or SDPCUT_PART_COMBALL");
@@ -125,7 +126,7 @@ extern "C" int sdpcut_shard_head_device(sdpcut_handle h, int strat, int64_t coun
         if (comball) {
             // every entry of the shard is visited by the scan: its combined ranking is a sub-list of the global one; the
             // record carries obj_improve as secondary key for the merge
-            rc = topk_select_enqueue(h, 4 /* TK_MODE_COMBALL */, count < h->N ? count : h->N, 0.0, rec + SHARD_HDR + count,
+            rc = topk_select_enqueue(h, TK_MODE_COMBALL, count < h->N ? count : h->N, 0.0, rec + SHARD_HDR + count,
                                      (double *)(rec + SHARD_HDR), &d_c4, 0, 0);
             rc = rc ? rc : 1;
         } else {
@@ -158,7 +159,7 @@ extern "C" int sdpcut_shard_finish_enqueue(sdpcut_handle h, int32_t world, int64
     if (world < 1 || count < 1 || !d_allrec || sel_size < 1 || sel_size > (int64_t)world * count || (fields != 2 && fields != 3) ||
         pitch_words < rl)
         return sdpcut_fail(h, SDPCUT_EINVAL, "bad shard_finish arguments");
-    if (sel_size > 16384) return sdpcut_fail(h, SDPCUT_EINVAL, "shard_finish: at most 16384 entries");
+    if (sel_size > TK_MAXK) return sdpcut_fail(h, SDPCUT_EINVAL, "shard_finish: at most " + std::to_string(TK_MAXK) + " entries");
     if (coef_ld < h->row_len_max || coef_ld > SDPCUT_ROW_LD) return sdpcut_fail(h, SDPCUT_EINVAL, "bad coef_ld");
     if (!h->have_point) return sdpcut_fail(h, SDPCUT_ESTATE, "set_point first");
     HIP_TRY(h, hipSetDevice(h->device));

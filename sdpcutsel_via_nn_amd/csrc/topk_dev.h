@@ -1,25 +1,15 @@
-// Device-side pieces of the top-k selection shared by topk.hip and score.hip (the score kernel
-// can emit the radix keys and the first histogram itself, see ScoreArgs::tk).
+// Device-side pieces of the top-k selection shared by its route files (topk_passes.hip, topk_compact.hip, topk_small.hip,
+// topk_sort.hip), the host file topk.hip and the producers of the scores: the score kernels (score.hip, eig.hip) can emit the
+// first histograms of the selection themselves, see ScoreArgs::tk.  Modes, limits and the route decision: topk_route.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "common.h"
 #include "keys.h"
+#include "topk_route.h"
 
-#define TK_THREADS 256
-#define TK_MAXBLK 1024   // most workgroups a selection pass is launched with (blk_eq / blk_gt slots)
-#define TK_LDSK 8192     // heads whose compacted superset (keys AND indices) fits the merge kernel's LDS
-#define TK_MAXK 16384    // largest head: the merge keeps the keys in LDS and reads indices only on ties
 #define TK_UNROLL 8      // grid-stride rounds whose loads are issued together
-// lists of at most TK_SMALLSEL_N candidates with a head of at most TK_LDSK: selection by ONE workgroup, keys in LDS (tk_smallsel_kernel)
-#ifndef TK_SMALLSEL
-#define TK_SMALLSEL 1
-#endif
-#ifndef TK_SMALLSORT
-#define TK_SMALLSORT 1     // ... and, for heads of one tile at most, sorted and emitted by it too (ONE launch for the round's selection)
-#endif
-#define TK_SMALLSEL_N 12288
 #define TK_SMALLSEL_THREADS 1024
 // Replicas of the global histogram: same-address device-scope atomics are serialised at ~15-20 ns
 // each, so 256 workgroups flushing into ONE row cost ~5 us per pass; block b adds into replica
@@ -81,13 +71,6 @@ __device__ __forceinline__ uint64_t pf_edge(int f, bool feas)
 }
 // word of bin f inside a replica of the global table: consecutive bins in consecutive 128-B lines
 __device__ __forceinline__ int pf_slot(int f) { return (f & 63) * 32 + (f >> 6); }
-
-// 4: combined strategy when the scan visits every entry -- the key is the new score of
-// cut_select_qp.py:606-623, ties between equal new scores go by obj_improve, then index
-// 5: combined strategy, regime resolved ON THE DEVICE by the first pass: STRONG if the score kernels
-// counted at least `sel` strong candidates (counters[5]), else COMBALL -- one selection, no host
-// round trip in either regime
-enum { TK_MODE_FEAS = 1, TK_MODE_OPT = 2, TK_MODE_STRONG = 3, TK_MODE_COMBALL = 4, TK_MODE_COMBAUTO = 5 };
 
 __device__ __forceinline__ int64_t ld_i64(const int64_t *p);
 
@@ -380,3 +363,22 @@ __device__ __forceinline__ uint64_t masked_key(int mode, double eig, double obj)
     return (obj > 0.0 && viol) ? key_of(obj) : 0ull;
 }
 
+// obj != NULL (mode COMBALL): equal keys are ordered by obj_improve descending before the index --
+// the first stable sort of the reference (:601) under its second one (:625).  The scores are only
+// fetched for equal keys (rare unless the point is degenerate); padding never reaches the fetch.
+// The sort kernels are instantiated twice: TIE = false is the plain composite compare (a memory
+// fetch and a branch inside the comparator cost the common modes 30 % of both kernels).
+template <bool TIE>
+__device__ __forceinline__ bool comp_less(uint64_t ka, uint32_t ia, uint64_t kb, uint32_t ib, const double *obj)
+{
+    if constexpr (!TIE) {
+        return ka < kb || (ka == kb && ia < ib);
+    } else {
+        if (ka != kb) return ka < kb;
+        if (ia != 0xffffffffu && ib != 0xffffffffu) {
+            const uint64_t oa = key_of(obj[ia]), ob = key_of(obj[ib]);
+            if (oa != ob) return oa > ob;
+        }
+        return ia < ib;
+    }
+}

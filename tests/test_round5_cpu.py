@@ -131,7 +131,7 @@ def test_fine_histogram_window_arithmetic():
 
 
 def test_fixed_step_lower_bound_of_the_merge_ranks():
-    """numpy twin of the branch-free search of csrc/topk.hip (mergerank_body): steps 256, 128 .. 1 over the first 511 entries of a
+    """numpy twin of the branch-free search of csrc/topk_sort.hip (mergerank_body): steps 256, 128 .. 1 over the first 511 entries of a
     sorted tile of 512, one more comparison for the 512-th, give the number of entries below e -- for every position of e,
     including below the first and above the last entry -- and the ranks of all entries of several tiles, each counted in its own
     tile by position and in the others by this search, are a permutation."""
