@@ -6,12 +6,11 @@
 #include <vector>
 
 #include "../../include/sdpcut.h"
+#include "net_pack.h"      // MAX_HIDDEN, MAX_LAYERS, SDPCUT_INPUT_CLAMP, net_pack
+#include "round_layout.h"  // RowsLayout, CsrLayout
 
 #define SDPCUT_NEG_EIGVAL (-1e-15) /* _THRES_NEG_EIGVAL, cut_select_qp.py:24 */
 #define SDPCUT_BIG_M 1000.0        /* _BIG_M, cut_select_qp.py:26 */
-
-#define MAX_HIDDEN 64
-#define MAX_LAYERS 5
 
 // Device-side description of one trained MLP (k = 2..5); passed to kernels by value.
 struct NetDev {
@@ -38,7 +37,6 @@ struct NetDev {
     // inputs of a candidate once instead of its 150..256 activations
     int unclamped_ok;
 };
-#define SDPCUT_INPUT_CLAMP 3.0
 
 struct Bucket {
     int64_t n = 0;
@@ -52,7 +50,7 @@ struct NetHost {
     double *d_blob = nullptr;   // one allocation behind all device pointers of dev
 };
 
-// a fused round between its two halves (capi.hip: round_begin / round_end)
+// a fused round between its two halves (round.hip: round_begin / round_end)
 struct PendingRound {
     bool active = false, csr = false, fast_tried = false;
     int strat = 0;
@@ -170,10 +168,22 @@ static inline hipError_t sdpcut_sync(sdpcut_ctx *h)
 
 int sdpcut_fail(sdpcut_ctx *h, int code, const std::string &msg);
 int ensure_stage(sdpcut_ctx *h, size_t bytes);   // capi.hip: grow h->d_stage
-// capi.hip: (re)allocate the device arrays of a list of N candidates, cnt[k] of them of size k
+// inputs.hip: (re)allocate the device arrays of a list of N candidates, cnt[k] of them of size k
 int alloc_candidates(sdpcut_ctx *h, int64_t N, const int64_t cnt[SDPCUT_MAX_K + 1], int64_t global_base);
 int ensure_pinned(sdpcut_ctx *h, size_t bytes);  // capi.hip: grow h->pinned / h->pinned_dev
-void free_candidates(sdpcut_ctx *h);             // capi.hip: drop the handle's list (N = 0, nothing scored)
+void free_candidates(sdpcut_ctx *h);             // inputs.hip: drop the handle's list (N = 0, nothing scored)
+
+// the measures a strategy's selection reads (the partial strategies of a sharded round read both)
+static inline uint32_t strat_need(int strat)
+{
+    return strat == SDPCUT_STRAT_FEAS ? SDPCUT_EIG : strat == SDPCUT_STRAT_OPT ? SDPCUT_NN : (SDPCUT_EIG | SDPCUT_NN);
+}
+static inline int check_round_strategy(sdpcut_ctx *h, int strat)
+{
+    if (strat != SDPCUT_STRAT_FEAS && strat != SDPCUT_STRAT_OPT && strat != SDPCUT_STRAT_COMB)
+        return sdpcut_fail(h, SDPCUT_EINVAL, "strategy must be 1 (feasibility), 2 (optimality) or 4 (combined)");
+    return 0;
+}
 
 #define HIP_TRY(h, expr)                                                                   \
     do {                                                                                   \
@@ -202,16 +212,14 @@ int launch_cut_rows(sdpcut_ctx *h, int64_t count, const int64_t *d_limit, const 
 int launch_round_rows(sdpcut_ctx *h, int64_t cap, const int64_t *d_c4, const int64_t *d_idx, const double *d_score,
                       int coef_ld, void *block, int64_t hdr_bytes = 64, int64_t done_serial = 0);
 int launch_point_copy(sdpcut_ctx *h, const double *src_mapped, int64_t n);
-// rows.hip: the round's epilogue in CSR form (sdpcut_round_csr); byte offsets of the block's arrays
-struct CsrLayout { size_t idx, score, lam, rhs, values, ks, sets, row_entry, indptr, indices, bytes; };
-CsrLayout csr_layout(int64_t cap, int ld);
+// rows.hip: the round's epilogue in CSR form (sdpcut_round_csr; block layout: round_layout.h, csr_layout)
 int launch_round_csr(sdpcut_ctx *h, int64_t cap, const int64_t *d_c4, int64_t limit, const int64_t *d_idx, const double *d_score,
                      int ld, void *block, int64_t serial);
 // eig.hip: lambda_min of every candidate, one launch over all size classes; tk = TopkWs of a feasibility selection or NULL
 int launch_eig_only(sdpcut_ctx *h, void *tk, hipEvent_t ev_start, hipEvent_t ev_stop, int64_t pf_k = 0);
-int wait_round_done(sdpcut_ctx *h, const int64_t *word, int64_t serial);   // capi.hip
+int wait_round_done(sdpcut_ctx *h, const int64_t *word, int64_t serial);   // round.hip
 int score_for_selection(sdpcut_ctx *h, int strat, int64_t sel_size, int64_t cap, uint32_t need, bool allow_auto, int *stage,
-                        bool *auto_out);                                   // capi.hip
+                        bool *auto_out);                                   // round.hip
 int launch_eig_batch(sdpcut_ctx *h, int k, int64_t count, const double *d_x, const double *d_X,
                      double *d_vals, double *d_vecs);
 int launch_nn_batch(sdpcut_ctx *h, int k, int64_t count, const double *d_in, double *d_out);

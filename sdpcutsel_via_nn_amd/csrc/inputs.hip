@@ -1,0 +1,223 @@
+// What a handle is given before it can score (include/sdpcut.h): the networks, the instance, the candidate list, the LP point.
+#include <cstring>
+
+#include "common.h"
+
+// Device arrays of a candidate list of N entries, cnt[k] of them with k variables (the callers
+// fill them: sdpcut_set_candidates from host arrays, the Philox generator and the cover
+// enumeration on the device).  Frees the previous list; sizes the ranking workspace.
+int alloc_candidates(sdpcut_ctx *h, int64_t N, const int64_t cnt[SDPCUT_MAX_K + 1], int64_t global_base)
+{
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, sdpcut_sync(h));
+    free_candidates(h);
+    h->base = global_base;
+    const size_t nn = (size_t)(N < 1 ? 1 : N);
+    HIP_TRY(h, hipMalloc((void **)&h->d_set_orig, nn * 5 * sizeof(int32_t)));
+    HIP_TRY(h, hipMalloc((void **)&h->d_k, nn * sizeof(int32_t)));
+    HIP_TRY(h, hipMalloc((void **)&h->d_eig, nn * sizeof(double)));
+    HIP_TRY(h, hipMalloc((void **)&h->d_obj, nn * sizeof(double)));
+    h->row_len_max = 5;
+    for (int k = 2; k <= SDPCUT_MAX_K; ++k) {
+        Bucket &b = h->bucket[k];
+        b.n = cnt[k];
+        if (!cnt[k]) continue;
+        h->row_len_max = k * (k + 3) / 2;
+        HIP_TRY(h, hipMalloc((void **)&b.d_set, (size_t)cnt[k] * k * sizeof(int32_t)));
+        HIP_TRY(h, hipMalloc((void **)&b.d_orig, (size_t)cnt[k] * sizeof(int32_t)));
+    }
+    h->N = N;
+    return 0;      // (the ranking workspaces are allocated by whoever first needs them: ensure_key_ws / ensure_rank_ws)
+}
+
+void free_candidates(sdpcut_ctx *h)
+{
+    for (int k = 0; k <= SDPCUT_MAX_K; ++k) {
+        hipFree(h->bucket[k].d_set);
+        hipFree(h->bucket[k].d_orig);
+        h->bucket[k] = Bucket();
+    }
+    hipFree(h->d_set_orig); hipFree(h->d_k); hipFree(h->d_eig); hipFree(h->d_obj);
+    h->d_set_orig = nullptr; h->d_k = nullptr; h->d_eig = nullptr; h->d_obj = nullptr;
+    h->N = 0; h->scored = 0; h->last_total = -1;
+    h->topk_alt_clean = false;      // (how much of the selection workspace a round's epilogue zeroes depends on the list's length)
+    h->side_choice = -1;      // (a new list measures for itself whether its small size classes go to side streams)
+}
+
+extern "C" {
+
+int sdpcut_set_network(sdpcut_handle h, int k, int n_layers, const int32_t *widths, const double *params,
+                       int64_t n_params)
+{
+    if (!h) return SDPCUT_EINVAL;
+    SDPCUT_NO_PENDING(h);
+    NetPack pk;
+    const char *why = nullptr;
+    if (net_pack(k, n_layers, widths, params, n_params, &pk, &why) != SDPCUT_OK) return sdpcut_fail(h, SDPCUT_EINVAL, why);
+    HIP_TRY(h, hipSetDevice(h->device));
+    NetHost &nh_ = h->net[k];
+    HIP_TRY(h, sdpcut_sync(h));
+    hipFree(nh_.d_blob);
+    nh_.d_blob = nullptr;
+    nh_.set = false;
+    HIP_TRY(h, hipMalloc((void **)&nh_.d_blob, pk.blob.size() * sizeof(double)));
+    HIP_TRY(h, hipMemcpy(nh_.d_blob, pk.blob.data(), pk.blob.size() * sizeof(double), hipMemcpyHostToDevice));
+    NetDev &d = nh_.dev;
+    d = NetDev{};
+    d.d_in = pk.d_in; d.n_hidden = pk.n_hidden; d.width = pk.width; d.s0 = pk.s0; d.sh = pk.sh;
+    d.inmap = nh_.d_blob + pk.o_inmap;
+    d.bias = nh_.d_blob + pk.o_bias;
+    d.bias_q = nh_.d_blob + pk.o_bias_q;
+    d.wout = nh_.d_blob + pk.o_wout;
+    d.wfrag = nh_.d_blob + pk.o_frag;
+    d.wvalu = nh_.d_blob + pk.o_wvalu;
+    d.wtail = nh_.d_blob + pk.o_wtail;
+    for (int l = 0; l < n_layers; ++l) { d.raw_w[l] = nh_.d_blob + pk.o_rw[l]; d.raw_b[l] = nh_.d_blob + pk.o_rb[l]; }
+    d.ymin = pk.ymin; d.b_out = pk.b_out; d.y_ymin = pk.y_ymin; d.y_gain = pk.y_gain; d.y_xoffset = pk.y_xoffset;
+    d.unclamped_ok = pk.unclamped_ok;
+    nh_.set = true;
+    return SDPCUT_OK;
+}
+int sdpcut_set_instance(sdpcut_handle h, int32_t nb_vars, const double *Q_arr)
+{
+    if (!h) return SDPCUT_EINVAL;
+    SDPCUT_NO_PENDING(h);
+    if (nb_vars < 2 || nb_vars > 40000 || !Q_arr) return sdpcut_fail(h, SDPCUT_EINVAL, "bad instance");
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, sdpcut_sync(h));
+    const int64_t L = (int64_t)nb_vars * (nb_vars + 1) / 2;
+    hipFree(h->d_Q); hipFree(h->d_vars);
+    h->d_Q = nullptr; h->d_vars = nullptr; h->have_point = false; h->scored = 0;
+    HIP_TRY(h, hipMalloc((void **)&h->d_Q, L * sizeof(double)));
+    HIP_TRY(h, hipMalloc((void **)&h->d_vars, (L + nb_vars) * sizeof(double)));
+    HIP_TRY(h, hipMemcpy(h->d_Q, Q_arr, L * sizeof(double), hipMemcpyHostToDevice));
+    h->nb_vars = nb_vars;
+    h->L = L;
+    return SDPCUT_OK;
+}
+
+int sdpcut_set_candidates(sdpcut_handle h, int64_t N, const int32_t *set_inds, int32_t ld, const int32_t *ks,
+                          int64_t global_base)
+{
+    if (!h) return SDPCUT_EINVAL;
+    SDPCUT_NO_PENDING(h);
+    if (h->nb_vars == 0) return sdpcut_fail(h, SDPCUT_ESTATE, "set_instance first");
+    if (N < 0 || N > 0x7fffffffLL || (N > 0 && (!set_inds || !ks)) || ld < 2)
+        return sdpcut_fail(h, SDPCUT_EINVAL, "bad candidate list");
+    HIP_TRY(h, hipSetDevice(h->device));
+    // validate + bucket by size on the host (once per instance)
+    int64_t cnt[SDPCUT_MAX_K + 1] = {0, 0, 0, 0, 0, 0};
+    for (int64_t i = 0; i < N; ++i) {
+        const int k = ks[i];
+        if (k < 2 || k > SDPCUT_MAX_K || k > ld) return sdpcut_fail(h, SDPCUT_EINVAL, "candidate size must be 2..5");
+        for (int a = 0; a < k; ++a) {
+            const int32_t v = set_inds[i * ld + a];
+            if (v < 0 || v >= h->nb_vars) return sdpcut_fail(h, SDPCUT_EINVAL, "variable index out of range");
+        }
+        ++cnt[k];
+    }
+    std::vector<int32_t> pad((size_t)N * 5, -1), kk((size_t)N);
+    std::vector<int32_t> soa[SDPCUT_MAX_K + 1], orig[SDPCUT_MAX_K + 1];
+    int64_t fill[SDPCUT_MAX_K + 1] = {0, 0, 0, 0, 0, 0};
+    for (int k = 2; k <= SDPCUT_MAX_K; ++k) { soa[k].resize((size_t)cnt[k] * k); orig[k].resize((size_t)cnt[k]); }
+    for (int64_t i = 0; i < N; ++i) {
+        const int k = ks[i];
+        kk[i] = k;
+        const int64_t p = fill[k]++;
+        orig[k][p] = (int32_t)i;
+        for (int a = 0; a < k; ++a) {
+            const int32_t v = set_inds[i * ld + a];
+            pad[i * 5 + a] = v;
+            soa[k][(size_t)a * cnt[k] + p] = v;
+        }
+    }
+    int rc = alloc_candidates(h, N, cnt, global_base);
+    if (rc) return rc;
+    if (N > 0) {
+        HIP_TRY(h, hipMemcpy(h->d_set_orig, pad.data(), (size_t)N * 5 * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIP_TRY(h, hipMemcpy(h->d_k, kk.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    for (int k = 2; k <= SDPCUT_MAX_K; ++k) {
+        Bucket &b = h->bucket[k];
+        if (!cnt[k]) continue;
+        HIP_TRY(h, hipMemcpy(b.d_set, soa[k].data(), soa[k].size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIP_TRY(h, hipMemcpy(b.d_orig, orig[k].data(), orig[k].size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    return SDPCUT_OK;
+}
+
+static int ensure_point_stage(sdpcut_ctx *h)
+{
+    const size_t bytes = (size_t)(h->L + h->nb_vars) * sizeof(double);
+    if (h->point_stage_bytes >= bytes) return 0;
+    HIP_TRY(h, sdpcut_sync(h));
+    if (h->point_stage) (void)hipHostFree(h->point_stage);
+    h->point_stage = nullptr;
+    h->point_stage_bytes = 0;
+    HIP_TRY(h, hipHostMalloc(&h->point_stage, bytes, hipHostMallocMapped));
+    HIP_TRY(h, hipHostGetDevicePointer(&h->point_stage_dev, h->point_stage, 0));
+    h->point_stage_bytes = bytes;
+    return 0;
+}
+
+int sdpcut_point_buffer(sdpcut_handle h, double **buf)
+{
+    if (!h) return SDPCUT_EINVAL;
+    if (!buf) return sdpcut_fail(h, SDPCUT_EINVAL, "buf is NULL");
+    if (!h->d_vars) return sdpcut_fail(h, SDPCUT_ESTATE, "set_instance first");
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = ensure_point_stage(h);
+    if (rc) return rc;
+    *buf = (double *)h->point_stage;
+    return SDPCUT_OK;
+}
+
+int sdpcut_set_point(sdpcut_handle h, const double *vars_values)
+{
+    if (!h) return SDPCUT_EINVAL;
+    SDPCUT_NO_PENDING(h);
+    if (!h->d_vars) return sdpcut_fail(h, SDPCUT_ESTATE, "set_instance first");
+    if (!vars_values) return sdpcut_fail(h, SDPCUT_EINVAL, "vars_values is NULL");
+    HIP_TRY(h, hipSetDevice(h->device));
+    // The caller's (pageable) buffer is copied into a pinned staging block and sent from there: the
+    // call returns as soon as the host copy is done -- the caller may reuse its buffer at once -- and
+    // the DMA runs behind it on the stream, in front of the score kernels (no blocking round trip
+    // per round).  The staging block is reused once the previous transfer out of it has completed.
+    // A caller that wrote the point straight into the staging block (sdpcut_point_buffer) skips the copy.
+    const size_t bytes = (size_t)(h->L + h->nb_vars) * sizeof(double);
+    int rc = ensure_point_stage(h);
+    if (rc) return rc;
+    if (vars_values != (const double *)h->point_stage) {
+        // (every round ends in a host wait on the device, so this one is normally skipped; an event per
+        // transfer would put a barrier packet -- ~10 us -- in front of every score launch)
+        if (h->point_inflight) HIP_TRY(h, sdpcut_sync(h));
+        std::memcpy(h->point_stage, vars_values, bytes);
+    }
+    // a kernel of the compute queue pulls the block over PCIe (mapped host memory): the score launch
+    // follows it in queue order, whereas a copy-engine transfer costs a cross-queue hand-off (~10 us)
+    // in front of every round
+    rc = launch_point_copy(h, (const double *)h->point_stage_dev, h->L + h->nb_vars);
+    if (rc) return rc;
+    h->point_inflight = true;
+    h->have_point = true;
+    h->scored = 0;
+    h->last_total = -1;
+    return SDPCUT_OK;
+}
+
+int sdpcut_set_point_device(sdpcut_handle h, const void *d_vars_values)
+{
+    if (!h) return SDPCUT_EINVAL;
+    SDPCUT_NO_PENDING(h);
+    if (!h->d_vars) return sdpcut_fail(h, SDPCUT_ESTATE, "set_instance first");
+    if (!d_vars_values) return sdpcut_fail(h, SDPCUT_EINVAL, "d_vars_values is NULL");
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipMemcpyAsync(h->d_vars, d_vars_values, (h->L + h->nb_vars) * sizeof(double),
+                              hipMemcpyDeviceToDevice, h->stream));
+    h->have_point = true;
+    h->scored = 0;
+    h->last_total = -1;
+    return SDPCUT_OK;
+}
+
+} // extern "C"

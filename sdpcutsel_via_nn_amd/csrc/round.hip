@@ -1,0 +1,352 @@
+// The fused round (include/sdpcut.h: sdpcut_select_round*, sdpcut_round_view, sdpcut_round_csr*): score -> rank -> rows in one
+// enqueue, one host wait.
+#include <cstring>
+
+#include "common.h"
+#include "topk_route.h"
+
+// Host wait for the serial number the last workgroup of a round's epilogue stores (system scope, after
+// its results) into pinned memory.  Bounded: after ~2 s without the word the stream is synchronised
+// the ordinary way, which also surfaces a faulted kernel as an error.
+int wait_round_done(sdpcut_ctx *h, const int64_t *word, int64_t serial)
+{
+    const volatile int64_t *w = (const volatile int64_t *)word;
+    for (long spin = 0; spin < 400000000L; ++spin) {
+        if (*w == serial) {
+            __atomic_thread_fence(__ATOMIC_ACQUIRE);
+            h->point_inflight = false;      // the round ran behind the point's transfer
+            return 0;
+        }
+        __builtin_ia32_pause();
+        if ((spin & 0xfffff) == 0xfffff && hipStreamQuery(h->stream) != hipErrorNotReady) break;
+    }
+    HIP_TRY(h, sdpcut_sync(h));
+    if (*w != serial) return sdpcut_fail(h, SDPCUT_EHIP, "round epilogue did not report completion");
+    return 0;
+}
+
+// Scores of a round's selection (strategy strat, head of `cap` entries), not computed yet at this point:
+// *stage / *auto_out are what topk_select_enqueue / rank_fast_enqueue take.
+// If nothing has been scored at the point and the head comes from the radix select, the score kernels work
+// for the selection that follows.  Combined strategy (allow_auto): they count the strong candidates into
+// its workspace and the selection resolves its regime on the device (at least sel_size strong ones:
+// those, + BIG_M; fewer: every entry visited) -- one selection and no host round trip in either regime.
+// SDPCUT_OPT_FUSE_KEYS: they also count the class members by the leading digit of the selection keys, so
+// that the selection starts at its second digit and needs no key pass (the every-entry-visited regime of
+// the combined strategy runs its own first digit inside the selection).
+int score_for_selection(sdpcut_ctx *h, int strat, int64_t sel_size, int64_t cap, uint32_t need, bool allow_auto, int *stage,
+                        bool *auto_out)
+{
+    *stage = 0;
+    *auto_out = false;
+    int rc;
+    const int fast_mode = (h->scored & need) == 0 ? rank_fast_mode(h, strat, sel_size, cap, nullptr) : 0;
+    const bool want_auto = allow_auto && strat == SDPCUT_STRAT_COMB;
+    // (the short-list predicate must be the one topk_select_enqueue will evaluate: it sees the tie-aware combined modes only when
+    // the regime is resolved on the device -- a combined round whose mode the HOST resolved runs as TK_MODE_STRONG)
+    const bool count_digit = h->fuse_keys && topk_fuse_ok(h, cap, want_auto);
+    if (fast_mode && (want_auto || count_digit)) {
+        void *ws = nullptr;
+        rc = topk_begin(h, &ws, nullptr);
+        if (rc) return rc;
+        int64_t *strong = (need == (SDPCUT_EIG | SDPCUT_NN)) ? topk_strong_counter(ws) : nullptr;
+        bool counted = false;
+        if (count_digit) {
+            ScoreFuse fuse;
+            fuse.ws = ws;
+            fuse.mode = fast_mode;
+            fuse.k = (h->prefilter && h->N >= SDPCUT_PF_MIN_N) ? cap : 0;
+            rc = launch_score(h, need, &fuse, &counted, strong);
+        } else {
+            rc = launch_score(h, need, nullptr, nullptr, strong);
+        }
+        if (rc) return rc;
+        h->scored |= need;
+        *stage = counted ? 3 : 1;
+        *auto_out = want_auto;
+    } else if ((h->scored & need) != need) {
+        rc = sdpcut_score(h, need & ~h->scored);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+// One fused round in two halves: round_begin enqueues everything -- score (if needed) -> rank -> epilogue into the pinned block --
+// WITHOUT waiting; round_end waits, reads the counters and, when the enqueued selection is not the answer (a void one; the
+// combined scan of heads > 8192), runs the general path.  csr = false: padded rows, block layout of sdpcut_select_round_view
+// (rows_layout behind 64 bytes; the staging area mirrors it); csr = true: the CSR block of sdpcut_round_csr (csr_layout).
+// Two handles may both begin before either ends: their device work overlaps (the QCQP round's two covers).
+static int round_begin(sdpcut_ctx *h, int strat, int64_t sel_size, int32_t coef_ld, bool csr)
+{
+    int rc = check_round_strategy(h, strat);
+    if (rc) return rc;
+    if (sel_size < 0) return sdpcut_fail(h, SDPCUT_EINVAL, "bad select_round arguments");
+    if (!h->have_point || !h->d_eig) return sdpcut_fail(h, SDPCUT_ESTATE, "set_candidates and set_point first");
+    if (coef_ld < h->row_len_max || coef_ld > SDPCUT_ROW_LD)
+        return sdpcut_fail(h, SDPCUT_EINVAL, "coef_ld must hold the longest row (k + k(k+1)/2) and be <= SDPCUT_ROW_LD");
+    SDPCUT_NO_PENDING(h);        // a fused round begun, or a sharded round enqueued and not waited for
+    HIP_TRY(h, hipSetDevice(h->device));
+    int64_t cap = sel_size < h->N ? sel_size : h->N;
+    int stage = 0;               // how far the selection's first pass has got (topk_select_enqueue)
+    bool auto_regime = false;
+    rc = score_for_selection(h, strat, sel_size, cap, strat_need(strat), h->auto_regime, &stage, &auto_regime);
+    if (rc) return rc;
+    PendingRound &P = h->pend;
+    P = PendingRound();
+    P.strat = strat; P.sel_size = sel_size; P.cap = cap; P.ld = coef_ld; P.csr = csr;
+    if (cap == 0) {   // nothing to generate; round_end still reports the ranking's length / strategy switch
+        P.active = true;
+        return SDPCUT_OK;
+    }
+    // one block for everything a round returns: counters | idx | score | lam | rhs | coef | ks
+    const RowsLayout y = rows_layout(64, cap, coef_ld);
+    rc = ensure_stage(h, y.bytes + 64);
+    if (rc) return rc;
+    rc = ensure_pinned(h, csr ? csr_layout(cap, coef_ld).bytes : y.bytes);
+    if (rc) return rc;
+    int64_t *d_idx = (int64_t *)((char *)h->d_stage + y.idx);
+    double *d_sc = (double *)((char *)h->d_stage + y.score);
+    if (h->timing > 1) HIP_TRY(h, hipEventRecord(h->ev[2], h->stream));
+    int64_t *hdr = (int64_t *)h->pinned;
+    if (csr) hdr[8] = hdr[9] = hdr[10] = 0;
+    // fast path: selection and rows are enqueued back to back; the epilogue kernel stores the
+    // results directly into the pinned host block (no copy engine); one synchronisation
+    const int64_t *d_cnt = nullptr;
+    rc = rank_fast_enqueue(h, strat, sel_size, cap, d_idx, d_sc, &d_cnt, stage, auto_regime);
+    if (rc < 0) return rc;
+    P.fast_tried = rc == 1;
+    if (P.fast_tried) {
+        if (h->timing > 1) HIP_TRY(h, hipEventRecord(h->ev[3], h->stream));
+        // the epilogue's last workgroup publishes this round's serial number in the block's header: the
+        // host polls that word instead of waiting for the runtime's completion signal (~5 us earlier)
+        P.serial = ++h->round_serial;
+        rc = csr ? launch_round_csr(h, cap, d_cnt, cap, d_idx, d_sc, coef_ld, h->pinned_dev, P.serial)
+                 : launch_round_rows(h, cap, d_cnt, d_idx, d_sc, coef_ld, h->pinned_dev, 64, P.serial);
+        if (rc) return rc;
+    }
+    P.active = true;
+    return SDPCUT_OK;
+}
+
+// CSR assembly of the first w entries of a head the host produced (ids and scores in the staging area), under a fresh serial
+// number, and the wait for it.  hdr[10] tells the caller whether the assembly gave up.
+static int csr_launch_wait(sdpcut_ctx *h, const PendingRound &P, int64_t w, const int64_t *d_idx, const double *d_sc)
+{
+    int64_t *hdr = (int64_t *)h->pinned;
+    hdr[8] = hdr[9] = hdr[10] = 0;
+    const int64_t serial = ++h->round_serial;
+    int rc = launch_round_csr(h, P.cap, nullptr, w, d_idx, d_sc, P.ld, h->pinned_dev, serial);
+    if (rc) return rc;
+    return wait_round_done(h, hdr + 7, serial);
+}
+
+// round_csr_kernel's look-back over lower-indexed workgroups is bounded (CSR_SPIN_LIMIT): on a device shared with a kernel that
+// blocks it for long it gives up and sets hdr[10].  That is a transient condition, not an error of the round: by the time the
+// host sees the mark every workgroup of that launch has retired, so ONE more launch over the same head (ids and scores still
+// in the staging area) finds its predecessors' aggregates as soon as they are dispatched.  Counted like the selection's
+// fallbacks; only a second give-up fails the call.
+static int csr_again(sdpcut_ctx *h, const PendingRound &P, int64_t w, const int64_t *d_idx, const double *d_sc)
+{
+    ++h->stat_fallbacks;
+    int rc = csr_launch_wait(h, P, w, d_idx, d_sc);
+    if (rc) return rc;
+    if (((const int64_t *)h->pinned)[10]) return sdpcut_fail(h, SDPCUT_EHIP, "round_csr: look-back of the row assembly timed out twice");
+    return SDPCUT_OK;
+}
+
+// Rows of the first w entries of a head the host just produced (after the enqueued epilogue ran), into the pinned block.
+// CSR: the assembly kernel once more (and once again if it gives up); padded: cut rows into the staging area, which
+// mirrors the pinned block, and one copy.  csr_if_empty: whether a head of no entries still runs the CSR assembly.
+static int emit_head(sdpcut_ctx *h, const PendingRound &P, int64_t w, bool csr_if_empty)
+{
+    const RowsLayout y = rows_layout(64, P.cap, P.ld);
+    char *st = (char *)h->d_stage;
+    const int64_t *d_idx = (const int64_t *)(st + y.idx);
+    int rc;
+    if (P.csr) {
+        if (w <= 0 && !csr_if_empty) return 0;
+        const double *d_sc = (const double *)(st + y.score);
+        rc = csr_launch_wait(h, P, w, d_idx, d_sc);
+        if (rc) return rc;
+        return ((const int64_t *)h->pinned)[10] ? csr_again(h, P, w, d_idx, d_sc) : 0;
+    }
+    if (w <= 0) return 0;
+    rc = launch_cut_rows(h, w, nullptr, d_idx, h->base, (double *)(st + y.lam), (double *)(st + y.coef), P.ld, (double *)(st + y.rhs),
+                         nullptr, (int32_t *)(st + y.ks));
+    if (rc) return rc;
+    HIP_TRY(h, hipMemcpyAsync(h->pinned, h->d_stage, y.bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, sdpcut_sync(h));
+    return 0;
+}
+
+static int round_end(sdpcut_ctx *h, const void **block, int64_t *cap_out, int64_t *n_out, int64_t *n_total, int32_t *new_strat,
+                     int64_t *counters)
+{
+    if (!block || !cap_out || !n_out) return sdpcut_fail(h, SDPCUT_EINVAL, "bad select_round arguments");
+    if (!h->pend.active) return sdpcut_fail(h, SDPCUT_ESTATE, "no round pending on this handle");
+    const PendingRound P = h->pend;
+    h->pend.active = false;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int strat = P.strat;
+    const int64_t sel_size = P.sel_size, cap = P.cap;
+    *n_out = 0;
+    *cap_out = cap;
+    *block = nullptr;
+    if (cap == 0) return sdpcut_rank(h, strat, sel_size, 0, nullptr, nullptr, n_total, new_strat, counters);
+    const RowsLayout y = rows_layout(64, cap, P.ld);
+    int64_t *d_idx = (int64_t *)((char *)h->d_stage + y.idx);
+    double *d_sc = (double *)((char *)h->d_stage + y.score);
+    int64_t *hdr = (int64_t *)h->pinned;
+    int rc;
+    int64_t w = 0;
+    bool have = false;
+    if (P.fast_tried) {
+        rc = wait_round_done(h, hdr + 7, P.serial);
+        if (rc) return rc;
+        have = rank_fast_finish(h, strat, sel_size, cap, (const int64_t *)h->pinned, &w, n_total, new_strat, counters) != 0;
+        if (have && P.csr && hdr[10] && w > 0) {      // the row assembly gave up its look-back (rows.hip): once more, see csr_again
+            rc = csr_again(h, P, w, d_idx, d_sc);
+            if (rc) return rc;
+        }
+    }
+    ++h->stat_rounds;
+    bool resorted = false;      // the head in d_idx / d_sc was produced after the enqueued epilogue ran: launch it again
+    if (P.fast_tried && !have && strat == SDPCUT_STRAT_COMB && hdr[4] == 2 && hdr[6] == TK_MODE_COMBALL) {
+        // the threshold tie group of the every-entry-visited ranking does not fit the sort buffers (a structured LP vertex):
+        // cut it by its secondary key with two more selections (topk.hip: topk_tie_split) instead of sorting the full list
+        int64_t c7[7];
+        for (int i = 0; i < 7; ++i) c7[i] = hdr[i];
+        rc = topk_tie_split(h, cap, d_idx, d_sc, nullptr);
+        if (rc < 0) return rc;
+        if (rc == 0) {
+            c7[4] = 0;
+            have = rank_fast_finish(h, strat, sel_size, cap, c7, &w, n_total, new_strat, counters) != 0;
+            resorted = have;
+        }
+    }
+    if (P.fast_tried && !have && hdr[4]) ++h->stat_fallbacks;
+    if (resorted) {
+        if (h->timing > 1) HIP_TRY(h, hipEventRecord(h->ev[3], h->stream));
+        rc = emit_head(h, P, w, true);       // (the CSR assembly runs here whatever w is)
+        if (rc) return rc;
+    }
+    if (!have) {
+        // general path (full sorts; the combined scan visiting every entry, or heads > 8192)
+        // (the fast attempt above already counted the strong candidates: no second attempt)
+        const int64_t *c5 = (const int64_t *)h->pinned;
+        const int64_t hint = (P.fast_tried && strat == SDPCUT_STRAT_COMB && !c5[4]) ? c5[0] : -1;
+        rc = rank_on_device(h, strat, sel_size, cap, d_idx, d_sc, &w, n_total, new_strat, counters, hint);
+        if (rc) return rc;
+        if (h->timing > 1) HIP_TRY(h, hipEventRecord(h->ev[3], h->stream));
+        rc = emit_head(h, P, w, false);
+        if (rc) return rc;
+    }
+    *n_out = w;
+    *block = h->pinned;
+    return SDPCUT_OK;
+}
+
+static int round_impl(sdpcut_ctx *h, int strat, int64_t sel_size, int32_t coef_ld, bool csr, const void **block,
+                      int64_t *cap_out, int64_t *n_out, int64_t *n_total, int32_t *new_strat, int64_t *counters)
+{
+    if (!block || !cap_out || !n_out) return sdpcut_fail(h, SDPCUT_EINVAL, "bad select_round arguments");
+    int rc = round_begin(h, strat, sel_size, coef_ld, csr);
+    if (rc) return rc;
+    return round_end(h, block, cap_out, n_out, n_total, new_strat, counters);
+}
+
+static int fill_csr_out(sdpcut_ctx *h, const void *block, sdpcut_round_csr_t *out)
+{
+    if (!block || out->cap == 0) return SDPCUT_OK;
+    const CsrLayout y = csr_layout(out->cap, out->row_ld);
+    const char *b = (const char *)block;
+    const int64_t *hdr = (const int64_t *)b;
+    out->idx = (const int64_t *)(b + y.idx);
+    out->score = (const double *)(b + y.score);
+    out->lam_min = (const double *)(b + y.lam);
+    out->ks = (const int32_t *)(b + y.ks);
+    out->set_inds = (const int32_t *)(b + y.sets);
+    out->n_rows = out->n_out > 0 ? hdr[8] : 0;
+    out->nnz = out->n_out > 0 ? hdr[9] : 0;
+    out->row_entry = (const int32_t *)(b + y.row_entry);
+    out->indptr = (const int32_t *)(b + y.indptr);
+    out->indices = (const int32_t *)(b + y.indices);
+    out->values = (const double *)(b + y.values);
+    out->rhs = (const double *)(b + y.rhs);
+    return SDPCUT_OK;
+}
+
+extern "C" {
+
+int sdpcut_select_round_view(sdpcut_handle h, int strat, int64_t sel_size, int32_t coef_ld, const void **block,
+                             int64_t *cap_out, int64_t *n_out, int64_t *n_total, int32_t *new_strat, int64_t *counters)
+{
+    if (!h) return SDPCUT_EINVAL;
+    return round_impl(h, strat, sel_size, coef_ld, false, block, cap_out, n_out, n_total, new_strat, counters);
+}
+
+int sdpcut_round_csr_begin(sdpcut_handle h, const double *vars_values, int strat, int64_t sel_size)
+{
+    if (!h) return SDPCUT_EINVAL;
+    int rc;
+    if (vars_values && (rc = sdpcut_set_point(h, vars_values))) return rc;
+    return round_begin(h, strat, sel_size, h->row_len_max, true);
+}
+
+int sdpcut_round_csr_end(sdpcut_handle h, sdpcut_round_csr_t *out)
+{
+    if (!h) return SDPCUT_EINVAL;
+    if (!out) return sdpcut_fail(h, SDPCUT_EINVAL, "out is NULL");
+    std::memset(out, 0, sizeof(*out));
+    if (!h->pend.active || !h->pend.csr) return sdpcut_fail(h, SDPCUT_ESTATE, "no sdpcut_round_csr_begin pending on this handle");
+    const void *block = nullptr;
+    out->row_ld = h->pend.ld;
+    int rc = round_end(h, &block, &out->cap, &out->n_out, &out->n_total, &out->new_strat, out->counters);
+    if (rc) return rc;
+    return fill_csr_out(h, block, out);
+}
+
+int sdpcut_round_csr(sdpcut_handle h, const double *vars_values, int strat, int64_t sel_size, sdpcut_round_csr_t *out)
+{
+    if (!h) return SDPCUT_EINVAL;
+    if (!out) return sdpcut_fail(h, SDPCUT_EINVAL, "out is NULL");
+    int rc = sdpcut_round_csr_begin(h, vars_values, strat, sel_size);
+    if (rc) { std::memset(out, 0, sizeof(*out)); return rc; }
+    return sdpcut_round_csr_end(h, out);
+}
+
+int sdpcut_round_view(sdpcut_handle h, const double *vars_values, int strat, int64_t sel_size, int32_t coef_ld,
+                      const void **block, int64_t *cap_out, int64_t *n_out, int64_t *n_total, int32_t *new_strat,
+                      int64_t *counters)
+{
+    int rc = sdpcut_set_point(h, vars_values);
+    if (rc) return rc;
+    return sdpcut_select_round_view(h, strat, sel_size, coef_ld, block, cap_out, n_out, n_total, new_strat, counters);
+}
+
+int sdpcut_select_round(sdpcut_handle h, int strat, int64_t sel_size, int32_t coef_ld, int64_t *idx_out,
+                        double *score_out, double *lam_min, double *coef, double *rhs, int32_t *ks, int64_t *n_out,
+                        int64_t *n_total, int32_t *new_strat, int64_t *counters)
+{
+    if (!h) return SDPCUT_EINVAL;
+    if (sel_size < 0 || (sel_size > 0 && (!idx_out || !score_out || !lam_min || !coef || !rhs || !ks)) || !n_out)
+        return sdpcut_fail(h, SDPCUT_EINVAL, "bad select_round arguments");
+    const void *block = nullptr;
+    int64_t cap = 0;
+    int rc = sdpcut_select_round_view(h, strat, sel_size, coef_ld, &block, &cap, n_out, n_total, new_strat, counters);
+    if (rc) return rc;
+    if (*n_out > 0) {
+        const size_t ww = (size_t)*n_out;
+        const RowsLayout y = rows_layout(64, cap, coef_ld);
+        const char *q = (const char *)block;
+        std::memcpy(idx_out, q + y.idx, ww * 8);
+        std::memcpy(score_out, q + y.score, ww * 8);
+        std::memcpy(lam_min, q + y.lam, ww * 8);
+        std::memcpy(rhs, q + y.rhs, ww * 8);
+        std::memcpy(coef, q + y.coef, ww * 8 * (size_t)coef_ld);
+        std::memcpy(ks, q + y.ks, ww * 4);
+    }
+    return SDPCUT_OK;
+}
+
+} // extern "C"

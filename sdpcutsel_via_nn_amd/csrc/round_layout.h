@@ -1,0 +1,48 @@
+// Byte layouts of the blocks a round returns (include/sdpcut.h documents them for the caller).  Plain C++:
+// tests/test_round_layout.py compiles this header with the host compiler.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+// Padded rows behind a header of hdr_bytes:  idx | score | lam | rhs | coef[entries][ld] | ks [| int32 pos[entries]]
+// (sdpcut_select_round_view: hdr_bytes = 64; sdpcut_shard_finish_wait: world headers of 64 bytes, pos in the compacted form).
+// No alignment padding anywhere; `bytes` ends behind ks, `bytes_pos` behind pos.
+struct RowsLayout { size_t idx, score, lam, rhs, coef, ks, pos, bytes, bytes_pos; };
+static inline RowsLayout rows_layout(size_t hdr_bytes, int64_t entries, int ld)
+{
+    RowsLayout y;
+    const size_t c = (size_t)entries;
+    size_t o = hdr_bytes;
+    y.idx = o; o += c * 8;
+    y.score = o; o += c * 8;
+    y.lam = o; o += c * 8;
+    y.rhs = o; o += c * 8;
+    y.coef = o; o += c * (size_t)ld * 8;
+    y.ks = o; o += c * 4;
+    y.pos = y.bytes = o;
+    y.bytes_pos = o + c * 4;
+    return y;
+}
+
+// Layout of the CSR round block for `cap` head entries and rows of at most `ld` non-zeros (offsets in bytes,
+// every array 8-byte aligned); the same arithmetic on the host (sdpcut_round_csr) and for the kernel's pointers.
+struct CsrLayout { size_t idx, score, lam, rhs, values, ks, sets, row_entry, indptr, indices, bytes; };
+static inline CsrLayout csr_layout(int64_t cap, int ld)
+{
+    CsrLayout y;
+    const size_t c = (size_t)cap;
+    auto al = [](size_t v) { return (v + 7) & ~(size_t)7; };
+    size_t o = 128;
+    y.idx = o; o += c * 8;
+    y.score = o; o += c * 8;
+    y.lam = o; o += c * 8;
+    y.rhs = o; o += c * 8;
+    y.values = o; o += c * (size_t)ld * 8;
+    y.ks = o; o = al(o + c * 4);
+    y.sets = o; o = al(o + c * 20);
+    y.row_entry = o; o = al(o + c * 4);
+    y.indptr = o; o = al(o + (c + 1) * 4);
+    y.indices = o; o = al(o + c * (size_t)ld * 4);
+    y.bytes = o;
+    return y;
+}

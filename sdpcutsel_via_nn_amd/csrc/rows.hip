@@ -368,7 +368,7 @@ __global__ __launch_bounds__(64) void round_csr_kernel(RoundCsrArgs R)
         pre_nnz += __shfl_xor(pre_nnz, off);
         gave_up |= __shfl_xor(gave_up, off);
     }
-    if (gave_up && lane == 0) R.o_hdr[10] = 1;      // the block is void; the host launches the assembly once more (capi.hip: csr_again)
+    if (gave_up && lane == 0) R.o_hdr[10] = 1;      // the block is void; the host launches the assembly once more (round.hip: emit_csr)
     if (keep) {
         const int64_t r = pre_rows + my_row;
         R.o_row_entry[r] = (int32_t)i;
@@ -451,28 +451,6 @@ int launch_round_rows(sdpcut_ctx *h, int64_t cap, const int64_t *d_c4, const int
     return 0;
 }
 
-
-// Layout of the CSR round block for `cap` head entries and rows of at most `ld` non-zeros (offsets in bytes,
-// every array 8-byte aligned); the same arithmetic on the host (sdpcut_round_csr) and for the kernel's pointers.
-CsrLayout csr_layout(int64_t cap, int ld)
-{
-    CsrLayout y;
-    const size_t c = (size_t)cap;
-    auto al = [](size_t v) { return (v + 7) & ~(size_t)7; };
-    size_t o = 128;
-    y.idx = o; o += c * 8;
-    y.score = o; o += c * 8;
-    y.lam = o; o += c * 8;
-    y.rhs = o; o += c * 8;
-    y.values = o; o += c * (size_t)ld * 8;
-    y.ks = o; o = al(o + c * 4);
-    y.sets = o; o = al(o + c * 20);
-    y.row_entry = o; o = al(o + c * 4);
-    y.indptr = o; o = al(o + (c + 1) * 4);
-    y.indices = o; o = al(o + c * (size_t)ld * 4);
-    y.bytes = o;
-    return y;
-}
 
 int launch_round_csr(sdpcut_ctx *h, int64_t cap, const int64_t *d_c4, int64_t limit, const int64_t *d_idx, const double *d_score,
                      int ld, void *block, int64_t serial)

@@ -99,8 +99,7 @@ extern "C" int sdpcut_shard_head_device(sdpcut_handle h, int strat, int64_t coun
     const bool comball = strat == SDPCUT_PART_COMBALL;
     if (strat != SDPCUT_STRAT_FEAS && strat != SDPCUT_STRAT_OPT && strat != SDPCUT_PART_STRONG && !comball)
         return sdpcut_fail(h, SDPCUT_EINVAL, "shard head: strategy must be 1, 2, SDPCUT_PART_STRONG or SDPCUT_PART_COMBALL");
-    const uint32_t need = strat == SDPCUT_STRAT_FEAS ? SDPCUT_EIG
-                          : strat == SDPCUT_STRAT_OPT ? SDPCUT_NN : (SDPCUT_EIG | SDPCUT_NN);
+    const uint32_t need = strat_need(strat);
     if (h->N > 0 && (!h->have_point || !h->d_eig)) return sdpcut_fail(h, SDPCUT_ESTATE, "set_candidates and set_point first");
     HIP_TRY(h, hipSetDevice(h->device));
     // Not scored at this point yet: the call scores the shard itself, and the score kernels count the leading
@@ -166,10 +165,9 @@ extern "C" int sdpcut_shard_finish_enqueue(sdpcut_handle h, int32_t world, int64
     const size_t tot = (size_t)world * count, s = (size_t)sel_size;
     // pinned host block, written by the device: headers | ids | scores | lam | rhs | coef | ks
     const size_t hdr_b = (size_t)world * SHARD_HDR * 8;
-    const size_t ret_bytes = hdr_b + s * 8 * (4 + (size_t)coef_ld) + s * 4;
     int rc = ensure_stage(h, s * 16 + 64);
     if (rc) return rc;
-    rc = ensure_pinned(h, ret_bytes + s * 4);      // + int32 pos[sel] of the compacted form
+    rc = ensure_pinned(h, rows_layout(hdr_b, sel_size, coef_ld).bytes_pos);      // with int32 pos[sel] of the compacted form
     if (rc) return rc;
     int64_t *d_mi = (int64_t *)h->d_stage;
     double *d_ms = (double *)(d_mi + s);
@@ -204,12 +202,13 @@ extern "C" int sdpcut_shard_finish_wait(sdpcut_handle h, int32_t compact_own, co
     *block = h->pinned;
     if (!compact_own) return SDPCUT_OK;
     const size_t s = (size_t)h->shard_pending_sel, ld = (size_t)h->shard_pending_ld;
-    char *p = (char *)h->pinned + (size_t)h->shard_pending_world * SHARD_HDR * 8 + s * 16;      // behind headers, ids, scores
-    double *lam = (double *)p;
-    double *rhs = lam + s;
-    double *coef = rhs + s;
-    int32_t *ks = (int32_t *)(coef + s * ld);
-    int32_t *pos = ks + s;
+    const RowsLayout y = rows_layout((size_t)h->shard_pending_world * SHARD_HDR * 8, h->shard_pending_sel, h->shard_pending_ld);
+    char *p = (char *)h->pinned;
+    double *lam = (double *)(p + y.lam);
+    double *rhs = (double *)(p + y.rhs);
+    double *coef = (double *)(p + y.coef);
+    int32_t *ks = (int32_t *)(p + y.ks);
+    int32_t *pos = (int32_t *)(p + y.pos);
     size_t w = 0;
     for (size_t i = 0; i < s; ++i) {
         if (ks[i] <= 0) continue;
@@ -254,13 +253,14 @@ extern "C" int sdpcut_shard_finish_round(sdpcut_handle h, int32_t world, int64_t
     int rc = sdpcut_shard_finish_round_view(h, world, count, d_allrec, sel_size, coef_ld, &block);
     if (rc) return rc;
     const size_t s = (size_t)sel_size, hdr_b = (size_t)world * SHARD_HDR * 8;
+    const RowsLayout y = rows_layout(hdr_b, sel_size, coef_ld);
     const char *q = (const char *)block;
-    std::memcpy(headers_out, q, hdr_b); q += hdr_b;
-    std::memcpy(idx_out, q, s * 8); q += s * 8;
-    std::memcpy(score_out, q, s * 8); q += s * 8;
-    std::memcpy(lam_min, q, s * 8); q += s * 8;
-    std::memcpy(rhs, q, s * 8); q += s * 8;
-    std::memcpy(coef, q, s * 8 * (size_t)coef_ld); q += s * 8 * (size_t)coef_ld;
-    std::memcpy(ks, q, s * 4);
+    std::memcpy(headers_out, q, hdr_b);
+    std::memcpy(idx_out, q + y.idx, s * 8);
+    std::memcpy(score_out, q + y.score, s * 8);
+    std::memcpy(lam_min, q + y.lam, s * 8);
+    std::memcpy(rhs, q + y.rhs, s * 8);
+    std::memcpy(coef, q + y.coef, s * 8 * (size_t)coef_ld);
+    std::memcpy(ks, q + y.ks, s * 4);
     return SDPCUT_OK;
 }
