@@ -102,9 +102,27 @@ enum { SDPCUT_KERNEL_MFMA = 0, SDPCUT_KERNEL_SIMPLE = 1, SDPCUT_KERNEL_VALU = 2 
  * its own m-th largest member, and publishes that floor).  Where the bin of the k-th largest key lies above every floor and its
  * members fit the sort buffers, the selection is resolved from the table: one pass over the scores, no digit pass, no grid barrier.
  * 0: the radix passes of rounds 2-4 (A/B; identical results). */
+/* SDPCUT_OPT_EXACT_HEAD (default 0): the head a selection under strategy 2 or 4 returns is the head of the reference's ranking
+ * with obj_improve computed in the REFERENCE's operation order (the arithmetic of SDPCUT_KERNEL_SIMPLE: no contraction, the host
+ * libm's exp, sums in index order) and this library's lambda_min; `score` carries those bits (strong class: the fp64 sum with
+ * BIG_M, cut_select_qp.py:611; entries whose score is -lambda_min are untouched), ties between equal exact scores go by ascending
+ * candidate index, the cut rows are those of that head, and under strategy 4 the classes, n_total / new_strat / counters follow
+ * the exact signs (strategy 2 has no class: its counters are what the option-off call reports).  The fast
+ * (MFMA) scores only filter: the selection runs for min(N, cap + max(256, cap / 8)) entries, that band is re-scored and
+ * re-ranked on the device, and csrc/exact_band.h decides on the device whether the band provably holds the exact head (the fast
+ * scores are within 1e-9 max(|obj|, 1e-3 max_elem) of the exact ones; measured 2e-11).  A band that does not is retried once with
+ * 8192 entries; if that fails too (masses of equal scores at the threshold; more than 1024 candidates whose sign the fast score
+ * cannot decide) the call GIVES UP: it returns exactly what it returns with the option off -- never a half-exact head -- and
+ * SDPCUT_STAT_EXACT_GAVE_UP counts it.
+ * Affects sdpcut_select_round*, sdpcut_round_view, sdpcut_round_csr*, and sdpcut_rank / sdpcut_rank_device when the head asked for
+ * is within the limit below (strategy 4: and max_out <= sel_size); strategies 1 and SDPCUT_PART_* ignore it.
+ * Head limit: min(N, cap + max(256, cap / 8)) <= 8192 (the reference's cap is 5000); a fused round with a longer head fails with
+ * SDPCUT_EINVAL while the option is on, sdpcut_rank* beyond it rank as with the option off.  The sharded entry points
+ * (sdpcut_shard_*) fail with SDPCUT_ESTATE while it is on.
+ * d_obj is NOT written back: sdpcut_get_scores and sdpcut_gather_scores_device keep returning what the score kernel produced. */
 enum { SDPCUT_OPT_KERNEL = 1, SDPCUT_OPT_TIMING = 2, SDPCUT_OPT_FUSE_KEYS = 3, SDPCUT_OPT_AUTO_REGIME = 4,
        SDPCUT_OPT_FUSED_TAIL = 5, SDPCUT_OPT_COOP_LAUNCH = 6, SDPCUT_OPT_EIG_KERNEL = 7, SDPCUT_OPT_STREAM_PRIORITY = 8,
-       SDPCUT_OPT_SIDE_STREAMS = 9, SDPCUT_OPT_ONE_LAUNCH = 10, SDPCUT_OPT_PREFILTER = 11 };
+       SDPCUT_OPT_SIDE_STREAMS = 9, SDPCUT_OPT_ONE_LAUNCH = 10, SDPCUT_OPT_PREFILTER = 11, SDPCUT_OPT_EXACT_HEAD = 12 };
 
 /* Counters of a handle: SDPCUT_STAT_ROUNDS = fused rounds served (sdpcut_select_round*),
  * SDPCUT_STAT_SELECT_FALLBACKS = rounds whose radix selection declared itself void (a grid barrier
@@ -118,9 +136,13 @@ enum { SDPCUT_OPT_KERNEL = 1, SDPCUT_OPT_TIMING = 2, SDPCUT_OPT_FUSE_KEYS = 3, S
  *   barrier: SDPCUT_OPT_PREFILTER); the others ran the radix passes (short lists, masses of equal keys at the threshold, the
  *   every-entry-visited regime).  Read from the device: the call waits for the handle's stream.  Same results either way.
  * SDPCUT_STAT_PF_BIN / _PF_FLOOR / _PF_COUNT: what the last selection that looked at the fine histogram found there -- the fine bin of
- *   the k-th largest key (-1: none), the floor the producers published (fine bins), the members at or above that bin.  Diagnostics. */
+ *   the k-th largest key (-1: none), the floor the producers published (fine bins), the members at or above that bin.  Diagnostics.
+ * SDPCUT_STAT_EXACT_HEAD = 1 if the last selection returned an exact head (SDPCUT_OPT_EXACT_HEAD), else 0;
+ * SDPCUT_STAT_EXACT_GAVE_UP = selections under the option that returned the ordinary head because a band did not fit;
+ * SDPCUT_STAT_EXACT_RETRIES = selections whose first band did not prove itself and that ran again with the widest one. */
 enum { SDPCUT_STAT_ROUNDS = 1, SDPCUT_STAT_SELECT_FALLBACKS = 2, SDPCUT_STAT_SCORED = 3, SDPCUT_STAT_TIE_SPLITS = 4,
-       SDPCUT_STAT_DIRECT_SELECTIONS = 5, SDPCUT_STAT_PF_BIN = 6, SDPCUT_STAT_PF_FLOOR = 7, SDPCUT_STAT_PF_COUNT = 8 };
+       SDPCUT_STAT_DIRECT_SELECTIONS = 5, SDPCUT_STAT_PF_BIN = 6, SDPCUT_STAT_PF_FLOOR = 7, SDPCUT_STAT_PF_COUNT = 8,
+       SDPCUT_STAT_EXACT_HEAD = 9, SDPCUT_STAT_EXACT_GAVE_UP = 10, SDPCUT_STAT_EXACT_RETRIES = 11 };
 int sdpcut_get_stat(sdpcut_handle h, int which, int64_t *value);
 
 /* Maximum sub-problem size (assert dim <= 5, cut_select_qp.py:93) */

@@ -3,6 +3,7 @@
 #include <cstring>
 
 #include "common.h"
+#include "topk_route.h"
 
 extern "C" {
 
@@ -57,6 +58,33 @@ int sdpcut_rank_device(sdpcut_handle h, int strat, int64_t sel_size, int64_t max
     if (max_out < 0 || (max_out > 0 && (!d_idx_out || !d_score_out))) return sdpcut_fail(h, SDPCUT_EINVAL, "bad output");
     HIP_TRY(h, hipSetDevice(h->device));
     if (h->timing > 1) HIP_TRY(h, hipEventRecord(h->ev[2], h->stream));
+    h->stat_exact_last = 0;
+    {
+        // SDPCUT_OPT_EXACT_HEAD: heads within the limit (strategy 4: a head of the scan's own length at most, whose regime the
+        // device resolves) are ordered by reference-order obj_improve; whatever it cannot serve ranks as with the option off
+        const int64_t cap = max_out < h->N ? max_out : h->N, sel = sel_size < h->N ? sel_size : h->N;
+        if (cap >= 1 && exact_head_applies(h, strat) && exact_first_band(h, cap) <= TK_LDSK && (strat != SDPCUT_STRAT_COMB || cap <= sel)) {
+            int64_t band = exact_first_band(h, cap);
+            for (int attempt = 0; attempt < 2; ++attempt) {
+                const int64_t *d_c4 = nullptr;
+                int64_t c4[7] = {0, 0, 0, 0, 0, 0, 0};
+                rc = exact_head_enqueue(h, strat, sel_size, cap, band, (int64_t *)d_idx_out, (double *)d_score_out, &d_c4);
+                if (rc) return rc;
+                HIP_TRY(h, hipMemcpyAsync(c4, d_c4, 7 * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+                HIP_TRY(h, sdpcut_sync(h));
+                const int v = exact_head_verdict(h, c4, band);
+                if (v == 0 && rank_fast_finish(h, strat, sel_size, cap, c4, n_written, n_total, new_strat, counters)) {
+                    h->stat_exact_last = 1;
+                    if (h->timing > 1) HIP_TRY(h, hipEventRecord(h->ev[3], h->stream));
+                    return SDPCUT_OK;
+                }
+                if (v != 1 || attempt == 1) break;
+                ++h->stat_exact_retries;
+                band = exact_widest_band(h);
+            }
+            ++h->stat_exact_gave_up;
+        }
+    }
     rc = rank_on_device(h, strat, sel_size, max_out, (int64_t *)d_idx_out, (double *)d_score_out, n_written, n_total,
                         new_strat, counters);
     if (rc) return rc;

@@ -56,6 +56,7 @@ struct PendingRound {
     int strat = 0;
     int32_t ld = 0;
     int64_t sel_size = 0, cap = 0, serial = 0;
+    int64_t exact_band = 0;        // > 0: the enqueued head is an exact one (SDPCUT_OPT_EXACT_HEAD) through a band of this many entries
 };
 
 // every entry point that touches the handle's scores, staging or pinned block refuses to run between the two halves of a round
@@ -90,6 +91,14 @@ struct sdpcut_ctx {
     unsigned long long *d_stats = nullptr;   // device counters that outlive a round: [0] direct selections
     bool coop_launch = false;      // SDPCUT_OPT_COOP_LAUNCH: cooperative launch of the kernels with grid barriers (+20 us per round)
     int64_t stat_rounds = 0, stat_fallbacks = 0, stat_tie_splits = 0;   // sdpcut_get_stat
+    // SDPCUT_OPT_EXACT_HEAD (exact_head.hip): NN-ranked heads ordered and reported by reference-order obj_improve
+    bool exact_head = false;
+    bool exact_suspended = false;  // a round that gave up is being served by the ordinary path
+    int64_t stat_exact_last = 0, stat_exact_gave_up = 0, stat_exact_retries = 0;
+    double q_absmax = 0.0;         // max |Q_arr| of the instance (bound on every candidate's max_elem, exact_band.h)
+    void *d_exact = nullptr;       // zero band, band ids and exact scores (exact_head.hip: ExactBufs)
+    double *d_obj_exact = nullptr; // [N] exact obj_improve of the band's members by candidate: tie key of the every-entry-visited sort
+    int64_t obj_exact_n = 0;
     int timing = 0;                // 0 off, 1 events around the score kernel, 2 also around the ranking
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     bool timed_score = false;      // ev[0] / ev[1] were attached to the last score launch
@@ -245,6 +254,21 @@ int rank_fast_enqueue(sdpcut_ctx *h, int strat, int64_t sel_size, int64_t max_ou
 int rank_fast_mode(sdpcut_ctx *h, int strat, int64_t sel_size, int64_t max_out, double *score_add);
 int rank_fast_finish(sdpcut_ctx *h, int strat, int64_t sel_size, int64_t max_out, const int64_t c4[7],
                      int64_t *n_written, int64_t *n_total, int32_t *new_strat, int64_t *counters_out);
+
+// exact_head.hip (SDPCUT_OPT_EXACT_HEAD)
+int exact_head_applies(const sdpcut_ctx *h, int strat);      // option on, strategy 2 or 4
+int64_t exact_first_band(const sdpcut_ctx *h, int64_t cap);  // entries of the first band of a head of cap entries
+int64_t exact_widest_band(const sdpcut_ctx *h);
+int exact_head_enqueue(sdpcut_ctx *h, int strat, int64_t sel_size, int64_t cap, int64_t band, int64_t *d_idx_out, double *d_score_out,
+                       const int64_t **d_c4);
+int exact_head_verdict(sdpcut_ctx *h, const int64_t c4[7], int64_t band);   // 0 exact, 1 retry with the widest band, 2 give up
+void free_exact_ws(sdpcut_ctx *h);
+// the sharded entry points have no exact merge
+#define SDPCUT_NO_EXACT(h)                                                                                                \
+    do {                                                                                                                  \
+        if ((h)->exact_head)                                                                                              \
+            return sdpcut_fail((h), SDPCUT_ESTATE, "SDPCUT_OPT_EXACT_HEAD is on: the sharded rounds have no exact merge"); \
+    } while (0)
 
 // tri.hip
 int tri_preprocess(sdpcut_ctx *h, const uint8_t *adjacency, int64_t *n_triples);

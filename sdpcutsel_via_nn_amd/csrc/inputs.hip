@@ -93,6 +93,11 @@ int sdpcut_set_instance(sdpcut_handle h, int32_t nb_vars, const double *Q_arr)
     HIP_TRY(h, hipMemcpy(h->d_Q, Q_arr, L * sizeof(double), hipMemcpyHostToDevice));
     h->nb_vars = nb_vars;
     h->L = L;
+    h->q_absmax = 0.0;
+    for (int64_t i = 0; i < L; ++i) {
+        const double a = Q_arr[i] < 0.0 ? -Q_arr[i] : Q_arr[i];
+        if (a > h->q_absmax) h->q_absmax = a;
+    }
     return SDPCUT_OK;
 }
 

@@ -76,6 +76,7 @@ int score_for_selection(sdpcut_ctx *h, int strat, int64_t sel_size, int64_t cap,
 // combined scan of heads > 8192), runs the general path.  csr = false: padded rows, block layout of sdpcut_select_round_view
 // (rows_layout behind 64 bytes; the staging area mirrors it); csr = true: the CSR block of sdpcut_round_csr (csr_layout).
 // Two handles may both begin before either ends: their device work overlaps (the QCQP round's two covers).
+static int round_begin_exact_again(sdpcut_ctx *h, PendingRound &P);
 static int round_begin(sdpcut_ctx *h, int strat, int64_t sel_size, int32_t coef_ld, bool csr)
 {
     int rc = check_round_strategy(h, strat);
@@ -89,11 +90,22 @@ static int round_begin(sdpcut_ctx *h, int strat, int64_t sel_size, int32_t coef_
     int64_t cap = sel_size < h->N ? sel_size : h->N;
     int stage = 0;               // how far the selection's first pass has got (topk_select_enqueue)
     bool auto_regime = false;
-    rc = score_for_selection(h, strat, sel_size, cap, strat_need(strat), h->auto_regime, &stage, &auto_regime);
+    // SDPCUT_OPT_EXACT_HEAD: the fast scores only filter (exact_head.hip); plain scoring, the selection counts for itself
+    const bool exact = cap > 0 && exact_head_applies(h, strat);
+    if (!h->exact_suspended) h->stat_exact_last = 0;
+    if (exact && exact_first_band(h, cap) > TK_LDSK)
+        return sdpcut_fail(h, SDPCUT_EINVAL, "SDPCUT_OPT_EXACT_HEAD: the head plus its band (min(N, sel_size + max(256, sel_size / 8))) must not exceed 8192 entries");
+    if (exact) {
+        const uint32_t need = strat_need(strat);
+        if ((h->scored & need) != need) rc = sdpcut_score(h, need & ~h->scored);
+    } else {
+        rc = score_for_selection(h, strat, sel_size, cap, strat_need(strat), h->auto_regime, &stage, &auto_regime);
+    }
     if (rc) return rc;
     PendingRound &P = h->pend;
     P = PendingRound();
     P.strat = strat; P.sel_size = sel_size; P.cap = cap; P.ld = coef_ld; P.csr = csr;
+    P.exact_band = exact ? exact_first_band(h, cap) : 0;
     if (cap == 0) {   // nothing to generate; round_end still reports the ranking's length / strategy switch
         P.active = true;
         return SDPCUT_OK;
@@ -112,7 +124,13 @@ static int round_begin(sdpcut_ctx *h, int strat, int64_t sel_size, int32_t coef_
     // fast path: selection and rows are enqueued back to back; the epilogue kernel stores the
     // results directly into the pinned host block (no copy engine); one synchronisation
     const int64_t *d_cnt = nullptr;
-    rc = rank_fast_enqueue(h, strat, sel_size, cap, d_idx, d_sc, &d_cnt, stage, auto_regime);
+    if (exact) {
+        rc = exact_head_enqueue(h, strat, sel_size, cap, P.exact_band, d_idx, d_sc, &d_cnt);
+        if (rc) return rc;
+        rc = 1;
+    } else {
+        rc = rank_fast_enqueue(h, strat, sel_size, cap, d_idx, d_sc, &d_cnt, stage, auto_regime);
+    }
     if (rc < 0) return rc;
     P.fast_tried = rc == 1;
     if (P.fast_tried) {
@@ -126,6 +144,24 @@ static int round_begin(sdpcut_ctx *h, int strat, int64_t sel_size, int32_t coef_
     }
     P.active = true;
     return SDPCUT_OK;
+}
+
+// SDPCUT_OPT_EXACT_HEAD: the first band of the pending round P did not prove that it holds the exact head; the same round through
+// the widest band (scores, staging and pinned block are in place), under a fresh serial number.
+static int round_begin_exact_again(sdpcut_ctx *h, PendingRound &P)
+{
+    const RowsLayout y = rows_layout(64, P.cap, P.ld);
+    int64_t *d_idx = (int64_t *)((char *)h->d_stage + y.idx);
+    double *d_sc = (double *)((char *)h->d_stage + y.score);
+    int64_t *hdr = (int64_t *)h->pinned;
+    if (P.csr) hdr[8] = hdr[9] = hdr[10] = 0;
+    P.exact_band = exact_widest_band(h);
+    const int64_t *d_cnt = nullptr;
+    int rc = exact_head_enqueue(h, P.strat, P.sel_size, P.cap, P.exact_band, d_idx, d_sc, &d_cnt);
+    if (rc) return rc;
+    P.serial = ++h->round_serial;
+    return P.csr ? launch_round_csr(h, P.cap, d_cnt, P.cap, d_idx, d_sc, P.ld, h->pinned_dev, P.serial)
+                 : launch_round_rows(h, P.cap, d_cnt, d_idx, d_sc, P.ld, h->pinned_dev, 64, P.serial);
 }
 
 // CSR assembly of the first w entries of a head the host produced (ids and scores in the staging area), under a fresh serial
@@ -184,9 +220,35 @@ static int round_end(sdpcut_ctx *h, const void **block, int64_t *cap_out, int64_
 {
     if (!block || !cap_out || !n_out) return sdpcut_fail(h, SDPCUT_EINVAL, "bad select_round arguments");
     if (!h->pend.active) return sdpcut_fail(h, SDPCUT_ESTATE, "no round pending on this handle");
-    const PendingRound P = h->pend;
+    PendingRound P = h->pend;
     h->pend.active = false;
     HIP_TRY(h, hipSetDevice(h->device));
+    if (P.exact_band > 0 && P.cap > 0) {
+        // the verdict of the band rule arrives with the block (hdr[4]): exact -- the ordinary code below finds its round complete;
+        // a band that did not prove itself -- once more with the widest one (a second wait); else the ordinary round, whole
+        int rc = wait_round_done(h, (const int64_t *)h->pinned + 7, P.serial);
+        if (rc) return rc;
+        int v = exact_head_verdict(h, (const int64_t *)h->pinned, P.exact_band);
+        if (v == 1) {
+            ++h->stat_exact_retries;
+            rc = round_begin_exact_again(h, P);
+            if (rc) return rc;
+            rc = wait_round_done(h, (const int64_t *)h->pinned + 7, P.serial);
+            if (rc) return rc;
+            v = exact_head_verdict(h, (const int64_t *)h->pinned, P.exact_band);
+        }
+        if (v != 0) {
+            ++h->stat_exact_gave_up;
+            h->exact_suspended = true;
+            rc = round_begin(h, P.strat, P.sel_size, P.ld, P.csr);
+            h->exact_suspended = false;
+            if (rc) return rc;
+            P = h->pend;
+            h->pend.active = false;
+        } else {
+            h->stat_exact_last = 1;
+        }
+    }
     const int strat = P.strat;
     const int64_t sel_size = P.sel_size, cap = P.cap;
     *n_out = 0;
@@ -233,6 +295,10 @@ static int round_end(sdpcut_ctx *h, const void **block, int64_t *cap_out, int64_
     if (!have) {
         // general path (full sorts; the combined scan visiting every entry, or heads > 8192)
         // (the fast attempt above already counted the strong candidates: no second attempt)
+        if (P.exact_band > 0 && h->stat_exact_last) {      // (never seen: an exact head's counters always answer) nothing half-exact
+            h->stat_exact_last = 0;
+            ++h->stat_exact_gave_up;
+        }
         const int64_t *c5 = (const int64_t *)h->pinned;
         const int64_t hint = (P.fast_tried && strat == SDPCUT_STRAT_COMB && !c5[4]) ? c5[0] : -1;
         rc = rank_on_device(h, strat, sel_size, cap, d_idx, d_sc, &w, n_total, new_strat, counters, hint);

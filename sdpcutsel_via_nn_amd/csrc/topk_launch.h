@@ -16,6 +16,7 @@ struct TkJob {
     double *d_score_out;
     int raw;                      // see tk_mergerank_big_kernel
     int64_t emit_limit;
+    const double *tie_obj = nullptr;   // obj_improve the sort tail orders equal keys by (modes with a tie key); NULL: the handle's scores
 };
 
 // topk_passes.hip: the key passes, the fused kernel (TK_ROUTE_ONFLY / TK_ROUTE_COOP / TK_ROUTE_FUSED), the launch per digit

@@ -228,7 +228,7 @@ static void sort_launch(sdpcut_ctx *h, const TkPlan &p, const TkJob &j)
 {
     uint64_t *tile_key = h->d_sel_key + TK_MAXK;      // first half: compacted selection, second half: the sorted tiles
     uint32_t *tile_idx = h->d_sel_idx + TK_MAXK;
-    const double *tie_obj = T ? h->d_obj : nullptr;
+    const double *tie_obj = T ? (j.tie_obj ? j.tie_obj : h->d_obj) : nullptr;
     const dim3 g_sort(p.ntiles), g_merge(p.ntiles * TK_TILE / TK_THREADS), blk(TK_THREADS);      // idle tiles exit at once
     hipLaunchKernelGGL(tk_tilesort_kernel<T>, g_sort, blk, 0, h->stream, j.ws, h->d_sel_key, h->d_sel_idx, tile_key, tile_idx, tie_obj);
     if constexpr (T < 2) {

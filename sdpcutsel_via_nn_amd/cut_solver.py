@@ -472,6 +472,9 @@ class GpuCutSelectionMixin(object):
     _gpu_device = 0
     _sparse_pair = None
     _gpu_overlap = True      # begin the follower list's round together with the leader's (QCQP: two covers per LP point)
+    # heads under the NN-ranked strategies (2, 4) ordered and reported by obj_improve in the reference's operation order
+    # (SDPCUT_OPT_EXACT_HEAD, include/sdpcut.h); a subclass or make_dropin_classes(..., exact_heads=True) switches it on
+    _gpu_exact_heads = False
 
     # ------------------------------------------------------------------ a11 loader
     def _load_neural_nets(self):
@@ -498,6 +501,8 @@ class GpuCutSelectionMixin(object):
         sc = _capi.Scorer(self._gpu_device)
         for d, (widths, params) in getattr(self, "_gpu_nets", {}).items():
             sc.set_network(d, widths, params)
+        if self._gpu_exact_heads:
+            sc.set_option(_capi.OPT_EXACT_HEAD, 1)
         return sc
 
     def _gpu_bind(self):
@@ -899,8 +904,9 @@ class CutSolver(GpuCutSelectionMixin):
     _SDP_CUTS_PER_ROUND_MAX = 5000
     _THRES_MAX_SUBS = 4 * (10 ** 6)
 
-    def __init__(self, device=0):
+    def __init__(self, device=0, exact_heads=False):
         self._gpu_device = device
+        self._gpu_exact_heads = bool(exact_heads)
         self._dim = 0
         self._nb_vars = 0
         self._nb_lifted = 0
@@ -1062,7 +1068,7 @@ class CutSolverQCQP(CutSolver):
         return log.bounds, quota, [0] + log.column("sdp"), [0] + opt + [0] * (nb_rounds_cuts - len(opt))
 
 
-def make_dropin_classes(cut_select_qp, cut_select_qcqp=None):
+def make_dropin_classes(cut_select_qp, cut_select_qcqp=None, exact_heads=False):
     """Compose the GPU mixin with the reference's own classes (modules passed in, nothing is
     imported here) -> (GpuCutSolver, GpuCutSolverQCQP or None).
 
@@ -1074,8 +1080,11 @@ def make_dropin_classes(cut_select_qp, cut_select_qcqp=None):
         GpuCutSolver     = (GpuCutSelectionMixin, CutSolver)
         GpuCutSolverQCQP = (CutSolverQCQP, GpuCutSolver)
         MRO: GpuCutSolverQCQP, CutSolverQCQP, GpuCutSolver, GpuCutSelectionMixin, CutSolver, object
+
+    exact_heads: the classes' ``_gpu_exact_heads`` (SDPCUT_OPT_EXACT_HEAD on every handle they create).
     """
-    qp = type("GpuCutSolver", (GpuCutSelectionMixin, cut_select_qp.CutSolver), {"__doc__": "CutSolver with the hot path on the GPU"})
+    qp = type("GpuCutSolver", (GpuCutSelectionMixin, cut_select_qp.CutSolver),
+              {"__doc__": "CutSolver with the hot path on the GPU", "_gpu_exact_heads": bool(exact_heads)})
     qcqp = None
     if cut_select_qcqp is not None:
         qcqp = type("GpuCutSolverQCQP", (cut_select_qcqp.CutSolverQCQP, qp), {"__doc__": "CutSolverQCQP with the hot path on the GPU"})
