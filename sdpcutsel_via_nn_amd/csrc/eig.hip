@@ -3,7 +3,7 @@
 //
 // Fifteen of the twenty recorded rounds of BASELINE configs[2] (the strategy switches 4 -> 1 in round 5)
 // and every QCQP round over the constraints-only cover (cut_select_qcqp.py:75-77) are this scan.  It has
-// no MLP: no weights, no LDS strips, no MFMA accumulators.  score_mfma_kernel serves it with a uniform
+// no MLP: no weights, no LDS strips, no MFMA accumulators.  score_mfma_kernel (score_mfma.hip) serves it with a uniform
 // branch but is compiled for the MLP's 225-245 registers (2 waves per SIMD), and a feasibility round is a
 // chain of dependent v_rsq / v_rcp / fma sequences behind two dependent memory round trips (index set,
 // then the gathers it addresses) -- exactly the kind of code that needs many waves to hide latency.
@@ -21,6 +21,7 @@
 
 #include "common.h"
 #include "gather.h"
+#include "score_plan.h"      // pf_mloc_rule
 #include "topk_dev.h"
 
 struct EigArgs {
@@ -226,13 +227,13 @@ __global__ __launch_bounds__(256, EigOcc<KMAX>::W) void eig_only_kernel(EigArgs 
     int par = 0;
     // tiles of all classes form one list, largest size first; workgroup b takes tiles b, b + G, ... -- class by class, so that
     // the index set of its NEXT tile (HBM) is requested before the current one is worked on (the first of the two dependent
-    // memory round trips of a tile off the critical path, as in score_mfma_kernel)
+    // memory round trips of a tile off the critical path, as in score_mfma_body, score_mfma.hip)
     if constexpr (KMAX >= 5) eig_class<5, FUSE>(A, 0, A.tile_end[5], s_state, s_out, s_packed, par, tk_hist, c_viol);
     if constexpr (KMAX >= 4) eig_class<4, FUSE>(A, A.tile_end[5], A.tile_end[4], s_state, s_out, s_packed, par, tk_hist, c_viol);
     if constexpr (KMAX >= 3) eig_class<3, FUSE>(A, A.tile_end[4], A.tile_end[3], s_state, s_out, s_packed, par, tk_hist, c_viol);
     eig_class<2, FUSE>(A, A.tile_end[3], A.tile_end[2], s_state, s_out, s_packed, par, tk_hist, c_viol);
     if constexpr (FUSE) {
-        // (no ticket, nobody waits: the kernel boundary orders the atomics before the selection, see score.hip)
+        // (no ticket, nobody waits: the kernel boundary orders the atomics before the selection, see score_mfma.hip)
         for (int off = 32; off > 0; off >>= 1) c_viol += __shfl_xor((int)c_viol, off);
         if ((threadIdx.x & 63) == 0 && c_viol) atomicAdd(&tk_cnt, c_viol);
         __syncthreads();
@@ -263,11 +264,8 @@ static void eig_launch(sdpcut_ctx *h, EigArgs &A, hipEvent_t ev_start, hipEvent_
     const int grid = (int)(ntiles < cap ? ntiles : cap);
     A.pf_mloc = 0;
 #if SDPCUT_LMIN
-    if (FUSE && pf_k > 0 && h->N > 0) {      // as pf_mloc_for (score.hip): 24 + eight times the workgroup's expected share of the head
-        const int64_t per_wg = (ntiles + grid - 1) / grid * 256;
-        const double m = 24.0 + 8.0 * (double)pf_k * (double)per_wg / (double)h->N;
-        A.pf_mloc = per_wg >= 60000 ? 0 : (m > 60000.0 ? 60000 : (int)(m + 0.999));
-    }
+    if (FUSE && pf_k > 0 && h->N > 0)      // the rule of the score kernels (score_plan.h), for a workgroup's whole tiles
+        A.pf_mloc = pf_mloc_rule(pf_k, (ntiles + grid - 1) / grid * 256, h->N);
 #endif
     A.spread = A.pf_mloc > 0 && ntiles <= grid;
     if (FUSE && A.pf_mloc == 0) h->pf_counted = false;

@@ -1,5 +1,5 @@
 // Gather of one candidate's slices from the instance tables and its lambda_min -- shared by the
-// scoring kernels (score.hip) and the eigenvalue-only kernel of the feasibility rounds (eig.hip).
+// scoring kernels (score_mfma.hip, score_alt.hip) and the eigenvalue-only kernel of the feasibility rounds (eig.hip).
 #pragma once
 #include "common.h"
 #include "jacobi.h"
@@ -104,7 +104,7 @@ __device__ __forceinline__ double candidate_eigmin(const Cand<K> &cd)
 #endif
 }
 
-// The same for the two hot kernels (eig_only_kernel, score_mfma_body).  The lanes Jacobi is left with go through a REAL function
+// The same for the two hot kernels (eig_only_kernel in eig.hip, score_mfma_body in score_mfma.hip).  The lanes Jacobi is left with go through a REAL function
 // call (noinline): they gather their matrix again from the index set -- same tables, same values, same lambda_min as the inline
 // form above -- so that neither x / X (k(k+3)/2 doubles, 40 registers at k = 5) nor Jacobi's own (k+1)^2 working set weigh on
 // the register allocation of the path every wave at a generic LP point takes.

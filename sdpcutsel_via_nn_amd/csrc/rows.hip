@@ -8,7 +8,7 @@
 #include "gather.h"
 #include "topk_dev.h"
 
-// LDS traffic private to one wave needs no workgroup barrier (see score.hip)
+// LDS traffic private to one wave needs no workgroup barrier (see score_mfma.hip)
 __device__ __forceinline__ void wave_lds_sync()
 {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");

@@ -20,7 +20,7 @@
 // coherent for plain loads inside a launch).
 //
 // A round that scores for itself (sdpcut_select_round on a fresh point) does not run the first pass
-// here: the score kernels count the leading digit of the class members' keys (score.hip, ScoreArgs::tk)
+// here: the score kernels count the leading digit of the class members' keys (score_mfma.hip; ScoreArgs::tk, score_launch.h)
 // and tk_refine_kernel<true> starts at the second digit, building the keys from the scores as it
 // reads them -- tk_keys_kernel and the key array are for selections over scores that exist already.
 //

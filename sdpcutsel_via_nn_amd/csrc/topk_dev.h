@@ -1,5 +1,5 @@
 // Device-side pieces of the top-k selection shared by its route files (topk_passes.hip, topk_compact.hip, topk_small.hip,
-// topk_sort.hip), the host file topk.hip and the producers of the scores: the score kernels (score.hip, eig.hip) can emit the
+// topk_sort.hip), the host file topk.hip and the producers of the scores: the score kernels (score_mfma.hip, eig.hip) can emit the
 // first histograms of the selection themselves, see ScoreArgs::tk.  Modes, limits and the route decision: topk_route.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -155,7 +155,7 @@ __device__ __forceinline__ void hist_add_few(uint32_t *hist, uint32_t bin, bool 
     if ((rem >> lane) & 1ull) atomicAdd(&hist[bin], 1u);
 }
 
-// ---- fine histogram: device side of the producers (score.hip, eig.hip) -------------------------------------------------
+// ---- fine histogram: device side of the producers (score_mfma.hip, eig.hip) -------------------------------------------------
 __device__ __forceinline__ void pf_publish_floor(TopkWs *ws, int floor_f)
 {
     if (floor_f > 0)

@@ -346,8 +346,8 @@ def test_short_list_tie_group_beyond_the_sort_buffers(oracle, count):
 
 @pytest.mark.parametrize("k,count", [(3, 1000003), (4, 1010101)])
 def test_balanced_last_round_of_the_scoring_kernel(k, count):
-    """Lists whose last round-robin round is at least 90 % full have it dealt out evenly in column tiles (score.hip
-    set_balanced_tail): strips of three tiles, a last strip that ends inside a tile.  Every candidate is scored once, and its
+    """Lists whose last round-robin round is at least 90 % full have it dealt out evenly in column tiles (score_plan.h
+    score_plan): strips of three tiles, a last strip that ends inside a tile.  Every candidate is scored once, and its
     scores are bit for bit what the same candidate gets in a list that is split differently (its last 300 001 candidates alone:
     whole strips) -- a score depends on the candidate, never on where the work split puts it."""
     from sdpcutsel_via_nn_amd import _capi, networks, synthetic

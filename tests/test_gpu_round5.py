@@ -181,7 +181,7 @@ def test_direct_selection_steps_aside_for_masses_of_equal_keys(golden_boxqp):
 def test_direct_selection_on_a_real_cover(oracle):
     """spar125-075-1 dim 4 (1 700 215 four-variable candidates, enumerated index set by index set: the head clusters) at recorded
     LP points: the feasibility round 8 is resolved from the fine histogram; the combined rounds 4 and 2 are not -- the score
-    kernel of 4-variable candidates does not count (csrc/score.hip: it costs that kernel more than the selection saves).  All
+    kernel of 4-variable candidates does not count (csrc/score_plan.h, SDPCUT_PF_SCORE_KMASK: it costs that kernel more than the selection saves).  All
     identical to the radix passes."""
     import os
     import sdpcutsel_via_nn_amd as pkg

@@ -1,12 +1,12 @@
 #!/bin/bash
-# Development aid: build variants of the library with -DSDPCUT_ABL_<X> switches of score.hip
+# Development aid: build variants of the library with -DSDPCUT_ABL_<X> switches of score_mfma.hip
 # (results are WRONG by design; only the kernel time is of interest) into sdpcutsel_via_nn_amd/_abl/.
 # usage: [ABL_SRC=eig] tools/build_ablation.sh NAME1[:FLAG,FLAG] NAME2 ...   e.g.  base nobias:NOBIAS notansig:NOTANSIG
-# (ABL_SRC: the translation unit the switches apply to, default score)
+# (ABL_SRC: the translation unit the switches apply to, default score_mfma)
 set -e
 cd "$(dirname "$0")/.."
 P=sdpcutsel_via_nn_amd
-SRC=${ABL_SRC:-score}
+SRC=${ABL_SRC:-score_mfma}
 mkdir -p $P/_abl
 python -m $P.build >/dev/null 2>&1
 for spec in "$@"; do
