@@ -401,6 +401,41 @@ int sdpcut_round_csr_begin(sdpcut_handle h, const double *vars_values, int strat
 int sdpcut_round_csr_end(sdpcut_handle h, sdpcut_round_csr_t *out);
 
 /*
+ * Dense eigen-cuts: strategy 0 of cut_select_algo, the paper's baseline (replaces __gen_dense_eigcuts, cut_select_qp.py:757-786:
+ * numpy.linalg.eigh of the whole lifted matrix [[1, x^T],[x, X]] of order dim = nb_vars + 1 and the per-entry Python comprehension
+ * that builds one fully dense cut for every negative eigenvalue but the largest).  Both calls need sdpcut_set_instance and a point
+ * only -- no candidates, no networks (SDPCUT_ESTATE without them) -- and nb_vars <= SDPCUT_DENSE_MAX_VARS (SDPCUT_EINVAL beyond:
+ * the eigensolver is one workgroup with the matrix resident in LDS, csrc/dense.hip).  Neither touches the candidate list or its
+ * scores.  A round begun with sdpcut_round_csr_begin must be ended first (SDPCUT_ESTATE).
+ *
+ * sdpcut_dense_round: vars_values as in sdpcut_round_csr (NULL keeps the current point).  Two kernels and ONE host wait:
+ *   eigvals[dim]            all eigenvalues, ascending (two-sided cyclic Jacobi; within a few ulp of ||A||_F of LAPACK's);
+ *                           eigvals[0] is lambda_min of the lifted matrix -- the PSD-infeasibility of the LP point itself
+ *   n_rows                  #{r < nb_vars : eigvals[r] < -1e-15} (:773-774); row r belongs to eigvals[r]
+ *   cols[row_len]           [L .. L+n-1 | 0 .. L-1], the LP columns of EVERY row (:779), row_len = n + n(n+1)/2
+ *   values[n_rows][row_len] [2 v0 v1 .. 2 v0 vn | v1^2, 2 v1 v2, .., vn^2] of the unit eigenvector v of eigvals[r] (:776-777);
+ *                           unlike the sparse rows NO component is zeroed
+ *   rhs[n_rows]             -v0^2 (:780); every row has sense "G"
+ *   sweeps                  Jacobi sweeps the decomposition took
+ * The pointers point into the handle's pinned host block (written by the device): valid until the next call on the handle.
+ * With SDPCUT_OPT_TIMING, sdpcut_last_timing reports ms[0] = the eigensolver and (option value 2) ms[1] = the row assembly.
+ *
+ * sdpcut_dense_eig: the decomposition alone at the current point.  eigvals[dim] ascending; evecs (may be NULL) [dim][dim] with
+ * evecs[i][j] = component i of the eigenvector of eigvals[j] (numpy's column convention).  Caller-owned buffers.
+ */
+#define SDPCUT_DENSE_MAX_VARS 127
+typedef struct sdpcut_dense_round {
+    int32_t dim, n_rows, sweeps, reserved;   /* dim = nb_vars + 1 */
+    int64_t row_len;                         /* n + n(n+1)/2 */
+    const double *eigvals;                   /* dim, ascending; row r belongs to eigvals[r] */
+    const int32_t *cols;                     /* row_len, shared by all rows */
+    const double *values;                    /* [n_rows][row_len] */
+    const double *rhs;                       /* n_rows */
+} sdpcut_dense_round_t;
+int sdpcut_dense_round(sdpcut_handle h, const double *vars_values, sdpcut_dense_round_t *out);
+int sdpcut_dense_eig(sdpcut_handle h, double *eigvals, double *evecs);
+
+/*
  * The same round over candidate shards (one handle per GPU, SURVEY 8 e): the two device-side
  * halves around the single all-gather the caller performs (torch.distributed / RCCL).
  *

@@ -38,6 +38,11 @@ class RoundCsr(_c.Structure):
                 ("n_rows", _c.c_int64), ("nnz", _c.c_int64), ("row_entry", _vp), ("indptr", _vp), ("indices", _vp),
                 ("values", _vp), ("rhs", _vp)]
 
+class DenseRound(_c.Structure):
+    """sdpcut_dense_round_t of include/sdpcut.h"""
+    _fields_ = [("dim", _c.c_int32), ("n_rows", _c.c_int32), ("sweeps", _c.c_int32), ("reserved", _c.c_int32), ("row_len", _c.c_int64),
+                ("eigvals", _vp), ("cols", _vp), ("values", _vp), ("rhs", _vp)]
+
 
 # name -> argtypes (restype is c_int unless listed in _RESTYPES); kept in one table so that the
 # CPU test-suite can check that the library exports every symbol the header declares
@@ -76,6 +81,8 @@ SIGNATURES = {
     "sdpcut_round_csr": [_vp, _dp, _c.c_int, _c.c_int64, _c.POINTER(RoundCsr)],
     "sdpcut_round_csr_begin": [_vp, _dp, _c.c_int, _c.c_int64],
     "sdpcut_round_csr_end": [_vp, _c.POINTER(RoundCsr)],
+    "sdpcut_dense_round": [_vp, _dp, _c.POINTER(DenseRound)],
+    "sdpcut_dense_eig": [_vp, _dp, _dp],
     "sdpcut_shard_head_device": [_vp, _c.c_int, _c.c_int64, _vp],
     "sdpcut_shard_finish_enqueue": [_vp, _c.c_int32, _c.c_int64, _c.c_int32, _vp, _c.c_int64, _c.c_int64, _c.c_int32],
     "sdpcut_shard_finish_wait": [_vp, _c.c_int32, _c.POINTER(_c.c_void_p), _i64p],
@@ -529,6 +536,39 @@ class Scorer(object):
         res.update(n_total=int(out.n_total), new_strat=int(out.new_strat),
                    counters=dict(nb_violated=int(cnt[0]), strong=int(cnt[1]), violated=int(cnt[2]), nb_positive=int(cnt[3])))
         return res
+
+    # ------------------------------------------------------------------ dense eigen-cuts (strategy 0)
+    def dense_round(self, point=None, copy=False):
+        """Dense eigen-cuts of the whole lifted matrix at the LP point (sdpcut_dense_round; strategy 0, cut_select_qp.py:757-786)
+        -> dict(eigvals [n+1] ascending, n_rows, sweeps, cols [row_len] shared by all rows, values [n_rows, row_len], rhs [n_rows]).
+        Needs set_instance and a point only.  The arrays are numpy views of the handle's pinned host block (valid until the next
+        call on this Scorer); copy=True detaches them.  point=None keeps the current LP point."""
+        vv = self._csr_point(point)
+        self.round_count += 1
+        out = DenseRound()
+        self._check(self._lib.sdpcut_dense_round(self._h, _ptr(vv, _dp), ctypes.byref(out)))
+        D, r, rl = int(out.dim), int(out.n_rows), int(out.row_len)
+
+        def view(ptr, dtype, count, shape=None):
+            if count == 0:
+                return np.zeros(shape or 0, dtype=dtype)
+            a = np.frombuffer((_c.c_char * (count * np.dtype(dtype).itemsize)).from_address(ptr), dtype=dtype, count=count)
+            return a.reshape(shape) if shape else a
+        res = dict(eigvals=view(out.eigvals, np.float64, D), cols=view(out.cols, np.int32, rl),
+                   values=view(out.values, np.float64, r * rl, (r, rl)), rhs=view(out.rhs, np.float64, r))
+        if copy:
+            res = {k: a.copy() for k, a in res.items()}
+        res.update(n_rows=r, sweeps=int(out.sweeps))
+        return res
+
+    def dense_eig(self, vectors=False):
+        """Eigen-decomposition of the whole lifted matrix at the current point (sdpcut_dense_eig): eigenvalues ascending
+        [n+1], and with vectors=True also V [n+1, n+1] with V[:, j] the unit vector of eigenvalue j (numpy.linalg.eigh's layout)."""
+        D = self.nb_vars + 1
+        w = np.empty(D)
+        v = np.empty((D, D)) if vectors else None
+        self._check(self._lib.sdpcut_dense_eig(self._h, _ptr(w, _dp), _ptr(v, _dp)))
+        return (w, v) if vectors else w
 
     # ------------------------------------------------------------------ sharded round (multi-GPU)
     def shard_head_device(self, strat, count, d_record_ptr):

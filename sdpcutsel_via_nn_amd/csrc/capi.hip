@@ -99,6 +99,7 @@ int sdpcut_destroy(sdpcut_handle h)
     free_rank_ws(h);
     free_topk_ws(h);
     free_exact_ws(h);
+    free_dense_ws(h);
     (void)hipFree(h->d_tri); (void)hipFree(h->d_tri_dense3);
     if (h->pinned) (void)hipHostFree(h->pinned);
     if (h->point_stage) (void)hipHostFree(h->point_stage);

@@ -161,6 +161,7 @@ struct sdpcut_ctx {
     int64_t round_serial = 0;      // completion word of the fused round (round_rows_kernel -> pinned header)
     uint32_t *d_done_ticket = nullptr;
     PendingRound pend;
+    void *d_dense = nullptr;       // dense eigen-cuts (dense.hip): V^T, sorted vectors, eigenvalues, n_rows; allocated by the first call
     // sdpcut_shard_finish_enqueue -> sdpcut_shard_finish_wait
     int64_t shard_pending_serial = 0, shard_pending_sel = 0;
     int32_t shard_pending_world = 0, shard_pending_ld = 0;
@@ -270,6 +271,9 @@ void free_exact_ws(sdpcut_ctx *h);
         if ((h)->exact_head)                                                                                              \
             return sdpcut_fail((h), SDPCUT_ESTATE, "SDPCUT_OPT_EXACT_HEAD is on: the sharded rounds have no exact merge"); \
     } while (0)
+
+// dense.hip
+void free_dense_ws(sdpcut_ctx *h);
 
 // tri.hip
 int tri_preprocess(sdpcut_ctx *h, const uint8_t *adjacency, int64_t *n_triples);

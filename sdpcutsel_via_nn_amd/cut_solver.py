@@ -751,6 +751,35 @@ class GpuCutSelectionMixin(object):
         store.add(lin_expr=rows, rhs=rhs_out, senses=["G"] * len(rows))
         return len(rows)
 
+    # ------------------------------------------------------------------ dense eigen-cuts (strategy 0)
+    def _gpu_dense_scorer(self):
+        """Handle that holds the instance for the dense eigen-cuts (no candidates, no networks): made once per instance."""
+        key = (self._nb_vars, id(self._Q_arr))
+        if getattr(self, "_gpu_dense_key", None) != key:
+            sc = _capi.Scorer(self._gpu_device)
+            sc.set_instance(self._nb_vars, np.asarray(self._Q_arr, dtype=np.float64))
+            self._gpu_dense_sc, self._gpu_dense_key = sc, key
+        return self._gpu_dense_sc
+
+    def _gen_dense_eigcuts(self, vars_values=None):
+        """One fully dense eigen-cut per negative eigenvalue (but the largest) of the whole lifted matrix at ``vars_values``,
+        appended to the LP (cut_select_qp.py:757-786); decomposition and rows on the device (sdpcut_dense_round).
+        -> number of cuts."""
+        r = self._gpu_dense_scorer().dense_round(np.ascontiguousarray(vars_values, dtype=np.float64))
+        nb, cols, values, rhs = r["n_rows"], r["cols"], r["values"], r["rhs"]
+        store = self._my_prob.linear_constraints
+        if hasattr(store, "add_csr"):
+            # (copies: the arrays are views of the scorer's pinned block, which the next round overwrites)
+            store.add_csr(np.arange(nb + 1, dtype=np.int64) * cols.shape[0], np.tile(cols, nb), values.reshape(-1).copy(), rhs.copy(), "G")
+            return nb
+        pair = self._sparse_pair or _default_sparse_pair()
+        ind = cols.tolist()
+        store.add(lin_expr=[pair(ind=ind, val=values[c].tolist()) for c in range(nb)], rhs=rhs.tolist(), senses=["G"] * nb)
+        return nb
+
+    # the reference's loop reaches it through the name-mangled private name (cut_select_qp.py:166)
+    _CutSolver__gen_dense_eigcuts = _gen_dense_eigcuts
+
     def _gpu_add_csr(self, csr, pair):
         """Hand a block of assembled cuts to the LP: as arrays when the row store takes them (``add_csr``), else as the
         reference's per-row objects (cut_select_qp.py:747-754).  The arrays are copied: they are views of the scorer's
@@ -941,14 +970,15 @@ class CutSolver(GpuCutSelectionMixin):
         the reference's entry point (cut_select_qp.py:73-221), with HiGHS as LP solver, the native
         cover enumeration and the GPU selection / generation / triangle separation in between.
         ``max_subs=None`` lifts the reference's 4e6 candidate guard (:117-120); ``on_round(r, log)`` is
-        called after every LP solve (progress of long runs).  Dense cuts
-        (strat 0), exact-SDP strategies and chordal extensions are out of scope.
+        called after every LP solve (progress of long runs).  Strategy 0 adds
+        the fully dense eigen-cuts of :meth:`_gen_dense_eigcuts` instead of a selection (the cover is still enumerated: the tuple
+        reports its size); exact-SDP strategies and chordal extensions are out of scope.
         -> (bound per solve, total s, round s, separation s, PSD cuts per round, triangle cuts per
         round, number of candidates)."""
         from timeit import default_timer as clock
         from . import harness
-        if strat not in (1, 2, 4, 5):
-            raise AssertionError("strategies on the GPU path: 1 feasibility, 2 optimality, 4 combined, 5 random")
+        if strat not in (0, 1, 2, 4, 5):
+            raise AssertionError("strategies on the GPU path: 0 dense, 1 feasibility, 2 optimality, 4 combined, 5 random")
         assert 0 < sel_size, "The selection size must be a % or number (of cuts) >0!"
         assert dim <= 5, "Keep SDP vertex cover low-dimensional (<=5)!"
         t_start = clock()
@@ -973,9 +1003,14 @@ class CutSolver(GpuCutSelectionMixin):
         if triangle_on:
             self._preprocess_triangle_ineq()
         state = {"strat": strat}
+        if strat == 0:      # the cover's scorer already holds the instance
+            self._gpu_dense_sc, self._gpu_dense_key = sc, (self._nb_vars, id(self._Q_arr))
 
         def separate(round_no, point):
             cur = state["strat"]
+            if cur == 0:
+                sdp = self._gen_dense_eigcuts(vars_values=point)
+                return {"sdp": sdp, "tri": self._separate_and_add_triangle(sel_size, point) if triangle_on else 0}
             picked = self._sel_eigcut_by_ordering_on_measure(cur, point, round_no, **({"sel_size": quota} if cur == 4 else {}))
             if cur == 4 and isinstance(picked, tuple):
                 state["strat"], picked = picked       # the switch takes effect next round (:181 vs :188)
@@ -985,7 +1020,9 @@ class CutSolver(GpuCutSelectionMixin):
 
         log = harness.run_cut_rounds(lp, separate, nb_rounds_cuts, setup_s=t_model,
                                      stop_tol=self._CONVERGENCE_TOL if term_on else None, on_round=on_round,
-                                     after_solve=self._gpu_wake)
+                                     after_solve=self._gpu_wake,
+                                     # dense cuts: past the 4th round, stop once the rounds have taken 1000 s (:157)
+                                     stop=(lambda r, lg: r > 4 and sum(lg.solve_s) + sum(lg.separation_s) > 1000) if strat == 0 and term_on else None)
         sep = [t_model] + log.separation_s
         return ([-v for v in log.bounds], clock() - t_start, [a + b for a, b in zip(log.solve_s, [0.0] + log.separation_s)],
                 sep, [0] + log.column("sdp"), log.column("tri"), n_cand)

@@ -303,12 +303,14 @@ class RoundLog(object):
         return len(b) >= 3 and b[-1] != b[0] and (b[-1] - b[-2]) / (b[-1] - b[0]) < tol
 
 
-def run_cut_rounds(lp, separate, max_rounds, setup_s=0.0, stop_tol=None, clock=None, on_round=None, after_solve=None):
+def run_cut_rounds(lp, separate, max_rounds, setup_s=0.0, stop_tol=None, clock=None, on_round=None, after_solve=None, stop=None):
     """Drive ``max_rounds`` rounds on ``lp`` (anything with solve / get_values /
     get_objective_value): ``separate(round_no, point) -> dict of counts`` appends cuts to the LP
     between two solves.  ``setup_s`` is added to the first solve's time (model building).
     ``on_round(round_no, log)`` is called after every solve (progress of long runs); ``after_solve()`` the moment a solve
     returns, before the solution vector is extracted (the GPU classes poke the idle device there: sdpcut_wake).
+    ``stop(round_no, log)`` is asked before every round and ends the run when it says True (the dense strategy's time limit,
+    cut_select_qp.py:157).
     -> RoundLog."""
     from timeit import default_timer
     clock = clock or default_timer
@@ -329,6 +331,8 @@ def run_cut_rounds(lp, separate, max_rounds, setup_s=0.0, stop_tol=None, clock=N
         on_round(0, log)
     for round_no in range(1, max_rounds + 1):
         if stop_tol is not None and log.stalled(stop_tol):
+            break
+        if stop is not None and stop(round_no, log):
             break
         t = clock()
         log.counts.append(separate(round_no, point))
