@@ -45,11 +45,12 @@ enum {
     SDPCUT_ENOMEM = -5
 };
 
-/* score flags */
-enum { SDPCUT_EIG = 1, SDPCUT_NN = 2 };
+/* score flags (SDPCUT_SDP: the exact optimum of the small SDP the MLP of SDPCUT_NN estimates, see sdpcut_score) */
+enum { SDPCUT_EIG = 1, SDPCUT_NN = 2, SDPCUT_SDP = 4 };
 
-/* selection strategies, numbering of cut_select_algo (cut_select_qp.py:79-80) */
-enum { SDPCUT_STRAT_FEAS = 1, SDPCUT_STRAT_OPT = 2, SDPCUT_STRAT_COMB = 4 };
+/* selection strategies, numbering of cut_select_algo (cut_select_qp.py:79-80); SDPCUT_STRAT_EXACT is accepted only while
+ * SDPCUT_OPT_EXACT_SDP is on */
+enum { SDPCUT_STRAT_FEAS = 1, SDPCUT_STRAT_OPT = 2, SDPCUT_STRAT_EXACT = 3, SDPCUT_STRAT_COMB = 4 };
 /* Partial ranking for candidate sets sharded over several GPUs (SURVEY.md section 8 e): only
  * the "strong" class of the combined scan (cut_select_qp.py:607-613: obj_improve > 0 and
  * violated), by obj_improve.  Its merged per-shard heads give the global position at which
@@ -120,9 +121,17 @@ enum { SDPCUT_KERNEL_MFMA = 0, SDPCUT_KERNEL_SIMPLE = 1, SDPCUT_KERNEL_VALU = 2 
  * SDPCUT_EINVAL while the option is on, sdpcut_rank* beyond it rank as with the option off.  The sharded entry points
  * (sdpcut_shard_*) fail with SDPCUT_ESTATE while it is on.
  * d_obj is NOT written back: sdpcut_get_scores and sdpcut_gather_scores_device keep returning what the score kernel produced. */
+/* SDPCUT_OPT_EXACT_SDP (default 0): strategy 3 of cut_select_algo -- optimality via the EXACT SDP solution, cut_select_qp.py:584-598
+ * -- is accepted by sdpcut_rank / sdpcut_rank_device (and sdpcut_rank_fetch after them), sdpcut_select_round, sdpcut_select_round_view,
+ * sdpcut_round_view, sdpcut_round_csr and sdpcut_round_csr_begin / _end.  It is strategy 2 with the exact measure of SDPCUT_SDP in
+ * place of the MLP's estimate: all N candidates by that measure descending, ties by ascending candidate index (:601); n_total,
+ * counters as under strategy 2 (nb_positive counts the exact measure), *new_strat = 3.  sdpcut_rank* need a preceding
+ * sdpcut_score(SDPCUT_SDP); the fused calls score it themselves if it is missing, then run the selection that strategy 2 runs on
+ * scores that exist already.  No networks needed.  SDPCUT_OPT_EXACT_HEAD ignores strategy 3; the sharded entry points
+ * (sdpcut_shard_*) refuse it.  With the option off strategy 3 is refused exactly as before (SDPCUT_EINVAL, "strategy must be ..."). */
 enum { SDPCUT_OPT_KERNEL = 1, SDPCUT_OPT_TIMING = 2, SDPCUT_OPT_FUSE_KEYS = 3, SDPCUT_OPT_AUTO_REGIME = 4,
        SDPCUT_OPT_FUSED_TAIL = 5, SDPCUT_OPT_COOP_LAUNCH = 6, SDPCUT_OPT_EIG_KERNEL = 7, SDPCUT_OPT_STREAM_PRIORITY = 8,
-       SDPCUT_OPT_SIDE_STREAMS = 9, SDPCUT_OPT_ONE_LAUNCH = 10, SDPCUT_OPT_PREFILTER = 11, SDPCUT_OPT_EXACT_HEAD = 12 };
+       SDPCUT_OPT_SIDE_STREAMS = 9, SDPCUT_OPT_ONE_LAUNCH = 10, SDPCUT_OPT_PREFILTER = 11, SDPCUT_OPT_EXACT_HEAD = 12, SDPCUT_OPT_EXACT_SDP = 13 };
 
 /* Counters of a handle: SDPCUT_STAT_ROUNDS = fused rounds served (sdpcut_select_round*),
  * SDPCUT_STAT_SELECT_FALLBACKS = rounds whose radix selection declared itself void (a grid barrier
@@ -139,10 +148,14 @@ enum { SDPCUT_OPT_KERNEL = 1, SDPCUT_OPT_TIMING = 2, SDPCUT_OPT_FUSE_KEYS = 3, S
  *   the k-th largest key (-1: none), the floor the producers published (fine bins), the members at or above that bin.  Diagnostics.
  * SDPCUT_STAT_EXACT_HEAD = 1 if the last selection returned an exact head (SDPCUT_OPT_EXACT_HEAD), else 0;
  * SDPCUT_STAT_EXACT_GAVE_UP = selections under the option that returned the ordinary head because a band did not fit;
- * SDPCUT_STAT_EXACT_RETRIES = selections whose first band did not prove itself and that ran again with the widest one. */
+ * SDPCUT_STAT_EXACT_RETRIES = selections whose first band did not prove itself and that ran again with the widest one.
+ * SDPCUT_STAT_SDP_UNCONVERGED = candidates of the last exact-SDP solve (sdpcut_score with SDPCUT_SDP, or sdpcut_sdp_batch) that stopped
+ *   at the iteration cap instead of the gap target; they still returned their certified lower bound and their gap.  Read from the
+ *   device: the call waits for the handle's stream. */
 enum { SDPCUT_STAT_ROUNDS = 1, SDPCUT_STAT_SELECT_FALLBACKS = 2, SDPCUT_STAT_SCORED = 3, SDPCUT_STAT_TIE_SPLITS = 4,
        SDPCUT_STAT_DIRECT_SELECTIONS = 5, SDPCUT_STAT_PF_BIN = 6, SDPCUT_STAT_PF_FLOOR = 7, SDPCUT_STAT_PF_COUNT = 8,
-       SDPCUT_STAT_EXACT_HEAD = 9, SDPCUT_STAT_EXACT_GAVE_UP = 10, SDPCUT_STAT_EXACT_RETRIES = 11 };
+       SDPCUT_STAT_EXACT_HEAD = 9, SDPCUT_STAT_EXACT_GAVE_UP = 10, SDPCUT_STAT_EXACT_RETRIES = 11,
+       SDPCUT_STAT_SDP_UNCONVERGED = 12 };
 int sdpcut_get_stat(sdpcut_handle h, int which, int64_t *value);
 
 /* Maximum sub-problem size (assert dim <= 5, cut_select_qp.py:93) */
@@ -254,15 +267,29 @@ int sdpcut_set_point_device(sdpcut_handle h, const void *d_vars_values);
  *               (r4) Householder tridiagonalisation + Laguerre's iteration, Jacobi for nearly multiple lambda_min (csrc/lmin.h):
  *               as far from the exact eigenvalue as LAPACK is, ~1e-16 on average, <= 2e-15 against LAPACK on matrices of norm 2-4)
  *   SDPCUT_NN : obj_improve[i] = (-S) * max_elem + nn([x | Q_slice]) * max_elem  (a4, a5)
+ *   SDPCUT_SDP: obj_exact[i]   = (-S) * max_elem + p*_lower * max_elem   (cut_select_qp.py:575, :595 -- the MOSEK call of strategy 3,
+ *               :586-598).  p* = min sum_{i<=j} q_ij X_ij  s.t. [[X, x],[x^T, 1]] >= 0, X_ii <= x_i  with x = x_rho and q = Q_slice, the
+ *               MLP's own input.  With Y = X - x x^T, C_ii = q_ii, C_ij = q_ij / 2, d_i = max(x_i - x_i^2, 0):
+ *                   p* = sum q_ij x_i x_j + min{ <C, Y> : Y >= 0, Y_ii <= d_i } = sum q_ij x_i x_j - min{ d^T lam : lam >= 0, C + Diag(lam) >= 0 }
+ *               solved per candidate, one lane each, by a dual barrier method (csrc/exact_sdp.h) that keeps a CERTIFICATE: a dual
+ *               feasible lam (lower bound p*_lower, what the score uses) and a primal feasible Y (upper bound); gap[i] = upper - lower
+ *               >= 0 in the normalised units of p*.  Stops at gap <= 1e-9 max(1, |p*|) or at an iteration cap
+ *               (SDPCUT_STAT_SDP_UNCONVERGED counts the latter).  Rules: an index with d_i = 0 (x_i on or outside its bounds) is
+ *               eliminated -- row and column i of Y are zero, lam_i is reported as 0; if the scaled C is positive semidefinite already
+ *               the answer is lam = 0, Y = 0, p* = sum q_ij x_i x_j.  Needs an instance, candidates and a point -- NO networks; its own
+ *               arrays: eigmin / obj_improve and their scored bits are untouched.  Fetch with sdpcut_get_sdp_scores.
  * Results stay on the device; fetch with sdpcut_get_scores.
  */
 int sdpcut_score(sdpcut_handle h, uint32_t flags);
 int sdpcut_get_scores(sdpcut_handle h, double *eigmin, double *obj_improve); /* either may be NULL */
+/* the exact measure and its duality gap (either may be NULL); SDPCUT_ESTATE unless SDPCUT_SDP has been scored at the current point */
+int sdpcut_get_sdp_scores(sdpcut_handle h, double *obj_exact, double *gap);
 
 /*
  * Rank (replaces the sorts / combined scan, cut_select_qp.py:601-632 and :649-654).
  *   strat 1: violated candidates (lambda_min < -1e-15) by -lambda_min descending
  *   strat 2: all candidates by obj_improve descending
+ *   strat 3: all candidates by the exact measure of SDPCUT_SDP descending (only with SDPCUT_OPT_EXACT_SDP, see there)
  *   strat 4: combined scan with BIG_M, using sel_size; *new_strat = 1 or 4 (:630-631)
  * Ties keep ascending candidate index (Python's stable sort).  Writes the first
  * min(max_out, length) entries: idx_out = global candidate index, score_out = ranking score.
@@ -496,6 +523,16 @@ int sdpcut_eig_batch(sdpcut_handle h, int k, int64_t count, const double *x_rho,
 
 /* Batched raw MLP forward: inputs [count][d_in] -> out [count] (the NNs.so call, batched). */
 int sdpcut_nn_batch(sdpcut_handle h, int k, int64_t count, const double *inputs, double *out);
+
+/*
+ * Batched exact solve of the small SDP above on explicit inputs (the label generator for a user's own networks -- the targets
+ * sdpcut_set_network's MLPs are trained on -- and the window on the certificate): inputs [count][k(k+3)/2] = [x | Q_slice], the
+ * layout of sdpcut_nn_batch.  value [count] = certified LOWER bound on p*, gap [count] = upper - lower; optional (may be NULL):
+ * lam [count][k] the dual point, Y [count][k(k+1)/2] the primal point (upper triangle, row-major), iters [count] iterations taken.
+ * Needs nothing but the handle.
+ */
+int sdpcut_sdp_batch(sdpcut_handle h, int k, int64_t count, const double *inputs, double *value, double *gap, double *lam,
+                     double *Y, int32_t *iters);
 
 /* Timing of the last sdpcut_score / sdpcut_rank (HIP events on the handle's stream).
  * SDPCUT_OPT_TIMING = 1: events around the score kernels only; = 2: also around the ranking.

@@ -15,7 +15,9 @@ LIB_PATH = os.environ.get("SDPCUT_LIB") or os.path.join(HERE, "libsdpcut_hip.so"
 NNS_LIB_PATH = os.path.join(HERE, "libsdpcut_nns.so")
 
 EIG, NN = 1, 2
+SDP = 4                  # exact optimum of the small SDP the MLP estimates (sdpcut_score, include/sdpcut.h)
 STRAT_FEAS, STRAT_OPT, STRAT_COMB = 1, 2, 4
+STRAT_EXACT = 3          # strategy 2 on the exact measure; accepted only with OPT_EXACT_SDP
 PART_STRONG = 104
 PART_COMBALL = 105
 KERNEL_MFMA, KERNEL_SIMPLE, KERNEL_VALU = 0, 1, 2
@@ -23,6 +25,8 @@ OPT_KERNEL, OPT_TIMING, OPT_FUSE_KEYS, OPT_AUTO_REGIME, OPT_FUSED_TAIL, OPT_COOP
 OPT_EXACT_HEAD = 12      # NN-ranked heads ordered and reported by reference-order obj_improve (include/sdpcut.h)
 STAT_ROUNDS, STAT_SELECT_FALLBACKS, STAT_SCORED, STAT_TIE_SPLITS, STAT_DIRECT_SELECTIONS, STAT_PF_BIN, STAT_PF_FLOOR, STAT_PF_COUNT = 1, 2, 3, 4, 5, 6, 7, 8
 STAT_EXACT_HEAD, STAT_EXACT_GAVE_UP, STAT_EXACT_RETRIES = 9, 10, 11
+OPT_EXACT_SDP = 13       # strategy 3 accepted by the ranking and round calls (include/sdpcut.h)
+STAT_SDP_UNCONVERGED = 12
 ROW_LD = 20
 
 _c = ctypes
@@ -69,6 +73,7 @@ SIGNATURES = {
     "sdpcut_set_point_device": [_vp, _vp],
     "sdpcut_score": [_vp, _c.c_uint32],
     "sdpcut_get_scores": [_vp, _dp, _dp],
+    "sdpcut_get_sdp_scores": [_vp, _dp, _dp],
     "sdpcut_rank": [_vp, _c.c_int, _c.c_int64, _c.c_int64, _i64p, _dp, _i64p, _i32p, _i64p],
     "sdpcut_rank_device": [_vp, _c.c_int, _c.c_int64, _c.c_int64, _vp, _vp, _i64p, _i64p, _i32p, _i64p],
     "sdpcut_rank_fetch": [_vp, _c.c_int64, _c.c_int64, _i64p, _dp],
@@ -91,6 +96,7 @@ SIGNATURES = {
     "sdpcut_shard_finish_round_own": [_vp, _c.c_int32, _c.c_int64, _vp, _c.c_int64, _c.c_int32, _c.POINTER(_c.c_void_p), _i64p],
     "sdpcut_eig_batch": [_vp, _c.c_int, _c.c_int64, _dp, _dp, _dp, _dp],
     "sdpcut_nn_batch": [_vp, _c.c_int, _c.c_int64, _dp, _dp],
+    "sdpcut_sdp_batch": [_vp, _c.c_int, _c.c_int64, _dp, _dp, _dp, _dp, _dp, _i32p],
     "sdpcut_last_timing": [_vp, _dp, _c.c_int],
     "sdpcut_mfma_probe": [_vp, _dp, _dp, _dp],
     "sdpcut_tri_preprocess": [_vp, _c.POINTER(_c.c_uint8), _i64p],
@@ -344,6 +350,12 @@ class Scorer(object):
         o = np.empty(self.N) if obj else None
         self._check(self._lib.sdpcut_get_scores(self._h, _ptr(e, _dp), _ptr(o, _dp)))
         return e, o
+
+    def get_sdp_scores(self):
+        """-> (exact optimality measure [N], duality gap [N] in the normalised units of p*) of the last score(SDP)"""
+        o, g = np.empty(self.N), np.empty(self.N)
+        self._check(self._lib.sdpcut_get_sdp_scores(self._h, _ptr(o, _dp), _ptr(g, _dp)))
+        return o, g
 
     def rank(self, strat, sel_size=0, max_out=None):
         """-> (idx int64[w], score float64[w], n_total, new_strat, counters dict)"""
@@ -688,6 +700,24 @@ class Scorer(object):
         out = np.empty(c)
         self._check(self._lib.sdpcut_nn_batch(self._h, int(k), c, _ptr(inputs, _dp), _ptr(out, _dp)))
         return out
+
+    def sdp_batch(self, k, inputs, want_certificate=False):
+        """Exact solve of the small SDP on explicit inputs [count, k(k+3)/2] = [x | Q_slice] (sdpcut_sdp_batch)
+        -> (value = certified lower bound on p* [count], gap [count]); want_certificate=True: a dict with value, gap and the
+        certificate lam [count, k], Y [count, k(k+1)/2] (upper triangle), iters int32 [count]."""
+        inputs = _f64(inputs)
+        c = inputs.shape[0]
+        if inputs.shape != (c, k * (k + 3) // 2):
+            raise ValueError("inputs must be [count, k(k+3)/2]")
+        value, gap = np.empty(c), np.empty(c)
+        lam = Y = iters = None
+        if want_certificate:
+            lam, Y, iters = np.empty((c, k)), np.empty((c, k * (k + 1) // 2)), np.empty(c, dtype=np.int32)
+        self._check(self._lib.sdpcut_sdp_batch(self._h, int(k), c, _ptr(inputs, _dp), _ptr(value, _dp), _ptr(gap, _dp), _ptr(lam, _dp),
+                                               _ptr(Y, _dp), _ptr(iters, _i32p)))
+        if want_certificate:
+            return dict(value=value, gap=gap, lam=lam, Y=Y, iters=iters)
+        return value, gap
 
     def last_timing(self):
         ms = np.zeros(2)

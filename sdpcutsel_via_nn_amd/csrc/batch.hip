@@ -11,13 +11,20 @@ int sdpcut_score(sdpcut_handle h, uint32_t flags)
 {
     if (!h) return SDPCUT_EINVAL;
     SDPCUT_NO_PENDING(h);
-    if (!(flags & (SDPCUT_EIG | SDPCUT_NN)) || (flags & ~(uint32_t)(SDPCUT_EIG | SDPCUT_NN)))
-        return sdpcut_fail(h, SDPCUT_EINVAL, "flags must be a combination of SDPCUT_EIG and SDPCUT_NN");
+    if (!(flags & (SDPCUT_EIG | SDPCUT_NN | SDPCUT_SDP)) || (flags & ~(uint32_t)(SDPCUT_EIG | SDPCUT_NN | SDPCUT_SDP)))
+        return sdpcut_fail(h, SDPCUT_EINVAL, "flags must be a combination of SDPCUT_EIG, SDPCUT_NN and SDPCUT_SDP");
     if (!h->have_point) return sdpcut_fail(h, SDPCUT_ESTATE, "set_point first");
     if (!h->d_eig) return sdpcut_fail(h, SDPCUT_ESTATE, "set_candidates first");
     HIP_TRY(h, hipSetDevice(h->device));
-    int rc = launch_score(h, flags);   // with SDPCUT_OPT_TIMING the dispatches carry ev[0] / ev[1]
-    if (rc) return rc;
+    int rc;
+    if (flags & (SDPCUT_EIG | SDPCUT_NN)) {
+        rc = launch_score(h, flags & (SDPCUT_EIG | SDPCUT_NN));   // with SDPCUT_OPT_TIMING the dispatches carry ev[0] / ev[1]
+        if (rc) return rc;
+    }
+    if (flags & SDPCUT_SDP) {      // its own kernels and arrays (exact_sdp.hip): no network needed, d_eig / d_obj untouched
+        rc = launch_exact_sdp(h);
+        if (rc) return rc;
+    }
     h->scored |= flags;
     return SDPCUT_OK;
 }
@@ -53,6 +60,13 @@ int sdpcut_rank_device(sdpcut_handle h, int strat, int64_t sel_size, int64_t max
 {
     if (!h) return SDPCUT_EINVAL;
     SDPCUT_NO_PENDING(h);
+    if (strat_is_sdp(h, strat)) {      // strategy 2 on the exact measure
+        if (!(h->scored & SDPCUT_SDP)) return sdpcut_fail(h, SDPCUT_ESTATE, "sdpcut_score with the needed flags first");
+        SdpAsObj view(h);
+        const int rc3 = sdpcut_rank_device(h, SDPCUT_STRAT_OPT, sel_size, max_out, d_idx_out, d_score_out, n_written, n_total, new_strat, counters);
+        if (!rc3 && new_strat) *new_strat = SDPCUT_STRAT_EXACT;
+        return rc3;
+    }
     int rc = check_rank_args(h, strat);
     if (rc) return rc;
     if (max_out < 0 || (max_out > 0 && (!d_idx_out || !d_score_out))) return sdpcut_fail(h, SDPCUT_EINVAL, "bad output");

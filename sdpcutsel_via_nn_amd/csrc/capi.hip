@@ -100,6 +100,7 @@ int sdpcut_destroy(sdpcut_handle h)
     free_topk_ws(h);
     free_exact_ws(h);
     free_dense_ws(h);
+    (void)hipFree(h->d_sdp_unconverged);
     (void)hipFree(h->d_tri); (void)hipFree(h->d_tri_dense3);
     if (h->pinned) (void)hipHostFree(h->pinned);
     if (h->point_stage) (void)hipHostFree(h->point_stage);
@@ -154,6 +155,10 @@ int sdpcut_set_option(sdpcut_handle h, int option, int64_t value)
         SDPCUT_NO_PENDING(h);
         h->exact_head = value != 0;
         return SDPCUT_OK;
+    case SDPCUT_OPT_EXACT_SDP:
+        SDPCUT_NO_PENDING(h);
+        h->exact_sdp = value != 0;
+        return SDPCUT_OK;
     case SDPCUT_OPT_SIDE_STREAMS:
         if (value < 0 || value > 2) return sdpcut_fail(h, SDPCUT_EINVAL, "SDPCUT_OPT_SIDE_STREAMS: 0 off, 1 on, 2 measured");
         h->side_streams = (int)value;
@@ -192,6 +197,7 @@ int sdpcut_get_stat(sdpcut_handle h, int which, int64_t *value)
     case SDPCUT_STAT_EXACT_HEAD: *value = h->stat_exact_last; return SDPCUT_OK;
     case SDPCUT_STAT_EXACT_GAVE_UP: *value = h->stat_exact_gave_up; return SDPCUT_OK;
     case SDPCUT_STAT_EXACT_RETRIES: *value = h->stat_exact_retries; return SDPCUT_OK;
+    case SDPCUT_STAT_SDP_UNCONVERGED: return sdp_unconverged(h, value);
     case SDPCUT_STAT_DIRECT_SELECTIONS:
     case SDPCUT_STAT_PF_BIN:
     case SDPCUT_STAT_PF_FLOOR:

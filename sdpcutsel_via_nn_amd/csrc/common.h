@@ -54,6 +54,7 @@ struct NetHost {
 struct PendingRound {
     bool active = false, csr = false, fast_tried = false;
     int strat = 0;
+    bool by_sdp = false;           // strategy 3: the round was begun inside an SdpAsObj view and is ended inside one
     int32_t ld = 0;
     int64_t sel_size = 0, cap = 0, serial = 0;
     int64_t exact_band = 0;        // > 0: the enqueued head is an exact one (SDPCUT_OPT_EXACT_HEAD) through a band of this many entries
@@ -121,6 +122,10 @@ struct sdpcut_ctx {
     int32_t *d_set_orig = nullptr; // [N][5] padded, caller order
     int32_t *d_k = nullptr;        // [N]
     double *d_eig = nullptr, *d_obj = nullptr; // [N] caller order
+    // SDPCUT_SDP (exact_sdp.hip): exact optimality measure and its duality gap, [N] caller order, allocated by the first scoring
+    double *d_sdp = nullptr, *d_sdp_gap = nullptr;
+    unsigned long long *d_sdp_unconverged = nullptr;   // candidates of the last exact solve that stopped at the iteration cap
+    bool exact_sdp = false;        // SDPCUT_OPT_EXACT_SDP: strategy 3 is accepted
     uint32_t scored = 0;
     int64_t last_total = -1;       // length of the last ranking (-1: none), see sdpcut_rank_fetch
 
@@ -274,6 +279,37 @@ void free_exact_ws(sdpcut_ctx *h);
 
 // dense.hip
 void free_dense_ws(sdpcut_ctx *h);
+
+// exact_sdp.hip (SDPCUT_SDP, SDPCUT_OPT_EXACT_SDP)
+int launch_exact_sdp(sdpcut_ctx *h);                 // d_sdp / d_sdp_gap of every candidate at the current point
+int sdp_unconverged(sdpcut_ctx *h, int64_t *value);  // SDPCUT_STAT_SDP_UNCONVERGED (waits for the handle's stream)
+void free_sdp_ws(sdpcut_ctx *h);
+// Strategy 3 = strategy 2 on the exact measure (cut_select_qp.py:584-601: the same list, the same sort, another obj_improve).
+// The non-fused selection reads the handle's optimality array wherever it ranks (rank.hip, topk.hip); for the lifetime of this
+// object that array IS d_sdp and its `scored` bit is SDPCUT_SDP's, and SDPCUT_OPT_EXACT_HEAD -- which re-scores the MLP -- is
+// off.  Nothing scores inside a view: its scope begins after SDPCUT_SDP has been scored.
+struct SdpAsObj {
+    sdpcut_ctx *h;
+    double *obj;
+    uint32_t scored;
+    bool exact_head;
+    explicit SdpAsObj(sdpcut_ctx *ctx) : h(ctx), obj(ctx->d_obj), scored(ctx->scored), exact_head(ctx->exact_head)
+    {
+        h->d_obj = h->d_sdp;
+        h->scored = (scored & SDPCUT_EIG) | ((scored & SDPCUT_SDP) ? (uint32_t)SDPCUT_NN : 0u);
+        h->exact_head = false;
+    }
+    ~SdpAsObj()
+    {
+        h->d_obj = obj;
+        h->scored = scored;
+        h->exact_head = exact_head;
+    }
+    SdpAsObj(const SdpAsObj &) = delete;
+    SdpAsObj &operator=(const SdpAsObj &) = delete;
+};
+// strategy 3 where it is accepted: the option on (else the caller's own refusal of an unknown strategy stands)
+static inline bool strat_is_sdp(const sdpcut_ctx *h, int strat) { return strat == SDPCUT_STRAT_EXACT && h->exact_sdp; }
 
 // tri.hip
 int tri_preprocess(sdpcut_ctx *h, const uint8_t *adjacency, int64_t *n_triples);

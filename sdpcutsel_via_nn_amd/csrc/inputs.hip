@@ -38,6 +38,7 @@ void free_candidates(sdpcut_ctx *h)
         h->bucket[k] = Bucket();
     }
     hipFree(h->d_set_orig); hipFree(h->d_k); hipFree(h->d_eig); hipFree(h->d_obj);
+    free_sdp_ws(h);
     h->d_set_orig = nullptr; h->d_k = nullptr; h->d_eig = nullptr; h->d_obj = nullptr;
     h->N = 0; h->scored = 0; h->last_total = -1;
     h->topk_alt_clean = false;      // (how much of the selection workspace a round's epilogue zeroes depends on the list's length)

@@ -475,6 +475,9 @@ class GpuCutSelectionMixin(object):
     # heads under the NN-ranked strategies (2, 4) ordered and reported by obj_improve in the reference's operation order
     # (SDPCUT_OPT_EXACT_HEAD, include/sdpcut.h); a subclass or make_dropin_classes(..., exact_heads=True) switches it on
     _gpu_exact_heads = False
+    # strategies 3 (optimality via the exact SDP solution) and -1 (figure 8: estimated against exact measure) on the device
+    # (SDPCUT_OPT_EXACT_SDP, SDPCUT_SDP; exact_sdp.py is the numpy twin of the solver); off: both are refused as before
+    _gpu_exact_sdp = False
 
     # ------------------------------------------------------------------ a11 loader
     def _load_neural_nets(self):
@@ -503,6 +506,8 @@ class GpuCutSelectionMixin(object):
             sc.set_network(d, widths, params)
         if self._gpu_exact_heads:
             sc.set_option(_capi.OPT_EXACT_HEAD, 1)
+        if self._gpu_exact_sdp:
+            sc.set_option(_capi.OPT_EXACT_SDP, 1)
         return sc
 
     def _gpu_bind(self):
@@ -583,9 +588,9 @@ class GpuCutSelectionMixin(object):
 
     # ------------------------------------------------------------------ a7-a9 selection
     def _sel_eigcut_by_ordering_on_measure(self, strat, vars_values, cut_round, sel_size=0):
-        """Strategies 1 (feasibility), 2 (optimality via MLP), 4 (combined), 5 (random);
-        same returns as cut_select_qp.py:543-703.  Strategies 3 / -1 need an exact SDP
-        solver per candidate and are out of scope."""
+        """Strategies 1 (feasibility), 2 (optimality via MLP), 4 (combined), 5 (random); same returns as
+        cut_select_qp.py:543-703.  With ``_gpu_exact_sdp`` also 3 (optimality via the exact SDP solution: the layout of strategy 2)
+        and -1 (figure 8: ``(rank_list, overlap, std_dev_exact, this_round_cuts)`` of :660-702)."""
         if strat == 5:
             # random order, in place, like :634-637; the device twin of the old order is dropped
             agg = self._agg_list
@@ -597,12 +602,14 @@ class GpuCutSelectionMixin(object):
                 np.random.shuffle(agg)
             getattr(self, "_gpu_bindings", {}).pop(id(agg), None)
             return agg
-        if strat not in (1, 2, 4):
-            raise NotImplementedError("exact-SDP strategies (3, -1) are not part of the GPU path")
+        if strat not in (1, 2, 4) and not (self._gpu_exact_sdp and strat in (3, -1)):
+            raise NotImplementedError("exact-SDP strategies (3, -1) are not part of the GPU path unless exact_sdp is switched on")
         b = self._gpu_bind()
         N = len(self._agg_list)
         sel_size = min(sel_size, N)
-        flags = {1: _capi.EIG, 2: _capi.NN, 4: _capi.EIG | _capi.NN}[strat]
+        if strat == -1:
+            return self._gpu_figure8(b, vars_values, cut_round, sel_size)
+        flags = {1: _capi.EIG, 2: _capi.NN, 3: _capi.SDP, 4: _capi.EIG | _capi.NN}[strat]
         if N == 0:
             return []       # strat 4 included: sel_size is clamped to 0 and the reference falls through
         # head fetched eagerly: what the loop can consume (sel_size is only passed for strat 4;
@@ -658,6 +665,21 @@ class GpuCutSelectionMixin(object):
             # through to `return rank_list` (cut_select_qp.py:629-632, 703)
             return rl if sel_size == 0 else (new_strat, rl)
         return rl
+
+    def _gpu_figure8(self, b, vars_values, cut_round, sel_size):
+        """Strategy -1 (cut_select_qp.py:660-702): both measures of every candidate from the device -- the MLP's estimate and the
+        exact SDP optimum, ``p* max_elem - S max_elem`` -- and the reference's comparison of the two orderings in numpy
+        (exact_sdp.figure8).  -> (rank_list by the estimated measure, overlap / sel_size, std_dev_exact, this_round_cuts)."""
+        from . import exact_sdp
+        vv = self._gpu_point(b, vars_values, _capi.NN | _capi.SDP, cut_round)
+        self._gpu_last = None
+        _, nn = b.scorer.get_scores(eig=False)
+        exact, _ = b.scorer.get_sdp_scores()
+        order, overlap, std_dev_exact, rows = exact_sdp.figure8(nn, exact, cut_round, sel_size)
+        b.rank_serial += 1
+        # the whole list is on the host already: the rank list never goes back to the device (strategy 2's order, :688)
+        rl = RankList(self, b, 2, nn.shape[0], vv, order + b.scorer.base, nn[order], strat=2, sel_size=sel_size)
+        return rl, overlap, std_dev_exact, rows
 
     # ------------------------------------------------------------------ a10 generation
     def _gen_eigcuts_selected(self, strat, sel_size, rank_list, strong_only=False, vars_values=None):
@@ -933,9 +955,10 @@ class CutSolver(GpuCutSelectionMixin):
     _SDP_CUTS_PER_ROUND_MAX = 5000
     _THRES_MAX_SUBS = 4 * (10 ** 6)
 
-    def __init__(self, device=0, exact_heads=False):
+    def __init__(self, device=0, exact_heads=False, exact_sdp=False):
         self._gpu_device = device
         self._gpu_exact_heads = bool(exact_heads)
+        self._gpu_exact_sdp = bool(exact_sdp)
         self._dim = 0
         self._nb_vars = 0
         self._nb_lifted = 0
@@ -965,20 +988,25 @@ class CutSolver(GpuCutSelectionMixin):
     _CONVERGENCE_TOL = 10 ** (-3)         # cut_select_qp.py:29
 
     def cut_select_algo(self, filename, dim, sel_size, strat=2, nb_rounds_cuts=20, term_on=False,
-                        triangle_on=False, strong_only=False, max_subs=_THRES_MAX_SUBS, on_round=None):
+                        triangle_on=False, strong_only=False, max_subs=_THRES_MAX_SUBS, on_round=None, plots=False, sol=0):
         """Cutting-plane rounds on a BoxQP ``.in`` file, same arguments and default return tuple as
         the reference's entry point (cut_select_qp.py:73-221), with HiGHS as LP solver, the native
         cover enumeration and the GPU selection / generation / triangle separation in between.
         ``max_subs=None`` lifts the reference's 4e6 candidate guard (:117-120); ``on_round(r, log)`` is
         called after every LP solve (progress of long runs).  Strategy 0 adds
         the fully dense eigen-cuts of :meth:`_gen_dense_eigcuts` instead of a selection (the cover is still enumerated: the tuple
-        reports its size); exact-SDP strategies and chordal extensions are out of scope.
+        reports its size); chordal extensions are out of scope.  ``CutSolver(exact_sdp=True)`` also takes strategy 3
+        (optimality via the exact SDP solution) and -1 (figure 8); with ``strat=-1, plots=True`` the return is the reference's
+        ``(gap_closed_percent, rounds_stats, round_std_devs, rounds_all_cuts)`` with the gap closed measured against ``sol``
+        (:209-215).  ``plots`` with another strategy is out of scope.
         -> (bound per solve, total s, round s, separation s, PSD cuts per round, triangle cuts per
         round, number of candidates)."""
         from timeit import default_timer as clock
         from . import harness
-        if strat not in (0, 1, 2, 4, 5):
-            raise AssertionError("strategies on the GPU path: 0 dense, 1 feasibility, 2 optimality, 4 combined, 5 random")
+        if strat not in (0, 1, 2, 4, 5) and not (self._gpu_exact_sdp and strat in (3, -1)):
+            raise AssertionError("strategies on the GPU path: 0 dense, 1 feasibility, 2 optimality, 4 combined, 5 random "
+                                 "(3 exact optimality and -1 figure 8 with exact_sdp=True)")
+        assert not plots or strat == -1, "plots=True returns the figure-8 tuple: strat=-1 only"
         assert 0 < sel_size, "The selection size must be a % or number (of cuts) >0!"
         assert dim <= 5, "Keep SDP vertex cover low-dimensional (<=5)!"
         t_start = clock()
@@ -986,7 +1014,7 @@ class CutSolver(GpuCutSelectionMixin):
         self._dim = dim
         self._nb_vars, self._nb_lifted, self._Q_arr, self._Q_adj = (inst[k] for k in ("nb_vars", "nb_lifted", "Q_arr", "adj"))
         self._gpu_nets = {}
-        if strat in (2, 4):
+        if strat in (2, 4, -1):      # :103
             self._load_neural_nets()
         # the cover is enumerated on the device, straight into the scorer's candidate list
         sc = self._gpu_new_scorer()
@@ -1003,6 +1031,7 @@ class CutSolver(GpuCutSelectionMixin):
         if triangle_on:
             self._preprocess_triangle_ineq()
         state = {"strat": strat}
+        rounds_stats, round_std_devs, rounds_all_cuts = [], [], []      # figure 8 (:144)
         if strat == 0:      # the cover's scorer already holds the instance
             self._gpu_dense_sc, self._gpu_dense_key = sc, (self._nb_vars, id(self._Q_arr))
 
@@ -1011,9 +1040,14 @@ class CutSolver(GpuCutSelectionMixin):
             if cur == 0:
                 sdp = self._gen_dense_eigcuts(vars_values=point)
                 return {"sdp": sdp, "tri": self._separate_and_add_triangle(sel_size, point) if triangle_on else 0}
-            picked = self._sel_eigcut_by_ordering_on_measure(cur, point, round_no, **({"sel_size": quota} if cur == 4 else {}))
+            picked = self._sel_eigcut_by_ordering_on_measure(cur, point, round_no, **({"sel_size": quota} if cur in (4, -1) else {}))
             if cur == 4 and isinstance(picked, tuple):
                 state["strat"], picked = picked       # the switch takes effect next round (:181 vs :188)
+            if cur == -1:                             # :173-179
+                picked, round_stats, round_std_dev, round_all_cuts = picked
+                rounds_all_cuts.extend(round_all_cuts)
+                rounds_stats.append(round_stats)
+                round_std_devs.append(round_std_dev)
             sdp = self._gen_eigcuts_selected(cur, quota, picked, strong_only=strong_only, vars_values=point)
             tri = self._separate_and_add_triangle(sel_size, point) if triangle_on else 0
             return {"sdp": sdp, "tri": tri}
@@ -1024,6 +1058,9 @@ class CutSolver(GpuCutSelectionMixin):
                                      # dense cuts: past the 4th round, stop once the rounds have taken 1000 s (:157)
                                      stop=(lambda r, lg: r > 4 and sum(lg.solve_s) + sum(lg.separation_s) > 1000) if strat == 0 and term_on else None)
         sep = [t_model] + log.separation_s
+        if plots:       # :209-215 (curr_obj_vals of the reference = log.bounds)
+            gap_closed_percent = [0] + [(-v + log.bounds[0]) / (sol + log.bounds[0]) for v in log.bounds[1:]]
+            return gap_closed_percent, rounds_stats, round_std_devs, rounds_all_cuts
         return ([-v for v in log.bounds], clock() - t_start, [a + b for a, b in zip(log.solve_s, [0.0] + log.separation_s)],
                 sep, [0] + log.column("sdp"), log.column("tri"), n_cand)
 
@@ -1070,8 +1107,8 @@ class CutSolverQCQP(CutSolver):
         of both covers and :meth:`select_and_generate_round` between two solves.
         -> (objective value per solve, sel_size, PSD cuts per round, optimality cuts per round)."""
         from . import harness
-        if strat not in (1, 2, 4, 5):
-            raise AssertionError("strategies on the GPU path: 1 feasibility, 2 optimality, 4 combined, 5 random")
+        if strat not in (1, 2, 4, 5) and not (self._gpu_exact_sdp and strat == 3):      # cut_select_qcqp.py:26 allows 3
+            raise AssertionError("strategies on the GPU path: 1 feasibility, 2 optimality, 4 combined, 5 random (3 exact optimality with exact_sdp=True)")
         assert 0 < sel_size, "The selection size must be a % or number (of cuts) >0!"
         assert dim <= 5, "Keep SDP vertex cover low-dimensional (<=5)!"
         inst = harness.parse_osil(filename)
@@ -1105,7 +1142,7 @@ class CutSolverQCQP(CutSolver):
         return log.bounds, quota, [0] + log.column("sdp"), [0] + opt + [0] * (nb_rounds_cuts - len(opt))
 
 
-def make_dropin_classes(cut_select_qp, cut_select_qcqp=None, exact_heads=False):
+def make_dropin_classes(cut_select_qp, cut_select_qcqp=None, exact_heads=False, exact_sdp=False):
     """Compose the GPU mixin with the reference's own classes (modules passed in, nothing is
     imported here) -> (GpuCutSolver, GpuCutSolverQCQP or None).
 
@@ -1119,9 +1156,10 @@ def make_dropin_classes(cut_select_qp, cut_select_qcqp=None, exact_heads=False):
         MRO: GpuCutSolverQCQP, CutSolverQCQP, GpuCutSolver, GpuCutSelectionMixin, CutSolver, object
 
     exact_heads: the classes' ``_gpu_exact_heads`` (SDPCUT_OPT_EXACT_HEAD on every handle they create).
+    exact_sdp: the classes' ``_gpu_exact_sdp`` (strategies 3 and -1 on the device instead of a NotImplementedError).
     """
     qp = type("GpuCutSolver", (GpuCutSelectionMixin, cut_select_qp.CutSolver),
-              {"__doc__": "CutSolver with the hot path on the GPU", "_gpu_exact_heads": bool(exact_heads)})
+              {"__doc__": "CutSolver with the hot path on the GPU", "_gpu_exact_heads": bool(exact_heads), "_gpu_exact_sdp": bool(exact_sdp)})
     qcqp = None
     if cut_select_qcqp is not None:
         qcqp = type("GpuCutSolverQCQP", (cut_select_qcqp.CutSolverQCQP, qp), {"__doc__": "CutSolverQCQP with the hot path on the GPU"})

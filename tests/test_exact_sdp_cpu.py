@@ -1,0 +1,308 @@
+"""Exact-SDP optimality measure (strategies 3 and -1) without a device: the numpy twin of the kernel's solver
+(sdpcutsel_via_nn_amd/exact_sdp.py) against the published MOSEK column, its certificates, the degenerate rules, the plain-C++
+solver body the kernels are built from (csrc/exact_sdp.h, compiled for the host) against the twin, and the opt-in plumbing.
+
+Measured by these tests (python -m pytest tests/test_exact_sdp_cpu.py -s prints them):
+  worst |twin - published exact_measure| on the 1051 candidates of spar020-100-1, round 1: 4.32e-6 absolute, 3.0e-6 relative
+  largest iteration count of the twin over all inputs of this file: 69 (ITER_CAP = 138)
+  worst certificate violation of the twin in units of eps (||C||_F + ||lam||_inf): 0.85 (SLACK_UNITS = 3.4)
+"""
+import ctypes
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import GOLDEN, ROOT, golden_nn
+from sdpcutsel_via_nn_amd import exact_sdp
+
+CSRC = os.path.join(ROOT, "sdpcutsel_via_nn_amd", "csrc")
+TAG = "spar020_100_1_d3"
+PUBLISHED_BOUND = 1e-5      # |delta| <= 1e-5 max(1, |exact_measure|): the column carries MOSEK's own tolerance (4.3e-6 measured)
+
+
+def cover_inputs(z, tag, point):
+    """{k: (candidate ids, inputs [x | Q_slice], negSM, max_elem)} of a golden cover at a golden LP point (cut_select_qp.py:529-540, :575)"""
+    n, Q, S, ks, vv = int(z[tag + "_nb_vars"]), z[tag + "_Q_arr"], z[tag + "_set_inds"], z[tag + "_k"], z[tag + "_%s_vars" % point]
+    L = n * (n + 1) // 2
+    out = {}
+    for k in np.unique(ks):
+        k = int(k)
+        m = np.flatnonzero(ks == k)
+        s = S[m, :k].astype(np.int64)
+        ia, ib = np.triu_indices(k)
+        pos = n * s[:, ia] - s[:, ia] * (s[:, ia] + 1) // 2 + s[:, ib]
+        q = Q[pos]
+        me = k * np.abs(q).max(axis=1)
+        me = np.where(me == 0, 1.0, me)
+        qs = q / me[:, None]
+        out[k] = (m, np.hstack([vv[L + s], qs]), -(qs * vv[pos]).sum(axis=1) * me, me)
+    return out
+
+
+def published():
+    csv = np.loadtxt(os.path.join(GOLDEN, "fig8_round1.csv"), delimiter=",", skiprows=1)
+    ids = csv[:, 1].astype(int)
+    exact, sel = np.zeros(ids.shape[0]), np.zeros(ids.shape[0], dtype=bool)
+    exact[ids], sel[ids] = csv[:, 5], csv[:, 3] > 0
+    return exact, sel
+
+
+@pytest.fixture(scope="module")
+def fig8_twin(golden_boxqp):
+    co = cover_inputs(golden_boxqp, TAG, "mck")
+    N = golden_boxqp[TAG + "_k"].shape[0]
+    meas, iters, conv = np.zeros(N), np.zeros(N, dtype=int), np.zeros(N, dtype=bool)
+    for k, (m, inp, negSM, me) in co.items():
+        r = exact_sdp.solve(k, inp)
+        meas[m], iters[m], conv[m] = negSM + r["value"] * me, r["iters"], r["converged"]
+    return meas, iters, conv
+
+
+@pytest.fixture(scope="module")
+def nn_twin():
+    """the twin on the first 512 inputs of each tests/golden/nn_k*.npz"""
+    out = {}
+    for k in (2, 3, 4, 5):
+        inp = golden_nn(k)["inputs"][:512]
+        out[k] = (inp, exact_sdp.solve(k, inp))
+    return out
+
+
+def test_twin_against_published_column(fig8_twin):
+    meas, iters, conv = fig8_twin
+    exact, sel = published()
+    assert meas.shape == exact.shape == (1051,)
+    diff = np.abs(meas - exact)
+    rel = diff / np.maximum(1.0, np.abs(exact))
+    print("worst |twin - published|: %.3e absolute, %.3e relative, median %.3e; iterations max %d" % (diff.max(), rel.max(), np.median(diff), iters.max()))
+    assert conv.all()
+    assert rel.max() <= PUBLISHED_BOUND
+    top = np.argsort(-meas, kind="stable")[:100]
+    assert sel.sum() == 100 and set(top.tolist()) == set(np.flatnonzero(sel).tolist())
+
+
+@pytest.mark.parametrize("k", [2, 3, 4, 5])
+def test_twin_certificates(nn_twin, k):
+    inp, r = nn_twin[k]
+    x, C, xqx = exact_sdp.unpack(k, inp)
+    d = np.maximum(x - x * x, 0.0)
+    c = exact_sdp.certificate_check(C, d, r["lam"], r["Y"])
+    print("k = %d: iterations max %d, worst violation %.3f eps (||C||_F + ||lam||_inf), worst gap %.3e" % (k, r["iters"].max(), c["worst_units"], r["gap"].max()))
+    assert c["ok"].all()
+    assert r["converged"].all()
+    assert np.all(r["gap"] >= 0) and np.all(r["value"] <= r["upper"])
+    assert np.all(r["gap"] <= exact_sdp.GAP_TOL * np.maximum(1.0, np.abs(r["value"])))
+    # the certificate IS the proof: the value it implies is the value returned
+    ia, ib = np.triu_indices(k)
+    Ym = np.zeros((inp.shape[0], k, k))
+    Ym[:, ia, ib] = r["Y"]
+    Ym[:, ib, ia] = r["Y"]
+    assert np.abs(xqx - (d * r["lam"]).sum(axis=1) - r["value"]).max() <= 1e-14
+    assert np.abs(xqx + (C * Ym).sum(axis=(1, 2)) - r["upper"]).max() <= 1e-14
+
+
+def test_constants_rest_on_what_the_twin_shows(fig8_twin, nn_twin):
+    """ITER_CAP is twice the largest iteration count, SLACK_UNITS four times the worst certificate violation over this file's inputs."""
+    worst_it = max(int(fig8_twin[1].max()), max(int(r["iters"].max()) for _, r in nn_twin.values()))
+    worst_units = 0.0
+    for k, (inp, r) in nn_twin.items():
+        x, C, _ = exact_sdp.unpack(k, inp)
+        worst_units = max(worst_units, exact_sdp.certificate_check(C, np.maximum(x - x * x, 0.0), r["lam"], r["Y"])["worst_units"])
+    print("largest iteration count %d (ITER_CAP %d); worst violation %.3f units (SLACK_UNITS %.2f)" % (worst_it, exact_sdp.ITER_CAP, worst_units, exact_sdp.SLACK_UNITS))
+    assert exact_sdp.ITER_CAP == 2 * worst_it
+    assert 4 * worst_units <= exact_sdp.SLACK_UNITS <= 4 * worst_units + 0.1
+
+
+def _one(k, x, q):
+    return exact_sdp.solve(k, np.array([list(x) + list(q)], dtype=np.float64))
+
+
+def test_degenerate_rules():
+    q3 = [-0.3, 0.2, -0.1, 0.1, 0.3, -0.25]
+    # x_i in {0, 1} and x_i = -1e-9: d_i = 0, the index is eliminated (lam_i = 0, row i of Y zero) -- the rest is the 2-variable problem
+    for x0 in (0.0, 1.0, -1e-9):
+        r = _one(3, [x0, 0.4, 0.7], q3)
+        assert r["converged"][0] and r["lam"][0, 0] == 0.0 and np.all(r["Y"][0, :3] == 0.0)
+        sub = _one(2, [0.4, 0.7], [q3[3], q3[4], q3[5]])
+        xqx_rest = q3[0] * x0 * x0 + q3[1] * x0 * 0.4 + q3[2] * x0 * 0.7
+        assert abs(r["value"][0] - (sub["value"][0] + xqx_rest)) <= 2 * exact_sdp.GAP_TOL
+        x, C, _ = exact_sdp.unpack(3, np.array([[x0, 0.4, 0.7] + q3]))
+        assert exact_sdp.certificate_check(C, np.maximum(x - x * x, 0.0), r["lam"], r["Y"])["ok"].all()
+    # C positive semidefinite: lam = 0, p* = sum q_ij x_i x_j exactly, no iteration
+    qpsd = [0.3, 0.2, 0.25]          # [[0.3, 0.1], [0.1, 0.25]]
+    r = _one(2, [0.3, 0.6], qpsd)
+    assert r["iters"][0] == 0 and r["gap"][0] == 0.0 and np.all(r["lam"] == 0.0) and np.all(r["Y"] == 0.0)
+    assert r["value"][0] == 0.3 * 0.09 + 0.2 * 0.18 + 0.25 * 0.36
+    # C = 0
+    r = _one(4, [0.2, 0.5, 0.6, 0.9], [0.0] * 10)
+    assert r["iters"][0] == 0 and r["value"][0] == 0.0 and r["gap"][0] == 0.0
+    # all d = 0: p* = sum q_ij x_i x_j whatever C is
+    r = _one(3, [0.0, 1.0, 1.0], q3)
+    assert r["iters"][0] == 0 and r["gap"][0] == 0.0 and r["value"][0] == q3[3] + q3[4] + q3[5]
+    # a tiny positive d_i is NOT eliminated and still converges to a certificate
+    r = _one(2, [1e-13, 0.5], [-0.5, 0.5, -0.25])
+    x, C, _ = exact_sdp.unpack(2, np.array([[1e-13, 0.5, -0.5, 0.5, -0.25]]))
+    assert r["converged"][0] and exact_sdp.certificate_check(C, np.maximum(x - x * x, 0.0), r["lam"], r["Y"])["ok"].all()
+
+
+def test_iteration_cap_returns_a_certificate():
+    """a candidate stopped at the cap says so and still returns a bound the certificate check accepts"""
+    inp = golden_nn(3)["inputs"][:64]
+    r = exact_sdp.solve(3, inp, iter_cap=5)
+    hit = ~r["converged"]
+    assert hit.any() and np.all(r["iters"][hit] == 5) and np.all(r["gap"][hit] > exact_sdp.GAP_TOL)
+    x, C, _ = exact_sdp.unpack(3, inp)
+    assert exact_sdp.certificate_check(C, np.maximum(x - x * x, 0.0), r["lam"], r["Y"])["ok"].all()
+    full = exact_sdp.solve(3, inp)
+    assert np.all(r["value"] <= full["upper"] + 1e-12) and np.all(full["value"] <= r["upper"] + 1e-12)
+
+
+def test_certificate_check_refutes_a_wrong_bound():
+    inp = golden_nn(3)["inputs"][:64]
+    r = exact_sdp.solve(3, inp)
+    x, C, _ = exact_sdp.unpack(3, inp)
+    d = np.maximum(x - x * x, 0.0)
+    moved = r["iters"] > 0
+    assert moved.any()
+    assert not exact_sdp.certificate_check(C, d, 0.9 * r["lam"], r["Y"])["ok"][moved].any()       # no longer dual feasible
+    assert not exact_sdp.certificate_check(C, d, r["lam"], 1.1 * r["Y"])["ok"][moved].any()       # Y_ii above d_i
+
+
+def test_figure8_restatement():
+    rng = np.random.default_rng(3)
+    nn, ex = rng.normal(size=50), rng.normal(size=50)
+    nn[7] = nn[3]                      # a tie keeps candidate order (stable sort, cut_select_qp.py:688)
+    order, overlap, std, rows = exact_sdp.figure8(nn, ex, 2, 10)
+    rank_list = sorted([(i, nn[i]) for i in range(50)], key=lambda e: e[1], reverse=True)
+    exact_list = sorted([(i, ex[i]) for i in range(50)], key=lambda e: e[1], reverse=True)
+    both, ref_rows = 0, []
+    for estim_idx, cut in enumerate(rank_list):                                                  # :693-701
+        exact_idx = [e[0] for e in exact_list].index(cut[0])
+        a, b = (1 if estim_idx < 10 else 0), (1 if exact_idx < 10 else 0)
+        ref_rows.append([2, cut[0], a, b, cut[1], exact_list[exact_idx][1]])
+        both += a and b
+    assert list(order) == [e[0] for e in rank_list] and rows == ref_rows and overlap == both / 10
+    assert std == np.std(np.array([e[1] for e in exact_list[:10]]))
+
+
+# ---------------------------------------------------------------- the kernels' solver body, compiled for the host
+HOST_SRC = r"""
+#include "exact_sdp.h"
+template <int K> static void run(long count, const double *in, double *value, double *gap, double *lam, double *Y, int *iters, int *conv)
+{
+    constexpr int M = K * (K + 1) / 2;
+    for (long c = 0; c < count; ++c) {
+        double x[K], q[M];
+        for (int i = 0; i < K; ++i) x[i] = in[c * (K + M) + i];
+        for (int m = 0; m < M; ++m) q[m] = in[c * (K + M) + K + m];
+        const EsdpOut o = {value + c, gap + c, lam + c * K, Y + c * M, iters + c, 0.0, 1.0};
+        conv[c] = esdp_solve<K>(x, q, ESDP_ITER_CAP, o) ? 1 : 0;
+    }
+}
+extern "C" int esdp_host(int k, long count, const double *in, double *value, double *gap, double *lam, double *Y, int *iters, int *conv)
+{
+    switch (k) {
+    case 2: run<2>(count, in, value, gap, lam, Y, iters, conv); return 0;
+    case 3: run<3>(count, in, value, gap, lam, Y, iters, conv); return 0;
+    case 4: run<4>(count, in, value, gap, lam, Y, iters, conv); return 0;
+    case 5: run<5>(count, in, value, gap, lam, Y, iters, conv); return 0;
+    }
+    return -1;
+}
+"""
+
+
+@pytest.fixture(scope="module")
+def host_solver(tmp_path_factory):
+    d = tmp_path_factory.mktemp("exact_sdp")
+    src, so = d / "esdp_host.cpp", d / "libesdp_host.so"
+    src.write_text(HOST_SRC)
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-shared", "-fPIC", "-I", CSRC, "-o", str(so), str(src)])
+    lib = ctypes.CDLL(str(so))
+    dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)
+    lib.esdp_host.argtypes = [ctypes.c_int, ctypes.c_long, dp, dp, dp, dp, dp, ip, ip]
+
+    def solve(k, inputs):
+        inputs = np.ascontiguousarray(inputs, dtype=np.float64)
+        c, m = inputs.shape[0], k * (k + 1) // 2
+        out = dict(value=np.empty(c), gap=np.empty(c), lam=np.empty((c, k)), Y=np.empty((c, m)), iters=np.empty(c, dtype=np.int32),
+                   converged=np.empty(c, dtype=np.int32))
+        p = lambda a, t: a.ctypes.data_as(t)      # noqa: E731
+        assert lib.esdp_host(k, c, p(inputs, dp), p(out["value"], dp), p(out["gap"], dp), p(out["lam"], dp), p(out["Y"], dp),
+                             p(out["iters"], ip), p(out["converged"], ip)) == 0
+        return out
+    return solve
+
+
+@pytest.mark.parametrize("k", [2, 3, 4, 5])
+def test_header_solver_is_the_twin(host_solver, nn_twin, k):
+    """csrc/exact_sdp.h on the host: same iteration counts as the twin (same method, rounding apart), values within the two gaps,
+    and its own certificates pass the independent check"""
+    inp, t = nn_twin[k]
+    r = host_solver(k, inp)
+    assert r["converged"].all()
+    assert np.abs(r["iters"] - t["iters"]).max() <= 1 and np.mean(r["iters"] == t["iters"]) >= 0.99
+    assert np.all(np.abs(r["value"] - t["value"]) <= r["gap"] + t["gap"] + 1e-15)
+    x, C, _ = exact_sdp.unpack(k, inp)
+    assert exact_sdp.certificate_check(C, np.maximum(x - x * x, 0.0), r["lam"], r["Y"])["ok"].all()
+
+
+def test_header_degenerate_rules(host_solver):
+    q3 = [-0.3, 0.2, -0.1, 0.1, 0.3, -0.25]
+    cases = np.array([[0.0, 0.4, 0.7] + q3, [1.0, 0.4, 0.7] + q3, [-1e-9, 0.4, 0.7] + q3, [0.0, 1.0, 1.0] + q3, [0.2, 0.5, 0.6] + [0.0] * 6])
+    r, t = host_solver(3, cases), exact_sdp.solve(3, cases)
+    assert np.array_equal(r["iters"] == 0, t["iters"] == 0) and np.array_equal(r["iters"][3:], [0, 0])
+    assert np.all(np.abs(r["value"] - t["value"]) <= r["gap"] + t["gap"] + 1e-15)
+    assert np.all(r["lam"][:3, 0] == 0.0) and np.all(r["Y"][:3, :3] == 0.0)
+
+
+def test_header_and_twin_share_their_constants():
+    hdr = open(os.path.join(CSRC, "exact_sdp.h")).read()
+    val = lambda name: float(re.search(r"#define %s\s+(\S+)" % name, hdr).group(1))      # noqa: E731
+    assert val("ESDP_GAP_TOL") == exact_sdp.GAP_TOL and val("ESDP_MU_SHRINK") == exact_sdp.MU_SHRINK
+    assert val("ESDP_DELTA_CENTRED") == exact_sdp.DELTA_CENTRED and val("ESDP_FORCE_DIAG") == exact_sdp.FORCE_DIAG
+    assert val("ESDP_MAX_HALVINGS") == exact_sdp.MAX_HALVINGS and val("ESDP_ITER_CAP") == exact_sdp.ITER_CAP
+
+
+# ---------------------------------------------------------------- opt-in plumbing without a device
+def test_refusals_stay_without_the_option():
+    from sdpcutsel_via_nn_amd import cut_solver
+    cs = cut_solver.CutSolver()
+    assert cs._gpu_exact_sdp is False
+    path = os.path.join(GOLDEN, "instances", "spar020-100-1.in")
+    for strat in (3, -1):
+        with pytest.raises(AssertionError):
+            cs.cut_select_algo(path, 3, 0.1, strat=strat, nb_rounds_cuts=1)
+        with pytest.raises(NotImplementedError):
+            cs._sel_eigcut_by_ordering_on_measure(strat, np.zeros(5), 1)
+    with pytest.raises(AssertionError):
+        cut_solver.CutSolverQCQP().cut_select_algo(os.path.join(GOLDEN, "instances", "q_20_4_25_1.osil"), 3, strat=3)
+
+
+class _DeviceReached(Exception):
+    pass
+
+
+def test_option_passes_the_argument_checks(monkeypatch):
+    """CutSolver(exact_sdp=True): strategies 3 and -1 get through the argument checks, up to the first device call"""
+    from sdpcutsel_via_nn_amd import cut_solver
+
+    def no_device(self):
+        assert self._gpu_exact_sdp
+        raise _DeviceReached()
+    monkeypatch.setattr(cut_solver.GpuCutSelectionMixin, "_gpu_new_scorer", no_device)
+    path = os.path.join(GOLDEN, "instances", "spar020-100-1.in")
+    for strat, kw in ((3, {}), (-1, {}), (-1, dict(plots=True, sol=706.5))):
+        with pytest.raises(_DeviceReached):
+            cut_solver.CutSolver(exact_sdp=True).cut_select_algo(path, 3, 0.1, strat=strat, nb_rounds_cuts=1, **kw)
+    with pytest.raises(AssertionError):      # plots returns the figure-8 tuple only
+        cut_solver.CutSolver(exact_sdp=True).cut_select_algo(path, 3, 0.1, strat=3, nb_rounds_cuts=1, plots=True)
+    with pytest.raises(AssertionError):      # the other refusals stand
+        cut_solver.CutSolver(exact_sdp=True).cut_select_algo(path, 3, 0.1, strat=6, nb_rounds_cuts=1)
+    with pytest.raises(_DeviceReached):
+        cut_solver.CutSolverQCQP(exact_sdp=True).cut_select_algo(os.path.join(GOLDEN, "instances", "q_20_4_25_1.osil"), 3, strat=3)
+    qp, _ = cut_solver.make_dropin_classes(type("M", (), {"CutSolver": type("CutSolver", (), {})}), exact_sdp=True)
+    assert qp._gpu_exact_sdp is True and cut_solver.make_dropin_classes(type("M", (), {"CutSolver": type("CutSolver", (), {})}))[0]._gpu_exact_sdp is False
