@@ -534,6 +534,34 @@ int sdpcut_nn_batch(sdpcut_handle h, int k, int64_t count, const double *inputs,
 int sdpcut_sdp_batch(sdpcut_handle h, int k, int64_t count, const double *inputs, double *value, double *gap, double *lam,
                      double *Y, int32_t *iters);
 
+/*
+ * Training a network of one's own (the step between sdpcut_sdp_batch's labels and sdpcut_set_network): loss and gradient of a
+ * tansig MLP over a data set resident on the device.  The optimiser runs on the host (networks.py: train -- scaled conjugate
+ * gradient) and calls sdpcut_train_loss_grad twice per iteration.
+ *
+ * sdpcut_train_set_data copies `count` samples of size k to the device: inputs [count][k(k+3)/2] = [x | Q_slice], the layout of
+ * sdpcut_nn_batch, and targets [count] (e.g. the values of sdpcut_sdp_batch).  One set per candidate size; a new call replaces
+ * it, count = 0 drops it.  The set belongs to the handle and is independent of instance, candidates, point and networks.
+ *
+ * sdpcut_train_loss_grad: k, n_layers, widths, params, n_params are EXACTLY the packing of sdpcut_set_network, refused where and
+ * as that call refuses them.  In normalised units -- what MATLAB's mse performance minimises --
+ *     x_n = (x - xoffset) gain + ymin,  a_l = tansig(W_l a_(l-1) + b_l) for the hidden layers,  y_n = W_out a + b_out,
+ *     t_n = (t - y_xoffset) y_gain + y_ymin,      *loss = (1 / count) sum (y_n - t_n)^2   over samples [first, first + count)
+ * with tansig(n) = 2 / (1 + exp(-2n)) - 1 and NO input clamp (SDPCUT_INPUT_CLAMP is an inference matter).  grad (may be NULL:
+ * forward only) receives d loss / d(W, b) of every layer in the order of params: n_params - (2 d_in + 1 + 3) doubles -- the
+ * mapping constants are data, not parameters.  fp64 throughout, the matrix products on v_mfma_f64_16x16x4_f64; the partial
+ * gradients of the workgroups are added in a fixed order and nothing is accumulated atomically: two calls with the same arguments
+ * return the same bits, and *loss is the same with and without a gradient.
+ * Memory: a call keeps a workspace of (min(ceil(count / 16), 2 x compute units) + 1) x (n_params - 2 d_in - 3) + n_params doubles
+ * on the handle -- one row of partial sums per workgroup, 57 MB for the k = 5 network with four hidden layers of 64 on 256 compute
+ * units.  It grows to the largest call's need, is written and read once per evaluation and is freed with the handle.
+ * Needs nothing but the handle and the data: SDPCUT_ESTATE before sdpcut_train_set_data for this k and while a round begun with
+ * sdpcut_round_csr_begin is pending; SDPCUT_EINVAL for a bad k, a range outside the set or an n_params that does not match.
+ */
+int sdpcut_train_set_data(sdpcut_handle h, int k, int64_t count, const double *inputs, const double *targets);
+int sdpcut_train_loss_grad(sdpcut_handle h, int k, int n_layers, const int32_t *widths, const double *params, int64_t n_params,
+                           int64_t first, int64_t count, double *loss, double *grad);
+
 /* Timing of the last sdpcut_score / sdpcut_rank (HIP events on the handle's stream).
  * SDPCUT_OPT_TIMING = 1: events around the score kernels only; = 2: also around the ranking.
  * ms[0] = score kernels, ms[1] = rank (-1 when not recorded). */

@@ -97,6 +97,8 @@ SIGNATURES = {
     "sdpcut_eig_batch": [_vp, _c.c_int, _c.c_int64, _dp, _dp, _dp, _dp],
     "sdpcut_nn_batch": [_vp, _c.c_int, _c.c_int64, _dp, _dp],
     "sdpcut_sdp_batch": [_vp, _c.c_int, _c.c_int64, _dp, _dp, _dp, _dp, _dp, _i32p],
+    "sdpcut_train_set_data": [_vp, _c.c_int, _c.c_int64, _dp, _dp],
+    "sdpcut_train_loss_grad": [_vp, _c.c_int, _c.c_int, _i32p, _dp, _c.c_int64, _c.c_int64, _c.c_int64, _dp, _dp],
     "sdpcut_last_timing": [_vp, _dp, _c.c_int],
     "sdpcut_mfma_probe": [_vp, _dp, _dp, _dp],
     "sdpcut_tri_preprocess": [_vp, _c.POINTER(_c.c_uint8), _i64p],
@@ -201,6 +203,7 @@ class Scorer(object):
         self.N = 0
         self.nb_vars = 0
         self.base = 0
+        self._train_count = {}   # samples of the resident training set per candidate size (train_set_data)
         self.round_count = 0     # rounds that wrote the handle's pinned host block (views of it are good until the next one)
 
     # ------------------------------------------------------------------ plumbing
@@ -718,6 +721,32 @@ class Scorer(object):
         if want_certificate:
             return dict(value=value, gap=gap, lam=lam, Y=Y, iters=iters)
         return value, gap
+
+    def train_set_data(self, k, inputs, targets):
+        """Make (inputs [count, k(k+3)/2] = [x | Q_slice], targets [count]) the resident training set of size k
+        (sdpcut_train_set_data); an empty set drops it."""
+        inputs, targets = _f64(inputs), _f64(targets)
+        c = targets.shape[0]
+        if inputs.shape != (c, k * (k + 3) // 2) or targets.shape != (c,):
+            raise ValueError("inputs must be [count, k(k+3)/2] and targets [count]")
+        self._check(self._lib.sdpcut_train_set_data(self._h, int(k), c, _ptr(inputs, _dp), _ptr(targets, _dp)))
+        self._train_count[int(k)] = c
+
+    def train_loss_grad(self, k, widths, params, first=0, count=None, want_grad=True):
+        """Normalised mean squared error of the network (widths, params: the packing of set_network) over samples
+        [first, first + count) of the resident set and its gradient with respect to every W and b, in the order of params
+        (sdpcut_train_loss_grad) -> (loss, grad float64[n_params - (2 d_in + 4)]), grad None with want_grad=False.
+        count=None: through the end of the set."""
+        widths = np.ascontiguousarray(widths, dtype=np.int32)
+        params = _f64(params)
+        if count is None:
+            count = self._train_count.get(int(k), 0) - int(first)
+        loss = _c.c_double(0.0)
+        d_in = int(k) * (int(k) + 3) // 2
+        grad = np.empty(max(params.shape[0] - (2 * d_in + 4), 0)) if want_grad else None
+        self._check(self._lib.sdpcut_train_loss_grad(self._h, int(k), widths.shape[0], _ptr(widths, _i32p), _ptr(params, _dp),
+                                                     params.shape[0], int(first), int(count), ctypes.byref(loss), _ptr(grad, _dp)))
+        return float(loss.value), grad
 
     def last_timing(self):
         ms = np.zeros(2)

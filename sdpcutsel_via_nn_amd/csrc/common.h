@@ -50,6 +50,13 @@ struct NetHost {
     double *d_blob = nullptr;   // one allocation behind all device pointers of dev
 };
 
+// the resident training set of one candidate size and the workspace of its gradient evaluations (train.hip)
+struct TrainData {
+    int64_t count = 0;
+    double *d_in = nullptr;     // [count][k(k+3)/2], the layout of sdpcut_nn_batch
+    double *d_t = nullptr;      // [count]
+};
+
 // a fused round between its two halves (round.hip: round_begin / round_end)
 struct PendingRound {
     bool active = false, csr = false, fast_tried = false;
@@ -166,6 +173,9 @@ struct sdpcut_ctx {
     int64_t round_serial = 0;      // completion word of the fused round (round_rows_kernel -> pinned header)
     uint32_t *d_done_ticket = nullptr;
     PendingRound pend;
+    TrainData train[SDPCUT_MAX_K + 1];   // sdpcut_train_set_data; independent of instance, candidates, point and networks
+    double *d_train_ws = nullptr;  // parameters | per-workgroup partial sums | reduced loss and gradient (train.hip)
+    size_t train_ws_doubles = 0;
     void *d_dense = nullptr;       // dense eigen-cuts (dense.hip): V^T, sorted vectors, eigenvalues, n_rows; allocated by the first call
     // sdpcut_shard_finish_enqueue -> sdpcut_shard_finish_wait
     int64_t shard_pending_serial = 0, shard_pending_sel = 0;
@@ -279,6 +289,8 @@ void free_exact_ws(sdpcut_ctx *h);
 
 // dense.hip
 void free_dense_ws(sdpcut_ctx *h);
+// train.hip
+void free_train_ws(sdpcut_ctx *h);
 
 // exact_sdp.hip (SDPCUT_SDP, SDPCUT_OPT_EXACT_SDP)
 int launch_exact_sdp(sdpcut_ctx *h);                 // d_sdp / d_sdp_gap of every candidate at the current point

@@ -20,10 +20,9 @@ struct NetPack {
     double ymin, b_out, y_ymin, y_gain, y_xoffset;
 };
 
-// params = xoffset[d_in] | gain[d_in] | ymin | (W, b) per layer | y_ymin, y_gain, y_xoffset  (sdpcut_set_network).
+// What the library accepts as a network description (sdpcut_set_network, and sdpcut_train_loss_grad through the same lines):
 // -> SDPCUT_OK, or SDPCUT_EINVAL with *why set.
-static inline int net_pack(int k, int n_layers, const int32_t *widths, const double *params, int64_t n_params, NetPack *out,
-                           const char **why)
+static inline int net_check(int k, int n_layers, const int32_t *widths, const double *params, int64_t n_params, const char **why)
 {
     auto refuse = [&](const char *msg) { *why = msg; return SDPCUT_EINVAL; };
     if (k < 2 || k > SDPCUT_MAX_K) return refuse("k must be 2..5");
@@ -40,6 +39,18 @@ static inline int net_pack(int k, int n_layers, const int32_t *widths, const dou
         for (int l = 0; l < n_layers; ++l) { need += (int64_t)widths[l] * fan + widths[l]; fan = widths[l]; }
     }
     if (need != n_params) return refuse("n_params does not match the layer description");
+    return SDPCUT_OK;
+}
+
+// params = xoffset[d_in] | gain[d_in] | ymin | (W, b) per layer | y_ymin, y_gain, y_xoffset  (sdpcut_set_network).
+// -> SDPCUT_OK, or SDPCUT_EINVAL with *why set.
+static inline int net_pack(int k, int n_layers, const int32_t *widths, const double *params, int64_t n_params, NetPack *out,
+                           const char **why)
+{
+    if (net_check(k, n_layers, widths, params, n_params, why) != SDPCUT_OK) return SDPCUT_EINVAL;
+    const int d_in = k * (k + 3) / 2;
+    const int nh = n_layers - 1;
+    const int H = widths[0];
 
     // ---- unpack
     const double *p = params;

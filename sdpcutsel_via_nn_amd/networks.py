@@ -29,3 +29,259 @@ def load_network(k, path=None):
         layer += 1
     parts.append(np.array([z[p + "y_ymin"], z[p + "y_gain"], z[p + "y_xoffset"]], dtype=np.float64))
     return np.array(widths, dtype=np.int32), np.concatenate(parts).astype(np.float64)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Training a network of one's own: sample -> Scorer.sdp_batch (labels) -> train -> Scorer.set_network.
+# The reference trains with MATLAB (neural_nets/train_NNs.m: feedforwardnet + trainscg + dividerand 75/15/10, mapminmax on inputs
+# and targets, mse); here the loss and its gradient come from the device (Scorer.train_loss_grad, csrc/train.hip) or from the numpy
+# twin below, and Moller's scaled conjugate gradient runs on the host over the flat parameter vector.
+
+MAX_HIDDEN, MAX_LAYERS, INPUT_CLAMP = 64, 5, 3.0      # csrc/net_pack.h
+SCG_SIGMA, SCG_LAMBDA = 5e-5, 5e-7                      # trainscg's defaults
+
+
+def check_network(k, widths, params):
+    """The refusals of csrc/net_pack.h (net_check), with its messages: raises ValueError where sdpcut_set_network and
+    sdpcut_train_loss_grad return SDPCUT_EINVAL.  -> (d_in, offsets of (W, b) per layer in params, offset of the output mapping)"""
+    if k < 2 or k > 5:
+        raise ValueError("k must be 2..5")
+    n_layers = 0 if widths is None else len(widths)
+    if n_layers < 2 or n_layers > MAX_LAYERS or params is None:
+        raise ValueError("bad layer description")
+    d_in = k * (k + 3) // 2
+    H = int(widths[0])
+    if int(widths[-1]) != 1:
+        raise ValueError("last layer must have one output")
+    for w in widths[:-1]:
+        if int(w) != H or H < 1 or H > MAX_HIDDEN:
+            raise ValueError("hidden layers must share one width <= 64")
+    offs, o, fan = [], 2 * d_in + 1, d_in
+    for w in widths:
+        offs.append((o, o + int(w) * fan))
+        o += int(w) * fan + int(w)
+        fan = int(w)
+    if o + 3 != len(params):
+        raise ValueError("n_params does not match the layer description")
+    return d_in, offs, o
+
+
+def split_params(k, widths, params):
+    """-> (xoffset, gain, ymin, [W_l [out, in]], [b_l], (y_ymin, y_gain, y_xoffset)): views of params"""
+    d_in, offs, tail = check_network(k, widths, params)
+    Ws, Bs, fan = [], [], d_in
+    for w, (ow, ob) in zip(widths, offs):
+        Ws.append(params[ow:ob].reshape(int(w), fan))
+        Bs.append(params[ob:ob + int(w)])
+        fan = int(w)
+    return params[:d_in], params[d_in:2 * d_in], params[2 * d_in], Ws, Bs, params[tail:tail + 3]
+
+
+def unclamped_ok(k, widths, params):
+    """NetPack::unclamped_ok of csrc/net_pack.h: every hidden pre-activation is provably below 40 in magnitude for mapped inputs
+    in [-3, 3], so the score kernels may run their clamp-free variant (and the one-launch form over all size classes)."""
+    _, _, _, Ws, Bs, _ = split_params(k, widths, np.asarray(params, dtype=np.float64))
+    worst = 0.0
+    for l, (W, b) in enumerate(zip(Ws[:-1], Bs[:-1])):
+        worst = max(worst, float((np.abs(b) + np.abs(W).sum(axis=1) * (INPUT_CLAMP if l == 0 else 1.0)).max()))
+    return worst < 40.0
+
+
+def _tansig(n):
+    return 2.0 / (1.0 + np.exp(-2.0 * n)) - 1.0
+
+
+def forward_twin(k, widths, params, inputs, dtype=np.float64, normalised=False):
+    """The network's output on inputs [count, d_in] in `dtype` arithmetic, without the input clamp: what sdpcut_nn_batch returns,
+    or with normalised=True the y_n of the training loss (before the output mapping is undone)."""
+    params = np.asarray(params).astype(dtype)
+    xoffset, gain, ymin, Ws, Bs, (y_ymin, y_gain, y_xoffset) = split_params(k, widths, params)
+    a = (np.asarray(inputs).astype(dtype) - xoffset) * gain + ymin
+    for W, b in zip(Ws[:-1], Bs[:-1]):
+        a = _tansig(a @ W.T + b)
+    y = a @ Ws[-1][0] + Bs[-1][0]
+    return y if normalised else (y - y_ymin) / y_gain + y_xoffset
+
+
+def loss_grad_twin(k, widths, params, inputs, targets, dtype=np.float64):
+    """Plain numpy backprop of the loss sdpcut_train_loss_grad defines (include/sdpcut.h): the mean over the samples of
+    (y_n - t_n)^2 in normalised units, tansig(n) = 2 / (1 + exp(-2n)) - 1, no input clamp -> (loss, grad) with grad = d loss / d(W, b)
+    of every layer in the order of params.  All arithmetic in `dtype` (np.longdouble for a reference).  The checker of the device
+    kernel and the CPU back end of train()."""
+    params = np.asarray(params).astype(dtype)
+    xoffset, gain, ymin, Ws, Bs, (y_ymin, y_gain, y_xoffset) = split_params(k, widths, params)
+    x = np.asarray(inputs).astype(dtype)
+    t = np.asarray(targets).astype(dtype)
+    count = x.shape[0]
+    if x.ndim != 2 or x.shape[1] != k * (k + 3) // 2 or t.shape != (count,) or count < 1:
+        raise ValueError("inputs must be [count, k(k+3)/2] and targets [count], count >= 1")
+    acts = [(x - xoffset) * gain + ymin]
+    for W, b in zip(Ws[:-1], Bs[:-1]):
+        acts.append(_tansig(acts[-1] @ W.T + b))
+    y = acts[-1] @ Ws[-1][0] + Bs[-1][0]
+    e = y - ((t - y_xoffset) * y_gain + y_ymin)
+    loss = (e * e).sum() / dtype(count)
+    delta = (dtype(2) * e / dtype(count))[:, None]            # d loss / d y_n
+    grads = []
+    for l in range(len(Ws) - 1, -1, -1):
+        grads.append(delta.sum(axis=0))                       # db_l
+        grads.append((delta.T @ acts[l]).ravel())             # dW_l
+        if l > 0:
+            delta = (delta @ Ws[l]) * (dtype(1) - acts[l] * acts[l])
+    return loss, np.concatenate(grads[::-1])
+
+
+def sample_table1(k, count, seed=7):
+    """The sampling of the paper's Table 1 (utilities.py: gen_data_ndim) -> rows [x | Q_slice], float64 [count, k(k+3)/2], the
+    layout Scorer.sdp_batch and Scorer.nn_batch take.  Q = V diag(lam) V^T with V Haar-distributed orthogonal (QR of a Gaussian
+    matrix, columns multiplied by the signs of R's diagonal) and lam uniform in [-1, 1]; x uniform in [0, 1]; Q_slice is the upper
+    triangle row-major with the off-diagonal entries DOUBLED (Q = triu(Q, 1) + triu(Q, 0), utilities.py:48).
+    Same distribution as the reference's scipy.stats.ortho_group + numpy.random.seed stream, NOT the same numbers: the draws
+    come from numpy's Generator(PCG64(seed)) in one batch."""
+    rng = np.random.default_rng(seed)
+    G = rng.standard_normal((count, k, k))
+    lam = rng.uniform(-1.0, 1.0, (count, k))
+    x = rng.uniform(0.0, 1.0, (count, k))
+    V, R = np.linalg.qr(G)
+    V = V * np.sign(np.diagonal(R, axis1=1, axis2=2))[:, None, :]
+    Q = np.einsum("nij,nj,nkj->nik", V, lam, V)
+    Q = 0.5 * (Q + np.transpose(Q, (0, 2, 1)))
+    ia, ib = np.triu_indices(k)
+    return np.concatenate([x, np.where(ia == ib, 1.0, 2.0) * Q[:, ia, ib]], axis=1)
+
+
+def _mapminmax(a):
+    """MATLAB's mapminmax onto [-1, 1] per column -> (xoffset, gain); a constant column keeps gain 1"""
+    lo, hi = a.min(axis=0), a.max(axis=0)
+    rng = hi - lo
+    return lo, np.where(rng > 0, 2.0 / np.where(rng > 0, rng, 1.0), 1.0)
+
+
+def init_network(k, hidden, inputs, targets, seed=7):
+    """Seeded start of train(): mapping constants from the data (mapminmax), weights and biases uniform in +-sqrt(6 / (fan_in +
+    fan_out)) (not MATLAB's initnw) -> (widths int32, params float64) in the packing of sdpcut_set_network."""
+    rng = np.random.default_rng(seed)
+    d_in = k * (k + 3) // 2
+    widths = np.array(list(hidden) + [1], dtype=np.int32)
+    xoffset, gain = _mapminmax(np.asarray(inputs, dtype=np.float64))
+    y_xoffset, y_gain = _mapminmax(np.asarray(targets, dtype=np.float64)[:, None])
+    parts, fan = [xoffset, gain, np.array([-1.0])], d_in
+    for w in widths:
+        a = np.sqrt(6.0 / (fan + int(w)))
+        parts += [rng.uniform(-a, a, int(w) * fan), rng.uniform(-a, a, int(w))]
+        fan = int(w)
+    parts.append(np.array([-1.0, float(y_gain[0]), float(y_xoffset[0])]))
+    params = np.concatenate(parts).astype(np.float64)
+    check_network(k, widths, params)
+    return widths, params
+
+
+def train(k, inputs, targets, hidden=(50, 50, 50), scorer=None, epochs=1000, max_fail=100, min_grad=1e-6,
+          split=(0.75, 0.15, 0.10), seed=7):
+    """Train a tansig MLP on (inputs [count, k(k+3)/2], targets [count]) -> (widths, params, report); (widths, params) go straight
+    into Scorer.set_network.
+
+    What train_NNs.m does with MATLAB's toolbox: mapminmax on inputs and targets (the mapping constants are part of params and
+    stay fixed), a random train / validation / test split, mse in normalised units, Moller's scaled conjugate gradient with
+    trainscg's defaults (sigma 5e-5, lambda 5e-7): two gradient evaluations per iteration, a step is accepted only if the train
+    loss does not increase.  Stops after `epochs` iterations, after `max_fail` iterations in a row whose validation loss is above
+    the best one seen, or when the gradient's norm falls below `min_grad`; the weights of the best validation loss are returned.
+    The start is seeded (init_network), not MATLAB's initnw; trajectories are not MATLAB's.
+
+    scorer=None: loss and gradient from loss_grad_twin on the CPU.  With a Scorer the samples become its resident training set of
+    size k (train_set_data, permuted so that the three parts are ranges) and every evaluation runs on the device.  That REPLACES
+    whatever training set of size k the Scorer held, and the permuted samples stay resident after the call (train_set_data with
+    an empty set drops them).
+
+    report: train_loss / val_loss per iteration (entry 0 = the start), stop ('epochs' | 'max_fail' | 'min_grad'), iterations,
+    best_iteration, best_val_loss, test_loss, grad_evals, unclamped_ok (net_pack's status of the returned network: whether the
+    score kernels run their clamp-free variant on it), perm (the permutation of the samples: sample perm[i] is row i of the
+    permuted -- and, with a Scorer, resident -- set) and split ({'train' | 'val' | 'test': (first, count)}, ranges of that set)."""
+    inputs = np.ascontiguousarray(inputs, dtype=np.float64)
+    targets = np.ascontiguousarray(targets, dtype=np.float64)
+    count = targets.shape[0]
+    widths, w0 = init_network(k, hidden, inputs, targets, seed)
+    d_in = k * (k + 3) // 2
+    lo, hi = 2 * d_in + 1, w0.shape[0] - 3              # the trainable slice of params
+    perm = np.random.default_rng(seed + 1).permutation(count)
+    n_tr = int(round(split[0] * count))
+    n_va = int(round(split[1] * count))
+    if n_tr < 1 or n_va < 1 or n_tr + n_va > count:
+        raise ValueError("the split leaves the training or the validation part empty")
+    X, T = inputs[perm], targets[perm]
+    parts = {"train": (0, n_tr), "val": (n_tr, n_va), "test": (n_tr + n_va, count - n_tr - n_va)}
+    if scorer is not None:
+        scorer.train_set_data(k, X, T)
+    evals = [0]
+
+    def full(w):
+        p = w0.copy()
+        p[lo:hi] = w
+        return p
+
+    def fg(w, part, want_grad=True):
+        first, cnt = parts[part]
+        evals[0] += 1 if want_grad else 0
+        if scorer is not None:
+            return scorer.train_loss_grad(k, widths, full(w), first, cnt, want_grad=want_grad)
+        f, g = loss_grad_twin(k, widths, full(w), X[first:first + cnt], T[first:first + cnt])
+        return float(f), g
+
+    w = w0[lo:hi].copy()
+    f, g = fg(w, "train")
+    r, p = -g, -g
+    lam, lam_bar, success, delta, stop = SCG_LAMBDA, 0.0, True, 0.0, "epochs"
+    fv = fg(w, "val", False)[0]
+    best = (fv, w.copy(), 0)
+    fails = 0
+    train_loss, val_loss = [f], [fv]
+    n = w.shape[0]
+    it = 0
+    for it in range(1, int(epochs) + 1):
+        pp = float(p @ p)
+        if pp == 0.0 or np.sqrt(float(r @ r)) < min_grad:
+            stop, it = "min_grad", it - 1
+            break
+        if success:                                    # second-order information along p
+            sig = SCG_SIGMA / np.sqrt(pp)
+            s = (fg(w + sig * p, "train")[1] - g) / sig
+            delta = float(p @ s)
+        delta += (lam - lam_bar) * pp
+        if delta <= 0.0:                               # make the Hessian estimate positive definite
+            lam_bar = 2.0 * (lam - delta / pp)
+            delta = -delta + lam * pp
+            lam = lam_bar
+        mu = float(p @ r)
+        alpha = mu / delta
+        w_new = w + alpha * p
+        f_new, g_new = fg(w_new, "train")
+        Delta = 2.0 * delta * (f - f_new) / (mu * mu)
+        if Delta >= 0.0 and np.isfinite(f_new):       # accepted: the train loss did not increase
+            r_new = -g_new
+            lam_bar, success = 0.0, True
+            if it % n == 0:
+                p = r_new
+            else:
+                p = r_new + (float(r_new @ r_new) - float(r_new @ r)) / mu * p
+            w, f, g, r = w_new, f_new, g_new, r_new
+            if Delta >= 0.75:
+                lam *= 0.25
+        else:
+            lam_bar, success = lam, False
+        if not (Delta >= 0.25):                        # poor agreement with the quadratic model: raise the scale
+            lam = lam + delta * (1.0 - Delta) / pp if np.isfinite(Delta) else 2.0 * lam
+        fv = fg(w, "val", False)[0] if success else val_loss[-1]
+        train_loss.append(f)
+        val_loss.append(fv)
+        if fv < best[0]:
+            best, fails = (fv, w.copy(), it), 0
+        elif fv > best[0]:
+            fails += 1
+            if fails >= max_fail:
+                stop = "max_fail"
+                break
+    params = full(best[1])
+    report = dict(train_loss=train_loss, val_loss=val_loss, stop=stop, iterations=it, best_iteration=best[2],
+                  best_val_loss=best[0], test_loss=fg(best[1], "test", False)[0] if parts["test"][1] > 0 else float("nan"),
+                  grad_evals=evals[0], unclamped_ok=bool(unclamped_ok(k, widths, params)), split=dict(parts), perm=perm)
+    return widths, params, report
