@@ -151,11 +151,14 @@ enum { SDPCUT_OPT_KERNEL = 1, SDPCUT_OPT_TIMING = 2, SDPCUT_OPT_FUSE_KEYS = 3, S
  * SDPCUT_STAT_EXACT_RETRIES = selections whose first band did not prove itself and that ran again with the widest one.
  * SDPCUT_STAT_SDP_UNCONVERGED = candidates of the last exact-SDP solve (sdpcut_score with SDPCUT_SDP, or sdpcut_sdp_batch) that stopped
  *   at the iteration cap instead of the gap target; they still returned their certified lower bound and their gap.  Read from the
- *   device: the call waits for the handle's stream. */
+ *   device: the call waits for the handle's stream.
+ * SDPCUT_STAT_POINTS_REDONE = points of batched rounds (sdpcut_round_csr_points) on the one-launch route whose selection declared
+ *   itself void -- an every-entry-visited tie group beyond the one-workgroup sort, a structured LP vertex -- and that were served
+ *   by the single-point round inside the call instead.  Same results either way. */
 enum { SDPCUT_STAT_ROUNDS = 1, SDPCUT_STAT_SELECT_FALLBACKS = 2, SDPCUT_STAT_SCORED = 3, SDPCUT_STAT_TIE_SPLITS = 4,
        SDPCUT_STAT_DIRECT_SELECTIONS = 5, SDPCUT_STAT_PF_BIN = 6, SDPCUT_STAT_PF_FLOOR = 7, SDPCUT_STAT_PF_COUNT = 8,
        SDPCUT_STAT_EXACT_HEAD = 9, SDPCUT_STAT_EXACT_GAVE_UP = 10, SDPCUT_STAT_EXACT_RETRIES = 11,
-       SDPCUT_STAT_SDP_UNCONVERGED = 12 };
+       SDPCUT_STAT_SDP_UNCONVERGED = 12, SDPCUT_STAT_POINTS_REDONE = 13 };
 int sdpcut_get_stat(sdpcut_handle h, int which, int64_t *value);
 
 /* Maximum sub-problem size (assert dim <= 5, cut_select_qp.py:93) */
@@ -426,6 +429,40 @@ int sdpcut_round_csr(sdpcut_handle h, const double *vars_values, int strat, int6
  * (cut_select_qcqp.py:64-78): begin(objective cover), begin(constraints cover), end, end. */
 int sdpcut_round_csr_begin(sdpcut_handle h, const double *vars_values, int strat, int64_t sel_size);
 int sdpcut_round_csr_end(sdpcut_handle h, sdpcut_round_csr_t *out);
+
+/*
+ * Many LP points against ONE candidate list per call: the open nodes of a branch-and-bound tree, the children of a dive, the
+ * candidate points of a strong-branching step.  A single round on a short list costs its launch chain and the host hand-off, not
+ * arithmetic; these calls pay both once for n_points points.
+ *
+ * points: n_points rows of L + n doubles ([X packed | x], as sdpcut_set_point takes them), row p at points + p * point_ld,
+ * point_ld >= L + n.  1 <= n_points <= SDPCUT_BATCH_MAX_POINTS (SDPCUT_EINVAL beyond).  Both calls are synchronous, need an
+ * instance and candidates (SDPCUT_ESTATE without), refuse a handle with a pending round (sdpcut_round_csr_begin,
+ * sdpcut_shard_finish_enqueue: SDPCUT_ESTATE) and LEAVE THE HANDLE WITHOUT A CURRENT POINT: nothing is scored afterwards, and a
+ * single-point call that follows needs its own sdpcut_set_point (sdpcut_score, sdpcut_rank ... fail with SDPCUT_ESTATE until
+ * then; sdpcut_round_csr with a point is fine).  The handle's single-point arrays are scratch of the per-point fallback.
+ *
+ * sdpcut_score_points: flags = any combination of SDPCUT_EIG | SDPCUT_NN (SDPCUT_SDP is refused in this version).  eig_out /
+ * obj_out: host arrays [n_points][N], row p = what sdpcut_set_point(point p), sdpcut_score(flags), sdpcut_get_scores returns, bit
+ * for bit; the array of a measure that is not asked for may be NULL (one that is asked for may not).  One point copy and one
+ * score launch with a point axis per size class (an eigenvalue-only scan: one launch).
+ *
+ * sdpcut_round_csr_points: out[p] is what sdpcut_round_csr(h, points + p * point_ld, strat, sel_size, &o) returns -- every field
+ * and every array, bit for bit.  Strategies 1, 2 and 4 are served; 0, 3, -1, 5 and the SDPCUT_PART_* codes are refused with
+ * SDPCUT_EINVAL.  All pointers of out[0 .. n_points) point into ONE pinned block of the handle (point p's slice starts with its
+ * own header and is 64-byte aligned); they stay valid until the next call on the handle.
+ *   Lists of at most 4096 candidates with a head of 1 .. 512 entries (SDPCUT_OPT_EXACT_HEAD off, no shard base): one point copy,
+ *   one score launch per size class, ONE selection launch (a workgroup per point selects, sorts and emits its head), ONE row
+ *   assembly, ONE host wait.  A point whose selection declared itself void is served by the single-point round inside the call
+ *   (SDPCUT_STAT_POINTS_REDONE counts them).
+ *   Everything else -- longer lists, longer or empty heads, exact heads, a kernel variant without a point axis -- runs the
+ *   single-point round once per point inside the call and copies each result into the point's slice.
+ */
+#define SDPCUT_BATCH_MAX_POINTS 256
+int sdpcut_score_points(sdpcut_handle h, int32_t n_points, const double *points, int64_t point_ld, uint32_t flags, double *eig_out,
+                        double *obj_out);
+int sdpcut_round_csr_points(sdpcut_handle h, int32_t n_points, const double *points, int64_t point_ld, int strat, int64_t sel_size,
+                            sdpcut_round_csr_t *out /* [n_points] */);
 
 /*
  * Dense eigen-cuts: strategy 0 of cut_select_algo, the paper's baseline (replaces __gen_dense_eigcuts, cut_select_qp.py:757-786:

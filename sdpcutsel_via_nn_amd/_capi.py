@@ -27,6 +27,8 @@ STAT_ROUNDS, STAT_SELECT_FALLBACKS, STAT_SCORED, STAT_TIE_SPLITS, STAT_DIRECT_SE
 STAT_EXACT_HEAD, STAT_EXACT_GAVE_UP, STAT_EXACT_RETRIES = 9, 10, 11
 OPT_EXACT_SDP = 13       # strategy 3 accepted by the ranking and round calls (include/sdpcut.h)
 STAT_SDP_UNCONVERGED = 12
+STAT_POINTS_REDONE = 13   # points of batched rounds served by the single-point round inside the call (include/sdpcut.h)
+BATCH_MAX_POINTS = 256   # SDPCUT_BATCH_MAX_POINTS: most LP points of one score_points / round_csr_points call
 ROW_LD = 20
 
 _c = ctypes
@@ -41,6 +43,13 @@ class RoundCsr(_c.Structure):
                 ("counters", _c.c_int64 * 4), ("idx", _vp), ("score", _vp), ("lam_min", _vp), ("ks", _vp), ("set_inds", _vp),
                 ("n_rows", _c.c_int64), ("nnz", _c.c_int64), ("row_entry", _vp), ("indptr", _vp), ("indices", _vp),
                 ("values", _vp), ("rhs", _vp)]
+
+# the same record as a numpy dtype: the P records of a batched round are read as one structured array
+_ROUND_CSR_DTYPE = np.dtype([("cap", "<i8"), ("n_out", "<i8"), ("n_total", "<i8"), ("new_strat", "<i4"), ("row_ld", "<i4"), ("counters", "<i8", (4,)),
+                             ("idx", "<u8"), ("score", "<u8"), ("lam_min", "<u8"), ("ks", "<u8"), ("set_inds", "<u8"), ("n_rows", "<i8"),
+                             ("nnz", "<i8"), ("row_entry", "<u8"), ("indptr", "<u8"), ("indices", "<u8"), ("values", "<u8"), ("rhs", "<u8")])
+assert _ROUND_CSR_DTYPE.itemsize == _c.sizeof(RoundCsr)
+
 
 class DenseRound(_c.Structure):
     """sdpcut_dense_round_t of include/sdpcut.h"""
@@ -86,6 +95,8 @@ SIGNATURES = {
     "sdpcut_round_csr": [_vp, _dp, _c.c_int, _c.c_int64, _c.POINTER(RoundCsr)],
     "sdpcut_round_csr_begin": [_vp, _dp, _c.c_int, _c.c_int64],
     "sdpcut_round_csr_end": [_vp, _c.POINTER(RoundCsr)],
+    "sdpcut_score_points": [_vp, _c.c_int32, _dp, _c.c_int64, _c.c_uint32, _dp, _dp],
+    "sdpcut_round_csr_points": [_vp, _c.c_int32, _dp, _c.c_int64, _c.c_int, _c.c_int64, _c.POINTER(RoundCsr)],
     "sdpcut_dense_round": [_vp, _dp, _c.POINTER(DenseRound)],
     "sdpcut_dense_eig": [_vp, _dp, _dp],
     "sdpcut_shard_head_device": [_vp, _c.c_int, _c.c_int64, _vp],
@@ -550,6 +561,80 @@ class Scorer(object):
         cnt = out.counters
         res.update(n_total=int(out.n_total), new_strat=int(out.new_strat),
                    counters=dict(nb_violated=int(cnt[0]), strong=int(cnt[1]), violated=int(cnt[2]), nb_positive=int(cnt[3])))
+        return res
+
+    # ------------------------------------------------------------------ many LP points per call
+    def _points_arg(self, points):
+        pts = _f64(points)
+        n = self.nb_vars
+        if pts.ndim != 2 or pts.shape[1] != n * (n + 1) // 2 + n:
+            raise ValueError("points must be [P, n(n+1)/2 + n]: one LP point [X packed | x] per row")
+        if not 1 <= pts.shape[0] <= BATCH_MAX_POINTS:
+            raise ValueError("1 .. %d points per call" % BATCH_MAX_POINTS)
+        return pts
+
+    def score_points(self, points, eig=True, obj=True):
+        """Scores of the candidate list at P LP points in one call (sdpcut_score_points): points [P, n(n+1)/2 + n] ->
+        (eig [P, N] | None, obj [P, N] | None), row p = what set_point(points[p]), score, get_scores return.  Leaves the Scorer
+        without a current point."""
+        pts = self._points_arg(points)
+        if not (eig or obj):
+            raise ValueError("nothing asked for")
+        P = pts.shape[0]
+        e = np.empty((P, self.N)) if eig else None
+        o = np.empty((P, self.N)) if obj else None
+        self._check(self._lib.sdpcut_score_points(self._h, P, _ptr(pts, _dp), pts.shape[1], (EIG if eig else 0) | (NN if obj else 0),
+                                                  _ptr(e, _dp), _ptr(o, _dp)))
+        return e, o
+
+    def round_csr_points(self, points, strat, sel_size, copy=False):
+        """P rounds with the cuts assembled, one LP point each, in one call (sdpcut_round_csr_points): points [P, n(n+1)/2 + n] ->
+        list of P dicts, entry p = what round_csr(strat, sel_size, point=points[p]) returns (same keys, dtypes and values).  The
+        arrays are numpy views of the handle's pinned batch block, valid until the next call on this Scorer; copy=True detaches
+        them.  Strategies 1, 2 and 4.  Leaves the Scorer without a current point."""
+        pts = self._points_arg(points)
+        P = pts.shape[0]
+        if getattr(self, "_h", None) is None:
+            raise SdpCutError("the Scorer is closed")
+        self.round_count += 1
+        recs = getattr(self, "_csr_points_recs", None)
+        if recs is None or recs.shape[0] < P:
+            recs = self._csr_points_recs = np.zeros(max(P, 8), dtype=_ROUND_CSR_DTYPE)
+        self._check(self._lib.sdpcut_round_csr_points(self._h, P, _ptr(pts, _dp), pts.shape[1], int(strat), int(sel_size),
+                                                      recs.ctypes.data_as(_c.POINTER(RoundCsr))))
+        r = recs[:P]
+        base = int(r["idx"].min())
+        if base:
+            # ONE byte view over the batch block (cached while the block stays where it is); every array is a slice of it
+            c_max, ld = int(r["cap"].max()), int(r["row_ld"][0])
+            end = int(r["indices"].max()) + 4 * c_max * ld
+            key = (base, end)
+            if getattr(self, "_csr_points_key", None) != key:
+                self._csr_points_u8 = np.frombuffer((_c.c_char * (end - base)).from_address(base), dtype=np.uint8)
+                self._csr_points_key = key
+            u8 = self._csr_points_u8
+        cols = {f: r[f].tolist() for f in _ROUND_CSR_DTYPE.names}
+        res = []
+        for p in range(P):
+            c, w, nr, nnz = cols["cap"][p], cols["n_out"][p], cols["n_rows"][p], cols["nnz"][p]
+            if c and cols["idx"][p]:
+                def view(field, dtype, count, size):
+                    o = cols[field][p] - base
+                    return u8[o:o + count * size].view(dtype)
+                d = dict(idx=view("idx", np.int64, w, 8), score=view("score", np.float64, w, 8), lam=view("lam_min", np.float64, w, 8),
+                         ks=view("ks", np.int32, w, 4), set_inds=view("set_inds", np.int32, 5 * w, 4).reshape(w, 5),
+                         row_entry=view("row_entry", np.int32, nr, 4), indptr=view("indptr", np.int32, nr + 1, 4),
+                         indices=view("indices", np.int32, nnz, 4), values=view("values", np.float64, nnz, 8), rhs=view("rhs", np.float64, nr, 8))
+                if copy:
+                    d = {k: a.copy() for k, a in d.items()}
+            else:
+                z = np.zeros
+                d = dict(idx=z(0, np.int64), score=z(0), lam=z(0), ks=z(0, np.int32), set_inds=z((0, 5), np.int32),
+                         row_entry=z(0, np.int32), indptr=z(1, np.int32), indices=z(0, np.int32), values=z(0), rhs=z(0))
+            cnt = cols["counters"][p]
+            d.update(n_total=cols["n_total"][p], new_strat=cols["new_strat"][p],
+                     counters=dict(nb_violated=cnt[0], strong=cnt[1], violated=cnt[2], nb_positive=cnt[3]))
+            res.append(d)
         return res
 
     # ------------------------------------------------------------------ dense eigen-cuts (strategy 0)

@@ -78,6 +78,25 @@ struct PendingRound {
                                                    "sdpcut_shard_finish_wait first");                                    \
     } while (0)
 
+// what a batch of LP points needs beside the handle's single-point state (points.hip); everything grows on demand
+struct PointsBufs {
+    void *stage = nullptr, *stage_dev = nullptr;   // pinned staging of the points [P][L + n], as the host / the device sees it
+    size_t stage_bytes = 0;
+    double *d_pts = nullptr;                        // [P][L + n]
+    size_t pts_doubles = 0;
+    double *d_eig = nullptr, *d_obj = nullptr;      // [P][N]
+    size_t score_doubles = 0;
+    void *d_ws = nullptr;                           // TopkWs[P]: selection state and counters of every point
+    int ws_points = 0;
+    int64_t *d_idx = nullptr;                       // [P][cap] heads
+    double *d_score = nullptr;
+    size_t head_entries = 0;
+    uint64_t *d_agg = nullptr;                      // [P][BATCH_AGG_WORDS] look-back words of the row assembly
+    int agg_points = 0;
+    void *pinned = nullptr, *pinned_dev = nullptr;  // the batch block (batch_route.h: batch_layout)
+    size_t pinned_bytes = 0;
+};
+
 struct sdpcut_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr, stream = nullptr;
@@ -99,6 +118,8 @@ struct sdpcut_ctx {
     unsigned long long *d_stats = nullptr;   // device counters that outlive a round: [0] direct selections
     bool coop_launch = false;      // SDPCUT_OPT_COOP_LAUNCH: cooperative launch of the kernels with grid barriers (+20 us per round)
     int64_t stat_rounds = 0, stat_fallbacks = 0, stat_tie_splits = 0;   // sdpcut_get_stat
+    int64_t stat_points_redone = 0;   // SDPCUT_STAT_POINTS_REDONE
+    PointsBufs pts;                   // sdpcut_score_points / sdpcut_round_csr_points
     // SDPCUT_OPT_EXACT_HEAD (exact_head.hip): NN-ranked heads ordered and reported by reference-order obj_improve
     bool exact_head = false;
     bool exact_suspended = false;  // a round that gave up is being served by the ordinary path
@@ -210,6 +231,27 @@ static inline int check_round_strategy(sdpcut_ctx *h, int strat)
     return 0;
 }
 
+// The pointers, n_rows and nnz of *out for a CSR round block (round_layout.h: csr_layout) of out->cap > 0 entries with rows of
+// out->row_ld that lies at `block`; cap, row_ld and n_out are set already.
+static inline void csr_out_from_block(const void *block, sdpcut_round_csr_t *out)
+{
+    const CsrLayout y = csr_layout(out->cap, out->row_ld);
+    const char *b = (const char *)block;
+    const int64_t *hdr = (const int64_t *)b;
+    out->idx = (const int64_t *)(b + y.idx);
+    out->score = (const double *)(b + y.score);
+    out->lam_min = (const double *)(b + y.lam);
+    out->ks = (const int32_t *)(b + y.ks);
+    out->set_inds = (const int32_t *)(b + y.sets);
+    out->n_rows = out->n_out > 0 ? hdr[8] : 0;
+    out->nnz = out->n_out > 0 ? hdr[9] : 0;
+    out->row_entry = (const int32_t *)(b + y.row_entry);
+    out->indptr = (const int32_t *)(b + y.indptr);
+    out->indices = (const int32_t *)(b + y.indices);
+    out->values = (const double *)(b + y.values);
+    out->rhs = (const double *)(b + y.rhs);
+}
+
 #define HIP_TRY(h, expr)                                                                   \
     do {                                                                                   \
         hipError_t e__ = (expr);                                                           \
@@ -242,6 +284,15 @@ int launch_round_csr(sdpcut_ctx *h, int64_t cap, const int64_t *d_c4, int64_t li
                      int ld, void *block, int64_t serial);
 // eig.hip: lambda_min of every candidate, one launch over all size classes; tk = TopkWs of a feasibility selection or NULL
 int launch_eig_only(sdpcut_ctx *h, void *tk, hipEvent_t ev_start, hipEvent_t ev_stop, int64_t pf_k = 0);
+// the point-axis forms of the scoring and of the CSR assembly (a batch of LP points, points.hip): eig.hip, score.hip, rows.hip
+int launch_eig_only_points(sdpcut_ctx *h, int n_points, const double *d_pts, int64_t pts_stride, double *d_eig, int64_t eig_stride);
+bool score_points_served(const sdpcut_ctx *h, uint32_t flags);
+int launch_score_points(sdpcut_ctx *h, uint32_t flags, int n_points, const double *d_pts, int64_t pts_stride, double *d_eig, double *d_obj,
+                        int64_t score_stride, int64_t *d_strong, int64_t strong_stride);
+int launch_round_csr_points(sdpcut_ctx *h, int p_first, int n_points, int64_t cap, int ld, const int64_t *d_c4, int64_t c4_stride,
+                            const int64_t *d_idx, const double *d_score, const double *d_pts, int64_t pts_stride, const double *d_eig,
+                            int64_t eig_stride, uint64_t *d_agg, int64_t agg_stride, void *block, int64_t block_stride, int64_t serial);
+void free_points_ws(sdpcut_ctx *h);              // points.hip
 int wait_round_done(sdpcut_ctx *h, const int64_t *word, int64_t serial);   // round.hip
 int score_for_selection(sdpcut_ctx *h, int strat, int64_t sel_size, int64_t cap, uint32_t need, bool allow_auto, int *stage,
                         bool *auto_out);                                   // round.hip

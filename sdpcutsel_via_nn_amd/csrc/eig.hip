@@ -209,7 +209,7 @@ __device__ __forceinline__ void eig_class(const EigArgs &A, int64_t lo, int64_t 
 template <int KMAX> struct EigOcc { static constexpr int W = KMAX <= 3 ? SDPCUT_EIG_W3 : (KMAX == 4 ? SDPCUT_EIG_W : SDPCUT_EIG_W5); };
 
 template <int KMAX, bool FUSE>
-__global__ __launch_bounds__(256, EigOcc<KMAX>::W) void eig_only_kernel(EigArgs A)
+__device__ __forceinline__ void eig_only_body(const EigArgs &A)
 {
     __shared__ uint32_t tk_hist[256 + (FUSE ? PF_BINS / 2 : 0)];      // leading-digit histogram | (r5) the workgroup's table of window codes, 16-bit counters (topk_dev.h)
     __shared__ uint32_t tk_cnt;
@@ -247,6 +247,23 @@ __global__ __launch_bounds__(256, EigOcc<KMAX>::W) void eig_only_kernel(EigArgs 
     }
 }
 
+template <int KMAX, bool FUSE>
+__global__ __launch_bounds__(256, EigOcc<KMAX>::W) void eig_only_kernel(EigArgs A)
+{
+    eig_only_body<KMAX, FUSE>(A);
+}
+
+// The same scan at the P = gridDim.y LP points of a batch (sdpcut_score_points / sdpcut_round_csr_points, points.hip): workgroup
+// row y reads point y of a [P][vars_stride] table and writes row y of a [P][out_stride] score array.  The offsets are applied to
+// the kernel argument (scalar registers) before the unchanged body runs; no histogram (the batched selection builds its own keys).
+template <int KMAX>
+__global__ __launch_bounds__(256, EigOcc<KMAX>::W) void eig_only_points_kernel(EigArgs A, int64_t vars_stride, int64_t out_stride)
+{
+    A.vars += (int64_t)blockIdx.y * vars_stride;
+    A.eig_out += (int64_t)blockIdx.y * out_stride;
+    eig_only_body<KMAX, false>(A);
+}
+
 // workgroups launched per resident slot: four short-lived ones -- the dispatcher balances tiles whose Jacobi needs a sweep
 // more; one long-lived workgroup per slot with the next tile's index set in flight was measured 5 % slower
 #ifndef SDPCUT_EIG_BLOCKS_PER_SLOT
@@ -277,9 +294,9 @@ static void eig_launch(sdpcut_ctx *h, EigArgs &A, hipEvent_t ev_start, hipEvent_
 
 // lambda_min of every candidate of the handle's list at the current point, one launch.
 // tk != nullptr: also the leading-digit histogram / violated count of a feasibility selection (TopkWs).
-int launch_eig_only(sdpcut_ctx *h, void *tk, hipEvent_t ev_start, hipEvent_t ev_stop, int64_t pf_k)
+// the launch's arguments for the handle's list and single-point arrays; -> the largest size class present (0: no candidates)
+static int fill_eig_args(const sdpcut_ctx *h, EigArgs &A)
 {
-    EigArgs A;
     int kmax = 0;
     int64_t acc = 0;
     for (int k = SDPCUT_MAX_K; k >= 2; --k) {
@@ -290,10 +307,18 @@ int launch_eig_only(sdpcut_ctx *h, void *tk, hipEvent_t ev_start, hipEvent_t ev_
         if (b.n > 0 && k > kmax) kmax = k;
     }
     A.set[0] = A.set[1] = nullptr; A.orig[0] = A.orig[1] = nullptr; A.n[0] = A.n[1] = 0; A.tile_end[0] = A.tile_end[1] = acc;
-    if (kmax == 0) return 0;
-    A.vars = h->d_vars; A.nv = h->nb_vars; A.L = h->L; A.eig_out = h->d_eig; A.tk = (TopkWs *)tk;
+    A.vars = h->d_vars; A.nv = h->nb_vars; A.L = h->L; A.eig_out = h->d_eig; A.tk = nullptr;
     A.pf_mloc = 0;      // (set with the grid: eig_launch)
     A.spread = 0;
+    return kmax;
+}
+
+int launch_eig_only(sdpcut_ctx *h, void *tk, hipEvent_t ev_start, hipEvent_t ev_stop, int64_t pf_k)
+{
+    EigArgs A;
+    const int kmax = fill_eig_args(h, A);
+    if (kmax == 0) return 0;
+    A.tk = (TopkWs *)tk;
 #define EIG_LAUNCH(KM)                                                   \
     do {                                                                 \
         if (tk) eig_launch<KM, true>(h, A, ev_start, ev_stop, pf_k);     \
@@ -306,6 +331,33 @@ int launch_eig_only(sdpcut_ctx *h, void *tk, hipEvent_t ev_start, hipEvent_t ev_
     default: EIG_LAUNCH(5); break;
     }
 #undef EIG_LAUNCH
+    HIP_TRY(h, hipGetLastError());
+    return 0;
+}
+
+// lambda_min of every candidate at each of n_points LP points (rows of d_pts, stride pts_stride) into rows of d_eig (stride
+// eig_stride): eig_only_points_kernel, the grid of the single-point launch with a point axis.
+int launch_eig_only_points(sdpcut_ctx *h, int n_points, const double *d_pts, int64_t pts_stride, double *d_eig, int64_t eig_stride)
+{
+    EigArgs A;
+    const int kmax = fill_eig_args(h, A);
+    if (kmax == 0) return 0;
+    A.vars = d_pts;
+    A.eig_out = d_eig;
+    const int64_t ntiles = A.tile_end[2];
+#define EIG_POINTS_LAUNCH(KM)                                                                                                  \
+    do {                                                                                                                       \
+        const int64_t cap = (int64_t)h->n_cu * EigOcc<KM>::W * SDPCUT_EIG_BLOCKS_PER_SLOT;                                     \
+        const int grid = (int)(ntiles < cap ? ntiles : cap);                                                                   \
+        hipLaunchKernelGGL((eig_only_points_kernel<KM>), dim3(grid, n_points), dim3(256), 0, h->stream, A, pts_stride, eig_stride); \
+    } while (0)
+    switch (kmax) {
+    case 2: EIG_POINTS_LAUNCH(2); break;
+    case 3: EIG_POINTS_LAUNCH(3); break;
+    case 4: EIG_POINTS_LAUNCH(4); break;
+    default: EIG_POINTS_LAUNCH(5); break;
+    }
+#undef EIG_POINTS_LAUNCH
     HIP_TRY(h, hipGetLastError());
     return 0;
 }

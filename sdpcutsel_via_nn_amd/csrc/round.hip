@@ -343,21 +343,7 @@ static int round_impl(sdpcut_ctx *h, int strat, int64_t sel_size, int32_t coef_l
 static int fill_csr_out(sdpcut_ctx *h, const void *block, sdpcut_round_csr_t *out)
 {
     if (!block || out->cap == 0) return SDPCUT_OK;
-    const CsrLayout y = csr_layout(out->cap, out->row_ld);
-    const char *b = (const char *)block;
-    const int64_t *hdr = (const int64_t *)b;
-    out->idx = (const int64_t *)(b + y.idx);
-    out->score = (const double *)(b + y.score);
-    out->lam_min = (const double *)(b + y.lam);
-    out->ks = (const int32_t *)(b + y.ks);
-    out->set_inds = (const int32_t *)(b + y.sets);
-    out->n_rows = out->n_out > 0 ? hdr[8] : 0;
-    out->nnz = out->n_out > 0 ? hdr[9] : 0;
-    out->row_entry = (const int32_t *)(b + y.row_entry);
-    out->indptr = (const int32_t *)(b + y.indptr);
-    out->indices = (const int32_t *)(b + y.indices);
-    out->values = (const double *)(b + y.values);
-    out->rhs = (const double *)(b + y.rhs);
+    csr_out_from_block(block, out);
     return SDPCUT_OK;
 }
 

@@ -286,12 +286,13 @@ struct RoundCsrArgs {
 #define ROUND_MIN_BLOCKS 8      // workgroups of an epilogue launch at least (they share the zeroing of the next round's top-k workspace)
 #endif
 
-__global__ __launch_bounds__(64) void round_csr_kernel(RoundCsrArgs R)
+// The assembly itself: workgroup blockIdx.x of the gridDim.x that serve ONE head (round_csr_kernel: the launch; the batched
+// kernel below: one row of its grid).  Everything but the zeroing of the next round's workspace and the completion word.
+__device__ __forceinline__ void round_csr_body(const RoundCsrArgs &R)
 {
     __shared__ double s_val[64 * SDPCUT_ROW_LD];
     __shared__ int32_t s_ind[64 * SDPCUT_ROW_LD];
     const int lane = threadIdx.x;
-    for (int w = blockIdx.x * 64 + lane; w < R.zero_words; w += gridDim.x * 64) R.zero_ptr[w] = 0ull;
     const int64_t first = (int64_t)blockIdx.x * 64;
     const int64_t i = first + lane;
     const int64_t gid_any = i < R.cap ? R.idx[i] : 0;
@@ -388,6 +389,13 @@ __global__ __launch_bounds__(64) void round_csr_kernel(RoundCsrArgs R)
         R.o_hdr[8] = pre_rows + wg_rows;
         R.o_hdr[9] = pre_nnz + wg_nnz;
     }
+}
+
+__global__ __launch_bounds__(64) void round_csr_kernel(RoundCsrArgs R)
+{
+    const int lane = threadIdx.x;
+    for (int w = blockIdx.x * 64 + lane; w < R.zero_words; w += gridDim.x * 64) R.zero_ptr[w] = 0ull;
+    round_csr_body(R);
     // completion word for the polling host (see round_rows_kernel)
     __threadfence_system();
     if (lane == 0) {
@@ -398,6 +406,39 @@ __global__ __launch_bounds__(64) void round_csr_kernel(RoundCsrArgs R)
             __hip_atomic_store(R.o_hdr + 7, R.serial, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
+}
+
+// The same assembly for the P points of a batch (sdpcut_round_csr_points, points.hip): row y of the grid serves point p_first + y --
+// its own head (ids, scores, selection counters), LP point and lambda_min array, its own slice of the pinned batch block (header
+// with counters, n_rows, nnz and the give-up flag included) and its own look-back words, so a workgroup still only waits for
+// workgroups in front of it in its own row.  R describes point 0; the strides are applied to the kernel argument before the
+// unchanged body runs.  No workspace to zero and no completion word: the host waits for the stream.
+struct RoundCsrPointStrides {
+    int32_t p_first;
+    int64_t c4;        // int64 words between the selection counters of two points (sizeof(TopkWs) / 8)
+    int64_t head;      // entries between two heads (cap)
+    int64_t vars;      // doubles between two LP points
+    int64_t eig;       // doubles between two lambda_min arrays
+    int64_t block;     // BYTES between two slices of the batch block
+    int64_t agg;       // look-back words per point
+};
+
+template <class T> __device__ __forceinline__ void shift_bytes(T *&p, int64_t off) { p = (T *)((char *)p + off); }
+
+__global__ __launch_bounds__(64) void round_csr_points_kernel(RoundCsrArgs R, RoundCsrPointStrides ps)
+{
+    const int64_t p = (int64_t)ps.p_first + (int64_t)blockIdx.y;
+    R.d_c4 += p * ps.c4;
+    R.idx += p * ps.head;
+    R.score += p * ps.head;
+    R.vars += p * ps.vars;
+    if (R.eig) R.eig += p * ps.eig;
+    const int64_t off = p * ps.block;
+    shift_bytes(R.o_hdr, off); shift_bytes(R.o_idx, off); shift_bytes(R.o_score, off); shift_bytes(R.o_lam, off);
+    shift_bytes(R.o_ks, off); shift_bytes(R.o_sets, off); shift_bytes(R.o_row_entry, off); shift_bytes(R.o_indptr, off);
+    shift_bytes(R.o_rhs, off); shift_bytes(R.o_indices, off); shift_bytes(R.o_values, off);
+    R.agg += p * ps.agg;
+    round_csr_body(R);
 }
 
 // LP point: mapped host memory -> device table (sdpcut_set_point)
@@ -483,5 +524,36 @@ int launch_round_csr(sdpcut_ctx *h, int64_t cap, const int64_t *d_c4, int64_t li
     hipLaunchKernelGGL(round_csr_kernel, dim3(grid), dim3(64), 0, h->stream, R);
     HIP_TRY(h, hipGetLastError());
     h->topk_alt_clean = true;
+    return 0;
+}
+
+// CSR assembly of points [p_first, p_first + n_points) of a batch (round_csr_points_kernel).  Point p: head ids / scores at
+// d_idx / d_score + p * cap, selection counters at d_c4 + p * c4_stride, LP point d_pts + p * pts_stride, lambda_min d_eig + p *
+// eig_stride (d_eig NULL: the rows compute it), look-back words d_agg + p * agg_stride, slice block + p * block_stride.
+int launch_round_csr_points(sdpcut_ctx *h, int p_first, int n_points, int64_t cap, int ld, const int64_t *d_c4, int64_t c4_stride,
+                            const int64_t *d_idx, const double *d_score, const double *d_pts, int64_t pts_stride, const double *d_eig,
+                            int64_t eig_stride, uint64_t *d_agg, int64_t agg_stride, void *block, int64_t block_stride, int64_t serial)
+{
+    if (cap <= 0 || n_points <= 0) return 0;
+    const int grid = (int)((cap + 63) / 64);
+    if (grid > agg_stride) return sdpcut_fail(h, SDPCUT_EINVAL, "round_csr_points: head too long");
+    RoundCsrArgs R;
+    R.cap = cap; R.d_c4 = d_c4; R.limit = cap; R.idx = d_idx; R.score = d_score; R.idx_base = h->base; R.n_local = h->N;
+    R.set5 = h->d_set_orig; R.ks = h->d_k; R.vars = d_pts; R.nv = h->nb_vars; R.L = h->L;
+    R.eig = d_eig;
+    const CsrLayout y = csr_layout(cap, ld);
+    char *b = (char *)block;
+    R.o_hdr = (int64_t *)b;
+    R.o_idx = (int64_t *)(b + y.idx); R.o_score = (double *)(b + y.score); R.o_lam = (double *)(b + y.lam);
+    R.o_rhs = (double *)(b + y.rhs); R.o_values = (double *)(b + y.values); R.o_ks = (int32_t *)(b + y.ks);
+    R.o_sets = (int32_t *)(b + y.sets); R.o_row_entry = (int32_t *)(b + y.row_entry); R.o_indptr = (int32_t *)(b + y.indptr);
+    R.o_indices = (int32_t *)(b + y.indices);
+    R.zero_ptr = nullptr; R.zero_words = 0;
+    R.serial = serial; R.done_ticket = nullptr; R.agg = d_agg;
+    RoundCsrPointStrides ps;
+    ps.p_first = p_first; ps.c4 = c4_stride; ps.head = cap; ps.vars = pts_stride; ps.eig = eig_stride; ps.block = block_stride;
+    ps.agg = agg_stride;
+    hipLaunchKernelGGL(round_csr_points_kernel, dim3(grid, n_points), dim3(64), 0, h->stream, R, ps);
+    HIP_TRY(h, hipGetLastError());
     return 0;
 }

@@ -143,10 +143,9 @@ static int calibrate_side_streams(sdpcut_ctx *h, uint32_t flags, int kbig)
     return 0;
 }
 
-int launch_score(sdpcut_ctx *h, uint32_t flags, const ScoreFuse *fuse, bool *fused, int64_t *strong_out)
+// what score_form is asked about a call on this handle
+static ScoreFormIn form_in(const sdpcut_ctx *h, uint32_t flags, const ScoreFuse *fuse)
 {
-    // (r5) did EVERY launch of this round count the fine histogram of the selection's class?  (The selection reads the table only then.)
-    h->pf_counted = fuse != nullptr && fuse->k > 0;
     ScoreFormIn in;
     in.variant = h->kernel_variant;
     in.flags = flags;
@@ -165,6 +164,14 @@ int launch_score(sdpcut_ctx *h, uint32_t flags, const ScoreFuse *fuse, bool *fus
     in.side_streams = h->side_streams;
     in.side_choice = h->side_choice;
     in.timing = h->timing;
+    return in;
+}
+
+int launch_score(sdpcut_ctx *h, uint32_t flags, const ScoreFuse *fuse, bool *fused, int64_t *strong_out)
+{
+    // (r5) did EVERY launch of this round count the fine histogram of the selection's class?  (The selection reads the table only then.)
+    h->pf_counted = fuse != nullptr && fuse->k > 0;
+    const ScoreFormIn in = form_in(h, flags, fuse);
     const ScoreForm f = score_form(in);
     if (fused) *fused = f.fused;
     if (f.err) return sdpcut_fail(h, f.err, score_form_msg(f.msg));
@@ -186,4 +193,43 @@ int launch_score(sdpcut_ctx *h, uint32_t flags, const ScoreFuse *fuse, bool *fus
     es[f.first] = ev_start;
     ee[f.last] = ev_stop;
     return launch_classes_seq(h, flags, fuse, strong_out, es, ee);
+}
+
+// ---- a batch of LP points (points.hip) ------------------------------------------------------------------------------------------
+// Do the point-axis kernels serve a scoring of `flags` on this handle?  The eigenvalue-only kernel (flags == SDPCUT_EIG) and the
+// MFMA kernel have one; the VALU / simple variants and networks of another shape (score_alt.hip) do not: such a batch is scored
+// point by point through launch_score.  A call launch_score would refuse is "served": launch_score_points refuses it the same way.
+bool score_points_served(const sdpcut_ctx *h, uint32_t flags)
+{
+    const ScoreFormIn in = form_in(h, flags, nullptr);
+    const ScoreForm f = score_form(in);
+    if (f.err || f.form == SCORE_FORM_EIG) return true;
+    if (in.variant != SDPCUT_KERNEL_MFMA) return false;
+    for (int k = 2; k <= SDPCUT_MAX_K; ++k)
+        if (in.n[k] > 0 && !score_class_shaped(in, k)) return false;
+    return true;
+}
+
+// The scores of the handle's list at n_points LP points, rows of d_pts (stride pts_stride), into rows of d_eig / d_obj (stride
+// score_stride): ONE launch with a point axis for an eigenvalue-only scan, else one per size class (every class with the plan -- and
+// so the scores -- of its single-point launch).  d_strong (optional, needs both flags): point p's launches add its strong
+// candidates to the eight replicas at d_strong + p * strong_stride.
+int launch_score_points(sdpcut_ctx *h, uint32_t flags, int n_points, const double *d_pts, int64_t pts_stride, double *d_eig, double *d_obj,
+                        int64_t score_stride, int64_t *d_strong, int64_t strong_stride)
+{
+    const ScoreFormIn in = form_in(h, flags, nullptr);
+    const ScoreForm f = score_form(in);
+    if (f.err) return sdpcut_fail(h, f.err, score_form_msg(f.msg));
+    if (!score_points_served(h, flags)) return sdpcut_fail(h, SDPCUT_ESTATE, "score: this kernel variant has no point axis");
+    if (f.form == SCORE_FORM_EIG) return launch_eig_only_points(h, n_points, d_pts, pts_stride, d_eig, score_stride);
+    const ScorePointStrides ps = {pts_stride, score_stride, strong_stride};
+    for (int k = 2; k <= SDPCUT_MAX_K; ++k) {
+        if (h->bucket[k].n == 0) continue;
+        const ScorePlan p = plan_class(h, k, nullptr);
+        ScoreArgs A = fill_score_args(h, k, flags, nullptr, d_strong, p);
+        A.vars = d_pts; A.eig_out = d_eig; A.obj_out = d_obj;
+        score_mfma_points_launch(k, A, ps, p.grid, n_points, h->stream);
+    }
+    HIP_TRY(h, hipGetLastError());
+    return 0;
 }

@@ -74,6 +74,12 @@ static inline ScoreArgs fill_score_args(const sdpcut_ctx *h, int K, uint32_t fla
     return A;
 }
 
+// A batch of LP points (points.hip): what workgroup row y of score_mfma_points_kernel adds to the pointers of its ScoreArgs, in
+// elements: vars += y * vars, eig_out / obj_out += y * scores, strong_out (if set) += y * strong.
+struct ScorePointStrides {
+    int64_t vars, scores, strong;
+};
+
 // With SDPCUT_OPT_TIMING the kernel's own dispatch carries the two events (hipExtLaunchKernelGGL):
 // its start / end timestamps are taken from the dispatch packet, without the two barrier packets
 // and ~20 us per step that hipEventRecord around the launch costs.
@@ -89,5 +95,7 @@ static inline ScoreArgs fill_score_args(const sdpcut_ctx *h, int K, uint32_t fla
 // has refused everything else) and 0 otherwise.
 void score_mfma_launch(int K, const ScoreArgs &A, int grid, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop);   // score_mfma_kernel, CLAMP = !A.net.unclamped_ok
 void score_mfma_all_launch(const ScoreArgsAll &AA, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop);            // score_mfma_all_kernel over AA.bend[nclasses - 1] workgroups
+// score_mfma_points_kernel over class K at n_points points: grid x n_points workgroups, A.tk must be NULL
+void score_mfma_points_launch(int K, const ScoreArgs &A, const ScorePointStrides &ps, int grid, int n_points, hipStream_t st);
 // score_alt.hip: score_valu_kernel (valu; the class's network has the shape of NetShape<K>) or score_simple_kernel
 void score_alt_launch(int K, bool valu, const ScoreArgs &A, int n_cu, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop);

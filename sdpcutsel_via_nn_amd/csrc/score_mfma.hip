@@ -649,6 +649,23 @@ __global__ __launch_bounds__(256, (JK == 1 ? SDPCUT_MFMA_J1_WAVES : 2)) void sco
     score_mfma_body<K, H, NH, FUSE, CLAMP, JK>(A, S, (int)blockIdx.x, (int)gridDim.x);
 }
 
+// The same kernel at the P = gridDim.y LP points of a batch (sdpcut_score_points / sdpcut_round_csr_points, points.hip): workgroup
+// row y reads point y and writes row y of the batch's score arrays (and adds to point y's strong counter).  The offsets are applied
+// to the kernel ARGUMENT -- blockIdx.y and the strides are scalars, the sums stay in scalar registers -- and the unchanged body runs
+// on the copy: the same code per candidate, the same scores.  No histogram variants (FUSE = 0): the batched selection builds its
+// own keys.
+template <int K, int H, int NH, bool CLAMP, int JK>
+__global__ __launch_bounds__(256, (JK == 1 ? SDPCUT_MFMA_J1_WAVES : 2)) void score_mfma_points_kernel(ScoreArgs A, ScorePointStrides ps)
+{
+    __shared__ MfmaLds<K, H, NH> S;
+    const int64_t p = (int64_t)blockIdx.y;
+    A.vars += p * ps.vars;
+    A.eig_out += p * ps.scores;
+    A.obj_out += p * ps.scores;
+    if (A.strong_out) A.strong_out += p * ps.strong;
+    score_mfma_body<K, H, NH, 0, CLAMP, JK>(A, S, (int)blockIdx.x, (int)gridDim.x);
+}
+
 // ONE launch for every size class of a list (r3).  Real covers hold one large class and a few sets of the smaller sizes
 // (spar100-050-1, dim 5: 72 673 five-variable sets, 103 of four, 1 of three); a launch per class costs what one pass costs however
 // few candidates it holds, and side streams run side by side only if the process's streams were handed different hardware queues.
@@ -723,6 +740,25 @@ void score_mfma_launch(int K, const ScoreArgs &A, int grid, hipStream_t st, hipE
     case 3: score_mfma_launch_k<3>(A, grid, st, ev_start, ev_stop); break;
     case 4: score_mfma_launch_k<4>(A, grid, st, ev_start, ev_stop); break;
     default: score_mfma_launch_k<5>(A, grid, st, ev_start, ev_stop); break;
+    }
+}
+
+template <int K>
+static void score_mfma_points_launch_k(const ScoreArgs &A, const ScorePointStrides &ps, int grid, int n_points, hipStream_t st)
+{
+    if (A.net.unclamped_ok)
+        hipLaunchKernelGGL((score_mfma_points_kernel<K, NetShape<K>::H, NetShape<K>::NH, false, mfma_cols(K)>), dim3(grid, n_points), dim3(256), 0, st, A, ps);
+    else
+        hipLaunchKernelGGL((score_mfma_points_kernel<K, NetShape<K>::H, NetShape<K>::NH, true, mfma_cols(K)>), dim3(grid, n_points), dim3(256), 0, st, A, ps);
+}
+
+void score_mfma_points_launch(int K, const ScoreArgs &A, const ScorePointStrides &ps, int grid, int n_points, hipStream_t st)
+{
+    switch (K) {
+    case 2: score_mfma_points_launch_k<2>(A, ps, grid, n_points, st); break;
+    case 3: score_mfma_points_launch_k<3>(A, ps, grid, n_points, st); break;
+    case 4: score_mfma_points_launch_k<4>(A, ps, grid, n_points, st); break;
+    default: score_mfma_points_launch_k<5>(A, ps, grid, n_points, st); break;
     }
 }
 

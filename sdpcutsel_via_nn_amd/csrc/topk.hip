@@ -34,6 +34,8 @@
 //   DIGITS, its compaction                  topk_compact.hip  tk_count_kernel, tk_write_kernel
 //   the sort tail of all but SMALLSORT      topk_sort.hip     tk_tilesort_kernel<TIE>, tk_mergerank_kernel<TIE>, tk_mergerank_big_kernel<TIE>
 // Device code shared between them (TopkWs, resolve_digit, finish_pass, comp_less) and with the score kernels: topk_dev.h.
+// The one-workgroup select-sort-emit algorithm (smallsel_body) is in topk_small_dev.h: tk_smallsel_kernel and the batched
+// tk_points_kernel (points.hip, a workgroup per LP point) are its two hosts.
 
 #include "topk_launch.h"
 

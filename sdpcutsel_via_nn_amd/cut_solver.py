@@ -817,6 +817,20 @@ class GpuCutSelectionMixin(object):
         store.add(lin_expr=rows, rhs=rhs.tolist(), senses=["G"] * r)
         return r
 
+    def separate_points(self, strat, points, sel_size):
+        """One separation round at EACH of several LP points of the bound instance in one device call (sdpcut_round_csr_points):
+        the open nodes of a tree search, the children of a dive.  points [P, L + n]; strat 1, 2 or 4; sel_size as
+        ``_sel_eigcut_by_ordering_on_measure`` takes it (a number of cuts).
+        -> list of P tuples ``(csr, n_total, new_strat, counters)``: ``csr = (indptr, indices, values, rhs)`` is what
+        :meth:`_gpu_add_csr` takes -- the caller adds each node's cuts to that node's LP -- and the rest is what the single-point
+        selection reports (length of the ranking, the combined strategy's switch, its counters).  The arrays are views of the
+        scorer's batch block, good until its next call; the scorer holds no current LP point afterwards."""
+        b = self._gpu_bind()
+        b.drain()
+        rounds = b.scorer.round_csr_points(points, strat, sel_size)
+        b.point_copy, b.scored, b.point_token = None, 0, None      # (the next single-point selection uploads its point)
+        return [((r["indptr"], r["indices"], r["values"], r["rhs"]), r["n_total"], r["new_strat"], r["counters"]) for r in rounds]
+
     def _gen_from_entries(self, entries, feas_sel, vars_values, pair):
         """Generic path for entries that do not carry a candidate index (random strategy, foreign
         lists): host gather of the tiny slices, GPU batched eigen-decomposition, row assembly."""

@@ -1,0 +1,110 @@
+#!/usr/bin/env python3
+"""GPU box: what a separation round costs per LP point when P points of one instance are handed over in ONE call
+(Scorer.round_csr_points) against the same P points through a loop of single-point rounds (Scorer.round_csr).
+
+Lists: the spar020-100-1 dim-3 cover (1051 three-variable candidates) and the spar040-030-1 dim-5 cover (sizes 2..5 mixed).
+P in {1, 8, 64, 256}, strategies 1 and 4, sel_size = 10 % of the list.  Times are host to host (time.perf_counter around the call,
+which ends in the device wait), in ms per call and us per point.
+
+Method: both forms are warmed up at every shape (first launches load code objects); then `--repeats` blocks, each block timing the
+batched form and the loop form one after the other (alternating, so that drift of the box hits both), `--calls` calls per timing.
+Reported: the median over the blocks and their min .. max (the run-to-run spread on this box during this run).
+
+usage: tools/batch_points.py [--repeats R] [--calls C] [--loop-only] [--out [FILE]]
+  --loop-only   time the single-point loop only (runs on a library without the batched entry points: the parent commit's)
+  --out         also write the table to FILE (default profiles/batch_points.txt)"""
+import argparse
+import gc
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+sys.path.insert(0, ROOT)
+import sdpcutsel_via_nn_amd as pkg  # noqa: E402
+from sdpcutsel_via_nn_amd import _capi, harness, networks  # noqa: E402
+
+INST = os.path.join(ROOT, "tests", "golden", "instances")
+LISTS = (("spar020-100-1 dim 3", "spar020-100-1.in", 3), ("spar040-030-1 dim 5", "spar040-030-1.in", 5))
+POINTS = (1, 8, 64, 256)
+
+
+def timed(fn, calls):
+    t0 = time.perf_counter()
+    for _ in range(calls):
+        fn()
+    return (time.perf_counter() - t0) / calls
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=9)
+    ap.add_argument("--calls", type=int, default=0, help="calls per timing (default: about 4096 points' worth, at least 8)")
+    ap.add_argument("--loop-only", action="store_true")
+    ap.add_argument("--out", nargs="?", const=os.path.join(ROOT, "profiles", "batch_points.txt"), default=None)
+    args = ap.parse_args()
+    lines = ["# tools/batch_points.py --repeats %d%s: ms per call, us per point; median over the blocks (min .. max)"
+             % (args.repeats, " --loop-only" if args.loop_only else ""),
+             "# batched = round_csr_points(P points); loop = P x round_csr(point=p); sel_size = 10 % of the list"]
+    gc.collect()
+    gc.freeze()
+    for title, fname, dim in LISTS:
+        inst = harness.parse_boxqp(os.path.join(INST, fname))
+        S, ks, N = _capi.enumerate_cover(inst["adj"], dim)
+        n = inst["nb_vars"]
+        sc = pkg.Scorer(0)
+        for k in (2, 3, 4, 5):
+            sc.set_network(k, *networks.load_network(k))
+        sc.set_instance(n, inst["Q_arr"])
+        sc.set_candidates(S, ks)
+        sel = max(1, int(0.1 * N))
+        pts_all = np.stack([harness.random_mccormick_point(n, np.random.default_rng(100 + i)) for i in range(max(POINTS))])
+        sizes = ", ".join("%d of %d" % (int((ks == k).sum()), k) for k in (2, 3, 4, 5) if (ks == k).any())
+        lines.append("")
+        lines.append("%s: %d candidates (%s), head %d" % (title, N, sizes, sel))
+        lines.append("  strat    P | batched ms/call          us/point | loop ms/call             us/point | loop / batched")
+        for strat in (1, 4):
+            for P in POINTS:
+                pts = np.ascontiguousarray(pts_all[:P])
+                rows = [pts[p] for p in range(P)]
+                calls = args.calls or max(8, 4096 // P)
+
+                def loop():
+                    for v in rows:
+                        sc.round_csr(strat, sel, point=v)
+
+                def batched():
+                    sc.round_csr_points(pts, strat, sel)
+
+                forms = [loop] if args.loop_only else [batched, loop]
+                for f in forms:                      # warm-up at this shape
+                    timed(f, max(4, calls // 4))
+                t = {f.__name__: [] for f in forms}
+                for _ in range(args.repeats):
+                    for f in forms:
+                        t[f.__name__].append(timed(f, calls))
+
+                def cell(name):
+                    a = np.array(t[name]) * 1e3
+                    return "%8.4f (%7.4f .. %7.4f) %8.2f" % (np.median(a), a.min(), a.max(), np.median(a) * 1e3 / P)
+                if args.loop_only:
+                    lines.append("  %5d %4d | %-40s | %s |" % (strat, P, "-", cell("loop")))
+                else:
+                    ratio = np.median(t["loop"]) / np.median(t["batched"])
+                    lines.append("  %5d %4d | %s | %s | %6.2f" % (strat, P, cell("batched"), cell("loop"), ratio))
+                print(lines[-1], flush=True)
+        if not args.loop_only:
+            lines.append("  points redone through the single-point round: %d, selection fallbacks: %d"
+                         % (sc.get_stat(_capi.STAT_POINTS_REDONE), sc.get_stat(_capi.STAT_SELECT_FALLBACKS)))
+        sc.close()
+    text = "\n".join(lines) + "\n"
+    print(text)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text)
+
+
+if __name__ == "__main__":
+    main()
