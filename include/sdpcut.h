@@ -237,6 +237,22 @@ int sdpcut_set_candidates_cover(sdpcut_handle h, const uint8_t *adjacency, int32
                                 int64_t *count_out);
 
 /*
+ * The covers on a chordal extension of the sparsity pattern (ch_ext of _get_sdp_vertex_cover, cut_select_qp.py:385-455), on the
+ * device: same sets, same order as the host twins.  adjacency_orig is the pattern of Q, adjacency_ext its chordal extension
+ * (sdpcut_chordal_extension, or the caller's own); both as in sdpcut_set_candidates_cover.
+ *   ch_ext =  0  P^E_dim: sdpcut_set_candidates_cover on adjacency_orig (adjacency_ext may be NULL);
+ *   ch_ext =  1  P^bar(E)_dim: the same enumeration on adjacency_ext (adjacency_orig may be NULL), any dim 3..5 -- what the
+ *                reference's loops do once Q_adj is replaced (:396);
+ *   ch_ext =  2  bar(P*_3), :429-449: triangles of the extended graph with at least 2 of their 3 edges in the original one, and
+ *                the original edges that belong to none (sdpcut_enumerate_cover_ch).  dim must be 3: the reference silently
+ *                degrades ch_ext = 2 to ch_ext = 1 at dim 4 and 5 (:456-522 never look at it), this call refuses it;
+ *   ch_ext = -1  P^E+_3, :450-455: all triples = the dim-3 cover of the complete graph (both adjacencies may be NULL); dim 3 only.
+ * Guards, count_out and max_subs as in sdpcut_set_candidates_cover.
+ */
+int sdpcut_set_candidates_cover_ch(sdpcut_handle h, const uint8_t *adjacency_ext, const uint8_t *adjacency_orig, int32_t ch_ext,
+                                   int32_t dim, int64_t max_subs, int64_t *count_out);
+
+/*
  * The two candidate lists of a QCQP instance (replaces __get_vertex_cover, cut_select_qcqp.py:314-334, including its
  * list-membership intersection): h_in receives the sub-problems of the cover of `adjacency_all` (objective + all
  * constraints) that also belong to the cover of `adjacency_obj` (self._agg_list, :331), h_out the others
@@ -615,6 +631,33 @@ int sdpcut_last_timing(sdpcut_handle h, double *ms, int n);
  */
 int sdpcut_enumerate_cover(int32_t nb_vars, const uint8_t *adjacency, int32_t dim, int64_t max_out,
                            int32_t *set_inds_out, int32_t *ks_out, int64_t *count_out);
+
+/*
+ * Host twin of sdpcut_set_candidates_cover_ch at dim 3: ch_ext = 0 / 1 / -1 are sdpcut_enumerate_cover on adjacency_orig /
+ * adjacency_ext / the complete graph, ch_ext = 2 is bar(P*_3).  Per edge (i1,i2) of the EXTENDED graph, in lexicographic order:
+ * every forward triangle (i3 > i2 adjacent to both in the extended graph) with at least 2 of its 3 edges in the ORIGINAL graph;
+ * if there is none and no smaller i3 != i1 closes such a triangle and (i1,i2) is an original edge, the pair.  Outputs as in
+ * sdpcut_enumerate_cover.  An adjacency the mode does not read may be NULL.  Host function, no handle needed.
+ */
+int sdpcut_enumerate_cover_ch(int32_t nb_vars, const uint8_t *adjacency_ext, const uint8_t *adjacency_orig, int32_t ch_ext,
+                              int64_t max_out, int32_t *set_inds_out, int32_t *ks_out, int64_t *count_out);
+
+/*
+ * Chordal extension of a sparsity pattern by the elimination game (replaces chompack's symbolic factorisation,
+ * cut_select_qp.py:386-396).  adjacency: [nb_vars][nb_vars] bytes, symmetrised, diagonal ignored; 2 <= nb_vars <= 1024
+ * (SDPCUT_EINVAL otherwise).  For each vertex v of the order, the not-yet-eliminated neighbours of v in the current filled graph
+ * become a clique, then v is eliminated.
+ *   ext_out   [nb_vars][nb_vars] bytes: the original edges plus the fill, symmetric, zero diagonal -- a chordal graph;
+ *   order_out [nb_vars]: the order used, a perfect elimination ordering of ext_out;
+ *   fill_out  the number of fill edges.
+ * order_in (may be NULL) must be a permutation of 0..nb_vars-1 (SDPCUT_EINVAL otherwise): a caller who holds the reference's AMD
+ * permutation gets the reference's pattern exactly.  With NULL the order is greedy minimum degree on the elimination graph: at
+ * each step the not-yet-eliminated vertex with the fewest not-yet-eliminated neighbours in the current filled graph, ties to the
+ * lowest index.  This is NOT cvxopt's AMD: cover sizes can differ from the published nb_subproblems.
+ * Host function, no handle and no GPU needed.
+ */
+int sdpcut_chordal_extension(int32_t nb_vars, const uint8_t *adjacency, const int32_t *order_in, uint8_t *ext_out,
+                             int32_t *order_out, int64_t *fill_out);
 
 /*
  * Triangle inequalities (SURVEY.md section 8 f row 3; cut_select_qp.py:799-863).

@@ -74,6 +74,7 @@ SIGNATURES = {
     "sdpcut_set_candidates": [_vp, _c.c_int64, _i32p, _c.c_int32, _i32p, _c.c_int64],
     "sdpcut_set_candidates_philox": [_vp, _c.c_int32, _c.c_int64, _c.c_uint64, _c.c_int64],
     "sdpcut_set_candidates_cover": [_vp, _c.POINTER(_c.c_uint8), _c.c_int32, _c.c_int64, _i64p],
+    "sdpcut_set_candidates_cover_ch": [_vp, _c.POINTER(_c.c_uint8), _c.POINTER(_c.c_uint8), _c.c_int32, _c.c_int32, _c.c_int64, _i64p],
     "sdpcut_set_candidates_cover_split": [_vp, _vp, _c.POINTER(_c.c_uint8), _c.POINTER(_c.c_uint8), _c.c_int32, _i64p, _i64p],
     "sdpcut_get_candidates": [_vp, _c.c_int64, _i64p, _i32p, _i32p],
     "sdpcut_set_builtin_networks": [_vp, _c.c_int],
@@ -116,6 +117,8 @@ SIGNATURES = {
     "sdpcut_tri_get_triples": [_vp, _i32p, _c.POINTER(_c.c_uint8)],
     "sdpcut_tri_separate": [_vp, _c.c_int64, _i64p, _dp, _i64p, _i64p],
     "sdpcut_enumerate_cover": [_c.c_int32, _c.POINTER(_c.c_uint8), _c.c_int32, _c.c_int64, _i32p, _i32p, _i64p],
+    "sdpcut_enumerate_cover_ch": [_c.c_int32, _c.POINTER(_c.c_uint8), _c.POINTER(_c.c_uint8), _c.c_int32, _c.c_int64, _i32p, _i32p, _i64p],
+    "sdpcut_chordal_extension": [_c.c_int32, _c.POINTER(_c.c_uint8), _i32p, _c.POINTER(_c.c_uint8), _i32p, _i64p],
 }
 _RESTYPES = {"sdpcut_last_error": _c.c_char_p}
 # the reference's own FFI (cut_select_qp.py:297-303): ALL that libsdpcut_nns.so exports (include/sdpcut_nns.h)
@@ -174,19 +177,76 @@ class SdpCutError(RuntimeError):
     pass
 
 
-def enumerate_cover(adjacency, dim, max_subs=None):
+def _adj_u8(adjacency, n=None):
+    adj = np.ascontiguousarray(np.asarray(adjacency) != 0, dtype=np.uint8)
+    if adj.ndim != 2 or adj.shape[0] != adj.shape[1] or (n is not None and adj.shape[0] != n):
+        raise ValueError("adjacency must be square" if n is None else "adjacency must be [n, n]")
+    return adj
+
+
+_u8p = _c.POINTER(_c.c_uint8)
+
+
+def chordal_extension(adjacency, order=None):
+    """Chordal extension of a sparsity pattern by the elimination game (sdpcut_chordal_extension; replaces chompack's symbolic
+    factorisation, cut_select_qp.py:386-396).  order: a permutation of 0..n-1 to eliminate in (the reference's own AMD permutation
+    reproduces the reference's pattern); None = greedy minimum degree on the elimination graph, ties to the lowest index.
+    -> (ext bool [n, n]: original edges plus fill, zero diagonal; order int32 [n]: the order used; number of fill edges)."""
+    lib = load_library()
+    adj = _adj_u8(adjacency)
+    n = adj.shape[0]
+    if order is not None:
+        order = np.ascontiguousarray(order, dtype=np.int32)
+        if order.shape != (n,):
+            raise ValueError("order must be a permutation of 0..n-1")
+    ext = np.zeros((n, n), dtype=np.uint8)
+    used = np.zeros(n, dtype=np.int32)
+    fill = _c.c_int64(0)
+    rc = lib.sdpcut_chordal_extension(n, adj.ctypes.data_as(_u8p), _ptr(order, _i32p), ext.ctypes.data_as(_u8p), _ptr(used, _i32p),
+                                      ctypes.byref(fill))
+    if rc != 0:
+        raise ValueError("sdpcut_chordal_extension: 2 <= n <= 1024 and order must be a permutation of 0..n-1")
+    return ext.astype(bool), used, int(fill.value)
+
+
+def _cover_patterns(adj, dim, ch_ext, order):
+    """(extended pattern | None, dim checked) for a ch_ext of 1, 2 or -1"""
+    if ch_ext not in (1, 2, -1):
+        raise ValueError("ch_ext must be 0 (P^E), 1 (P^bar(E)), 2 (bar(P*_3)) or -1 (P^E+_3)")
+    if ch_ext in (2, -1) and int(dim) != 3:
+        raise ValueError("ch_ext = 2 and ch_ext = -1 are covers of dimension 3 only")
+    if ch_ext == -1:
+        return None
+    return np.ascontiguousarray(chordal_extension(adj, order)[0], dtype=np.uint8)
+
+
+def enumerate_cover(adjacency, dim, max_subs=None, ch_ext=0, order=None):
     """Index sets of the semidefinite vertex cover P^E_dim in the reference's order
     (cut_select_qp.py:399-524).  adjacency: [n, n] array, non-zero = edge.
     -> (set_inds int32 [N, 5] padded with -1, ks int32 [N], N).  If max_subs is given and
-    N >= max_subs only the count is returned (arrays None), like the reference's RAM guard."""
+    N >= max_subs only the count is returned (arrays None), like the reference's RAM guard.
+
+    ch_ext (cut_select_qp.py:385-455): 1 = P^bar(E)_dim, the same cover on the chordal extension of the pattern
+    (:func:`chordal_extension` with ``order``); 2 = bar(P*_3), the triangles of the extension with at least 2 original edges and
+    the original edges in none (sdpcut_enumerate_cover_ch); -1 = P^E+_3, all triples.  2 and -1 need dim = 3: the reference
+    silently degrades ch_ext = 2 to ch_ext = 1 at dim 4 and 5, here it is refused."""
     lib = load_library()
-    adj = np.ascontiguousarray(np.asarray(adjacency) != 0, dtype=np.uint8)
+    adj = _adj_u8(adjacency)
     n = adj.shape[0]
-    if adj.shape != (n, n):
-        raise ValueError("adjacency must be square")
+    if ch_ext == 0:
+        def call(max_out, sets, ks, cnt):
+            return lib.sdpcut_enumerate_cover(n, adj.ctypes.data_as(_u8p), int(dim), max_out, sets, ks, cnt)
+    else:
+        ext = _cover_patterns(adj, dim, ch_ext, order)
+        if ch_ext == 1:      # any dim: the enumeration of ch_ext = 0 on the extended pattern
+            def call(max_out, sets, ks, cnt):
+                return lib.sdpcut_enumerate_cover(n, ext.ctypes.data_as(_u8p), int(dim), max_out, sets, ks, cnt)
+        else:
+            def call(max_out, sets, ks, cnt):
+                return lib.sdpcut_enumerate_cover_ch(n, ext.ctypes.data_as(_u8p) if ext is not None else None, adj.ctypes.data_as(_u8p),
+                                                     int(ch_ext), max_out, sets, ks, cnt)
     cnt = _c.c_int64(0)
-    u8 = adj.ctypes.data_as(_c.POINTER(_c.c_uint8))
-    rc = lib.sdpcut_enumerate_cover(n, u8, int(dim), 0, None, None, ctypes.byref(cnt))
+    rc = call(0, None, None, ctypes.byref(cnt))
     if rc != 0:
         raise ValueError("sdpcut_enumerate_cover: bad arguments (dim must be 3..5)")
     N = cnt.value
@@ -194,7 +254,7 @@ def enumerate_cover(adjacency, dim, max_subs=None):
         return None, None, N
     sets = np.empty((max(N, 1), 5), dtype=np.int32)
     ks = np.empty(max(N, 1), dtype=np.int32)
-    rc = lib.sdpcut_enumerate_cover(n, u8, int(dim), N, _ptr(sets, _i32p), _ptr(ks, _i32p), ctypes.byref(cnt))
+    rc = call(N, _ptr(sets, _i32p), _ptr(ks, _i32p), ctypes.byref(cnt))
     assert rc == 0 and cnt.value == N
     return sets[:N], ks[:N], N
 
@@ -295,15 +355,22 @@ class Scorer(object):
         self.N, self.base = int(count), int(first_id)
         self.row_len = int(k) * (int(k) + 3) // 2
 
-    def set_candidates_cover(self, adjacency, dim, max_subs=0):
+    def set_candidates_cover(self, adjacency, dim, max_subs=0, ch_ext=0, order=None):
         """semidefinite vertex cover enumerated on the device into this handle's list
-        -> number of candidates (with max_subs > 0 and count >= max_subs the list is NOT replaced)"""
+        -> number of candidates (with max_subs > 0 and count >= max_subs the list is NOT replaced).
+        ch_ext, order: the covers on a chordal extension, as in :func:`enumerate_cover` (sdpcut_set_candidates_cover_ch)"""
         adj = np.ascontiguousarray(np.asarray(adjacency) != 0, dtype=np.uint8)
         if adj.shape != (self.nb_vars, self.nb_vars):
             raise ValueError("adjacency must be [n, n]")
         cnt = _c.c_int64(0)
-        self._check(self._lib.sdpcut_set_candidates_cover(self._h, adj.ctypes.data_as(_c.POINTER(_c.c_uint8)), int(dim),
-                                                          int(max_subs or 0), ctypes.byref(cnt)))
+        if ch_ext == 0:
+            self._check(self._lib.sdpcut_set_candidates_cover(self._h, adj.ctypes.data_as(_c.POINTER(_c.c_uint8)), int(dim),
+                                                              int(max_subs or 0), ctypes.byref(cnt)))
+        else:
+            ext = _cover_patterns(adj, dim, ch_ext, order)
+            self._check(self._lib.sdpcut_set_candidates_cover_ch(self._h, ext.ctypes.data_as(_u8p) if ext is not None else None,
+                                                                 adj.ctypes.data_as(_u8p), int(ch_ext), int(dim), int(max_subs or 0),
+                                                                 ctypes.byref(cnt)))
         if not (max_subs and cnt.value >= max_subs):
             self.N, self.base = int(cnt.value), 0
             self.row_len = int(dim) * (int(dim) + 3) // 2      # upper bound: the largest size present is <= dim

@@ -318,6 +318,123 @@ int run_cover(sdpcut_ctx *h, const std::vector<uint64_t> &adj_host, const std::v
     return SDPCUT_OK;
 }
 
+// bar(P*_3) on a chordal extension (cut_select_qp.py:429-449, csrc/cover.cpp: sdpcut_enumerate_cover_ch with ch_ext = 2).
+// Same three steps as above with one wave per edge (i1,i2) of the EXTENDED graph and one lane per qualifying forward
+// triangle -- third vertices adjacent to both ends in the extended graph with at least 2 of the 3 edges in the ORIGINAL
+// one -- in rounds of 64.  There is no subtree below a triangle here: every lane emits exactly one set, so the wave's
+// exclusive prefix sum of the per-lane counts is the lane's rank m itself, and an edge's count is a popcount.  An edge
+// without a qualifying forward triangle emits its pair iff no smaller vertex closes a qualifying triangle and the edge is
+// an original one.  per_edge / off have the five columns of cover_scan_kernel ({total, n2, n3, 0, 0}).
+template <int W, bool WRITE>
+__global__ __launch_bounds__(256) void cover3_ch_kernel(const uint64_t *ext, const uint64_t *orig, const int32_t *edges,
+                                                        int64_t n_edges, int32_t *per_edge, const int64_t *off, Sink sk)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t e = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (e >= n_edges) return;          // wave-uniform
+    const int i1 = edges[2 * e], i2 = edges[2 * e + 1];
+    const bool c12 = (orig[(size_t)i1 * W + (i2 >> 6)] >> (i2 & 63)) & 1;
+    Bits<W> q;          // third vertices that close a qualifying triangle (neither i1 nor i2: the diagonals are clear)
+#pragma unroll
+    for (int u = 0; u < W; ++u) {
+        const uint64_t o1 = orig[(size_t)i1 * W + u], o2 = orig[(size_t)i2 * W + u];
+        q.w[u] = ext[(size_t)i1 * W + u] & ext[(size_t)i2 * W + u] & (c12 ? (o1 | o2) : (o1 & o2));
+    }
+    const Bits<W> f3 = above<W>(q, i2);
+    const int n3 = popcount<W>(f3);
+    const int n2 = (n3 == 0 && c12 && !any_below<W>(q, i2)) ? 1 : 0;
+    if constexpr (!WRITE) {
+        if (lane == 0) {
+            per_edge[5 * e] = n2 + n3;
+            per_edge[5 * e + 1] = n2;
+            per_edge[5 * e + 2] = n3;
+            per_edge[5 * e + 3] = 0;
+            per_edge[5 * e + 4] = 0;
+        }
+    } else {
+        const int64_t base = off[5 * e];
+        if (n2 && lane == 0) {
+            const int64_t p = off[5 * e + 1];
+            sk.set5[base * 5 + 0] = i1; sk.set5[base * 5 + 1] = i2;
+            sk.set5[base * 5 + 2] = -1; sk.set5[base * 5 + 3] = -1; sk.set5[base * 5 + 4] = -1;
+            sk.ks[base] = 2;
+            sk.soa[2][p] = i1;
+            sk.soa[2][sk.cls_n[2] + p] = i2;
+            sk.orig[2][p] = (int32_t)base;
+        }
+        const int64_t cbase = off[5 * e + 2];
+        for (int m = lane; m < n3; m += 64) {
+            const int i3 = nth_bit<W>(f3, m);
+            const int64_t g = base + m, p = cbase + m;
+            sk.set5[g * 5 + 0] = i1; sk.set5[g * 5 + 1] = i2; sk.set5[g * 5 + 2] = i3;
+            sk.set5[g * 5 + 3] = -1; sk.set5[g * 5 + 4] = -1;
+            sk.ks[g] = 3;
+            sk.soa[3][p] = i1;
+            sk.soa[3][sk.cls_n[3] + p] = i2;
+            sk.soa[3][2 * sk.cls_n[3] + p] = i3;
+            sk.orig[3][p] = (int32_t)g;
+        }
+    }
+}
+
+template <int W>
+int run_cover_ch(sdpcut_ctx *h, const std::vector<uint64_t> &ext_host, const std::vector<uint64_t> &orig_host,
+                 const std::vector<int32_t> &edges, int64_t max_subs, int64_t *count_out)
+{
+    const int64_t E = (int64_t)(edges.size() / 2);
+    uint64_t *d_ext = nullptr, *d_orig = nullptr;
+    int32_t *d_edges = nullptr, *d_per = nullptr;
+    int64_t *d_off = nullptr;
+    auto cleanup = [&]() { hipFree(d_ext); hipFree(d_orig); hipFree(d_edges); hipFree(d_per); hipFree(d_off); };
+#define COVER_TRY(expr)                                                                         \
+    do {                                                                                        \
+        hipError_t e__ = (expr);                                                                \
+        if (e__ != hipSuccess) {                                                                \
+            cleanup();                                                                          \
+            return sdpcut_fail(h, SDPCUT_EHIP, std::string(#expr) + ": " + hipGetErrorString(e__)); \
+        }                                                                                       \
+    } while (0)
+    COVER_TRY(hipMalloc((void **)&d_ext, ext_host.size() * 8));
+    COVER_TRY(hipMalloc((void **)&d_orig, orig_host.size() * 8));
+    COVER_TRY(hipMalloc((void **)&d_edges, (size_t)(E < 1 ? 1 : E) * 8));
+    COVER_TRY(hipMalloc((void **)&d_per, (size_t)(E < 1 ? 1 : E) * 20));
+    COVER_TRY(hipMalloc((void **)&d_off, (size_t)(E + 1) * 40));
+    COVER_TRY(hipMemcpy(d_ext, ext_host.data(), ext_host.size() * 8, hipMemcpyHostToDevice));
+    COVER_TRY(hipMemcpy(d_orig, orig_host.data(), orig_host.size() * 8, hipMemcpyHostToDevice));
+    if (E > 0) COVER_TRY(hipMemcpy(d_edges, edges.data(), (size_t)E * 8, hipMemcpyHostToDevice));
+    const unsigned grid = (unsigned)((E + 3) / 4);
+    Sink sk{};
+    if (E > 0) hipLaunchKernelGGL((cover3_ch_kernel<W, false>), dim3(grid), dim3(256), 0, h->stream, d_ext, d_orig, d_edges, E, d_per,
+                                  (const int64_t *)nullptr, sk);
+    hipLaunchKernelGGL(cover_scan_kernel, dim3(1), dim3(1024), 0, h->stream, d_per, E, d_off);
+    COVER_TRY(hipGetLastError());
+    int64_t totals[5] = {0, 0, 0, 0, 0};
+    COVER_TRY(hipMemcpyAsync(totals, d_off + 5 * E, 40, hipMemcpyDeviceToHost, h->stream));
+    COVER_TRY(sdpcut_sync(h));
+    *count_out = totals[0];
+    if (totals[0] > 0x7fffffffLL) { cleanup(); return sdpcut_fail(h, SDPCUT_EINVAL, "cover has more than 2^31 - 1 candidates"); }
+    if (max_subs > 0 && totals[0] >= max_subs) { cleanup(); return SDPCUT_OK; }     // count only (the reference's guard)
+    int64_t cnt[SDPCUT_MAX_K + 1] = {0, 0, totals[1], totals[2], 0, 0};
+    int rc = alloc_candidates(h, totals[0], cnt, 0);
+    if (rc) { cleanup(); return rc; }
+    if (totals[0] > 0) {
+        sk.set5 = h->d_set_orig;
+        sk.ks = h->d_k;
+        for (int s = 2; s <= SDPCUT_MAX_K; ++s) {
+            sk.soa[s] = h->bucket[s].d_set;
+            sk.orig[s] = h->bucket[s].d_orig;
+            sk.cls_n[s] = cnt[s];
+        }
+        hipLaunchKernelGGL((cover3_ch_kernel<W, true>), dim3(grid), dim3(256), 0, h->stream, d_ext, d_orig, d_edges, E, d_per,
+                           (const int64_t *)d_off, sk);
+        COVER_TRY(hipGetLastError());
+        COVER_TRY(sdpcut_sync(h));
+    }
+    cleanup();
+#undef COVER_TRY
+    return SDPCUT_OK;
+}
+
 } // namespace
 
 extern "C" int sdpcut_set_candidates_cover(sdpcut_handle h, const uint8_t *adjacency, int32_t dim, int64_t max_subs,
@@ -346,5 +463,49 @@ extern "C" int sdpcut_set_candidates_cover(sdpcut_handle h, const uint8_t *adjac
     case 2: return run_cover<2>(h, adj, edges, dim, max_subs, count_out);
     case 4: return run_cover<4>(h, adj, edges, dim, max_subs, count_out);
     default: return run_cover<16>(h, adj, edges, dim, max_subs, count_out);
+    }
+}
+
+// Covers on a chordal extension (include/sdpcut.h).  ch_ext = 0, 1, -1 are the enumeration above on the original pattern,
+// the extended one and the complete graph; ch_ext = 2 (dim 3 only) has its own kernels.
+extern "C" int sdpcut_set_candidates_cover_ch(sdpcut_handle h, const uint8_t *adjacency_ext, const uint8_t *adjacency_orig,
+                                              int32_t ch_ext, int32_t dim, int64_t max_subs, int64_t *count_out)
+{
+    if (!h) return SDPCUT_EINVAL;
+    SDPCUT_NO_PENDING(h);
+    if (h->nb_vars == 0) return sdpcut_fail(h, SDPCUT_ESTATE, "set_instance first");
+    if (ch_ext < -1 || ch_ext > 2) return sdpcut_fail(h, SDPCUT_EINVAL, "ch_ext must be 0 (P^E), 1 (P^bar(E)), 2 (bar(P*_3)) or -1 (P^E+_3)");
+    if ((ch_ext == 2 || ch_ext == -1) && dim != 3)
+        return sdpcut_fail(h, SDPCUT_EINVAL, "ch_ext = 2 and ch_ext = -1 are covers of dimension 3 only");
+    if (dim < 3 || dim > SDPCUT_MAX_K || !count_out || max_subs < 0 || ((ch_ext == 0 || ch_ext == 2) && !adjacency_orig) ||
+        ((ch_ext == 1 || ch_ext == 2) && !adjacency_ext))
+        return sdpcut_fail(h, SDPCUT_EINVAL, "bad cover arguments (dim must be 3..5)");
+    const int n = h->nb_vars;
+    if (n > 1024) return sdpcut_fail(h, SDPCUT_EINVAL, "device cover enumeration supports nb_vars <= 1024");
+    if (ch_ext == 0) return sdpcut_set_candidates_cover(h, adjacency_orig, dim, max_subs, count_out);
+    if (ch_ext == 1) return sdpcut_set_candidates_cover(h, adjacency_ext, dim, max_subs, count_out);
+    if (ch_ext == -1) {
+        const std::vector<uint8_t> complete((size_t)n * n, 1);
+        return sdpcut_set_candidates_cover(h, complete.data(), dim, max_subs, count_out);
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int W = n <= 64 ? 1 : n <= 128 ? 2 : n <= 256 ? 4 : 16;
+    std::vector<uint64_t> ext((size_t)n * W, 0), orig((size_t)n * W, 0);
+    std::vector<int32_t> edges;
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) {
+            if (i == j) continue;
+            if (adjacency_ext[(size_t)i * n + j] || adjacency_ext[(size_t)j * n + i]) {
+                ext[(size_t)i * W + (j >> 6)] |= 1ull << (j & 63);
+                if (i < j) { edges.push_back(i); edges.push_back(j); }      // lexicographic by construction
+            }
+            if (adjacency_orig[(size_t)i * n + j] || adjacency_orig[(size_t)j * n + i]) orig[(size_t)i * W + (j >> 6)] |= 1ull << (j & 63);
+        }
+    *count_out = 0;
+    switch (W) {
+    case 1: return run_cover_ch<1>(h, ext, orig, edges, max_subs, count_out);
+    case 2: return run_cover_ch<2>(h, ext, orig, edges, max_subs, count_out);
+    case 4: return run_cover_ch<4>(h, ext, orig, edges, max_subs, count_out);
+    default: return run_cover_ch<16>(h, ext, orig, edges, max_subs, count_out);
     }
 }

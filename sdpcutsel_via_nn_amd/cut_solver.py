@@ -1002,14 +1002,20 @@ class CutSolver(GpuCutSelectionMixin):
     _CONVERGENCE_TOL = 10 ** (-3)         # cut_select_qp.py:29
 
     def cut_select_algo(self, filename, dim, sel_size, strat=2, nb_rounds_cuts=20, term_on=False,
-                        triangle_on=False, strong_only=False, max_subs=_THRES_MAX_SUBS, on_round=None, plots=False, sol=0):
+                        triangle_on=False, strong_only=False, max_subs=_THRES_MAX_SUBS, on_round=None, plots=False, sol=0,
+                        ch_ext=0):
         """Cutting-plane rounds on a BoxQP ``.in`` file, same arguments and default return tuple as
         the reference's entry point (cut_select_qp.py:73-221), with HiGHS as LP solver, the native
         cover enumeration and the GPU selection / generation / triangle separation in between.
         ``max_subs=None`` lifts the reference's 4e6 candidate guard (:117-120); ``on_round(r, log)`` is
         called after every LP solve (progress of long runs).  Strategy 0 adds
         the fully dense eigen-cuts of :meth:`_gen_dense_eigcuts` instead of a selection (the cover is still enumerated: the tuple
-        reports its size); chordal extensions are out of scope.  ``CutSolver(exact_sdp=True)`` also takes strategy 3
+        reports its size).  ``ch_ext`` (:84): 0 = P^E_dim, 1 = P^bar(E)_dim, 2 = bar(P*_3), the covers on a chordal extension of
+        the sparsity pattern -- the elimination game under greedy minimum degree (``_capi.chordal_extension``), not cvxopt's AMD,
+        so the number of candidates can differ from the published one.  As in the reference once ``self._Q_adj`` is replaced
+        (:396), the McCormick rows and the triangle inequalities then use the EXTENDED pattern, which ``self._Q_adj`` holds
+        afterwards.  ``ch_ext=2`` needs ``dim=3`` (the reference silently degrades it to ``ch_ext=1`` at dim 4 and 5; here it is
+        refused).  ``CutSolver(exact_sdp=True)`` also takes strategy 3
         (optimality via the exact SDP solution) and -1 (figure 8); with ``strat=-1, plots=True`` the return is the reference's
         ``(gap_closed_percent, rounds_stats, round_std_devs, rounds_all_cuts)`` with the gap closed measured against ``sol``
         (:209-215).  ``plots`` with another strategy is out of scope.
@@ -1023,6 +1029,7 @@ class CutSolver(GpuCutSelectionMixin):
         assert not plots or strat == -1, "plots=True returns the figure-8 tuple: strat=-1 only"
         assert 0 < sel_size, "The selection size must be a % or number (of cuts) >0!"
         assert dim <= 5, "Keep SDP vertex cover low-dimensional (<=5)!"
+        assert (ch_ext in [0, 1, 2]), "Chordal extension flags: 0-P^E_3, 1-P^bar(E)_3, 2-bar(P*_3)!"      # :94
         t_start = clock()
         inst = harness.parse_boxqp(filename)
         self._dim = dim
@@ -1033,7 +1040,10 @@ class CutSolver(GpuCutSelectionMixin):
         # the cover is enumerated on the device, straight into the scorer's candidate list
         sc = self._gpu_new_scorer()
         sc.set_instance(self._nb_vars, np.asarray(self._Q_arr, dtype=np.float64))
-        n_cand = sc.set_candidates_cover(inst["adj"], dim, max_subs=max_subs or 0)
+        n_cand = sc.set_candidates_cover(inst["adj"], dim, max_subs=max_subs or 0, ch_ext=ch_ext)
+        if ch_ext:      # :396 -- everything after the cover sees the extended pattern
+            inst = dict(inst, adj=_capi.chordal_extension(inst["adj"])[0])
+            self._Q_adj = inst["adj"]
         if (max_subs and n_cand >= max_subs) or nb_rounds_cuts == 0:
             sc.close()
             return [0, 0], clock() - t_start, 0, 0, [0], 0, n_cand                      # the reference's guard tuple
