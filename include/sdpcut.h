@@ -481,6 +481,45 @@ int sdpcut_round_csr_points(sdpcut_handle h, int32_t n_points, const double *poi
                             sdpcut_round_csr_t *out /* [n_points] */);
 
 /*
+ * Diverse selection: a parallelism filter on the ranked head.  A round takes the first sel_size entries of its ranking however
+ * similar their cuts are; candidates that share two of three variables share five of nine LP columns and their eigen-cuts are often
+ * nearly the same row.  These calls walk a POOL in rank order and accept an entry only if its cut is not too parallel to the cuts
+ * accepted before it -- the second criterion of every MIP solver's cut selector.  The rule ("Diverse selection"):
+ *   row a_t of entry t    what sdpcut_cut_rows gives for the candidate at the current point, on its LP columns
+ *                         [L + i for i in set_inds] + Xarr_inds; the right-hand side takes no part
+ *   eligible              lam_min < -1e-15 and ||a_t|| > 0
+ *   walk t = 0, 1, ...    an eligible entry is accepted iff fewer than the quota are accepted so far and every accepted s has
+ *                         |<a_s, a_t>| <= max_parallel ||a_s|| ||a_t||  (inner product over the shared LP columns: x_c for every
+ *                         common variable c, X_cd for common c <= d; compared without a division)
+ *   max_parallel >= 1     no comparison at all: the first `quota` eligible entries (a list may hold a candidate twice)
+ * The walk ends with the entry that fills the quota.  info: pool = entries of the pool, examined = entries the walk looked at,
+ * skipped_nonviolated = those that were not eligible, rejected_parallel = eligible ones refused as parallel
+ * (examined = accepted + skipped_nonviolated + rejected_parallel).
+ *
+ * sdpcut_round_csr_diverse: one round as sdpcut_round_csr (vars_values NULL keeps the current point), strategies 1, 2 and 4.  The
+ * pool is the first min(pool_size, length) entries of what sdpcut_rank(h, strat, sel_size, max_out = pool_size, ...) returns --
+ * sel_size stays the combined strategy's quota; n_total, new_strat and counters are those of that call; SDPCUT_OPT_EXACT_HEAD is
+ * honoured as that call honours it.  *out is the block of sdpcut_round_csr for the ACCEPTED entries in rank order: cap =
+ * min(sel_size, pool), n_out accepted entries, every one with its row (n_rows == n_out, row_entry[r] == r).  Synchronous; the
+ * pointers stay valid until the next call on the handle.  With max_parallel = 1 and pool_size = sel_size the block equals that of
+ * sdpcut_round_csr restricted to its cut-yielding entries, bit for bit.
+ *
+ * sdpcut_filter_parallel: the same walk over `count` candidates in an order the CALLER supplies (local ids; a QCQP caller's
+ * concatenated list, a merged sharded head, a ranking of one's own) at the current point: keep_out[i] = 1 iff entry i is accepted.
+ *
+ * SDPCUT_EINVAL: a strategy outside {1, 2, 4}, max_parallel outside [0, 1] or NaN, sel_size / quota < 1, pool_size < sel_size, a
+ * pool or count above SDPCUT_DIVERSE_MAX_POOL, an id outside the list.  SDPCUT_ESTATE: no instance, candidates or point; a round
+ * pending.  Device memory: per pool entry 250 bytes, and -- only when max_parallel < 1 -- the lower-triangular bit matrix of the pair
+ * test, 16.8 MB at a pool of 16384 (4 KB at 256); allocated by the first call, grown to the largest pool, freed with the handle.
+ */
+#define SDPCUT_DIVERSE_MAX_POOL 16384
+typedef struct sdpcut_diverse_info { int64_t pool, examined, skipped_nonviolated, rejected_parallel; } sdpcut_diverse_info_t;
+int sdpcut_round_csr_diverse(sdpcut_handle h, const double *vars_values, int strat, int64_t sel_size, int64_t pool_size,
+                             double max_parallel, sdpcut_round_csr_t *out, sdpcut_diverse_info_t *info);
+int sdpcut_filter_parallel(sdpcut_handle h, int64_t count, const int64_t *idx, int64_t quota, double max_parallel, uint8_t *keep_out,
+                           sdpcut_diverse_info_t *info);
+
+/*
  * Dense eigen-cuts: strategy 0 of cut_select_algo, the paper's baseline (replaces __gen_dense_eigcuts, cut_select_qp.py:757-786:
  * numpy.linalg.eigh of the whole lifted matrix [[1, x^T],[x, X]] of order dim = nb_vars + 1 and the per-entry Python comprehension
  * that builds one fully dense cut for every negative eigenvalue but the largest).  Both calls need sdpcut_set_instance and a point

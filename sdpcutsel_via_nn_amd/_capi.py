@@ -29,6 +29,7 @@ OPT_EXACT_SDP = 13       # strategy 3 accepted by the ranking and round calls (i
 STAT_SDP_UNCONVERGED = 12
 STAT_POINTS_REDONE = 13   # points of batched rounds served by the single-point round inside the call (include/sdpcut.h)
 BATCH_MAX_POINTS = 256   # SDPCUT_BATCH_MAX_POINTS: most LP points of one score_points / round_csr_points call
+DIVERSE_MAX_POOL = 16384   # SDPCUT_DIVERSE_MAX_POOL: longest pool of round_csr_diverse / list of filter_parallel
 ROW_LD = 20
 
 _c = ctypes
@@ -49,6 +50,11 @@ _ROUND_CSR_DTYPE = np.dtype([("cap", "<i8"), ("n_out", "<i8"), ("n_total", "<i8"
                              ("idx", "<u8"), ("score", "<u8"), ("lam_min", "<u8"), ("ks", "<u8"), ("set_inds", "<u8"), ("n_rows", "<i8"),
                              ("nnz", "<i8"), ("row_entry", "<u8"), ("indptr", "<u8"), ("indices", "<u8"), ("values", "<u8"), ("rhs", "<u8")])
 assert _ROUND_CSR_DTYPE.itemsize == _c.sizeof(RoundCsr)
+
+
+class DiverseInfo(_c.Structure):
+    """sdpcut_diverse_info_t of include/sdpcut.h"""
+    _fields_ = [("pool", _c.c_int64), ("examined", _c.c_int64), ("skipped_nonviolated", _c.c_int64), ("rejected_parallel", _c.c_int64)]
 
 
 class DenseRound(_c.Structure):
@@ -98,6 +104,8 @@ SIGNATURES = {
     "sdpcut_round_csr_end": [_vp, _c.POINTER(RoundCsr)],
     "sdpcut_score_points": [_vp, _c.c_int32, _dp, _c.c_int64, _c.c_uint32, _dp, _dp],
     "sdpcut_round_csr_points": [_vp, _c.c_int32, _dp, _c.c_int64, _c.c_int, _c.c_int64, _c.POINTER(RoundCsr)],
+    "sdpcut_round_csr_diverse": [_vp, _dp, _c.c_int, _c.c_int64, _c.c_int64, _c.c_double, _c.POINTER(RoundCsr), _c.POINTER(DiverseInfo)],
+    "sdpcut_filter_parallel": [_vp, _c.c_int64, _i64p, _c.c_int64, _c.c_double, _c.POINTER(_c.c_uint8), _c.POINTER(DiverseInfo)],
     "sdpcut_dense_round": [_vp, _dp, _c.POINTER(DenseRound)],
     "sdpcut_dense_eig": [_vp, _dp, _dp],
     "sdpcut_shard_head_device": [_vp, _c.c_int, _c.c_int64, _vp],
@@ -175,6 +183,28 @@ def _ptr(a, typ):
 
 class SdpCutError(RuntimeError):
     pass
+
+
+def check_diverse_args(max_parallel, quota, pool_size=None, strat=None):
+    """The refusals of the diverse selection that need no device (the library repeats them): -> (max_parallel, quota, pool_size)."""
+    mp = float(max_parallel)
+    if not 0.0 <= mp <= 1.0:      # (NaN fails both comparisons)
+        raise ValueError("max_parallel must lie in [0, 1]")
+    quota = int(quota)
+    if quota < 1:
+        raise ValueError("the quota (sel_size) must be >= 1")
+    if strat is not None and strat not in (STRAT_FEAS, STRAT_OPT, STRAT_COMB):
+        raise ValueError("diverse selection serves strategies 1 (feasibility), 2 (optimality) and 4 (combined)")
+    if pool_size is None:
+        pool_size = min(4 * quota, DIVERSE_MAX_POOL)
+        if quota > DIVERSE_MAX_POOL:
+            raise ValueError("sel_size must not exceed %d" % DIVERSE_MAX_POOL)
+    pool_size = int(pool_size)
+    if pool_size < quota:
+        raise ValueError("pool_size must be >= sel_size")
+    if pool_size > DIVERSE_MAX_POOL:
+        raise ValueError("pool_size must not exceed %d" % DIVERSE_MAX_POOL)
+    return mp, quota, pool_size
 
 
 def _adj_u8(adjacency, n=None):
@@ -629,6 +659,45 @@ class Scorer(object):
         res.update(n_total=int(out.n_total), new_strat=int(out.new_strat),
                    counters=dict(nb_violated=int(cnt[0]), strong=int(cnt[1]), violated=int(cnt[2]), nb_positive=int(cnt[3])))
         return res
+
+    # ------------------------------------------------------------------ diverse selection
+    @staticmethod
+    def _diverse_info(info):
+        return dict(pool=int(info.pool), examined=int(info.examined), skipped_nonviolated=int(info.skipped_nonviolated),
+                    rejected_parallel=int(info.rejected_parallel))
+
+    def round_csr_diverse(self, point, strat, sel_size, max_parallel, pool_size=None, copy=False):
+        """One round with a parallelism filter on the ranked head (sdpcut_round_csr_diverse): the first ``pool_size`` entries of the
+        strategy's ranking (default ``min(4 * sel_size, 16384)``) are walked in rank order and an entry is accepted only while fewer
+        than ``sel_size`` are and its cut has ``|cos| <= max_parallel`` with every cut accepted before it.  -> the dict of
+        :meth:`round_csr` for the accepted entries (every one with its row) plus ``info = dict(pool, examined, skipped_nonviolated,
+        rejected_parallel)``.  point=None keeps the current LP point; strategies 1, 2 and 4."""
+        mp, sel_size, pool_size = check_diverse_args(max_parallel, sel_size, pool_size, strat)
+        vv = self._csr_point(point)
+        if getattr(self, "_h", None) is None:
+            raise SdpCutError("the Scorer is closed")
+        self.round_count += 1
+        out, info = self._csr_out(), DiverseInfo()
+        self._check(self._lib.sdpcut_round_csr_diverse(self._h, _ptr(vv, _dp), int(strat), sel_size, pool_size, mp, ctypes.byref(out),
+                                                       ctypes.byref(info)))
+        res = self._csr_unpack(out, copy)
+        res["info"] = self._diverse_info(info)
+        return res
+
+    def filter_parallel(self, ids, quota, max_parallel):
+        """The same walk over candidates in the CALLER's order (sdpcut_filter_parallel; local ids, at the current LP point)
+        -> (keep bool [count], info dict as in :meth:`round_csr_diverse`)."""
+        mp, quota, _ = check_diverse_args(max_parallel, quota, DIVERSE_MAX_POOL)
+        idx = np.ascontiguousarray(ids, dtype=np.int64)
+        if idx.ndim != 1 or idx.shape[0] > DIVERSE_MAX_POOL:
+            raise ValueError("ids must be a list of at most %d local candidate ids" % DIVERSE_MAX_POOL)
+        if getattr(self, "_h", None) is None:
+            raise SdpCutError("the Scorer is closed")
+        keep = np.zeros(max(idx.shape[0], 1), dtype=np.uint8)
+        info = DiverseInfo()
+        self._check(self._lib.sdpcut_filter_parallel(self._h, idx.shape[0], _ptr(idx, _i64p), quota, mp, keep.ctypes.data_as(_u8p),
+                                                     ctypes.byref(info)))
+        return keep[:idx.shape[0]].astype(bool), self._diverse_info(info)
 
     # ------------------------------------------------------------------ many LP points per call
     def _points_arg(self, points):

@@ -198,6 +198,7 @@ struct sdpcut_ctx {
     double *d_train_ws = nullptr;  // parameters | per-workgroup partial sums | reduced loss and gradient (train.hip)
     size_t train_ws_doubles = 0;
     void *d_dense = nullptr;       // dense eigen-cuts (dense.hip): V^T, sorted vectors, eigenvalues, n_rows; allocated by the first call
+    void *diverse = nullptr;       // diverse selection (diverse.hip: DiverseWs): pool rows, pair bits, accepted head; allocated by the first call
     // sdpcut_shard_finish_enqueue -> sdpcut_shard_finish_wait
     int64_t shard_pending_serial = 0, shard_pending_sel = 0;
     int32_t shard_pending_world = 0, shard_pending_ld = 0;
@@ -342,6 +343,8 @@ void free_exact_ws(sdpcut_ctx *h);
 void free_dense_ws(sdpcut_ctx *h);
 // train.hip
 void free_train_ws(sdpcut_ctx *h);
+// diverse.hip
+void free_diverse_ws(sdpcut_ctx *h);
 
 // exact_sdp.hip (SDPCUT_SDP, SDPCUT_OPT_EXACT_SDP)
 int launch_exact_sdp(sdpcut_ctx *h);                 // d_sdp / d_sdp_gap of every candidate at the current point

@@ -1,0 +1,435 @@
+// Diverse cut selection (include/sdpcut.h: sdpcut_round_csr_diverse, sdpcut_filter_parallel): a parallelism filter on the ranked
+// head.  The ranking, the cut rows and the CSR assembly are the existing ones (sdpcut_rank_device, cut_rows_kernel, round_csr_kernel);
+// new here are the three steps between them:
+//   div_prepare_kernel  one lane per pool entry: norm of its row, eligibility, its index set
+//   div_pairs_kernel    one bit per pair s < t of the pool: |<a_s, a_t>| > max_parallel |a_s| |a_t|  (lower-triangular bit matrix)
+//   div_greedy_kernel   ONE workgroup walks the pool in rank order, 64 entries at a time, accepted mask in LDS
+// The walk is the definition of DESIGN.md section 5 "Diverse selection"; diversity.py is its numpy twin.
+#include <cstring>
+#include <new>
+
+#include "common.h"
+
+#define DIV_MAX_POOL SDPCUT_DIVERSE_MAX_POOL
+#define DIV_WORDS (DIV_MAX_POOL / 64)
+
+// everything the filter keeps on the device, sized for `cap` pool entries (grown on demand, freed with the handle)
+struct DiverseWs {
+    int64_t cap = 0;           // pool entries the arrays hold
+    int64_t bit_blocks = 0;    // 64-row blocks the bit matrix holds
+    int64_t *ids = nullptr;    // [cap] candidate ids of the pool in rank order (global for a ranked pool, local for a caller's list)
+    double *score = nullptr;   // [cap]
+    double *lam = nullptr, *rhs = nullptr, *norm = nullptr;   // [cap]
+    double *coef = nullptr;    // [cap][SDPCUT_ROW_LD]
+    int32_t *ks = nullptr;     // [cap]
+    int32_t *sets = nullptr;   // [cap][5] padded with -1
+    uint8_t *elig = nullptr;   // [cap]
+    uint8_t *keep = nullptr;   // [cap]
+    int64_t *acc_ids = nullptr;    // [cap] accepted entries, compacted in rank order: the head the CSR assembly reads
+    double *acc_score = nullptr;   // [cap]
+    int64_t *info = nullptr;       // [8]: examined, skipped (not eligible), rejected (parallel), accepted, 0, 0, 0
+    unsigned long long *bits = nullptr;   // lower-triangular bit matrix, see div_bits_offset
+};
+
+// Rows 64 b .. 64 b + 63 of the bit matrix hold b + 1 words each (columns 0 .. 64 b + 63); the blocks follow one another.
+// 16384 entries: 64 * 256 * 257 / 2 words = 16.8 MB.
+static __host__ __device__ __forceinline__ int64_t div_bits_offset(int64_t t)
+{
+    const int64_t b = t >> 6;
+    return 32 * b * (b + 1) + (t & 63) * (b + 1);
+}
+static inline int64_t div_bits_words(int64_t blocks) { return 32 * blocks * (blocks + 1); }
+
+static void div_free(DiverseWs *w)
+{
+    (void)hipFree(w->ids); (void)hipFree(w->score); (void)hipFree(w->lam); (void)hipFree(w->rhs); (void)hipFree(w->norm);
+    (void)hipFree(w->coef); (void)hipFree(w->ks); (void)hipFree(w->sets); (void)hipFree(w->elig); (void)hipFree(w->keep);
+    (void)hipFree(w->acc_ids); (void)hipFree(w->acc_score); (void)hipFree(w->bits);
+    const auto info = w->info;
+    *w = DiverseWs();
+    w->info = info;
+}
+
+void free_diverse_ws(sdpcut_ctx *h)
+{
+    DiverseWs *w = (DiverseWs *)h->diverse;
+    if (!w) return;
+    div_free(w);
+    (void)hipFree(w->info);
+    delete w;
+    h->diverse = nullptr;
+}
+
+// workspace for a pool of P entries; with_bits: the pair test will run (max_parallel < 1)
+static int div_ensure(sdpcut_ctx *h, int64_t P, bool with_bits, DiverseWs **out)
+{
+    DiverseWs *w = (DiverseWs *)h->diverse;
+    if (!w) {
+        w = new (std::nothrow) DiverseWs();
+        if (!w) return sdpcut_fail(h, SDPCUT_ENOMEM, "out of host memory");
+        h->diverse = w;
+        HIP_TRY(h, hipMalloc((void **)&w->info, 8 * sizeof(int64_t)));
+    }
+    if (P > w->cap) {
+        HIP_TRY(h, sdpcut_sync(h));
+        div_free(w);
+        const size_t c = (size_t)((P + 63) & ~(int64_t)63);
+        HIP_TRY(h, hipMalloc((void **)&w->ids, c * 8));
+        HIP_TRY(h, hipMalloc((void **)&w->score, c * 8));
+        HIP_TRY(h, hipMalloc((void **)&w->lam, c * 8));
+        HIP_TRY(h, hipMalloc((void **)&w->rhs, c * 8));
+        HIP_TRY(h, hipMalloc((void **)&w->norm, c * 8));
+        HIP_TRY(h, hipMalloc((void **)&w->coef, c * 8 * SDPCUT_ROW_LD));
+        HIP_TRY(h, hipMalloc((void **)&w->ks, c * 4));
+        HIP_TRY(h, hipMalloc((void **)&w->sets, c * 20));
+        HIP_TRY(h, hipMalloc((void **)&w->elig, c));
+        HIP_TRY(h, hipMalloc((void **)&w->keep, c));
+        HIP_TRY(h, hipMalloc((void **)&w->acc_ids, c * 8));
+        HIP_TRY(h, hipMalloc((void **)&w->acc_score, c * 8));
+        w->cap = (int64_t)c;
+    }
+    const int64_t blocks = (P + 63) / 64;
+    if (with_bits && blocks > w->bit_blocks) {
+        HIP_TRY(h, sdpcut_sync(h));
+        (void)hipFree(w->bits);
+        w->bits = nullptr;
+        w->bit_blocks = 0;
+        HIP_TRY(h, hipMalloc((void **)&w->bits, (size_t)div_bits_words(blocks) * 8));
+        w->bit_blocks = blocks;
+    }
+    *out = w;
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// Norm, eligibility and index set of every pool entry; the rows themselves are cut_rows_kernel's (rows.hip), stride SDPCUT_ROW_LD,
+// zero beyond the row's length.  An id outside the list has ks = 0 there and is not eligible.
+__global__ __launch_bounds__(64) void div_prepare_kernel(int64_t P, const int64_t *ids, int64_t idx_base, int64_t n_local,
+                                                         const int32_t *set5, const double *lam, const double *coef, const int32_t *ks,
+                                                         double *norm, uint8_t *elig, int32_t *sets)
+{
+    const int64_t t = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (t >= P) return;
+    const int k = ks[t];
+    const int64_t c = ids[t] - idx_base;
+    const bool in_list = c >= 0 && c < n_local && k >= 2 && k <= SDPCUT_MAX_K;
+    double ss = 0.0;
+    {
+#pragma clang fp contract(off)
+        for (int m = 0; m < SDPCUT_ROW_LD; ++m) {
+            const double v = coef[t * SDPCUT_ROW_LD + m];
+            ss = ss + v * v;
+        }
+    }
+    const double nr = in_list ? sqrt(ss) : 0.0;
+    norm[t] = nr;
+    elig[t] = (in_list && lam[t] < SDPCUT_NEG_EIGVAL && nr > 0.0) ? 1 : 0;
+    for (int a = 0; a < 5; ++a) sets[t * 5 + a] = (in_list && a < k) ? set5[c * 5 + a] : -1;
+}
+
+// <a_s, a_t> over the shared LP columns: x_c for every common variable c, X_cd for common c <= d.  m[a] = position in s's set of
+// t's a-th variable (-1: not shared).  Coefficient positions: a for x of local index a, k + a k - a (a - 1) / 2 + (b - a) for X of
+// the local pair a <= b.  Fixed order: the x columns by t's ascending local index, then the X pairs row-major; no contraction.
+// ct / cs: rows in LDS (their positions depend on the candidate sizes).
+__device__ __forceinline__ double div_dot(const double *ct, int kt, const double *cs, int ks, const int (&m)[5])
+{
+#pragma clang fp contract(off)
+    double acc = 0.0;
+#pragma unroll
+    for (int a = 0; a < 5; ++a)
+        if (m[a] >= 0) acc = acc + ct[a] * cs[m[a]];
+#pragma unroll
+    for (int a = 0; a < 5; ++a) {
+#pragma unroll
+        for (int b = a; b < 5; ++b) {
+            if (m[a] < 0 || m[b] < 0) continue;
+            const int pa = m[a] < m[b] ? m[a] : m[b], pb = m[a] < m[b] ? m[b] : m[a];
+            acc = acc + ct[kt + a * kt - a * (a - 1) / 2 + (b - a)] * cs[ks + pa * ks - pa * (pa - 1) / 2 + (pb - pa)];
+        }
+    }
+    return acc;
+}
+
+// Tile (row block blockIdx.y, column word blockIdx.x <= blockIdx.y) of the bit matrix: lane l owns row t = 64 by + l and tests
+// it against the 64 entries s of the column word; both sets of rows sit in LDS.  A lane's 64 results leave as ONE word, stored by
+// that lane.
+__global__ __launch_bounds__(64) void div_pairs_kernel(int64_t P, double max_parallel, const double *coef, const int32_t *ks,
+                                                       const int32_t *sets, const double *norm, const uint8_t *elig,
+                                                       unsigned long long *bits)
+{
+    const int bx = blockIdx.x, by = blockIdx.y;
+    if (bx > by) return;
+    __shared__ double s_coef[64 * SDPCUT_ROW_LD];
+    __shared__ double t_coef[64 * SDPCUT_ROW_LD];
+    __shared__ double s_norm[64];
+    __shared__ int32_t s_set[64 * 5];
+    __shared__ int32_t s_k[64];
+    __shared__ int32_t s_el[64];
+    const int lane = threadIdx.x;
+    const int64_t t = (int64_t)by * 64 + lane;
+    {
+        const int64_t s = (int64_t)bx * 64 + lane;
+        const bool live = s < P;
+        s_norm[lane] = live ? norm[s] : 0.0;
+        s_k[lane] = live ? ks[s] : 0;
+        s_el[lane] = live ? (int32_t)elig[s] : 0;
+        for (int a = 0; a < 5; ++a) s_set[lane * 5 + a] = live ? sets[s * 5 + a] : -1;
+        for (int m = 0; m < SDPCUT_ROW_LD; ++m) {
+            s_coef[lane * SDPCUT_ROW_LD + m] = live ? coef[s * SDPCUT_ROW_LD + m] : 0.0;
+            t_coef[lane * SDPCUT_ROW_LD + m] = t < P ? coef[t * SDPCUT_ROW_LD + m] : 0.0;
+        }
+    }
+    __syncthreads();
+    if (t >= P) return;
+    unsigned long long word = 0ull;
+    if (elig[t]) {
+        int32_t st[5];
+#pragma unroll
+        for (int a = 0; a < 5; ++a) st[a] = sets[t * 5 + a];      // -1 beyond the candidate's size: matches nothing
+        const double *ct = t_coef + lane * SDPCUT_ROW_LD;
+        const int kt = ks[t];
+        const double nt = norm[t];
+        const int jmax = (bx == by) ? lane : 64;      // pairs s < t only
+        for (int j = 0; j < jmax; ++j) {
+            if (!s_el[j]) continue;
+            const int kj = s_k[j];
+            int m[5];
+            bool any = false;
+#pragma unroll
+            for (int a = 0; a < 5; ++a) {
+                m[a] = -1;
+#pragma unroll
+                for (int b = 0; b < 5; ++b)
+                    if (st[a] >= 0 && s_set[j * 5 + b] == st[a]) m[a] = b;
+                any = any || m[a] >= 0;
+            }
+            if (!any) continue;       // no common variable, no common column
+            const double dot = div_dot(ct, kt, s_coef + j * SDPCUT_ROW_LD, kj, m);
+            bool hit;
+            {
+#pragma clang fp contract(off)
+                hit = fabs(dot) > max_parallel * s_norm[j] * nt;
+            }
+            if (hit) word |= 1ull << j;
+        }
+    }
+    bits[div_bits_offset(t) + bx] = word;
+}
+
+// The walk.  One workgroup of 256 threads; block b = entries 64 b .. 64 b + 63.  (1) Four threads per entry AND its row of the bit
+// matrix against the accepted mask of the blocks in front (LDS); (2) the first wave settles the block's own entries one after the other from
+// the in-block word of each (bits s < t of the diagonal tile); (3) lanes store keep flags and the compacted head.  The walk ends with
+// the entry that fills the quota.  bits == NULL: no comparison at all (max_parallel >= 1).
+__global__ __launch_bounds__(256) void div_greedy_kernel(int64_t P, int64_t quota, const uint8_t *elig, const unsigned long long *bits,
+                                                         const int64_t *ids, const double *score, uint8_t *keep, int64_t *acc_ids,
+                                                         double *acc_score, int64_t *info)
+{
+    __shared__ unsigned long long s_acc[DIV_WORDS];
+    __shared__ unsigned long long s_diag[64];
+    __shared__ int32_t s_conf[256];
+    __shared__ int32_t s_el[64];
+    __shared__ unsigned long long s_word;
+    __shared__ int64_t s_cnt[4];      // accepted, examined, skipped, rejected
+    const int tid = threadIdx.x;
+    const int l = tid & 63, q = tid >> 6;
+    if (tid < 4) s_cnt[tid] = 0;
+    const int64_t nblk = (P + 63) / 64;
+    __syncthreads();
+    for (int64_t b = 0; b < nblk; ++b) {
+        const int64_t t = b * 64 + l;
+        const bool live = t < P;
+        int conf = 0;
+        if (bits && live && elig[t]) {
+            const unsigned long long *row = bits + div_bits_offset(t);
+            for (int64_t w = q; w < b; w += 4) {
+                const unsigned long long a = s_acc[w];
+                if (a && (row[w] & a)) conf = 1;
+            }
+            if (q == 0) s_diag[l] = row[b];
+        } else if (q == 0) {
+            s_diag[l] = 0ull;
+        }
+        if (q == 0) s_el[l] = (live && elig[t]) ? 1 : 0;
+        s_conf[tid] = conf;
+        __syncthreads();
+        if (q == 0) {
+            // the whole first wave, every lane with its own entry in registers: entry j is accepted iff it is eligible, clear of
+            // the blocks in front and clear of what this block has accepted so far -- lane j's bit of the ballot in step j
+            const bool ok = s_el[l] && !(s_conf[l] | s_conf[64 + l] | s_conf[128 + l] | s_conf[192 + l]);
+            const unsigned long long d = s_diag[l];
+            unsigned long long acc = 0ull;
+            int64_t n_acc = s_cnt[0];
+            const int nlive = (P - b * 64 < 64) ? (int)(P - b * 64) : 64;
+            int j = 0;
+            for (; j < nlive && n_acc < quota; ++j) {
+                const unsigned long long m = __ballot(ok && !(d & acc));
+                if ((m >> j) & 1ull) { acc |= 1ull << j; ++n_acc; }
+            }
+            // (the walk ends WITH the entry that fills the quota: what follows it in the block was not examined)
+            const unsigned long long seen = j >= 64 ? ~0ull : ((1ull << j) - 1ull);
+            const unsigned long long el = __ballot(s_el[l] != 0);
+            if (l == 0) {
+                s_word = acc;
+                s_acc[b] = acc;
+                s_cnt[1] += j;
+                s_cnt[2] += __popcll(~el & seen);
+                s_cnt[3] += __popcll(el & seen & ~acc);
+                // s_cnt[0] is advanced after the lanes have read it as their base
+            }
+        }
+        __syncthreads();
+        const unsigned long long acc = s_word;
+        const int64_t base = s_cnt[0];
+        if (q == 0 && live) {
+            const bool mine = (acc >> l) & 1ull;
+            keep[t] = mine ? 1 : 0;
+            if (mine) {
+                const int64_t pos = base + __popcll(acc & ((1ull << l) - 1ull));
+                acc_ids[pos] = ids[t];
+                acc_score[pos] = score[t];
+            }
+        }
+        __syncthreads();
+        if (tid == 0) s_cnt[0] = base + __popcll(acc);
+        __syncthreads();
+        if (s_cnt[0] >= quota) {
+            // entries behind the walk's end keep nothing
+            for (int64_t r = (b + 1) * 64 + tid; r < P; r += 256) keep[r] = 0;
+            break;
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        info[0] = s_cnt[1];
+        info[1] = s_cnt[2];
+        info[2] = s_cnt[3];
+        info[3] = s_cnt[0];
+        info[4] = info[5] = info[6] = info[7] = 0;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// rows -> norms -> pair bits -> walk, for the P ids in w->ids (minus idx_base = local candidate index); all on the handle's stream
+static int div_filter_enqueue(sdpcut_ctx *h, DiverseWs *w, int64_t P, int64_t idx_base, int64_t quota, double max_parallel)
+{
+    int rc = launch_cut_rows(h, P, nullptr, w->ids, idx_base, w->lam, w->coef, SDPCUT_ROW_LD, w->rhs, nullptr, w->ks);
+    if (rc) return rc;
+    const int grid = (int)((P + 63) / 64);
+    hipLaunchKernelGGL(div_prepare_kernel, dim3(grid), dim3(64), 0, h->stream, P, w->ids, idx_base, h->N, h->d_set_orig, w->lam, w->coef,
+                       w->ks, w->norm, w->elig, w->sets);
+    HIP_TRY(h, hipGetLastError());
+    const bool compare = max_parallel < 1.0;
+    if (compare) {
+        hipLaunchKernelGGL(div_pairs_kernel, dim3(grid, grid), dim3(64), 0, h->stream, P, max_parallel, w->coef, w->ks, w->sets, w->norm,
+                           w->elig, w->bits);
+        HIP_TRY(h, hipGetLastError());
+    }
+    hipLaunchKernelGGL(div_greedy_kernel, dim3(1), dim3(256), 0, h->stream, P, quota, w->elig, compare ? w->bits : nullptr, w->ids,
+                       w->score, w->keep, w->acc_ids, w->acc_score, w->info);
+    HIP_TRY(h, hipGetLastError());
+    return 0;
+}
+
+static int div_check_common(sdpcut_ctx *h, double max_parallel)
+{
+    if (!(max_parallel >= 0.0 && max_parallel <= 1.0)) return sdpcut_fail(h, SDPCUT_EINVAL, "max_parallel must lie in [0, 1]");
+    return 0;
+}
+
+extern "C" {
+
+int sdpcut_filter_parallel(sdpcut_handle h, int64_t count, const int64_t *idx, int64_t quota, double max_parallel, uint8_t *keep_out,
+                           sdpcut_diverse_info_t *info)
+{
+    if (!h) return SDPCUT_EINVAL;
+    int rc = div_check_common(h, max_parallel);
+    if (rc) return rc;
+    if (count < 0 || count > DIV_MAX_POOL) return sdpcut_fail(h, SDPCUT_EINVAL, "count must lie in 0 .. SDPCUT_DIVERSE_MAX_POOL");
+    if (quota < 1) return sdpcut_fail(h, SDPCUT_EINVAL, "quota must be >= 1");
+    if (count > 0 && (!idx || !keep_out)) return sdpcut_fail(h, SDPCUT_EINVAL, "bad filter_parallel arguments");
+    if (!h->have_point || !h->d_set_orig) return sdpcut_fail(h, SDPCUT_ESTATE, "set_candidates and set_point first");
+    SDPCUT_NO_PENDING(h);
+    for (int64_t i = 0; i < count; ++i)
+        if (idx[i] < 0 || idx[i] >= h->N) return sdpcut_fail(h, SDPCUT_EINVAL, "candidate index out of range");
+    if (info) { info->pool = count; info->examined = info->skipped_nonviolated = info->rejected_parallel = 0; }
+    if (count == 0) return SDPCUT_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    DiverseWs *w = nullptr;
+    rc = div_ensure(h, count, max_parallel < 1.0, &w);
+    if (rc) return rc;
+    HIP_TRY(h, hipMemcpyAsync(w->ids, idx, (size_t)count * 8, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemsetAsync(w->score, 0, (size_t)count * 8, h->stream));
+    rc = div_filter_enqueue(h, w, count, 0, quota, max_parallel);
+    if (rc) return rc;
+    int64_t c8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    HIP_TRY(h, hipMemcpyAsync(keep_out, w->keep, (size_t)count, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(c8, w->info, sizeof(c8), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, sdpcut_sync(h));
+    if (info) { info->examined = c8[0]; info->skipped_nonviolated = c8[1]; info->rejected_parallel = c8[2]; }
+    return SDPCUT_OK;
+}
+
+int sdpcut_round_csr_diverse(sdpcut_handle h, const double *vars_values, int strat, int64_t sel_size, int64_t pool_size,
+                             double max_parallel, sdpcut_round_csr_t *out, sdpcut_diverse_info_t *info)
+{
+    if (!h) return SDPCUT_EINVAL;
+    if (!out) return sdpcut_fail(h, SDPCUT_EINVAL, "out is NULL");
+    std::memset(out, 0, sizeof(*out));
+    if (info) std::memset(info, 0, sizeof(*info));
+    int rc = check_round_strategy(h, strat);
+    if (rc) return rc;
+    rc = div_check_common(h, max_parallel);
+    if (rc) return rc;
+    if (sel_size < 1) return sdpcut_fail(h, SDPCUT_EINVAL, "sel_size must be >= 1");
+    if (pool_size < sel_size) return sdpcut_fail(h, SDPCUT_EINVAL, "pool_size must be >= sel_size");
+    if (pool_size > DIV_MAX_POOL) return sdpcut_fail(h, SDPCUT_EINVAL, "pool_size must not exceed SDPCUT_DIVERSE_MAX_POOL");
+    if (h->nb_vars == 0 || !h->d_eig || !(h->have_point || vars_values))
+        return sdpcut_fail(h, SDPCUT_ESTATE, "set_instance, set_candidates and a point first");
+    SDPCUT_NO_PENDING(h);
+    if (vars_values && (rc = sdpcut_set_point(h, vars_values))) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    // 1. the pool: the head of the strategy's ranking, by the existing ranking call (SDPCUT_OPT_EXACT_HEAD included)
+    const uint32_t need = strat_need(strat);
+    if ((h->scored & need) != need && (rc = sdpcut_score(h, need & ~h->scored))) return rc;
+    const int64_t want = pool_size < h->N ? pool_size : h->N;
+    out->row_ld = h->row_len_max;
+    if (want == 0) return sdpcut_rank(h, strat, sel_size, 0, nullptr, nullptr, &out->n_total, &out->new_strat, out->counters);
+    DiverseWs *w = nullptr;
+    rc = div_ensure(h, want, max_parallel < 1.0, &w);
+    if (rc) return rc;
+    int64_t P = 0;
+    rc = sdpcut_rank_device(h, strat, sel_size, want, w->ids, w->score, &P, &out->n_total, &out->new_strat, out->counters);
+    if (rc) return rc;
+    if (info) info->pool = P;
+    if (P <= 0) return SDPCUT_OK;      // an empty ranking (no violated candidate): an empty block
+    // 2. - 4. rows, pair test, walk
+    rc = div_filter_enqueue(h, w, P, h->base, sel_size, max_parallel);
+    if (rc) return rc;
+    // 5. emit: the accepted entries are a head like any other; the existing assembly reads its length from word 3 of w->info and
+    // copies the walk's counts into the block's header with it
+    const int64_t cap = sel_size < P ? sel_size : P;
+    const int32_t ld = h->row_len_max;
+    rc = ensure_pinned(h, csr_layout(cap, ld).bytes);
+    if (rc) return rc;
+    int64_t *hdr = (int64_t *)h->pinned;
+    for (int attempt = 0;; ++attempt) {
+        hdr[8] = hdr[9] = hdr[10] = 0;
+        const int64_t serial = ++h->round_serial;
+        rc = launch_round_csr(h, cap, w->info, cap, w->acc_ids, w->acc_score, ld, h->pinned_dev, serial);
+        if (rc) return rc;
+        rc = wait_round_done(h, hdr + 7, serial);
+        if (rc) return rc;
+        if (!hdr[10]) break;
+        // the assembly's bounded look-back gave up (a device shared with a long kernel): once more, as the plain round does
+        ++h->stat_fallbacks;
+        if (attempt == 1) return sdpcut_fail(h, SDPCUT_EHIP, "round_csr_diverse: look-back of the row assembly timed out twice");
+    }
+    ++h->stat_rounds;
+    if (info) { info->examined = hdr[0]; info->skipped_nonviolated = hdr[1]; info->rejected_parallel = hdr[2]; }
+    out->cap = cap;
+    out->n_out = hdr[3];
+    csr_out_from_block(h->pinned, out);
+    return SDPCUT_OK;
+}
+
+} // extern "C"

@@ -1003,7 +1003,7 @@ class CutSolver(GpuCutSelectionMixin):
 
     def cut_select_algo(self, filename, dim, sel_size, strat=2, nb_rounds_cuts=20, term_on=False,
                         triangle_on=False, strong_only=False, max_subs=_THRES_MAX_SUBS, on_round=None, plots=False, sol=0,
-                        ch_ext=0):
+                        ch_ext=0, max_parallel=None, pool_factor=4):
         """Cutting-plane rounds on a BoxQP ``.in`` file, same arguments and default return tuple as
         the reference's entry point (cut_select_qp.py:73-221), with HiGHS as LP solver, the native
         cover enumeration and the GPU selection / generation / triangle separation in between.
@@ -1019,6 +1019,11 @@ class CutSolver(GpuCutSelectionMixin):
         (optimality via the exact SDP solution) and -1 (figure 8); with ``strat=-1, plots=True`` the return is the reference's
         ``(gap_closed_percent, rounds_stats, round_std_devs, rounds_all_cuts)`` with the gap closed measured against ``sol``
         (:209-215).  ``plots`` with another strategy is out of scope.
+        ``max_parallel`` (off by default; strategies 1, 2 and 4 only): a parallelism filter on the ranked head
+        (``Scorer.round_csr_diverse``, DESIGN.md section 5 "Diverse selection").  Each round walks the first
+        ``min(pool_factor * quota, 16384)`` ranked candidates and adds a cut only while fewer than the quota are added and its
+        ``|cos|`` with every cut added before it in the round is at most ``max_parallel``; the walk's counts of every round are
+        kept in ``self.diverse_log``.  The combined strategy's switch and ``strong_only`` work as without the filter.
         -> (bound per solve, total s, round s, separation s, PSD cuts per round, triangle cuts per
         round, number of candidates)."""
         from timeit import default_timer as clock
@@ -1030,6 +1035,12 @@ class CutSolver(GpuCutSelectionMixin):
         assert 0 < sel_size, "The selection size must be a % or number (of cuts) >0!"
         assert dim <= 5, "Keep SDP vertex cover low-dimensional (<=5)!"
         assert (ch_ext in [0, 1, 2]), "Chordal extension flags: 0-P^E_3, 1-P^bar(E)_3, 2-bar(P*_3)!"      # :94
+        if max_parallel is not None:
+            if strat not in (1, 2, 4):
+                raise AssertionError("max_parallel filters the ranked head of strategies 1 (feasibility), 2 (optimality) and 4 (combined) only")
+            assert 0.0 <= max_parallel <= 1.0, "max_parallel is a bound on |cos| between two cuts: 0 .. 1"
+            assert pool_factor >= 1, "the pool is pool_factor times the quota: pool_factor >= 1"
+            self.diverse_log = []
         t_start = clock()
         inst = harness.parse_boxqp(filename)
         self._dim = dim
@@ -1059,6 +1070,34 @@ class CutSolver(GpuCutSelectionMixin):
         if strat == 0:      # the cover's scorer already holds the instance
             self._gpu_dense_sc, self._gpu_dense_key = sc, (self._nb_vars, id(self._Q_arr))
 
+        def separate_diverse(round_no, point):
+            """a round through the parallelism filter: ranking, walk and assembled cuts in one library call"""
+            cur = state["strat"]
+            sdp = 0
+            if quota >= 1:
+                b = self._gpu_bind()
+                b.drain()
+                vv = np.ascontiguousarray(point, dtype=np.float64)
+                pool = int(min(max(int(pool_factor * quota), quota), _capi.DIVERSE_MAX_POOL))
+                r = b.scorer.round_csr_diverse(vv, cur, quota, max_parallel, pool_size=pool)
+                b.note_point(vv, {1: _capi.EIG, 2: _capi.NN, 4: _capi.EIG | _capi.NN}[cur])
+                b.rank_serial += 1
+                self._gpu_last = None
+                self.diverse_log.append(dict(r["info"], round=round_no, strat=cur, accepted=int(r["idx"].shape[0])))
+                if cur == 4:
+                    state["strat"] = r["new_strat"]       # the switch takes effect next round (:181 vs :188)
+                rows = int(r["rhs"].shape[0])             # every accepted entry has its row
+                if strong_only and cur in (2, 4):         # :725-726
+                    stop = np.flatnonzero(r["score"][:rows] <= 0)
+                    if stop.size:
+                        rows = int(stop[0])
+                nnz = int(r["indptr"][rows])
+                sdp = self._gpu_add_csr((r["indptr"][:rows + 1], r["indices"][:nnz], r["values"][:nnz], r["rhs"][:rows]),
+                                        self._sparse_pair or _default_sparse_pair())
+            else:
+                self._my_prob.linear_constraints.add(lin_expr=[], rhs=[], senses=[])
+            return {"sdp": sdp, "tri": self._separate_and_add_triangle(sel_size, point) if triangle_on else 0}
+
         def separate(round_no, point):
             cur = state["strat"]
             if cur == 0:
@@ -1076,7 +1115,7 @@ class CutSolver(GpuCutSelectionMixin):
             tri = self._separate_and_add_triangle(sel_size, point) if triangle_on else 0
             return {"sdp": sdp, "tri": tri}
 
-        log = harness.run_cut_rounds(lp, separate, nb_rounds_cuts, setup_s=t_model,
+        log = harness.run_cut_rounds(lp, separate if max_parallel is None else separate_diverse, nb_rounds_cuts, setup_s=t_model,
                                      stop_tol=self._CONVERGENCE_TOL if term_on else None, on_round=on_round,
                                      after_solve=self._gpu_wake,
                                      # dense cuts: past the 4th round, stop once the rounds have taken 1000 s (:157)
