@@ -520,6 +520,60 @@ int sdpcut_filter_parallel(sdpcut_handle h, int64_t count, const int64_t *idx, i
                            sdpcut_diverse_info_t *info);
 
 /*
+ * All violated eigen-cuts of a selected set: multi-cut rounds.  A round emits ONE cut per selected index set, the eigenvector of
+ * the smallest eigenvalue of [[1, x^T],[x, X]] (cut_select_qp.py:737-750); the small matrices often have several negative
+ * eigenvalues, and every one of them is a valid cut.  These calls emit up to max_per_set of them per set.  The rule (DESIGN.md
+ * section 5, "All violated eigen-cuts"):
+ *   head            the one sdpcut_round_csr returns for (strat, sel_size) at the point: same ids, scores, n_out, n_total,
+ *                   new_strat, counters (SDPCUT_OPT_EXACT_HEAD honoured, and refused, as there)
+ *   entry i offers  its eigenpairs with eigenvalue < -1e-15 in ascending eigenvalue order, at most max_per_set of them (there
+ *                   are at most k: the (0,0) entry is 1); equal eigenvalues keep the order of the solver's columns
+ *   row             as sdpcut_cut_rows builds it from a vector: components with |v| <= 1e-15 zeroed, coefficient v_i v_j (doubled
+ *                   off the diagonal) on the columns [L + i for i in set_inds] + Xarr_inds, rhs -v0^2, sense "G"
+ *   walk            rows are numbered in (entry, eigenvalue) order; rows numbered >= row_quota are dropped, so the walk may end
+ *                   inside an entry.  row_quota = sel_size hands the LP as many rows as a plain round at most; row_quota =
+ *                   max_per_set * sel_size keeps every offered cut
+ * max_per_set = 1 is sdpcut_round_csr bit for bit (the call forwards to it; n_neg is then 0 or 1: only the smallest eigenvalue
+ * was looked at).  For max_per_set >= 2 all rows of an entry come from ONE full decomposition with vectors (cyclic Jacobi,
+ * csrc/jacobi.h): they are an orthonormal set even inside a multiple eigenvalue, lam_min of an entry is that decomposition's
+ * smallest eigenvalue, and row 0 of an entry may differ from sdpcut_round_csr's row in the last bits (another solver).
+ *
+ * sdpcut_round_csr_multi: strategies 1, 2, 4, and 3 under SDPCUT_OPT_EXACT_SDP; vars_values NULL keeps the current point;
+ * synchronous.  out->csr is the block of sdpcut_round_csr with the row arrays (row_entry, indptr, indices, values, rhs) sized for
+ * row_cap = min(row_quota, max_per_set * cap) rows, plus
+ *   n_neg[n_out]      violated eigenvalues of the entry (before max_per_set and before the quota)
+ *   row_lam[n_rows]   the row's eigenvalue;   row_rank[n_rows]  0 for the entry's smallest eigenvalue, then 1, ...
+ *   n_used            1 + row_entry[n_rows - 1], or 0 without rows;   quota_hit  1 if a row was dropped
+ * row_entry ascends: a caller that keeps only the first entries (strong_only) slices a prefix.  All pointers point into the
+ * handle's blocks and stay valid until the next call on the handle.
+ * SDPCUT_EINVAL: max_per_set outside 1 .. SDPCUT_MULTI_MAX_PER_SET, row_quota < 1, another strategy, sel_size < 0 or a head
+ * longer than 16384 entries.  SDPCUT_ESTATE: no instance, candidates or point; a round pending.
+ *
+ * sdpcut_cut_rows_all: the same rows for `count` LOCAL candidate ids in the caller's order (repeats allowed) at the current point;
+ * no scoring, no quota.  Entry i owns rows row_ptr[i] .. row_ptr[i + 1] - 1 (row_ptr has count + 1 entries); row_lam, coef
+ * [.][SDPCUT_ROW_LD] and rhs are per ROW and must hold count * max_per_set rows; cols [count][SDPCUT_ROW_LD] and ks [count] are per
+ * ENTRY as in sdpcut_cut_rows (the rows of an entry share their columns).  max_per_set = 1: the rows sdpcut_cut_rows gives for the
+ * entries with lam_min < -1e-15, bit for bit.  Serves strategy 5, the QCQP round's concatenated list and caller-side merges.
+ *
+ * Not offered in this version: multi-cut rounds together with max_parallel (sdpcut_round_csr_diverse), for batched points
+ * (sdpcut_round_csr_points), for the sharded rounds (sdpcut_shard_*), and in two halves (begin / end).
+ */
+#define SDPCUT_MULTI_MAX_PER_SET 5
+typedef struct sdpcut_round_multi {
+    sdpcut_round_csr_t csr;
+    int64_t row_cap;
+    int64_t n_used;
+    int32_t quota_hit, reserved;
+    const int32_t *n_neg;
+    const double *row_lam;
+    const int32_t *row_rank;
+} sdpcut_round_multi_t;
+int sdpcut_round_csr_multi(sdpcut_handle h, const double *vars_values, int strat, int64_t sel_size, int32_t max_per_set,
+                           int64_t row_quota, sdpcut_round_multi_t *out);
+int sdpcut_cut_rows_all(sdpcut_handle h, int64_t count, const int64_t *idx, int32_t max_per_set, int64_t *row_ptr, double *row_lam,
+                        double *coef, double *rhs, int64_t *cols, int32_t *ks);
+
+/*
  * Dense eigen-cuts: strategy 0 of cut_select_algo, the paper's baseline (replaces __gen_dense_eigcuts, cut_select_qp.py:757-786:
  * numpy.linalg.eigh of the whole lifted matrix [[1, x^T],[x, X]] of order dim = nb_vars + 1 and the per-entry Python comprehension
  * that builds one fully dense cut for every negative eigenvalue but the largest).  Both calls need sdpcut_set_instance and a point

@@ -30,6 +30,7 @@ STAT_SDP_UNCONVERGED = 12
 STAT_POINTS_REDONE = 13   # points of batched rounds served by the single-point round inside the call (include/sdpcut.h)
 BATCH_MAX_POINTS = 256   # SDPCUT_BATCH_MAX_POINTS: most LP points of one score_points / round_csr_points call
 DIVERSE_MAX_POOL = 16384   # SDPCUT_DIVERSE_MAX_POOL: longest pool of round_csr_diverse / list of filter_parallel
+MULTI_MAX_PER_SET = 5      # SDPCUT_MULTI_MAX_PER_SET: most eigen-cuts one index set offers (round_csr_multi / cut_rows_all)
 ROW_LD = 20
 
 _c = ctypes
@@ -50,6 +51,12 @@ _ROUND_CSR_DTYPE = np.dtype([("cap", "<i8"), ("n_out", "<i8"), ("n_total", "<i8"
                              ("idx", "<u8"), ("score", "<u8"), ("lam_min", "<u8"), ("ks", "<u8"), ("set_inds", "<u8"), ("n_rows", "<i8"),
                              ("nnz", "<i8"), ("row_entry", "<u8"), ("indptr", "<u8"), ("indices", "<u8"), ("values", "<u8"), ("rhs", "<u8")])
 assert _ROUND_CSR_DTYPE.itemsize == _c.sizeof(RoundCsr)
+
+
+class RoundMulti(_c.Structure):
+    """sdpcut_round_multi_t of include/sdpcut.h"""
+    _fields_ = [("csr", RoundCsr), ("row_cap", _c.c_int64), ("n_used", _c.c_int64), ("quota_hit", _c.c_int32), ("reserved", _c.c_int32),
+                ("n_neg", _vp), ("row_lam", _vp), ("row_rank", _vp)]
 
 
 class DiverseInfo(_c.Structure):
@@ -106,6 +113,8 @@ SIGNATURES = {
     "sdpcut_round_csr_points": [_vp, _c.c_int32, _dp, _c.c_int64, _c.c_int, _c.c_int64, _c.POINTER(RoundCsr)],
     "sdpcut_round_csr_diverse": [_vp, _dp, _c.c_int, _c.c_int64, _c.c_int64, _c.c_double, _c.POINTER(RoundCsr), _c.POINTER(DiverseInfo)],
     "sdpcut_filter_parallel": [_vp, _c.c_int64, _i64p, _c.c_int64, _c.c_double, _c.POINTER(_c.c_uint8), _c.POINTER(DiverseInfo)],
+    "sdpcut_round_csr_multi": [_vp, _dp, _c.c_int, _c.c_int64, _c.c_int32, _c.c_int64, _c.POINTER(RoundMulti)],
+    "sdpcut_cut_rows_all": [_vp, _c.c_int64, _i64p, _c.c_int32, _i64p, _dp, _dp, _dp, _i64p, _i32p],
     "sdpcut_dense_round": [_vp, _dp, _c.POINTER(DenseRound)],
     "sdpcut_dense_eig": [_vp, _dp, _dp],
     "sdpcut_shard_head_device": [_vp, _c.c_int, _c.c_int64, _vp],
@@ -205,6 +214,28 @@ def check_diverse_args(max_parallel, quota, pool_size=None, strat=None):
     if pool_size > DIVERSE_MAX_POOL:
         raise ValueError("pool_size must not exceed %d" % DIVERSE_MAX_POOL)
     return mp, quota, pool_size
+
+
+def check_multi_args(cuts_per_set, row_quota, sel_size=None, strat=None):
+    """The refusals of the multi-cut calls that need no device (the library repeats them): -> (cuts_per_set, row_quota).
+    row_quota None = sel_size (the LP gets as many rows as from a plain round at most), "sets" = cuts_per_set * sel_size (every
+    selected set keeps all the cuts it offers)."""
+    m = int(cuts_per_set)
+    if m != cuts_per_set or not 1 <= m <= MULTI_MAX_PER_SET:
+        raise ValueError("cuts_per_set must be an integer in 1 .. %d" % MULTI_MAX_PER_SET)
+    if strat is not None and strat not in (STRAT_FEAS, STRAT_OPT, STRAT_EXACT, STRAT_COMB):
+        raise ValueError("multi-cut rounds serve strategies 1 (feasibility), 2 (optimality), 3 (exact, with OPT_EXACT_SDP) and 4 (combined)")
+    if row_quota is None or (isinstance(row_quota, str) and row_quota == "sets"):
+        if sel_size is None:
+            raise ValueError("row_quota needs a number where there is no sel_size")
+        q = int(sel_size) * (m if row_quota == "sets" else 1)
+    elif isinstance(row_quota, str):
+        raise ValueError('row_quota must be a number, None or "sets"')
+    else:
+        q = int(row_quota)
+    if q < 1:
+        raise ValueError("row_quota must be >= 1")
+    return m, q
 
 
 def _adj_u8(adjacency, n=None):
@@ -698,6 +729,67 @@ class Scorer(object):
         self._check(self._lib.sdpcut_filter_parallel(self._h, idx.shape[0], _ptr(idx, _i64p), quota, mp, keep.ctypes.data_as(_u8p),
                                                      ctypes.byref(info)))
         return keep[:idx.shape[0]].astype(bool), self._diverse_info(info)
+
+    # ------------------------------------------------------------------ all violated eigen-cuts of a set
+    def round_csr_multi(self, point, strat, sel_size, cuts_per_set, row_quota=None, copy=False):
+        """One round that emits up to ``cuts_per_set`` eigen-cuts per selected set (sdpcut_round_csr_multi; the rule is DESIGN.md
+        section 5 "All violated eigen-cuts"): the head of :meth:`round_csr`, every entry offering its eigenpairs with eigenvalue
+        < -1e-15 in ascending order, rows numbered in (entry, eigenvalue) order and those numbered >= ``row_quota`` dropped
+        (None: sel_size, "sets": cuts_per_set * sel_size).  -> the dict of :meth:`round_csr` plus ``row_lam`` [rows], ``row_rank``
+        [rows], ``n_neg`` [entries], ``n_used`` (entries that have a row) and ``quota_hit``.  cuts_per_set = 1 is :meth:`round_csr`
+        bit for bit.  point=None keeps the current LP point; views as there unless copy=True."""
+        m, quota = check_multi_args(cuts_per_set, row_quota, sel_size, strat)
+        vv = self._csr_point(point)
+        if getattr(self, "_h", None) is None:
+            raise SdpCutError("the Scorer is closed")
+        self.round_count += 1
+        out = RoundMulti()
+        self._check(self._lib.sdpcut_round_csr_multi(self._h, _ptr(vv, _dp), int(strat), int(sel_size), m, quota, ctypes.byref(out)))
+        o = out.csr
+        c, w, r, nnz = int(o.cap), int(o.n_out), int(o.n_rows), int(o.nnz)
+
+        def view(ptr, dtype, count, shape=None):
+            if not ptr or count == 0:
+                return np.zeros(shape if shape else 0, dtype=dtype)
+            a = np.frombuffer((_c.c_char * (count * np.dtype(dtype).itemsize)).from_address(ptr), dtype=dtype, count=count)
+            return a.reshape(shape) if shape else a
+        if not (c and o.idx):
+            w = r = nnz = 0
+        res = dict(idx=view(o.idx, np.int64, w), score=view(o.score, np.float64, w), lam=view(o.lam_min, np.float64, w),
+                   ks=view(o.ks, np.int32, w), set_inds=view(o.set_inds, np.int32, 5 * w, (w, 5)),
+                   row_entry=view(o.row_entry, np.int32, r), indices=view(o.indices, np.int32, nnz), values=view(o.values, np.float64, nnz),
+                   rhs=view(o.rhs, np.float64, r), n_neg=view(out.n_neg, np.int32, w), row_lam=view(out.row_lam, np.float64, r),
+                   row_rank=view(out.row_rank, np.int32, r))
+        res["indptr"] = view(o.indptr, np.int32, r + 1) if (c and o.idx) else np.zeros(1, np.int32)
+        if copy:
+            res = {k: a.copy() for k, a in res.items()}
+        cnt = o.counters
+        res.update(n_total=int(o.n_total), new_strat=int(o.new_strat), n_used=int(out.n_used), quota_hit=bool(out.quota_hit),
+                   row_cap=int(out.row_cap),
+                   counters=dict(nb_violated=int(cnt[0]), strong=int(cnt[1]), violated=int(cnt[2]), nb_positive=int(cnt[3])))
+        return res
+
+    def cut_rows_all(self, local_idx, cuts_per_set):
+        """Up to ``cuts_per_set`` eigen-cuts of each of the given candidates (local ids, any order, repeats allowed) at the current
+        LP point (sdpcut_cut_rows_all) -> (row_ptr int64 [count + 1], row_lam [rows], coef [rows, 20], rhs [rows], cols int64
+        [count, 20], ks int32 [count]): entry i owns rows row_ptr[i] .. row_ptr[i + 1] - 1, all on the columns cols[i]."""
+        m, _ = check_multi_args(cuts_per_set, 1)
+        idx = np.ascontiguousarray(local_idx, dtype=np.int64)
+        if idx.ndim != 1:
+            raise ValueError("local_idx must be a list of local candidate ids")
+        if getattr(self, "_h", None) is None:
+            raise SdpCutError("the Scorer is closed")
+        c = idx.shape[0]
+        row_ptr = np.zeros(c + 1, dtype=np.int64)
+        lam = np.empty(max(c * m, 1))
+        coef = np.empty((max(c * m, 1), ROW_LD))
+        rhs = np.empty(max(c * m, 1))
+        cols = np.empty((max(c, 1), ROW_LD), dtype=np.int64)
+        ks = np.empty(max(c, 1), dtype=np.int32)
+        self._check(self._lib.sdpcut_cut_rows_all(self._h, c, _ptr(idx, _i64p), m, _ptr(row_ptr, _i64p), _ptr(lam, _dp), _ptr(coef, _dp),
+                                                  _ptr(rhs, _dp), _ptr(cols, _i64p), _ptr(ks, _i32p)))
+        n = int(row_ptr[c])
+        return row_ptr, lam[:n], coef[:n], rhs[:n], cols[:c], ks[:c]
 
     # ------------------------------------------------------------------ many LP points per call
     def _points_arg(self, points):

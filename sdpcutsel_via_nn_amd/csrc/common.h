@@ -199,6 +199,7 @@ struct sdpcut_ctx {
     size_t train_ws_doubles = 0;
     void *d_dense = nullptr;       // dense eigen-cuts (dense.hip): V^T, sorted vectors, eigenvalues, n_rows; allocated by the first call
     void *diverse = nullptr;       // diverse selection (diverse.hip: DiverseWs): pool rows, pair bits, accepted head; allocated by the first call
+    void *multi = nullptr;         // multi-cut rounds (multirows.hip: MultiWs): head, look-back words, host arrays; allocated by the first call
     // sdpcut_shard_finish_enqueue -> sdpcut_shard_finish_wait
     int64_t shard_pending_serial = 0, shard_pending_sel = 0;
     int32_t shard_pending_world = 0, shard_pending_ld = 0;
@@ -345,6 +346,8 @@ void free_dense_ws(sdpcut_ctx *h);
 void free_train_ws(sdpcut_ctx *h);
 // diverse.hip
 void free_diverse_ws(sdpcut_ctx *h);
+// multirows.hip
+void free_multi_ws(sdpcut_ctx *h);
 
 // exact_sdp.hip (SDPCUT_SDP, SDPCUT_OPT_EXACT_SDP)
 int launch_exact_sdp(sdpcut_ctx *h);                 // d_sdp / d_sdp_gap of every candidate at the current point

@@ -478,6 +478,11 @@ class GpuCutSelectionMixin(object):
     # strategies 3 (optimality via the exact SDP solution) and -1 (figure 8: estimated against exact measure) on the device
     # (SDPCUT_OPT_EXACT_SDP, SDPCUT_SDP; exact_sdp.py is the numpy twin of the solver); off: both are refused as before
     _gpu_exact_sdp = False
+    # all violated eigen-cuts of a selected set: with cuts_per_set > 1 _gen_eigcuts_selected emits up to
+    # that many rows per selected set (Scorer.cut_rows_all) and keeps the first quota of them in list order -- the sel_size it is
+    # called with, or cuts_per_set times that with cuts_row_quota = "sets".  make_dropin_classes(..., cuts_per_set=m) sets it.
+    cuts_per_set = 1
+    cuts_row_quota = None
 
     # ------------------------------------------------------------------ a11 loader
     def _load_neural_nets(self):
@@ -685,6 +690,8 @@ class GpuCutSelectionMixin(object):
     def _gen_eigcuts_selected(self, strat, sel_size, rank_list, strong_only=False, vars_values=None):
         """Eigen-cuts of the first ``sel_size`` ranked candidates, appended to
         ``self._my_prob.linear_constraints`` (cut_select_qp.py:705-755)."""
+        if int(self.cuts_per_set) > 1 and sel_size > 0 and len(rank_list) > 0:
+            return self._gen_eigcuts_multi(strat, sel_size, rank_list, strong_only, vars_values)
         sel_size = min(sel_size, len(rank_list))
         opt_sel, feas_sel = strat in (2, 3, 4, -1), strat == 1
         pair = self._sparse_pair or _default_sparse_pair()
@@ -772,6 +779,112 @@ class GpuCutSelectionMixin(object):
             rhs_out.append(float(rhs[c]))
         store.add(lin_expr=rows, rhs=rhs_out, senses=["G"] * len(rows))
         return len(rows)
+
+    # ------------------------------------------------------------------ all violated eigen-cuts of a selected set
+    def _multi_log_add(self, **rec):
+        if getattr(self, "multi_log", None) is None:
+            self.multi_log = []
+        self.multi_log.append(rec)
+
+    def _multi_groups(self, strat, sel_size, rank_list, strong_only):
+        """The first ``sel_size`` entries of a rank list as runs of (binding, global candidate ids) in list order, or None where an
+        entry cannot be traced to a bound candidate."""
+        opt_sel = strat in (2, 3, 4, -1)
+
+        def of_rank_list(rl, count, cut_at_nonpositive):
+            idx = np.asarray(rl.ids(count), dtype=np.int64)
+            if cut_at_nonpositive:                            # cut_select_qp.py:725-726
+                stop = np.nonzero(rl.scores(count) <= 0)[0]
+                if stop.size:
+                    idx = idx[:stop[0]]
+            return rl._b, idx
+
+        def of_entries(entries, as_opt):
+            if as_opt:
+                if strong_only:
+                    cut = next((p for p, e in enumerate(entries) if e[1] <= 0), len(entries))
+                    entries = entries[:cut]
+                return [(self._gpu_bind(), np.array([e[0] for e in entries], dtype=np.int64))]
+            if not all(isinstance(e, FeasEntry) and e.binding is not None for e in entries):
+                return None
+            runs = []
+            for e in entries:
+                if runs and runs[-1][0] is e.binding:
+                    runs[-1][1].append(e.agg_idx)
+                else:
+                    runs.append((e.binding, [e.agg_idx]))
+            return [(g, np.array(ix, dtype=np.int64)) for g, ix in runs]
+
+        if isinstance(rank_list, _Concat):
+            groups, left = [], sel_size
+            for part in rank_list._parts:
+                if left <= 0:
+                    break
+                take = min(left, len(part))
+                rl = part.parent if isinstance(part, RankListHead) else part
+                if isinstance(rl, RankList):
+                    groups.append(of_rank_list(rl, take, opt_sel and strong_only and rl._kind != 1))
+                else:
+                    entries = list(part[0:take])
+                    g = of_entries(entries, bool(entries) and not isinstance(entries[0], FeasEntry) and opt_sel)
+                    if g is None:
+                        return None
+                    groups.extend(g)
+                left -= take
+            return groups
+        if isinstance(rank_list, RankListHead):
+            rank_list, sel_size = rank_list.parent, min(sel_size, len(rank_list))
+        if isinstance(rank_list, RankList):
+            return [of_rank_list(rank_list, sel_size, opt_sel and strong_only)]
+        if strat == 5 and rank_list is self._agg_list:
+            return [(self._gpu_bind(), np.arange(min(sel_size, len(rank_list)), dtype=np.int64) + self._gpu_bind().scorer.base)]
+        return of_entries(list(rank_list[0:sel_size]), opt_sel)
+
+    def _gen_eigcuts_multi(self, strat, sel_size, rank_list, strong_only, vars_values):
+        """_gen_eigcuts_selected with ``cuts_per_set`` > 1: every selected set offers up to that many eigen-cuts
+        (``Scorer.cut_rows_all``: one decomposition per set on the device), the first ``sel_size`` rows in list order are kept
+        (``cuts_row_quota = "sets"``: the first ``cuts_per_set * sel_size``).  One record per call goes to ``self.multi_log``."""
+        m = int(self.cuts_per_set)
+        quota = int(sel_size) * (m if self.cuts_row_quota == "sets" else 1)
+        groups = self._multi_groups(strat, min(sel_size, len(rank_list)), rank_list, strong_only)
+        if groups is None:
+            raise NotImplementedError("cuts_per_set > 1 needs rank lists whose entries name candidates bound to the device")
+        vv = vars_values
+        if vv is None:
+            rl = rank_list.parent if isinstance(rank_list, RankListHead) else rank_list
+            vv = getattr(rl, "_vv", None)
+        coef, rhs, cols, ks, per_entry = [], [], [], [], []
+        for g, idx in groups:
+            if idx.size:
+                self._gpu_point(g, vv, 0)
+                rp, _, co, rh, cl, kk = g.scorer.cut_rows_all(idx - g.scorer.base, m)
+                n = np.diff(rp)
+                ent = np.repeat(np.arange(idx.shape[0]), n)
+                coef.append(co), rhs.append(rh), cols.append(cl[ent]), ks.append(kk[ent]), per_entry.append(n)
+        store = self._my_prob.linear_constraints
+        if not coef:
+            store.add(lin_expr=[], rhs=[], senses=[])
+            self._multi_log_add(strat=strat, entries=0, entries_used=0, rows=0, offered=0, offered_hist=[0] * (m + 1), quota=quota, quota_hit=False)
+            return 0
+        coef, rhs, cols, ks, per_entry = (np.concatenate(a) for a in (coef, rhs, cols, ks, per_entry))
+        offered = int(coef.shape[0])
+        rows = min(offered, quota)
+        starts = np.concatenate([[0], np.cumsum(per_entry)[:-1]])
+        self._multi_log_add(strat=strat, entries=int(per_entry.shape[0]), entries_used=int(np.count_nonzero((per_entry > 0) & (starts < rows))),
+                            rows=rows, offered=offered, offered_hist=np.bincount(per_entry, minlength=m + 1).tolist(), quota=quota,
+                            quota_hit=offered > quota)
+        coef, rhs, cols, ks = coef[:rows], rhs[:rows], cols[:rows], ks[:rows]
+        if hasattr(store, "add_csr"):
+            indptr, ind, val = rows_to_csr(coef, cols, ks)
+            store.add_csr(indptr, ind, val, rhs, "G")
+            return rows
+        pair = self._sparse_pair or _default_sparse_pair()
+        out = []
+        for c in range(rows):
+            w = int(ks[c]) * (int(ks[c]) + 3) // 2
+            out.append(pair(ind=cols[c, :w].tolist(), val=coef[c, :w].tolist()))
+        store.add(lin_expr=out, rhs=rhs.tolist(), senses=["G"] * rows)
+        return rows
 
     # ------------------------------------------------------------------ dense eigen-cuts (strategy 0)
     def _gpu_dense_scorer(self):
@@ -1003,7 +1116,7 @@ class CutSolver(GpuCutSelectionMixin):
 
     def cut_select_algo(self, filename, dim, sel_size, strat=2, nb_rounds_cuts=20, term_on=False,
                         triangle_on=False, strong_only=False, max_subs=_THRES_MAX_SUBS, on_round=None, plots=False, sol=0,
-                        ch_ext=0, max_parallel=None, pool_factor=4):
+                        ch_ext=0, max_parallel=None, pool_factor=4, cuts_per_set=1, row_quota=None):
         """Cutting-plane rounds on a BoxQP ``.in`` file, same arguments and default return tuple as
         the reference's entry point (cut_select_qp.py:73-221), with HiGHS as LP solver, the native
         cover enumeration and the GPU selection / generation / triangle separation in between.
@@ -1024,6 +1137,12 @@ class CutSolver(GpuCutSelectionMixin):
         ``min(pool_factor * quota, 16384)`` ranked candidates and adds a cut only while fewer than the quota are added and its
         ``|cos|`` with every cut added before it in the round is at most ``max_parallel``; the walk's counts of every round are
         kept in ``self.diverse_log``.  The combined strategy's switch and ``strong_only`` work as without the filter.
+        ``cuts_per_set`` (1 = today's round, untouched; up to 5; not with strategy 0 or -1, not with ``max_parallel``): every
+        selected set offers all its violated eigen-cuts, at most that many (``Scorer.round_csr_multi``, DESIGN.md section 5 "All
+        violated eigen-cuts"; strategy 5 through ``Scorer.cut_rows_all``).  ``row_quota=None`` keeps the LP budget of a plain round
+        -- at most ``quota`` rows, so fewer sets are used -- and ``row_quota="sets"`` lets every one of the ``quota`` sets keep all
+        it offers (up to ``cuts_per_set * quota`` rows).  ``self.multi_log`` records every round: entries used, rows, the
+        histogram of violated eigenvalues per entry, whether the quota dropped a row.
         -> (bound per solve, total s, round s, separation s, PSD cuts per round, triangle cuts per
         round, number of candidates)."""
         from timeit import default_timer as clock
@@ -1041,6 +1160,14 @@ class CutSolver(GpuCutSelectionMixin):
             assert 0.0 <= max_parallel <= 1.0, "max_parallel is a bound on |cos| between two cuts: 0 .. 1"
             assert pool_factor >= 1, "the pool is pool_factor times the quota: pool_factor >= 1"
             self.diverse_log = []
+        m_cuts, _ = _capi.check_multi_args(cuts_per_set, 1)
+        if m_cuts > 1:
+            if max_parallel is not None:
+                raise AssertionError("cuts_per_set > 1 together with max_parallel is not offered")
+            if strat in (0, -1):
+                raise AssertionError("cuts_per_set > 1 serves the selecting strategies 1, 2, 3, 4 and 5 (strategy 0 emits every dense cut already)")
+            assert row_quota in (None, "sets"), 'row_quota is None (the round\'s quota in rows) or "sets" (cuts_per_set times the quota)'
+            self.multi_log = []
         t_start = clock()
         inst = harness.parse_boxqp(filename)
         self._dim = dim
@@ -1098,6 +1225,34 @@ class CutSolver(GpuCutSelectionMixin):
                 self._my_prob.linear_constraints.add(lin_expr=[], rhs=[], senses=[])
             return {"sdp": sdp, "tri": self._separate_and_add_triangle(sel_size, point) if triangle_on else 0}
 
+        def separate_multi(round_no, point):
+            """a round with all violated eigen-cuts of the selected sets: ranking, decompositions and assembled cuts in one library call"""
+            cur = state["strat"]
+            if cur == 5 or quota < 1:
+                return separate(round_no, point)          # (strategy 5: _gen_eigcuts_selected sees self.cuts_per_set)
+            b = self._gpu_bind()
+            b.drain()
+            vv = np.ascontiguousarray(point, dtype=np.float64)
+            r = b.scorer.round_csr_multi(vv, cur, quota, m_cuts, row_quota=row_quota)
+            b.note_point(vv, {1: _capi.EIG, 2: _capi.NN, 3: _capi.SDP, 4: _capi.EIG | _capi.NN}[cur])
+            b.rank_serial += 1
+            self._gpu_last = None
+            if cur == 4:
+                state["strat"] = r["new_strat"]           # the switch takes effect next round (:181 vs :188)
+            rows = int(r["rhs"].shape[0])
+            if strong_only and cur in (2, 3, 4):          # :725-726 -- row_entry ascends: the rows of the first entries are a prefix
+                stop = np.flatnonzero(r["score"] <= 0)
+                if stop.size:
+                    rows = int(np.searchsorted(r["row_entry"], int(stop[0])))
+            nnz = int(r["indptr"][rows])
+            used = int(r["row_entry"][rows - 1]) + 1 if rows else 0
+            self._multi_log_add(round=round_no, strat=cur, entries=int(r["idx"].shape[0]), entries_used=int(np.unique(r["row_entry"][:rows]).shape[0]),
+                                last_entry=used, rows=rows, n_neg_hist=np.bincount(r["n_neg"], minlength=6).tolist(),
+                                quota=int(r["row_cap"]), quota_hit=bool(r["quota_hit"]))
+            sdp = self._gpu_add_csr((r["indptr"][:rows + 1], r["indices"][:nnz], r["values"][:nnz], r["rhs"][:rows]),
+                                    self._sparse_pair or _default_sparse_pair())
+            return {"sdp": sdp, "tri": self._separate_and_add_triangle(sel_size, point) if triangle_on else 0}
+
         def separate(round_no, point):
             cur = state["strat"]
             if cur == 0:
@@ -1115,11 +1270,18 @@ class CutSolver(GpuCutSelectionMixin):
             tri = self._separate_and_add_triangle(sel_size, point) if triangle_on else 0
             return {"sdp": sdp, "tri": tri}
 
-        log = harness.run_cut_rounds(lp, separate if max_parallel is None else separate_diverse, nb_rounds_cuts, setup_s=t_model,
-                                     stop_tol=self._CONVERGENCE_TOL if term_on else None, on_round=on_round,
-                                     after_solve=self._gpu_wake,
-                                     # dense cuts: past the 4th round, stop once the rounds have taken 1000 s (:157)
-                                     stop=(lambda r, lg: r > 4 and sum(lg.solve_s) + sum(lg.separation_s) > 1000) if strat == 0 and term_on else None)
+        sep_fn = separate_multi if m_cuts > 1 else (separate if max_parallel is None else separate_diverse)
+        keep_attr = (self.cuts_per_set, self.cuts_row_quota)
+        if m_cuts > 1:
+            self.cuts_per_set, self.cuts_row_quota = m_cuts, row_quota
+        try:
+            log = harness.run_cut_rounds(lp, sep_fn, nb_rounds_cuts, setup_s=t_model,
+                                         stop_tol=self._CONVERGENCE_TOL if term_on else None, on_round=on_round,
+                                         after_solve=self._gpu_wake,
+                                         # dense cuts: past the 4th round, stop once the rounds have taken 1000 s (:157)
+                                         stop=(lambda r, lg: r > 4 and sum(lg.solve_s) + sum(lg.separation_s) > 1000) if strat == 0 and term_on else None)
+        finally:
+            self.cuts_per_set, self.cuts_row_quota = keep_attr
         sep = [t_model] + log.separation_s
         if plots:       # :209-215 (curr_obj_vals of the reference = log.bounds)
             gap_closed_percent = [0] + [(-v + log.bounds[0]) / (sol + log.bounds[0]) for v in log.bounds[1:]]
@@ -1151,6 +1313,11 @@ class CutSolverQCQP(CutSolver):
         self._agg_list = agg_list                            # :78
         n_obj = min(len(comb_obj), sel_size)
         rank_list = comb_obj[0:n_obj] + feas_cons[0:sel_size - n_obj]      # == (A + B)[0:sel_size], :79
+        if int(self.cuts_per_set) > 1 and strat_old != 1:
+            # all violated eigen-cuts: ONE walk over the concatenated head, so that the row quota is applied in list order
+            nb_opt_cuts = (comb_obj.count_above(_BIG_M) if isinstance(comb_obj, RankList) else
+                           int(np.count_nonzero(np.array([e[1] for e in comb_obj]) > _BIG_M))) if len(comb_obj) else 0
+            return strat, rank_list, self._gen_eigcuts_selected(strat_old, sel_size, rank_list, vars_values=vars_values), nb_opt_cuts
         if strat_old == 1:
             nb = self._gen_eigcuts_selected(strat_old, sel_size, rank_list, vars_values=vars_values)
             return strat, rank_list, nb, 0
@@ -1164,16 +1331,20 @@ class CutSolverQCQP(CutSolver):
                                           vars_values=vars_values)
         return strat, rank_list, nb_a + nb_b, nb_opt_cuts
 
-    def cut_select_algo(self, filename, dim, sel_size=0.1, strat=2, nb_rounds_cuts=20):
+    def cut_select_algo(self, filename, dim, sel_size=0.1, strat=2, nb_rounds_cuts=20, cuts_per_set=1):
         """Cutting-plane rounds on a QCQP in OSiL format, same arguments and return tuple as the
         reference's QCQP entry point (cut_select_qcqp.py:16-113), with HiGHS, the native enumeration
         of both covers and :meth:`select_and_generate_round` between two solves.
+        ``cuts_per_set`` > 1: the two-handle selection runs as before, then each handle emits up to that many eigen-cuts for its
+        part of the concatenated head (``Scorer.cut_rows_all``) and the first ``sel_size`` rows in list order are kept
+        (``self.multi_log`` has one record per round).
         -> (objective value per solve, sel_size, PSD cuts per round, optimality cuts per round)."""
         from . import harness
         if strat not in (1, 2, 4, 5) and not (self._gpu_exact_sdp and strat == 3):      # cut_select_qcqp.py:26 allows 3
             raise AssertionError("strategies on the GPU path: 1 feasibility, 2 optimality, 4 combined, 5 random (3 exact optimality with exact_sdp=True)")
         assert 0 < sel_size, "The selection size must be a % or number (of cuts) >0!"
         assert dim <= 5, "Keep SDP vertex cover low-dimensional (<=5)!"
+        m_cuts, _ = _capi.check_multi_args(cuts_per_set, 1)
         inst = harness.parse_osil(filename)
         self._dim = dim
         self._nb_vars, self._nb_lifted, self._Q_arr = inst["nb_vars"], inst["nb_lifted"], inst["Q_arr"]
@@ -1200,12 +1371,18 @@ class CutSolverQCQP(CutSolver):
                                                                          cover_obj, cover_cons)
             return {"sdp": sdp, "opt": opt}
 
-        log = harness.run_cut_rounds(lp, separate, nb_rounds_cuts, after_solve=self._gpu_wake)
+        keep_attr = (self.cuts_per_set, self.cuts_row_quota)
+        if m_cuts > 1:
+            self.cuts_per_set, self.cuts_row_quota, self.multi_log = m_cuts, None, []
+        try:
+            log = harness.run_cut_rounds(lp, separate, nb_rounds_cuts, after_solve=self._gpu_wake)
+        finally:
+            self.cuts_per_set, self.cuts_row_quota = keep_attr
         opt = log.column("opt")
         return log.bounds, quota, [0] + log.column("sdp"), [0] + opt + [0] * (nb_rounds_cuts - len(opt))
 
 
-def make_dropin_classes(cut_select_qp, cut_select_qcqp=None, exact_heads=False, exact_sdp=False):
+def make_dropin_classes(cut_select_qp, cut_select_qcqp=None, exact_heads=False, exact_sdp=False, cuts_per_set=1):
     """Compose the GPU mixin with the reference's own classes (modules passed in, nothing is
     imported here) -> (GpuCutSolver, GpuCutSolverQCQP or None).
 
@@ -1220,9 +1397,13 @@ def make_dropin_classes(cut_select_qp, cut_select_qcqp=None, exact_heads=False, 
 
     exact_heads: the classes' ``_gpu_exact_heads`` (SDPCUT_OPT_EXACT_HEAD on every handle they create).
     exact_sdp: the classes' ``_gpu_exact_sdp`` (strategies 3 and -1 on the device instead of a NotImplementedError).
+    cuts_per_set: the classes' ``cuts_per_set`` (1 .. 5): ``_gen_eigcuts_selected`` emits up to that many eigen-cuts per selected set
+        and keeps the first ``sel_size`` rows (all violated eigen-cuts).
     """
+    m_cuts, _ = _capi.check_multi_args(cuts_per_set, 1)
     qp = type("GpuCutSolver", (GpuCutSelectionMixin, cut_select_qp.CutSolver),
-              {"__doc__": "CutSolver with the hot path on the GPU", "_gpu_exact_heads": bool(exact_heads), "_gpu_exact_sdp": bool(exact_sdp)})
+              {"__doc__": "CutSolver with the hot path on the GPU", "_gpu_exact_heads": bool(exact_heads), "_gpu_exact_sdp": bool(exact_sdp),
+               "cuts_per_set": m_cuts})
     qcqp = None
     if cut_select_qcqp is not None:
         qcqp = type("GpuCutSolverQCQP", (cut_select_qcqp.CutSolverQCQP, qp), {"__doc__": "CutSolverQCQP with the hot path on the GPU"})
