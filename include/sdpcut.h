@@ -129,9 +129,14 @@ enum { SDPCUT_KERNEL_MFMA = 0, SDPCUT_KERNEL_SIMPLE = 1, SDPCUT_KERNEL_VALU = 2 
  * sdpcut_score(SDPCUT_SDP); the fused calls score it themselves if it is missing, then run the selection that strategy 2 runs on
  * scores that exist already.  No networks needed.  SDPCUT_OPT_EXACT_HEAD ignores strategy 3; the sharded entry points
  * (sdpcut_shard_*) refuse it.  With the option off strategy 3 is refused exactly as before (SDPCUT_EINVAL, "strategy must be ..."). */
+/* SDPCUT_OPT_COUNT_RANK (default 1): the sort tail of a top-k selection whose head fits 8192 entries orders the compacted
+ * superset of the head by COUNTING in one launch (csrc/topk_sort.hip, tk_countrank_kernel: the rank of an entry is the number of
+ * (key, [obj_improve,] index) composites in front of it) instead of a tile sort and a rank merge in two.  Same head, bit for bit.
+ * 0: the two launches (A/B; they also serve heads of 8193 .. 16384 entries, raw key output and shard records either way). */
 enum { SDPCUT_OPT_KERNEL = 1, SDPCUT_OPT_TIMING = 2, SDPCUT_OPT_FUSE_KEYS = 3, SDPCUT_OPT_AUTO_REGIME = 4,
        SDPCUT_OPT_FUSED_TAIL = 5, SDPCUT_OPT_COOP_LAUNCH = 6, SDPCUT_OPT_EIG_KERNEL = 7, SDPCUT_OPT_STREAM_PRIORITY = 8,
-       SDPCUT_OPT_SIDE_STREAMS = 9, SDPCUT_OPT_ONE_LAUNCH = 10, SDPCUT_OPT_PREFILTER = 11, SDPCUT_OPT_EXACT_HEAD = 12, SDPCUT_OPT_EXACT_SDP = 13 };
+       SDPCUT_OPT_SIDE_STREAMS = 9, SDPCUT_OPT_ONE_LAUNCH = 10, SDPCUT_OPT_PREFILTER = 11, SDPCUT_OPT_EXACT_HEAD = 12, SDPCUT_OPT_EXACT_SDP = 13,
+       SDPCUT_OPT_COUNT_RANK = 14 };
 
 /* Counters of a handle: SDPCUT_STAT_ROUNDS = fused rounds served (sdpcut_select_round*),
  * SDPCUT_STAT_SELECT_FALLBACKS = rounds whose radix selection declared itself void (a grid barrier

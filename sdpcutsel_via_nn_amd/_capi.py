@@ -26,6 +26,7 @@ OPT_EXACT_HEAD = 12      # NN-ranked heads ordered and reported by reference-ord
 STAT_ROUNDS, STAT_SELECT_FALLBACKS, STAT_SCORED, STAT_TIE_SPLITS, STAT_DIRECT_SELECTIONS, STAT_PF_BIN, STAT_PF_FLOOR, STAT_PF_COUNT = 1, 2, 3, 4, 5, 6, 7, 8
 STAT_EXACT_HEAD, STAT_EXACT_GAVE_UP, STAT_EXACT_RETRIES = 9, 10, 11
 OPT_EXACT_SDP = 13       # strategy 3 accepted by the ranking and round calls (include/sdpcut.h)
+OPT_COUNT_RANK = 14      # the sort tail of a selection ranks by counting in one launch (include/sdpcut.h); default on
 STAT_SDP_UNCONVERGED = 12
 STAT_POINTS_REDONE = 13   # points of batched rounds served by the single-point round inside the call (include/sdpcut.h)
 BATCH_MAX_POINTS = 256   # SDPCUT_BATCH_MAX_POINTS: most LP points of one score_points / round_csr_points call

@@ -155,6 +155,9 @@ int sdpcut_set_option(sdpcut_handle h, int option, int64_t value)
     case SDPCUT_OPT_PREFILTER:
         h->prefilter = value != 0;
         return SDPCUT_OK;
+    case SDPCUT_OPT_COUNT_RANK:
+        h->count_rank = value != 0;
+        return SDPCUT_OK;
     case SDPCUT_OPT_EXACT_HEAD:
         SDPCUT_NO_PENDING(h);
         h->exact_head = value != 0;

@@ -175,6 +175,8 @@ struct sdpcut_ctx {
     bool topk_alt_clean = false;   // d_topk_ws_alt has been (stream-ordered) zeroed and may be swapped in
     uint64_t *d_sel_key = nullptr;
     uint32_t *d_sel_idx = nullptr;
+    bool count_rank = true;        // SDPCUT_OPT_COUNT_RANK: the sort tail ranks by counting in one launch (tk_countrank_kernel)
+    unsigned long long *d_rank_acc = nullptr;   // [TK_LDSK] rank sum | arrivals of every compacted entry; zero between launches
     // triangle inequalities (tri.hip)
     int32_t *d_tri = nullptr;          // [T][3]
     uint8_t *d_tri_dense3 = nullptr;   // [T] density == 3

@@ -307,7 +307,7 @@ int exact_head_enqueue(sdpcut_ctx *h, int strat, int64_t sel_size, int64_t cap, 
     const int64_t sel = sel_size < n ? sel_size : n;
     TkRouteIn in;
     in.n = band; in.k = cap; in.mode = mode; in.stage = 1; in.prekeys = true;
-    in.fused_tail = h->fused_tail; in.tk_coresident = h->tk_coresident;
+    in.fused_tail = h->fused_tail; in.tk_coresident = h->tk_coresident; in.count_rank = h->count_rank;
     const TkPlan p = tk_route(in);      // (only the sort tail's grid and tie rule are read)
     if (p.err) return sdpcut_fail(h, p.err, p.msg);
     // ---- zero band.  Combined strategy only: under strategy 2 no class depends on the sign of obj_improve (the one thing that

@@ -32,7 +32,8 @@
 //   ONFLY, COOP, FUSED, DIGITS              topk_passes.hip   tk_keys_kernel / tk_prekeys_kernel (key pass of COOP, FUSED, DIGITS),
 //                                                             tk_refine_kernel<ONFLY>, tk_hist_kernel (DIGITS)
 //   DIGITS, its compaction                  topk_compact.hip  tk_count_kernel, tk_write_kernel
-//   the sort tail of all but SMALLSORT      topk_sort.hip     tk_tilesort_kernel<TIE>, tk_mergerank_kernel<TIE>, tk_mergerank_big_kernel<TIE>
+//   the sort tail of all but SMALLSORT      topk_sort.hip     tk_countrank_kernel<TIE>, or tk_tilesort_kernel<TIE> and
+//                                                             tk_mergerank_kernel<TIE> / tk_mergerank_big_kernel<TIE>
 // Device code shared between them (TopkWs, resolve_digit, finish_pass, comp_less) and with the score kernels: topk_dev.h.
 // The one-workgroup select-sort-emit algorithm (smallsel_body) is in topk_small_dev.h: tk_smallsel_kernel and the batched
 // tk_points_kernel (points.hip, a workgroup per LP point) are its two hosts.
@@ -47,6 +48,9 @@ int ensure_topk_ws(sdpcut_ctx *h)
     // first half: compacted selection, second half: the sorted tiles
     HIP_TRY(h, hipMalloc((void **)&h->d_sel_key, 2 * TK_MAXK * sizeof(uint64_t)));
     HIP_TRY(h, hipMalloc((void **)&h->d_sel_idx, 2 * TK_MAXK * sizeof(uint32_t)));
+    // tk_countrank_kernel's per-entry words: zeroed once here, the wave that completes a word leaves it zero again
+    HIP_TRY(h, hipMalloc((void **)&h->d_rank_acc, TK_LDSK * sizeof(unsigned long long)));
+    HIP_TRY(h, hipMemsetAsync(h->d_rank_acc, 0, TK_LDSK * sizeof(unsigned long long), h->stream));
     const int rc = tk_refine_coresident(h, &h->tk_coresident);
     if (rc) return rc;
     if (h->tk_coresident < 1) h->fused_tail = false;      // (never on gfx950: 4 per CU by LDS) the launch-per-digit path has no waits
@@ -56,6 +60,8 @@ int ensure_topk_ws(sdpcut_ctx *h)
 void free_topk_ws(sdpcut_ctx *h)
 {
     (void)hipFree(h->d_topk_ws); (void)hipFree(h->d_topk_ws_alt); (void)hipFree(h->d_sel_key); (void)hipFree(h->d_sel_idx);
+    (void)hipFree(h->d_rank_acc);
+    h->d_rank_acc = nullptr;
     h->d_topk_ws = nullptr; h->d_topk_ws_alt = nullptr; h->d_sel_key = nullptr; h->d_sel_idx = nullptr;
     h->topk_alt_clean = false;
 }
@@ -102,7 +108,7 @@ static TkPlan plan_for(const sdpcut_ctx *h, int64_t n, int64_t k, int mode, int 
     in.n = n; in.k = k; in.mode = mode; in.stage = stage;
     in.fused_tail = h->fused_tail; in.coop_launch = h->coop_launch; in.shard_rec = h->shard_rec != nullptr;
     in.prefilter = h->prefilter; in.pf_counted = h->pf_counted; in.tk_coresident = h->tk_coresident;
-    in.prekeys = prekeys; in.raw = raw;
+    in.prekeys = prekeys; in.raw = raw; in.count_rank = h->count_rank;
     return tk_route(in);
 }
 

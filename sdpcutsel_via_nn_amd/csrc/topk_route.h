@@ -11,6 +11,11 @@
 #define TK_LDSK 8192     // heads whose compacted superset (keys AND indices) fits the merge kernel's LDS
 #define TK_MAXK 16384    // largest head: the merge keeps the keys in LDS and reads indices only on ties
 #define TK_TILE 512      // entries of a sort tile (tk_tilesort_kernel)
+// tk_countrank_kernel: every group of 64 compacted entries is ranked by TK_CR_SLICES waves, one per slice of the scanned keys
+// (a multiple of the four waves of a workgroup)
+#ifndef TK_CR_SLICES
+#define TK_CR_SLICES 32
+#endif
 #define TK_CACHE 4096    // keys of a workgroup's chunk kept in LDS between the passes (32 KB)
 // lists of at most TK_SMALLSEL_N candidates with a head of at most TK_LDSK: selection by ONE workgroup, keys in LDS (tk_smallsel_kernel)
 #ifndef TK_SMALLSEL
@@ -68,6 +73,7 @@ struct TkRouteIn {
     bool prekeys = false;                             // the keys exist already (tk_prekeys_kernel is the key pass): rows 5-7 only
     bool raw = false;                                 // the head's scores are emitted as raw key images (big-head merge only)
     bool smallsel = TK_SMALLSEL != 0, smallsort = TK_SMALLSORT != 0;
+    bool count_rank = true;                           // SDPCUT_OPT_COUNT_RANK
 };
 
 struct TkPlan {
@@ -75,10 +81,13 @@ struct TkPlan {
     const char *msg = nullptr;
     int route = 0;                // TkRoute
     int64_t maxk = 0;             // what the sort buffers of this head hold: an early stop compacts up to maxk entries
-    // sort tail (none behind TK_ROUTE_SMALLSORT): tk_tilesort_kernel<sort_tie>, then tk_mergerank_kernel<sort_tie> or, for big
-    // heads, tk_mergerank_big_kernel<sort_tie != 0>
+    // sort tail (none behind TK_ROUTE_SMALLSORT): tk_countrank_kernel<sort_tie> alone where count_rank says so, else
+    // tk_tilesort_kernel<sort_tie>, then tk_mergerank_kernel<sort_tie> or, for big heads, tk_mergerank_big_kernel<sort_tie != 0>
     int sort_tie = 0;             // 0 ties by index, 1 COMBALL (by obj_improve, then index), 2 COMBAUTO (decided on the device)
     bool big_merge = false;       // heads of 8193 .. 16384: keys-only merge
+    // ranks by counting in ONE launch (topk_sort.hip): heads that fit TK_LDSK, scores emitted as scores, no shard record behind
+    // the head (its header and padding are written by tk_mergerank_kernel)
+    bool count_rank = false;
     int ntiles = 0;               // grid of the tile sort; the merge runs ntiles * TK_TILE / TK_THREADS workgroups
     int grid_keys = 0;            // grid of the key pass (tk_keys_kernel / tk_prekeys_kernel)
     int grid_pass = 0;            // grid of the digit passes, the count and the compaction
@@ -138,6 +147,7 @@ static inline TkPlan tk_route(const TkRouteIn &in)
         p.route = in.coop_launch ? TK_ROUTE_COOP : TK_ROUTE_FUSED;      // cooperative: the runtime guarantees the co-residency (+20 us per launch)
     else      // one launch per digit, no wait anywhere inside a kernel: the path that always answers
         p.route = TK_ROUTE_DIGITS;
+    p.count_rank = in.count_rank && !p.big_merge && !in.raw && !in.shard_rec;
     // big heads (8193 .. 16384): keys-only merge; the device-resolved regime never asks for them
     if (p.big_merge && in.mode == TK_MODE_COMBAUTO) return tk_refuse(p, SDPCUT_EINVAL, "top-k select: head too long for this mode");
     if (!p.big_merge && in.raw) return tk_refuse(p, SDPCUT_EINVAL, "top-k select: raw output needs the big-head merge");

@@ -8,7 +8,9 @@
 //   2. tk_mergerank_kernel: every entry's final rank = its position in its own tile + the number
 //      of entries preceding it in every other tile (binary searches over tiles staged in LDS;
 //      composites are unique, so ranks are a permutation).
-// ~k log k work instead of the k^2 of a counting sort, two short launches.
+// ~k log k work instead of the k^2 of a counting sort, two short launches.  They serve the big heads, the raw key output and
+// the shard records.  Everything else (TkPlan::count_rank) is ranked by tk_countrank_kernel below: on a chain of short
+// dependent launches a launch costs more than k^2 comparisons spread over an otherwise idle device.
 
 template <bool TIE>
 __device__ __forceinline__ void tilesort_body(const TopkWs *ws, const uint64_t *sel_key, const uint32_t *sel_idx,
@@ -221,6 +223,89 @@ __global__ __launch_bounds__(TK_THREADS) void tk_mergerank_big_kernel(int64_t ba
     score_out[rank] = raw ? __longlong_as_double((long long)(~ke & 0x7fffffffffffffffull)) : score_of(~ke) + score_add;
 }
 
+// ---- ranks by counting, ONE launch (TkPlan::count_rank) ----------------------------------------------------------------------
+// The rank of an entry among the n_sel <= TK_LDSK unique composites is the number of composites in front of it.  A wave is
+// (group g of 64 compacted entries, slice s of the TK_CR_SLICES slices of the scanned entries); lane = entry.  The slice bounds
+// depend on n_sel alone, so the scanned keys and indices are wave-uniform and arrive through scalar loads, eight pairs at a time;
+// per scanned key a 64-bit compare with an add, and a compare for equality whose vcc decides ONE scalar branch: only where some
+// lane holds an equal key does the tie rule of comp_less<TIE> run (by index; TIE: obj_improve of the scanned entry first -- a
+// scalar load; the lane's own side is fetched once, in front of the loop).
+// The TK_CR_SLICES partial ranks of an entry meet in acc[entry] = arrivals << 32 | rank sum through one returning device-scope
+// add each.  The wave that sees the last arrival holds the final rank, emits the entry exactly as mergerank_body does and leaves
+// the word zero for the next launch (the words are zeroed once, when the workspace is made: ensure_topk_ws).  No workgroup waits
+// for another.  Groups beyond n_sel return at once, as idle tiles do.
+template <bool TIE>
+__device__ __forceinline__ void countrank_body(int64_t base, double score_add, const TopkWs *ws, const uint64_t *__restrict__ sel_key,
+                                               const uint32_t *__restrict__ sel_idx, unsigned long long *acc, int64_t *idx_out,
+                                               double *score_out, const double *__restrict__ obj)
+{
+    constexpr int WPG = TK_THREADS / 64;              // slices (waves) per workgroup
+    constexpr int BPG = TK_CR_SLICES / WPG;           // workgroups per entry group
+    static_assert(TK_CR_SLICES % WPG == 0 && BPG >= 1, "a workgroup holds whole slices");
+    int n_sel = (int)ws->n_sel;
+    if (n_sel > TK_LDSK) n_sel = TK_LDSK;             // (never: this path is planned for heads whose superset fits TK_LDSK)
+    const int k_eff = (int)ws->counters[3];
+    const int g = blockIdx.x / BPG;
+    if (g * 64 >= n_sel) return;                      // uniform
+    const int s = __builtin_amdgcn_readfirstlane((int)(blockIdx.x % BPG) * WPG + (int)(threadIdx.x >> 6));
+    const int e = g * 64 + (int)(threadIdx.x & 63);
+    const bool live = e < n_sel;
+    const uint64_t ke = live ? ~sel_key[e] : 0ull;
+    const uint32_t ie = live ? sel_idx[e] : 0u;
+    uint64_t oe = 0ull;
+    if constexpr (TIE) oe = live ? key_of(obj[ie]) : 0ull;
+    const int len = ((n_sel + TK_CR_SLICES - 1) / TK_CR_SLICES + 7) & ~7;
+    const int lo = s * len;
+    const int hi = lo + len < n_sel ? lo + len : n_sel;      // (lo >= n_sel: an empty slice still reports its zero)
+    uint32_t rank = 0;
+    auto scan = [&](const uint64_t key, const uint32_t si) __attribute__((always_inline)) {
+        const uint64_t sk = ~key;
+        rank += sk < ke ? 1u : 0u;
+        if (__ballot(sk == ke)) {                     // some lane ties with the scanned key (its own entry included): scalar branch
+            asm volatile("" ::: "memory");            // (keeps the branch: flattened, every key pays the tie rule's compares)
+            bool first = si < ie;
+            if constexpr (TIE) {
+                const uint64_t os = key_of(obj[si]);
+                first = os != oe ? os > oe : first;
+            }
+            rank += (sk == ke && first) ? 1u : 0u;
+        }
+    };
+    int j = lo;
+    for (; j + 8 <= hi; j += 8) {
+        uint64_t kk[8];
+        uint32_t ii[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) { kk[u] = sel_key[j + u]; ii[u] = sel_idx[j + u]; }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) scan(kk[u], ii[u]);
+    }
+    for (; j < hi; ++j) scan(sel_key[j], sel_idx[j]);
+    if (!live) return;
+    const unsigned long long old = __hip_atomic_fetch_add(&acc[e], (1ull << 32) | (unsigned long long)rank, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if ((uint32_t)(old >> 32) != (uint32_t)(TK_CR_SLICES - 1)) return;
+    __hip_atomic_store(&acc[e], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int final_rank = (int)((uint32_t)old + rank);
+    if (final_rank >= k_eff) return;                  // superset entries beyond the head
+    idx_out[final_rank] = base + (int64_t)ie;
+    score_out[final_rank] = score_of(~ke) + score_add;
+}
+
+// TIE as in tk_tilesort_kernel
+template <int TIE>
+__global__ __launch_bounds__(TK_THREADS) void tk_countrank_kernel(int64_t base, double score_add, const TopkWs *ws,
+                                                                  const uint64_t *sel_key, const uint32_t *sel_idx,
+                                                                  unsigned long long *acc, int64_t *idx_out, double *score_out,
+                                                                  const double *obj)
+{
+    if (TIE == 1 || (TIE == 2 && ws->mode == TK_MODE_COMBALL)) {
+        // (device-resolved regime: BIG_M belongs to the strong class only, not to COMBALL's own scores)
+        countrank_body<true>(base, TIE == 2 ? 0.0 : score_add, ws, sel_key, sel_idx, acc, idx_out, score_out, obj);
+    } else {
+        countrank_body<false>(base, score_add, ws, sel_key, sel_idx, acc, idx_out, score_out, obj);
+    }
+}
+
 // T: the plan's sort_tie.  Big heads (8193 .. 16384) go through the keys-only merge, the only one with the raw key output;
 // the device-resolved regime (T = 2) never asks for them (tk_route refuses).
 template <int T>
@@ -229,6 +314,12 @@ static void sort_launch(sdpcut_ctx *h, const TkPlan &p, const TkJob &j)
     uint64_t *tile_key = h->d_sel_key + TK_MAXK;      // first half: compacted selection, second half: the sorted tiles
     uint32_t *tile_idx = h->d_sel_idx + TK_MAXK;
     const double *tie_obj = T ? (j.tie_obj ? j.tie_obj : h->d_obj) : nullptr;
+    if (p.count_rank) {      // one launch: 64-entry groups x slices, four slices per workgroup; idle groups exit at once
+        const dim3 g_count(p.ntiles * (TK_TILE / 64) * (TK_CR_SLICES / (TK_THREADS / 64)));
+        hipLaunchKernelGGL(tk_countrank_kernel<T>, g_count, dim3(TK_THREADS), 0, h->stream, j.base, j.score_add, j.ws, h->d_sel_key,
+                           h->d_sel_idx, h->d_rank_acc, j.d_idx_out, j.d_score_out, tie_obj);
+        return;
+    }
     const dim3 g_sort(p.ntiles), g_merge(p.ntiles * TK_TILE / TK_THREADS), blk(TK_THREADS);      // idle tiles exit at once
     hipLaunchKernelGGL(tk_tilesort_kernel<T>, g_sort, blk, 0, h->stream, j.ws, h->d_sel_key, h->d_sel_idx, tile_key, tile_idx, tie_obj);
     if constexpr (T < 2) {
