@@ -197,6 +197,14 @@ int sdpcut_wake(sdpcut_handle h);
  *   xoffset[d_in], gain[d_in], ymin,
  *   for each layer: W[width][fan_in] row-major, b[width],
  *   y_ymin, y_gain, y_xoffset                      with d_in = k(k+3)/2.
+ * Any tansig MLP with one hidden width <= 64 and <= 4 hidden layers is accepted.  The input domain of a network is
+ * x_i in [0, 1] (the first k inputs) and q_m in [-1/k, 1/k] (Q_slice / max_elem); input i is mapped by
+ * v -> (v - xoffset_i) gain_i + ymin.  On that domain every score kernel computes the network itself.  A network whose hidden
+ * pre-activations are provably below 40 for mapped inputs in [-3, 3] AND whose mapping sends the domain into [-3, 3] runs the
+ * clamp-free variant of the MFMA kernel, which cuts a mapped input outside [-3, 3] -- an LP point beyond the box -- at +-3;
+ * every other network runs the variant that clamps the tansig arguments and no input.
+ * Replacing the network of a size class invalidates the optimality scores of the current list (they are computed again by the
+ * next call that needs them).
  */
 int sdpcut_set_network(sdpcut_handle h, int k, int n_layers, const int32_t *widths,
                        const double *params, int64_t n_params);

@@ -33,8 +33,9 @@ struct NetDev {
     const double *raw_b[MAX_LAYERS];
     double ymin, b_out, y_ymin, y_gain, y_xoffset;
     // every pre-activation is provably below the tansig's overflow clamp when the mapped inputs lie in
-    // [-SDPCUT_INPUT_CLAMP, SDPCUT_INPUT_CLAMP] (sdpcut_set_network): the MFMA kernel then clamps the 9..20
-    // inputs of a candidate once instead of its 150..256 activations
+    // [-SDPCUT_INPUT_CLAMP, SDPCUT_INPUT_CLAMP], AND the network's mapping sends the input domain (x in [0, 1], |q| <= 1/k)
+    // into that interval (net_pack.h, sdpcut_set_network): the MFMA kernel then clamps the 9..20 inputs of a candidate once
+    // instead of its 150..256 activations, and that clamp changes nothing on the domain
     int unclamped_ok;
 };
 

@@ -61,6 +61,7 @@ int sdpcut_set_network(sdpcut_handle h, int k, int n_layers, const int32_t *widt
     hipFree(nh_.d_blob);
     nh_.d_blob = nullptr;
     nh_.set = false;
+    h->scored &= ~(uint32_t)SDPCUT_NN;      // the list's optimality scores were the old network's: a round scores again
     HIP_TRY(h, hipMalloc((void **)&nh_.d_blob, pk.blob.size() * sizeof(double)));
     HIP_TRY(h, hipMemcpy(nh_.d_blob, pk.blob.data(), pk.blob.size() * sizeof(double), hipMemcpyHostToDevice));
     NetDev &d = nh_.dev;

@@ -144,7 +144,8 @@ static inline int net_pack(int k, int n_layers, const int32_t *widths, const dou
     }
     {
         // bound of every hidden pre-activation: |n_j| <= sum_i |W_ji| max|in_i| + |b_j| with |in| <= SDPCUT_INPUT_CLAMP
-        // for the mapped inputs (x in [0,1], |q| <= 1/k map into [-1,1]) and <= 1 behind a tansig.  The tansig4 path
+        // for the mapped inputs (the clamp-free kernel cuts them there; the shipped mappings send x in [0,1], |q| <= 1/k into
+        // [-1,1]) and <= 1 behind a tansig.  The tansig4 path
         // needs -2n <= 176, the tail rows -2n <= 704; 80 leaves a factor of two.
         double worst = 0.0;
         int fan = d_in;
@@ -157,7 +158,20 @@ static inline int net_pack(int k, int n_layers, const int32_t *widths, const dou
             }
             fan = H;
         }
-        out->unclamped_ok = worst < 40.0 ? 1 : 0;      // |n| < 40  <=>  -2n < 80
+        // ... and the clamp-free variant clamps the mapped inputs to +-SDPCUT_INPUT_CLAMP, which is what makes the bound a proof.
+        // It may only run where that clamp cannot change a score: the image of the documented input domain -- x_i in [0, 1] for
+        // i < k, q_m in [-1/k, 1/k] behind them (Q_slice / max_elem, max_elem = k max|Q_slice|) -- under
+        // v -> (v - xoffset_i) gain_i + ymin must lie in [-3, 3] for every input (an affine map: its two endpoints decide).
+        // True of the shipped mappings (gain ~ 2, ymin -1); a network trained on a narrower range (x in [0.4, 0.6]: gain 10) maps
+        // [0, 1] onto [-5, 5] and takes the CLAMP = true instantiation, which clamps no input and needs no bound.
+        bool domain_ok = true;
+        for (int i = 0; i < d_in; ++i) {
+            const double lo = i < k ? 0.0 : -1.0 / (double)k, hi = i < k ? 1.0 : 1.0 / (double)k;
+            const double a = (lo - xoffset[i]) * gain[i] + out->ymin, b = (hi - xoffset[i]) * gain[i] + out->ymin;
+            // (written so that a NaN fails)
+            if (!(std::fabs(a) <= SDPCUT_INPUT_CLAMP && std::fabs(b) <= SDPCUT_INPUT_CLAMP)) domain_ok = false;
+        }
+        out->unclamped_ok = (worst < 40.0 && domain_ok) ? 1 : 0;      // |n| < 40  <=>  -2n < 80
     }
     return SDPCUT_OK;
 }

@@ -200,8 +200,11 @@ __device__ __forceinline__ void tail_rows1(const double (&ts)[1][NT ? NT : 1], c
 // ------------------------------------------------------------------------------------------
 // MFMA kernel.  K candidate size, H hidden width, NH hidden layers; FUSE = TK_MODE_FEAS / OPT / STRONG:
 // also count the class members by the leading radix digit of that mode's selection keys (ScoreArgs::tk).
-// CLAMP = false (NetDev::unclamped_ok): the tansig clamps are dropped and the staged inputs are
-// clamped to [-3, 3] instead (inactive for every x in [0, 1], |q| <= 1/k, see sdpcut_set_network).
+// CLAMP = false (NetDev::unclamped_ok): the tansig clamps are dropped and the staged (mapped) inputs are
+// clamped to [-3, 3] instead.  net_pack grants unclamped_ok only to a network whose own mapping sends the input
+// domain -- x in [0, 1], |q| <= 1/k -- into [-3, 3], so on the domain the clamp is inactive and the kernel computes
+// the network itself; outside it (an LP point a solver tolerance beyond the box) it cuts the mapped input at +-3,
+// which keeps the bound on the pre-activations a proof.  CLAMP = true clamps no input (see sdpcut_set_network).
 // JK = 16-candidate column tiles per pass (mfma_cols, score_plan.h).
 
 // LDS of one workgroup of the MFMA kernel for size class K (a union of these serves the launch over all classes)

@@ -79,12 +79,18 @@ def split_params(k, widths, params):
 
 def unclamped_ok(k, widths, params):
     """NetPack::unclamped_ok of csrc/net_pack.h: every hidden pre-activation is provably below 40 in magnitude for mapped inputs
-    in [-3, 3], so the score kernels may run their clamp-free variant (and the one-launch form over all size classes)."""
-    _, _, _, Ws, Bs, _ = split_params(k, widths, np.asarray(params, dtype=np.float64))
+    in [-3, 3], AND the mapping sends the documented input domain (x_i in [0, 1], q_m in [-1/k, 1/k]) into [-3, 3], so that the
+    input clamp of the clamp-free variant changes no score on the domain.  Then the score kernels run that variant (and the
+    one-launch form over all size classes); otherwise the variant with the tansig clamps, which clamps no input."""
+    xoffset, gain, ymin, Ws, Bs, _ = split_params(k, widths, np.asarray(params, dtype=np.float64))
     worst = 0.0
     for l, (W, b) in enumerate(zip(Ws[:-1], Bs[:-1])):
         worst = max(worst, float((np.abs(b) + np.abs(W).sum(axis=1) * (INPUT_CLAMP if l == 0 else 1.0)).max()))
-    return worst < 40.0
+    lo = np.where(np.arange(xoffset.shape[0]) < k, 0.0, -1.0 / k)
+    hi = np.where(np.arange(xoffset.shape[0]) < k, 1.0, 1.0 / k)
+    with np.errstate(invalid="ignore", over="ignore"):
+        ends = np.abs(np.stack([(lo - xoffset) * gain + ymin, (hi - xoffset) * gain + ymin]))
+    return bool(worst < 40.0 and np.all(ends <= INPUT_CLAMP))
 
 
 def _tansig(n):

@@ -15,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "sdpcutsel_via_nn_amd", "csrc")
 
 OK, EINVAL = 0, -1      # include/sdpcut.h
-INPUT_CLAMP = 3.0       # the mapped inputs of the first layer lie in [-3, 3]; behind a tansig in [-1, 1]
+INPUT_CLAMP = 3.0       # the clamp-free kernel cuts the mapped inputs of the first layer to [-3, 3]; behind a tansig they lie in [-1, 1]
 WIDTHS = (1, 7, 16, 47, 48, 49, 50, 52, 63, 64)
 OFFS = ("inmap", "bias", "bias_q", "wout", "frag", "wtail", "wvalu")
 
@@ -89,6 +89,26 @@ def _bound(k, widths, params):
     _, _, _, _, Ws, Bs, _ = _split(k, widths, params)
     return max(float((np.abs(B) + np.abs(W).sum(axis=1) * (INPUT_CLAMP if l == 0 else 1.0)).max())
                for l, (W, B) in enumerate(zip(Ws[:-1], Bs[:-1])))
+
+
+def _domain_ok(k, widths, params):
+    """does the network's own mapping v -> (v - xoffset_i) gain_i + ymin send the input domain -- x_i in [0, 1] for the first k
+    inputs, q_m in [-1/k, 1/k] for the others -- into [-INPUT_CLAMP, INPUT_CLAMP]?  (Affine: the two endpoints decide.)  Only
+    then is the input clamp of the clamp-free kernel inactive on the domain."""
+    d_in, xoffset, gain, ymin, _, _, _ = _split(k, widths, params)
+    lo = np.array([0.0] * k + [-1.0 / k] * (d_in - k))
+    hi = np.array([1.0] * k + [1.0 / k] * (d_in - k))
+    ends = np.concatenate([(lo - xoffset) * gain + ymin, (hi - xoffset) * gain + ymin])
+    return bool(np.all(np.abs(ends) <= INPUT_CLAMP))
+
+
+def _domain_margin(k, widths, params):
+    """smallest distance of a mapped endpoint of the domain from +-INPUT_CLAMP (the rule is not this test's business at a tie)"""
+    d_in, xoffset, gain, ymin, _, _, _ = _split(k, widths, params)
+    lo = np.array([0.0] * k + [-1.0 / k] * (d_in - k))
+    hi = np.array([1.0] * k + [1.0 / k] * (d_in - k))
+    ends = np.concatenate([(lo - xoffset) * gain + ymin, (hi - xoffset) * gain + ymin])
+    return float(np.abs(np.abs(ends) - INPUT_CLAMP).min())
 
 
 def _expected(k, widths, params):
@@ -181,22 +201,53 @@ def test_shipped_networks_pack_bit_for_bit(lib):
         widths, params = networks.load_network(k)
         ok = _compare(lib, k, widths, params)
         b = _bound(k, widths, params)
+        assert _domain_ok(k, widths, params) and _domain_margin(k, widths, params) > 1.0, k      # gain ~ 2, ymin -1: [0, 1] -> [-1, 1]
         if not 39.0 <= b <= 41.0:      # (at the threshold the order of the sum decides: not this test's business)
             assert ok == (1 if b < 40.0 else 0), (k, b)
+        assert b < 39.0 and ok == 1, (k, b)      # the shipped networks stay on the clamp-free kernels
 
 
 def test_random_networks_pack_bit_for_bit(lib):
     rng = np.random.default_rng(20261016)
     targets = itertools.cycle((0.5, 12.0, 38.5, 41.5, 90.0, 700.0))
-    seen = set()
+    seen, seen_rule = set(), set()
     for k, n_layers, H in itertools.product((2, 3, 4, 5), (2, 3, 4, 5), WIDTHS):
         widths, params = _random_network(rng, k, n_layers, H, next(targets))
         b = _bound(k, widths, params)
         assert not 39.0 <= b <= 41.0, ("test set-up: a generated network lies at the threshold", k, n_layers, H, b)
+        assert _domain_margin(k, widths, params) > 1e-9, ("test set-up: a mapped endpoint lies at the clamp", k, n_layers, H)
+        dom = _domain_ok(k, widths, params)
         ok = _compare(lib, k, widths, params)
-        assert ok == (1 if b < 40.0 else 0), (k, n_layers, H, b)
+        assert ok == (1 if (b < 40.0 and dom) else 0), (k, n_layers, H, b, dom)
+        assert bool(ok) == networks.unclamped_ok(k, widths, params), (k, n_layers, H)      # the Python twin of the rule
         seen.add(ok)
-    assert seen == {0, 1}      # both sides of the threshold occur
+        seen_rule.add((b < 40.0, dom))
+    assert seen == {0, 1}      # both outcomes occur ...
+    # ... and both outcomes of EACH condition, in every combination (xoffset / gain are drawn from N(0, 1))
+    assert seen_rule == {(True, True), (True, False), (False, True), (False, False)}
+
+
+def test_domain_condition_alone_decides_a_bounded_network(lib):
+    """a shipped network (bounded, mapping near gain 2 / ymin -1) stays clamp-free; the same weights behind a mapping trained on a
+    narrower range -- the middle fifth of an input's interval, x in [0.4, 0.6]: mapminmax gives xoffset 0.4, gain 10 -- send x = 0, 1 to -5, +5 and lose the status, input
+    by input and endpoint by endpoint"""
+    for k in (2, 3, 4, 5):
+        widths, params = networks.load_network(k)
+        d_in = k * (k + 3) // 2
+        assert _compare(lib, k, widths, params) == 1
+        for i in (0, k - 1, k, d_in - 1):
+            lo, hi = (0.0, 1.0) if i < k else (-1.0 / k, 1.0 / k)
+            for gain, xoff in ((10.0 / (hi - lo), lo + 0.4 * (hi - lo)), (2.0 / (hi - lo), lo + 1.01 * (hi - lo)), (2.0 / (hi - lo), lo - 1.01 * (hi - lo))):
+                p = params.copy()
+                p[i], p[d_in + i] = xoff, gain
+                assert _bound(k, widths, p) == _bound(k, widths, params) and not _domain_ok(k, widths, p)
+                assert _compare(lib, k, widths, p) == 0, (k, i, gain, xoff)
+                assert not networks.unclamped_ok(k, widths, p)
+            p = params.copy()      # just inside: [lo, hi] -> [-3, 3] shrunk by 1 %
+            p[i], p[d_in + i] = lo, (2.0 * INPUT_CLAMP * 0.99) / (hi - lo)
+            p[2 * d_in] = -INPUT_CLAMP * 0.99
+            assert _domain_ok(k, widths, p), (k, i)      # (the other inputs keep their shipped mapping: [-1, 1] - 1.97)
+            assert _compare(lib, k, widths, p) == 1 and networks.unclamped_ok(k, widths, p), (k, i)
 
 
 def test_refusals_keep_their_texts(lib):
