@@ -587,6 +587,64 @@ int sdpcut_cut_rows_all(sdpcut_handle h, int64_t count, const int64_t *idx, int3
                         double *coef, double *rhs, int64_t *cols, int32_t *ks);
 
 /*
+ * Cut pool: age out slack cuts, separate parked ones again.  Without it every cut of every round stays in the LP for good.  The
+ * pool holds the rows a loop has added (eigen-cuts, triangle rows; any sparse row of at most SDPCUT_ROW_LD entries on the LP's
+ * columns [X packed | x]), each either IN THE LP (state 0) or PARKED (state 1), in ascending order of a serial number given at add
+ * time (strictly increasing, never reused).  One step at an LP point v ("Cut pool"; cutpool.py is the twin):
+ *   act  = sum over the row's entries, left to right, of value * v[column]   (multiply and add separate, no contraction)
+ *   norm = sqrt(sum of value^2), same order, computed once at add time
+ *   d    = sense * (act - rhs)   (sense +1: a.v >= rhs, -1: a.v <= rhs; d >= 0 means satisfied)
+ *   a row in the LP      age = (d > tight_tol * norm) ? age + 1 : 0; at age >= max_age it is parked with age 0 and reported in `leave`
+ *   a row parked before  violated iff -d > viol_tol * norm, key (-d) / norm.  The violated rows by (key descending, serial
+ *   the step             ascending): the first max_return return to the LP with age 0 and are reported in `enter` in that order,
+ *                        with their rows in CSR form and their keys.  Every other parked row gets age + 1 and is DROPPED at
+ *                        age >= drop_age: reported in `dropped` and removed (the rows behind it move up, order kept).
+ * A row parked by a step is not examined as parked in that step.  One host wait per step.
+ *
+ * sdpcut_pool_create: capacity = most rows the pool ever holds at once, 1 .. SDPCUT_POOL_MAX_ROWS; there is no eviction under
+ *   pressure.  Needs sdpcut_set_instance (columns are checked against nb_lifted + nb_vars); a later sdpcut_set_instance with
+ *   another nb_vars makes every pool call but create / destroy fail with SDPCUT_ESTATE.  An existing pool is replaced.  Device
+ *   memory: about 600 bytes per row of capacity (two sets of arrays: the compaction writes out of place).
+ * sdpcut_pool_destroy: frees it (sdpcut_destroy does too); no pool is fine.
+ * sdpcut_pool_add_csr: n_rows rows from host CSR arrays (row i = entries indptr[i] .. indptr[i + 1] - 1), state 0, age 0, serials
+ *   *first_serial .. *first_serial + n_rows - 1.  sense may be NULL (all +1).  Refused with SDPCUT_EINVAL, the pool unchanged: an
+ *   empty row, a row longer than SDPCUT_ROW_LD, a column outside [0, nb_lifted + nb_vars), a non-finite coefficient or right-hand
+ *   side, a sense other than +-1, a block that would exceed the capacity.
+ * sdpcut_pool_step: vars_values as in sdpcut_round_csr (NULL keeps the handle's current point; otherwise the call sets it, and a
+ *   round that follows may pass NULL).  All pointers of *out point into a pinned block of the pool: valid until the next pool call.
+ *   leave / dropped are in ascending serial order.  n_in_lp / n_parked count the rows after the step.
+ * sdpcut_pool_get: the whole state in row order, for tests and tools: *n_rows, *next_serial and the first min(max_rows, *n_rows)
+ *   entries of every array that is not NULL; cols / vals are [.][SDPCUT_ROW_LD], zero beyond a row's nnz.
+ */
+#define SDPCUT_POOL_MAX_ROWS 4194304
+typedef struct sdpcut_pool_params {
+    double tight_tol, viol_tol;
+    int32_t max_age, drop_age;
+    int64_t max_return;
+} sdpcut_pool_params_t;
+typedef struct sdpcut_pool_step {
+    int64_t n_in_lp, n_parked;      /* after the step */
+    int64_t n_violated;             /* violated parked rows before the cap max_return */
+    int64_t n_dropped, n_leave, n_enter, enter_nnz;
+    const int64_t *leave;           /* n_leave serials */
+    const int64_t *enter;           /* n_enter serials, rank order */
+    const int64_t *dropped;         /* n_dropped serials */
+    const int32_t *enter_indptr;    /* n_enter + 1 */
+    const int32_t *enter_indices;   /* enter_nnz */
+    const double *enter_values;     /* enter_nnz */
+    const double *enter_rhs;        /* n_enter */
+    const int32_t *enter_sense;     /* n_enter */
+    const double *enter_key;        /* n_enter */
+} sdpcut_pool_step_t;
+int sdpcut_pool_create(sdpcut_handle h, int64_t capacity);
+int sdpcut_pool_destroy(sdpcut_handle h);
+int sdpcut_pool_add_csr(sdpcut_handle h, int64_t n_rows, const int32_t *indptr, const int32_t *indices, const double *values,
+                        const double *rhs, const int32_t *sense, int64_t *first_serial);
+int sdpcut_pool_step(sdpcut_handle h, const double *vars_values, const sdpcut_pool_params_t *params, sdpcut_pool_step_t *out);
+int sdpcut_pool_get(sdpcut_handle h, int64_t max_rows, int64_t *n_rows, int64_t *next_serial, int64_t *serial, int32_t *state,
+                    int32_t *age, int32_t *nnz, int32_t *sense, double *rhs, double *norm, int32_t *cols, double *vals);
+
+/*
  * Dense eigen-cuts: strategy 0 of cut_select_algo, the paper's baseline (replaces __gen_dense_eigcuts, cut_select_qp.py:757-786:
  * numpy.linalg.eigh of the whole lifted matrix [[1, x^T],[x, X]] of order dim = nb_vars + 1 and the per-entry Python comprehension
  * that builds one fully dense cut for every negative eigenvalue but the largest).  Both calls need sdpcut_set_instance and a point

@@ -32,6 +32,7 @@ STAT_POINTS_REDONE = 13   # points of batched rounds served by the single-point 
 BATCH_MAX_POINTS = 256   # SDPCUT_BATCH_MAX_POINTS: most LP points of one score_points / round_csr_points call
 DIVERSE_MAX_POOL = 16384   # SDPCUT_DIVERSE_MAX_POOL: longest pool of round_csr_diverse / list of filter_parallel
 MULTI_MAX_PER_SET = 5      # SDPCUT_MULTI_MAX_PER_SET: most eigen-cuts one index set offers (round_csr_multi / cut_rows_all)
+POOL_MAX_ROWS = 4194304    # SDPCUT_POOL_MAX_ROWS: largest capacity of a cut pool (pool_create)
 ROW_LD = 20
 
 _c = ctypes
@@ -63,6 +64,20 @@ class RoundMulti(_c.Structure):
 class DiverseInfo(_c.Structure):
     """sdpcut_diverse_info_t of include/sdpcut.h"""
     _fields_ = [("pool", _c.c_int64), ("examined", _c.c_int64), ("skipped_nonviolated", _c.c_int64), ("rejected_parallel", _c.c_int64)]
+
+
+class PoolParams(_c.Structure):
+    """sdpcut_pool_params_t of include/sdpcut.h"""
+    _fields_ = [("tight_tol", _c.c_double), ("viol_tol", _c.c_double), ("max_age", _c.c_int32), ("drop_age", _c.c_int32),
+                ("max_return", _c.c_int64)]
+
+
+class PoolStep(_c.Structure):
+    """sdpcut_pool_step_t of include/sdpcut.h"""
+    _fields_ = [("n_in_lp", _c.c_int64), ("n_parked", _c.c_int64), ("n_violated", _c.c_int64), ("n_dropped", _c.c_int64),
+                ("n_leave", _c.c_int64), ("n_enter", _c.c_int64), ("enter_nnz", _c.c_int64), ("leave", _vp), ("enter", _vp),
+                ("dropped", _vp), ("enter_indptr", _vp), ("enter_indices", _vp), ("enter_values", _vp), ("enter_rhs", _vp),
+                ("enter_sense", _vp), ("enter_key", _vp)]
 
 
 class DenseRound(_c.Structure):
@@ -116,6 +131,11 @@ SIGNATURES = {
     "sdpcut_filter_parallel": [_vp, _c.c_int64, _i64p, _c.c_int64, _c.c_double, _c.POINTER(_c.c_uint8), _c.POINTER(DiverseInfo)],
     "sdpcut_round_csr_multi": [_vp, _dp, _c.c_int, _c.c_int64, _c.c_int32, _c.c_int64, _c.POINTER(RoundMulti)],
     "sdpcut_cut_rows_all": [_vp, _c.c_int64, _i64p, _c.c_int32, _i64p, _dp, _dp, _dp, _i64p, _i32p],
+    "sdpcut_pool_create": [_vp, _c.c_int64],
+    "sdpcut_pool_destroy": [_vp],
+    "sdpcut_pool_add_csr": [_vp, _c.c_int64, _i32p, _i32p, _dp, _dp, _i32p, _i64p],
+    "sdpcut_pool_step": [_vp, _dp, _c.POINTER(PoolParams), _c.POINTER(PoolStep)],
+    "sdpcut_pool_get": [_vp, _c.c_int64, _i64p, _i64p, _i64p, _i32p, _i32p, _i32p, _i32p, _dp, _dp, _i32p, _dp],
     "sdpcut_dense_round": [_vp, _dp, _c.POINTER(DenseRound)],
     "sdpcut_dense_eig": [_vp, _dp, _dp],
     "sdpcut_shard_head_device": [_vp, _c.c_int, _c.c_int64, _vp],
@@ -237,6 +257,51 @@ def check_multi_args(cuts_per_set, row_quota, sel_size=None, strat=None):
     if q < 1:
         raise ValueError("row_quota must be >= 1")
     return m, q
+
+
+def check_pool_params(tight_tol, viol_tol, max_age, drop_age, max_return):
+    """The refusals of a cut-pool step that need no device (the library repeats them)
+    -> (tight_tol, viol_tol, max_age, drop_age, max_return)."""
+    tt, vt = float(tight_tol), float(viol_tol)
+    if not (0.0 <= tt < float("inf") and 0.0 <= vt < float("inf")):      # (NaN fails the comparisons)
+        raise ValueError("tight_tol and viol_tol must be finite and >= 0")
+    ma, da, mr = int(max_age), int(drop_age), int(max_return)
+    if ma != max_age or da != drop_age or ma < 1 or da < 1:
+        raise ValueError("max_age and drop_age must be integers >= 1")
+    if mr != max_return or mr < 0:
+        raise ValueError("max_return must be an integer >= 0")
+    return tt, vt, ma, da, mr
+
+
+def check_pool_rows(indptr, indices, values, rhs, sense, ncols, room):
+    """A block of rows for a cut pool, checked as sdpcut_pool_add_csr checks it (ValueError, nothing changed)
+    -> (indptr int32, indices int32, values f64, rhs f64, sense int32), contiguous."""
+    indptr = np.ascontiguousarray(indptr, dtype=np.int32)
+    indices = np.ascontiguousarray(indices, dtype=np.int32)
+    values, rhs = _f64(values), _f64(rhs)
+    m = rhs.shape[0]
+    if indptr.ndim != 1 or indptr.shape[0] != m + 1 or rhs.ndim != 1 or indices.ndim != 1 or values.shape != indices.shape:
+        raise ValueError("rows must be CSR arrays: indptr [m + 1], indices / values [nnz], rhs [m]")
+    sense = np.ones(m, dtype=np.int32) if sense is None else np.ascontiguousarray(sense, dtype=np.int32)
+    if sense.shape != (m,) or not np.all(np.abs(sense) == 1):
+        raise ValueError("sense must be +1 (G) or -1 (L) per row")
+    if m == 0:
+        return indptr, indices, values, rhs, sense
+    if m > room:
+        raise ValueError("the block would exceed the pool's capacity")
+    if indptr[0] < 0 or indptr[-1] > indices.shape[0]:
+        raise ValueError("indptr does not fit indices")
+    lens = np.diff(indptr)
+    if lens.min() < 1:
+        raise ValueError("a pool row must have at least one entry")
+    if lens.max() > ROW_LD:
+        raise ValueError("a pool row must have at most %d entries" % ROW_LD)
+    used = slice(int(indptr[0]), int(indptr[-1]))
+    if indices[used].min() < 0 or indices[used].max() >= ncols:
+        raise ValueError("a column index lies outside the LP's columns")
+    if not (np.all(np.isfinite(values[used])) and np.all(np.isfinite(rhs))):
+        raise ValueError("a coefficient or right-hand side is not finite")
+    return indptr, indices, values, rhs, sense
 
 
 def _adj_u8(adjacency, n=None):
@@ -791,6 +856,90 @@ class Scorer(object):
                                                   _ptr(rhs, _dp), _ptr(cols, _i64p), _ptr(ks, _i32p)))
         n = int(row_ptr[c])
         return row_ptr, lam[:n], coef[:n], rhs[:n], cols[:c], ks[:c]
+
+    # ------------------------------------------------------------------ cut pool
+    pool_capacity = 0
+
+    def _pool_open(self):
+        if getattr(self, "_h", None) is None:
+            raise SdpCutError("the Scorer is closed")
+        if not self.pool_capacity:
+            raise SdpCutError("pool_create first")
+
+    def pool_create(self, capacity):
+        """A cut pool of at most ``capacity`` rows on this handle (sdpcut_pool_create; DESIGN.md section 5 "Cut pool"); needs
+        set_instance.  Replaces an existing pool."""
+        capacity = int(capacity)
+        if not 1 <= capacity <= POOL_MAX_ROWS:
+            raise ValueError("capacity must lie in 1 .. %d" % POOL_MAX_ROWS)
+        if getattr(self, "_h", None) is None:
+            raise SdpCutError("the Scorer is closed")
+        self._check(self._lib.sdpcut_pool_create(self._h, capacity))
+        self.pool_capacity, self._pool_rows = capacity, 0
+
+    def pool_destroy(self):
+        if getattr(self, "_h", None) is not None:
+            self._check(self._lib.sdpcut_pool_destroy(self._h))
+        self.pool_capacity, self._pool_rows = 0, 0
+
+    def pool_add(self, indptr, indices, values, rhs, sense=None):
+        """Rows (host CSR arrays; sense +1 "G" / -1 "L" per row, None = all "G") enter the pool in the LP with age 0
+        (sdpcut_pool_add_csr) -> the serial of the first one; the others follow it.  A refused block (ValueError) leaves the pool
+        unchanged."""
+        self._pool_open()
+        n = self.nb_vars
+        indptr, indices, values, rhs, sense = check_pool_rows(indptr, indices, values, rhs, sense, n * (n + 1) // 2 + n,
+                                                              self.pool_capacity - self._pool_rows)
+        first = _c.c_int64(0)
+        self._check(self._lib.sdpcut_pool_add_csr(self._h, rhs.shape[0], _ptr(indptr, _i32p), _ptr(indices, _i32p), _ptr(values, _dp),
+                                                  _ptr(rhs, _dp), _ptr(sense, _i32p), ctypes.byref(first)))
+        self._pool_rows += rhs.shape[0]
+        return int(first.value)
+
+    def pool_step(self, point=None, tight_tol=1e-9, viol_tol=1e-6, max_age=3, drop_age=10, max_return=0, copy=True):
+        """One step of the pool at an LP point (sdpcut_pool_step; point=None keeps the current one): the LP rows age and the slack
+        ones are parked, the violated parked rows return most violated first, the others age and drop.
+        -> dict(leave, enter, dropped: serials; enter_indptr, enter_indices, enter_values, enter_rhs, enter_sense, enter_key: the
+        returning rows in rank order; n_in_lp, n_parked (after the step), n_violated (before the cap max_return), n_dropped).
+        copy=False returns views of the pool's pinned block, valid until the next pool call."""
+        self._pool_open()
+        tt, vt, ma, da, mr = check_pool_params(tight_tol, viol_tol, max_age, drop_age, max_return)
+        vv = self._csr_point(point)
+        par, out = PoolParams(tt, vt, ma, da, mr), PoolStep()
+        self._check(self._lib.sdpcut_pool_step(self._h, _ptr(vv, _dp), ctypes.byref(par), ctypes.byref(out)))
+
+        def view(ptr, dtype, count):
+            if not ptr or count == 0:
+                return np.zeros(0, dtype=dtype)
+            a = np.frombuffer((_c.c_char * (count * np.dtype(dtype).itemsize)).from_address(ptr), dtype=dtype, count=count)
+            return a.copy() if copy else a
+        w, nnz = int(out.n_enter), int(out.enter_nnz)
+        self._pool_rows -= int(out.n_dropped)
+        return dict(leave=view(out.leave, np.int64, int(out.n_leave)), enter=view(out.enter, np.int64, w),
+                    dropped=view(out.dropped, np.int64, int(out.n_dropped)),
+                    enter_indptr=view(out.enter_indptr, np.int32, w + 1) if w else np.zeros(1, np.int32),
+                    enter_indices=view(out.enter_indices, np.int32, nnz), enter_values=view(out.enter_values, np.float64, nnz),
+                    enter_rhs=view(out.enter_rhs, np.float64, w), enter_sense=view(out.enter_sense, np.int32, w),
+                    enter_key=view(out.enter_key, np.float64, w), n_in_lp=int(out.n_in_lp), n_parked=int(out.n_parked),
+                    n_violated=int(out.n_violated), n_dropped=int(out.n_dropped))
+
+    def pool_state(self):
+        """The whole pool in row order (sdpcut_pool_get), for tests and tools -> dict(n, next_serial, serial, state, age, nnz,
+        sense, rhs, norm, cols [n, 20], vals [n, 20])."""
+        self._pool_open()
+        n, nxt = _c.c_int64(0), _c.c_int64(0)
+        self._check(self._lib.sdpcut_pool_get(self._h, 0, ctypes.byref(n), ctypes.byref(nxt), *([None] * 11)))
+        m = int(n.value)
+        a = dict(serial=np.zeros(m, np.int64), state=np.zeros(m, np.int32), age=np.zeros(m, np.int32), nnz=np.zeros(m, np.int32),
+                 sense=np.zeros(m, np.int32), rhs=np.zeros(m), norm=np.zeros(m), cols=np.zeros((m, ROW_LD), np.int32),
+                 vals=np.zeros((m, ROW_LD)))
+        if m:
+            self._check(self._lib.sdpcut_pool_get(self._h, m, ctypes.byref(n), ctypes.byref(nxt), _ptr(a["serial"], _i64p),
+                                                  _ptr(a["state"], _i32p), _ptr(a["age"], _i32p), _ptr(a["nnz"], _i32p),
+                                                  _ptr(a["sense"], _i32p), _ptr(a["rhs"], _dp), _ptr(a["norm"], _dp),
+                                                  _ptr(a["cols"], _i32p), _ptr(a["vals"], _dp)))
+        a.update(n=m, next_serial=int(nxt.value))
+        return a
 
     # ------------------------------------------------------------------ many LP points per call
     def _points_arg(self, points):

@@ -104,6 +104,7 @@ int sdpcut_destroy(sdpcut_handle h)
     free_points_ws(h);
     free_diverse_ws(h);
     free_multi_ws(h);
+    free_pool_ws(h);
     (void)hipFree(h->d_sdp_unconverged);
     (void)hipFree(h->d_tri); (void)hipFree(h->d_tri_dense3);
     if (h->pinned) (void)hipHostFree(h->pinned);

@@ -203,6 +203,7 @@ struct sdpcut_ctx {
     void *d_dense = nullptr;       // dense eigen-cuts (dense.hip): V^T, sorted vectors, eigenvalues, n_rows; allocated by the first call
     void *diverse = nullptr;       // diverse selection (diverse.hip: DiverseWs): pool rows, pair bits, accepted head; allocated by the first call
     void *multi = nullptr;         // multi-cut rounds (multirows.hip: MultiWs): head, look-back words, host arrays; allocated by the first call
+    void *pool = nullptr;          // cut pool (pool.hip: PoolWs): the rows of a loop, in the LP or parked; sdpcut_pool_create
     // sdpcut_shard_finish_enqueue -> sdpcut_shard_finish_wait
     int64_t shard_pending_serial = 0, shard_pending_sel = 0;
     int32_t shard_pending_world = 0, shard_pending_ld = 0;
@@ -351,6 +352,8 @@ void free_train_ws(sdpcut_ctx *h);
 void free_diverse_ws(sdpcut_ctx *h);
 // multirows.hip
 void free_multi_ws(sdpcut_ctx *h);
+// pool.hip
+void free_pool_ws(sdpcut_ctx *h);
 
 // exact_sdp.hip (SDPCUT_SDP, SDPCUT_OPT_EXACT_SDP)
 int launch_exact_sdp(sdpcut_ctx *h);                 // d_sdp / d_sdp_gap of every candidate at the current point

@@ -346,8 +346,17 @@ class _Binding(object):
         self.wasted = 0          # speculative rounds nobody asked for
         self.prioritised = False # its scorer's stream has been given the device's highest priority (a short list beside a long one)
 
+    point_fresh = False          # the cut pool's step has just uploaded the point a round is about to pass (point_arg)
+
+    def point_arg(self, vv):
+        """the point argument of a round call: None (keep the device's point) right after a pool step at this very point"""
+        fresh, self.point_fresh = self.point_fresh, False
+        if fresh and self.point_copy is not None and self.point_copy.shape == vv.shape and np.array_equal(vv, self.point_copy):
+            return None
+        return vv
+
     def begin(self, strat, head, vv, flags):
-        token = self.scorer.round_csr_begin(strat, head, point=vv)
+        token = self.scorer.round_csr_begin(strat, head, point=self.point_arg(vv))
         self.note_point(vv, flags)
         self._pending = (token, strat, head, self.point_copy)
 
@@ -1116,7 +1125,8 @@ class CutSolver(GpuCutSelectionMixin):
 
     def cut_select_algo(self, filename, dim, sel_size, strat=2, nb_rounds_cuts=20, term_on=False,
                         triangle_on=False, strong_only=False, max_subs=_THRES_MAX_SUBS, on_round=None, plots=False, sol=0,
-                        ch_ext=0, max_parallel=None, pool_factor=4, cuts_per_set=1, row_quota=None):
+                        ch_ext=0, max_parallel=None, pool_factor=4, cuts_per_set=1, row_quota=None,
+                        pool_max_age=None, pool_drop_age=10, pool_return=None, pool_tight_tol=1e-9, pool_viol_tol=1e-6):
         """Cutting-plane rounds on a BoxQP ``.in`` file, same arguments and default return tuple as
         the reference's entry point (cut_select_qp.py:73-221), with HiGHS as LP solver, the native
         cover enumeration and the GPU selection / generation / triangle separation in between.
@@ -1143,6 +1153,14 @@ class CutSolver(GpuCutSelectionMixin):
         -- at most ``quota`` rows, so fewer sets are used -- and ``row_quota="sets"`` lets every one of the ``quota`` sets keep all
         it offers (up to ``cuts_per_set * quota`` rows).  ``self.multi_log`` records every round: entries used, rows, the
         histogram of violated eigenvalues per entry, whether the quota dropped a row.
+        ``pool_max_age`` (None = no pool, today's loop untouched; not with strategy 0): a cut pool on the device
+        (``Scorer.pool_*``, DESIGN.md section 5 "Cut pool").  Every round begins with one pool step at the LP point: a cut that
+        has been slack by more than ``pool_tight_tol * ||row||`` at ``pool_max_age`` consecutive LP optima leaves the LP and is
+        parked; parked cuts violated by more than ``pool_viol_tol * ||row||`` return, most violated first, at most
+        ``pool_return`` of them (None = the round's quota; they do not count against it); a cut parked for ``pool_drop_age``
+        rounds is dropped.  Then the usual separation runs and its rows -- eigen-cuts and triangle rows, never the McCormick
+        rows -- go into both the LP and the pool.  ``self.pool_log`` has one record per round: leave, enter, dropped, in_lp, parked
+        (after the step), violated, lp_rows (rows of the LP that was just solved), added (rows the separation added).
         -> (bound per solve, total s, round s, separation s, PSD cuts per round, triangle cuts per
         round, number of candidates)."""
         from timeit import default_timer as clock
@@ -1168,6 +1186,13 @@ class CutSolver(GpuCutSelectionMixin):
                 raise AssertionError("cuts_per_set > 1 serves the selecting strategies 1, 2, 3, 4 and 5 (strategy 0 emits every dense cut already)")
             assert row_quota in (None, "sets"), 'row_quota is None (the round\'s quota in rows) or "sets" (cuts_per_set times the quota)'
             self.multi_log = []
+        pooled = pool_max_age is not None
+        if pooled:
+            if strat == 0:
+                raise AssertionError("the cut pool holds sparse rows of at most 20 entries: strategy 0 (dense cuts) is not pooled")
+            pool_par = _capi.check_pool_params(pool_tight_tol, pool_viol_tol, pool_max_age, pool_drop_age,
+                                               0 if pool_return is None else pool_return)
+            assert nb_rounds_cuts >= 0
         t_start = clock()
         inst = harness.parse_boxqp(filename)
         self._dim = dim
@@ -1206,7 +1231,7 @@ class CutSolver(GpuCutSelectionMixin):
                 b.drain()
                 vv = np.ascontiguousarray(point, dtype=np.float64)
                 pool = int(min(max(int(pool_factor * quota), quota), _capi.DIVERSE_MAX_POOL))
-                r = b.scorer.round_csr_diverse(vv, cur, quota, max_parallel, pool_size=pool)
+                r = b.scorer.round_csr_diverse(b.point_arg(vv), cur, quota, max_parallel, pool_size=pool)
                 b.note_point(vv, {1: _capi.EIG, 2: _capi.NN, 4: _capi.EIG | _capi.NN}[cur])
                 b.rank_serial += 1
                 self._gpu_last = None
@@ -1233,7 +1258,7 @@ class CutSolver(GpuCutSelectionMixin):
             b = self._gpu_bind()
             b.drain()
             vv = np.ascontiguousarray(point, dtype=np.float64)
-            r = b.scorer.round_csr_multi(vv, cur, quota, m_cuts, row_quota=row_quota)
+            r = b.scorer.round_csr_multi(b.point_arg(vv), cur, quota, m_cuts, row_quota=row_quota)
             b.note_point(vv, {1: _capi.EIG, 2: _capi.NN, 3: _capi.SDP, 4: _capi.EIG | _capi.NN}[cur])
             b.rank_serial += 1
             self._gpu_last = None
@@ -1271,6 +1296,31 @@ class CutSolver(GpuCutSelectionMixin):
             return {"sdp": sdp, "tri": tri}
 
         sep_fn = separate_multi if m_cuts > 1 else (separate if max_parallel is None else separate_diverse)
+        if pooled:
+            from . import cutpool
+            # capacity = the most rows the run can add: there is no eviction under pressure
+            per_round = quota * (m_cuts if row_quota == "sets" else 1) + (self._TRI_CUTS_PER_ROUND_MAX if triangle_on else 0)
+            capacity = max(1, nb_rounds_cuts * per_round)
+            if capacity > _capi.POOL_MAX_ROWS:
+                raise ValueError("the run can add %d rows, a cut pool holds at most %d" % (capacity, _capi.POOL_MAX_ROWS))
+            sc.pool_create(capacity)
+            ploop = cutpool.PoolLoop(lp, sc, pool_par[2], pool_par[3], pool_par[0], pool_par[1])
+            self.pool_log, self.pool_loop = ploop.log, ploop
+            inner_fn = sep_fn
+
+            def sep_fn(round_no, point):
+                """the pool's step first (its upload of the point serves the round), then the round; its rows join the pool"""
+                vv = np.ascontiguousarray(point, dtype=np.float64)
+                b = self._gpu_bind() if state["strat"] != 5 else None
+                if b is not None:
+                    b.drain()
+                ploop.step(vv, quota if pool_return is None else pool_par[4])
+                if b is not None and b.scorer is sc:
+                    b.note_point(vv, 0)
+                    b.point_fresh = True
+                counts = inner_fn(round_no, point)
+                ploop.adopt()
+                return dict(counts, pool_enter=ploop.log[-1]["enter"], pool_leave=ploop.log[-1]["leave"])
         keep_attr = (self.cuts_per_set, self.cuts_row_quota)
         if m_cuts > 1:
             self.cuts_per_set, self.cuts_row_quota = m_cuts, row_quota

@@ -92,6 +92,29 @@ class _RowStore(object):
     def get_num(self):
         return self._n
 
+    def delete_rows(self, positions):
+        """Remove the rows at the given current positions (any order, each once); the rows behind them shift down.  The store
+        is rewritten as one CSR block of the rows that stay -- once per round in a loop with a cut pool."""
+        pos = np.unique(np.asarray(positions, dtype=np.int64))
+        if pos.size != np.size(positions):
+            raise ValueError("delete_rows: a position is named twice")
+        if pos.size == 0:
+            return
+        if pos[0] < 0 or pos[-1] >= self._n:
+            raise IndexError("delete_rows: position outside 0 .. %d" % (self._n - 1))
+        data, cols, lens = self.csr_parts(0)
+        rhs, senses = self.rhs_from(0), self.senses_from(0)
+        keep = np.ones(self._n, dtype=bool)
+        keep[pos] = False
+        ptr = np.concatenate([[0], np.cumsum(lens)])
+        entry_keep = np.repeat(keep, lens)
+        new_ptr = np.concatenate([[0], np.cumsum(lens[keep])]).astype(np.int64)
+        self._blocks = [("csr", new_ptr, cols[entry_keep], data[entry_keep])]
+        self._rhs = [rhs[keep]]
+        self._senses = [senses[keep].tolist()]
+        self._n = int(keep.sum())
+        assert ptr[-1] == data.shape[0]
+
     @property
     def rows(self):
         out = []
@@ -210,6 +233,19 @@ class LinearRelaxation(object):
             raise RuntimeError("HiGHS: " + res.message)
         self._values, self._objval = res.x, res.fun
         return res
+
+    def delete_rows(self, positions):
+        """Remove rows by their current position (0 = the first row ever added and still there); the rows behind them shift down.
+        With the incremental model the rows HiGHS already holds are deleted there (``deleteRows``) and its basis lives on;
+        without it the next solve builds the smaller model from scratch.  Deleting rows that are inactive at the last optimum
+        leaves that optimum's value unchanged."""
+        pos = np.unique(np.asarray(positions, dtype=np.int64))
+        self.linear_constraints.delete_rows(positions)
+        if self._core is not None and self._model is not None:
+            passed = pos[pos < self._rows_passed]
+            if passed.size:
+                self._model.deleteRows(int(passed.size), passed.astype(np.int32))
+                self._rows_passed -= int(passed.size)
 
     def get_values(self):
         return self._values
