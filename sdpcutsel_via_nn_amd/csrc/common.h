@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -195,14 +196,14 @@ struct sdpcut_ctx {
     size_t point_stage_bytes = 0;
     bool point_inflight = false;   // a transfer out of point_stage may still be running
     int64_t round_serial = 0;      // completion word of the fused round (round_rows_kernel -> pinned header)
-    uint32_t *d_done_ticket = nullptr;
+    uint32_t *d_done_ticket = nullptr;   // completion ticket, then the look-back words of the row assemblies (ensure_round_sync)
     PendingRound pend;
     TrainData train[SDPCUT_MAX_K + 1];   // sdpcut_train_set_data; independent of instance, candidates, point and networks
     double *d_train_ws = nullptr;  // parameters | per-workgroup partial sums | reduced loss and gradient (train.hip)
     size_t train_ws_doubles = 0;
     void *d_dense = nullptr;       // dense eigen-cuts (dense.hip): V^T, sorted vectors, eigenvalues, n_rows; allocated by the first call
     void *diverse = nullptr;       // diverse selection (diverse.hip: DiverseWs): pool rows, pair bits, accepted head; allocated by the first call
-    void *multi = nullptr;         // multi-cut rounds (multirows.hip: MultiWs): head, look-back words, host arrays; allocated by the first call
+    void *multi = nullptr;         // multi-cut rounds (multirows.hip: MultiWs): head, host arrays; allocated by the first call
     void *pool = nullptr;          // cut pool (pool.hip: PoolWs): the rows of a loop, in the LP or parked; sdpcut_pool_create
     // sdpcut_shard_finish_enqueue -> sdpcut_shard_finish_wait
     int64_t shard_pending_serial = 0, shard_pending_sel = 0;
@@ -288,6 +289,12 @@ int launch_point_copy(sdpcut_ctx *h, const double *src_mapped, int64_t n);
 // rows.hip: the round's epilogue in CSR form (sdpcut_round_csr; block layout: round_layout.h, csr_layout)
 int launch_round_csr(sdpcut_ctx *h, int64_t cap, const int64_t *d_c4, int64_t limit, const int64_t *d_idx, const double *d_score,
                      int ld, void *block, int64_t serial);
+// rows.hip: h->d_done_ticket = the completion ticket of an epilogue launch (rows_dev.h: publish_round_done) followed by one
+// look-back word per workgroup of the largest assembly grid, the multi-cut round's 512 workgroups (rows_dev.h: csr_lookback)
+#define ROUND_TICKET_BYTES 64
+#define ROUND_AGG_WORDS 512
+int ensure_round_sync(sdpcut_ctx *h);
+static inline uint64_t *round_agg_words(sdpcut_ctx *h) { return (uint64_t *)((char *)h->d_done_ticket + ROUND_TICKET_BYTES); }
 // eig.hip: lambda_min of every candidate, one launch over all size classes; tk = TopkWs of a feasibility selection or NULL
 int launch_eig_only(sdpcut_ctx *h, void *tk, hipEvent_t ev_start, hipEvent_t ev_stop, int64_t pf_k = 0);
 // the point-axis forms of the scoring and of the CSR assembly (a batch of LP points, points.hip): eig.hip, score.hip, rows.hip
@@ -300,6 +307,9 @@ int launch_round_csr_points(sdpcut_ctx *h, int p_first, int n_points, int64_t ca
                             int64_t eig_stride, uint64_t *d_agg, int64_t agg_stride, void *block, int64_t block_stride, int64_t serial);
 void free_points_ws(sdpcut_ctx *h);              // points.hip
 int wait_round_done(sdpcut_ctx *h, const int64_t *word, int64_t serial);   // round.hip
+// round.hip: a CSR assembly into the handle's pinned block, launched here and waited for, once more if its look-back gave up
+int csr_assemble_wait(sdpcut_ctx *h, int last_word, int launches, bool count_failure, const char *what,
+                      const std::function<int(int64_t serial)> &launch);
 int score_for_selection(sdpcut_ctx *h, int strat, int64_t sel_size, int64_t cap, uint32_t need, bool allow_auto, int *stage,
                         bool *auto_out);                                   // round.hip
 // batch_kernels.hip

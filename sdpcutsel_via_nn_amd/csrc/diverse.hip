@@ -411,19 +411,11 @@ int sdpcut_round_csr_diverse(sdpcut_handle h, const double *vars_values, int str
     const int32_t ld = h->row_len_max;
     rc = ensure_pinned(h, csr_layout(cap, ld).bytes);
     if (rc) return rc;
-    int64_t *hdr = (int64_t *)h->pinned;
-    for (int attempt = 0;; ++attempt) {
-        hdr[8] = hdr[9] = hdr[10] = 0;
-        const int64_t serial = ++h->round_serial;
-        rc = launch_round_csr(h, cap, w->info, cap, w->acc_ids, w->acc_score, ld, h->pinned_dev, serial);
-        if (rc) return rc;
-        rc = wait_round_done(h, hdr + 7, serial);
-        if (rc) return rc;
-        if (!hdr[10]) break;
-        // the assembly's bounded look-back gave up (a device shared with a long kernel): once more, as the plain round does
-        ++h->stat_fallbacks;
-        if (attempt == 1) return sdpcut_fail(h, SDPCUT_EHIP, "round_csr_diverse: look-back of the row assembly timed out twice");
-    }
+    const int64_t *hdr = (const int64_t *)h->pinned;
+    rc = csr_assemble_wait(h, 10, 2, true, "round_csr_diverse", [&](int64_t serial) {
+        return launch_round_csr(h, cap, w->info, cap, w->acc_ids, w->acc_score, ld, h->pinned_dev, serial);
+    });
+    if (rc) return rc;
     ++h->stat_rounds;
     if (info) { info->examined = hdr[0]; info->skipped_nonviolated = hdr[1]; info->rejected_parallel = hdr[2]; }
     out->cap = cap;

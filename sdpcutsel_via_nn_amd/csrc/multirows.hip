@@ -2,26 +2,18 @@
 // section 5 "All violated eigen-cuts", multicut.py its numpy twin).  A plain round emits one row per head entry (rows.hip); here an
 // entry emits one row per violated eigenvalue, up to max_per_set of them, all from ONE Jacobi decomposition with vectors, and a row
 // quota ends the walk -- inside an entry if it falls there.
-//   multi_csr_kernel       the CSR assembly of a ranked head; the scheme of round_csr_body (rows.hip): head order, (rows, non-zeros)
-//                          aggregates published under the round serial, look-back over lower-indexed workgroups only, a give-up
-//                          word that makes the host launch the assembly once more
+//   multi_csr_kernel       the CSR assembly of a ranked head, in head order like round_csr_body (rows.hip), several rows per entry
 //   cut_rows_all_kernel    padded rows of an explicit id list, one lane per entry: no quota, no look-back
-// The plain round's kernels and launchers are not touched: the head comes from sdpcut_rank_device, as the diverse round's does.
+// The gather, the row of an eigenvector, the look-back across workgroups and the completion word are rows_dev.h's, shared with
+// the plain round's kernels; so are the handle's ticket and look-back words (rows.hip: ensure_round_sync) and the host's
+// launch-wait-retry rule (round.hip: csr_assemble_wait).  The head comes from sdpcut_rank_device, as the diverse round's does.
 #include <cstring>
 #include <new>
 #include <vector>
 
 #include "common.h"
-#include "gather.h"
+#include "rows_dev.h"
 #include "topk_route.h"
-
-// LDS traffic private to one wave needs no workgroup barrier (see rows.hip)
-__device__ __forceinline__ void multi_wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 #define MULTI_DMAX (SDPCUT_MAX_K + 1)
 
@@ -42,26 +34,7 @@ __device__ __forceinline__ void multi_decompose(const int32_t *s5, const double 
     constexpr int M = K * (K + 1) / 2;
     constexpr int D = K + 1;
     double x[K], X[M];
-    int32_t s[K];
-#pragma unroll
-    for (int a = 0; a < K; ++a) {
-        s[a] = s5[a];
-        x[a] = vars[L + s[a]];
-        cl[a] = L + s[a];
-    }
-    {
-        int m = 0;
-#pragma unroll
-        for (int a = 0; a < K; ++a) {
-            const int32_t rowbase = nv * s[a] - (s[a] * (s[a] + 1)) / 2;
-#pragma unroll
-            for (int b = a; b < K; ++b) {
-                X[m] = vars[rowbase + s[b]];
-                cl[K + m] = rowbase + s[b];
-                ++m;
-            }
-        }
-    }
+    gather_lifted<K>(s5, vars, nv, L, x, X, cl);
     double a[D][D], v[D][D];
     fill_lifted<K>(a, x, X);
     jacobi_eig<D, true>(a, v);
@@ -103,45 +76,15 @@ __device__ __forceinline__ double multi_pick(const MultiEig &E, int r, double (&
     return lam;
 }
 
-// the row of a vector, exactly as cut_row_one builds it (rows.hip; cut_select_qp.py:744-750)
-template <int K>
-__device__ __forceinline__ void multi_row(const double (&ev6)[MULTI_DMAX], double (&coef)[SDPCUT_ROW_LD], double &rhs)
-{
-    constexpr int D = K + 1;
-    double ev[D];
-#pragma unroll
-    for (int i = 0; i < D; ++i) ev[i] = (fabs(ev6[i]) <= -SDPCUT_NEG_EIGVAL) ? 0.0 : ev6[i];
-    {
-#pragma clang fp contract(off)
-        int m = 0;
-#pragma unroll
-        for (int i = 0; i < D; ++i)
-#pragma unroll
-            for (int j = (i > 1 ? i : 1); j < D; ++j) {
-                coef[m++] = (i != j) ? ev[i] * ev[j] * 2 : ev[i] * ev[j];
-            }
-        rhs = -ev[0] * ev[0];
-    }
-}
-
+// the two size-templated steps for a size known at run time
 __device__ __forceinline__ void multi_decompose_k(int k, const int32_t *sp, const double *vars, int32_t nv, int64_t L, MultiEig &E,
                                                   int64_t (&cl)[SDPCUT_ROW_LD])
 {
-    switch (k) {
-    case 2: multi_decompose<2>(sp, vars, nv, L, E, cl); break;
-    case 3: multi_decompose<3>(sp, vars, nv, L, E, cl); break;
-    case 4: multi_decompose<4>(sp, vars, nv, L, E, cl); break;
-    default: multi_decompose<5>(sp, vars, nv, L, E, cl); break;
-    }
+    CALL_FOR_SET_SIZE(k, multi_decompose, sp, vars, nv, L, E, cl);
 }
 __device__ __forceinline__ void multi_row_k(int k, const double (&ev)[MULTI_DMAX], double (&co)[SDPCUT_ROW_LD], double &rhs)
 {
-    switch (k) {
-    case 2: multi_row<2>(ev, co, rhs); break;
-    case 3: multi_row<3>(ev, co, rhs); break;
-    case 4: multi_row<4>(ev, co, rhs); break;
-    default: multi_row<5>(ev, co, rhs); break;
-    }
+    CALL_FOR_SET_SIZE(k, eigcut_row, ev, co, &rhs);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -151,10 +94,7 @@ __device__ __forceinline__ void multi_row_k(int k, const double (&ev)[MULTI_DMAX
 #define MULTI_TILE 32
 #define MULTI_MAX_HEAD 16384
 #define MULTI_MAX_BLOCKS (MULTI_MAX_HEAD / MULTI_TILE)
-#define MULTI_SPIN_LIMIT (1 << 22)
-// the aggregate word is serial (32) | rows (16) | non-zeros (16)
-static_assert(MULTI_TILE * SDPCUT_MULTI_MAX_PER_SET <= 0xffff, "rows of a workgroup must fit 16 bits");
-static_assert(MULTI_TILE * SDPCUT_MULTI_MAX_PER_SET * SDPCUT_ROW_LD <= 0xffff, "non-zeros of a workgroup must fit 16 bits");
+static_assert(MULTI_MAX_BLOCKS <= ROUND_AGG_WORDS, "a look-back word per workgroup");
 static_assert(MULTI_TILE <= 64 && SDPCUT_MULTI_MAX_PER_SET <= SDPCUT_MAX_K, "one lane per entry; an entry has at most k violated eigenvalues");
 static_assert(MULTI_TILE * SDPCUT_MULTI_MAX_PER_SET * SDPCUT_ROW_LD * 12 <= 64 * 1024, "staging must fit the LDS of a workgroup");
 
@@ -234,30 +174,8 @@ __global__ __launch_bounds__(64) void multi_csr_kernel(MultiCsrArgs R)
     const int my_row = incl_r - cnt, my_off = incl_z - cnt * len;
     const int wg_rows = __shfl(incl_r, 63), wg_nnz = __shfl(incl_z, 63);
     // publish this workgroup's aggregate (BEFORE the quota: a workgroup behind the quota must see it passed), then sum those in front
-    const uint32_t tag = (uint32_t)R.serial;
-    if (lane == 0)
-        __hip_atomic_store(&R.agg[blockIdx.x], ((uint64_t)tag << 32) | ((uint64_t)wg_rows << 16) | (uint64_t)wg_nnz, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-    int64_t pre_rows = 0, pre_nnz = 0;
-    int gave_up = 0;
-    for (int b = lane; b < (int)blockIdx.x && !gave_up; b += 64) {
-        uint64_t w = __hip_atomic_load(&R.agg[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        uint32_t it = 0;
-        while ((uint32_t)(w >> 32) != tag) {
-            __builtin_amdgcn_s_sleep(2);
-            if (++it > MULTI_SPIN_LIMIT) { gave_up = 1; break; }
-            w = __hip_atomic_load(&R.agg[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        if (!gave_up) {
-            pre_rows += (int64_t)((w >> 16) & 0xffffull);
-            pre_nnz += (int64_t)(w & 0xffffull);
-        }
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        pre_rows += __shfl_xor(pre_rows, off);
-        pre_nnz += __shfl_xor(pre_nnz, off);
-        gave_up |= __shfl_xor(gave_up, off);
-    }
+    int64_t pre_rows, pre_nnz;
+    const int gave_up = csr_lookback(R.agg, (uint32_t)R.serial, wg_rows, wg_nnz, pre_rows, pre_nnz);
     if (gave_up && lane == 0) R.o_hdr[10] = 1;      // the block is void; the host launches the assembly once more
     // The rows, now that their global numbers are known.  Row g of the round is kept iff g < row_cap; the row numbered row_cap
     // itself -- the first one dropped -- says where the block ends.  With a give-up the numbers are wrong but stay inside the
@@ -293,7 +211,7 @@ __global__ __launch_bounds__(64) void multi_csr_kernel(MultiCsrArgs R)
     // kept rows are a prefix of the workgroup's rows: their non-zeros are a prefix of its staging area
     int kept_nnz = kept * len;
     for (int off = 32; off > 0; off >>= 1) kept_nnz += __shfl_xor(kept_nnz, off);
-    multi_wave_lds_sync();
+    wave_lds_sync();
     for (int w = lane; w < kept_nnz; w += 64) {      // contiguous, coalesced stores over PCIe
         R.o_values[pre_nnz + w] = s_val[w];
         R.o_indices[pre_nnz + w] = s_ind[w];
@@ -303,16 +221,7 @@ __global__ __launch_bounds__(64) void multi_csr_kernel(MultiCsrArgs R)
         R.o_hdr[8] = pre_rows + wg_rows;
         R.o_hdr[9] = pre_nnz + wg_nnz;
     }
-    // completion word for the polling host, exactly as round_csr_kernel publishes it (rows.hip)
-    __threadfence_system();
-    if (lane == 0) {
-        const uint32_t t = __hip_atomic_fetch_add(R.done_ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        if (t == gridDim.x - 1) {
-            __hip_atomic_store(R.done_ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __threadfence_system();
-            __hip_atomic_store(R.o_hdr + 7, R.serial, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
+    publish_round_done(R.done_ticket, R.o_hdr + 7, R.serial);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -366,7 +275,6 @@ struct MultiWs {
     int64_t cap = 0;                 // head entries ids / score hold
     int64_t *ids = nullptr;          // [cap] the ranked head (sdpcut_rank_device)
     double *score = nullptr;
-    uint64_t *agg = nullptr;         // [MULTI_MAX_BLOCKS] look-back words
     // max_per_set = 1 forwards to the plain round, whose block has no room for the per-row extras: they live here
     std::vector<int32_t> h_nneg, h_rank;
     std::vector<double> h_rlam;
@@ -376,7 +284,7 @@ void free_multi_ws(sdpcut_ctx *h)
 {
     MultiWs *w = (MultiWs *)h->multi;
     if (!w) return;
-    (void)hipFree(w->ids); (void)hipFree(w->score); (void)hipFree(w->agg);
+    (void)hipFree(w->ids); (void)hipFree(w->score);
     delete w;
     h->multi = nullptr;
 }
@@ -388,10 +296,6 @@ static int multi_ensure(sdpcut_ctx *h, int64_t cap, MultiWs **out)
         w = new (std::nothrow) MultiWs();
         if (!w) return sdpcut_fail(h, SDPCUT_ENOMEM, "out of host memory");
         h->multi = w;
-    }
-    if (cap > 0 && !w->agg) {
-        HIP_TRY(h, hipMalloc((void **)&w->agg, MULTI_MAX_BLOCKS * 8));
-        HIP_TRY(h, hipMemsetAsync(w->agg, 0, MULTI_MAX_BLOCKS * 8, h->stream));      // no word carries a serial yet (serials start at 1)
     }
     if (cap > w->cap) {
         HIP_TRY(h, sdpcut_sync(h));
@@ -410,11 +314,8 @@ static int launch_multi_csr(sdpcut_ctx *h, MultiWs *w, int64_t cap, int64_t limi
 {
     const int grid = (int)((cap + MULTI_TILE - 1) / MULTI_TILE);
     if (grid < 1 || grid > MULTI_MAX_BLOCKS) return sdpcut_fail(h, SDPCUT_EINVAL, "round_csr_multi: head too long");
-    if (!h->d_done_ticket) {
-        // completion ticket (64 B) + the look-back words of the plain CSR epilogue (256 x 8 B), as rows.hip allocates them
-        HIP_TRY(h, hipMalloc((void **)&h->d_done_ticket, 64 + 256 * 8));
-        HIP_TRY(h, hipMemsetAsync(h->d_done_ticket, 0, 64 + 256 * 8, h->stream));
-    }
+    const int rc = ensure_round_sync(h);
+    if (rc) return rc;
     MultiCsrArgs R;
     R.cap = cap; R.limit = limit; R.row_cap = row_cap; R.m = m; R.idx = w->ids; R.score = w->score; R.idx_base = h->base;
     R.n_local = h->N; R.set5 = h->d_set_orig; R.ks = h->d_k; R.vars = h->d_vars; R.nv = h->nb_vars; R.L = h->L;
@@ -426,7 +327,7 @@ static int launch_multi_csr(sdpcut_ctx *h, MultiWs *w, int64_t cap, int64_t limi
     R.o_row_entry = (int32_t *)(b + y.row_entry); R.o_row_rank = (int32_t *)(b + y.row_rank); R.o_indptr = (int32_t *)(b + y.indptr);
     R.o_rhs = (double *)(b + y.rhs); R.o_row_lam = (double *)(b + y.row_lam); R.o_indices = (int32_t *)(b + y.indices);
     R.o_values = (double *)(b + y.values);
-    R.serial = serial; R.done_ticket = h->d_done_ticket; R.agg = w->agg;
+    R.serial = serial; R.done_ticket = h->d_done_ticket; R.agg = round_agg_words(h);
     hipLaunchKernelGGL(multi_csr_kernel, dim3(grid), dim3(64), 0, h->stream, R);
     HIP_TRY(h, hipGetLastError());
     return 0;
@@ -505,19 +406,11 @@ int sdpcut_round_csr_multi(sdpcut_handle h, const double *vars_values, int strat
     const CsrMultiLayout y = csr_multi_layout(cap, row_cap, ld);
     rc = ensure_pinned(h, y.bytes);
     if (rc) return rc;
-    int64_t *hdr = (int64_t *)h->pinned;
-    for (int attempt = 0;; ++attempt) {
-        hdr[8] = hdr[9] = hdr[10] = hdr[11] = 0;
-        const int64_t serial = ++h->round_serial;
-        rc = launch_multi_csr(h, w, cap, P, row_cap, max_per_set, ld, h->pinned_dev, serial);
-        if (rc) return rc;
-        rc = wait_round_done(h, hdr + 7, serial);
-        if (rc) return rc;
-        if (!hdr[10]) break;
-        // the bounded look-back gave up (a device shared with a long kernel): once more, as the plain round does
-        ++h->stat_fallbacks;
-        if (attempt == 1) return sdpcut_fail(h, SDPCUT_EHIP, "round_csr_multi: look-back of the row assembly timed out twice");
-    }
+    const int64_t *hdr = (const int64_t *)h->pinned;
+    rc = csr_assemble_wait(h, 11, 2, true, "round_csr_multi", [&](int64_t serial) {
+        return launch_multi_csr(h, w, cap, P, row_cap, max_per_set, ld, h->pinned_dev, serial);
+    });
+    if (rc) return rc;
     ++h->stat_rounds;
     const char *b = (const char *)h->pinned;
     o.cap = cap;

@@ -310,7 +310,7 @@ int sdpcut_round_csr_points(sdpcut_handle h, int32_t n_points, const double *poi
         ++h->stat_rounds;
         if (hdr[10] && o.n_out > 0) again.push_back(p);
     }
-    // a point whose row assembly gave up its bounded look-back (rows.hip): once more over the same head, like csr_again
+    // a point whose row assembly gave up its bounded look-back (rows.hip): once more over the same head, like csr_assemble_wait (round.hip)
     for (int p : again) {
         int64_t *hdr = (int64_t *)(block + batch_point_offset(y, p));
         hdr[8] = hdr[9] = hdr[10] = 0;

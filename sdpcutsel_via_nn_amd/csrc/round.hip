@@ -176,50 +176,55 @@ static int round_begin_exact_again(sdpcut_ctx *h, PendingRound &P)
                  : launch_round_rows(h, P.cap, d_cnt, d_idx, d_sc, P.ld, h->pinned_dev, 64, P.serial);
 }
 
-// CSR assembly of the first w entries of a head the host produced (ids and scores in the staging area), under a fresh serial
-// number, and the wait for it.  hdr[10] tells the caller whether the assembly gave up.
-static int csr_launch_wait(sdpcut_ctx *h, const PendingRound &P, int64_t w, const int64_t *d_idx, const double *d_sc)
+// A CSR assembly into the handle's pinned block, launched here and waited for: header words 8 .. last_word zeroed (10 for the
+// plain assembly, 11 for the multi-cut one), a fresh serial number, launch(serial), wait_round_done.
+// The look-back of the assembly kernels over lower-indexed workgroups is bounded (rows_dev.h: CSR_SPIN_LIMIT): on a device shared
+// with a kernel that blocks it for long it gives up and sets header word 10.  That is a transient condition, not an error of the
+// round: by the time the host sees the mark every workgroup of that launch has retired, so ONE more launch over the same head
+// (ids and scores still on the device) finds its predecessors' aggregates as soon as they are dispatched.  A give-up that is
+// followed by another launch is counted like the selection's fallbacks; after `launches` of them (2; 1 where the caller's own
+// launch was the first and has given up) the call fails in the name of `what`, and count_failure says whether that last give-up
+// is counted too (the diverse and the multi-cut round always did, the plain round never).
+int csr_assemble_wait(sdpcut_ctx *h, int last_word, int launches, bool count_failure, const char *what,
+                      const std::function<int(int64_t serial)> &launch)
 {
     int64_t *hdr = (int64_t *)h->pinned;
-    hdr[8] = hdr[9] = hdr[10] = 0;
-    const int64_t serial = ++h->round_serial;
-    int rc = launch_round_csr(h, P.cap, nullptr, w, d_idx, d_sc, P.ld, h->pinned_dev, serial);
-    if (rc) return rc;
-    return wait_round_done(h, hdr + 7, serial);
+    for (;;) {
+        for (int w = 8; w <= last_word; ++w) hdr[w] = 0;
+        const int64_t serial = ++h->round_serial;
+        int rc = launch(serial);
+        if (rc) return rc;
+        rc = wait_round_done(h, hdr + 7, serial);
+        if (rc) return rc;
+        if (!hdr[10]) return SDPCUT_OK;
+        --launches;
+        if (launches > 0 || count_failure) ++h->stat_fallbacks;
+        if (launches <= 0) return sdpcut_fail(h, SDPCUT_EHIP, std::string(what) + ": look-back of the row assembly timed out twice");
+    }
 }
 
-// round_csr_kernel's look-back over lower-indexed workgroups is bounded (CSR_SPIN_LIMIT): on a device shared with a kernel that
-// blocks it for long it gives up and sets hdr[10].  That is a transient condition, not an error of the round: by the time the
-// host sees the mark every workgroup of that launch has retired, so ONE more launch over the same head (ids and scores still
-// in the staging area) finds its predecessors' aggregates as soon as they are dispatched.  Counted like the selection's
-// fallbacks; only a second give-up fails the call.
-static int csr_again(sdpcut_ctx *h, const PendingRound &P, int64_t w, const int64_t *d_idx, const double *d_sc)
+// The plain assembly of the first w entries of a head the host produced (ids and scores in the staging area).
+static int csr_head_again(sdpcut_ctx *h, const PendingRound &P, int64_t w, int launches)
 {
-    ++h->stat_fallbacks;
-    int rc = csr_launch_wait(h, P, w, d_idx, d_sc);
-    if (rc) return rc;
-    if (((const int64_t *)h->pinned)[10]) return sdpcut_fail(h, SDPCUT_EHIP, "round_csr: look-back of the row assembly timed out twice");
-    return SDPCUT_OK;
+    const RowsLayout y = rows_layout(64, P.cap, P.ld);
+    const int64_t *d_idx = (const int64_t *)((char *)h->d_stage + y.idx);
+    const double *d_sc = (const double *)((char *)h->d_stage + y.score);
+    return csr_assemble_wait(h, 10, launches, false, "round_csr", [&](int64_t serial) {
+        return launch_round_csr(h, P.cap, nullptr, w, d_idx, d_sc, P.ld, h->pinned_dev, serial);
+    });
 }
 
 // Rows of the first w entries of a head the host just produced (after the enqueued epilogue ran), into the pinned block.
-// CSR: the assembly kernel once more (and once again if it gives up); padded: cut rows into the staging area, which
+// CSR: the assembly kernel once more (csr_assemble_wait); padded: cut rows into the staging area, which
 // mirrors the pinned block, and one copy.  csr_if_empty: whether a head of no entries still runs the CSR assembly.
 static int emit_head(sdpcut_ctx *h, const PendingRound &P, int64_t w, bool csr_if_empty)
 {
+    if (P.csr) return (w <= 0 && !csr_if_empty) ? 0 : csr_head_again(h, P, w, 2);
+    if (w <= 0) return 0;
     const RowsLayout y = rows_layout(64, P.cap, P.ld);
     char *st = (char *)h->d_stage;
     const int64_t *d_idx = (const int64_t *)(st + y.idx);
-    int rc;
-    if (P.csr) {
-        if (w <= 0 && !csr_if_empty) return 0;
-        const double *d_sc = (const double *)(st + y.score);
-        rc = csr_launch_wait(h, P, w, d_idx, d_sc);
-        if (rc) return rc;
-        return ((const int64_t *)h->pinned)[10] ? csr_again(h, P, w, d_idx, d_sc) : 0;
-    }
-    if (w <= 0) return 0;
-    rc = launch_cut_rows(h, w, nullptr, d_idx, h->base, (double *)(st + y.lam), (double *)(st + y.coef), P.ld, (double *)(st + y.rhs),
+    int rc = launch_cut_rows(h, w, nullptr, d_idx, h->base, (double *)(st + y.lam), (double *)(st + y.coef), P.ld, (double *)(st + y.rhs),
                          nullptr, (int32_t *)(st + y.ks));
     if (rc) return rc;
     HIP_TRY(h, hipMemcpyAsync(h->pinned, h->d_stage, y.bytes, hipMemcpyDeviceToHost, h->stream));
@@ -285,8 +290,9 @@ static int round_end(sdpcut_ctx *h, const void **block, int64_t *cap_out, int64_
         rc = wait_round_done(h, hdr + 7, P.serial);
         if (rc) return rc;
         have = rank_fast_finish(h, strat, sel_size, cap, (const int64_t *)h->pinned, &w, n_total, new_strat, counters) != 0;
-        if (have && P.csr && hdr[10] && w > 0) {      // the row assembly gave up its look-back (rows.hip): once more, see csr_again
-            rc = csr_again(h, P, w, d_idx, d_sc);
+        if (have && P.csr && hdr[10] && w > 0) {      // the enqueued assembly gave up its look-back: once more, see csr_assemble_wait
+            ++h->stat_fallbacks;
+            rc = csr_head_again(h, P, w, 1);
             if (rc) return rc;
         }
     }
@@ -340,13 +346,6 @@ static int round_impl(sdpcut_ctx *h, int strat, int64_t sel_size, int32_t coef_l
     return round_end(h, block, cap_out, n_out, n_total, new_strat, counters);
 }
 
-static int fill_csr_out(sdpcut_ctx *h, const void *block, sdpcut_round_csr_t *out)
-{
-    if (!block || out->cap == 0) return SDPCUT_OK;
-    csr_out_from_block(block, out);
-    return SDPCUT_OK;
-}
-
 extern "C" {
 
 int sdpcut_select_round_view(sdpcut_handle h, int strat, int64_t sel_size, int32_t coef_ld, const void **block,
@@ -374,7 +373,8 @@ int sdpcut_round_csr_end(sdpcut_handle h, sdpcut_round_csr_t *out)
     out->row_ld = h->pend.ld;
     int rc = round_end(h, &block, &out->cap, &out->n_out, &out->n_total, &out->new_strat, out->counters);
     if (rc) return rc;
-    return fill_csr_out(h, block, out);
+    if (block && out->cap != 0) csr_out_from_block(block, out);
+    return SDPCUT_OK;
 }
 
 int sdpcut_round_csr(sdpcut_handle h, const double *vars_values, int strat, int64_t sel_size, sdpcut_round_csr_t *out)

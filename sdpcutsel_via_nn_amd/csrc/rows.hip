@@ -2,19 +2,13 @@
 // (cut_select_qp.py:737-750) -- as padded rows (cut_rows_kernel, round_rows_kernel) or assembled into
 // one CSR block on the device (round_csr_kernel: SURVEY 8 f row 4, the replacement of the per-cut
 // SparsePair loop of :747-754) -- written straight into pinned host memory, and the LP point's way in.
+// The gather, the row of an eigenvector, the look-back and the completion word are rows_dev.h's, shared with the multi-cut
+// kernels (multirows.hip); the completion ticket and the look-back words of a handle are allocated here (ensure_round_sync).
 #include <hip/hip_ext.h>
 
 #include "common.h"
-#include "gather.h"
+#include "rows_dev.h"
 #include "topk_dev.h"
-
-// LDS traffic private to one wave needs no workgroup barrier (see score_mfma.hip)
-__device__ __forceinline__ void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // ------------------------------------------------------------------------------------------
 // Eigen-cut rows of selected candidates (cut_select_qp.py:737-750), one lane per cut.
@@ -25,26 +19,7 @@ __device__ __forceinline__ void cut_row_one(const int32_t *s5, const double *var
     constexpr int M = K * (K + 1) / 2;
     constexpr int D = K + 1;
     double x[K], X[M];
-    int32_t s[K];
-#pragma unroll
-    for (int a = 0; a < K; ++a) {
-        s[a] = s5[a];
-        x[a] = vars[L + s[a]];
-        cols[a] = L + s[a];
-    }
-    {
-        int m = 0;
-#pragma unroll
-        for (int a = 0; a < K; ++a) {
-            const int32_t rowbase = nv * s[a] - (s[a] * (s[a] + 1)) / 2;
-#pragma unroll
-            for (int b = a; b < K; ++b) {
-                X[m] = vars[rowbase + s[b]];
-                cols[K + m] = rowbase + s[b];
-                ++m;
-            }
-        }
-    }
+    gather_lifted<K>(s5, vars, nv, L, x, X, cols);
     double a[D][D];
     fill_lifted<K>(a, x, X);
     double lam = 0.0;
@@ -89,19 +64,7 @@ __device__ __forceinline__ void cut_row_one(const int32_t *s5, const double *var
             for (int i = 0; i < D; ++i) ev[i] = less ? v[i][j] : ev[i];
         }
     }
-#pragma unroll
-    for (int i = 0; i < D; ++i) ev[i] = (fabs(ev[i]) <= -SDPCUT_NEG_EIGVAL) ? 0.0 : ev[i];  // :744
-    {
-#pragma clang fp contract(off)
-        int m = 0;
-#pragma unroll
-        for (int i = 0; i < D; ++i)
-#pragma unroll
-            for (int j = (i > 1 ? i : 1); j < D; ++j) {     // :745-746
-                coef[m++] = (i != j) ? ev[i] * ev[j] * 2 : ev[i] * ev[j];
-            }
-        *rhs = -ev[0] * ev[0];
-    }
+    eigcut_row<K>(ev, coef, rhs);
     *lam_out = lam;
 }
 
@@ -135,12 +98,7 @@ __global__ __launch_bounds__(64) void cut_rows_kernel(int64_t count, const int64
 #pragma unroll
     for (int m = 0; m < SDPCUT_ROW_LD; ++m) { co[m] = 0.0; cl[m] = -1; }
     ks_out[i] = k;
-    switch (k) {
-    case 2: cut_row_one<2>(s5, vars, nv, L, lam + i, co, rhs + i, cl, eig ? eig + c : nullptr); break;
-    case 3: cut_row_one<3>(s5, vars, nv, L, lam + i, co, rhs + i, cl, eig ? eig + c : nullptr); break;
-    case 4: cut_row_one<4>(s5, vars, nv, L, lam + i, co, rhs + i, cl, eig ? eig + c : nullptr); break;
-    default: cut_row_one<5>(s5, vars, nv, L, lam + i, co, rhs + i, cl, eig ? eig + c : nullptr); break;
-    }
+    CALL_FOR_SET_SIZE(k, cut_row_one, s5, vars, nv, L, lam + i, co, rhs + i, cl, eig ? eig + c : nullptr);
 #pragma unroll
     for (int m = 0; m < SDPCUT_ROW_LD; ++m) {
         if (m < coef_ld) coef[i * coef_ld + m] = co[m];
@@ -201,12 +159,7 @@ __global__ __launch_bounds__(64) void round_rows_kernel(int64_t cap, const int64
         if (c >= 0 && c < n_local) {
             k = ks[c];
             const int32_t *s5 = set5 + c * 5;
-            switch (k) {
-            case 2: cut_row_one<2>(s5, vars, nv, L, &lam, co, &rhs, cl, eig ? eig + c : nullptr); break;
-            case 3: cut_row_one<3>(s5, vars, nv, L, &lam, co, &rhs, cl, eig ? eig + c : nullptr); break;
-            case 4: cut_row_one<4>(s5, vars, nv, L, &lam, co, &rhs, cl, eig ? eig + c : nullptr); break;
-            default: cut_row_one<5>(s5, vars, nv, L, &lam, co, &rhs, cl, eig ? eig + c : nullptr); break;
-            }
+            CALL_FOR_SET_SIZE(k, cut_row_one, s5, vars, nv, L, &lam, co, &rhs, cl, eig ? eig + c : nullptr);
         }
         o_lam[i] = lam;
         o_rhs[i] = rhs;
@@ -219,19 +172,7 @@ __global__ __launch_bounds__(64) void round_rows_kernel(int64_t cap, const int64
     const int64_t nlive = (limit - first < 64) ? limit - first : 64;
     const int total = nlive > 0 ? (int)nlive * coef_ld : 0;
     for (int w = lane; w < total; w += 64) o_coef[first * coef_ld + w] = tile[w];
-    if (done_serial) {
-        // completion word for the polling host: every workgroup makes its stores to the host block
-        // visible system-wide, then takes a ticket; the last one publishes the round's serial number
-        __threadfence_system();
-        if (lane == 0) {
-            const uint32_t t = __hip_atomic_fetch_add(done_ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-            if (t == gridDim.x - 1) {
-                __hip_atomic_store(done_ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // ready for the next round
-                __threadfence_system();
-                __hip_atomic_store(o_c4 + 7, done_serial, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-        }
-    }
+    if (done_serial) publish_round_done(done_ticket, o_c4 + 7, done_serial);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -244,10 +185,7 @@ __global__ __launch_bounds__(64) void round_rows_kernel(int64_t cap, const int64
 //
 // One lane per head entry, 64 entries per workgroup.  A cut's position in the block (row number, offset of
 // its non-zeros) is the number of cuts / non-zeros in front of it in head order: inside the workgroup a
-// wave scan, across workgroups a look-back over the aggregates the workgroups in front have published
-// (word = round serial | cuts | non-zeros: the serial makes a word of an earlier round invisible, nothing
-// is zeroed).  A workgroup only ever waits for workgroups with a LOWER index, which the dispatcher started
-// before it: the wait cannot deadlock whatever else runs on the device.
+// wave scan, across workgroups the look-back of rows_dev.h (csr_lookback).
 struct RoundCsrArgs {
     int64_t cap;               // head entries the block is laid out for
     const int64_t *d_c4;       // TopkWs::counters of the selection (k_eff at [3]); NULL: `limit` entries exist
@@ -281,7 +219,6 @@ struct RoundCsrArgs {
     uint64_t *agg;             // [gridDim.x] look-back words
 };
 
-#define CSR_SPIN_LIMIT (1 << 22)
 #ifndef ROUND_MIN_BLOCKS
 #define ROUND_MIN_BLOCKS 8      // workgroups of an epilogue launch at least (they share the zeroing of the next round's top-k workspace)
 #endif
@@ -319,12 +256,7 @@ __device__ __forceinline__ void round_csr_body(const RoundCsrArgs &R)
             const int32_t *sp = R.set5 + c * 5;
 #pragma unroll
             for (int a = 0; a < 5; ++a) s5[a] = sp[a];
-            switch (k) {
-            case 2: cut_row_one<2>(sp, R.vars, R.nv, R.L, &lam, co, &rhs, cl, R.eig ? R.eig + c : nullptr); break;
-            case 3: cut_row_one<3>(sp, R.vars, R.nv, R.L, &lam, co, &rhs, cl, R.eig ? R.eig + c : nullptr); break;
-            case 4: cut_row_one<4>(sp, R.vars, R.nv, R.L, &lam, co, &rhs, cl, R.eig ? R.eig + c : nullptr); break;
-            default: cut_row_one<5>(sp, R.vars, R.nv, R.L, &lam, co, &rhs, cl, R.eig ? R.eig + c : nullptr); break;
-            }
+            CALL_FOR_SET_SIZE(k, cut_row_one, sp, R.vars, R.nv, R.L, &lam, co, &rhs, cl, R.eig ? R.eig + c : nullptr);
         }
         R.o_lam[i] = lam;
         R.o_ks[i] = k;
@@ -345,31 +277,9 @@ __device__ __forceinline__ void round_csr_body(const RoundCsrArgs &R)
     const int my_off = incl - len;
     const int wg_nnz = __shfl(incl, 63);
     // publish this workgroup's aggregate, then sum those of the workgroups in front
-    const uint32_t tag = (uint32_t)R.serial;
-    if (lane == 0)
-        __hip_atomic_store(&R.agg[blockIdx.x], ((uint64_t)tag << 32) | ((uint64_t)wg_rows << 16) | (uint64_t)wg_nnz, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-    int64_t pre_rows = 0, pre_nnz = 0;
-    int gave_up = 0;
-    for (int b = lane; b < (int)blockIdx.x && !gave_up; b += 64) {
-        uint64_t w = __hip_atomic_load(&R.agg[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        uint32_t it = 0;
-        while ((uint32_t)(w >> 32) != tag) {
-            __builtin_amdgcn_s_sleep(2);
-            if (++it > CSR_SPIN_LIMIT) { gave_up = 1; break; }
-            w = __hip_atomic_load(&R.agg[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        if (!gave_up) {
-            pre_rows += (int64_t)((w >> 16) & 0xffffull);
-            pre_nnz += (int64_t)(w & 0xffffull);
-        }
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        pre_rows += __shfl_xor(pre_rows, off);
-        pre_nnz += __shfl_xor(pre_nnz, off);
-        gave_up |= __shfl_xor(gave_up, off);
-    }
-    if (gave_up && lane == 0) R.o_hdr[10] = 1;      // the block is void; the host launches the assembly once more (round.hip: emit_csr)
+    int64_t pre_rows, pre_nnz;
+    const int gave_up = csr_lookback(R.agg, (uint32_t)R.serial, wg_rows, wg_nnz, pre_rows, pre_nnz);
+    if (gave_up && lane == 0) R.o_hdr[10] = 1;      // the block is void; the host launches the assembly once more (round.hip: csr_assemble_wait)
     if (keep) {
         const int64_t r = pre_rows + my_row;
         R.o_row_entry[r] = (int32_t)i;
@@ -396,16 +306,7 @@ __global__ __launch_bounds__(64) void round_csr_kernel(RoundCsrArgs R)
     const int lane = threadIdx.x;
     for (int w = blockIdx.x * 64 + lane; w < R.zero_words; w += gridDim.x * 64) R.zero_ptr[w] = 0ull;
     round_csr_body(R);
-    // completion word for the polling host (see round_rows_kernel)
-    __threadfence_system();
-    if (lane == 0) {
-        const uint32_t t = __hip_atomic_fetch_add(R.done_ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        if (t == gridDim.x - 1) {
-            __hip_atomic_store(R.done_ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __threadfence_system();
-            __hip_atomic_store(R.o_hdr + 7, R.serial, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
+    publish_round_done(R.done_ticket, R.o_hdr + 7, R.serial);
 }
 
 // The same assembly for the P points of a batch (sdpcut_round_csr_points, points.hip): row y of the grid serves point p_first + y --
@@ -449,6 +350,32 @@ __global__ __launch_bounds__(256) void point_copy_kernel(const double *src, doub
 
 // ------------------------------------------------------------------------------------------
 // host launchers
+
+// The completion ticket and the look-back words of the handle's row assemblies (common.h: ROUND_TICKET_BYTES, ROUND_AGG_WORDS),
+// allocated by the first launch that needs them; zero once: the ticket returns to zero with every launch, and no look-back word
+// carries a serial yet (serials start at 1).  The plain, the diverse and the multi-cut round share them: no two assemblies of one
+// handle run at the same time, because every route refuses to start while a round is pending (SDPCUT_NO_PENDING) and waits for
+// its own assembly before it returns.
+int ensure_round_sync(sdpcut_ctx *h)
+{
+    if (h->d_done_ticket) return 0;
+    const size_t bytes = ROUND_TICKET_BYTES + (size_t)ROUND_AGG_WORDS * 8;
+    HIP_TRY(h, hipMalloc((void **)&h->d_done_ticket, bytes));
+    HIP_TRY(h, hipMemsetAsync(h->d_done_ticket, 0, bytes, h->stream));
+    return 0;
+}
+
+// output pointers of a CSR assembly into the block (device view) of a head of cap entries with rows of ld (round_layout.h: csr_layout)
+static void csr_args_out(RoundCsrArgs &R, void *block, int64_t cap, int ld)
+{
+    const CsrLayout y = csr_layout(cap, ld);
+    char *b = (char *)block;
+    R.o_hdr = (int64_t *)b;
+    R.o_idx = (int64_t *)(b + y.idx); R.o_score = (double *)(b + y.score); R.o_lam = (double *)(b + y.lam);
+    R.o_rhs = (double *)(b + y.rhs); R.o_values = (double *)(b + y.values); R.o_ks = (int32_t *)(b + y.ks);
+    R.o_sets = (int32_t *)(b + y.sets); R.o_row_entry = (int32_t *)(b + y.row_entry); R.o_indptr = (int32_t *)(b + y.indptr);
+    R.o_indices = (int32_t *)(b + y.indices);
+}
 int launch_cut_rows(sdpcut_ctx *h, int64_t count, const int64_t *d_limit, const int64_t *d_idx, int64_t idx_base,
                     double *d_lam, double *d_coef, int coef_ld, double *d_rhs, int64_t *d_cols, int32_t *d_ks)
 {
@@ -474,13 +401,11 @@ int launch_round_rows(sdpcut_ctx *h, int64_t cap, const int64_t *d_c4, const int
                       int coef_ld, void *block, int64_t hdr_bytes, int64_t done_serial)
 {
     if (cap <= 0) return 0;
-    if (done_serial && !h->d_done_ticket) {
-        HIP_TRY(h, hipMalloc((void **)&h->d_done_ticket, 64 + 256 * 8));      // + look-back words of round_csr_kernel
-        HIP_TRY(h, hipMemsetAsync(h->d_done_ticket, 0, 64 + 256 * 8, h->stream));
-    }
+    int rc;
+    if (done_serial && (rc = ensure_round_sync(h))) return rc;
     uint64_t *zp = nullptr;
     int zw = 0;
-    int rc = topk_alt_ws(h, &zp, &zw);
+    rc = topk_alt_ws(h, &zp, &zw);
     if (rc) return rc;
     int grid = (int)((cap + 63) / 64);
     if (grid < ROUND_MIN_BLOCKS) grid = ROUND_MIN_BLOCKS;      // (the workspace zeroing, see launch_round_csr)
@@ -498,29 +423,21 @@ int launch_round_csr(sdpcut_ctx *h, int64_t cap, const int64_t *d_c4, int64_t li
 {
     if (cap <= 0) return 0;
     int grid = (int)((cap + 63) / 64);
+    static_assert(256 <= ROUND_AGG_WORDS, "a look-back word per workgroup");
     if (grid > 256) return sdpcut_fail(h, SDPCUT_EINVAL, "round_csr: head too long");
     // (r4) the kernel also zeroes the next round's top-k workspace (124 KB): a head of a few entries is ONE workgroup, whose 64 lanes
     // then spend ~20 us on 242 stores each -- most of the epilogue of a QCQP round with 7 cuts.  Workgroups beyond the head only zero.
     if (grid < ROUND_MIN_BLOCKS) grid = ROUND_MIN_BLOCKS;
-    if (!h->d_done_ticket) {
-        // completion ticket (64 B) + the look-back words of the CSR epilogue (256 x 8 B)
-        HIP_TRY(h, hipMalloc((void **)&h->d_done_ticket, 64 + 256 * 8));
-        HIP_TRY(h, hipMemsetAsync(h->d_done_ticket, 0, 64 + 256 * 8, h->stream));
-    }
+    int rc = ensure_round_sync(h);
+    if (rc) return rc;
     RoundCsrArgs R;
     R.cap = cap; R.d_c4 = d_c4; R.limit = limit; R.idx = d_idx; R.score = d_score; R.idx_base = h->base; R.n_local = h->N;
     R.set5 = h->d_set_orig; R.ks = h->d_k; R.vars = h->d_vars; R.nv = h->nb_vars; R.L = h->L;
     R.eig = (h->scored & SDPCUT_EIG) ? h->d_eig : nullptr;
-    const CsrLayout y = csr_layout(cap, ld);
-    char *b = (char *)block;
-    R.o_hdr = (int64_t *)b;
-    R.o_idx = (int64_t *)(b + y.idx); R.o_score = (double *)(b + y.score); R.o_lam = (double *)(b + y.lam);
-    R.o_rhs = (double *)(b + y.rhs); R.o_values = (double *)(b + y.values); R.o_ks = (int32_t *)(b + y.ks);
-    R.o_sets = (int32_t *)(b + y.sets); R.o_row_entry = (int32_t *)(b + y.row_entry); R.o_indptr = (int32_t *)(b + y.indptr);
-    R.o_indices = (int32_t *)(b + y.indices);
-    int rc = topk_alt_ws(h, &R.zero_ptr, &R.zero_words);
+    csr_args_out(R, block, cap, ld);
+    rc = topk_alt_ws(h, &R.zero_ptr, &R.zero_words);
     if (rc) return rc;
-    R.serial = serial; R.done_ticket = h->d_done_ticket; R.agg = (uint64_t *)((char *)h->d_done_ticket + 64);
+    R.serial = serial; R.done_ticket = h->d_done_ticket; R.agg = round_agg_words(h);
     hipLaunchKernelGGL(round_csr_kernel, dim3(grid), dim3(64), 0, h->stream, R);
     HIP_TRY(h, hipGetLastError());
     h->topk_alt_clean = true;
@@ -541,13 +458,7 @@ int launch_round_csr_points(sdpcut_ctx *h, int p_first, int n_points, int64_t ca
     R.cap = cap; R.d_c4 = d_c4; R.limit = cap; R.idx = d_idx; R.score = d_score; R.idx_base = h->base; R.n_local = h->N;
     R.set5 = h->d_set_orig; R.ks = h->d_k; R.vars = d_pts; R.nv = h->nb_vars; R.L = h->L;
     R.eig = d_eig;
-    const CsrLayout y = csr_layout(cap, ld);
-    char *b = (char *)block;
-    R.o_hdr = (int64_t *)b;
-    R.o_idx = (int64_t *)(b + y.idx); R.o_score = (double *)(b + y.score); R.o_lam = (double *)(b + y.lam);
-    R.o_rhs = (double *)(b + y.rhs); R.o_values = (double *)(b + y.values); R.o_ks = (int32_t *)(b + y.ks);
-    R.o_sets = (int32_t *)(b + y.sets); R.o_row_entry = (int32_t *)(b + y.row_entry); R.o_indptr = (int32_t *)(b + y.indptr);
-    R.o_indices = (int32_t *)(b + y.indices);
+    csr_args_out(R, block, cap, ld);
     R.zero_ptr = nullptr; R.zero_words = 0;
     R.serial = serial; R.done_ticket = nullptr; R.agg = d_agg;
     RoundCsrPointStrides ps;
