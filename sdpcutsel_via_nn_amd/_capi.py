@@ -211,6 +211,33 @@ def _ptr(a, typ):
     return a.ctypes.data_as(typ) if a is not None else None
 
 
+def _view(ptr, dtype, count, shape=None):
+    """``count`` items of ``dtype`` at address ``ptr`` (memory the library owns) as a numpy array, no copy; an empty array for
+    a null pointer or no items"""
+    if not ptr or count == 0:
+        return np.zeros(shape if shape else 0, dtype=dtype)
+    a = np.frombuffer((_c.c_char * (count * np.dtype(dtype).itemsize)).from_address(ptr), dtype=dtype, count=count)
+    return a.reshape(shape) if shape else a
+
+
+def _counters(cnt):
+    """the four counters of a ranking (sdpcut_rank, the ``counters`` of sdpcut_round_csr_t) by name"""
+    return dict(nb_violated=int(cnt[0]), strong=int(cnt[1]), violated=int(cnt[2]), nb_positive=int(cnt[3]))
+
+
+def _empty_round():
+    """the arrays of a round without a head (fresh ones: callers may keep and change what they get)"""
+    z = np.zeros
+    return dict(idx=z(0, np.int64), score=z(0), lam=z(0), ks=z(0, np.int32), set_inds=z((0, 5), np.int32),
+                row_entry=z(0, np.int32), indptr=z(1, np.int32), indices=z(0, np.int32), values=z(0), rhs=z(0))
+
+
+# the arrays of a round inside the batch block of round_csr_points: (key, record field, dtype, item size)
+_BATCH_ARRAYS = (("idx", "idx", np.int64, 8), ("score", "score", np.float64, 8), ("lam", "lam_min", np.float64, 8), ("ks", "ks", np.int32, 4),
+                 ("set_inds", "set_inds", np.int32, 4), ("row_entry", "row_entry", np.int32, 4), ("indptr", "indptr", np.int32, 4),
+                 ("indices", "indices", np.int32, 4), ("values", "values", np.float64, 8), ("rhs", "rhs", np.float64, 8))
+
+
 class SdpCutError(RuntimeError):
     pass
 
@@ -413,6 +440,21 @@ class Scorer(object):
             raise ValueError(msg)
         raise SdpCutError("sdpcut error %d: %s" % (rc, msg))
 
+    def _open(self):
+        if getattr(self, "_h", None) is None:
+            raise SdpCutError("the Scorer is closed")
+
+    def _point_len(self):
+        """length of an LP point [X packed | x]: n(n+1)/2 + n"""
+        n = self.nb_vars
+        return n * (n + 1) // 2 + n
+
+    def _point(self, vars_values):
+        vv = _f64(vars_values)
+        if vv.shape != (self._point_len(),):
+            raise ValueError("vars_values must be [X packed | x] of length n(n+1)/2 + n")
+        return vv
+
     def close(self):
         if getattr(self, "_h", None):
             self._lib.sdpcut_destroy(self._h)
@@ -530,10 +572,7 @@ class Scorer(object):
         return out[:idx.shape[0]], ks[:idx.shape[0]]
 
     def set_point(self, vars_values):
-        vv = _f64(vars_values)
-        n = self.nb_vars
-        if vv.shape != (n * (n + 1) // 2 + n,):
-            raise ValueError("vars_values must be [X packed | x] of length n(n+1)/2 + n")
+        vv = self._point(vars_values)
         self._check(self._lib.sdpcut_set_point(self._h, _ptr(vv, _dp)))
 
     def point_buffer(self):
@@ -541,8 +580,7 @@ class Scorer(object):
         and pass IT to set_point / select_round / round_csr -- the library then skips its host copy of the point."""
         p = _dp()
         self._check(self._lib.sdpcut_point_buffer(self._h, ctypes.byref(p)))
-        n = self.nb_vars
-        count = n * (n + 1) // 2 + n
+        count = self._point_len()
         addr = ctypes.cast(p, _vp).value
         return np.frombuffer((_c.c_double * count).from_address(addr), dtype=np.float64, count=count)
 
@@ -576,8 +614,7 @@ class Scorer(object):
         self._check(self._lib.sdpcut_rank(self._h, int(strat), int(sel_size), cap, _ptr(idx, _i64p), _ptr(sc, _dp),
                                           ctypes.byref(n_total), ctypes.byref(new_strat), _ptr(cnt, _i64p)))
         w = min(cap, n_total.value)
-        counters = dict(nb_violated=int(cnt[0]), strong=int(cnt[1]), violated=int(cnt[2]), nb_positive=int(cnt[3]))
-        return idx[:w], sc[:w], int(n_total.value), int(new_strat.value), counters
+        return idx[:w], sc[:w], int(n_total.value), int(new_strat.value), _counters(cnt)
 
     def rank_fetch(self, offset, count):
         idx = np.empty(max(count, 1), dtype=np.int64)
@@ -591,8 +628,7 @@ class Scorer(object):
         self._check(self._lib.sdpcut_rank_device(self._h, int(strat), int(sel_size), int(max_out), _vp(d_idx_ptr),
                                                  _vp(d_score_ptr), ctypes.byref(n_written), ctypes.byref(n_total),
                                                  ctypes.byref(new_strat), _ptr(cnt, _i64p)))
-        counters = dict(nb_violated=int(cnt[0]), strong=int(cnt[1]), violated=int(cnt[2]), nb_positive=int(cnt[3]))
-        return int(n_written.value), int(n_total.value), int(new_strat.value), counters
+        return int(n_written.value), int(n_total.value), int(new_strat.value), _counters(cnt)
 
     def merge_topk_device(self, count, d_scores_ptr, d_ids_ptr, max_out, d_score_out_ptr, d_id_out_ptr,
                           d_secondary_ptr=None):
@@ -638,10 +674,7 @@ class Scorer(object):
                                   _ptr(cnt, _i64p)))
         block, cap, n_out, n_total, new_strat, cnt, refs = st
         if point is not None:
-            vv = _f64(point)
-            n = self.nb_vars
-            if vv.shape != (n * (n + 1) // 2 + n,):
-                raise ValueError("vars_values must be [X packed | x] of length n(n+1)/2 + n")
+            vv = self._csr_point(point)
             self._check(self._lib.sdpcut_round_view(self._h, _ptr(vv, _dp), int(strat), int(sel_size), ld, *refs))
         else:
             self._check(self._lib.sdpcut_select_round_view(self._h, int(strat), int(sel_size), ld, *refs))
@@ -668,9 +701,7 @@ class Scorer(object):
             idx, sc, lam, rhs = np.empty(0, np.int64), np.empty(0), np.empty(0), np.empty(0)
             coef, ks = np.empty((0, ld)), np.empty(0, np.int32)
         return dict(idx=idx, score=sc, lam=lam, coef=coef, rhs=rhs, ks=ks,
-                    n_total=int(n_total.value), new_strat=int(new_strat.value),
-                    counters=dict(nb_violated=int(cnt[0]), strong=int(cnt[1]), violated=int(cnt[2]),
-                                  nb_positive=int(cnt[3])))
+                    n_total=int(n_total.value), new_strat=int(new_strat.value), counters=_counters(cnt))
 
     def round_csr(self, strat, sel_size, point=None, copy=False):
         """One round with the cuts assembled on the device (sdpcut_round_csr): LP point -> score -> rank -> eigen-cuts
@@ -710,13 +741,7 @@ class Scorer(object):
         return True
 
     def _csr_point(self, point):
-        if point is None:
-            return None
-        vv = _f64(point)
-        n = self.nb_vars
-        if vv.shape != (n * (n + 1) // 2 + n,):
-            raise ValueError("vars_values must be [X packed | x] of length n(n+1)/2 + n")
-        return vv
+        return None if point is None else self._point(point)
 
     def _csr_out(self):
         out = getattr(self, "_csr_struct", None)
@@ -724,22 +749,21 @@ class Scorer(object):
             out = self._csr_struct = RoundCsr()
         return out
 
-    def _csr_unpack(self, out, copy):
+    def _csr_unpack(self, out, copy, row_cap=None):
+        """sdpcut_round_csr_t -> the round dict: the one place that maps the record.  row_cap: the capacity of the row arrays where
+        it is not the head's (a multi-cut round holds up to cuts_per_set rows per entry)."""
         c, w, r = int(out.cap), int(out.n_out), int(out.n_rows)
         if c and out.idx:
-            key = (out.idx, c, int(out.row_ld))
+            ld, rc = int(out.row_ld), c if row_cap is None else int(row_cap)
+            # (plain and multi-cut rounds lay the same block out differently: the first, a middle and the last array pin the layout)
+            key = (out.idx, out.ks, out.indices, c, ld, rc)
             if getattr(self, "_csr_view_key", None) != key:       # the block is reused round after round
-                ld = int(out.row_ld)
-
-                def view(ptr, dtype, count, shape=None):
-                    a = np.frombuffer((_c.c_char * (count * np.dtype(dtype).itemsize)).from_address(ptr), dtype=dtype, count=count)
-                    return a.reshape(shape) if shape else a
                 self._csr_views = dict(
-                    idx=view(out.idx, np.int64, c), score=view(out.score, np.float64, c), lam=view(out.lam_min, np.float64, c),
-                    ks=view(out.ks, np.int32, c), set_inds=view(out.set_inds, np.int32, 5 * c, (c, 5)),
-                    row_entry=view(out.row_entry, np.int32, c), indptr=view(out.indptr, np.int32, c + 1),
-                    indices=view(out.indices, np.int32, c * ld), values=view(out.values, np.float64, c * ld),
-                    rhs=view(out.rhs, np.float64, c))
+                    idx=_view(out.idx, np.int64, c), score=_view(out.score, np.float64, c), lam=_view(out.lam_min, np.float64, c),
+                    ks=_view(out.ks, np.int32, c), set_inds=_view(out.set_inds, np.int32, 5 * c, (c, 5)),
+                    row_entry=_view(out.row_entry, np.int32, rc), indptr=_view(out.indptr, np.int32, rc + 1),
+                    indices=_view(out.indices, np.int32, rc * ld), values=_view(out.values, np.float64, rc * ld),
+                    rhs=_view(out.rhs, np.float64, rc))
                 self._csr_view_key = key
             v = self._csr_views
             nnz = int(out.nnz)
@@ -749,12 +773,8 @@ class Scorer(object):
             if copy:
                 res = {k: a.copy() for k, a in res.items()}
         else:
-            z = np.zeros
-            res = dict(idx=z(0, np.int64), score=z(0), lam=z(0), ks=z(0, np.int32), set_inds=z((0, 5), np.int32),
-                       row_entry=z(0, np.int32), indptr=z(1, np.int32), indices=z(0, np.int32), values=z(0), rhs=z(0))
-        cnt = out.counters
-        res.update(n_total=int(out.n_total), new_strat=int(out.new_strat),
-                   counters=dict(nb_violated=int(cnt[0]), strong=int(cnt[1]), violated=int(cnt[2]), nb_positive=int(cnt[3])))
+            res = _empty_round()
+        res.update(n_total=int(out.n_total), new_strat=int(out.new_strat), counters=_counters(out.counters))
         return res
 
     # ------------------------------------------------------------------ diverse selection
@@ -771,8 +791,7 @@ class Scorer(object):
         rejected_parallel)``.  point=None keeps the current LP point; strategies 1, 2 and 4."""
         mp, sel_size, pool_size = check_diverse_args(max_parallel, sel_size, pool_size, strat)
         vv = self._csr_point(point)
-        if getattr(self, "_h", None) is None:
-            raise SdpCutError("the Scorer is closed")
+        self._open()
         self.round_count += 1
         out, info = self._csr_out(), DiverseInfo()
         self._check(self._lib.sdpcut_round_csr_diverse(self._h, _ptr(vv, _dp), int(strat), sel_size, pool_size, mp, ctypes.byref(out),
@@ -788,9 +807,8 @@ class Scorer(object):
         idx = np.ascontiguousarray(ids, dtype=np.int64)
         if idx.ndim != 1 or idx.shape[0] > DIVERSE_MAX_POOL:
             raise ValueError("ids must be a list of at most %d local candidate ids" % DIVERSE_MAX_POOL)
-        if getattr(self, "_h", None) is None:
-            raise SdpCutError("the Scorer is closed")
-        keep = np.zeros(max(idx.shape[0], 1), dtype=np.uint8)
+        self._open()
+        keep =np.zeros(max(idx.shape[0], 1), dtype=np.uint8)
         info = DiverseInfo()
         self._check(self._lib.sdpcut_filter_parallel(self._h, idx.shape[0], _ptr(idx, _i64p), quota, mp, keep.ctypes.data_as(_u8p),
                                                      ctypes.byref(info)))
@@ -806,33 +824,15 @@ class Scorer(object):
         bit for bit.  point=None keeps the current LP point; views as there unless copy=True."""
         m, quota = check_multi_args(cuts_per_set, row_quota, sel_size, strat)
         vv = self._csr_point(point)
-        if getattr(self, "_h", None) is None:
-            raise SdpCutError("the Scorer is closed")
+        self._open()
         self.round_count += 1
         out = RoundMulti()
         self._check(self._lib.sdpcut_round_csr_multi(self._h, _ptr(vv, _dp), int(strat), int(sel_size), m, quota, ctypes.byref(out)))
-        o = out.csr
-        c, w, r, nnz = int(o.cap), int(o.n_out), int(o.n_rows), int(o.nnz)
-
-        def view(ptr, dtype, count, shape=None):
-            if not ptr or count == 0:
-                return np.zeros(shape if shape else 0, dtype=dtype)
-            a = np.frombuffer((_c.c_char * (count * np.dtype(dtype).itemsize)).from_address(ptr), dtype=dtype, count=count)
-            return a.reshape(shape) if shape else a
-        if not (c and o.idx):
-            w = r = nnz = 0
-        res = dict(idx=view(o.idx, np.int64, w), score=view(o.score, np.float64, w), lam=view(o.lam_min, np.float64, w),
-                   ks=view(o.ks, np.int32, w), set_inds=view(o.set_inds, np.int32, 5 * w, (w, 5)),
-                   row_entry=view(o.row_entry, np.int32, r), indices=view(o.indices, np.int32, nnz), values=view(o.values, np.float64, nnz),
-                   rhs=view(o.rhs, np.float64, r), n_neg=view(out.n_neg, np.int32, w), row_lam=view(out.row_lam, np.float64, r),
-                   row_rank=view(out.row_rank, np.int32, r))
-        res["indptr"] = view(o.indptr, np.int32, r + 1) if (c and o.idx) else np.zeros(1, np.int32)
-        if copy:
-            res = {k: a.copy() for k, a in res.items()}
-        cnt = o.counters
-        res.update(n_total=int(o.n_total), new_strat=int(o.new_strat), n_used=int(out.n_used), quota_hit=bool(out.quota_hit),
-                   row_cap=int(out.row_cap),
-                   counters=dict(nb_violated=int(cnt[0]), strong=int(cnt[1]), violated=int(cnt[2]), nb_positive=int(cnt[3])))
+        res = self._csr_unpack(out.csr, copy, row_cap=out.row_cap)
+        w, r = res["idx"].shape[0], res["rhs"].shape[0]
+        extra = dict(n_neg=_view(out.n_neg, np.int32, w), row_lam=_view(out.row_lam, np.float64, r), row_rank=_view(out.row_rank, np.int32, r))
+        res.update({k: a.copy() for k, a in extra.items()} if copy else extra)
+        res.update(n_used=int(out.n_used), quota_hit=bool(out.quota_hit), row_cap=int(out.row_cap))
         return res
 
     def cut_rows_all(self, local_idx, cuts_per_set):
@@ -843,8 +843,7 @@ class Scorer(object):
         idx = np.ascontiguousarray(local_idx, dtype=np.int64)
         if idx.ndim != 1:
             raise ValueError("local_idx must be a list of local candidate ids")
-        if getattr(self, "_h", None) is None:
-            raise SdpCutError("the Scorer is closed")
+        self._open()
         c = idx.shape[0]
         row_ptr = np.zeros(c + 1, dtype=np.int64)
         lam = np.empty(max(c * m, 1))
@@ -861,8 +860,7 @@ class Scorer(object):
     pool_capacity = 0
 
     def _pool_open(self):
-        if getattr(self, "_h", None) is None:
-            raise SdpCutError("the Scorer is closed")
+        self._open()
         if not self.pool_capacity:
             raise SdpCutError("pool_create first")
 
@@ -872,8 +870,7 @@ class Scorer(object):
         capacity = int(capacity)
         if not 1 <= capacity <= POOL_MAX_ROWS:
             raise ValueError("capacity must lie in 1 .. %d" % POOL_MAX_ROWS)
-        if getattr(self, "_h", None) is None:
-            raise SdpCutError("the Scorer is closed")
+        self._open()
         self._check(self._lib.sdpcut_pool_create(self._h, capacity))
         self.pool_capacity, self._pool_rows = capacity, 0
 
@@ -887,8 +884,7 @@ class Scorer(object):
         (sdpcut_pool_add_csr) -> the serial of the first one; the others follow it.  A refused block (ValueError) leaves the pool
         unchanged."""
         self._pool_open()
-        n = self.nb_vars
-        indptr, indices, values, rhs, sense = check_pool_rows(indptr, indices, values, rhs, sense, n * (n + 1) // 2 + n,
+        indptr, indices, values, rhs, sense = check_pool_rows(indptr, indices, values, rhs, sense, self._point_len(),
                                                               self.pool_capacity - self._pool_rows)
         first = _c.c_int64(0)
         self._check(self._lib.sdpcut_pool_add_csr(self._h, rhs.shape[0], _ptr(indptr, _i32p), _ptr(indices, _i32p), _ptr(values, _dp),
@@ -908,20 +904,18 @@ class Scorer(object):
         par, out = PoolParams(tt, vt, ma, da, mr), PoolStep()
         self._check(self._lib.sdpcut_pool_step(self._h, _ptr(vv, _dp), ctypes.byref(par), ctypes.byref(out)))
 
-        def view(ptr, dtype, count):
-            if not ptr or count == 0:
-                return np.zeros(0, dtype=dtype)
-            a = np.frombuffer((_c.c_char * (count * np.dtype(dtype).itemsize)).from_address(ptr), dtype=dtype, count=count)
-            return a.copy() if copy else a
         w, nnz = int(out.n_enter), int(out.enter_nnz)
         self._pool_rows -= int(out.n_dropped)
-        return dict(leave=view(out.leave, np.int64, int(out.n_leave)), enter=view(out.enter, np.int64, w),
-                    dropped=view(out.dropped, np.int64, int(out.n_dropped)),
-                    enter_indptr=view(out.enter_indptr, np.int32, w + 1) if w else np.zeros(1, np.int32),
-                    enter_indices=view(out.enter_indices, np.int32, nnz), enter_values=view(out.enter_values, np.float64, nnz),
-                    enter_rhs=view(out.enter_rhs, np.float64, w), enter_sense=view(out.enter_sense, np.int32, w),
-                    enter_key=view(out.enter_key, np.float64, w), n_in_lp=int(out.n_in_lp), n_parked=int(out.n_parked),
-                    n_violated=int(out.n_violated), n_dropped=int(out.n_dropped))
+        res = dict(leave=_view(out.leave, np.int64, int(out.n_leave)), enter=_view(out.enter, np.int64, w),
+                   dropped=_view(out.dropped, np.int64, int(out.n_dropped)),
+                   enter_indptr=_view(out.enter_indptr, np.int32, w + 1) if w else np.zeros(1, np.int32),
+                   enter_indices=_view(out.enter_indices, np.int32, nnz), enter_values=_view(out.enter_values, np.float64, nnz),
+                   enter_rhs=_view(out.enter_rhs, np.float64, w), enter_sense=_view(out.enter_sense, np.int32, w),
+                   enter_key=_view(out.enter_key, np.float64, w))
+        if copy:
+            res = {k: a.copy() for k, a in res.items()}
+        res.update(n_in_lp=int(out.n_in_lp), n_parked=int(out.n_parked), n_violated=int(out.n_violated), n_dropped=int(out.n_dropped))
+        return res
 
     def pool_state(self):
         """The whole pool in row order (sdpcut_pool_get), for tests and tools -> dict(n, next_serial, serial, state, age, nnz,
@@ -944,8 +938,7 @@ class Scorer(object):
     # ------------------------------------------------------------------ many LP points per call
     def _points_arg(self, points):
         pts = _f64(points)
-        n = self.nb_vars
-        if pts.ndim != 2 or pts.shape[1] != n * (n + 1) // 2 + n:
+        if pts.ndim != 2 or pts.shape[1] != self._point_len():
             raise ValueError("points must be [P, n(n+1)/2 + n]: one LP point [X packed | x] per row")
         if not 1 <= pts.shape[0] <= BATCH_MAX_POINTS:
             raise ValueError("1 .. %d points per call" % BATCH_MAX_POINTS)
@@ -972,10 +965,9 @@ class Scorer(object):
         them.  Strategies 1, 2 and 4.  Leaves the Scorer without a current point."""
         pts = self._points_arg(points)
         P = pts.shape[0]
-        if getattr(self, "_h", None) is None:
-            raise SdpCutError("the Scorer is closed")
+        self._open()
         self.round_count += 1
-        recs = getattr(self, "_csr_points_recs", None)
+        recs =getattr(self, "_csr_points_recs", None)
         if recs is None or recs.shape[0] < P:
             recs = self._csr_points_recs = np.zeros(max(P, 8), dtype=_ROUND_CSR_DTYPE)
         self._check(self._lib.sdpcut_round_csr_points(self._h, P, _ptr(pts, _dp), pts.shape[1], int(strat), int(sel_size),
@@ -996,22 +988,17 @@ class Scorer(object):
         for p in range(P):
             c, w, nr, nnz = cols["cap"][p], cols["n_out"][p], cols["n_rows"][p], cols["nnz"][p]
             if c and cols["idx"][p]:
-                def view(field, dtype, count, size):
+                counts = dict(idx=w, score=w, lam=w, ks=w, set_inds=5 * w, row_entry=nr, indptr=nr + 1, indices=nnz, values=nnz, rhs=nr)
+                d = {}
+                for key, field, dtype, size in _BATCH_ARRAYS:
                     o = cols[field][p] - base
-                    return u8[o:o + count * size].view(dtype)
-                d = dict(idx=view("idx", np.int64, w, 8), score=view("score", np.float64, w, 8), lam=view("lam_min", np.float64, w, 8),
-                         ks=view("ks", np.int32, w, 4), set_inds=view("set_inds", np.int32, 5 * w, 4).reshape(w, 5),
-                         row_entry=view("row_entry", np.int32, nr, 4), indptr=view("indptr", np.int32, nr + 1, 4),
-                         indices=view("indices", np.int32, nnz, 4), values=view("values", np.float64, nnz, 8), rhs=view("rhs", np.float64, nr, 8))
+                    d[key] = u8[o:o + counts[key] * size].view(dtype)
+                d["set_inds"] = d["set_inds"].reshape(w, 5)
                 if copy:
                     d = {k: a.copy() for k, a in d.items()}
             else:
-                z = np.zeros
-                d = dict(idx=z(0, np.int64), score=z(0), lam=z(0), ks=z(0, np.int32), set_inds=z((0, 5), np.int32),
-                         row_entry=z(0, np.int32), indptr=z(1, np.int32), indices=z(0, np.int32), values=z(0), rhs=z(0))
-            cnt = cols["counters"][p]
-            d.update(n_total=cols["n_total"][p], new_strat=cols["new_strat"][p],
-                     counters=dict(nb_violated=cnt[0], strong=cnt[1], violated=cnt[2], nb_positive=cnt[3]))
+                d = _empty_round()
+            d.update(n_total=cols["n_total"][p], new_strat=cols["new_strat"][p], counters=_counters(cols["counters"][p]))
             res.append(d)
         return res
 
@@ -1026,14 +1013,8 @@ class Scorer(object):
         out = DenseRound()
         self._check(self._lib.sdpcut_dense_round(self._h, _ptr(vv, _dp), ctypes.byref(out)))
         D, r, rl = int(out.dim), int(out.n_rows), int(out.row_len)
-
-        def view(ptr, dtype, count, shape=None):
-            if count == 0:
-                return np.zeros(shape or 0, dtype=dtype)
-            a = np.frombuffer((_c.c_char * (count * np.dtype(dtype).itemsize)).from_address(ptr), dtype=dtype, count=count)
-            return a.reshape(shape) if shape else a
-        res = dict(eigvals=view(out.eigvals, np.float64, D), cols=view(out.cols, np.int32, rl),
-                   values=view(out.values, np.float64, r * rl, (r, rl)), rhs=view(out.rhs, np.float64, r))
+        res = dict(eigvals=_view(out.eigvals, np.float64, D), cols=_view(out.cols, np.int32, rl),
+                   values=_view(out.values, np.float64, r * rl, (r, rl)), rhs=_view(out.rhs, np.float64, r))
         if copy:
             res = {k: a.copy() for k, a in res.items()}
         res.update(n_rows=r, sweeps=int(out.sweeps))

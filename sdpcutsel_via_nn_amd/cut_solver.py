@@ -19,16 +19,27 @@ All arithmetic (gather, eigen-decomposition, MLP, ranking, cut coefficients) run
 libsdpcut_hip.so; this file only marshals arrays and builds the Python objects the loop
 expects.  No CPU fallback exists: without the library / a gfx950 GPU the methods raise.
 """
-from collections.abc import Sequence
+from types import SimpleNamespace
 
 import numpy as np
 
 from . import _capi, networks
+from .rank_list import (AggArrays, DeviceAgg, FeasEntry, RankList, RankListHead, _BIG_M, _Binding, _Concat,  # noqa: F401
+                        csr_prefix, rows_to_csr, strong_prefix)
 
 _THRES_NEG_EIGVAL = -10 ** (-15)      # cut_select_qp.py:24
-_BIG_M = 1000                         # cut_select_qp.py:26
 _HEAD = 5000                          # _SDP_CUTS_PER_ROUND_MAX (:37): rank-list head fetched eagerly
 _FUSED_HEAD_MAX = 16384               # longest head the fused round (sdpcut_round_csr) assembles
+# what each selecting strategy has the device score: feasibility, optimality (MLP), exact optimality, combined
+_MEASURES = {1: _capi.EIG, 2: _capi.NN, 3: _capi.SDP, 4: _capi.EIG | _capi.NN}
+_OPT_STRATS = (2, 3, 4, -1)           # strategies whose rank-list entries are optimality tuples (cut_select_qp.py:599)
+
+
+def _lp_point(vars_values):
+    """the LP point as a contiguous float64 array: the caller's own array where it already is one"""
+    if isinstance(vars_values, np.ndarray) and vars_values.dtype == np.float64 and vars_values.flags.c_contiguous:
+        return vars_values
+    return np.ascontiguousarray(vars_values, dtype=np.float64)
 
 
 _SPARSE_PAIR = None
@@ -46,433 +57,6 @@ def _default_sparse_pair():
             from .harness import SparsePair
             _SPARSE_PAIR = SparsePair
     return _SPARSE_PAIR
-
-
-def rows_to_csr(coef, cols, ks):
-    """Padded cut rows (stride SDPCUT_ROW_LD, row c has k_c(k_c+3)/2 live entries) -> CSR
-    (indptr int64 [R+1], indices int64, values float64)."""
-    ks = np.asarray(ks, dtype=np.int64)
-    lens = ks * (ks + 3) // 2
-    indptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
-    live = np.arange(coef.shape[1])[None, :] < lens[:, None]
-    return indptr, np.ascontiguousarray(cols[live], dtype=np.int64), np.ascontiguousarray(coef[live], dtype=np.float64)
-
-
-class FeasEntry(tuple):
-    """``(set_inds, -eigval, Xarr_inds, dim_act)`` of cut_select_qp.py:649, remembering which
-    candidate it came from so that cut generation needs no search."""
-    agg_idx = -1
-    binding = None
-
-    def __new__(cls, items, agg_idx, binding=None):
-        self = super().__new__(cls, items)
-        self.agg_idx = agg_idx
-        self.binding = binding
-        return self
-
-
-class RankList(Sequence):
-    """Lazy stand-in for the reference's sorted ``rank_list``.
-
-    The reference materialises N Python tuples; downstream code only looks at the first
-    ``sel_size`` of them.  This object keeps the ranking on the device, fetches windows on
-    demand (``sdpcut_rank_fetch``) and builds entry tuples only for what is indexed.
-    ``a + b`` (cut_select_qcqp.py:79) and slicing return plain lists of entries.
-    """
-
-    def __init__(self, owner, binding, kind, total, vars_values, head_idx, head_score, strat=None, sel_size=0, fused=None):
-        self._owner, self._b, self._kind, self._n = owner, binding, kind, int(total)
-        self._vv = vars_values
-        self._strat, self._sel_size = strat, sel_size
-        self._idx, self._score = head_idx, head_score
-        self._have = head_idx.shape[0]
-        self._point = binding.point_token
-        # fused round (sdpcut_round_csr): the cuts of the head already sit, assembled, in the scorer's pinned block;
-        # `fused` holds views of it, good until the scorer runs its next round (round_count moves on)
-        self._fused, self._fused_at = fused, binding.scorer.round_count
-        self._head_sets = self._head_ks = None
-        if fused is not None:
-            self._head_sets, self._head_ks = fused["set_inds"].copy(), fused["ks"].copy()
-
-    def fused_rows(self, count, strong_only=False, vars_values=None):
-        """The assembled cuts of the first ``count`` entries if the fused round's block still holds them:
-        (indptr, indices, values, rhs) views, or None (stale block, longer head, another LP point)."""
-        f = self._fused
-        if f is None or self._b.scorer.round_count != self._fused_at or count > self._have:
-            return None
-        if vars_values is not None and vars_values is not self._vv and not np.array_equal(vars_values, self._vv):
-            return None
-        if strong_only:                                   # cut_select_qp.py:725-726
-            stop = np.flatnonzero(self._score[:count] <= 0)
-            if stop.size:
-                count = int(stop[0])
-        r = int(np.searchsorted(f["row_entry"], count))   # cuts of the first `count` entries = a prefix of the block
-        nnz = int(f["indptr"][r])
-        return f["indptr"][:r + 1], f["indices"][:nnz], f["values"][:nnz], f["rhs"][:r]
-
-    # -- data access -----------------------------------------------------------------
-    def _need(self, upto):
-        """The head came from the device's top-k selection; anything beyond it asks for the
-        complete ranking (full device sort), once."""
-        upto = min(upto, self._n)
-        if upto <= self._have:
-            return
-        if self._b.point_token != self._point:
-            raise RuntimeError("rank list is stale: the device now holds the scores of a newer LP point")
-        self._b.drain()
-        idx, sc, total, _, _ = self._b.scorer.rank(self._strat, self._sel_size, max_out=self._n)
-        self._idx, self._score, self._have = idx, sc, idx.shape[0]
-
-    def ids(self, count=None):
-        count = self._n if count is None else min(count, self._n)
-        self._need(count)
-        return self._idx[:count]
-
-    def scores(self, count=None):
-        count = self._n if count is None else min(count, self._n)
-        self._need(count)
-        return self._score[:count]
-
-    def count_above(self, thr):
-        """Number of entries of the WHOLE list whose score exceeds ``thr`` (cut_select_qcqp.py:85-87 counts the entries above
-        BIG_M).  The list is sorted by score, so the head answers when its last score is <= thr; under the combined strategy a
-        head that consists of marked entries only (obj_improve + BIG_M, cut_select_qp.py:611) answers too when the entries behind
-        it -- the ones the scan never reached, all with an obj_improve no larger than the last marked one's -- cannot exceed thr.
-        Otherwise the complete ranking is fetched."""
-        h = self._score
-        if self._have == 0:
-            return 0
-        last = float(h[self._have - 1])
-        if self._have >= self._n or last <= thr or (self._strat == 4 and last > _BIG_M and last - _BIG_M <= thr):
-            return int(np.count_nonzero(h[:self._have] > thr))
-        return int(np.count_nonzero(self.scores() > thr))
-
-    def _sets(self, lo, hi, loc):
-        """(index sets [m, 5], sizes [m]) of positions [lo, hi): from the fused round's head when it covers them"""
-        if self._head_sets is not None and hi <= self._head_sets.shape[0]:
-            return self._head_sets[lo:hi], self._head_ks[lo:hi]
-        return self._b.sets_of(loc)
-
-    def _entry(self, pos):
-        idx, score = int(self._idx[pos]), float(self._score[pos])
-        if self._b.agg_list is None or isinstance(self._b.agg_list, DeviceAgg):
-            S, ks = self._sets(pos, pos + 1, np.array([idx - self._b.scorer.base], dtype=np.int64))
-            k, n = int(ks[0]), self._b.nb_vars
-            set_inds = [int(v) for v in S[0, :k]]
-            Xarr_inds = [n * set_inds[a] - set_inds[a] * (set_inds[a] + 1) // 2 + set_inds[c] for a in range(k) for c in range(a, k)]
-        else:
-            set_inds, Xarr_inds = self._b.agg_entry(idx)
-        if self._kind == 1:
-            return FeasEntry((set_inds, score, Xarr_inds, len(set_inds)), idx, self._b)
-        L = self._b.nb_lifted
-        curr_pt = tuple(self._vv[L + i] for i in set_inds)
-        X_slice = tuple(self._vv[i] for i in Xarr_inds)
-        return (idx, score, curr_pt, X_slice)
-
-    def _entries(self, lo, hi):
-        """Entry tuples of positions [lo, hi) built with array gathers (one fancy-indexing pass per
-        candidate size instead of a Python loop per value): what iteration and slicing use."""
-        hi = min(hi, self._n)
-        if hi <= lo:
-            return []
-        if hi - lo < 8:
-            return [self._entry(p) for p in range(lo, hi)]
-        b, vv, L, n = self._b, self._vv, self._b.nb_lifted, self._b.nb_vars
-        ids = np.asarray(self._idx[lo:hi], dtype=np.int64)
-        loc = ids - b.scorer.base
-        scores = np.asarray(self._score[lo:hi], dtype=np.float64).tolist()
-        S_all, ks = self._sets(lo, hi, loc)
-        out = [None] * (hi - lo)
-        for k in np.unique(ks):
-            k = int(k)
-            m = np.nonzero(ks == k)[0]
-            S = S_all[m, :k].astype(np.int64)
-            ia, ib = np.triu_indices(k)
-            pos = n * S[:, ia] - S[:, ia] * (S[:, ia] + 1) // 2 + S[:, ib]
-            if self._kind == 1:
-                for j, s_row, p_row in zip(m.tolist(), S.tolist(), pos.tolist()):
-                    i = int(ids[j])
-                    if b.agg_list is not None and not isinstance(b.agg_list, DeviceAgg):      # hand out the caller's own lists, as the reference does
-                        s_row, p_row = b.agg_list[int(loc[j])][0:2]
-                    out[j] = FeasEntry((s_row, scores[j], p_row, k), i, b)
-            else:
-                cp, Xs = vv[L + S].tolist(), vv[pos].tolist()
-                for t, j in enumerate(m.tolist()):
-                    out[j] = (int(ids[j]), scores[j], tuple(cp[t]), tuple(Xs[t]))
-        return out
-
-    # -- Sequence protocol -----------------------------------------------------------
-    def __len__(self):
-        return self._n
-
-    def __getitem__(self, key):
-        if isinstance(key, slice):
-            rng = range(*key.indices(self._n))
-            if not len(rng):
-                return []
-            self._need((rng[-1] if rng.step > 0 else rng[0]) + 1)      # (max(rng) walks the range: 16 us for a head of 5000)
-            if rng.step == 1 and rng.start == 0:
-                return RankListHead(self, rng.stop)
-            if rng.step == 1:
-                return self._entries(rng.start, rng.stop)
-            return [self._entry(p) for p in rng]
-        if key < 0:
-            key += self._n
-        if not 0 <= key < self._n:
-            raise IndexError(key)
-        self._need(key + 1)
-        return self._entry(key)
-
-    def __iter__(self):
-        for lo in range(0, self._n, 65536):
-            hi = min(lo + 65536, self._n)
-            self._need(hi)
-            for e in self._entries(lo, hi):
-                yield e
-
-    def __add__(self, other):
-        """``a + b`` of cut_select_qcqp.py:79 without building either list: the caller slices
-        ``[0:sel_size]`` off the concatenation, and only that slice is materialised."""
-        return _Concat([self, other])
-
-    def __radd__(self, other):
-        return _Concat([other, self])
-
-
-class RankListHead(Sequence):
-    """``rank_list[0:count]`` (cut_select_qp.py:181 hands the whole list over, cut_select_qcqp.py:79-97 slices of
-    it): the entries are built when somebody looks at them, and cut generation still finds the rows the fused
-    round assembled for exactly these candidates."""
-
-    def __init__(self, parent, count):
-        self.parent, self._n = parent, int(count)
-        self._list = None
-
-    def _entries(self):
-        if self._list is None:
-            self._list = self.parent._entries(0, self._n)
-        return self._list
-
-    def __len__(self):
-        return self._n
-
-    def __getitem__(self, key):
-        if isinstance(key, slice):
-            start, stop, step = key.indices(self._n)
-            if start == 0 and step == 1:
-                return RankListHead(self.parent, stop)
-        return self._entries()[key]
-
-    def __iter__(self):
-        return iter(self._entries())
-
-    def __eq__(self, other):
-        return list(self) == list(other)
-
-    def __add__(self, other):
-        return _Concat([self, other])
-
-    def __radd__(self, other):
-        return _Concat([other, self])
-
-
-class _Concat(Sequence):
-    """Lazy concatenation of rank lists (``rank_list_comb_obj + rank_list_feas_cons``)."""
-
-    def __init__(self, parts):
-        self._parts = [p for p in parts]
-
-    def __len__(self):
-        return sum(len(p) for p in self._parts)
-
-    def __iter__(self):
-        for p in self._parts:
-            for e in p:
-                yield e
-
-    def __getitem__(self, key):
-        n = len(self)
-        if isinstance(key, slice):
-            start, stop, step = key.indices(n)
-            if step != 1:
-                return [self[i] for i in range(start, stop, step)]
-            # a slice stays a concatenation of (slices of) its parts: heads of rank lists keep the link to the cuts
-            # their fused rounds assembled (cut_select_qcqp.py:79 slices (A + B)[0:sel_size] before generating)
-            sub, off = [], 0
-            for p in self._parts:
-                lo, hi = max(start - off, 0), min(stop - off, len(p))
-                if lo < hi:
-                    sub.append(p[lo:hi])
-                off += len(p)
-            return _Concat(sub)
-        if key < 0:
-            key += n
-        off = 0
-        for p in self._parts:
-            if key - off < len(p):
-                return p[key - off]
-            off += len(p)
-        raise IndexError(key)
-
-    def __eq__(self, other):
-        return list(self) == list(other)
-
-    def __add__(self, other):
-        return _Concat(self._parts + [other])
-
-    def __radd__(self, other):
-        return _Concat([other] + self._parts)
-
-
-class _Binding(object):
-    """Device-side twin of one ``agg_list``: a Scorer handle holding its index sets."""
-
-    def __init__(self, scorer, agg_list, nb_vars, nb_lifted):
-        self.scorer, self.agg_list = scorer, agg_list
-        self.nb_vars, self.nb_lifted = nb_vars, nb_lifted
-        self.rank_serial = 0
-        self.point_token = None  # identifies the LP point whose scores the device holds
-        self.point_copy = None   # copy of the LP point last uploaded through this binding
-        self.point_serial = 0
-        self.scored = 0
-        self.serial = 0
-        self.set_arr = None      # [N, 5] index sets as arrays (vectorised entry building)
-        # a fused round begun on the scorer and not yet ended (sdpcut_round_csr_begin): (strat, head, LP point)
-        self._pending = None
-        # (binding, head) ranked by feasibility right after this one at the same LP point last time (the QCQP round's
-        # second cover, cut_select_qcqp.py:75-76): its round is begun together with this one's
-        self.follower = None
-        self.leader = None       # the binding this one follows (a follower never leads: no cycles)
-        self.wasted = 0          # speculative rounds nobody asked for
-        self.prioritised = False # its scorer's stream has been given the device's highest priority (a short list beside a long one)
-
-    point_fresh = False          # the cut pool's step has just uploaded the point a round is about to pass (point_arg)
-
-    def point_arg(self, vv):
-        """the point argument of a round call: None (keep the device's point) right after a pool step at this very point"""
-        fresh, self.point_fresh = self.point_fresh, False
-        if fresh and self.point_copy is not None and self.point_copy.shape == vv.shape and np.array_equal(vv, self.point_copy):
-            return None
-        return vv
-
-    def begin(self, strat, head, vv, flags):
-        token = self.scorer.round_csr_begin(strat, head, point=self.point_arg(vv))
-        self.note_point(vv, flags)
-        self._pending = (token, strat, head, self.point_copy)
-
-    @property
-    def pending(self):
-        """(strat, head, LP point) of the round begun through this binding and still pending on its scorer, or None"""
-        p = self._pending
-        if p is not None and self.scorer.pending is not p[0]:       # somebody ended or dropped it on the scorer
-            p = self._pending = None
-        return None if p is None else p[1:]
-
-    def end(self):
-        self._pending = None
-        return self.scorer.round_csr_end()
-
-    def drain(self):
-        """end a round nobody collected (the scorer's block and scores are about to be used for something else)"""
-        if self.pending is not None:
-            self.end()
-            self.wasted += 1
-            if self.leader is not None:                   # the pair is not a pattern after all
-                self.leader.follower, self.leader = None, None
-
-    def note_point(self, vv, scored=0):
-        """the device now holds LP point ``vv`` (and the measures ``scored`` at it)"""
-        self.point_serial += 1
-        self.point_token = self.point_serial
-        self.point_copy = np.array(vv, dtype=np.float64)
-        self.scored = scored
-
-    def agg_entry(self, idx):
-        if self.agg_list is not None:
-            e = self.agg_list[idx]
-            return e[0], e[1]
-        S, ks = self.sets_of(np.array([idx], dtype=np.int64))
-        k = int(ks[0])
-        s = [int(v) for v in S[0, :k]]
-        n = self.nb_vars
-        pos = [n * s[a] - s[a] * (s[a] + 1) // 2 + s[b] for a in range(k) for b in range(a, k)]
-        return s, pos
-
-    def sets_of(self, local_ids):
-        """(index sets [m, 5], sizes [m]) of candidates by local index: from the host arrays the
-        list was bound from, or fetched from the device for lists that only exist there."""
-        if self.set_arr is not None:
-            return self.set_arr[local_ids], self.ks[local_ids]
-        self.drain()
-        return self.scorer.get_candidates(local_ids)
-
-
-class AggArrays(Sequence):
-    """Array-backed ``agg_list``: the candidate records of cut_select_qp.py:529-540 built on
-    demand.  A Python list of 1.7e6 tuples (spar125-075-1, dim 4) takes minutes to build and
-    GBs to hold; the loop only ever reads ``[0]`` / ``[1]`` of the few thousand selected entries."""
-
-    def __init__(self, set_inds, ks, nb_vars, Q_arr=None):
-        self.set_inds = np.ascontiguousarray(set_inds, dtype=np.int32)
-        self.ks = np.ascontiguousarray(ks, dtype=np.int32)
-        self.nb_vars, self.Q_arr = nb_vars, Q_arr
-        self.serial = 0          # bumped by shuffle(): device bindings of the old order are stale
-
-    def __len__(self):
-        return self.ks.shape[0]
-
-    def shuffle(self):
-        """In-place random reordering, the array form of ``np.random.shuffle(agg_list)``
-        (cut_select_qp.py:636): ``np.random.permutation(N)`` draws the same permutation from the
-        global legacy generator as the list shuffle would (same seed -> same order)."""
-        perm = np.random.permutation(len(self))
-        self.set_inds = np.ascontiguousarray(self.set_inds[perm])
-        self.ks = np.ascontiguousarray(self.ks[perm])
-        self.serial += 1
-
-    def __getitem__(self, idx):
-        if isinstance(idx, slice):
-            return [self[i] for i in range(*idx.indices(len(self)))]
-        k = int(self.ks[idx])
-        s = [int(v) for v in self.set_inds[idx, :k]]
-        n = self.nb_vars
-        pos = [n * s[a] - s[a] * (s[a] + 1) // 2 + s[b] for a in range(k) for b in range(a, k)]
-        if self.Q_arr is None:
-            return (s, pos, None, None)
-        q = [self.Q_arr[p] for p in pos]
-        max_elem = k * abs(max(q, key=abs))
-        max_elem += 1 if not max_elem else 0
-        return (s, pos, tuple(np.divide(q, max_elem)), max_elem)
-
-
-class DeviceAgg(Sequence):
-    """``agg_list`` whose index sets were enumerated on the device and never came to the host
-    (``sdpcut_set_candidates_cover``): a length, and records fetched on demand for the few entries
-    somebody indexes.  Bound to the scorer that holds the list."""
-
-    def __init__(self, scorer, count, nb_vars, Q_arr=None):
-        self.scorer, self._n, self.nb_vars, self.Q_arr = scorer, int(count), nb_vars, Q_arr
-        self.serial = 0
-
-    def __len__(self):
-        return self._n
-
-    def __getitem__(self, idx):
-        if isinstance(idx, slice):
-            rng = range(*idx.indices(self._n))
-            S, ks = self.scorer.get_candidates(np.fromiter(rng, dtype=np.int64, count=len(rng)))
-            return [AggArrays(S[i:i + 1], ks[i:i + 1], self.nb_vars, self.Q_arr)[0] for i in range(len(rng))]
-        if idx < 0:
-            idx += self._n
-        if not 0 <= idx < self._n:
-            raise IndexError(idx)
-        S, ks = self.scorer.get_candidates(np.array([idx], dtype=np.int64))
-        return AggArrays(S, ks, self.nb_vars, self.Q_arr)[0]
-
-    def to_arrays(self):
-        """the whole list on the host (tests; the random strategy reorders a host copy)"""
-        S, ks = self.scorer.get_candidates(np.arange(self._n, dtype=np.int64))
-        return AggArrays(S, ks, self.nb_vars, self.Q_arr)
 
 
 class GpuCutSelectionMixin(object):
@@ -573,7 +157,7 @@ class GpuCutSelectionMixin(object):
         return b
 
     @staticmethod
-    def _gpu_point(b, vars_values, flags, cut_round=None):
+    def _gpu_point(b, vars_values, flags):
         """Make ``vars_values`` the device's LP point and score what ``flags`` asks for.
 
         The upload is skipped only when the point equals -- entry by entry -- the copy kept of the last one
@@ -581,8 +165,7 @@ class GpuCutSelectionMixin(object):
         itself is an asynchronous copy out of pinned staging, so a redundant one costs little.
         :meth:`invalidate_point` forces the next call to upload."""
         b.drain()
-        vv = vars_values if (isinstance(vars_values, np.ndarray) and vars_values.dtype == np.float64 and
-                             vars_values.flags.c_contiguous) else np.ascontiguousarray(vars_values, dtype=np.float64)
+        vv = _lp_point(vars_values)
         same = b.point_copy is not None and b.point_copy.shape == vv.shape and np.array_equal(vv, b.point_copy)
         if not same:
             b.scorer.set_point(vv)
@@ -623,14 +206,13 @@ class GpuCutSelectionMixin(object):
         sel_size = min(sel_size, N)
         if strat == -1:
             return self._gpu_figure8(b, vars_values, cut_round, sel_size)
-        flags = {1: _capi.EIG, 2: _capi.NN, 3: _capi.SDP, 4: _capi.EIG | _capi.NN}[strat]
+        flags = _MEASURES[strat]
         if N == 0:
             return []       # strat 4 included: sel_size is clamped to 0 and the reference falls through
         # head fetched eagerly: what the loop can consume (sel_size is only passed for strat 4;
         # for 1 / 2 the cap of :37 bounds it)
         head = min(N, sel_size if (strat == 4 and sel_size > 0) else _HEAD)
-        vv = vars_values if (isinstance(vars_values, np.ndarray) and vars_values.dtype == np.float64 and
-                             vars_values.flags.c_contiguous) else np.ascontiguousarray(vars_values, dtype=np.float64)
+        vv = _lp_point(vars_values)
         fused = None
         # which list is ranked by feasibility right after which at the same point: the QCQP loop's pair (cut_select_qcqp.py:64-76)
         last = getattr(self, "_gpu_last", None)
@@ -669,10 +251,10 @@ class GpuCutSelectionMixin(object):
             self._gpu_last = (b, b.point_copy)
         else:
             self._gpu_last = None
-            vv = self._gpu_point(b, vv, flags, cut_round)
+            vv = self._gpu_point(b, vv, flags)
             idx, score, total, new_strat, counters = b.scorer.rank(strat, sel_size, head)
         b.rank_serial += 1
-        rl = RankList(self, b, 1 if strat == 1 else 2, total, vv, idx, score, strat=strat, sel_size=sel_size, fused=fused)
+        rl = RankList(b, 1 if strat == 1 else 2, total, vv, idx, score, strat=strat, sel_size=sel_size, fused=fused)
         rl.counters = counters
         if strat == 4:
             # the reference divides by sel_size and swallows the ZeroDivisionError, falling
@@ -685,127 +267,57 @@ class GpuCutSelectionMixin(object):
         exact SDP optimum, ``p* max_elem - S max_elem`` -- and the reference's comparison of the two orderings in numpy
         (exact_sdp.figure8).  -> (rank_list by the estimated measure, overlap / sel_size, std_dev_exact, this_round_cuts)."""
         from . import exact_sdp
-        vv = self._gpu_point(b, vars_values, _capi.NN | _capi.SDP, cut_round)
+        vv = self._gpu_point(b, vars_values, _capi.NN | _capi.SDP)
         self._gpu_last = None
         _, nn = b.scorer.get_scores(eig=False)
         exact, _ = b.scorer.get_sdp_scores()
         order, overlap, std_dev_exact, rows = exact_sdp.figure8(nn, exact, cut_round, sel_size)
         b.rank_serial += 1
         # the whole list is on the host already: the rank list never goes back to the device (strategy 2's order, :688)
-        rl = RankList(self, b, 2, nn.shape[0], vv, order + b.scorer.base, nn[order], strat=2, sel_size=sel_size)
+        rl = RankList(b, 2, nn.shape[0], vv, order + b.scorer.base, nn[order], strat=2, sel_size=sel_size)
         return rl, overlap, std_dev_exact, rows
 
     # ------------------------------------------------------------------ a10 generation
-    def _gen_eigcuts_selected(self, strat, sel_size, rank_list, strong_only=False, vars_values=None):
-        """Eigen-cuts of the first ``sel_size`` ranked candidates, appended to
-        ``self._my_prob.linear_constraints`` (cut_select_qp.py:705-755)."""
-        if int(self.cuts_per_set) > 1 and sel_size > 0 and len(rank_list) > 0:
-            return self._gen_eigcuts_multi(strat, sel_size, rank_list, strong_only, vars_values)
-        sel_size = min(sel_size, len(rank_list))
-        opt_sel, feas_sel = strat in (2, 3, 4, -1), strat == 1
-        pair = self._sparse_pair or _default_sparse_pair()
-        if sel_size <= 0:
-            self._my_prob.linear_constraints.add(lin_expr=[], rhs=[], senses=[])
-            return 0
-        # (binding, candidate indices, point) groups in list order; most lists have one group
-        groups, vv = None, vars_values
-        if isinstance(rank_list, _Concat):
-            # (A + B)[0:sel_size] of the QCQP round: the cuts of each part, in list order, if every part still has them
-            blocks, left = [], sel_size
-            for part in rank_list._parts:
-                if left <= 0:
-                    break
-                rl = part.parent if isinstance(part, RankListHead) else part
-                csr = None
-                if isinstance(rl, RankList):
-                    csr = rl.fused_rows(min(left, len(part)), strong_only=opt_sel and strong_only and rl._kind != 1,
-                                        vars_values=vars_values if rl._kind == 1 else None)
-                if csr is None:
-                    blocks = None
-                    break
-                blocks.append(csr)
-                left -= min(left, len(part))
-            if blocks is not None:
-                return sum(self._gpu_add_csr(c, pair) for c in blocks)
-        if isinstance(rank_list, RankListHead):
-            rank_list, sel_size = rank_list.parent, min(sel_size, len(rank_list))
-        if isinstance(rank_list, RankList):
-            csr = rank_list.fused_rows(sel_size, strong_only=opt_sel and strong_only,
-                                       vars_values=vars_values if feas_sel else None)
-            if csr is not None:
-                return self._gpu_add_csr(csr, pair)
-            idx, vv = rank_list.ids(sel_size), rank_list._vv
-            if opt_sel and strong_only:                       # :725-726
-                stop = np.nonzero(rank_list.scores(sel_size) <= 0)[0]
-                if stop.size:
-                    idx = idx[:stop[0]]
-            groups = [(rank_list._b, idx)]
-        elif strat == 5 and rank_list is self._agg_list:
-            # random selection (:729-732): the shuffled list itself, entries 0 .. sel_size-1
-            groups = [(self._gpu_bind(), np.arange(sel_size, dtype=np.int64))]
-        else:
-            entries = list(rank_list[0:sel_size])
-            if opt_sel:
-                if strong_only:
-                    cut = next((p for p, e in enumerate(entries) if e[1] <= 0), len(entries))
-                    entries = entries[:cut]
-                groups = [(self._gpu_bind(), np.array([e[0] for e in entries], dtype=np.int64))]
-            elif feas_sel and all(isinstance(e, FeasEntry) and e.binding is not None for e in entries):
-                # runs of entries of one candidate list (the QCQP feasibility round concatenates the
-                # lists of two covers, cut_select_qcqp.py:79)
-                groups = []
-                for e in entries:
-                    if groups and groups[-1][0] is e.binding:
-                        groups[-1][1].append(e.agg_idx)
-                    else:
-                        groups.append((e.binding, [e.agg_idx]))
-                groups = [(g, np.array(ix, dtype=np.int64)) for g, ix in groups]
-            if groups is None:
-                return self._gen_from_entries(entries, feas_sel, vars_values, pair)
-        if not opt_sel or vv is None:
-            vv = vars_values
-        parts = []
-        for g, idx in groups:
-            if idx.size:
-                self._gpu_point(g, vv, 0)
-                parts.append(g.scorer.cut_rows(idx - g.scorer.base))
-        if not parts:
-            self._my_prob.linear_constraints.add(lin_expr=[], rhs=[], senses=[])
-            return 0
-        lam, coef, rhs, cols, ks = (np.concatenate(a) for a in zip(*parts)) if len(parts) > 1 else parts[0]
-        keep = np.nonzero(lam < _THRES_NEG_EIGVAL)[0]          # :743
+    def _gpu_pair(self):
+        """the per-row object of a reference-style row store: ``self._sparse_pair``, else the installed LP library's"""
+        return self._sparse_pair or _default_sparse_pair()
+
+    def _gpu_add_csr(self, csr, pair=None, copy=True, integral=False):
+        """Hand a block of assembled cuts ``(indptr, indices, values, rhs)`` to the LP; the one place that knows the two kinds of
+        row store: as arrays when the store takes them (``add_csr``), else as the reference's per-row objects
+        (cut_select_qp.py:747-754) with Python int indices and float values.  ``csr=None`` hands over nothing, the way the
+        reference adds its empty lists.  copy: the arrays are views of a scorer's pinned block, which the next round overwrites, so
+        the store gets copies; a caller that built the arrays itself passes False.  integral: the per-row objects carry integer
+        coefficients and right-hand sides (the triangle rows, :833-836).  -> number of rows."""
         store = self._my_prob.linear_constraints
+        if csr is None:
+            store.add(lin_expr=[], rhs=[], senses=[])
+            return 0
+        indptr, ind, val, rhs = csr
+        r = rhs.shape[0]
         if hasattr(store, "add_csr"):
-            # batched assembly (SURVEY 8 f row 4): the padded device rows become one CSR block with
-            # array operations, no Python object per cut
-            indptr, ind, val = rows_to_csr(coef[keep], cols[keep], ks[keep])
-            store.add_csr(indptr, ind, val, rhs[keep], "G")
-            return int(keep.size)
-        rows, rhs_out = [], []
-        for c in keep:
-            w = int(ks[c]) * (int(ks[c]) + 3) // 2
-            rows.append(pair(ind=cols[c, :w].tolist(), val=coef[c, :w].tolist()))
-            rhs_out.append(float(rhs[c]))
-        store.add(lin_expr=rows, rhs=rhs_out, senses=["G"] * len(rows))
-        return len(rows)
+            if copy:
+                indptr, ind, val, rhs = np.array(indptr), np.array(ind), np.array(val), np.array(rhs)      # (int32 index arrays as the device wrote them)
+            store.add_csr(indptr, ind, val, rhs, "G")
+            return r
+        pair = pair or self._gpu_pair()
+        ptr, ind, val, rhs = indptr.tolist(), ind.tolist(), val.tolist(), rhs.tolist()
+        if integral:
+            val, rhs = [int(v) for v in val], [int(v) for v in rhs]
+        store.add(lin_expr=[pair(ind=ind[ptr[c]:ptr[c + 1]], val=val[ptr[c]:ptr[c + 1]]) for c in range(r)], rhs=rhs, senses=["G"] * r)
+        return r
 
-    # ------------------------------------------------------------------ all violated eigen-cuts of a selected set
-    def _multi_log_add(self, **rec):
-        if getattr(self, "multi_log", None) is None:
-            self.multi_log = []
-        self.multi_log.append(rec)
-
-    def _multi_groups(self, strat, sel_size, rank_list, strong_only):
+    def _rank_groups(self, strat, sel_size, rank_list, strong_only):
         """The first ``sel_size`` entries of a rank list as runs of (binding, global candidate ids) in list order, or None where an
-        entry cannot be traced to a bound candidate."""
-        opt_sel = strat in (2, 3, 4, -1)
+        entry cannot be traced to a bound candidate.  The one walk from what the loop hands to cut generation -- a RankList, its
+        head, a concatenation of such (cut_select_qcqp.py:79), the shuffled list of strategy 5, plain entry lists -- to what the
+        device can be asked about."""
+        opt_sel = strat in _OPT_STRATS
 
         def of_rank_list(rl, count, cut_at_nonpositive):
             idx = np.asarray(rl.ids(count), dtype=np.int64)
             if cut_at_nonpositive:                            # cut_select_qp.py:725-726
-                stop = np.nonzero(rl.scores(count) <= 0)[0]
-                if stop.size:
-                    idx = idx[:stop[0]]
+                idx = idx[:strong_prefix(rl.scores(count), count)]
             return rl._b, idx
 
         def of_entries(entries, as_opt):
@@ -816,6 +328,7 @@ class GpuCutSelectionMixin(object):
                 return [(self._gpu_bind(), np.array([e[0] for e in entries], dtype=np.int64))]
             if not all(isinstance(e, FeasEntry) and e.binding is not None for e in entries):
                 return None
+            # runs of entries of one candidate list (the QCQP feasibility round concatenates the lists of two covers)
             runs = []
             for e in entries:
                 if runs and runs[-1][0] is e.binding:
@@ -846,8 +359,70 @@ class GpuCutSelectionMixin(object):
         if isinstance(rank_list, RankList):
             return [of_rank_list(rank_list, sel_size, opt_sel and strong_only)]
         if strat == 5 and rank_list is self._agg_list:
-            return [(self._gpu_bind(), np.arange(min(sel_size, len(rank_list)), dtype=np.int64) + self._gpu_bind().scorer.base)]
+            # random selection (:729-732): the shuffled list itself, entries 0 .. sel_size-1
+            b = self._gpu_bind()
+            return [(b, np.arange(min(sel_size, len(rank_list)), dtype=np.int64) + b.scorer.base)]
         return of_entries(list(rank_list[0:sel_size]), opt_sel)
+
+    def _fused_blocks(self, strat, sel_size, rank_list, strong_only, vars_values):
+        """The cuts of the first ``sel_size`` entries as the blocks their fused rounds assembled, in list order: one of a rank
+        list or its head, one per part of ``(A + B)[0:sel_size]`` of the QCQP round; None unless every part still has them."""
+        mixed = isinstance(rank_list, _Concat)
+        blocks, left = [], sel_size
+        for part in (rank_list._parts if mixed else [rank_list]):
+            if left <= 0:
+                break
+            take = min(left, len(part))
+            rl = part.parent if isinstance(part, RankListHead) else part
+            if not isinstance(rl, RankList):
+                return None
+            feas = rl._kind == 1 if mixed else strat == 1
+            csr = rl.fused_rows(take, strong_only=strong_only and strat in _OPT_STRATS and not feas, vars_values=vars_values if feas else None)
+            if csr is None:
+                return None
+            blocks.append(csr)
+            left -= take
+        return blocks
+
+    def _gen_eigcuts_selected(self, strat, sel_size, rank_list, strong_only=False, vars_values=None):
+        """Eigen-cuts of the first ``sel_size`` ranked candidates, appended to
+        ``self._my_prob.linear_constraints`` (cut_select_qp.py:705-755)."""
+        if int(self.cuts_per_set) > 1 and sel_size > 0 and len(rank_list) > 0:
+            return self._gen_eigcuts_multi(strat, sel_size, rank_list, strong_only, vars_values)
+        sel_size = min(sel_size, len(rank_list))
+        if sel_size <= 0:
+            return self._gpu_add_csr(None)
+        # the rows the fused round assembled, if its block still has them
+        blocks = self._fused_blocks(strat, sel_size, rank_list, strong_only, vars_values)
+        if blocks is not None:
+            return sum(self._gpu_add_csr(c) for c in blocks)
+        # else the candidates' rows from the device, else (entries that name no bound candidate) the generic path
+        groups = self._rank_groups(strat, sel_size, rank_list, strong_only)
+        if groups is None:
+            return self._gen_from_entries(list(rank_list[0:sel_size]), strat == 1, vars_values, self._gpu_pair())
+        # optimality cuts at the point the list was ranked at, feasibility cuts at the caller's
+        rl = rank_list.parent if isinstance(rank_list, RankListHead) else rank_list
+        vv = rl._vv if strat in _OPT_STRATS and isinstance(rl, RankList) else None
+        if vv is None:
+            vv = vars_values
+        parts = []
+        for g, idx in groups:
+            if idx.size:
+                self._gpu_point(g, vv, 0)
+                parts.append(g.scorer.cut_rows(idx - g.scorer.base))
+        if not parts:
+            return self._gpu_add_csr(None)
+        lam, coef, rhs, cols, ks = (np.concatenate(a) for a in zip(*parts)) if len(parts) > 1 else parts[0]
+        keep = np.nonzero(lam < _THRES_NEG_EIGVAL)[0]          # :743
+        # batched assembly (SURVEY 8 f row 4): the padded device rows become one CSR block with
+        # array operations, no Python object per cut
+        return self._gpu_add_csr(rows_to_csr(coef[keep], cols[keep], ks[keep]) + (rhs[keep],), copy=False)
+
+    # ------------------------------------------------------------------ all violated eigen-cuts of a selected set
+    def _multi_log_add(self, **rec):
+        if getattr(self, "multi_log", None) is None:
+            self.multi_log = []
+        self.multi_log.append(rec)
 
     def _gen_eigcuts_multi(self, strat, sel_size, rank_list, strong_only, vars_values):
         """_gen_eigcuts_selected with ``cuts_per_set`` > 1: every selected set offers up to that many eigen-cuts
@@ -855,7 +430,7 @@ class GpuCutSelectionMixin(object):
         (``cuts_row_quota = "sets"``: the first ``cuts_per_set * sel_size``).  One record per call goes to ``self.multi_log``."""
         m = int(self.cuts_per_set)
         quota = int(sel_size) * (m if self.cuts_row_quota == "sets" else 1)
-        groups = self._multi_groups(strat, min(sel_size, len(rank_list)), rank_list, strong_only)
+        groups = self._rank_groups(strat, min(sel_size, len(rank_list)), rank_list, strong_only)
         if groups is None:
             raise NotImplementedError("cuts_per_set > 1 needs rank lists whose entries name candidates bound to the device")
         vv = vars_values
@@ -870,11 +445,9 @@ class GpuCutSelectionMixin(object):
                 n = np.diff(rp)
                 ent = np.repeat(np.arange(idx.shape[0]), n)
                 coef.append(co), rhs.append(rh), cols.append(cl[ent]), ks.append(kk[ent]), per_entry.append(n)
-        store = self._my_prob.linear_constraints
         if not coef:
-            store.add(lin_expr=[], rhs=[], senses=[])
             self._multi_log_add(strat=strat, entries=0, entries_used=0, rows=0, offered=0, offered_hist=[0] * (m + 1), quota=quota, quota_hit=False)
-            return 0
+            return self._gpu_add_csr(None)
         coef, rhs, cols, ks, per_entry = (np.concatenate(a) for a in (coef, rhs, cols, ks, per_entry))
         offered = int(coef.shape[0])
         rows = min(offered, quota)
@@ -882,18 +455,7 @@ class GpuCutSelectionMixin(object):
         self._multi_log_add(strat=strat, entries=int(per_entry.shape[0]), entries_used=int(np.count_nonzero((per_entry > 0) & (starts < rows))),
                             rows=rows, offered=offered, offered_hist=np.bincount(per_entry, minlength=m + 1).tolist(), quota=quota,
                             quota_hit=offered > quota)
-        coef, rhs, cols, ks = coef[:rows], rhs[:rows], cols[:rows], ks[:rows]
-        if hasattr(store, "add_csr"):
-            indptr, ind, val = rows_to_csr(coef, cols, ks)
-            store.add_csr(indptr, ind, val, rhs, "G")
-            return rows
-        pair = self._sparse_pair or _default_sparse_pair()
-        out = []
-        for c in range(rows):
-            w = int(ks[c]) * (int(ks[c]) + 3) // 2
-            out.append(pair(ind=cols[c, :w].tolist(), val=coef[c, :w].tolist()))
-        store.add(lin_expr=out, rhs=rhs.tolist(), senses=["G"] * rows)
-        return rows
+        return self._gpu_add_csr(rows_to_csr(coef[:rows], cols[:rows], ks[:rows]) + (rhs[:rows],), copy=False)
 
     # ------------------------------------------------------------------ dense eigen-cuts (strategy 0)
     def _gpu_dense_scorer(self):
@@ -909,35 +471,14 @@ class GpuCutSelectionMixin(object):
         """One fully dense eigen-cut per negative eigenvalue (but the largest) of the whole lifted matrix at ``vars_values``,
         appended to the LP (cut_select_qp.py:757-786); decomposition and rows on the device (sdpcut_dense_round).
         -> number of cuts."""
-        r = self._gpu_dense_scorer().dense_round(np.ascontiguousarray(vars_values, dtype=np.float64))
-        nb, cols, values, rhs = r["n_rows"], r["cols"], r["values"], r["rhs"]
-        store = self._my_prob.linear_constraints
-        if hasattr(store, "add_csr"):
-            # (copies: the arrays are views of the scorer's pinned block, which the next round overwrites)
-            store.add_csr(np.arange(nb + 1, dtype=np.int64) * cols.shape[0], np.tile(cols, nb), values.reshape(-1).copy(), rhs.copy(), "G")
-            return nb
-        pair = self._sparse_pair or _default_sparse_pair()
-        ind = cols.tolist()
-        store.add(lin_expr=[pair(ind=ind, val=values[c].tolist()) for c in range(nb)], rhs=rhs.tolist(), senses=["G"] * nb)
-        return nb
+        r = self._gpu_dense_scorer().dense_round(_lp_point(vars_values))
+        nb, cols = r["n_rows"], r["cols"]
+        # (values and rhs are copied: they are views of the scorer's pinned block, which the next round overwrites)
+        return self._gpu_add_csr((np.arange(nb + 1, dtype=np.int64) * cols.shape[0], np.tile(cols, nb), r["values"].reshape(-1).copy(),
+                                  r["rhs"].copy()), copy=False)
 
     # the reference's loop reaches it through the name-mangled private name (cut_select_qp.py:166)
     _CutSolver__gen_dense_eigcuts = _gen_dense_eigcuts
-
-    def _gpu_add_csr(self, csr, pair):
-        """Hand a block of assembled cuts to the LP: as arrays when the row store takes them (``add_csr``), else as the
-        reference's per-row objects (cut_select_qp.py:747-754).  The arrays are copied: they are views of the scorer's
-        pinned block, which the next round overwrites."""
-        indptr, ind, val, rhs = csr
-        r = rhs.shape[0]
-        store = self._my_prob.linear_constraints
-        if hasattr(store, "add_csr"):
-            store.add_csr(np.array(indptr), np.array(ind), np.array(val), np.array(rhs), "G")      # (int32 index arrays as the device wrote them)
-            return r
-        ptr, ind, val = indptr.tolist(), ind.tolist(), val.tolist()
-        rows = [pair(ind=ind[ptr[c]:ptr[c + 1]], val=val[ptr[c]:ptr[c + 1]]) for c in range(r)]
-        store.add(lin_expr=rows, rhs=rhs.tolist(), senses=["G"] * r)
-        return r
 
     def separate_points(self, strat, points, sel_size):
         """One separation round at EACH of several LP points of the bound instance in one device call (sdpcut_round_csr_points):
@@ -1019,14 +560,12 @@ class GpuCutSelectionMixin(object):
         """Separate the violated triangle inequalities at the current point, rank them by
         (density, violation) and append the selected ones (cut_select_qp.py:824-863)."""
         sc, tri, L, n = self._gpu_tri, self._gpu_tri_triples, self._nb_lifted, self._nb_vars
-        sc.set_point(np.ascontiguousarray(vars_values, dtype=np.float64))
+        sc.set_point(_lp_point(vars_values))
         ent, vio, nb_viol = sc.tri_separate(self._TRI_CUTS_PER_ROUND_MAX)
         nb_tri_cuts = max(min(self._TRI_CUTS_PER_ROUND_MIN, int(np.floor(sel_size * nb_viol))),
                           min(self._TRI_CUTS_PER_ROUND_MAX, nb_viol))                       # :844-845
-        pair = self._sparse_pair or _default_sparse_pair()
         if nb_tri_cuts <= 0:
-            self._my_prob.linear_constraints.add(lin_expr=[], rhs=[], senses=[])
-            return 0
+            return self._gpu_add_csr(None)
         # the rows as ONE CSR block built with array operations (the per-row Python loop of :847-861 cost ~3 us per cut, 30 ms for
         # the 10 000 cuts of a round -- two orders of magnitude more than the device took to find them): inequality c of triple
         # (a, b, d) has columns X_ab, X_ad, X_bd and x_(a|b|d)[c]  (c < 3: 4 non-zeros, rhs 0) or x_a, x_b, x_d (c = 3: 6, rhs -1)
@@ -1053,16 +592,8 @@ class GpuCutSelectionMixin(object):
             val[p4 + j] = v4[:, j]
         for j, v in enumerate((1.0, 1.0, 1.0, -1.0, -1.0, -1.0)):
             val[p6 + j] = v
-        rhs = np.where(four, 0.0, -1.0)
-        store = self._my_prob.linear_constraints
-        if hasattr(store, "add_csr"):
-            store.add_csr(indptr, ind, val, rhs, "G")
-            return int(e.shape[0])
-        ptr, ind_l = indptr.tolist(), ind.tolist()
-        val_l = [int(v) for v in val.tolist()]                    # the reference hands integer coefficients (:833-836)
-        rows = [pair(ind=ind_l[ptr[r]:ptr[r + 1]], val=val_l[ptr[r]:ptr[r + 1]]) for r in range(e.shape[0])]
-        store.add(lin_expr=rows, rhs=[int(v) for v in rhs.tolist()], senses=["G"] * len(rows))
-        return len(rows)
+        # (built here: no second copy; the reference hands integer coefficients and right-hand sides, :833-836)
+        return self._gpu_add_csr((indptr, ind, val, np.where(four, 0.0, -1.0)), copy=False, integral=True)
 
     # the reference reaches these two through name-mangled private names inside class CutSolver
     _CutSolver__preprocess_triangle_ineq = _preprocess_triangle_ineq
@@ -1122,6 +653,79 @@ class CutSolver(GpuCutSelectionMixin):
 
     # ------------------------------------------------------------------ rounds without CPLEX (SURVEY 8 f row 2)
     _CONVERGENCE_TOL = 10 ** (-3)         # cut_select_qp.py:29
+
+    # the separation step between two LP solves of cut_select_algo, one function per kind of round; they read the run's
+    # settings from self._run and return the round's counts
+    def _round_counts(self, sdp, point):
+        """the counts of a round that added ``sdp`` eigen-cuts: the triangle inequalities are separated behind them"""
+        run = self._run
+        return {"sdp": sdp, "tri": self._separate_and_add_triangle(run.sel_size, point) if run.triangle_on else 0}
+
+    def _round_plain(self, round_no, point):
+        """selection, then generation, as the reference's loop calls them (cut_select_qp.py:165-182)"""
+        run = self._run
+        cur = run.strat
+        if cur == 0:
+            return self._round_counts(self._gen_dense_eigcuts(vars_values=point), point)
+        picked = self._sel_eigcut_by_ordering_on_measure(cur, point, round_no, **({"sel_size": run.quota} if cur in (4, -1) else {}))
+        if cur == 4 and isinstance(picked, tuple):
+            run.strat, picked = picked            # the switch takes effect next round (:181 vs :188)
+        if cur == -1:                             # :173-179
+            picked, round_stats, round_std_dev, round_all_cuts = picked
+            run.figure8[0].append(round_stats)
+            run.figure8[1].append(round_std_dev)
+            run.figure8[2].extend(round_all_cuts)
+        sdp = self._gen_eigcuts_selected(cur, run.quota, picked, strong_only=run.strong_only, vars_values=point)
+        return self._round_counts(sdp, point)
+
+    def _round_one_call(self, round_no, point):
+        """a round whose ranking and assembled cuts come from ONE library call: through the parallelism filter (``max_parallel``),
+        or with all violated eigen-cuts of the selected sets (``cuts_per_set`` > 1)"""
+        run = self._run
+        cur = run.strat
+        if cur == 5 or run.quota < 1:
+            return self._round_plain(round_no, point)     # (strategy 5: _gen_eigcuts_selected sees self.cuts_per_set)
+        multi = run.m_cuts > 1
+        b = self._gpu_bind()
+        b.drain()
+        vv = _lp_point(point)
+        if multi:
+            r = b.scorer.round_csr_multi(b.point_arg(vv), cur, run.quota, run.m_cuts, row_quota=run.row_quota)
+        else:
+            pool = int(min(max(int(run.pool_factor * run.quota), run.quota), _capi.DIVERSE_MAX_POOL))
+            r = b.scorer.round_csr_diverse(b.point_arg(vv), cur, run.quota, run.max_parallel, pool_size=pool)
+        b.note_point(vv, _MEASURES[cur])
+        b.rank_serial += 1
+        self._gpu_last = None
+        if cur == 4:
+            run.strat = r["new_strat"]            # the switch takes effect next round (:181 vs :188)
+        entries = int(r["idx"].shape[0])
+        csr = csr_prefix(r, strong_prefix(r["score"], entries) if run.strong_only and cur in _OPT_STRATS else entries)      # :725-726
+        if multi:
+            rows = csr[3].shape[0]
+            used = r["row_entry"][:rows]
+            self._multi_log_add(round=round_no, strat=cur, entries=entries, entries_used=int(np.unique(used).shape[0]),
+                                last_entry=int(used[-1]) + 1 if rows else 0, rows=rows, n_neg_hist=np.bincount(r["n_neg"], minlength=6).tolist(),
+                                quota=int(r["row_cap"]), quota_hit=bool(r["quota_hit"]))
+        else:
+            self.diverse_log.append(dict(r["info"], round=round_no, strat=cur, accepted=entries))
+        return self._round_counts(self._gpu_add_csr(csr), point)
+
+    def _round_pooled(self, round_no, point):
+        """the pool's step first (its upload of the point serves the round), then the round; its rows join the pool"""
+        run = self._run
+        ploop = run.pool
+        vv = _lp_point(point)
+        b = self._gpu_bind() if run.strat != 5 else None
+        if b is not None:
+            b.drain()
+        ploop.step(vv, run.pool_return)
+        if b is not None and b.scorer is ploop.pool:
+            b.note_point(vv, 0)
+            b.point_fresh = True
+        counts = run.unpooled(round_no, point)
+        ploop.adopt()
+        return dict(counts, pool_enter=ploop.log[-1]["enter"], pool_leave=ploop.log[-1]["leave"])
 
     def cut_select_algo(self, filename, dim, sel_size, strat=2, nb_rounds_cuts=20, term_on=False,
                         triangle_on=False, strong_only=False, max_subs=_THRES_MAX_SUBS, on_round=None, plots=False, sol=0,
@@ -1217,85 +821,14 @@ class CutSolver(GpuCutSelectionMixin):
         t_model = clock() - t_model
         if triangle_on:
             self._preprocess_triangle_ineq()
-        state = {"strat": strat}
         rounds_stats, round_std_devs, rounds_all_cuts = [], [], []      # figure 8 (:144)
         if strat == 0:      # the cover's scorer already holds the instance
             self._gpu_dense_sc, self._gpu_dense_key = sc, (self._nb_vars, id(self._Q_arr))
-
-        def separate_diverse(round_no, point):
-            """a round through the parallelism filter: ranking, walk and assembled cuts in one library call"""
-            cur = state["strat"]
-            sdp = 0
-            if quota >= 1:
-                b = self._gpu_bind()
-                b.drain()
-                vv = np.ascontiguousarray(point, dtype=np.float64)
-                pool = int(min(max(int(pool_factor * quota), quota), _capi.DIVERSE_MAX_POOL))
-                r = b.scorer.round_csr_diverse(b.point_arg(vv), cur, quota, max_parallel, pool_size=pool)
-                b.note_point(vv, {1: _capi.EIG, 2: _capi.NN, 4: _capi.EIG | _capi.NN}[cur])
-                b.rank_serial += 1
-                self._gpu_last = None
-                self.diverse_log.append(dict(r["info"], round=round_no, strat=cur, accepted=int(r["idx"].shape[0])))
-                if cur == 4:
-                    state["strat"] = r["new_strat"]       # the switch takes effect next round (:181 vs :188)
-                rows = int(r["rhs"].shape[0])             # every accepted entry has its row
-                if strong_only and cur in (2, 4):         # :725-726
-                    stop = np.flatnonzero(r["score"][:rows] <= 0)
-                    if stop.size:
-                        rows = int(stop[0])
-                nnz = int(r["indptr"][rows])
-                sdp = self._gpu_add_csr((r["indptr"][:rows + 1], r["indices"][:nnz], r["values"][:nnz], r["rhs"][:rows]),
-                                        self._sparse_pair or _default_sparse_pair())
-            else:
-                self._my_prob.linear_constraints.add(lin_expr=[], rhs=[], senses=[])
-            return {"sdp": sdp, "tri": self._separate_and_add_triangle(sel_size, point) if triangle_on else 0}
-
-        def separate_multi(round_no, point):
-            """a round with all violated eigen-cuts of the selected sets: ranking, decompositions and assembled cuts in one library call"""
-            cur = state["strat"]
-            if cur == 5 or quota < 1:
-                return separate(round_no, point)          # (strategy 5: _gen_eigcuts_selected sees self.cuts_per_set)
-            b = self._gpu_bind()
-            b.drain()
-            vv = np.ascontiguousarray(point, dtype=np.float64)
-            r = b.scorer.round_csr_multi(b.point_arg(vv), cur, quota, m_cuts, row_quota=row_quota)
-            b.note_point(vv, {1: _capi.EIG, 2: _capi.NN, 3: _capi.SDP, 4: _capi.EIG | _capi.NN}[cur])
-            b.rank_serial += 1
-            self._gpu_last = None
-            if cur == 4:
-                state["strat"] = r["new_strat"]           # the switch takes effect next round (:181 vs :188)
-            rows = int(r["rhs"].shape[0])
-            if strong_only and cur in (2, 3, 4):          # :725-726 -- row_entry ascends: the rows of the first entries are a prefix
-                stop = np.flatnonzero(r["score"] <= 0)
-                if stop.size:
-                    rows = int(np.searchsorted(r["row_entry"], int(stop[0])))
-            nnz = int(r["indptr"][rows])
-            used = int(r["row_entry"][rows - 1]) + 1 if rows else 0
-            self._multi_log_add(round=round_no, strat=cur, entries=int(r["idx"].shape[0]), entries_used=int(np.unique(r["row_entry"][:rows]).shape[0]),
-                                last_entry=used, rows=rows, n_neg_hist=np.bincount(r["n_neg"], minlength=6).tolist(),
-                                quota=int(r["row_cap"]), quota_hit=bool(r["quota_hit"]))
-            sdp = self._gpu_add_csr((r["indptr"][:rows + 1], r["indices"][:nnz], r["values"][:nnz], r["rhs"][:rows]),
-                                    self._sparse_pair or _default_sparse_pair())
-            return {"sdp": sdp, "tri": self._separate_and_add_triangle(sel_size, point) if triangle_on else 0}
-
-        def separate(round_no, point):
-            cur = state["strat"]
-            if cur == 0:
-                sdp = self._gen_dense_eigcuts(vars_values=point)
-                return {"sdp": sdp, "tri": self._separate_and_add_triangle(sel_size, point) if triangle_on else 0}
-            picked = self._sel_eigcut_by_ordering_on_measure(cur, point, round_no, **({"sel_size": quota} if cur in (4, -1) else {}))
-            if cur == 4 and isinstance(picked, tuple):
-                state["strat"], picked = picked       # the switch takes effect next round (:181 vs :188)
-            if cur == -1:                             # :173-179
-                picked, round_stats, round_std_dev, round_all_cuts = picked
-                rounds_all_cuts.extend(round_all_cuts)
-                rounds_stats.append(round_stats)
-                round_std_devs.append(round_std_dev)
-            sdp = self._gen_eigcuts_selected(cur, quota, picked, strong_only=strong_only, vars_values=point)
-            tri = self._separate_and_add_triangle(sel_size, point) if triangle_on else 0
-            return {"sdp": sdp, "tri": tri}
-
-        sep_fn = separate_multi if m_cuts > 1 else (separate if max_parallel is None else separate_diverse)
+        # what the round functions read, and the strategy they update (the combined strategy's switch)
+        self._run = run = SimpleNamespace(strat=strat, quota=quota, sel_size=sel_size, triangle_on=triangle_on, strong_only=strong_only,
+                                          max_parallel=max_parallel, pool_factor=pool_factor, m_cuts=m_cuts, row_quota=row_quota,
+                                          figure8=(rounds_stats, round_std_devs, rounds_all_cuts))
+        sep_fn = self._round_plain if m_cuts == 1 and max_parallel is None else self._round_one_call
         if pooled:
             from . import cutpool
             # capacity = the most rows the run can add: there is no eviction under pressure
@@ -1306,21 +839,8 @@ class CutSolver(GpuCutSelectionMixin):
             sc.pool_create(capacity)
             ploop = cutpool.PoolLoop(lp, sc, pool_par[2], pool_par[3], pool_par[0], pool_par[1])
             self.pool_log, self.pool_loop = ploop.log, ploop
-            inner_fn = sep_fn
-
-            def sep_fn(round_no, point):
-                """the pool's step first (its upload of the point serves the round), then the round; its rows join the pool"""
-                vv = np.ascontiguousarray(point, dtype=np.float64)
-                b = self._gpu_bind() if state["strat"] != 5 else None
-                if b is not None:
-                    b.drain()
-                ploop.step(vv, quota if pool_return is None else pool_par[4])
-                if b is not None and b.scorer is sc:
-                    b.note_point(vv, 0)
-                    b.point_fresh = True
-                counts = inner_fn(round_no, point)
-                ploop.adopt()
-                return dict(counts, pool_enter=ploop.log[-1]["enter"], pool_leave=ploop.log[-1]["leave"])
+            run.pool, run.pool_return, run.unpooled = ploop, quota if pool_return is None else pool_par[4], sep_fn
+            sep_fn = self._round_pooled
         keep_attr = (self.cuts_per_set, self.cuts_row_quota)
         if m_cuts > 1:
             self.cuts_per_set, self.cuts_row_quota = m_cuts, row_quota
@@ -1363,23 +883,27 @@ class CutSolverQCQP(CutSolver):
         self._agg_list = agg_list                            # :78
         n_obj = min(len(comb_obj), sel_size)
         rank_list = comb_obj[0:n_obj] + feas_cons[0:sel_size - n_obj]      # == (A + B)[0:sel_size], :79
-        if int(self.cuts_per_set) > 1 and strat_old != 1:
-            # all violated eigen-cuts: ONE walk over the concatenated head, so that the row quota is applied in list order
-            nb_opt_cuts = (comb_obj.count_above(_BIG_M) if isinstance(comb_obj, RankList) else
-                           int(np.count_nonzero(np.array([e[1] for e in comb_obj]) > _BIG_M))) if len(comb_obj) else 0
-            return strat, rank_list, self._gen_eigcuts_selected(strat_old, sel_size, rank_list, vars_values=vars_values), nb_opt_cuts
         if strat_old == 1:
             nb = self._gen_eigcuts_selected(strat_old, sel_size, rank_list, vars_values=vars_values)
             return strat, rank_list, nb, 0
         # :85-92 counters, from the device arrays instead of a Python loop over N tuples
         nb_opt_cuts = (comb_obj.count_above(_BIG_M) if isinstance(comb_obj, RankList) else
                        int(np.count_nonzero(np.array([e[1] for e in comb_obj]) > _BIG_M))) if len(comb_obj) else 0
+        if int(self.cuts_per_set) > 1:
+            # all violated eigen-cuts: ONE walk over the concatenated head, so that the row quota is applied in list order
+            return strat, rank_list, self._gen_eigcuts_selected(strat_old, sel_size, rank_list, vars_values=vars_values), nb_opt_cuts
         nb_cuts_combined = n_obj      # :90-92 counts the entries whose first field is an int: the objective cover's (optimality / combined entries)
         rest = sel_size - nb_cuts_combined
         nb_a = self._gen_eigcuts_selected(1, rest, feas_cons[0:rest], vars_values=vars_values)
         nb_b = self._gen_eigcuts_selected(strat_old, nb_cuts_combined, comb_obj[0:nb_cuts_combined],
                                           vars_values=vars_values)
         return strat, rank_list, nb_a + nb_b, nb_opt_cuts
+
+    def _round_qcqp(self, round_no, point):
+        """the separation step between two LP solves of the QCQP loop"""
+        run = self._run
+        run.strat, _, sdp, opt = self.select_and_generate_round(run.strat, point, round_no, run.quota, *run.covers)
+        return {"sdp": sdp, "opt": opt}
 
     def cut_select_algo(self, filename, dim, sel_size=0.1, strat=2, nb_rounds_cuts=20, cuts_per_set=1):
         """Cutting-plane rounds on a QCQP in OSiL format, same arguments and return tuple as the
@@ -1414,18 +938,12 @@ class CutSolverQCQP(CutSolver):
             cover_obj = cover_obj.to_arrays()       # the random strategy reorders its list in place, round after round (:634-637)
         self._agg_list = cover_obj
         quota = self.selection_size(sel_size, len(cover_obj), minimum=1)                         # :55-58
-        state = {"strat": strat}
-
-        def separate(round_no, point):
-            state["strat"], _, sdp, opt = self.select_and_generate_round(state["strat"], point, round_no, quota,
-                                                                         cover_obj, cover_cons)
-            return {"sdp": sdp, "opt": opt}
-
+        self._run = SimpleNamespace(strat=strat, quota=quota, covers=(cover_obj, cover_cons))
         keep_attr = (self.cuts_per_set, self.cuts_row_quota)
         if m_cuts > 1:
             self.cuts_per_set, self.cuts_row_quota, self.multi_log = m_cuts, None, []
         try:
-            log = harness.run_cut_rounds(lp, separate, nb_rounds_cuts, after_solve=self._gpu_wake)
+            log = harness.run_cut_rounds(lp, self._round_qcqp, nb_rounds_cuts, after_solve=self._gpu_wake)
         finally:
             self.cuts_per_set, self.cuts_row_quota = keep_attr
         opt = log.column("opt")

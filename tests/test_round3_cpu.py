@@ -34,7 +34,7 @@ def _rank_list(n_head=10, n_total=50, strat=4):
     indptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
     fused = dict(idx=idx, score=score, lam=-np.ones(n_head), ks=ks[idx], set_inds=S[idx], row_entry=row_entry, indptr=indptr,
                  indices=np.arange(indptr[-1], dtype=np.int32), values=np.arange(indptr[-1], dtype=np.float64) / 10, rhs=-np.arange(6.0))
-    return RankList(None, b, 1 if strat == 1 else 2, n_total, vv, idx.copy(), score.copy(), strat=strat, sel_size=n_head, fused=fused), b, vv
+    return RankList(b, 1 if strat == 1 else 2, n_total, vv, idx.copy(), score.copy(), strat=strat, sel_size=n_head, fused=fused), b, vv
 
 
 def test_fused_rows_are_a_prefix_of_the_block():
