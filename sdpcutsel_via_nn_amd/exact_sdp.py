@@ -25,7 +25,23 @@ Degenerate rules (the same in the kernel):
   * an index with d_i = 0 is eliminated -- row and column i of Y are zero, lam_i is reported as 0 and plays no part in the dual
     feasibility of the rest (in the scaled problem its row of A vanishes and its l_i is left out of the bound);
   * if A is positive semidefinite already (a pivoted-free LDL^T with pivots >= 0, columns under a zero pivot zero) the answer is
-    lam = 0, Y = 0, p* = sum q_ij x_i x_j, zero iterations.
+    lam = 0, Y = 0, p* = sum q_ij x_i x_j, zero iterations.  The decision is taken on A, in the scaled units, with an allowance of
+    8 eps max|A|: a d_i of 1e-16 (x_i = 1e-16 or 0.9999999999999999: ordinary LP output) puts a pivot of -3e-17 inside it while
+    C + Diag(0) itself has lambda_min = -0.33.  The value is right to 3e-17; certificate_check judges dual feasibility in the same
+    scaled units, which is where the bound is proved.
+
+Known limitation -- degenerate optima.  Where a bound Y_ii <= d_i is active with a ZERO multiplier (equal-magnitude weights at
+x = 0.5: the round-1 point of every BoxQP run on a unit-weight instance) the upper bound may stall: Z_ii sits on its bound while
+l_i -> 0, neither of the two recovery rules of s fits, and the primal point stops improving near a gap of 1e-5 .. 1e-3 while the
+lower bound reaches the optimum.  Such a lane ends at ITER_CAP, flagged (converged False; SDPCUT_STAT_SDP_UNCONVERGED on the device)
+with a valid but wider bracket; `value` remains a certified lower bound.  More iterations do not help (300 and 1000 both leave
+the case below at 6.6e-6); the cure is a different primal recovery.  Measured on x = 0.5, q_ij in {0, +-1/k} (tests/sdp_inputs.py `vertex`, 256
+inputs per k): none for k = 2, 3; k = 4: twin 2, host-compiled header 3, MI355X 2 (largest gap at the cap 1.9e-3); k = 5: twin 1,
+header 1, MI355X 0 (6.9e-4).  Which tied input stalls depends on last-bit rounding: the three implementations disagree on it.
+The smallest case, k = 4, x = 0.5, q = (1, -1, 0, 1, 0, 1, 1, 1, 0, 1) / 4, p* = 15/64: the twin ends at the cap with a gap of
+5.1e-4 and the lower bound within 1e-9 of 15/64, the header converges in 83 iterations.  Every other family of tests/sdp_inputs.py
+(x on, next to and outside its bounds, one-signed, tied-sign and tiny weights, nearly positive semidefinite C, the golden covers
+late in a run) converges everywhere, in at most 91 iterations.
 """
 import numpy as np
 
@@ -36,8 +52,9 @@ FORCE_DIAG = 1e5     # Z_ii is set to its bound 1 where l_i (S^-1)_ii >= this (l
 MAX_HALVINGS = 30    # of a step that leaves the domain (the damped step never does in exact arithmetic)
 # twice the largest iteration count the twin shows on the CPU test inputs
 ITER_CAP = 2 * 69
-# feasibility slack of certificate_check in units of eps * (||C||_F + ||lam||_inf): 4 x the worst the twin shows on the CPU test
-# inputs (0.85 on the twin; the device's own certificates showed 1.28 on an MI355X, inside it)
+# feasibility slack of certificate_check in units of eps * (||C||_F + ||lam||_inf), eps * (||A||_F + ||l||_inf) for dual
+# feasibility: 4 x the worst the twin shows on the inputs of tests/test_exact_sdp_cpu.py (0.85 on the twin; the
+# device's own certificates showed 1.28 on an MI355X, inside it; on the edge families of tests/sdp_inputs.py twin 1.55, device 2.45)
 SLACK_UNITS = 3.4
 _EPS = np.finfo(np.float64).eps
 
@@ -228,9 +245,18 @@ def measure(k, inputs, negSM, max_elem, **kw):
 def certificate_check(C, d, lam, Y, slack_units=SLACK_UNITS):
     """Independent optimality proof of one batch: C [n, k, k] symmetric, d [n, k] (already max(., 0)), lam [n, k],
     Y [n, k(k+1)/2] upper triangle.  Checks with numpy.linalg.eigvalsh, on the indices with d_i > 0 (the others are eliminated: their
-    rows of Y must vanish):  C + Diag(lam) >= -s,  lam >= 0,  Y >= -s,  Y_ii <= d_i + s,  and weak duality  -d^T lam <= <C, Y> + s
-    with s = slack_units * eps * (||C||_F + ||lam||_inf).
-    -> dict(ok bool [n], dual_min, primal_min, diag_excess, worst_units: the largest violation seen in units of eps (||C||_F + ||lam||_inf))."""
+    rows of Y must vanish):  lam >= 0,  Y >= -s,  Y_ii <= d_i + s,  weak duality  -d^T lam <= <C, Y> + s
+    with s = slack_units * eps * (||C||_F + ||lam||_inf), and dual feasibility WHERE THE SOLVER DECIDED IT, in the units scaled by
+    r = sqrt(d) (A = Diag(r) C Diag(r), l_i = d_i lam_i):
+        Diag(r) (C + Diag(lam)) Diag(r) = A + Diag(l) >= -s_A,      s_A = slack_units * eps * (||A||_F + ||l||_inf)
+    plus, for an answer with lam = 0 (the positive-semidefinite shortcut), the shortcut's own allowance 8 eps max|A|.
+    That is a proof of  value - k s_A <= p*:  every feasible Y is Diag(r) Z Diag(r) with Z >= 0, Z_ii <= 1 (so trace Z <= k), and
+        <C, Y> = <A + Diag(l), Z> - sum l_i Z_ii >= -s_A trace Z - sum l_i >= -k s_A - d^T lam.
+    (Judged on C + Diag(lam) itself, a d_i of 1e-16 turns a pivot of A that is -3e-17, rounding, into lambda_min = -0.33: the
+    bound such an answer returns is right to 3e-17, and the unscaled matrix says nothing about it.  `dual_min_unscaled` reports it.)
+    -> dict(ok bool [n], dual_min (of A + Diag l), dual_min_unscaled (of C + Diag lam), primal_min, diag_excess, units [n]: the
+            largest violation of each candidate in units of eps (||C||_F + ||lam||_inf) -- eps (||A||_F + ||l||_inf) for the dual
+            one, net of the shortcut's allowance --, worst_units: the largest of them)."""
     C, d, lam = np.asarray(C, float), np.asarray(d, float), np.asarray(lam, float)
     n, k = d.shape
     ia, ib = _triu(k)
@@ -243,16 +269,27 @@ def certificate_check(C, d, lam, Y, slack_units=SLACK_UNITS):
     s = slack_units * unit
     mask = act[:, :, None] & act[:, None, :]
     # eliminated indices become decoupled unit diagonals: they do not move the smallest eigenvalue of the rest below zero
-    S = np.where(mask, C + lam[:, :, None] * np.eye(k), np.eye(k)[None])
-    dual_min = np.linalg.eigvalsh(S)[:, 0]
+    eye = np.eye(k)[None]
+    r = np.sqrt(d)
+    A, l = C * r[:, :, None] * r[:, None, :], d * lam
+    SA = A + l[:, :, None] * eye
+    size = np.abs(SA).reshape(n, -1).max(axis=1)      # (the eliminated diagonal at the size of the rest: eigvalsh errs by eps x the largest entry)
+    dual_min = np.linalg.eigvalsh(np.where(mask, SA, np.where(size > 0, size, 1.0)[:, None, None] * eye))[:, 0]
+    dual_min_unscaled = np.linalg.eigvalsh(np.where(mask, C + lam[:, :, None] * eye, eye))[:, 0]
+    unit_A = _EPS * (np.sqrt((A * A).sum(axis=(1, 2))) + np.abs(l).max(axis=1))
+    unit_A = np.where(unit_A > 0, unit_A, _EPS)
+    shortcut = np.where((lam == 0.0).all(axis=1), 8 * _EPS * np.abs(A).reshape(n, -1).max(axis=1), 0.0)
+    dual_viol = np.maximum(-dual_min - shortcut, 0.0)
     primal_min = np.linalg.eigvalsh(Ym)[:, 0]
     dgY = Ym[:, np.arange(k), np.arange(k)]
     diag_excess = (dgY - d).max(axis=1)
     elim_rows = np.where(mask, 0.0, np.abs(Ym)).reshape(n, -1).max(axis=1)
     lower, upper = -(d * lam).sum(axis=1), (C * Ym).sum(axis=(1, 2))
-    viol = np.maximum.reduce([-dual_min, -primal_min, diag_excess, -lam.min(axis=1), lower - upper, np.zeros(n)])
-    ok = (viol <= s) & (elim_rows == 0.0)
-    return dict(ok=ok, dual_min=dual_min, primal_min=primal_min, diag_excess=diag_excess, worst_units=float((viol / unit).max()) if n else 0.0)
+    viol = np.maximum.reduce([-primal_min, diag_excess, -lam.min(axis=1), lower - upper, np.zeros(n)])
+    ok = (viol <= s) & (dual_viol <= slack_units * unit_A) & (elim_rows == 0.0)
+    units = np.maximum(viol / unit, dual_viol / unit_A)
+    return dict(ok=ok, dual_min=dual_min, dual_min_unscaled=dual_min_unscaled, primal_min=primal_min, diag_excess=diag_excess, units=units,
+                worst_units=float(units.max()) if n else 0.0)
 
 
 def figure8(nn_measure, exact_measure, cut_round, sel_size):

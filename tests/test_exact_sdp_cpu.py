@@ -142,7 +142,7 @@ def test_degenerate_rules():
     # all d = 0: p* = sum q_ij x_i x_j whatever C is
     r = _one(3, [0.0, 1.0, 1.0], q3)
     assert r["iters"][0] == 0 and r["gap"][0] == 0.0 and r["value"][0] == q3[3] + q3[4] + q3[5]
-    # a tiny positive d_i is NOT eliminated and still converges to a certificate
+    # a tiny positive d_i is NOT eliminated and still converges to a certificate (1e-16 as well: test_exact_sdp_edges_cpu.test_reproducers)
     r = _one(2, [1e-13, 0.5], [-0.5, 0.5, -0.25])
     x, C, _ = exact_sdp.unpack(2, np.array([[1e-13, 0.5, -0.5, 0.5, -0.25]]))
     assert r["converged"][0] and exact_sdp.certificate_check(C, np.maximum(x - x * x, 0.0), r["lam"], r["Y"])["ok"].all()
