@@ -133,10 +133,20 @@ enum { SDPCUT_KERNEL_MFMA = 0, SDPCUT_KERNEL_SIMPLE = 1, SDPCUT_KERNEL_VALU = 2 
  * superset of the head by COUNTING in one launch (csrc/topk_sort.hip, tk_countrank_kernel: the rank of an entry is the number of
  * (key, [obj_improve,] index) composites in front of it) instead of a tile sort and a rank merge in two.  Same head, bit for bit.
  * 0: the two launches (A/B; they also serve heads of 8193 .. 16384 entries, raw key output and shard records either way). */
+/* SDPCUT_OPT_SKIP_NONVIOLATED (default 1): a fused combined round (sdpcut_select_round*, sdpcut_round_*, sdpcut_shard_head_device with
+ * SDPCUT_PART_STRONG) whose list holds one size class with a skipping kernel (3-variable candidates; csrc/score_plan.h:
+ * SDPCUT_SKIP_KMASK) runs the MLP only for VIOLATED candidates: in its strong regime -- at least sel_size candidates violated with a
+ * positive measure -- the ranking of cut_select_qp.py:601-632 reads the measure of no other.  Same head, scores, rows, new_strat,
+ * nb_violated / strong / violated_in_scan, bit for bit; nb_positive of such a round counts the positive measures among the
+ * VIOLATED candidates (the others were not evaluated).  A round that turns out to visit every entry completes the measure (one
+ * NN-only scoring launch) and runs again inside the call; so does whatever else reads the measure of the list afterwards
+ * (sdpcut_get_scores, sdpcut_rank*, sdpcut_gather_scores_device, diverse / multi-cut / pool rounds, strategy 2):
+ * SDPCUT_STAT_NN_COMPLETIONS counts those launches, SDPCUT_STAT_SCORED reports SDPCUT_NN either way.
+ * 1: lists the score kernel cuts into strips of 64 (more than 65 536 candidates on a 256-CU device); 0: never; 2: every list (tests). */
 enum { SDPCUT_OPT_KERNEL = 1, SDPCUT_OPT_TIMING = 2, SDPCUT_OPT_FUSE_KEYS = 3, SDPCUT_OPT_AUTO_REGIME = 4,
        SDPCUT_OPT_FUSED_TAIL = 5, SDPCUT_OPT_COOP_LAUNCH = 6, SDPCUT_OPT_EIG_KERNEL = 7, SDPCUT_OPT_STREAM_PRIORITY = 8,
        SDPCUT_OPT_SIDE_STREAMS = 9, SDPCUT_OPT_ONE_LAUNCH = 10, SDPCUT_OPT_PREFILTER = 11, SDPCUT_OPT_EXACT_HEAD = 12, SDPCUT_OPT_EXACT_SDP = 13,
-       SDPCUT_OPT_COUNT_RANK = 14 };
+       SDPCUT_OPT_COUNT_RANK = 14, SDPCUT_OPT_SKIP_NONVIOLATED = 15 };
 
 /* Counters of a handle: SDPCUT_STAT_ROUNDS = fused rounds served (sdpcut_select_round*),
  * SDPCUT_STAT_SELECT_FALLBACKS = rounds whose radix selection declared itself void (a grid barrier
@@ -159,11 +169,16 @@ enum { SDPCUT_OPT_KERNEL = 1, SDPCUT_OPT_TIMING = 2, SDPCUT_OPT_FUSE_KEYS = 3, S
  *   device: the call waits for the handle's stream.
  * SDPCUT_STAT_POINTS_REDONE = points of batched rounds (sdpcut_round_csr_points) on the one-launch route whose selection declared
  *   itself void -- an every-entry-visited tie group beyond the one-workgroup sort, a structured LP vertex -- and that were served
- *   by the single-point round inside the call instead.  Same results either way. */
+ *   by the single-point round inside the call instead.  Same results either way.
+ * SDPCUT_STAT_NN_SKIPPED = candidates the handle's last scoring launch did not run the MLP for: list length - nb_violated after a
+ *   launch under SDPCUT_OPT_SKIP_NONVIOLATED, 0 after any other (a completion included) and after a new list; after
+ *   sdpcut_shard_head_device it is read from the device: the call waits for the handle's stream;
+ * SDPCUT_STAT_NN_COMPLETIONS = NN scoring launches since the handle was made that completed a measure such a launch left partial. */
 enum { SDPCUT_STAT_ROUNDS = 1, SDPCUT_STAT_SELECT_FALLBACKS = 2, SDPCUT_STAT_SCORED = 3, SDPCUT_STAT_TIE_SPLITS = 4,
        SDPCUT_STAT_DIRECT_SELECTIONS = 5, SDPCUT_STAT_PF_BIN = 6, SDPCUT_STAT_PF_FLOOR = 7, SDPCUT_STAT_PF_COUNT = 8,
        SDPCUT_STAT_EXACT_HEAD = 9, SDPCUT_STAT_EXACT_GAVE_UP = 10, SDPCUT_STAT_EXACT_RETRIES = 11,
-       SDPCUT_STAT_SDP_UNCONVERGED = 12, SDPCUT_STAT_POINTS_REDONE = 13 };
+       SDPCUT_STAT_SDP_UNCONVERGED = 12, SDPCUT_STAT_POINTS_REDONE = 13,
+       SDPCUT_STAT_NN_SKIPPED = 14, SDPCUT_STAT_NN_COMPLETIONS = 15 };
 int sdpcut_get_stat(sdpcut_handle h, int which, int64_t *value);
 
 /* Maximum sub-problem size (assert dim <= 5, cut_select_qp.py:93) */

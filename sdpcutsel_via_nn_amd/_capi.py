@@ -28,6 +28,8 @@ STAT_EXACT_HEAD, STAT_EXACT_GAVE_UP, STAT_EXACT_RETRIES = 9, 10, 11
 OPT_EXACT_SDP = 13       # strategy 3 accepted by the ranking and round calls (include/sdpcut.h)
 OPT_COUNT_RANK = 14      # the sort tail of a selection ranks by counting in one launch (include/sdpcut.h); default on
 STAT_SDP_UNCONVERGED = 12
+OPT_SKIP_NONVIOLATED = 15   # fused combined rounds run the MLP for violated candidates only (include/sdpcut.h); 0 never, 1 long lists (default), 2 every list
+STAT_NN_SKIPPED, STAT_NN_COMPLETIONS = 14, 15   # candidates the last such launch skipped; NN launches that completed a partial measure
 STAT_POINTS_REDONE = 13   # points of batched rounds served by the single-point round inside the call (include/sdpcut.h)
 BATCH_MAX_POINTS = 256   # SDPCUT_BATCH_MAX_POINTS: most LP points of one score_points / round_csr_points call
 DIVERSE_MAX_POOL = 16384   # SDPCUT_DIVERSE_MAX_POOL: longest pool of round_csr_diverse / list of filter_parallel

@@ -5,6 +5,11 @@
 #include "common.h"
 #include "topk_route.h"
 
+int obj_complete(sdpcut_ctx *h)
+{
+    return h->obj_partial ? sdpcut_score(h, SDPCUT_NN) : 0;
+}
+
 extern "C" {
 
 int sdpcut_score(sdpcut_handle h, uint32_t flags)
@@ -34,6 +39,8 @@ int sdpcut_get_scores(sdpcut_handle h, double *eigmin, double *obj_improve)
     if (!h) return SDPCUT_EINVAL;
     SDPCUT_NO_PENDING(h);
     HIP_TRY(h, hipSetDevice(h->device));
+    int rc;
+    if (obj_improve && (rc = obj_complete(h))) return rc;
     if (eigmin) {
         if (!(h->scored & SDPCUT_EIG)) return sdpcut_fail(h, SDPCUT_ESTATE, "eigenvalues not scored");
         HIP_TRY(h, hipMemcpyAsync(eigmin, h->d_eig, h->N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -51,6 +58,7 @@ static int check_rank_args(sdpcut_ctx *h, int strat)
     int rc;
     if (strat != SDPCUT_PART_STRONG && (rc = check_round_strategy(h, strat))) return rc;
     const uint32_t need = strat_need(strat);
+    if ((rc = obj_complete(h))) return rc;      // (a feasibility ranking too: its nb_positive reads the measure)
     if ((h->scored & need) != need) return sdpcut_fail(h, SDPCUT_ESTATE, "sdpcut_score with the needed flags first");
     return 0;
 }
@@ -168,6 +176,8 @@ int sdpcut_gather_scores_device(sdpcut_handle h, int64_t count, const void *d_id
     if (!h) return SDPCUT_EINVAL;
     SDPCUT_NO_PENDING(h);
     if (count < 0 || (count > 0 && !d_ids)) return sdpcut_fail(h, SDPCUT_EINVAL, "bad gather arguments");
+    int rc;
+    if (d_obj_out && (rc = obj_complete(h))) return rc;
     if ((d_eig_out && !(h->scored & SDPCUT_EIG)) || (d_obj_out && !(h->scored & SDPCUT_NN)))
         return sdpcut_fail(h, SDPCUT_ESTATE, "sdpcut_score with the needed flags first");
     HIP_TRY(h, hipSetDevice(h->device));

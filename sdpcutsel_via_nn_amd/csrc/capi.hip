@@ -79,8 +79,8 @@ int sdpcut_create(int device_id, sdpcut_handle *out)
     h->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     if (hipSetDevice(device_id) != hipSuccess || hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess ||
         hipMalloc((void **)&h->d_counters, 8 * sizeof(int64_t)) != hipSuccess ||
-        hipMalloc((void **)&h->d_stats, 4 * sizeof(unsigned long long)) != hipSuccess ||
-        hipMemset(h->d_stats, 0, 4 * sizeof(unsigned long long)) != hipSuccess) {
+        hipMalloc((void **)&h->d_stats, 5 * sizeof(unsigned long long)) != hipSuccess ||
+        hipMemset(h->d_stats, 0, 5 * sizeof(unsigned long long)) != hipSuccess) {
         delete h;
         return sdpcut_fail(nullptr, SDPCUT_EHIP, "stream / counter allocation failed");
     }
@@ -159,6 +159,11 @@ int sdpcut_set_option(sdpcut_handle h, int option, int64_t value)
     case SDPCUT_OPT_COUNT_RANK:
         h->count_rank = value != 0;
         return SDPCUT_OK;
+    case SDPCUT_OPT_SKIP_NONVIOLATED:
+        SDPCUT_NO_PENDING(h);
+        if (value < 0 || value > 2) return sdpcut_fail(h, SDPCUT_EINVAL, "SDPCUT_OPT_SKIP_NONVIOLATED: 0 never, 1 long lists, 2 every list");
+        h->skip_nonviolated = (int)value;
+        return SDPCUT_OK;
     case SDPCUT_OPT_EXACT_HEAD:
         SDPCUT_NO_PENDING(h);
         h->exact_head = value != 0;
@@ -200,7 +205,20 @@ int sdpcut_get_stat(sdpcut_handle h, int which, int64_t *value)
     switch (which) {
     case SDPCUT_STAT_ROUNDS: *value = h->stat_rounds; return SDPCUT_OK;
     case SDPCUT_STAT_SELECT_FALLBACKS: *value = h->stat_fallbacks; return SDPCUT_OK;
-    case SDPCUT_STAT_SCORED: *value = h->have_point ? (int64_t)h->scored : 0; return SDPCUT_OK;
+    // (a skipped round has scored the optimality measure -- of every candidate its ranking reads; the rest follows on demand)
+    case SDPCUT_STAT_SCORED: *value = h->have_point ? (int64_t)(h->scored | (h->obj_partial ? (uint32_t)SDPCUT_NN : 0u)) : 0; return SDPCUT_OK;
+    case SDPCUT_STAT_NN_COMPLETIONS: *value = h->stat_nn_completions; return SDPCUT_OK;
+    case SDPCUT_STAT_NN_SKIPPED:
+        if (h->nn_skipped_on_device) {      // a sharded head: its violated count was copied to d_stats[4] behind the selection
+            unsigned long long nviol = 0;
+            HIP_TRY(h, hipSetDevice(h->device));
+            HIP_TRY(h, hipMemcpyAsync(&nviol, h->d_stats + 4, sizeof(nviol), hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(h, sdpcut_sync(h));
+            h->stat_nn_skipped = h->nn_skipped_n - (int64_t)nviol;
+            h->nn_skipped_on_device = false;
+        }
+        *value = h->stat_nn_skipped;
+        return SDPCUT_OK;
     case SDPCUT_STAT_TIE_SPLITS: *value = h->stat_tie_splits; return SDPCUT_OK;
     case SDPCUT_STAT_POINTS_REDONE: *value = h->stat_points_redone; return SDPCUT_OK;
     case SDPCUT_STAT_EXACT_HEAD: *value = h->stat_exact_last; return SDPCUT_OK;

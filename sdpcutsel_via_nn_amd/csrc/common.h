@@ -62,6 +62,7 @@ struct TrainData {
 // a fused round between its two halves (round.hip: round_begin / round_end)
 struct PendingRound {
     bool active = false, csr = false, fast_tried = false;
+    bool skipped = false;          // its scoring launch ran the MLP for violated candidates only (SDPCUT_OPT_SKIP_NONVIOLATED)
     int strat = 0;
     bool by_sdp = false;           // strategy 3: the round was begun inside an SdpAsObj view and is ended inside one
     int32_t ld = 0;
@@ -117,7 +118,7 @@ struct sdpcut_ctx {
     bool eig_kernel = true;        // SDPCUT_OPT_EIG_KERNEL: eigenvalue-only launches run eig_only_kernel (eig.hip)
     bool pf_counted = false;       // the scoring launches of the current round all counted the fine histogram (launch_score)
     bool prefilter = true;         // SDPCUT_OPT_PREFILTER: fine histogram in the score kernels, direct selection (topk_dev.h)
-    unsigned long long *d_stats = nullptr;   // device counters that outlive a round: [0] direct selections
+    unsigned long long *d_stats = nullptr;   // device counters that outlive a round: [0] direct selections, [1..3] its diagnostics, [4] nb_violated of a skipped sharded head
     bool coop_launch = false;      // SDPCUT_OPT_COOP_LAUNCH: cooperative launch of the kernels with grid barriers (+20 us per round)
     int64_t stat_rounds = 0, stat_fallbacks = 0, stat_tie_splits = 0;   // sdpcut_get_stat
     int64_t stat_points_redone = 0;   // SDPCUT_STAT_POINTS_REDONE
@@ -157,6 +158,19 @@ struct sdpcut_ctx {
     unsigned long long *d_sdp_unconverged = nullptr;   // candidates of the last exact solve that stopped at the iteration cap
     bool exact_sdp = false;        // SDPCUT_OPT_EXACT_SDP: strategy 3 is accepted
     uint32_t scored = 0;
+    // SDPCUT_OPT_SKIP_NONVIOLATED (score_mfma_skip_kernel): 0 never, 1 lists score_plan cuts into strips of 64, 2 every list
+    int skip_nonviolated = 1;
+    bool skip_launched = false;    // the last launch_score ran the skipping kernel
+    // d_obj holds the optimality measure of the VIOLATED candidates only (a skipped round in its strong regime).  While set,
+    // `scored` carries no SDPCUT_NN -- whoever needs the measure scores it like a missing one, which completes the array
+    // (launch_score counts that) -- and SDPCUT_STAT_SCORED still reports the bit.  Cleared with `scored`.
+    bool obj_partial = false;
+    // SDPCUT_STAT_NN_SKIPPED: what the last scoring launch skipped (0 after one that scored everybody; reset with the list).  A
+    // sharded head has no host wait: its selection's nb_violated is copied on the stream into d_stats[4] (which outlives every
+    // workspace) and the stat is nn_skipped_n - d_stats[4], read when asked for (nn_skipped_on_device).
+    int64_t stat_nn_skipped = 0, nn_skipped_n = 0;
+    bool nn_skipped_on_device = false;
+    int64_t stat_nn_completions = 0;   // SDPCUT_STAT_NN_COMPLETIONS
     int64_t last_total = -1;       // length of the last ranking (-1: none), see sdpcut_rank_fetch
 
     NetHost net[SDPCUT_MAX_K + 1];
@@ -231,6 +245,20 @@ static inline uint32_t strat_need(int strat)
 {
     return strat == SDPCUT_STRAT_FEAS ? SDPCUT_EIG : strat == SDPCUT_STRAT_OPT ? SDPCUT_NN : (SDPCUT_EIG | SDPCUT_NN);
 }
+// The selection of a skipped launch has been enqueued: from here on d_obj counts as not scored (sdpcut_ctx::obj_partial).  The
+// guard does it on every way out of the scope that enqueues the selection, the refused ones included.
+static inline void obj_demote(sdpcut_ctx *h)
+{
+    h->scored &= ~(uint32_t)SDPCUT_NN;
+    h->obj_partial = true;
+}
+struct ObjDemoteGuard {
+    sdpcut_ctx *h;
+    bool on;
+    ~ObjDemoteGuard() { if (on) obj_demote(h); }
+};
+// batch.hip: complete d_obj if it is partial (the NN-only scoring of the list: per candidate the bits the skipped launch gives)
+int obj_complete(sdpcut_ctx *h);
 static inline int check_round_strategy(sdpcut_ctx *h, int strat)
 {
     if (strat != SDPCUT_STRAT_FEAS && strat != SDPCUT_STRAT_OPT && strat != SDPCUT_STRAT_COMB)
@@ -372,23 +400,28 @@ void free_sdp_ws(sdpcut_ctx *h);
 // Strategy 3 = strategy 2 on the exact measure (cut_select_qp.py:584-601: the same list, the same sort, another obj_improve).
 // The non-fused selection reads the handle's optimality array wherever it ranks (rank.hip, topk.hip); for the lifetime of this
 // object that array IS d_sdp and its `scored` bit is SDPCUT_SDP's, and SDPCUT_OPT_EXACT_HEAD -- which re-scores the MLP -- is
-// off.  Nothing scores inside a view: its scope begins after SDPCUT_SDP has been scored.
+// off.  Nothing scores inside a view: its scope begins after SDPCUT_SDP has been scored.  The exact measure is whole whatever a
+// skipped round left of the MLP's (obj_partial): inside the view that flag is down -- obj_complete has nothing to do there and
+// must not, its launch would write the MLP's scores into d_sdp -- and the real array's state comes back with the array.
 struct SdpAsObj {
     sdpcut_ctx *h;
     double *obj;
     uint32_t scored;
-    bool exact_head;
-    explicit SdpAsObj(sdpcut_ctx *ctx) : h(ctx), obj(ctx->d_obj), scored(ctx->scored), exact_head(ctx->exact_head)
+    bool exact_head, obj_partial;
+    explicit SdpAsObj(sdpcut_ctx *ctx)
+        : h(ctx), obj(ctx->d_obj), scored(ctx->scored), exact_head(ctx->exact_head), obj_partial(ctx->obj_partial)
     {
         h->d_obj = h->d_sdp;
         h->scored = (scored & SDPCUT_EIG) | ((scored & SDPCUT_SDP) ? (uint32_t)SDPCUT_NN : 0u);
         h->exact_head = false;
+        h->obj_partial = false;
     }
     ~SdpAsObj()
     {
         h->d_obj = obj;
         h->scored = scored;
         h->exact_head = exact_head;
+        h->obj_partial = obj_partial;
     }
     SdpAsObj(const SdpAsObj &) = delete;
     SdpAsObj &operator=(const SdpAsObj &) = delete;

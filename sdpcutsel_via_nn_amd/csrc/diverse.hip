@@ -390,6 +390,7 @@ int sdpcut_round_csr_diverse(sdpcut_handle h, const double *vars_values, int str
     HIP_TRY(h, hipSetDevice(h->device));
     // 1. the pool: the head of the strategy's ranking, by the existing ranking call (SDPCUT_OPT_EXACT_HEAD included)
     const uint32_t need = strat_need(strat);
+    if ((rc = obj_complete(h))) return rc;      // a measure a skipped round left partial: whole before this round counts by it
     if ((h->scored & need) != need && (rc = sdpcut_score(h, need & ~h->scored))) return rc;
     const int64_t want = pool_size < h->N ? pool_size : h->N;
     out->row_ld = h->row_len_max;

@@ -40,7 +40,8 @@ void free_candidates(sdpcut_ctx *h)
     hipFree(h->d_set_orig); hipFree(h->d_k); hipFree(h->d_eig); hipFree(h->d_obj);
     free_sdp_ws(h);
     h->d_set_orig = nullptr; h->d_k = nullptr; h->d_eig = nullptr; h->d_obj = nullptr;
-    h->N = 0; h->scored = 0; h->last_total = -1;
+    h->N = 0; h->scored = 0; h->obj_partial = false; h->last_total = -1;
+    h->stat_nn_skipped = 0; h->nn_skipped_on_device = false;
     h->topk_alt_clean = false;      // (how much of the selection workspace a round's epilogue zeroes depends on the list's length)
     h->side_choice = -1;      // (a new list measures for itself whether its small size classes go to side streams)
 }
@@ -61,7 +62,7 @@ int sdpcut_set_network(sdpcut_handle h, int k, int n_layers, const int32_t *widt
     hipFree(nh_.d_blob);
     nh_.d_blob = nullptr;
     nh_.set = false;
-    h->scored &= ~(uint32_t)SDPCUT_NN;      // the list's optimality scores were the old network's: a round scores again
+    h->scored &= ~(uint32_t)SDPCUT_NN; h->obj_partial = false;      // the list's optimality scores were the old network's: a round scores again
     HIP_TRY(h, hipMalloc((void **)&nh_.d_blob, pk.blob.size() * sizeof(double)));
     HIP_TRY(h, hipMemcpy(nh_.d_blob, pk.blob.data(), pk.blob.size() * sizeof(double), hipMemcpyHostToDevice));
     NetDev &d = nh_.dev;
@@ -89,7 +90,7 @@ int sdpcut_set_instance(sdpcut_handle h, int32_t nb_vars, const double *Q_arr)
     HIP_TRY(h, sdpcut_sync(h));
     const int64_t L = (int64_t)nb_vars * (nb_vars + 1) / 2;
     hipFree(h->d_Q); hipFree(h->d_vars);
-    h->d_Q = nullptr; h->d_vars = nullptr; h->have_point = false; h->scored = 0;
+    h->d_Q = nullptr; h->d_vars = nullptr; h->have_point = false; h->scored = 0; h->obj_partial = false;
     HIP_TRY(h, hipMalloc((void **)&h->d_Q, L * sizeof(double)));
     HIP_TRY(h, hipMalloc((void **)&h->d_vars, (L + nb_vars) * sizeof(double)));
     HIP_TRY(h, hipMemcpy(h->d_Q, Q_arr, L * sizeof(double), hipMemcpyHostToDevice));
@@ -207,7 +208,7 @@ int sdpcut_set_point(sdpcut_handle h, const double *vars_values)
     if (rc) return rc;
     h->point_inflight = true;
     h->have_point = true;
-    h->scored = 0;
+    h->scored = 0; h->obj_partial = false;
     h->last_total = -1;
     return SDPCUT_OK;
 }
@@ -222,7 +223,7 @@ int sdpcut_set_point_device(sdpcut_handle h, const void *d_vars_values)
     HIP_TRY(h, hipMemcpyAsync(h->d_vars, d_vars_values, (h->L + h->nb_vars) * sizeof(double),
                               hipMemcpyDeviceToDevice, h->stream));
     h->have_point = true;
-    h->scored = 0;
+    h->scored = 0; h->obj_partial = false;
     h->last_total = -1;
     return SDPCUT_OK;
 }

@@ -389,6 +389,7 @@ int sdpcut_round_csr_multi(sdpcut_handle h, const double *vars_values, int strat
     if (!by_sdp && cap > 0 && exact_head_applies(h, strat) && exact_first_band(h, cap) > TK_LDSK)
         return sdpcut_fail(h, SDPCUT_EINVAL, "SDPCUT_OPT_EXACT_HEAD: the head plus its band (min(N, sel_size + max(256, sel_size / 8))) must not exceed 8192 entries");
     const uint32_t need = by_sdp ? (uint32_t)SDPCUT_SDP : strat_need(strat);
+    if ((rc = obj_complete(h))) return rc;      // a measure a skipped round left partial: whole before this round counts by it
     if ((h->scored & need) != need && (rc = sdpcut_score(h, need & ~h->scored))) return rc;
     sdpcut_round_csr_t &o = out->csr;
     o.row_ld = h->row_len_max;

@@ -177,7 +177,7 @@ struct NoPointAfter {
     ~NoPointAfter()
     {
         h->have_point = false;
-        h->scored = 0;
+        h->scored = 0; h->obj_partial = false;
         h->last_total = -1;
     }
 };

@@ -39,7 +39,11 @@ int score_for_selection(sdpcut_ctx *h, int strat, int64_t sel_size, int64_t cap,
 {
     *stage = 0;
     *auto_out = false;
+    h->skip_launched = false;
     int rc;
+    // a measure a skipped round left partial (same point, another selection): whole before anything ranks or counts by it -- a
+    // feasibility selection too, whose nb_positive reads it
+    if ((rc = obj_complete(h))) return rc;
     const int fast_mode = (h->scored & need) == 0 ? rank_fast_mode(h, strat, sel_size, cap, nullptr) : 0;
     const bool want_auto = allow_auto && strat == SDPCUT_STRAT_COMB;
     // (the short-list predicate must be the one topk_select_enqueue will evaluate: it sees the tie-aware combined modes only when
@@ -114,9 +118,12 @@ static int round_begin(sdpcut_ctx *h, int strat, int64_t sel_size, int32_t coef_
         rc = score_for_selection(h, strat, sel_size, cap, strat_need(strat), h->auto_regime, &stage, &auto_regime);
     }
     if (rc) return rc;
+    // a launch that skipped the non-violated candidates: d_obj serves the selection enqueued below and nobody else
+    const ObjDemoteGuard partial = {h, !exact && h->skip_launched};
     PendingRound &P = h->pend;
     P = PendingRound();
     P.strat = strat; P.sel_size = sel_size; P.cap = cap; P.ld = coef_ld; P.csr = csr;
+    P.skipped = partial.on;
     P.exact_band = exact ? exact_first_band(h, cap) : 0;
     if (cap == 0) {   // nothing to generate; round_end still reports the ranking's length / strategy switch
         P.active = true;
@@ -271,6 +278,30 @@ static int round_end(sdpcut_ctx *h, const void **block, int64_t *cap_out, int64_
             h->pend.active = false;
         } else {
             h->stat_exact_last = 1;
+        }
+    }
+    if (P.skipped) {
+        // SDPCUT_OPT_SKIP_NONVIOLATED: the enqueued selection is the answer only if it ran in the strong regime and was not void --
+        // nothing else of the round reads the measure of a candidate that is not violated.  Every entry visited (resolved on the
+        // device, or by the host below), or a selection that gave up: complete d_obj and begin the round again -- scored now, it
+        // takes the ordinary road under a fresh serial number.
+        // (fast_tried and cap > 0 hold for every skipped round -- score_for_selection lets the launch count, and so skip, only for a
+        // head rank_fast_mode serves, which rank_fast_enqueue then enqueues; were they not to, the round is simply begun again)
+        bool keep = false;
+        if (P.fast_tried && P.cap > 0) {
+            int rc = wait_round_done(h, (const int64_t *)h->pinned + 7, P.serial);
+            if (rc) return rc;
+            const int64_t *c = (const int64_t *)h->pinned;
+            keep = !c[4] && c[6] == TK_MODE_STRONG && c[0] >= (P.sel_size < h->N ? P.sel_size : h->N);
+            h->stat_nn_skipped = h->N - c[1];
+        }
+        if (!keep) {
+            int rc = obj_complete(h);
+            if (rc) return rc;
+            rc = round_begin(h, P.strat, P.sel_size, P.ld, P.csr);
+            if (rc) return rc;
+            P = h->pend;
+            h->pend.active = false;
         }
     }
     const int strat = P.strat;

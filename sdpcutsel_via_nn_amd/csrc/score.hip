@@ -22,10 +22,19 @@ static int launch_score_k(sdpcut_ctx *h, int K, uint32_t flags, hipEvent_t ev_st
 {
     if (h->bucket[K].n == 0) return 0;
     if (!st) st = h->stream;
-    const ScorePlan p = plan_class(h, K, fuse);
-    const ScoreArgs A = fill_score_args(h, K, flags, fuse, strong_out, p);
     const bool shaped = net_shape_ok(h, K, flags);
-    if (h->kernel_variant == SDPCUT_KERNEL_MFMA && shaped) {
+    // SDPCUT_OPT_SKIP_NONVIOLATED: the fused launch of a combined round (the strong class is all it counts for) over a list of
+    // this one class runs the MLP for violated candidates only; d_obj is then valid for those alone (obj_demote)
+    const bool skip = fuse && fuse->mode == TK_MODE_STRONG && flags == (uint32_t)(SDPCUT_EIG | SDPCUT_NN) && shaped &&
+                      h->kernel_variant == SDPCUT_KERNEL_MFMA && h->bucket[K].n == h->N && score_mfma_skip_built(K) &&
+                      score_skip_applies(h->bucket[K].n, h->n_cu, K, h->skip_nonviolated);
+    const ScorePlan p = skip ? score_plan_skip(h->bucket[K].n, h->n_cu, K, h->N, fuse->k, h->skip_nonviolated == 2) : plan_class(h, K, fuse);
+    const ScoreArgs A = fill_score_args(h, K, flags, fuse, strong_out, p);
+    if (skip) {
+        if (A.pf_mloc == 0) h->pf_counted = false;
+        score_mfma_skip_launch(K, A, p.grid, st, ev_start, ev_stop);
+        h->skip_launched = true;
+    } else if (h->kernel_variant == SDPCUT_KERNEL_MFMA && shaped) {
         if (A.tk && A.pf_mloc == 0) h->pf_counted = false;
         score_mfma_launch(K, A, p.grid, st, ev_start, ev_stop);
     } else
@@ -167,10 +176,11 @@ static ScoreFormIn form_in(const sdpcut_ctx *h, uint32_t flags, const ScoreFuse 
     return in;
 }
 
-int launch_score(sdpcut_ctx *h, uint32_t flags, const ScoreFuse *fuse, bool *fused, int64_t *strong_out)
+static int launch_score_form(sdpcut_ctx *h, uint32_t flags, const ScoreFuse *fuse, bool *fused, int64_t *strong_out)
 {
     // (r5) did EVERY launch of this round count the fine histogram of the selection's class?  (The selection reads the table only then.)
     h->pf_counted = fuse != nullptr && fuse->k > 0;
+    h->skip_launched = false;      // set by the launch that skips (launch_score_k)
     const ScoreFormIn in = form_in(h, flags, fuse);
     const ScoreForm f = score_form(in);
     if (fused) *fused = f.fused;
@@ -193,6 +203,21 @@ int launch_score(sdpcut_ctx *h, uint32_t flags, const ScoreFuse *fuse, bool *fus
     es[f.first] = ev_start;
     ee[f.last] = ev_stop;
     return launch_classes_seq(h, flags, fuse, strong_out, es, ee);
+}
+
+int launch_score(sdpcut_ctx *h, uint32_t flags, const ScoreFuse *fuse, bool *fused, int64_t *strong_out)
+{
+    const int rc = launch_score_form(h, flags, fuse, fused, strong_out);
+    // a launch that wrote the optimality measure of every candidate has completed what a skipped round left partial
+    if (!rc && (flags & SDPCUT_NN) && h->obj_partial && !h->skip_launched) {
+        h->obj_partial = false;
+        ++h->stat_nn_completions;
+    }
+    if (!rc && !h->skip_launched) {      // SDPCUT_STAT_NN_SKIPPED is the LAST scoring launch's: this one skipped nobody
+        h->stat_nn_skipped = 0;
+        h->nn_skipped_on_device = false;
+    }
+    return rc;
 }
 
 // ---- a batch of LP points (points.hip) ------------------------------------------------------------------------------------------

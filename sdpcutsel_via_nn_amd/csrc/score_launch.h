@@ -94,6 +94,10 @@ struct ScorePointStrides {
 // score_mfma.hip.  The FUSE argument of the kernel is A.tk_mode where A.tk is set (one of TK_MODE_FEAS / OPT / STRONG: score_form
 // has refused everything else) and 0 otherwise.
 void score_mfma_launch(int K, const ScoreArgs &A, int grid, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop);   // score_mfma_kernel, CLAMP = !A.net.unclamped_ok
+// score_mfma_skip_kernel (the MLP for violated candidates only) over class K, if score_mfma_skip_built(K): A.tk set, A.tk_mode
+// TK_MODE_STRONG, both flags, the work split of score_plan_skip
+bool score_mfma_skip_built(int K);
+void score_mfma_skip_launch(int K, const ScoreArgs &A, int grid, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop);
 void score_mfma_all_launch(const ScoreArgsAll &AA, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop);            // score_mfma_all_kernel over AA.bend[nclasses - 1] workgroups
 // score_mfma_points_kernel over class K at n_points points: grid x n_points workgroups, A.tk must be NULL
 void score_mfma_points_launch(int K, const ScoreArgs &A, const ScorePointStrides &ps, int grid, int n_points, hipStream_t st);

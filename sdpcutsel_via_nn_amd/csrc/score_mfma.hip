@@ -15,8 +15,9 @@
 //            registers; weights are pre-packed host-side into A-fragment order and streamed
 //            from L2 as coalesced 512-B wave loads; tansig runs on the VALU between MFMAs.
 //
-// This unit holds the kernel for one class (score_mfma_kernel), the one over all classes of a list (score_mfma_all_kernel:
-// the same body per class) and the two launchers that start them (score_launch.h).  Which wave scores which candidate is
+// This unit holds the kernel for one class (score_mfma_kernel), its variant that runs the MLP for violated candidates only
+// (score_mfma_skip_kernel: the same body with SKIP), the one over all classes of a list (score_mfma_all_kernel: the same body per
+// class) and the launchers that start them (score_launch.h).  Which wave scores which candidate is
 // decided on the host (score_plan.h); the cross-check kernels are in score_alt.hip.
 #include <type_traits>
 
@@ -224,11 +225,41 @@ struct MfmaLds {
     uint32_t pf_tab[pf_score_k(K) ? PF_BINS / 2 : 1];    // (r5) the class members by window code, 16-bit counters, two per word (topk_dev.h)
 };
 
+// LDS of one workgroup of the skipping kernel (SKIP, see score_mfma_body): instead of a strip, a wave keeps a QUEUE of the violated
+// candidates it has met -- their mapped features (feat, column = queue slot) and what the epilogue needs of them (negSM, max_elem,
+// output slot).  A ring of QCAP = 96 slots: a pass takes the oldest 32, so at most 31 are pending when a strip appends at most 64.
+template <int K, int H, int NH>
+struct MfmaLdsSkip {
+    static constexpr int S0 = (K + K * (K + 1) / 2 + 3) / 4;
+    static constexpr int T = (H + 15) / 16;
+    static constexpr int NT = (H - 16 * (T - 1) <= 4) ? H - 16 * (T - 1) : 0;
+    static constexpr int QCAP = 96;
+    double feat[4][S0 * 4][QCAP];
+    double ynn[4][QCAP];
+    double q_negsm[4][QCAP];
+    double q_maxel[4][QCAP];
+    int32_t q_out[4][QCAP];
+    double s_bias[NH * 64];
+    double s_wtail[NT ? NH * 4 * 64 : 1];
+    double s_wout[64];
+    uint32_t tk_hist[256];
+    uint32_t tk_cnt[2];
+    uint32_t s_strong;
+    uint32_t pf_tab[pf_score_k(K) ? PF_BINS / 2 : 1];
+};
+
 // bid / nblk: this workgroup's index among the nblk workgroups that serve the class (blockIdx.x / gridDim.x of a launch over
 // one class; the launch over all classes of a list hands every class its own range of workgroups, score_mfma_all_kernel)
-template <int K, int H, int NH, int FUSE, bool CLAMP, int JK>
-__device__ __forceinline__ void score_mfma_body(const ScoreArgs A, MfmaLds<K, H, NH> &S, const int bid, const int nblk)
+// SKIP (FUSE = TK_MODE_STRONG, both flags, JK = 2 only; LDS = MfmaLdsSkip): the MLP runs for VIOLATED candidates only -- the strong
+// class the launch counts for holds no other, and nothing else of a combined round in its strong regime reads obj_improve.  Phase A
+// is unchanged (every valid lane stores lambda_min and is counted); the violated lanes then append to the wave's queue, and phase
+// B runs a two-tile pass over the oldest 32 entries while there are 32; the wave's last strip flushes the rest (one tile if <= 16).
+// A queue entry's score does not depend on its slot or its neighbours (tansig.h), and mlp_pass<1> equals mlp_pass<2> bit for bit:
+// a violated candidate gets the bits the plain kernel gives it.  Non-violated candidates get NO obj_out store.
+template <int K, int H, int NH, int FUSE, bool CLAMP, int JK, bool SKIP = false, class LDS = MfmaLds<K, H, NH>>
+__device__ __forceinline__ void score_mfma_body(const ScoreArgs A, LDS &S, const int bid, const int nblk)
 {
+    static_assert(!SKIP || (FUSE == TK_MODE_STRONG && JK == 2), "the skipping variant serves the fused launch of a combined round");
     constexpr int M = K * (K + 1) / 2;
     constexpr int DIN = K + M;
     constexpr int S0 = (DIN + 3) / 4;      // k-steps of the input layer
@@ -333,6 +364,7 @@ __device__ __forceinline__ void score_mfma_body(const ScoreArgs A, MfmaLds<K, H,
         __syncthreads();
     }
 
+    [[maybe_unused]] int q_head = 0, q_fill = 0;      // (SKIP) the wave's queue: first pending slot (0, 32 or 64) and pending entries; scalar
     PHASE_DECL;
     while (more) {
         PHASE_MARK(0);
@@ -378,6 +410,23 @@ __device__ __forceinline__ void score_mfma_body(const ScoreArgs A, MfmaLds<K, H,
             continue;
         }
 
+        // (SKIP) the violated lanes append to the queue: slot = its end + the lane's rank among them
+        [[maybe_unused]] bool q_viol = true;
+        [[maybe_unused]] int q_slot = lane;
+        if constexpr (SKIP) {
+            q_viol = valid && lam < SDPCUT_NEG_EIGVAL;
+            c_viol += q_viol;
+            const unsigned long long vm = __ballot(q_viol);
+            const int rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(vm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)vm, 0u));
+            const int tail_slot = q_head + q_fill >= LDS::QCAP ? q_head + q_fill - LDS::QCAP : q_head + q_fill;      // (scalar)
+            q_slot = tail_slot + rank >= LDS::QCAP ? tail_slot + rank - LDS::QCAP : tail_slot + rank;
+            q_fill += __popcll(vm);
+            if (q_viol) {
+                S.q_negsm[wave][q_slot] = cd.negSM;
+                S.q_maxel[wave][q_slot] = cd.max_elem;
+                S.q_out[wave][q_slot] = out_idx;
+            }
+        }
         // ---- stage mapminmax'ed inputs (neural_net_3D.m:69-73): xp = (v - xoffset)*gain + ymin
 #pragma unroll
         for (int i = 0; i < S0 * 4; ++i) {
@@ -387,7 +436,11 @@ __device__ __forceinline__ void score_mfma_body(const ScoreArgs A, MfmaLds<K, H,
                 xp = (v - net.inmap[i]) * net.inmap[DIN + i] + net.ymin;
                 if constexpr (!CLAMP) xp = min_f64_raw(max_f64_raw(xp, -SDPCUT_INPUT_CLAMP), SDPCUT_INPUT_CLAMP);
             }
-            feat[wave][i][lane] = xp;
+            if constexpr (SKIP) {
+                if (q_viol) feat[wave][i][q_slot] = xp;
+            } else {
+                feat[wave][i][lane] = xp;
+            }
         }
         wave_lds_sync();
         PHASE_MARK(3);
@@ -567,6 +620,48 @@ __device__ __forceinline__ void score_mfma_body(const ScoreArgs A, MfmaLds<K, H,
                 if (q == 0) ynn[wave][col0 + 16 * j + c16] = part;
             }
         };
+        if constexpr (SKIP) {
+            // the epilogue of a pass over the cnt <= 32 entries from slot q_head on: the arithmetic of the plain epilogue below on
+            // what the queue kept of the candidate; every entry is violated, so it is strong exactly when its measure is positive
+            auto skip_epilogue = [&](const int cnt) __attribute__((always_inline)) {
+#pragma clang fp contract(off)
+                const int s = q_head + (lane & 31);
+                const bool live = lane < cnt;
+                double acc = ynn[wave][s];
+                acc = acc + net.b_out;
+                const double y = (acc - net.y_ymin) / net.y_gain + net.y_xoffset;
+                double obj = S.q_negsm[wave][s];
+                obj = obj + y * S.q_maxel[wave][s];
+                if (live) A.obj_out[S.q_out[wave][s]] = obj;
+                const bool pos = live && obj > 0.0;
+                c_strong += pos;
+                c_pos += pos;
+                const uint64_t key = key_of(obj);
+                hist_add_few(tk_hist, (uint32_t)(key >> 56), pos);
+                if (PF && pos) { const int f = pf_code(key, false); atomicAdd(&pf_tab[f >> 1], (f & 1) ? 0x10000u : 1u); }
+            };
+            // passes while 32 entries are pending; behind the wave's last strip the rest (padding columns compute on stale slots, their
+            // results are not stored)
+            while (q_fill > 16 && (q_fill >= 32 || !nx_more)) {
+                const int cnt = q_fill < 32 ? q_fill : 32;
+                mlp_pass(std::integral_constant<int, 2>{}, q_head);
+                wave_lds_sync();
+                skip_epilogue(cnt);
+                wave_lds_sync();      // the slots are free for the next strip's entries
+                q_head = q_head + 32 >= LDS::QCAP ? 0 : q_head + 32;
+                q_fill -= cnt;
+            }
+            if (!nx_more && q_fill > 0) {
+                mlp_pass(std::integral_constant<int, 1>{}, q_head);
+                wave_lds_sync();
+                skip_epilogue(q_fill);
+                wave_lds_sync();
+                q_fill = 0;
+            }
+            PHASE_MARK(4);
+            tail = tail || nx_tail; s0 = nx_s0; more = nx_more;
+            continue;
+        }
         {
             const int units = (int)((lim - s0 + 15) >> 4);      // column tiles of this strip that hold candidates
             // (a whole strip has its own loop with a constant trip count, and the rare paths are marked so: with one generic loop
@@ -650,6 +745,16 @@ __global__ __launch_bounds__(256, (JK == 1 ? SDPCUT_MFMA_J1_WAVES : 2)) void sco
 {
     __shared__ MfmaLds<K, H, NH> S;
     score_mfma_body<K, H, NH, FUSE, CLAMP, JK>(A, S, (int)blockIdx.x, (int)gridDim.x);
+}
+
+// The skipping variant (SKIP of score_mfma_body; score_plan_skip decides its work split): the fused scoring launch of a combined
+// round over a class whose size is in SDPCUT_SKIP_KMASK.  Two workgroups per CU must stay resident: 80 KB of LDS at the most.
+template <int K, int H, int NH, bool CLAMP>
+__global__ __launch_bounds__(256, 2) void score_mfma_skip_kernel(ScoreArgs A)
+{
+    static_assert(sizeof(MfmaLdsSkip<K, H, NH>) <= 80 * 1024, "two workgroups of the skipping kernel must fit a CU's LDS");
+    __shared__ MfmaLdsSkip<K, H, NH> S;
+    score_mfma_body<K, H, NH, TK_MODE_STRONG, CLAMP, 2, true>(A, S, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // The same kernel at the P = gridDim.y LP points of a batch (sdpcut_score_points / sdpcut_round_csr_points, points.hip): workgroup
@@ -743,6 +848,28 @@ void score_mfma_launch(int K, const ScoreArgs &A, int grid, hipStream_t st, hipE
     case 3: score_mfma_launch_k<3>(A, grid, st, ev_start, ev_stop); break;
     case 4: score_mfma_launch_k<4>(A, grid, st, ev_start, ev_stop); break;
     default: score_mfma_launch_k<5>(A, grid, st, ev_start, ev_stop); break;
+    }
+}
+
+template <int K>
+static void score_mfma_skip_launch_k(const ScoreArgs &A, int grid, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop)
+{
+    if constexpr (skip_k(K) && mfma_cols(K) == 2) {
+        if (A.net.unclamped_ok) SCORE_LAUNCH((score_mfma_skip_kernel<K, NetShape<K>::H, NetShape<K>::NH, false>), grid, 256);
+        else SCORE_LAUNCH((score_mfma_skip_kernel<K, NetShape<K>::H, NetShape<K>::NH, true>), grid, 256);
+    }
+}
+
+// has size class K a skipping instantiation?  (score_skip_applies asks skip_k alone; the one-tile-per-pass experiment has none)
+bool score_mfma_skip_built(int K) { return skip_k(K) && mfma_cols(K) == 2; }
+
+void score_mfma_skip_launch(int K, const ScoreArgs &A, int grid, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop)
+{
+    switch (K) {
+    case 2: score_mfma_skip_launch_k<2>(A, grid, st, ev_start, ev_stop); break;
+    case 3: score_mfma_skip_launch_k<3>(A, grid, st, ev_start, ev_stop); break;
+    case 4: score_mfma_skip_launch_k<4>(A, grid, st, ev_start, ev_stop); break;
+    default: score_mfma_skip_launch_k<5>(A, grid, st, ev_start, ev_stop); break;
     }
 }
 

@@ -142,6 +142,63 @@ static inline ScorePlan score_plan(int64_t n, int n_cu, int K, int64_t n_total, 
     return p;
 }
 
+// ---- the work split of the skipping kernel (score_mfma_skip_kernel) --------------------------------------------------------------
+// The fused scoring launch of a combined round (FUSE = TK_MODE_STRONG) runs the MLP only for violated candidates: a wave packs
+// them into a private queue that carries over from strip to strip and runs a pass per 32 queued.  Packing pays with the number
+// of strips a wave sees, so the launch has fewer, longer-lived waves than score_plan's: SDPCUT_SKIP_BLOCKS_PER_CU workgroups per
+// CU (2 = one resident generation).  On the violated pattern of the 10^6-candidate benchmark list the model of passes gives
+// 0.908 of today's at 8 workgroups per CU (1.9 strips per wave), 0.878 at 4, 0.862 at 2 (7.6 strips).
+#ifndef SDPCUT_SKIP_KMASK
+#define SDPCUT_SKIP_KMASK (1 << 3)      // candidate sizes with a skipping instantiation (bit k; 0: none)
+#endif
+constexpr bool skip_k(int k) { return ((SDPCUT_SKIP_KMASK >> k) & 1) != 0; }
+#ifndef SDPCUT_SKIP_BLOCKS_PER_CU
+#define SDPCUT_SKIP_BLOCKS_PER_CU 2
+#endif
+// most strips per wave a forced skip (option value 2) aims at on a list that leaves the device part-empty
+#define SDPCUT_SKIP_FORCED_STRIPS 4
+
+// Does the skipping kernel serve a class of n candidates of size K?  opt = SDPCUT_OPT_SKIP_NONVIOLATED: 0 never; 1 where
+// score_plan uses strips of 64 (a part-empty device runs one pass per wave and has nothing to pack) and a workgroup's share still
+// fits the 16-bit counters of the fine histogram (pf_mloc_rule); 2 whatever the length (tests).
+static inline bool score_skip_applies(int64_t n, int n_cu, int K, int opt)
+{
+    if (!skip_k(K) || opt == 0 || n < 1) return false;
+    if (opt == 2) return true;
+    return n > 32 * (int64_t)n_cu * 4 * 2 && n < 59000 * (int64_t)n_cu * SDPCUT_SKIP_BLOCKS_PER_CU;
+}
+
+// The plan of the skipping launch over n >= 1 candidates; the fields mean what they mean in score_plan.  Strips of 64 round-robin
+// over the whole rounds, the last partial round always split evenly in column tiles (there is no later generation of workgroups
+// to fill the gaps).  force: at most ceil(strips / SDPCUT_SKIP_FORCED_STRIPS) waves, so that a short list still hands a wave
+// several strips.
+static inline ScorePlan score_plan_skip(int64_t n, int n_cu, int K, int64_t n_total, int64_t fuse_k, bool force)
+{
+    ScorePlan p;
+    p.strip = 64;
+    const int64_t strips = (n + 63) / 64;
+    int64_t waves = (int64_t)n_cu * SDPCUT_SKIP_BLOCKS_PER_CU * 4;
+    if (force) {
+        const int64_t w = (strips + SDPCUT_SKIP_FORCED_STRIPS - 1) / SDPCUT_SKIP_FORCED_STRIPS;
+        waves = w < waves ? w : waves;
+    }
+    waves = strips < waves ? strips : waves;
+    p.grid = (int)((waves + 3) / 4 < 1 ? 1 : (waves + 3) / 4);
+    p.rr_end = n;
+    const int64_t W = (int64_t)p.grid * 4, round = W * 64;
+    const int64_t R = n / round, rem = n - R * round;
+    if (R >= 1 && rem > 0) {
+        const int64_t tiles = (rem + 15) / 16, lo = tiles / W;      // lo <= 4, and 4 only with tail_nhi = 0: rem is less than a round
+        p.rr_end = R * round;
+        p.tail_lo = (int32_t)lo;
+        p.tail_hi = (int32_t)lo + 1;
+        p.tail_nhi = (tiles - lo * W + 3) / 4 * 4;
+    }
+    p.pf_mloc = pf_score_k(K) ? pf_mloc_rule(fuse_k, (n + p.grid - 1) / p.grid, n_total) : 0;
+    p.spread = 0;
+    return p;
+}
+
 // ---- the form of a scoring call ------------------------------------------------------------------------------------------------
 enum ScoreFormKind {
     SCORE_FORM_EIG = 1,     // flags == SDPCUT_EIG: the eigenvalue-only kernel, one launch over all classes (eig.hip)

@@ -107,12 +107,16 @@ extern "C" int sdpcut_shard_head_device(sdpcut_handle h, int strat, int64_t coun
     // digit of the selection keys on the way (score_for_selection) -- a sharded round needs no sdpcut_score.
     int stage = 0;
     bool auto_regime = false;
+    h->skip_launched = false;
     if (h->N > 0) {
         int rc0;
         if (comball) rc0 = ((h->scored & need) != need) ? sdpcut_score(h, need & ~h->scored) : 0;     // (normally scored by the round's first attempt)
         else rc0 = score_for_selection(h, strat, 0, count, need, false, &stage, &auto_regime);
         if (rc0) return rc0;
     }
+    // SDPCUT_PART_STRONG scored by the skipping kernel: d_obj serves the selection enqueued below and nobody else; an
+    // every-entry-visited head asked for afterwards (SDPCUT_PART_COMBALL, above) finds the measure missing and scores it
+    const ObjDemoteGuard partial = {h, h->skip_launched};
     int64_t *rec = (int64_t *)d_record;
     const int grid = (int)((count + 255) / 256);
     if (h->N > 0) {
@@ -135,6 +139,11 @@ extern "C" int sdpcut_shard_head_device(sdpcut_handle h, int strat, int64_t coun
         h->shard_rec = nullptr;
         if (rc < 0) return rc;
         if (rc != 1) return sdpcut_fail(h, SDPCUT_EINVAL, "shard head: request not eligible for the select path");
+        if (partial.on) {      // SDPCUT_STAT_NN_SKIPPED = N - nb_violated of this selection: no host wait here, the count stays on the device
+            HIP_TRY(h, hipMemcpyAsync(h->d_stats + 4, d_c4 + 1, sizeof(int64_t), hipMemcpyDeviceToDevice, h->stream));
+            h->nn_skipped_n = h->N;
+            h->nn_skipped_on_device = true;
+        }
         if (comball)
             hipLaunchKernelGGL(shard_secondary_kernel, dim3(grid), dim3(256), 0, h->stream, count, d_c4, rec + SHARD_HDR + count, h->base,
                                h->N, h->d_obj, rec + SHARD_HDR + 2 * count);
