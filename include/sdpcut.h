@@ -308,6 +308,43 @@ int sdpcut_point_buffer(sdpcut_handle h, double **buf);
 int sdpcut_set_point_device(sdpcut_handle h, const void *d_vars_values);
 
 /*
+ * Node box: the variable bounds l <= x <= u of a node of a spatial branch and bound (the reference assumes [0, 1] throughout,
+ * cut_select_qcqp.py:275-276).  The small SDP the MLP estimates carries the secant of the unit box, X_ii <= x_i; at a node the valid
+ * constraint is X_ii <= (l_i + u_i) x_i - l_i u_i.  The problem is affine-invariant: with d = u - l and x = l + D x' the node problem in
+ * x' IS the unit-box problem the networks were trained on, on the tables
+ *     x'_i  = (x_i - l_i) / d_i
+ *     X'_ij = (((X_ij - l_i x_j) - l_j x_i) + l_i l_j) / (d_i d_j)      i <= j, diagonal included
+ *     Q'_ij = Q_ij (d_i d_j)
+ * (fp64, this operation order, no contraction: on the unit box all three equal the originals bit for bit), and the affine terms in
+ * x cancel between <Q, X> and the minimum, so the measure stays the objective improvement in the ORIGINAL units -- comparable
+ * across nodes and with BIG_M.  csrc/box.hip writes Q' once per sdpcut_set_box and the transformed point once per LP point, in
+ * stream order behind the point's copy (one launch more per round).
+ * With a box set SDPCUT_NN and SDPCUT_SDP are computed from the transformed tables; lambda_min (SDPCUT_EIG), the violated test,
+ * the eigenvectors and every cut row from the original point as before (PSD cuts do not depend on bounds): strategies 0, 1 and 5
+ * are unaffected.  A call that scores SDPCUT_EIG | SDPCUT_NN runs two launches, and a round scores first and then takes the
+ * selection of an already scored list (no fused launch, no SDPCUT_OPT_SKIP_NONVIOLATED).  With SDPCUT_OPT_TIMING the score time
+ * of such a two-launch call is the LAST launch's (the MLP's): both dispatches carry the same pair of events.  What a boxed round
+ * costs next to the plain round of the same list, and what it gains in bound per round: tools/node_rounds.py ->
+ * profiles/node_rounds.txt, run on two short lists only (single samples: 5-12 % more per round at 243 candidates; at 6608
+ * candidates level under strategy 2 and up to ~40 % more under strategy 4; no bound gain beyond the scatter between nodes);
+ * long lists are not measured.  DESIGN.md section 5 "Node boxes".
+ * lb, ub: [nb_vars] each, 0 <= lb_i < ub_i <= 1 and ub_i - lb_i >= SDPCUT_BOX_MIN_WIDTH (ten halvings of a variable; the division
+ * amplifies rounding by ~ 8 eps / (d_i d_j) absolute on X'), else SDPCUT_EINVAL: fixed and nearly fixed variables are a limitation.
+ * Both NULL clears the box.  Clears the SDPCUT_NN and SDPCUT_SDP bits of the scores at the current point and keeps SDPCUT_EIG; a
+ * current point is transformed again.  sdpcut_set_instance clears the box.
+ * Refused while a box is set (SDPCUT_ESTATE, handle unchanged): sdpcut_score_points and sdpcut_round_csr_points (their kernels
+ * have one Q for all points), the sharded entry points (sdpcut_shard_*), and switching SDPCUT_OPT_EXACT_HEAD on (reference-exact
+ * bits have no meaning where the reference has no boxes); sdpcut_set_box refuses a box while that option is on.
+ */
+#define SDPCUT_BOX_MIN_WIDTH 0.0009765625 /* 2^-10 */
+int sdpcut_set_box(sdpcut_handle h, const double *lb, const double *ub);
+/* the box ([nb_vars] each, either may be NULL; [0, 1] when none is set) and whether one is set */
+int sdpcut_get_box(sdpcut_handle h, double *lb, double *ub, int *is_set);
+/* The transformed tables as the kernels read them: Q_box [L], vars_box [L + n] (either may be NULL).  SDPCUT_ESTATE without a box;
+ * vars_box needs a current point.  Waits for the handle's stream. */
+int sdpcut_get_box_tables(sdpcut_handle h, double *Q_box, double *vars_box);
+
+/*
  * Score every candidate at the current point (replaces the per-candidate loop bodies of
  * _sel_eigcut_by_ordering_on_measure, cut_select_qp.py:570-582 and :642-648):
  *   SDPCUT_EIG: eigmin[i]      = lambda_min([[1, x^T],[x, X]])          (a6; numpy.linalg.eigvalsh(...)[0] at cut_select_qp.py:796.

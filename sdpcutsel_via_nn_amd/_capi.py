@@ -112,6 +112,9 @@ SIGNATURES = {
     "sdpcut_set_point": [_vp, _dp],
     "sdpcut_point_buffer": [_vp, _c.POINTER(_dp)],
     "sdpcut_set_point_device": [_vp, _vp],
+    "sdpcut_set_box": [_vp, _dp, _dp],
+    "sdpcut_get_box": [_vp, _dp, _dp, _c.POINTER(_c.c_int)],
+    "sdpcut_get_box_tables": [_vp, _dp, _dp],
     "sdpcut_score": [_vp, _c.c_uint32],
     "sdpcut_get_scores": [_vp, _dp, _dp],
     "sdpcut_get_sdp_scores": [_vp, _dp, _dp],
@@ -588,6 +591,39 @@ class Scorer(object):
 
     def set_point_device(self, dev_ptr):
         self._check(self._lib.sdpcut_set_point_device(self._h, _vp(dev_ptr)))
+
+    # ------------------------------------------------------------------ node box
+    def set_box(self, lb, ub):
+        """The variable bounds lb <= x <= ub of a branch-and-bound node (sdpcut_set_box): from here on the optimality measures
+        (NN, SDP) are those of the node's small SDP -- computed on the instance tables re-expressed in the box's variables,
+        :mod:`nodebox` -- while lambda_min, the violated test and the cut rows stay those of the original point.  Both None clears
+        the box.  0 <= lb < ub <= 1 with ub - lb >= 2^-10, else ValueError."""
+        if lb is None and ub is None:
+            return self.clear_box()
+        if lb is None or ub is None:
+            raise ValueError("lb and ub must both be given (or both be None: clear_box)")
+        from .nodebox import check_box
+        lb, ub = check_box(self.nb_vars, lb, ub)
+        self._check(self._lib.sdpcut_set_box(self._h, _ptr(lb, _dp), _ptr(ub, _dp)))
+
+    def clear_box(self):
+        self._check(self._lib.sdpcut_set_box(self._h, None, None))
+
+    @property
+    def box(self):
+        """(lb, ub) of the node box, or None when none is set"""
+        lb, ub, flag = np.empty(self.nb_vars), np.empty(self.nb_vars), _c.c_int(0)
+        self._check(self._lib.sdpcut_get_box(self._h, _ptr(lb, _dp), _ptr(ub, _dp), ctypes.byref(flag)))
+        return (lb, ub) if flag.value else None
+
+    def box_tables(self, point=True):
+        """-> (Q', vars') as the scoring kernels read them while a box is set (sdpcut_get_box_tables); vars' is None with
+        point=False (a handle without a current LP point has none)"""
+        n = self.nb_vars
+        Qb = np.empty(n * (n + 1) // 2)
+        vb = np.empty(self._point_len()) if point else None
+        self._check(self._lib.sdpcut_get_box_tables(self._h, _ptr(Qb, _dp), _ptr(vb, _dp)))
+        return Qb, vb
 
     # ------------------------------------------------------------------ hot path
     def score(self, flags):

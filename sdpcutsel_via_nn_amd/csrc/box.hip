@@ -1,0 +1,139 @@
+// Node boxes (include/sdpcut.h: sdpcut_set_box): the instance tables re-expressed in the variables x' = (x - l) / d of a node's box
+// l <= x <= u, d = u - l, in which the node's small SDP is the unit-box problem the networks were trained on.  The map is
+// elementwise on the tables, not per candidate: Q' once per box, the transformed point once per LP point; the scoring kernels
+// run on those tables as they are (gather.h recomputes max_elem and Q_slice from whatever table it is handed).
+//   box_q_kernel       Q'_ij = Q_ij (d_i d_j)
+//   box_point_kernel   X'_ij = (((X_ij - l_i x_j) - l_j x_i) + l_i l_j) / (d_i d_j),  x'_i = (x_i - l_i) / d_i
+// fp64 in exactly this order, no contraction: on the unit box every entry is the original's bits.
+#include <cmath>
+
+#include "common.h"
+
+// (i, j), i <= j, of packed position p (row-major upper triangle: row i starts at i n - i (i - 1) / 2, cut_select_qp.py:531) without
+// a walk over the rows: the root of the quadratic, then one step down and one up (the square root is off by less than one row:
+// (2 n + 1)^2 and 8 p are exact in fp64 for n <= 40000)
+__device__ __forceinline__ void box_unpack(int64_t p, int32_t n, int32_t &i, int32_t &j)
+{
+    const double b = 2.0 * (double)n + 1.0;
+    int64_t r = (int64_t)floor((b - sqrt(b * b - 8.0 * (double)p)) * 0.5);
+    r = r < 0 ? 0 : (r > n - 1 ? n - 1 : r);
+    if (r * n - r * (r - 1) / 2 > p) --r;
+    if (r + 1 < n && (r + 1) * n - (r + 1) * r / 2 <= p) ++r;
+    i = (int32_t)r;
+    j = (int32_t)(r + (p - (r * n - r * (r - 1) / 2)));
+}
+
+__global__ __launch_bounds__(256) void box_q_kernel(const double *Q, const double *ld, int32_t n, int64_t L, double *Qb)
+{
+#pragma clang fp contract(off)
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= L) return;
+    int32_t i, j;
+    box_unpack(p, n, i, j);
+    Qb[p] = Q[p] * (ld[n + i] * ld[n + j]);
+}
+
+__global__ __launch_bounds__(256) void box_point_kernel(const double *vars, const double *ld, int32_t n, int64_t L, double *vb)
+{
+#pragma clang fp contract(off)
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= L + n) return;
+    if (p >= L) {
+        const int64_t i = p - L;
+        vb[p] = (vars[p] - ld[i]) / ld[n + i];
+        return;
+    }
+    int32_t i, j;
+    box_unpack(p, n, i, j);
+    const double li = ld[i], lj = ld[j];
+    vb[p] = (((vars[p] - li * vars[L + j]) - lj * vars[L + i]) + li * lj) / (ld[n + i] * ld[n + j]);
+}
+
+int box_after_point(sdpcut_ctx *h)
+{
+    if (!h->box_set) return 0;
+    const int64_t m = h->L + h->nb_vars;
+    hipLaunchKernelGGL(box_point_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, h->stream, (const double *)h->d_vars,
+                       (const double *)h->d_box_ld, h->nb_vars, h->L, h->d_vars_box);
+    HIP_TRY(h, hipGetLastError());
+    return 0;
+}
+
+void box_clear(sdpcut_ctx *h)
+{
+    (void)hipFree(h->d_box_ld); (void)hipFree(h->d_Q_box); (void)hipFree(h->d_vars_box);
+    h->d_box_ld = h->d_Q_box = h->d_vars_box = nullptr;
+    h->box_set = false;
+    h->box_lb.clear(); h->box_ub.clear();
+}
+
+extern "C" {
+
+int sdpcut_set_box(sdpcut_handle h, const double *lb, const double *ub)
+{
+    if (!h) return SDPCUT_EINVAL;
+    SDPCUT_NO_PENDING(h);
+    if (!h->d_Q) return sdpcut_fail(h, SDPCUT_ESTATE, "set_instance first");
+    if ((lb == nullptr) != (ub == nullptr)) return sdpcut_fail(h, SDPCUT_EINVAL, "set_box: lb and ub must both be given or both be NULL");
+    const int32_t n = h->nb_vars;
+    if (lb) {
+        if (h->exact_head) return sdpcut_fail(h, SDPCUT_ESTATE, "set_box: SDPCUT_OPT_EXACT_HEAD is on (reference-exact heads have no node box)");
+        for (int32_t i = 0; i < n; ++i)      // (written so that a NaN fails)
+            if (!(lb[i] >= 0.0 && ub[i] <= 1.0 && ub[i] - lb[i] >= SDPCUT_BOX_MIN_WIDTH))
+                return sdpcut_fail(h, SDPCUT_EINVAL, "set_box: variable " + std::to_string(i) + ": a box needs 0 <= lb, ub <= 1 and ub - lb >= "
+                                                     "SDPCUT_BOX_MIN_WIDTH (2^-10)");
+    } else if (!h->box_set) {
+        return SDPCUT_OK;      // nothing to clear: the scores stand
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (lb) {      // the tables first: a failed allocation leaves box, scores and tables as they were
+        if (!h->d_box_ld) HIP_TRY(h, hipMalloc((void **)&h->d_box_ld, (size_t)2 * n * sizeof(double)));
+        if (!h->d_Q_box) HIP_TRY(h, hipMalloc((void **)&h->d_Q_box, (size_t)h->L * sizeof(double)));
+        if (!h->d_vars_box) HIP_TRY(h, hipMalloc((void **)&h->d_vars_box, (size_t)(h->L + n) * sizeof(double)));
+    }
+    HIP_TRY(h, sdpcut_sync(h));      // (the launches of an earlier scoring read the tables rewritten below)
+    h->scored &= ~(uint32_t)(SDPCUT_NN | SDPCUT_SDP);      // the measures of the old box; lambda_min knows no box
+    h->obj_partial = false;
+    h->last_total = -1;
+    h->box_set = false;      // (until every table below is in place)
+    h->box_lb.clear(); h->box_ub.clear();
+    if (!lb) return SDPCUT_OK;
+    std::vector<double> ld((size_t)2 * n);
+    for (int32_t i = 0; i < n; ++i) { ld[i] = lb[i]; ld[(size_t)n + i] = ub[i] - lb[i]; }
+    HIP_TRY(h, hipMemcpy(h->d_box_ld, ld.data(), ld.size() * sizeof(double), hipMemcpyHostToDevice));
+    h->box_lb.assign(lb, lb + n);
+    h->box_ub.assign(ub, ub + n);
+    hipLaunchKernelGGL(box_q_kernel, dim3((unsigned)((h->L + 255) / 256)), dim3(256), 0, h->stream, (const double *)h->d_Q,
+                       (const double *)h->d_box_ld, n, h->L, h->d_Q_box);
+    HIP_TRY(h, hipGetLastError());
+    h->box_set = true;
+    return h->have_point ? box_after_point(h) : SDPCUT_OK;
+}
+
+int sdpcut_get_box(sdpcut_handle h, double *lb, double *ub, int *is_set)
+{
+    if (!h) return SDPCUT_EINVAL;
+    if (!h->d_Q) return sdpcut_fail(h, SDPCUT_ESTATE, "set_instance first");
+    for (int32_t i = 0; i < h->nb_vars; ++i) {
+        if (lb) lb[i] = h->box_set ? h->box_lb[i] : 0.0;
+        if (ub) ub[i] = h->box_set ? h->box_ub[i] : 1.0;
+    }
+    if (is_set) *is_set = h->box_set ? 1 : 0;
+    return SDPCUT_OK;
+}
+
+int sdpcut_get_box_tables(sdpcut_handle h, double *Q_box, double *vars_box)
+{
+    if (!h) return SDPCUT_EINVAL;
+    SDPCUT_NO_PENDING(h);
+    if (!h->box_set) return sdpcut_fail(h, SDPCUT_ESTATE, "get_box_tables: no node box is set");
+    if (vars_box && !h->have_point) return sdpcut_fail(h, SDPCUT_ESTATE, "get_box_tables: set_point first");
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (Q_box) HIP_TRY(h, hipMemcpyAsync(Q_box, h->d_Q_box, (size_t)h->L * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (vars_box)
+        HIP_TRY(h, hipMemcpyAsync(vars_box, h->d_vars_box, (size_t)(h->L + h->nb_vars) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, sdpcut_sync(h));
+    return SDPCUT_OK;
+}
+
+} // extern "C"

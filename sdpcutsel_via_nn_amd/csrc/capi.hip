@@ -105,6 +105,7 @@ int sdpcut_destroy(sdpcut_handle h)
     free_diverse_ws(h);
     free_multi_ws(h);
     free_pool_ws(h);
+    box_clear(h);
     (void)hipFree(h->d_sdp_unconverged);
     (void)hipFree(h->d_tri); (void)hipFree(h->d_tri_dense3);
     if (h->pinned) (void)hipHostFree(h->pinned);
@@ -166,6 +167,7 @@ int sdpcut_set_option(sdpcut_handle h, int option, int64_t value)
         return SDPCUT_OK;
     case SDPCUT_OPT_EXACT_HEAD:
         SDPCUT_NO_PENDING(h);
+        if (value != 0) SDPCUT_NO_BOX(h, "SDPCUT_OPT_EXACT_HEAD");      // (the reference has no boxes: no reference-exact bits at a node)
         h->exact_head = value != 0;
         return SDPCUT_OK;
     case SDPCUT_OPT_EXACT_SDP:

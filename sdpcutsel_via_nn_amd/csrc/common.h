@@ -146,6 +146,12 @@ struct sdpcut_ctx {
     int64_t *shard_rec = nullptr;
     int64_t shard_rec_count = 0, shard_rec_len = -1;
     bool have_point = false;
+    // node box (box.hip, sdpcut_set_box): the tables SDPCUT_NN / SDPCUT_SDP are computed from while a box is set
+    bool box_set = false;
+    double *d_box_ld = nullptr;    // [2 n]: l | d = u - l
+    double *d_Q_box = nullptr;     // [L] Q'
+    double *d_vars_box = nullptr;  // [L + n] the transformed point; follows d_vars in stream order (box_after_point)
+    std::vector<double> box_lb, box_ub;
 
     int64_t N = 0, base = 0;
     int32_t row_len_max = 5;       // k + k(k+1)/2 of the largest candidate size present
@@ -380,6 +386,25 @@ void free_exact_ws(sdpcut_ctx *h);
     do {                                                                                                                  \
         if ((h)->exact_head)                                                                                              \
             return sdpcut_fail((h), SDPCUT_ESTATE, "SDPCUT_OPT_EXACT_HEAD is on: the sharded rounds have no exact merge"); \
+    } while (0)
+
+// box.hip (node boxes, include/sdpcut.h: sdpcut_set_box)
+// the tables a launch that computes `flags` reads: the box tables where a box is set and the launch computes SDPCUT_NN or SDPCUT_SDP
+// (never together with SDPCUT_EIG: launch_score splits such a call), else the originals
+static inline const double *score_vars(const sdpcut_ctx *h, uint32_t flags)
+{
+    return (h->box_set && (flags & (SDPCUT_NN | SDPCUT_SDP)) && !(flags & SDPCUT_EIG)) ? h->d_vars_box : h->d_vars;
+}
+static inline const double *score_Q(const sdpcut_ctx *h, uint32_t flags)
+{
+    return (h->box_set && (flags & (SDPCUT_NN | SDPCUT_SDP)) && !(flags & SDPCUT_EIG)) ? h->d_Q_box : h->d_Q;
+}
+int box_after_point(sdpcut_ctx *h);   // the transformed point from d_vars, behind its copy on the handle's stream; nothing without a box
+void box_clear(sdpcut_ctx *h);        // drop the box and its tables (the caller has waited for the stream)
+#define SDPCUT_NO_BOX(h, what)                                                                                            \
+    do {                                                                                                                  \
+        if ((h)->box_set)                                                                                                 \
+            return sdpcut_fail((h), SDPCUT_ESTATE, std::string(what) + ": a node box is set (sdpcut_set_box); clear it first"); \
     } while (0)
 
 // dense.hip

@@ -88,10 +88,11 @@ int launch_exact_sdp(sdpcut_ctx *h)
         HIP_TRY(h, hipMalloc((void **)&h->d_sdp_gap, nn * sizeof(double)));
     }
     HIP_TRY(h, hipMemsetAsync(h->d_sdp_unconverged, 0, sizeof(unsigned long long), h->stream));
-#define ESDP_LAUNCH(KK)                                                                                                              \
+    const double *vars = score_vars(h, SDPCUT_SDP), *Q = score_Q(h, SDPCUT_SDP);      // (the box tables at a node, common.h)
+#define ESDP_LAUNCH(KK)                                                                                                            \
     if (h->bucket[KK].n > 0)                                                                                                         \
         hipLaunchKernelGGL((exact_sdp_kernel<KK>), dim3((unsigned)((h->bucket[KK].n + 63) / 64)), dim3(64), 0, h->stream, h->bucket[KK].d_set, \
-                           h->bucket[KK].d_orig, h->bucket[KK].n, h->d_vars, h->d_Q, h->nb_vars, h->L, h->d_sdp, h->d_sdp_gap, h->d_sdp_unconverged)
+                           h->bucket[KK].d_orig, h->bucket[KK].n, vars, Q, h->nb_vars, h->L, h->d_sdp, h->d_sdp_gap, h->d_sdp_unconverged)
     ESDP_LAUNCH(5);
     ESDP_LAUNCH(4);
     ESDP_LAUNCH(3);

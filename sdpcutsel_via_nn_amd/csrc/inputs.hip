@@ -90,6 +90,7 @@ int sdpcut_set_instance(sdpcut_handle h, int32_t nb_vars, const double *Q_arr)
     HIP_TRY(h, sdpcut_sync(h));
     const int64_t L = (int64_t)nb_vars * (nb_vars + 1) / 2;
     hipFree(h->d_Q); hipFree(h->d_vars);
+    box_clear(h);      // (a box belongs to the instance it was set for)
     h->d_Q = nullptr; h->d_vars = nullptr; h->have_point = false; h->scored = 0; h->obj_partial = false;
     HIP_TRY(h, hipMalloc((void **)&h->d_Q, L * sizeof(double)));
     HIP_TRY(h, hipMalloc((void **)&h->d_vars, (L + nb_vars) * sizeof(double)));
@@ -206,6 +207,7 @@ int sdpcut_set_point(sdpcut_handle h, const double *vars_values)
     // in front of every round
     rc = launch_point_copy(h, (const double *)h->point_stage_dev, h->L + h->nb_vars);
     if (rc) return rc;
+    if ((rc = box_after_point(h))) return rc;
     h->point_inflight = true;
     h->have_point = true;
     h->scored = 0; h->obj_partial = false;
@@ -222,6 +224,8 @@ int sdpcut_set_point_device(sdpcut_handle h, const void *d_vars_values)
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipMemcpyAsync(h->d_vars, d_vars_values, (h->L + h->nb_vars) * sizeof(double),
                               hipMemcpyDeviceToDevice, h->stream));
+    int rc = box_after_point(h);
+    if (rc) return rc;
     h->have_point = true;
     h->scored = 0; h->obj_partial = false;
     h->last_total = -1;

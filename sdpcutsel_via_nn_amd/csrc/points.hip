@@ -224,6 +224,7 @@ int sdpcut_score_points(sdpcut_handle h, int32_t n_points, const double *points,
     if (((flags & SDPCUT_EIG) && !eig_out) || ((flags & SDPCUT_NN) && !obj_out))
         return sdpcut_fail(h, SDPCUT_EINVAL, "the output array of a measure that is asked for is NULL");
     SDPCUT_NO_PENDING(h);
+    SDPCUT_NO_BOX(h, "sdpcut_score_points");      // (one Q for all points; a per-point Q' stride is a later step)
     HIP_TRY(h, hipSetDevice(h->device));
     NoPointAfter leave(h);
     const int P = n_points;
@@ -258,6 +259,7 @@ int sdpcut_round_csr_points(sdpcut_handle h, int32_t n_points, const double *poi
         return sdpcut_fail(h, SDPCUT_EINVAL, "sdpcut_round_csr_points serves strategies 1 (feasibility), 2 (optimality) and 4 (combined)");
     if (sel_size < 0) return sdpcut_fail(h, SDPCUT_EINVAL, "sel_size is negative");
     SDPCUT_NO_PENDING(h);
+    SDPCUT_NO_BOX(h, "sdpcut_round_csr_points");
     HIP_TRY(h, hipSetDevice(h->device));
     NoPointAfter leave(h);
     const int P = n_points;

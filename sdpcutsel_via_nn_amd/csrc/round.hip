@@ -44,6 +44,10 @@ int score_for_selection(sdpcut_ctx *h, int strat, int64_t sel_size, int64_t cap,
     // a measure a skipped round left partial (same point, another selection): whole before anything ranks or counts by it -- a
     // feasibility selection too, whose nb_positive reads it
     if ((rc = obj_complete(h))) return rc;
+    // a node box: the optimality measure comes from other tables than lambda_min, so no one launch can count for the selection --
+    // score first (sdpcut_score: an EIG launch on the original tables, an NN launch on the box tables); the selection below is
+    // then the one of a list scored already
+    if (h->box_set && (need & SDPCUT_NN) && (h->scored & need) != need && (rc = sdpcut_score(h, need & ~h->scored))) return rc;
     const int fast_mode = (h->scored & need) == 0 ? rank_fast_mode(h, strat, sel_size, cap, nullptr) : 0;
     const bool want_auto = allow_auto && strat == SDPCUT_STRAT_COMB;
     // (the short-list predicate must be the one topk_select_enqueue will evaluate: it sees the tie-aware combined modes only when

@@ -207,7 +207,17 @@ static int launch_score_form(sdpcut_ctx *h, uint32_t flags, const ScoreFuse *fus
 
 int launch_score(sdpcut_ctx *h, uint32_t flags, const ScoreFuse *fuse, bool *fused, int64_t *strong_out)
 {
-    const int rc = launch_score_form(h, flags, fuse, fused, strong_out);
+    int rc;
+    if (h->box_set && (flags & SDPCUT_EIG) && (flags & SDPCUT_NN)) {
+        // a node box: lambda_min from the original tables, the optimality measure from the box tables -- two launches, nothing
+        // counted for a selection (no class of the keys can be told from one of them alone: round.hip scores first with a box)
+        if (fuse || strong_out) return sdpcut_fail(h, SDPCUT_ESTATE, "score: no fused launch while a node box is set");
+        if (fused) *fused = false;
+        rc = launch_score_form(h, SDPCUT_EIG, nullptr, nullptr, nullptr);
+        if (!rc) rc = launch_score_form(h, SDPCUT_NN, nullptr, nullptr, nullptr);
+    } else {
+        rc = launch_score_form(h, flags, fuse, fused, strong_out);
+    }
     // a launch that wrote the optimality measure of every candidate has completed what a skipped round left partial
     if (!rc && (flags & SDPCUT_NN) && h->obj_partial && !h->skip_launched) {
         h->obj_partial = false;

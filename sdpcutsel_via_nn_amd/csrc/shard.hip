@@ -96,6 +96,7 @@ extern "C" int sdpcut_shard_head_device(sdpcut_handle h, int strat, int64_t coun
     if (!h) return SDPCUT_EINVAL;
     SDPCUT_NO_PENDING(h);
     SDPCUT_NO_EXACT(h);
+    SDPCUT_NO_BOX(h, "sharded rounds");
     if (count < 1 || count > TK_MAXK || !d_record) return sdpcut_fail(h, SDPCUT_EINVAL, "shard head: count must be 1.." + std::to_string(TK_MAXK));
     const bool comball = strat == SDPCUT_PART_COMBALL;
     if (strat != SDPCUT_STRAT_FEAS && strat != SDPCUT_STRAT_OPT && strat != SDPCUT_PART_STRONG && !comball)
@@ -164,6 +165,7 @@ extern "C" int sdpcut_shard_finish_enqueue(sdpcut_handle h, int32_t world, int64
     if (!h) return SDPCUT_EINVAL;
     SDPCUT_NO_PENDING(h);
     SDPCUT_NO_EXACT(h);
+    SDPCUT_NO_BOX(h, "sharded rounds");
     const int64_t rl = SHARD_HDR + (int64_t)fields * count;
     if (pitch_words == 0) pitch_words = rl;
     if (world < 1 || count < 1 || !d_allrec || sel_size < 1 || sel_size > (int64_t)world * count || (fields != 2 && fields != 3) ||

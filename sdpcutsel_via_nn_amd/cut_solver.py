@@ -76,6 +76,8 @@ class GpuCutSelectionMixin(object):
     # called with, or cuts_per_set times that with cuts_row_quota = "sets".  make_dropin_classes(..., cuts_per_set=m) sets it.
     cuts_per_set = 1
     cuts_row_quota = None
+    # the variable bounds of the branch-and-bound node the solver works at (set_node_box): None = the root's unit box
+    _gpu_node_box = None
 
     # ------------------------------------------------------------------ a11 loader
     def _load_neural_nets(self):
@@ -138,6 +140,8 @@ class GpuCutSelectionMixin(object):
         sc = self._gpu_new_scorer()
         sc.set_instance(self._nb_vars, np.asarray(self._Q_arr, dtype=np.float64))
         sc.set_candidates(S[:N], ks[:N])
+        if self._gpu_node_box is not None:
+            sc.set_box(*self._gpu_node_box)
         b = _Binding(sc, agg, self._nb_vars, self._nb_lifted)
         b.n_at_bind = N
         b.ks, b.set_arr = ks[:N], S[:N]
@@ -152,9 +156,41 @@ class GpuCutSelectionMixin(object):
         sc = self._gpu_new_scorer()
         sc.set_instance(nb_vars, Q_arr)
         sc.set_candidates(set_inds, ks, global_base)
+        if self._gpu_node_box is not None:
+            sc.set_box(*self._gpu_node_box)
         b = _Binding(sc, None, nb_vars, nb_vars * (nb_vars + 1) // 2)
         b.set_arr, b.ks, b.n_at_bind = np.asarray(set_inds), np.asarray(ks), len(ks)
         return b
+
+    def set_node_box(self, lb, ub):
+        """The solver works at a branch-and-bound node with the variable bounds ``lb <= x <= ub`` (both None: back at the root):
+        every handle bound to the solver, and every one it creates later (:meth:`_gpu_bind` for a host-side list,
+        :meth:`gpu_bind_arrays`), computes the optimality measures of strategies 2, 3 and 4 for the node's small SDP
+        (``Scorer.set_box``, :mod:`nodebox`); eigenvalues, the violated test and the cuts do not depend on bounds.  A list that
+        lives on a scorer of its own (``DeviceAgg``) and is bound AFTER this call keeps whatever box that scorer has: set it
+        there, or call this method again once the list is bound.  ``cut_select_algo`` takes its box as an argument and neither
+        uses nor changes this one.  The caller's LP carries the node's bounds itself (``harness.boxqp_relaxation(inst, lb, ub)``)."""
+        self._gpu_node_box = box = self._gpu_check_box(lb, ub)
+        for b in (getattr(self, "_gpu_bindings", None) or {}).values():
+            self._gpu_apply_box(b, box)
+
+    def _gpu_check_box(self, lb, ub):
+        """(lb, ub) as checked [n] arrays (scalars are broadcast), or None for no box"""
+        if lb is None and ub is None:
+            return None
+        from .nodebox import check_box
+        n = self._nb_vars
+        return check_box(n, np.broadcast_to(np.asarray(lb, dtype=np.float64), (n,)), np.broadcast_to(np.asarray(ub, dtype=np.float64), (n,)))
+
+    @staticmethod
+    def _gpu_apply_box(b, box):
+        b.drain()
+        if box is None:
+            b.scorer.clear_box()
+        else:
+            b.scorer.set_box(*box)
+        b.scored &= _capi.EIG      # (the library keeps lambda_min and drops the measures of the old box)
+        b.rank_serial += 1
 
     @staticmethod
     def _gpu_point(b, vars_values, flags):
@@ -480,16 +516,35 @@ class GpuCutSelectionMixin(object):
     # the reference's loop reaches it through the name-mangled private name (cut_select_qp.py:166)
     _CutSolver__gen_dense_eigcuts = _gen_dense_eigcuts
 
-    def separate_points(self, strat, points, sel_size):
+    def separate_points(self, strat, points, sel_size, boxes=None):
         """One separation round at EACH of several LP points of the bound instance in one device call (sdpcut_round_csr_points):
         the open nodes of a tree search, the children of a dive.  points [P, L + n]; strat 1, 2 or 4; sel_size as
         ``_sel_eigcut_by_ordering_on_measure`` takes it (a number of cuts).
         -> list of P tuples ``(csr, n_total, new_strat, counters)``: ``csr = (indptr, indices, values, rhs)`` is what
         :meth:`_gpu_add_csr` takes -- the caller adds each node's cuts to that node's LP -- and the rest is what the single-point
         selection reports (length of the ranking, the combined strategy's switch, its counters).  The arrays are views of the
-        scorer's batch block, good until its next call; the scorer holds no current LP point afterwards."""
+        scorer's batch block, good until its next call; the scorer holds no current LP point afterwards.
+        ``boxes`` [P, 2, n]: the variable bounds (lb, ub) of each point's node.  The points are then served one by one inside the
+        call -- ``set_box``, the single-point round -- because the point-axis kernels have one Q for all points (a one-launch route
+        for boxed batches is a later step); the arrays are copies, and the solver's own node box
+        (:meth:`set_node_box`) is in place again afterwards."""
         b = self._gpu_bind()
         b.drain()
+        if boxes is not None:
+            pts = np.asarray(points, dtype=np.float64)
+            bx = np.asarray(boxes, dtype=np.float64)
+            if pts.ndim != 2 or bx.shape != (pts.shape[0], 2, self._nb_vars):
+                raise ValueError("boxes must be [P, 2, n]: (lb, ub) per point")
+            out = []
+            try:
+                for p in range(pts.shape[0]):
+                    b.scorer.set_box(bx[p, 0], bx[p, 1])
+                    r = b.scorer.round_csr(strat, sel_size, point=pts[p], copy=True)
+                    out.append(((r["indptr"], r["indices"], r["values"], r["rhs"]), r["n_total"], r["new_strat"], r["counters"]))
+            finally:
+                b.point_copy, b.scored, b.point_token = None, 0, None
+                self._gpu_apply_box(b, self._gpu_node_box)
+            return out
         rounds = b.scorer.round_csr_points(points, strat, sel_size)
         b.point_copy, b.scored, b.point_token = None, 0, None      # (the next single-point selection uploads its point)
         return [((r["indptr"], r["indices"], r["values"], r["rhs"]), r["n_total"], r["new_strat"], r["counters"]) for r in rounds]
@@ -730,7 +785,7 @@ class CutSolver(GpuCutSelectionMixin):
     def cut_select_algo(self, filename, dim, sel_size, strat=2, nb_rounds_cuts=20, term_on=False,
                         triangle_on=False, strong_only=False, max_subs=_THRES_MAX_SUBS, on_round=None, plots=False, sol=0,
                         ch_ext=0, max_parallel=None, pool_factor=4, cuts_per_set=1, row_quota=None,
-                        pool_max_age=None, pool_drop_age=10, pool_return=None, pool_tight_tol=1e-9, pool_viol_tol=1e-6):
+                        pool_max_age=None, pool_drop_age=10, pool_return=None, pool_tight_tol=1e-9, pool_viol_tol=1e-6, box=None):
         """Cutting-plane rounds on a BoxQP ``.in`` file, same arguments and default return tuple as
         the reference's entry point (cut_select_qp.py:73-221), with HiGHS as LP solver, the native
         cover enumeration and the GPU selection / generation / triangle separation in between.
@@ -765,6 +820,10 @@ class CutSolver(GpuCutSelectionMixin):
         rounds is dropped.  Then the usual separation runs and its rows -- eigen-cuts and triangle rows, never the McCormick
         rows -- go into both the LP and the pool.  ``self.pool_log`` has one record per round: leave, enter, dropped, in_lp, parked
         (after the step), violated, lp_rows (rows of the LP that was just solved), added (rows the separation added).
+        ``box=(lb, ub)`` (scalars or [n] arrays; None = the root): the same loop at a branch-and-bound node with the variable bounds
+        ``lb <= x <= ub`` -- the LP is the node's relaxation (``harness.boxqp_relaxation(inst, lb, ub)``) and the optimality
+        measures are the node's (``Scorer.set_box`` on the run's own handle, DESIGN.md section 5 "Node boxes").  The run's box is
+        this argument alone: a box set with :meth:`set_node_box` is neither used nor changed.
         -> (bound per solve, total s, round s, separation s, PSD cuts per round, triangle cuts per
         round, number of candidates)."""
         from timeit import default_timer as clock
@@ -807,6 +866,9 @@ class CutSolver(GpuCutSelectionMixin):
         # the cover is enumerated on the device, straight into the scorer's candidate list
         sc = self._gpu_new_scorer()
         sc.set_instance(self._nb_vars, np.asarray(self._Q_arr, dtype=np.float64))
+        node_box = None if box is None else self._gpu_check_box(*box)      # (the run's own: set_node_box's is left alone)
+        if node_box is not None:
+            sc.set_box(*node_box)
         n_cand = sc.set_candidates_cover(inst["adj"], dim, max_subs=max_subs or 0, ch_ext=ch_ext)
         if ch_ext:      # :396 -- everything after the cover sees the extended pattern
             inst = dict(inst, adj=_capi.chordal_extension(inst["adj"])[0])
@@ -817,7 +879,7 @@ class CutSolver(GpuCutSelectionMixin):
         self._agg_list = DeviceAgg(sc, n_cand, self._nb_vars, self._Q_arr)
         quota = self.selection_size(sel_size, n_cand)
         t_model = clock()
-        self._my_prob = lp = harness.boxqp_relaxation(inst)
+        self._my_prob = lp = harness.boxqp_relaxation(inst, *(node_box or ()))
         t_model = clock() - t_model
         if triangle_on:
             self._preprocess_triangle_ineq()

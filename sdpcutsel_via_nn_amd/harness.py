@@ -310,10 +310,66 @@ def mccormick_csr(nb_vars, adj):
     return indptr, cols[live], vals[live], rhs
 
 
-def boxqp_relaxation(inst):
-    """McCormick relaxation M of a parsed BoxQP instance, ready to solve."""
+def mccormick_csr_box(nb_vars, adj, lb, ub):
+    """:func:`mccormick_csr` at a node with the variable bounds ``lb <= x <= ub`` (a sub-box of the unit box): ONE CSR block of
+    "<=" rows over [X packed | x], with l = lb, u = ub:
+
+        per variable i:      X_ii - (l_i + u_i) x_i <= -l_i u_i                      (secant)
+                            -X_ii + 2 u_i x_i <= u_i^2,   -X_ii + 2 l_i x_i <= l_i^2  (tangents at u and at l)
+                             x_i <= u_i,   -x_i <= -l_i
+        per edge i < j:     -X_ij + u_j x_i + u_i x_j <= u_i u_j,    X_ij - u_j x_i - l_i x_j <= -l_i u_j,
+                             X_ij - l_j x_i - u_i x_j <= -u_i l_j,  -X_ij + l_j x_i + l_i x_j <= l_i l_j
+
+    Rows that reduce to the column bounds 0 <= v <= 1 of the LP are left out (the tangent at l_i = 0, x_i <= 1, x_i >= 0, the last
+    edge row at l_i = l_j = 0) and so are entries whose coefficient is zero: on the unit box this IS mccormick_csr's block, same
+    order.  Rows are emitted variable by variable, a variable's diagonal rows first and then its edges by ascending j.
+    -> (indptr, indices, values, rhs)."""
+    n = int(nb_vars)
+    L = n * (n + 1) // 2
+    l, u = np.asarray(lb, dtype=np.float64), np.asarray(ub, dtype=np.float64)
+    assert l.shape == (n,) and u.shape == (n,)
+    A = np.asarray(adj) != 0
+    i_d = np.arange(n, dtype=np.int64)
+    X_d = n * i_d - i_d * (i_d - 1) // 2                      # packed position of X_ii
+    ei, ej = np.nonzero(np.triu(A, 1))
+    ei, ej = ei.astype(np.int64), ej.astype(np.int64)
+    X_e = X_d[ei] + (ej - ei)
+    none, nonee = -np.ones(n, np.int64), -np.ones(ei.size, np.int64)
+    z, ze = np.zeros(n), np.zeros(ei.size)
+    li, lj, ui, uj = l[ei], l[ej], u[ei], u[ej]
+    # three slots per row, unused slot = -1; sort key = (variable, diagonal rows first, j, row kind); keep = the row says more than a column bound
+    W = 4 * n + 5
+    blocks = [
+        (i_d * W + 0, np.stack([X_d, L + i_d, none], 1), np.stack([z + 1.0, -(l + u), z], 1), 0.0 - l * u, np.ones(n, bool)),
+        (i_d * W + 1, np.stack([X_d, L + i_d, none], 1), np.stack([z - 1.0, 2.0 * u, z], 1), u * u, np.ones(n, bool)),
+        (i_d * W + 2, np.stack([X_d, L + i_d, none], 1), np.stack([z - 1.0, 2.0 * l, z], 1), l * l, l > 0.0),
+        (i_d * W + 3, np.stack([L + i_d, none, none], 1), np.stack([z + 1.0, z, z], 1), u, u < 1.0),
+        (i_d * W + 4, np.stack([L + i_d, none, none], 1), np.stack([z - 1.0, z, z], 1), 0.0 - l, l > 0.0),
+        (ei * W + 5 + 4 * ej + 0, np.stack([X_e, L + ei, L + ej], 1), np.stack([ze - 1.0, uj, ui], 1), ui * uj, np.ones(ei.size, bool)),
+        (ei * W + 5 + 4 * ej + 1, np.stack([X_e, L + ei, L + ej], 1), np.stack([ze + 1.0, -uj, -li], 1), 0.0 - li * uj, np.ones(ei.size, bool)),
+        (ei * W + 5 + 4 * ej + 2, np.stack([X_e, L + ei, L + ej], 1), np.stack([ze + 1.0, -lj, -ui], 1), 0.0 - ui * lj, np.ones(ei.size, bool)),
+        (ei * W + 5 + 4 * ej + 3, np.stack([X_e, L + ei, L + ej], 1), np.stack([ze - 1.0, lj, li], 1), li * lj, (li > 0.0) | (lj > 0.0)),
+    ]
+    key = np.concatenate([b[0][b[4]] for b in blocks])
+    cols = np.concatenate([b[1][b[4]] for b in blocks])
+    vals = np.concatenate([b[2][b[4]] for b in blocks])
+    rhs = np.concatenate([b[3][b[4]] for b in blocks])
+    order = np.argsort(key, kind="stable")
+    cols, vals, rhs = cols[order], vals[order], rhs[order]
+    live = (cols >= 0) & (vals != 0.0)
+    indptr = np.concatenate([[0], np.cumsum(live.sum(axis=1))]).astype(np.int64)
+    return indptr, cols[live], vals[live], rhs
+
+
+def boxqp_relaxation(inst, lb=None, ub=None):
+    """McCormick relaxation M of a parsed BoxQP instance, ready to solve; with ``lb`` / ``ub`` the relaxation of the node with
+    those variable bounds (:func:`mccormick_csr_box`; a bound left None is the unit box's)."""
     lp = LinearRelaxation(np.concatenate([inst["Q_arr"], inst["c"]]))
-    lp.linear_constraints.add_csr(*mccormick_csr(inst["nb_vars"], inst["adj"]), "L")
+    if lb is None and ub is None:
+        lp.linear_constraints.add_csr(*mccormick_csr(inst["nb_vars"], inst["adj"]), "L")
+    else:
+        n = inst["nb_vars"]
+        lp.linear_constraints.add_csr(*mccormick_csr_box(n, inst["adj"], np.zeros(n) if lb is None else lb, np.ones(n) if ub is None else ub), "L")
     return lp
 
 
