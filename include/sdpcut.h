@@ -143,10 +143,18 @@ enum { SDPCUT_KERNEL_MFMA = 0, SDPCUT_KERNEL_SIMPLE = 1, SDPCUT_KERNEL_VALU = 2 
  * (sdpcut_get_scores, sdpcut_rank*, sdpcut_gather_scores_device, diverse / multi-cut / pool rounds, strategy 2):
  * SDPCUT_STAT_NN_COMPLETIONS counts those launches, SDPCUT_STAT_SCORED reports SDPCUT_NN either way.
  * 1: lists the score kernel cuts into strips of 64 (more than 65 536 candidates on a 256-CU device); 0: never; 2: every list (tests). */
+/* SDPCUT_OPT_FP32_FILTER (default 1): where a launch under SDPCUT_OPT_SKIP_NONVIOLATED runs and the class's network qualifies
+ * (sdpcut_get_filter_margin), the violated candidates first go through the network in fp32 on the matrix cores; the fp64 pass
+ * then runs only for those whose fp32 measure exceeds -margin * max_elem, margin a PROVEN bound on the difference of the two network
+ * outputs (csrc/net_pack.h), and for candidates with an input outside the domain the bound was derived on.  Every violated
+ * candidate with a positive measure is among them: same head, scores, rows, new_strat and counters as with the option off, bit for
+ * bit; the others keep their fp32 measure, which is not positive, until the measure is completed on demand exactly as under
+ * SDPCUT_OPT_SKIP_NONVIOLATED (no call returns it before).
+ * 0: never filter. */
 enum { SDPCUT_OPT_KERNEL = 1, SDPCUT_OPT_TIMING = 2, SDPCUT_OPT_FUSE_KEYS = 3, SDPCUT_OPT_AUTO_REGIME = 4,
        SDPCUT_OPT_FUSED_TAIL = 5, SDPCUT_OPT_COOP_LAUNCH = 6, SDPCUT_OPT_EIG_KERNEL = 7, SDPCUT_OPT_STREAM_PRIORITY = 8,
        SDPCUT_OPT_SIDE_STREAMS = 9, SDPCUT_OPT_ONE_LAUNCH = 10, SDPCUT_OPT_PREFILTER = 11, SDPCUT_OPT_EXACT_HEAD = 12, SDPCUT_OPT_EXACT_SDP = 13,
-       SDPCUT_OPT_COUNT_RANK = 14, SDPCUT_OPT_SKIP_NONVIOLATED = 15 };
+       SDPCUT_OPT_COUNT_RANK = 14, SDPCUT_OPT_SKIP_NONVIOLATED = 15, SDPCUT_OPT_FP32_FILTER = 16 };
 
 /* Counters of a handle: SDPCUT_STAT_ROUNDS = fused rounds served (sdpcut_select_round*),
  * SDPCUT_STAT_SELECT_FALLBACKS = rounds whose radix selection declared itself void (a grid barrier
@@ -173,13 +181,25 @@ enum { SDPCUT_OPT_KERNEL = 1, SDPCUT_OPT_TIMING = 2, SDPCUT_OPT_FUSE_KEYS = 3, S
  * SDPCUT_STAT_NN_SKIPPED = candidates the handle's last scoring launch did not run the MLP for: list length - nb_violated after a
  *   launch under SDPCUT_OPT_SKIP_NONVIOLATED, 0 after any other (a completion included) and after a new list; after
  *   sdpcut_shard_head_device it is read from the device: the call waits for the handle's stream;
- * SDPCUT_STAT_NN_COMPLETIONS = NN scoring launches since the handle was made that completed a measure such a launch left partial. */
+ * SDPCUT_STAT_NN_COMPLETIONS = NN scoring launches since the handle was made that completed a measure such a launch left partial.
+ * SDPCUT_STAT_NN_EVALUATED = fp64 MLP evaluations of the handle's last scoring launch that ran the network: the list length after a
+ *   launch that scored everybody, nb_violated after a skipping launch, the survivors of the fp32 filter after a filtering one (read
+ *   from the device: the call waits for the handle's stream); 0 after a new list. */
 enum { SDPCUT_STAT_ROUNDS = 1, SDPCUT_STAT_SELECT_FALLBACKS = 2, SDPCUT_STAT_SCORED = 3, SDPCUT_STAT_TIE_SPLITS = 4,
        SDPCUT_STAT_DIRECT_SELECTIONS = 5, SDPCUT_STAT_PF_BIN = 6, SDPCUT_STAT_PF_FLOOR = 7, SDPCUT_STAT_PF_COUNT = 8,
        SDPCUT_STAT_EXACT_HEAD = 9, SDPCUT_STAT_EXACT_GAVE_UP = 10, SDPCUT_STAT_EXACT_RETRIES = 11,
        SDPCUT_STAT_SDP_UNCONVERGED = 12, SDPCUT_STAT_POINTS_REDONE = 13,
-       SDPCUT_STAT_NN_SKIPPED = 14, SDPCUT_STAT_NN_COMPLETIONS = 15 };
+       SDPCUT_STAT_NN_SKIPPED = 14, SDPCUT_STAT_NN_COMPLETIONS = 15, SDPCUT_STAT_NN_EVALUATED = 16 };
 int sdpcut_get_stat(sdpcut_handle h, int which, int64_t *value);
+
+/* The fp32 filter (SDPCUT_OPT_FP32_FILTER) of the network set for k-variable candidates: *margin = the proven bound on
+ * |y32 - y64| of the unmapped network output the filter decides by, or NaN if that network does not filter (not clamp-free, not
+ * the shipped 3-variable shape, or a bound above the cut-off).  SDPCUT_ESTATE without a network for k. */
+int sdpcut_get_filter_margin(sdpcut_handle h, int k, double *margin);
+/* Audit of that bound on the device: runs the filter's fp32 pass -- the device function the scoring kernel runs -- for EVERY
+ * candidate of the handle's list at the current point and returns the fp32 network output, unmapped, in y32_out [N] (caller
+ * order).  The list must hold 3-variable candidates only and their network must filter; no node box.  Not a hot path. */
+int sdpcut_filter_audit(sdpcut_handle h, double *y32_out);
 
 /* Maximum sub-problem size (assert dim <= 5, cut_select_qp.py:93) */
 #define SDPCUT_MAX_K 5

@@ -30,6 +30,8 @@ OPT_COUNT_RANK = 14      # the sort tail of a selection ranks by counting in one
 STAT_SDP_UNCONVERGED = 12
 OPT_SKIP_NONVIOLATED = 15   # fused combined rounds run the MLP for violated candidates only (include/sdpcut.h); 0 never, 1 long lists (default), 2 every list
 STAT_NN_SKIPPED, STAT_NN_COMPLETIONS = 14, 15   # candidates the last such launch skipped; NN launches that completed a partial measure
+OPT_FP32_FILTER = 16     # the skipping launch filters the violated candidates in fp32 ahead of the fp64 pass (include/sdpcut.h); default on
+STAT_NN_EVALUATED = 16   # fp64 MLP evaluations of the last scoring launch that ran the network
 STAT_POINTS_REDONE = 13   # points of batched rounds served by the single-point round inside the call (include/sdpcut.h)
 BATCH_MAX_POINTS = 256   # SDPCUT_BATCH_MAX_POINTS: most LP points of one score_points / round_csr_points call
 DIVERSE_MAX_POOL = 16384   # SDPCUT_DIVERSE_MAX_POOL: longest pool of round_csr_diverse / list of filter_parallel
@@ -98,6 +100,8 @@ SIGNATURES = {
     "sdpcut_set_option": [_vp, _c.c_int, _c.c_int64],
     "sdpcut_set_stream": [_vp, _vp],
     "sdpcut_get_stat": [_vp, _c.c_int, _i64p],
+    "sdpcut_get_filter_margin": [_vp, _c.c_int, _dp],
+    "sdpcut_filter_audit": [_vp, _dp],
     "sdpcut_synchronize": [_vp],
     "sdpcut_wake": [_vp],
     "sdpcut_set_network": [_vp, _c.c_int, _c.c_int, _i32p, _dp, _c.c_int64],
@@ -484,6 +488,20 @@ class Scorer(object):
         v = _c.c_int64(0)
         self._check(self._lib.sdpcut_get_stat(self._h, int(which), ctypes.byref(v)))
         return int(v.value)
+
+    def filter_margin(self, k):
+        """the proven bound on |y32 - y64| the fp32 filter of the k-variable network decides by (sdpcut_get_filter_margin); NaN if
+        that network does not filter"""
+        v = _c.c_double(0.0)
+        self._check(self._lib.sdpcut_get_filter_margin(self._h, int(k), ctypes.byref(v)))
+        return float(v.value)
+
+    def filter_audit(self):
+        """the filter's fp32 network output, unmapped, of every candidate of a 3-variable list at the current point
+        (sdpcut_filter_audit) -> float64 [N]"""
+        y = np.empty(self.N, dtype=np.float64)
+        self._check(self._lib.sdpcut_filter_audit(self._h, _ptr(y, _dp)))
+        return y
 
     def wake(self):
         """an empty kernel on the handle's stream (sdpcut_wake): poke an idle device while the LP solution is still being extracted"""

@@ -79,8 +79,8 @@ int sdpcut_create(int device_id, sdpcut_handle *out)
     h->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     if (hipSetDevice(device_id) != hipSuccess || hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess ||
         hipMalloc((void **)&h->d_counters, 8 * sizeof(int64_t)) != hipSuccess ||
-        hipMalloc((void **)&h->d_stats, 5 * sizeof(unsigned long long)) != hipSuccess ||
-        hipMemset(h->d_stats, 0, 5 * sizeof(unsigned long long)) != hipSuccess) {
+        hipMalloc((void **)&h->d_stats, 6 * sizeof(unsigned long long)) != hipSuccess ||
+        hipMemset(h->d_stats, 0, 6 * sizeof(unsigned long long)) != hipSuccess) {
         delete h;
         return sdpcut_fail(nullptr, SDPCUT_EHIP, "stream / counter allocation failed");
     }
@@ -165,6 +165,10 @@ int sdpcut_set_option(sdpcut_handle h, int option, int64_t value)
         if (value < 0 || value > 2) return sdpcut_fail(h, SDPCUT_EINVAL, "SDPCUT_OPT_SKIP_NONVIOLATED: 0 never, 1 long lists, 2 every list");
         h->skip_nonviolated = (int)value;
         return SDPCUT_OK;
+    case SDPCUT_OPT_FP32_FILTER:
+        SDPCUT_NO_PENDING(h);
+        h->fp32_filter = value != 0;
+        return SDPCUT_OK;
     case SDPCUT_OPT_EXACT_HEAD:
         SDPCUT_NO_PENDING(h);
         if (value != 0) SDPCUT_NO_BOX(h, "SDPCUT_OPT_EXACT_HEAD");      // (the reference has no boxes: no reference-exact bits at a node)
@@ -210,6 +214,24 @@ int sdpcut_get_stat(sdpcut_handle h, int which, int64_t *value)
     // (a skipped round has scored the optimality measure -- of every candidate its ranking reads; the rest follows on demand)
     case SDPCUT_STAT_SCORED: *value = h->have_point ? (int64_t)(h->scored | (h->obj_partial ? (uint32_t)SDPCUT_NN : 0u)) : 0; return SDPCUT_OK;
     case SDPCUT_STAT_NN_COMPLETIONS: *value = h->stat_nn_completions; return SDPCUT_OK;
+    case SDPCUT_STAT_NN_EVALUATED:
+        if (h->nn_eval_mode == 2) {
+            unsigned long long v = 0;
+            HIP_TRY(h, hipSetDevice(h->device));
+            HIP_TRY(h, hipMemcpyAsync(&v, h->d_stats + 5, sizeof(v), hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(h, sdpcut_sync(h));
+            *value = (int64_t)v;
+            return SDPCUT_OK;
+        }
+        if (h->nn_eval_mode == 1) {
+            int64_t skipped = 0;
+            const int rc = sdpcut_get_stat(h, SDPCUT_STAT_NN_SKIPPED, &skipped);
+            if (rc) return rc;
+            *value = h->nn_eval_n - skipped;
+            return SDPCUT_OK;
+        }
+        *value = h->nn_eval_n;
+        return SDPCUT_OK;
     case SDPCUT_STAT_NN_SKIPPED:
         if (h->nn_skipped_on_device) {      // a sharded head: its violated count was copied to d_stats[4] behind the selection
             unsigned long long nviol = 0;
@@ -240,6 +262,34 @@ int sdpcut_get_stat(sdpcut_handle h, int which, int64_t *value)
     }
     }
     return sdpcut_fail(h, SDPCUT_EINVAL, "unknown statistic");
+}
+
+int sdpcut_get_filter_margin(sdpcut_handle h, int k, double *margin)
+{
+    if (!h || !margin) return SDPCUT_EINVAL;
+    if (k < 2 || k > SDPCUT_MAX_K) return sdpcut_fail(h, SDPCUT_EINVAL, "k must be 2..5");
+    if (!h->net[k].set) return sdpcut_fail(h, SDPCUT_ESTATE, "no network set for this candidate size");
+    *margin = h->net[k].dev.filter_ok ? h->net[k].dev.filter_margin : std::nan("");
+    return SDPCUT_OK;
+}
+
+int sdpcut_filter_audit(sdpcut_handle h, double *y32_out)
+{
+    if (!h || !y32_out) return SDPCUT_EINVAL;
+    SDPCUT_NO_PENDING(h);
+    SDPCUT_NO_BOX(h, "sdpcut_filter_audit");
+    if (h->N < 1 || h->bucket[3].n != h->N) return sdpcut_fail(h, SDPCUT_ESTATE, "filter audit: the list must hold 3-variable candidates only");
+    if (!h->have_point) return sdpcut_fail(h, SDPCUT_ESTATE, "set_point first");
+    if (!h->net[3].set || !h->net[3].dev.filter_ok) return sdpcut_fail(h, SDPCUT_ESTATE, "filter audit: the network of 3-variable candidates does not filter");
+    HIP_TRY(h, hipSetDevice(h->device));
+    double *d_y = nullptr;
+    HIP_TRY(h, hipMalloc((void **)&d_y, (size_t)h->N * sizeof(double)));
+    int rc = launch_filter_audit(h, d_y);
+    if (!rc && hipMemcpyAsync(y32_out, d_y, (size_t)h->N * sizeof(double), hipMemcpyDeviceToHost, h->stream) != hipSuccess)
+        rc = sdpcut_fail(h, SDPCUT_EHIP, "filter audit: copy failed");
+    if (!rc && sdpcut_sync(h) != hipSuccess) rc = sdpcut_fail(h, SDPCUT_EHIP, "filter audit: the kernel failed");
+    (void)hipFree(d_y);
+    return rc;
 }
 
 int sdpcut_set_stream(sdpcut_handle h, void *hip_stream)

@@ -38,6 +38,14 @@ struct NetDev {
     // into that interval (net_pack.h, sdpcut_set_network): the MFMA kernel then clamps the 9..20 inputs of a candidate once
     // instead of its 150..256 activations, and that clamp changes nothing on the domain
     int unclamped_ok;
+    // The fp32 filter of the skipping kernel (score_mfma.hip, stage F; net_pack.h has the packing and the derivation of the margin).
+    // filter_ok: clamp-free, the shipped 3-variable shape, margin below FILTER_MARGIN_CUTOFF; the pointers are set only then.
+    int filter_ok;
+    double filter_margin;      // proven bound on |y32 - y64| of the unmapped output for mapped inputs inside filter_box
+    const double *filter_box;  // [d_in][2]: lo, hi of every mapped input; a candidate outside bypasses the filter
+    const float *f32_in;       // (x -2 log2 e) input-layer A-fragments of v_mfma_f32_16x16x4_f32: [t][lane] float4, component = k-step
+    const float *f32_hid;      // (x -2 log2 e) hidden-layer A-fragments: [layer - 1][t][tk][lane] float4, component i = k-step (tk, i)
+    const float *f32_bias;     // (x -2 log2 e) [n_hidden][64] zero padded
 };
 
 struct Bucket {
@@ -118,7 +126,7 @@ struct sdpcut_ctx {
     bool eig_kernel = true;        // SDPCUT_OPT_EIG_KERNEL: eigenvalue-only launches run eig_only_kernel (eig.hip)
     bool pf_counted = false;       // the scoring launches of the current round all counted the fine histogram (launch_score)
     bool prefilter = true;         // SDPCUT_OPT_PREFILTER: fine histogram in the score kernels, direct selection (topk_dev.h)
-    unsigned long long *d_stats = nullptr;   // device counters that outlive a round: [0] direct selections, [1..3] its diagnostics, [4] nb_violated of a skipped sharded head
+    unsigned long long *d_stats = nullptr;   // device counters that outlive a round: [0] direct selections, [1..3] its diagnostics, [4] nb_violated of a skipped sharded head, [5] fp64 evaluations of a filtering launch
     bool coop_launch = false;      // SDPCUT_OPT_COOP_LAUNCH: cooperative launch of the kernels with grid barriers (+20 us per round)
     int64_t stat_rounds = 0, stat_fallbacks = 0, stat_tie_splits = 0;   // sdpcut_get_stat
     int64_t stat_points_redone = 0;   // SDPCUT_STAT_POINTS_REDONE
@@ -167,7 +175,15 @@ struct sdpcut_ctx {
     // SDPCUT_OPT_SKIP_NONVIOLATED (score_mfma_skip_kernel): 0 never, 1 lists score_plan cuts into strips of 64, 2 every list
     int skip_nonviolated = 1;
     bool skip_launched = false;    // the last launch_score ran the skipping kernel
-    // d_obj holds the optimality measure of the VIOLATED candidates only (a skipped round in its strong regime).  While set,
+    // SDPCUT_OPT_FP32_FILTER (score_mfma_filter_kernel): the skipping launch filters in fp32 where the network qualifies
+    bool fp32_filter = true;
+    bool filter_launched = false;  // ... and it was the filtering one
+    // SDPCUT_STAT_NN_EVALUATED of the last launch that ran the network: 0 everybody (nn_eval_n), 1 the violated candidates
+    // (nn_eval_n - SDPCUT_STAT_NN_SKIPPED), 2 the filter's survivors (d_stats[5], left there by the selection's first kernel)
+    int nn_eval_mode = 0;
+    int64_t nn_eval_n = 0;
+    // d_obj holds the optimality measure of a SUPERSET OF THE STRONG candidates only (a skipped round in its strong regime): of the
+    // violated ones, or -- behind the fp32 filter -- of the violated ones the filter could not prove non-positive.  While set,
     // `scored` carries no SDPCUT_NN -- whoever needs the measure scores it like a missing one, which completes the array
     // (launch_score counts that) -- and SDPCUT_STAT_SCORED still reports the bit.  Cleared with `scored`.
     bool obj_partial = false;
@@ -313,6 +329,7 @@ struct ScoreFuse {
 // obj_improve > 0 and lambda_min < -1e-15 to strong_out[workgroup % 8] (needs both flags; used by the device-resolved combined selection)
 int launch_score(sdpcut_ctx *h, uint32_t flags, const ScoreFuse *fuse = nullptr, bool *fused = nullptr,
                  int64_t *strong_out = nullptr);
+int launch_filter_audit(sdpcut_ctx *h, double *d_y32);   // score.hip: sdpcut_filter_audit's kernel over the (single) class 3, enqueued
 int launch_cut_rows(sdpcut_ctx *h, int64_t count, const int64_t *d_limit, const int64_t *d_idx, int64_t idx_base,
                     double *d_lam, double *d_coef, int coef_ld, double *d_rhs, int64_t *d_cols, int32_t *d_ks);
 // Epilogue of a fused round: rows of the ranking head + its ids, scores and the four counters,

@@ -12,13 +12,107 @@
 #define MAX_LAYERS 5
 #define SDPCUT_INPUT_CLAMP 3.0
 
+#define MAX_DIN 20                          /* k (k + 3) / 2 at k = 5 */
+// The fp32 filter of the skipping kernel (score_mfma.hip, stage F) evaluates tansig as 2 / (1 + 2^z) - 1 with z = FILTER_EXP_SCALE n:
+// the scale -2 log2(e) is folded into its copies of the hidden layers' weights and biases.
+#define FILTER_EXP_SCALE (-2.8853900817779268147)
+// a network filters only if the proven bound on |y32 - y64| is below this (see net_filter_margin)
+#define FILTER_MARGIN_CUTOFF 0.05
+
 // blob = inmap | bias | bias_q | wout | raw W,b per layer | A-fragments | tail rows | VALU packing; o_* = offsets in doubles
+// f32 (only where filter_ok) = input-layer A-fragments | hidden-layer A-fragments | biases; o32_* = offsets in floats
 struct NetPack {
     std::vector<double> blob;
     size_t o_inmap, o_bias, o_bias_q, o_wout, o_frag, o_wtail, o_wvalu, o_rw[MAX_LAYERS], o_rb[MAX_LAYERS];
     int d_in, n_hidden, width, s0, sh, unclamped_ok;
     double ymin, b_out, y_ymin, y_gain, y_xoffset;
+    std::vector<float> f32;
+    size_t o32_in, o32_hid, o32_bias;
+    int filter_ok;
+    double filter_margin;                 // bound on |y32 - y64| of the unmapped output for mapped inputs inside filter_box
+    double filter_box[MAX_DIN][2];        // [lo, hi] of every mapped input the bound was derived on
 };
+
+// the networks the fp32 filter is instantiated for: the shipped 3-variable class (NetShape<3> of score_plan.h)
+static inline bool filter_shape(int k, int H, int nh) { return k == 3 && H == 50 && nh == 3; }
+
+// ---- The margin of the fp32 filter: an a-priori bound on |y32 - y64|, y the unmapped network output, y32 what stage F of the
+// skipping kernel computes and y64 the network itself (the fp64 kernels are within 1e-11 of it, far inside the last factor).
+//
+// Stage F, per hidden layer: z_i = fl-chain(b~_i + sum_j w~_ij a^_j) on v_mfma_f32_16x16x4_f32 with b~ = fl32(c b), w~ = fl32(c W),
+// c = FILTER_EXP_SCALE, then a^_i = fma(2, rcp(exp2(z_i) + 1), -1).  With e_j >= |a^_j - a_j| of the layer's inputs and
+// A_j >= |a^_j|, u = 2^-24, gamma(m) = m u / (1 - m u):
+//   |z_i - c n_i| <=   sum_j |w~_ij| A_j gamma(m_j) + |b~_i| gamma(n)     the fmaf chain: the bias enters as C and sees all n
+//                                                                         roundings of the n live terms; a term sees its own and
+//                                                                         every later one.  The matrix core consumes the terms
+//                                                                         four at a time (one k-step); m_j counts from the FIRST
+//                                                                         term of j's k-step, so the order inside a k-step does
+//                                                                         not matter.  Zero-padded terms add 0 exactly: no rounding.
+//                    + sum_j |w~_ij - c W_ij| A_j + |b~_i - c b_i|        fp32 conversion of the scaled weights (the host knows
+//                                                                         both sides, no u-bound needed)
+//                    + |c| sum_j |W_ij| e_j                               the inputs' own error
+// The k-steps of a hidden layer hold neurons {16 t + 4 q + i, q = 0..3} for (t, i) in order -- the C/D fragment of one layer is the
+// B fragment of the next -- and those of the input layer inputs 4 s .. 4 s + 3.
+// tansig is 1-Lipschitz in n = z / c, which covers the error of exp2's ARGUMENT; what the hardware adds on top of the exact
+// 2 / (1 + 2^z) - 1:  v_exp_f32 and v_rcp_f32 are documented to 1 ulp, counted as 2 ulp = 4 u each, the add and the fma u each.
+// With E = 2^z, r = 1 / (1 + E) <= 1:  |2 r^ - 2 r| <= 2 r (4 u + u) + 2 (4 u) E / (1 + E)^2 <= 10 u + 2 u, and the fma's own
+// rounding of a value <= 1 adds u:  13 u.  (unclamped_ok bounds |z| by 116: exp2 neither overflows nor reaches the denormals.)
+//   e'_i = |z_i - c n_i| / |c| + 13 u,   A'_i = 1 + 8 u
+// Inputs: the staged fp64 feature is converted once, e_j = u B_j, A_j = (1 + u) B_j with B_j the larger endpoint of filter_box.
+// The output layer runs in fp64 on the fp32 activations: |acc32 - acc64| <= sum_j |Wout_j| e_j, and the output mapping divides by
+// its gain.  The factor 1 + 2^-10 covers the fp64 roundings of this derivation and of the kernels' epilogues and the terms of
+// second order in u; there is no other safety factor -- the margin decides how many candidates the filter passes on.
+// filter_box: the image of the input domain (x in [0, 1], |q| <= 1/k) under the network's mapping, 1e-9 wider at both ends so
+// that a contracted (v - xoffset) gain + ymin on the device and a quotient one ulp above 1/k stay inside.
+// networks.filter_margin restates this in numpy (tests/test_filter_margin_cpu.py).
+static inline double net_filter_margin(int k, int nh, int H, int d_in, const double *const *W, const double *const *B,
+                                       const double *xoffset, const double *gain, double ymin, double y_gain, double (*box)[2])
+{
+    const double u = 0x1p-24, c = FILTER_EXP_SCALE;
+    auto gamma = [&](int m) { return m * u / (1.0 - m * u); };
+    double e[MAX_HIDDEN], A[MAX_HIDDEN], en[MAX_HIDDEN];
+    for (int i = 0; i < d_in; ++i) {
+        const double lo = i < k ? 0.0 : -1.0 / (double)k, hi = i < k ? 1.0 : 1.0 / (double)k;
+        const double a = (lo - xoffset[i]) * gain[i] + ymin, b = (hi - xoffset[i]) * gain[i] + ymin;
+        box[i][0] = (a < b ? a : b) - 1e-9;
+        box[i][1] = (a < b ? b : a) + 1e-9;
+        const double Bi = std::fabs(box[i][0]) > std::fabs(box[i][1]) ? std::fabs(box[i][0]) : std::fabs(box[i][1]);
+        e[i] = u * Bi;
+        A[i] = (1.0 + u) * Bi;
+    }
+    int fan = d_in;
+    for (int l = 0; l < nh; ++l) {
+        int before[MAX_HIDDEN];      // live terms in front of the k-step of input j
+        if (l == 0) {
+            for (int j = 0; j < fan; ++j) before[j] = 4 * (j / 4);
+        } else {
+            int cnt = 0;
+            for (int t = 0; t < 4; ++t)
+                for (int i = 0; i < 4; ++i) {
+                    int live = 0;
+                    for (int q = 0; q < 4; ++q) {
+                        const int j = 16 * t + 4 * q + i;
+                        if (j < fan) { before[j] = cnt; ++live; }
+                    }
+                    cnt += live;
+                }
+        }
+        for (int i = 0; i < H; ++i) {
+            const double bt = (double)(float)(c * B[l][i]);
+            double acc = std::fabs(bt) * gamma(fan) + std::fabs(bt - c * B[l][i]);
+            for (int j = 0; j < fan; ++j) {
+                const double w = W[l][(size_t)i * fan + j], wt = (double)(float)(c * w);
+                acc += std::fabs(wt) * A[j] * gamma(fan - before[j]) + std::fabs(wt - c * w) * A[j] + std::fabs(c * w) * e[j];
+            }
+            en[i] = acc / std::fabs(c) + 13.0 * u;
+        }
+        for (int i = 0; i < H; ++i) { e[i] = en[i]; A[i] = 1.0 + 8.0 * u; }
+        fan = H;
+    }
+    double out = 0.0;
+    for (int j = 0; j < H; ++j) out += std::fabs(W[nh][j]) * e[j];
+    return out / std::fabs(y_gain) * (1.0 + 0x1p-10);
+}
 
 // What the library accepts as a network description (sdpcut_set_network, and sdpcut_train_loss_grad through the same lines):
 // -> SDPCUT_OK, or SDPCUT_EINVAL with *why set.
@@ -172,6 +266,43 @@ static inline int net_pack(int k, int n_layers, const int32_t *widths, const dou
             if (!(std::fabs(a) <= SDPCUT_INPUT_CLAMP && std::fabs(b) <= SDPCUT_INPUT_CLAMP)) domain_ok = false;
         }
         out->unclamped_ok = (worst < 40.0 && domain_ok) ? 1 : 0;      // |n| < 40  <=>  -2n < 80
+    }
+    // ---- the fp32 filter (stage F of the skipping kernel): its margin, and -- where the network qualifies -- its weights
+    out->filter_margin = net_filter_margin(k, nh, H, d_in, W, B, xoffset, gain, out->ymin, out->y_gain, out->filter_box);
+    // (written so that a NaN margin fails)
+    out->filter_ok = (out->unclamped_ok && filter_shape(k, H, nh) && out->filter_margin < FILTER_MARGIN_CUTOFF) ? 1 : 0;
+    out->f32.clear();
+    out->o32_in = out->o32_hid = out->o32_bias = 0;
+    if (out->filter_ok) {
+        const double c = FILTER_EXP_SCALE;
+        std::vector<float> &f = out->f32;
+        // A-fragment of v_mfma_f32_16x16x4_f32: lane l holds A[row = l & 15][k = l >> 4].  Input layer: one float4 per lane and row
+        // tile, component s = k-step s:  in[t][l][s] = c W0[16 t + (l & 15)][4 s + (l >> 4)]  (s0 <= 4 for this shape)
+        out->o32_in = f.size();
+        f.resize(f.size() + (size_t)T * 64 * 4, 0.f);
+        for (int t = 0; t < T; ++t)
+            for (int ln = 0; ln < 64; ++ln)
+                for (int s = 0; s < s0; ++s) {
+                    const int row = 16 * t + (ln & 15), col = 4 * s + (ln >> 4);
+                    if (row < H && col < d_in) f[out->o32_in + ((size_t)t * 64 + ln) * 4 + s] = (float)(c * W[0][(size_t)row * d_in + col]);
+                }
+        // Hidden layers: the C/D fragment of the layer in front holds rows 16 tk + 4 (l >> 4) + i in register i of row tile tk,
+        // so k-step (tk, i) multiplies neurons {16 tk + 4 q + i}:  hid[layer][t][tk][l][i] = c W[16 t + (l & 15)][16 tk + 4 (l >> 4) + i]
+        out->o32_hid = f.size();
+        f.resize(f.size() + (size_t)(nh - 1) * T * 4 * 64 * 4, 0.f);
+        for (int l = 1; l < nh; ++l)
+            for (int t = 0; t < T; ++t)
+                for (int tk = 0; tk < 4; ++tk)
+                    for (int ln = 0; ln < 64; ++ln)
+                        for (int i = 0; i < 4; ++i) {
+                            const int row = 16 * t + (ln & 15), col = 16 * tk + 4 * (ln >> 4) + i;
+                            if (row < H && col < H)
+                                f[out->o32_hid + ((((size_t)(l - 1) * T + t) * 4 + tk) * 64 + ln) * 4 + i] = (float)(c * W[l][(size_t)row * H + col]);
+                        }
+        out->o32_bias = f.size();
+        f.resize(f.size() + (size_t)nh * 64, 0.f);
+        for (int l = 0; l < nh; ++l)
+            for (int j = 0; j < H; ++j) f[out->o32_bias + (size_t)l * 64 + j] = (float)(c * B[l][j]);
     }
     return SDPCUT_OK;
 }

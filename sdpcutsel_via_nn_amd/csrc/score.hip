@@ -32,8 +32,12 @@ static int launch_score_k(sdpcut_ctx *h, int K, uint32_t flags, hipEvent_t ev_st
     const ScoreArgs A = fill_score_args(h, K, flags, fuse, strong_out, p);
     if (skip) {
         if (A.pf_mloc == 0) h->pf_counted = false;
-        score_mfma_skip_launch(K, A, p.grid, st, ev_start, ev_stop);
+        // SDPCUT_OPT_FP32_FILTER: an fp32 pass with a proven error bound in front of the fp64 one (NetDev::filter_ok)
+        const bool filter = h->fp32_filter && A.net.filter_ok && score_mfma_filter_built(K);
+        if (filter) score_mfma_filter_launch(K, A, p.grid, st, ev_start, ev_stop);
+        else score_mfma_skip_launch(K, A, p.grid, st, ev_start, ev_stop);
         h->skip_launched = true;
+        h->filter_launched = filter;
     } else if (h->kernel_variant == SDPCUT_KERNEL_MFMA && shaped) {
         if (A.tk && A.pf_mloc == 0) h->pf_counted = false;
         score_mfma_launch(K, A, p.grid, st, ev_start, ev_stop);
@@ -181,6 +185,7 @@ static int launch_score_form(sdpcut_ctx *h, uint32_t flags, const ScoreFuse *fus
     // (r5) did EVERY launch of this round count the fine histogram of the selection's class?  (The selection reads the table only then.)
     h->pf_counted = fuse != nullptr && fuse->k > 0;
     h->skip_launched = false;      // set by the launch that skips (launch_score_k)
+    h->filter_launched = false;
     const ScoreFormIn in = form_in(h, flags, fuse);
     const ScoreForm f = score_form(in);
     if (fused) *fused = f.fused;
@@ -227,6 +232,12 @@ int launch_score(sdpcut_ctx *h, uint32_t flags, const ScoreFuse *fuse, bool *fus
         h->stat_nn_skipped = 0;
         h->nn_skipped_on_device = false;
     }
+    // SDPCUT_STAT_NN_EVALUATED: a launch that ran the network ran it for everybody (N), for the violated candidates (a skipping
+    // launch: N - SDPCUT_STAT_NN_SKIPPED) or for the filter's survivors (counted on the device, d_stats[5])
+    if (!rc && (flags & SDPCUT_NN)) {
+        h->nn_eval_mode = h->filter_launched ? 2 : h->skip_launched ? 1 : 0;
+        h->nn_eval_n = h->N;
+    }
     return rc;
 }
 
@@ -265,6 +276,20 @@ int launch_score_points(sdpcut_ctx *h, uint32_t flags, int n_points, const doubl
         A.vars = d_pts; A.eig_out = d_eig; A.obj_out = d_obj;
         score_mfma_points_launch(k, A, ps, p.grid, n_points, h->stream);
     }
+    HIP_TRY(h, hipGetLastError());
+    return 0;
+}
+
+// sdpcut_filter_audit: the filter's fp32 pass for every candidate of a list of 3-variable candidates (the caller has checked that)
+int launch_filter_audit(sdpcut_ctx *h, double *d_y32)
+{
+    const int K = 3;
+    const uint32_t flags = SDPCUT_EIG | SDPCUT_NN;
+    const ScorePlan p = plan_class(h, K, nullptr);
+    const ScoreArgs A = fill_score_args(h, K, flags, nullptr, nullptr, p);
+    const int64_t rounds = (h->bucket[K].n + 127) / 128;      // a workgroup takes 128 candidates at a time
+    const int grid = (int)(rounds < 4 * (int64_t)h->n_cu ? (rounds < 1 ? 1 : rounds) : 4 * (int64_t)h->n_cu);
+    score_filter_audit_launch(K, A, grid, d_y32, h->stream);
     HIP_TRY(h, hipGetLastError());
     return 0;
 }

@@ -16,7 +16,8 @@
 //            from L2 as coalesced 512-B wave loads; tansig runs on the VALU between MFMAs.
 //
 // This unit holds the kernel for one class (score_mfma_kernel), its variant that runs the MLP for violated candidates only
-// (score_mfma_skip_kernel: the same body with SKIP), the one over all classes of a list (score_mfma_all_kernel: the same body per
+// (score_mfma_skip_kernel: the same body with SKIP; score_mfma_filter_kernel: with an fp32 pass in front of the fp64 one, FILTER, and
+// filter_audit_kernel, which runs that fp32 pass for every candidate), the one over all classes of a list (score_mfma_all_kernel: the same body per
 // class) and the launchers that start them (score_launch.h).  Which wave scores which candidate is
 // decided on the host (score_plan.h); the cross-check kernels are in score_alt.hip.
 #include <type_traits>
@@ -248,6 +249,141 @@ struct MfmaLdsSkip {
     uint32_t pf_tab[pf_score_k(K) ? PF_BINS / 2 : 1];
 };
 
+// LDS of one workgroup of the skipping kernel with the fp32 filter (FILTER, see score_mfma_body): TWO rings per wave.  Ring 1 (f_*,
+// FCAP = 96 slots: <= 31 pending + <= 64 appended by a strip) holds the violated candidates, ring 2 (the names of MfmaLdsSkip,
+// QCAP = 64: <= 31 pending + <= 32 survivors of one filter pass) those of them the fp32 pass could not rule out.  Only the DIN live
+// feature rows are kept; the fp64 pass reads the padding rows of its B fragments as literal zeros.
+template <int K, int H, int NH>
+struct MfmaLdsFilter {
+    static constexpr int DIN = K + K * (K + 1) / 2;
+    static constexpr int T = (H + 15) / 16;
+    static constexpr int NT = (H - 16 * (T - 1) <= 4) ? H - 16 * (T - 1) : 0;
+    static constexpr int QCAP = 64, FCAP = 96;
+    double feat[4][DIN][QCAP];
+    double ynn[4][QCAP];
+    double q_negsm[4][QCAP];
+    double q_maxel[4][QCAP];
+    int32_t q_out[4][QCAP];
+    double f_feat[4][DIN][FCAP];
+    double f_negsm[4][FCAP];
+    double f_maxel[4][FCAP];
+    int32_t f_out[4][FCAP];
+    uint8_t f_byp[4][FCAP];      // the candidate has a mapped input outside NetDev::filter_box: it survives unconditionally
+    double f_y[4][32];           // raw fp32-pass outputs of the 32 entries of a filter pass
+    alignas(16) float s_bias32[NH * 64];
+    double s_bias[NH * 64];
+    double s_wtail[NT ? NH * 4 * 64 : 1];
+    double s_wout[64];
+    uint32_t tk_hist[256];
+    uint32_t tk_cnt[3];
+    uint32_t s_strong;
+    uint32_t pf_tab[pf_score_k(K) ? PF_BINS / 2 : 1];
+};
+
+// ------------------------------------------------------------------------------------------
+// The fp32 pass of the filter (stage F of the skipping kernel, and all of filter_audit_kernel): the MLP of 32 candidates on
+// v_mfma_f32_16x16x4_f32, two column tiles of 16 = two independent accumulator chains.  feat_at(row, col) is the staged (mapped,
+// fp64) input `row` of column col = 0..31.  Returns in yraw[j], on every lane of column c16 of tile j, the output layer's sum
+// (without b_out) as a double.
+//  * Layouts: A lane l = A[row l & 15][k l >> 4], B lane l = B[k l >> 4][col l & 15], C/D register i of lane l = row
+//    4 (l >> 4) + i.  So register i of row tile tk IS the B operand of a k-step that multiplies neurons {16 tk + 4 q + i}: the
+//    host packs the A-fragments in that k-order (net_pack.h) and the activations never leave registers.  All four row tiles run
+//    on the matrix core; k-steps (3, 2) and (3, 3) hold no neuron below H = 50 and are left out.
+//  * The accumulator starts as the (scaled) bias and the k-steps follow in order: the chain the margin's derivation counts.
+//  * The output layer is a fp64 dot product of the fp32 activations with the fp64 output weights (13 fma per lane and tile) and the
+//    cross-lane sum of the fp64 pass: no fp32 rounding behind the last tansig.
+// Columns are independent: a stale or padding column (NaN included) changes no other column's result.
+template <int K, int H, int NH, class FeatAt>
+__device__ __forceinline__ void filter_pass_f32(const NetDev &net, const float *s_bias32, const double *s_wout, FeatAt feat_at,
+                                                const int lane, double (&yraw)[2])
+{
+    constexpr int DIN = K + K * (K + 1) / 2;
+    constexpr int S0 = (DIN + 3) / 4;
+    static_assert(S0 <= 4 && H > 48 && H <= 64, "one float4 of input k-steps per lane; four row tiles");
+    const int q = lane >> 4, c16 = lane & 15;
+    float bin[S0][2];
+#pragma unroll
+    for (int s = 0; s < S0; ++s)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int row = 4 * s + q;
+            const double v = feat_at(row < DIN ? row : 0, 16 * j + c16);
+            bin[s][j] = row < DIN ? (float)v : 0.0f;
+        }
+    // tansig of a C/D fragment of row tile t; rows >= H are padding -> 0
+    auto act = [&](const f4 z, const int t) __attribute__((always_inline)) {
+        f4 a;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) a[i] = (16 * t + 4 * q + i < H) ? tansig_f32_z(z[i]) : 0.0f;
+        return a;
+    };
+    f4 cur[4][2], prev[4][2];
+    // ---------------- input layer
+    {
+        const f4 *w_in = (const f4 *)net.f32_in;
+        f4 w[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) w[t] = w_in[t * 64 + lane];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const f4 bias = *(const f4 *)&s_bias32[16 * t + 4 * q];
+            f4 acc0 = bias, acc1 = bias;
+#pragma unroll
+            for (int s = 0; s < S0; ++s) {
+                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w[t][s], bin[s][0], acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w[t][s], bin[s][1], acc1, 0, 0, 0);
+            }
+            cur[t][0] = act(acc0, t);
+            cur[t][1] = act(acc1, t);
+        }
+    }
+    // ---------------- hidden -> hidden layers (rolled); the fragments of row tile t + 1 are requested while tile t computes
+#pragma unroll 1
+    for (int l = 1; l < NH; ++l) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) { prev[t][0] = cur[t][0]; prev[t][1] = cur[t][1]; }
+        const f4 *wh = (const f4 *)net.f32_hid + (size_t)(l - 1) * 4 * 4 * 64 + lane;
+        f4 wnx[4];
+#pragma unroll
+        for (int tk = 0; tk < 4; ++tk) wnx[tk] = wh[tk * 64];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            f4 w[4];
+#pragma unroll
+            for (int tk = 0; tk < 4; ++tk) w[tk] = wnx[tk];
+            if (t + 1 < 4) {
+#pragma unroll
+                for (int tk = 0; tk < 4; ++tk) wnx[tk] = wh[((t + 1) * 4 + tk) * 64];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            const f4 bias = *(const f4 *)&s_bias32[l * 64 + 16 * t + 4 * q];
+            f4 acc0 = bias, acc1 = bias;
+#pragma unroll
+            for (int tk = 0; tk < 4; ++tk)
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    if (16 * tk + i < H) {      // (the k-step's first neuron, q = 0)
+                        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w[tk][i], prev[tk][0][i], acc0, 0, 0, 0);
+                        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w[tk][i], prev[tk][1][i], acc1, 0, 0, 0);
+                    }
+            cur[t][0] = act(acc0, t);
+            cur[t][1] = act(acc1, t);
+        }
+    }
+    // ---------------- linear output layer in fp64
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        double part = 0.0;
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) part = fma((double)cur[t][j][i], s_wout[16 * t + 4 * q + i], part);
+        part = xor_add16(part);
+        part = xor_add32(part);
+        yraw[j] = part;
+    }
+}
+
 // bid / nblk: this workgroup's index among the nblk workgroups that serve the class (blockIdx.x / gridDim.x of a launch over
 // one class; the launch over all classes of a list hands every class its own range of workgroups, score_mfma_all_kernel)
 // SKIP (FUSE = TK_MODE_STRONG, both flags, JK = 2 only; LDS = MfmaLdsSkip): the MLP runs for VIOLATED candidates only -- the strong
@@ -256,10 +392,18 @@ struct MfmaLdsSkip {
 // B runs a two-tile pass over the oldest 32 entries while there are 32; the wave's last strip flushes the rest (one tile if <= 16).
 // A queue entry's score does not depend on its slot or its neighbours (tansig.h), and mlp_pass<1> equals mlp_pass<2> bit for bit:
 // a violated candidate gets the bits the plain kernel gives it.  Non-violated candidates get NO obj_out store.
-template <int K, int H, int NH, int FUSE, bool CLAMP, int JK, bool SKIP = false, class LDS = MfmaLds<K, H, NH>>
+// FILTER (SKIP with LDS = MfmaLdsFilter; NetDev::filter_ok): a stage F between the two.  The violated lanes append to ring 1; while
+// it holds 32 entries an fp32 pass (filter_pass_f32) evaluates the network for them, and an entry moves on to ring 2 -- the queue of
+// the fp64 pass, which is unchanged -- iff  obj32 = negSM + y32 max_elem > -filter_margin max_elem,  or it carries the bypass bit
+// (a mapped input outside filter_box, where the margin was not derived).  |y32 - y64| <= filter_margin is proven (net_pack.h), so
+// every violated candidate with a positive measure survives and gets the bits the plain kernel gives it; the others are not strong
+// whatever their measure, and store their (non-positive) fp32 measure so that the selection, which reads obj_out of every violated
+// candidate, sees them as what they are.  The strong count, the histograms and the head are the plain kernel's.
+template <int K, int H, int NH, int FUSE, bool CLAMP, int JK, bool SKIP = false, class LDS = MfmaLds<K, H, NH>, bool FILTER = false>
 __device__ __forceinline__ void score_mfma_body(const ScoreArgs A, LDS &S, const int bid, const int nblk)
 {
     static_assert(!SKIP || (FUSE == TK_MODE_STRONG && JK == 2), "the skipping variant serves the fused launch of a combined round");
+    static_assert(!FILTER || (SKIP && !CLAMP), "the fp32 filter is a stage of the clamp-free skipping variant");
     constexpr int M = K * (K + 1) / 2;
     constexpr int DIN = K + M;
     constexpr int S0 = (DIN + 3) / 4;      // k-steps of the input layer
@@ -338,6 +482,9 @@ __device__ __forceinline__ void score_mfma_body(const ScoreArgs A, LDS &S, const
         if constexpr (NT > 0)
             for (int i = threadIdx.x; i < NH * 4 * 64; i += 256) s_wtail[i] = net.wtail[i];
         if (threadIdx.x < 64) s_wout[threadIdx.x] = net.wout[threadIdx.x];
+        if constexpr (FILTER) {
+            if (threadIdx.x < NH * 64) S.s_bias32[threadIdx.x] = net.f32_bias[threadIdx.x];
+        }
         __syncthreads();
     }
 #endif
@@ -346,6 +493,7 @@ __device__ __forceinline__ void score_mfma_body(const ScoreArgs A, LDS &S, const
     auto &tk_hist = S.tk_hist;
     auto &tk_cnt = S.tk_cnt;
     uint32_t c_viol = 0, c_pos = 0, c_strong = 0;     // per lane (vector registers: the scalar file is full)
+    [[maybe_unused]] uint32_t c_eval = 0;             // (FILTER) entries the fp64 pass evaluated
     // (r5) the fine histogram of the selection's class (topk_dev.h) is compiled into the kernel of 3-variable candidates only:
     // merely present -- not executed -- it costs the 4-variable kernel 11 us on the 1.7e6-candidate cover of spar125-075-1 (240
     // registers, 112 bytes of scratch: the allocation of its hot loop moves), executed 22, against the 12 us the selection saves
@@ -356,7 +504,7 @@ __device__ __forceinline__ void score_mfma_body(const ScoreArgs A, LDS &S, const
     auto &pf_tab = S.pf_tab;
     if constexpr (FUSE != 0) {
         tk_hist[threadIdx.x] = 0;
-        if (threadIdx.x < 2) tk_cnt[threadIdx.x] = 0;
+        if (threadIdx.x < sizeof(tk_cnt) / sizeof(tk_cnt[0])) tk_cnt[threadIdx.x] = 0;
         if constexpr (PF) {
 #pragma unroll
             for (int j = 0; j < PF_BINS / 2 / 256; ++j) pf_tab[threadIdx.x + 256 * j] = 0;
@@ -365,6 +513,7 @@ __device__ __forceinline__ void score_mfma_body(const ScoreArgs A, LDS &S, const
     }
 
     [[maybe_unused]] int q_head = 0, q_fill = 0;      // (SKIP) the wave's queue: first pending slot (0, 32 or 64) and pending entries; scalar
+    [[maybe_unused]] int f_head = 0, f_fill = 0;      // (FILTER) the same for ring 1; q_* is ring 2 then
     PHASE_DECL;
     while (more) {
         PHASE_MARK(0);
@@ -418,15 +567,27 @@ __device__ __forceinline__ void score_mfma_body(const ScoreArgs A, LDS &S, const
             c_viol += q_viol;
             const unsigned long long vm = __ballot(q_viol);
             const int rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(vm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)vm, 0u));
-            const int tail_slot = q_head + q_fill >= LDS::QCAP ? q_head + q_fill - LDS::QCAP : q_head + q_fill;      // (scalar)
-            q_slot = tail_slot + rank >= LDS::QCAP ? tail_slot + rank - LDS::QCAP : tail_slot + rank;
-            q_fill += __popcll(vm);
-            if (q_viol) {
-                S.q_negsm[wave][q_slot] = cd.negSM;
-                S.q_maxel[wave][q_slot] = cd.max_elem;
-                S.q_out[wave][q_slot] = out_idx;
+            if constexpr (FILTER) {
+                const int tail_slot = f_head + f_fill >= LDS::FCAP ? f_head + f_fill - LDS::FCAP : f_head + f_fill;      // (scalar)
+                q_slot = tail_slot + rank >= LDS::FCAP ? tail_slot + rank - LDS::FCAP : tail_slot + rank;
+                f_fill += __popcll(vm);
+                if (q_viol) {
+                    S.f_negsm[wave][q_slot] = cd.negSM;
+                    S.f_maxel[wave][q_slot] = cd.max_elem;
+                    S.f_out[wave][q_slot] = out_idx;
+                }
+            } else {
+                const int tail_slot = q_head + q_fill >= LDS::QCAP ? q_head + q_fill - LDS::QCAP : q_head + q_fill;      // (scalar)
+                q_slot = tail_slot + rank >= LDS::QCAP ? tail_slot + rank - LDS::QCAP : tail_slot + rank;
+                q_fill += __popcll(vm);
+                if (q_viol) {
+                    S.q_negsm[wave][q_slot] = cd.negSM;
+                    S.q_maxel[wave][q_slot] = cd.max_elem;
+                    S.q_out[wave][q_slot] = out_idx;
+                }
             }
         }
+        [[maybe_unused]] bool f_outside = false;      // (FILTER) a mapped input lies outside the box the margin was derived on
         // ---- stage mapminmax'ed inputs (neural_net_3D.m:69-73): xp = (v - xoffset)*gain + ymin
 #pragma unroll
         for (int i = 0; i < S0 * 4; ++i) {
@@ -436,11 +597,19 @@ __device__ __forceinline__ void score_mfma_body(const ScoreArgs A, LDS &S, const
                 xp = (v - net.inmap[i]) * net.inmap[DIN + i] + net.ymin;
                 if constexpr (!CLAMP) xp = min_f64_raw(max_f64_raw(xp, -SDPCUT_INPUT_CLAMP), SDPCUT_INPUT_CLAMP);
             }
-            if constexpr (SKIP) {
+            if constexpr (FILTER) {
+                if (i < DIN) {
+                    f_outside = f_outside || !(xp >= net.filter_box[2 * i] && xp <= net.filter_box[2 * i + 1]);      // (a NaN is outside)
+                    if (q_viol) S.f_feat[wave][i][q_slot] = xp;
+                }
+            } else if constexpr (SKIP) {
                 if (q_viol) feat[wave][i][q_slot] = xp;
             } else {
                 feat[wave][i][lane] = xp;
             }
+        }
+        if constexpr (FILTER) {
+            if (q_viol) S.f_byp[wave][q_slot] = f_outside ? 1 : 0;
         }
         wave_lds_sync();
         PHASE_MARK(3);
@@ -481,7 +650,15 @@ __device__ __forceinline__ void score_mfma_body(const ScoreArgs A, LDS &S, const
 #pragma unroll
             for (int s = 0; s < S0; ++s)
 #pragma unroll
-                for (int j = 0; j < J; ++j) bin[s][j] = feat[wave][4 * s + q][col0 + 16 * j + c16];
+                for (int j = 0; j < J; ++j) {
+                    if constexpr (FILTER) {      // (ring 2 keeps the DIN live rows; the padding rows of the strip hold 0.0)
+                        const int row = 4 * s + q;
+                        const double v = feat[wave][row < DIN ? row : 0][col0 + 16 * j + c16];
+                        bin[s][j] = row < DIN ? v : 0.0;
+                    } else {
+                        bin[s][j] = feat[wave][4 * s + q][col0 + 16 * j + c16];
+                    }
+                }
 
             d4 prev[T][J], cur[T][J];
             const double *wf = net.wfrag;
@@ -634,12 +811,86 @@ __device__ __forceinline__ void score_mfma_body(const ScoreArgs A, LDS &S, const
                 obj = obj + y * S.q_maxel[wave][s];
                 if (live) A.obj_out[S.q_out[wave][s]] = obj;
                 const bool pos = live && obj > 0.0;
+                if constexpr (FILTER) c_eval += live;
                 c_strong += pos;
                 c_pos += pos;
                 const uint64_t key = key_of(obj);
                 hist_add_few(tk_hist, (uint32_t)(key >> 56), pos);
                 if (PF && pos) { const int f = pf_code(key, false); atomicAdd(&pf_tab[f >> 1], (f & 1) ? 0x10000u : 1u); }
             };
+            if constexpr (FILTER) {
+                // one fp32 pass over the cnt <= 32 oldest entries of ring 1 (always two column tiles: padding columns compute on
+                // stale slots and are not live); the survivors are appended to ring 2 in ring-1 order
+                auto filter_round = [&](const int cnt) __attribute__((always_inline)) {
+                    double yr[2];
+                    filter_pass_f32<K, H, NH>(net, S.s_bias32, s_wout,
+                                              [&](const int row, const int col) { return S.f_feat[wave][row][f_head + col]; }, lane, yr);
+                    if (q == 0) { S.f_y[wave][c16] = yr[0]; S.f_y[wave][16 + c16] = yr[1]; }
+                    wave_lds_sync();
+                    {
+#pragma clang fp contract(off)
+                        const int s = f_head + (lane & 31);
+                        const bool live = lane < cnt;
+                        // the exact epilogue's arithmetic on the fp32 pass's output
+                        double acc = S.f_y[wave][lane & 31];
+                        acc = acc + net.b_out;
+                        const double y = (acc - net.y_ymin) / net.y_gain + net.y_xoffset;
+                        const double me = S.f_maxel[wave][s];
+                        double obj = S.f_negsm[wave][s];
+                        obj = obj + y * me;
+                        // (written so that a NaN survives)
+                        const bool surv = live && (S.f_byp[wave][s] != 0 || !(obj <= -(net.filter_margin * me)));
+                        // The selection that follows reads obj_out of every violated candidate to tell the strong ones: an entry that
+                        // stops here stores its fp32 measure, which is <= -margin max_elem <= 0 -- not strong, as proven.  (The
+                        // array counts as not scored after such a launch; a completion overwrites the value.)
+                        if (live && !surv) A.obj_out[S.f_out[wave][s]] = obj;
+                        const unsigned long long sm = __ballot(surv);
+                        const int rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(sm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)sm, 0u));
+                        const int tail_slot = q_head + q_fill >= LDS::QCAP ? q_head + q_fill - LDS::QCAP : q_head + q_fill;      // (scalar)
+                        const int s2 = tail_slot + rank >= LDS::QCAP ? tail_slot + rank - LDS::QCAP : tail_slot + rank;
+                        if (surv) {
+#pragma unroll
+                            for (int i = 0; i < DIN; ++i) feat[wave][i][s2] = S.f_feat[wave][i][s];
+                            S.q_negsm[wave][s2] = S.f_negsm[wave][s];
+                            S.q_maxel[wave][s2] = me;
+                            S.q_out[wave][s2] = S.f_out[wave][s];
+                        }
+                        q_fill += __popcll(sm);
+                    }
+                    wave_lds_sync();      // ring 2 is complete for the fp64 pass, the ring-1 slots are free
+                    f_head = f_head + 32 >= LDS::FCAP ? 0 : f_head + 32;
+                    f_fill -= cnt;
+                };
+                // ring 2 first (an fp32 pass needs room for 32 survivors behind <= 31 pending), then ring 1; behind the wave's last
+                // strip both are drained
+                for (;;) {
+                    if (q_fill >= 32 || (!nx_more && f_fill == 0 && q_fill > 16)) {
+                        const int cnt = q_fill < 32 ? q_fill : 32;
+                        mlp_pass(std::integral_constant<int, 2>{}, q_head);
+                        wave_lds_sync();
+                        skip_epilogue(cnt);
+                        wave_lds_sync();
+                        q_head = q_head + 32 >= LDS::QCAP ? 0 : q_head + 32;
+                        q_fill -= cnt;
+                        continue;
+                    }
+                    if (f_fill >= 32 || (!nx_more && f_fill > 0)) {
+                        filter_round(f_fill < 32 ? f_fill : 32);
+                        continue;
+                    }
+                    break;
+                }
+                if (!nx_more && q_fill > 0) {
+                    mlp_pass(std::integral_constant<int, 1>{}, q_head);
+                    wave_lds_sync();
+                    skip_epilogue(q_fill);
+                    wave_lds_sync();
+                    q_fill = 0;
+                }
+                PHASE_MARK(4);
+                tail = tail || nx_tail; s0 = nx_s0; more = nx_more;
+                continue;
+            }
             // passes while 32 entries are pending; behind the wave's last strip the rest (padding columns compute on stale slots, their
             // results are not stored)
             while (q_fill > 16 && (q_fill >= 32 || !nx_more)) {
@@ -723,11 +974,22 @@ __device__ __forceinline__ void score_mfma_body(const ScoreArgs A, LDS &S, const
             c_viol += __shfl_xor((int)c_viol, off);
             c_pos += __shfl_xor((int)c_pos, off);
         }
+        if constexpr (FILTER) {
+            for (int off = 32; off > 0; off >>= 1) c_eval += __shfl_xor((int)c_eval, off);
+        }
         if (lane == 0) {
             if (c_viol) atomicAdd(&tk_cnt[0], c_viol);
             if (c_pos) atomicAdd(&tk_cnt[1], c_pos);
+            if constexpr (FILTER) {
+                if (c_eval) atomicAdd(&tk_cnt[2], c_eval);
+            }
         }
         __syncthreads();
+        if constexpr (FILTER) {
+            if (threadIdx.x == 2 && tk_cnt[2])
+                __hip_atomic_fetch_add((unsigned long long *)&A.tk->eval_rep[blockIdx.x % TK_SHREP], (unsigned long long)tk_cnt[2],
+                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
         if (threadIdx.x < 2 && tk_cnt[threadIdx.x])
             __hip_atomic_fetch_add((unsigned long long *)(threadIdx.x ? &A.tk->pos_rep[blockIdx.x % TK_SHREP] : &A.tk->viol_rep[blockIdx.x % TK_SHREP]),
                                    (unsigned long long)tk_cnt[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -755,6 +1017,63 @@ __global__ __launch_bounds__(256, 2) void score_mfma_skip_kernel(ScoreArgs A)
     static_assert(sizeof(MfmaLdsSkip<K, H, NH>) <= 80 * 1024, "two workgroups of the skipping kernel must fit a CU's LDS");
     __shared__ MfmaLdsSkip<K, H, NH> S;
     score_mfma_body<K, H, NH, TK_MODE_STRONG, CLAMP, 2, true>(A, S, (int)blockIdx.x, (int)gridDim.x);
+}
+
+// The skipping variant with the fp32 filter (FILTER of score_mfma_body): launched instead of it for a network with
+// NetDev::filter_ok under SDPCUT_OPT_FP32_FILTER.  Clamp-free by construction (filter_ok implies unclamped_ok).
+template <int K, int H, int NH>
+__global__ __launch_bounds__(256, 2) void score_mfma_filter_kernel(ScoreArgs A)
+{
+    static_assert(sizeof(MfmaLdsFilter<K, H, NH>) <= 80 * 1024, "two workgroups of the filtering kernel must fit a CU's LDS");
+    __shared__ MfmaLdsFilter<K, H, NH> S;
+    score_mfma_body<K, H, NH, TK_MODE_STRONG, false, 2, true, MfmaLdsFilter<K, H, NH>, true>(A, S, (int)blockIdx.x, (int)gridDim.x);
+}
+
+// sdpcut_filter_audit: the fp32 pass of the filter -- the same device function as stage F -- for EVERY candidate of the class, its
+// output unmapped into y32_out (caller order).  Not on the hot path: a wave takes 32 candidates at a time, stages their mapped
+// inputs exactly as the scoring kernel does (clamp-free form) and runs one pass.
+template <int K, int H, int NH>
+__global__ __launch_bounds__(256) void filter_audit_kernel(ScoreArgs A, double *y32_out)
+{
+    constexpr int DIN = K + K * (K + 1) / 2;
+    __shared__ double s_feat[4][DIN][32];
+    __shared__ alignas(16) float s_bias32[NH * 64];
+    __shared__ double s_wout[64];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int q = lane >> 4, c16 = lane & 15;
+    const NetDev &net = A.net;
+    if (threadIdx.x < NH * 64) s_bias32[threadIdx.x] = net.f32_bias[threadIdx.x];
+    if (threadIdx.x < 64) s_wout[threadIdx.x] = net.wout[threadIdx.x];
+    __syncthreads();
+    for (int64_t base = ((int64_t)blockIdx.x * 4 + wave) * 32; base < A.n; base += (int64_t)gridDim.x * 4 * 32) {
+        const int64_t c = base + (lane & 31);
+        Cand<K> cd;
+        gather_candidate<K>(cd, A.set, A.n, c < A.n ? c : base, A.vars, A.Q, A.nv, A.L, true);
+        if (lane < 32) {
+#pragma unroll
+            for (int i = 0; i < DIN; ++i) {
+                const double v = (i < K) ? cd.x[i < K ? i : 0] : cd.q[i >= K ? i - K : 0];
+                double xp = (v - net.inmap[i]) * net.inmap[DIN + i] + net.ymin;
+                xp = min_f64_raw(max_f64_raw(xp, -SDPCUT_INPUT_CLAMP), SDPCUT_INPUT_CLAMP);
+                s_feat[wave][i][lane] = xp;
+            }
+        }
+        wave_lds_sync();
+        double yr[2];
+        filter_pass_f32<K, H, NH>(net, s_bias32, s_wout, [&](const int row, const int col) { return s_feat[wave][row][col]; }, lane, yr);
+        if (q == 0) {
+#pragma clang fp contract(off)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int64_t cj = base + 16 * j + c16;
+                double acc = yr[j];
+                acc = acc + net.b_out;
+                const double y = (acc - net.y_ymin) / net.y_gain + net.y_xoffset;
+                if (cj < A.n) y32_out[A.orig[cj]] = y;
+            }
+        }
+        wave_lds_sync();      // s_feat is rewritten by the next round
+    }
 }
 
 // The same kernel at the P = gridDim.y LP points of a batch (sdpcut_score_points / sdpcut_round_csr_points, points.hip): workgroup
@@ -871,6 +1190,20 @@ void score_mfma_skip_launch(int K, const ScoreArgs &A, int grid, hipStream_t st,
     case 4: score_mfma_skip_launch_k<4>(A, grid, st, ev_start, ev_stop); break;
     default: score_mfma_skip_launch_k<5>(A, grid, st, ev_start, ev_stop); break;
     }
+}
+
+// The fp32 filter is instantiated for the shipped 3-variable class alone (net_pack.h: filter_shape grants filter_ok to no other)
+static_assert(NetShape<3>::H == 50 && NetShape<3>::NH == 3 && skip_k(3) && mfma_cols(3) == 2, "filter_shape of net_pack.h names NetShape<3>");
+bool score_mfma_filter_built(int K) { return K == 3; }
+
+void score_mfma_filter_launch(int K, const ScoreArgs &A, int grid, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop)
+{
+    if (K == 3) SCORE_LAUNCH((score_mfma_filter_kernel<3, NetShape<3>::H, NetShape<3>::NH>), grid, 256);
+}
+
+void score_filter_audit_launch(int K, const ScoreArgs &A, int grid, double *d_y32, hipStream_t st)
+{
+    if (K == 3) hipLaunchKernelGGL((filter_audit_kernel<3, NetShape<3>::H, NetShape<3>::NH>), dim3(grid), dim3(256), 0, st, A, d_y32);
 }
 
 template <int K>

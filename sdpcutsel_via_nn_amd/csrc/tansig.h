@@ -199,3 +199,17 @@ __device__ __forceinline__ d4 tansig_tile(d4 c, int t)
     out[3] = (16 * t + 12 < H) ? v3 : 0.0;
     return out;
 }
+
+// ---- fp32, for the filter stage of the skipping kernel (score_mfma.hip, stage F).  Its accumulators hold z = -2 log2(e) n (the
+// scale is folded into the packed weights and biases, net_pack.h), so tansig(n) = 2 / (1 + 2^z) - 1 is v_exp_f32, v_add_f32,
+// v_rcp_f32, v_fma_f32 -- no range reduction, no refinement.  Accuracy: both transcendentals are documented to 1 ulp; the
+// derivation of the filter's margin (net_pack.h: net_filter_margin) charges 13 * 2^-24 per activation for this function on top of
+// the exact formula and spells out where each part comes from.  |z| <= 116 for a network with unclamped_ok, the only kind that
+// filters: 2^z stays a normal number.  A NaN or an infinity (a stale queue slot) passes through as NaN or saturates; the filter
+// lets a NaN survive.
+typedef float f4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float tansig_f32_z(float z)
+{
+    const float d = __builtin_amdgcn_exp2f(z) + 1.0f;
+    return __builtin_fmaf(2.0f, __builtin_amdgcn_rcpf(d), -1.0f);
+}

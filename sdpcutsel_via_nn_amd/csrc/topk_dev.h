@@ -103,6 +103,7 @@ struct TopkWs {
     int64_t viol_rep[TK_SHREP];           // violated / positive candidates counted by the same kernels, replicated by workgroup:
     int64_t pos_rep[TK_SHREP];            // ONE counter each would queue thousands of retiring workgroups on one address (~15 ns
                                           // apiece: 58 us for the eigenvalue kernel's 3907 workgroups -- longer than the kernel runs)
+    int64_t eval_rep[TK_SHREP];           // fp64 MLP evaluations of a filtering score launch (score_mfma_filter_kernel), the same way
     // (r5) the FINE histogram the score / eigenvalue kernels leave for the selection (see above); LAST in the struct: lists too
     // short for it zero only what lies in front (offsetof(TopkWs, pf_floor))
     uint32_t pf_floor[PF_FLOOR_REP][32];  // max over the reporting units of the lowest bin they reported (replicas in separate lines)

@@ -248,6 +248,11 @@ __global__ __launch_bounds__(TK_THREADS) void tk_refine_kernel(int64_t n, int64_
             st_i64(&ws->counters[6], mode);
             st_i64(&ws->counters[5], strong);      // for the host (round header)
             st_i64(&ws->counters[0], cls);
+            if (d_stats) {      // SDPCUT_STAT_NN_EVALUATED of a filtering launch: what its waves passed on to the fp64 pass
+                int64_t neval = 0;
+                for (int r = 0; r < TK_SHREP; ++r) neval += ws->eval_rep[r];
+                d_stats[5] = (unsigned long long)neval;
+            }
         }
         if (both && mode == TK_MODE_COMBALL) {      // uniform over the grid
             p_first = 0;

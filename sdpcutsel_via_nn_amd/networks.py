@@ -93,6 +93,61 @@ def unclamped_ok(k, widths, params):
     return bool(worst < 40.0 and np.all(ends <= INPUT_CLAMP))
 
 
+FILTER_EXP_SCALE = -2.8853900817779268147      # -2 log2(e), csrc/net_pack.h
+FILTER_MARGIN_CUTOFF = 0.05
+
+
+def filter_box(k, widths, params):
+    """NetPack::filter_box of csrc/net_pack.h: [d_in, 2], the mapped image of the input domain, 1e-9 wider at both ends"""
+    xoffset, gain, ymin, _, _, _ = split_params(k, widths, np.asarray(params, dtype=np.float64))
+    idx = np.arange(xoffset.shape[0])
+    lo, hi = np.where(idx < k, 0.0, -1.0 / k), np.where(idx < k, 1.0, 1.0 / k)
+    a, b = (lo - xoffset) * gain + ymin, (hi - xoffset) * gain + ymin
+    return np.stack([np.minimum(a, b) - 1e-9, np.maximum(a, b) + 1e-9], axis=1)
+
+
+def filter_margin(k, widths, params):
+    """net_filter_margin of csrc/net_pack.h, restated: the a-priori bound on |y32 - y64| of the unmapped network output for mapped
+    inputs inside filter_box, y32 as the fp32 filter of the skipping kernel computes it (the derivation is the comment there):
+    per layer  e' = (|w~| A gamma(m) + |b~| gamma(n) + |w~ - c W| A + |b~ - c b| + |c| |W| e) / |c| + 13 u,  the output layer in
+    fp64, the output mapping's gain, and 1 + 2^-10."""
+    p = np.asarray(params, dtype=np.float64)
+    xoffset, gain, ymin, Ws, Bs, (y_ymin, y_gain, y_xoffset) = split_params(k, widths, p)
+    u, c = 2.0 ** -24, FILTER_EXP_SCALE
+
+    def gamma(m):
+        return m * u / (1.0 - m * u)
+
+    Bx = np.abs(filter_box(k, widths, p)).max(axis=1)
+    e, A = u * Bx, (1.0 + u) * Bx
+    for l, (W, b) in enumerate(zip(Ws[:-1], Bs[:-1])):
+        fan = W.shape[1]
+        j = np.arange(fan)
+        if l == 0:
+            before = 4 * (j // 4)      # k-step s holds inputs 4 s .. 4 s + 3
+        else:                          # k-step (t, i) holds neurons 16 t + 4 q + i, q = 0..3: the live terms in front of it
+            before = np.zeros(fan, dtype=np.int64)
+            cnt = 0
+            for t in range(4):
+                for i in range(4):
+                    live = [16 * t + 4 * q + i for q in range(4) if 16 * t + 4 * q + i < fan]
+                    before[live] = cnt
+                    cnt += len(live)
+        wt = (c * W).astype(np.float32).astype(np.float64)
+        bt = (c * b).astype(np.float32).astype(np.float64)
+        acc = np.abs(bt) * gamma(fan) + np.abs(bt - c * b)
+        acc = acc + (np.abs(wt) * (A * gamma(fan - before)) + np.abs(wt - c * W) * A + np.abs(c * W) * e).sum(axis=1)
+        e = acc / abs(c) + 13.0 * u
+        A = np.full(W.shape[0], 1.0 + 8.0 * u)
+    return float((np.abs(Ws[-1][0]) * e).sum() / abs(y_gain) * (1.0 + 2.0 ** -10))
+
+
+def filter_ok(k, widths, params):
+    """NetPack::filter_ok: clamp-free, the shipped 3-variable shape (three hidden layers of 50), margin below the cut-off"""
+    return bool(unclamped_ok(k, widths, params) and k == 3 and [int(w) for w in widths] == [50, 50, 50, 1]
+                and filter_margin(k, widths, params) < FILTER_MARGIN_CUTOFF)
+
+
 def _tansig(n):
     return 2.0 / (1.0 + np.exp(-2.0 * n)) - 1.0
 
