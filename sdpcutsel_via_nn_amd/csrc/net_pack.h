@@ -52,7 +52,20 @@ static inline bool filter_shape(int k, int H, int nh) { return k == 3 && H == 50
 //                                                                         both sides, no u-bound needed)
 //                    + |c| sum_j |W_ij| e_j                               the inputs' own error
 // The k-steps of a hidden layer hold neurons {16 t + 4 q + i, q = 0..3} for (t, i) in order -- the C/D fragment of one layer is the
-// B fragment of the next -- and those of the input layer inputs 4 s .. 4 s + 3.
+// B fragment of the next -- and those of the input layer inputs 4 s .. 4 s + 3.  That is the chain of rows 0 .. 47, the three
+// row tiles on the matrix core; k-steps (3, 0) and (3, 1), their last, hold neurons 48 and 49 alone.
+// TAIL ROWS.  A last row tile with NT = H - 48 <= 4 live rows (two at H = 50) does not run on the matrix core: each of its rows
+// is summed on the VALU, by the four lanes q = 0..3 of the candidate's column (score_mfma.hip: filter_pass_f32).  Lane q chains
+//   p_q = fma-chain( [q = 0: b~_i, then w~_i,48 a^_48, w~_i,49 a^_49 (the tail neurons of the layer in front)],
+//                    then its twelve terms j = 16 tk + 4 q + i' in the order of 4 tk + i' = 0 .. 11 ),
+// one rounding per fma (on q >= 1 the head of the chain adds exact zeros to an exact zero), and the lanes are summed as
+//   z_i = (p_q + p_(q^1)) + (p_(q^2) + p_(q^3)):  two more roundings for every term.
+// So in a tail row term j < 48 sees m_j = 12 - (4 tk + i') + 2 roundings (its own fma, the later ones of its lane, the tree),
+// tail term 48 + v sees NT - v + 12 + 2 and the bias NT + 12 + 2; these replace gamma(fan - before[j]) and gamma(fan) above.
+// In the input layer lane q chains the inputs q, 4 + q, 8 + q .. below the fan-in (`live` of them; a padded term adds an exact
+// zero) behind the bias on q = 0:  m_j = live - j / 4 + 2, and the bias sees the ceil(fan / 4) links of lane 0 and the tree.
+// Every other term of the bound -- conversion, inputs' error, tansig -- is that of the other rows.  (Widths whose last tile
+// holds more than four rows, or none, have no tail rows: NT = 0.)
 // tansig is 1-Lipschitz in n = z / c, which covers the error of exp2's ARGUMENT; what the hardware adds on top of the exact
 // 2 / (1 + 2^z) - 1:  v_exp_f32 and v_rcp_f32 are documented to 1 ulp, counted as 2 ulp = 4 u each, the add and the fma u each.
 // With E = 2^z, r = 1 / (1 + E) <= 1:  |2 r^ - 2 r| <= 2 r (4 u + u) + 2 (4 u) E / (1 + E)^2 <= 10 u + 2 u, and the fma's own
@@ -70,6 +83,7 @@ static inline double net_filter_margin(int k, int nh, int H, int d_in, const dou
 {
     const double u = 0x1p-24, c = FILTER_EXP_SCALE;
     auto gamma = [&](int m) { return m * u / (1.0 - m * u); };
+    const int NT = (H > 48 && H <= 52) ? H - 48 : 0;      // tail rows 48 .. H - 1 (two at the width that filters, 50)
     double e[MAX_HIDDEN], A[MAX_HIDDEN], en[MAX_HIDDEN];
     for (int i = 0; i < d_in; ++i) {
         const double lo = i < k ? 0.0 : -1.0 / (double)k, hi = i < k ? 1.0 : 1.0 / (double)k;
@@ -97,12 +111,28 @@ static inline double net_filter_margin(int k, int nh, int H, int d_in, const dou
                     cnt += live;
                 }
         }
+        // the tail rows' own count: roundings seen by term j, and by the bias
+        int mtail[MAX_HIDDEN], mtail_bias = 0;
+        if (NT > 0) {
+            if (l == 0) {
+                for (int j = 0; j < fan; ++j) {
+                    const int q = j % 4, s = j / 4, live = (fan - q + 3) / 4;      // lane q chains inputs q, 4 + q, ...: `live` of them
+                    mtail[j] = live - s + 2;
+                }
+                mtail_bias = (fan + 3) / 4 + 2;
+            } else {
+                for (int j = 0; j < 48; ++j) mtail[j] = 12 - (4 * (j / 16) + j % 4) + 2;      // j = 16 tk + 4 q + i: link 4 tk + i of 12
+                for (int j = 48; j < fan; ++j) mtail[j] = NT - (j - 48) + 12 + 2;
+                mtail_bias = NT + 12 + 2;
+            }
+        }
         for (int i = 0; i < H; ++i) {
+            const bool tail = NT > 0 && i >= 48;
             const double bt = (double)(float)(c * B[l][i]);
-            double acc = std::fabs(bt) * gamma(fan) + std::fabs(bt - c * B[l][i]);
+            double acc = std::fabs(bt) * gamma(tail ? mtail_bias : fan) + std::fabs(bt - c * B[l][i]);
             for (int j = 0; j < fan; ++j) {
                 const double w = W[l][(size_t)i * fan + j], wt = (double)(float)(c * w);
-                acc += std::fabs(wt) * A[j] * gamma(fan - before[j]) + std::fabs(wt - c * w) * A[j] + std::fabs(c * w) * e[j];
+                acc += std::fabs(wt) * A[j] * gamma(tail ? mtail[j] : fan - before[j]) + std::fabs(wt - c * w) * A[j] + std::fabs(c * w) * e[j];
             }
             en[i] = acc / std::fabs(c) + 13.0 * u;
         }

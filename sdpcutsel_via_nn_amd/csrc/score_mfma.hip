@@ -249,6 +249,17 @@ struct MfmaLdsSkip {
     uint32_t pf_tab[pf_score_k(K) ? PF_BINS / 2 : 1];
 };
 
+// The small fp32 constants of the filter's pass in LDS: [NH][64] biases, then the weights of the two tail neurons 48 and 49 as
+// the lanes of the VALU tail read them, [layer][u][q][16]: for a hidden layer entries 4 tk + i = c W[48 + u][16 tk + 4 q + i]
+// (tk < 3: the twelve activations lane (q, c) holds), entries 12, 13 = c W[48 + u][48], c W[48 + u][49]; for the input layer
+// entries s = c W0[48 + u][4 s + q].  All of them are read out of the packed A-fragments of row tile 3 (net_pack.h: lane
+// u + 16 q of fragment (3, tk)), the same fl32(c W) values the matrix core used to multiply (filter_lds_fill below).
+template <int NH>
+struct FilterLds {
+    static constexpr int BIAS = NH * 64, TAIL = NH * 2 * 4 * 16;
+    alignas(16) float v[BIAS + TAIL];
+};
+
 // LDS of one workgroup of the skipping kernel with the fp32 filter (FILTER, see score_mfma_body): TWO rings per wave.  Ring 1 (f_*,
 // FCAP = 96 slots: <= 31 pending + <= 64 appended by a strip) holds the violated candidates, ring 2 (the names of MfmaLdsSkip,
 // QCAP = 64: <= 31 pending + <= 32 survivors of one filter pass) those of them the fp32 pass could not rule out.  Only the DIN live
@@ -270,7 +281,7 @@ struct MfmaLdsFilter {
     int32_t f_out[4][FCAP];
     uint8_t f_byp[4][FCAP];      // the candidate has a mapped input outside NetDev::filter_box: it survives unconditionally
     double f_y[4][32];           // raw fp32-pass outputs of the 32 entries of a filter pass
-    alignas(16) float s_bias32[NH * 64];
+    FilterLds<NH> s_f32;         // biases and tail-neuron weights of the fp32 pass
     double s_bias[NH * 64];
     double s_wtail[NT ? NH * 4 * 64 : 1];
     double s_wout[64];
@@ -281,25 +292,67 @@ struct MfmaLdsFilter {
 };
 
 // ------------------------------------------------------------------------------------------
+// v + v(lane ^ 32) and v + v(lane ^ 16) of a float, as xor_add32 / xor_add16 above: both lanes of a pair add the same two values
+__device__ __forceinline__ float xor_add32f(float v)
+{
+    const unsigned x = __float_as_uint(v);
+    const u32x2 a = __builtin_amdgcn_permlane32_swap(x, x, false, false);
+    return __uint_as_float(a[0]) + __uint_as_float(a[1]);
+}
+__device__ __forceinline__ float xor_add16f(float v)
+{
+    const unsigned x = __float_as_uint(v);
+    const u32x2 a = __builtin_amdgcn_permlane16_swap(x, x, false, false);
+    return __uint_as_float(a[0]) + __uint_as_float(a[1]);
+}
+
+// Fills FilterLds (above) from the packed fp32 weights.  Call before a __syncthreads().
+template <int NH>
+__device__ __forceinline__ void filter_lds_fill(const NetDev &net, FilterLds<NH> &F)
+{
+    for (int i = threadIdx.x; i < FilterLds<NH>::BIAS; i += blockDim.x) F.v[i] = net.f32_bias[i];
+    for (int i = threadIdx.x; i < FilterLds<NH>::TAIL; i += blockDim.x) {
+        const int l = i >> 7, u = (i >> 6) & 1, q = (i >> 4) & 3, e = i & 15;
+        float w = 0.0f;
+        if (l == 0) {
+            if (e < 4) w = net.f32_in[((size_t)(3 * 64 + u + 16 * q)) * 4 + e];
+        } else if (e < 12) {
+            w = net.f32_hid[((((size_t)(l - 1) * 4 + 3) * 4 + (e >> 2)) * 64 + u + 16 * q) * 4 + (e & 3)];
+        } else if (e < 14) {
+            w = net.f32_hid[((((size_t)(l - 1) * 4 + 3) * 4 + 3) * 64 + u) * 4 + (e - 12)];
+        }
+        F.v[FilterLds<NH>::BIAS + i] = w;
+    }
+}
+
 // The fp32 pass of the filter (stage F of the skipping kernel, and all of filter_audit_kernel): the MLP of 32 candidates on
 // v_mfma_f32_16x16x4_f32, two column tiles of 16 = two independent accumulator chains.  feat_at(row, col) is the staged (mapped,
 // fp64) input `row` of column col = 0..31.  Returns in yraw[j], on every lane of column c16 of tile j, the output layer's sum
 // (without b_out) as a double.
 //  * Layouts: A lane l = A[row l & 15][k l >> 4], B lane l = B[k l >> 4][col l & 15], C/D register i of lane l = row
 //    4 (l >> 4) + i.  So register i of row tile tk IS the B operand of a k-step that multiplies neurons {16 tk + 4 q + i}: the
-//    host packs the A-fragments in that k-order (net_pack.h) and the activations never leave registers.  All four row tiles run
-//    on the matrix core; k-steps (3, 2) and (3, 3) hold no neuron below H = 50 and are left out.
-//  * The accumulator starts as the (scaled) bias and the k-steps follow in order: the chain the margin's derivation counts.
+//    host packs the A-fragments in that k-order (net_pack.h) and the activations never leave registers.
+//  * Row tiles 0..2 (neurons 0..47) run on the matrix core.  Their accumulator starts as the (scaled) bias and the k-steps follow
+//    in order -- (0, 0) .. (2, 3), then (3, 0) and (3, 1), whose B operand holds the tail neurons 48 and 49 on the q = 0 lanes and
+//    an exact 0.0f on the others: the chain the margin's derivation counts.
+//  * Neurons 48 and 49 (a fourth row tile would be 14 rows of padding) run on the VALU.  Lane (q, c) chains
+//        p = (q == 0 ? bias : 0);  p = fma(w[48], a48, p);  p = fma(w[49], a49, p);  p = fma(w[16 tk + 4 q + i], a, p), (tk, i) in order
+//    over the two tail activations of the layer in front (0 on q >= 1: the bias and these two terms enter on the q = 0 lane
+//    only, at the HEAD of its chain) and the twelve activations it holds; the four q-lanes of the column are then summed as
+//    (p_q + p_(q^1)) + (the same of q^2), and every lane takes the tansig.  The input layer's tail chains the lane's S0 inputs
+//    4 s + q the same way.  This order, too, is what net_filter_margin counts.
 //  * The output layer is a fp64 dot product of the fp32 activations with the fp64 output weights (13 fma per lane and tile) and the
 //    cross-lane sum of the fp64 pass: no fp32 rounding behind the last tansig.
-// Columns are independent: a stale or padding column (NaN included) changes no other column's result.
+// Columns are independent: the tail's sums go across the q-lanes of ONE column, so a stale or padding column (NaN included)
+// changes no other column's result, and the select behind the tansig puts a finite zero on q >= 1 whatever the sum was.
 template <int K, int H, int NH, class FeatAt>
-__device__ __forceinline__ void filter_pass_f32(const NetDev &net, const float *s_bias32, const double *s_wout, FeatAt feat_at,
+__device__ __forceinline__ void filter_pass_f32(const NetDev &net, const FilterLds<NH> &F, const double *s_wout, FeatAt feat_at,
                                                 const int lane, double (&yraw)[2])
 {
     constexpr int DIN = K + K * (K + 1) / 2;
     constexpr int S0 = (DIN + 3) / 4;
-    static_assert(S0 <= 4 && H > 48 && H <= 64, "one float4 of input k-steps per lane; four row tiles");
+    static_assert(S0 <= 4 && H == 50, "one float4 of input k-steps per lane; three row tiles and the tail neurons 48, 49");
+    const float *s_bias32 = F.v, *s_tail32 = F.v + FilterLds<NH>::BIAS;
     const int q = lane >> 4, c16 = lane & 15;
     float bin[S0][2];
 #pragma unroll
@@ -310,22 +363,42 @@ __device__ __forceinline__ void filter_pass_f32(const NetDev &net, const float *
             const double v = feat_at(row < DIN ? row : 0, 16 * j + c16);
             bin[s][j] = row < DIN ? (float)v : 0.0f;
         }
-    // tansig of a C/D fragment of row tile t; rows >= H are padding -> 0
-    auto act = [&](const f4 z, const int t) __attribute__((always_inline)) {
+    // tansig of a C/D fragment of a row tile below 48: every row is a neuron
+    auto act = [&](const f4 z) __attribute__((always_inline)) {
         f4 a;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) a[i] = (16 * t + 4 * q + i < H) ? tansig_f32_z(z[i]) : 0.0f;
+        for (int i = 0; i < 4; ++i) a[i] = tansig_f32_z(z[i]);
         return a;
     };
-    f4 cur[4][2], prev[4][2];
+    // a tail neuron from its lane chain: the column's four q-lanes summed, tansig, and the value kept on q = 0 only
+    auto tail_act = [&](float p) __attribute__((always_inline)) {
+        p = xor_add16f(p);
+        p = xor_add32f(p);
+        const float a = tansig_f32_z(p);
+        return q == 0 ? a : 0.0f;
+    };
+    f4 cur[3][2], prev[3][2];
+    float ctl[2][2], ptl[2][2];      // [column tile][u]: neurons 48 + u
     // ---------------- input layer
     {
         const f4 *w_in = (const f4 *)net.f32_in;
-        f4 w[4];
+        f4 w[3];
 #pragma unroll
-        for (int t = 0; t < 4; ++t) w[t] = w_in[t * 64 + lane];
+        for (int t = 0; t < 3; ++t) w[t] = w_in[t * 64 + lane];
 #pragma unroll
-        for (int t = 0; t < 4; ++t) {
+        for (int u = 0; u < 2; ++u) {
+            const f4 wt = *(const f4 *)&s_tail32[(u * 4 + q) * 16];
+            const float b = q == 0 ? s_bias32[48 + u] : 0.0f;
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                float p = b;
+#pragma unroll
+                for (int s = 0; s < S0; ++s) p = __builtin_fmaf(wt[s], bin[s][j], p);
+                ctl[j][u] = tail_act(p);
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
             const f4 bias = *(const f4 *)&s_bias32[16 * t + 4 * q];
             f4 acc0 = bias, acc1 = bias;
 #pragma unroll
@@ -333,25 +406,27 @@ __device__ __forceinline__ void filter_pass_f32(const NetDev &net, const float *
                 acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w[t][s], bin[s][0], acc0, 0, 0, 0);
                 acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w[t][s], bin[s][1], acc1, 0, 0, 0);
             }
-            cur[t][0] = act(acc0, t);
-            cur[t][1] = act(acc1, t);
+            cur[t][0] = act(acc0);
+            cur[t][1] = act(acc1);
         }
     }
     // ---------------- hidden -> hidden layers (rolled); the fragments of row tile t + 1 are requested while tile t computes
 #pragma unroll 1
     for (int l = 1; l < NH; ++l) {
 #pragma unroll
-        for (int t = 0; t < 4; ++t) { prev[t][0] = cur[t][0]; prev[t][1] = cur[t][1]; }
+        for (int t = 0; t < 3; ++t) { prev[t][0] = cur[t][0]; prev[t][1] = cur[t][1]; }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) { ptl[j][0] = ctl[j][0]; ptl[j][1] = ctl[j][1]; }
         const f4 *wh = (const f4 *)net.f32_hid + (size_t)(l - 1) * 4 * 4 * 64 + lane;
         f4 wnx[4];
 #pragma unroll
         for (int tk = 0; tk < 4; ++tk) wnx[tk] = wh[tk * 64];
 #pragma unroll
-        for (int t = 0; t < 4; ++t) {
+        for (int t = 0; t < 3; ++t) {
             f4 w[4];
 #pragma unroll
             for (int tk = 0; tk < 4; ++tk) w[tk] = wnx[tk];
-            if (t + 1 < 4) {
+            if (t + 1 < 3) {
 #pragma unroll
                 for (int tk = 0; tk < 4; ++tk) wnx[tk] = wh[((t + 1) * 4 + tk) * 64];
             }
@@ -359,25 +434,54 @@ __device__ __forceinline__ void filter_pass_f32(const NetDev &net, const float *
             const f4 bias = *(const f4 *)&s_bias32[l * 64 + 16 * t + 4 * q];
             f4 acc0 = bias, acc1 = bias;
 #pragma unroll
-            for (int tk = 0; tk < 4; ++tk)
+            for (int tk = 0; tk < 3; ++tk)
 #pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    if (16 * tk + i < H) {      // (the k-step's first neuron, q = 0)
-                        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w[tk][i], prev[tk][0][i], acc0, 0, 0, 0);
-                        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w[tk][i], prev[tk][1][i], acc1, 0, 0, 0);
+                for (int i = 0; i < 4; ++i) {
+                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w[tk][i], prev[tk][0][i], acc0, 0, 0, 0);
+                    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w[tk][i], prev[tk][1][i], acc1, 0, 0, 0);
+                }
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {      // k-steps (3, 0) and (3, 1): neurons 48 + u on q = 0, zeros elsewhere
+                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w[3][u], ptl[0][u], acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w[3][u], ptl[1][u], acc1, 0, 0, 0);
+            }
+            if (t == 0) {
+                // the layer's two tail neurons, in the region of tile 0: everything they read is the layer in front
+                const float *tw = &s_tail32[((l * 2) * 4 + q) * 16];
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    f4 wk[3];
+#pragma unroll
+                    for (int tk = 0; tk < 3; ++tk) wk[tk] = *(const f4 *)&tw[u * 64 + 4 * tk];
+                    const float w48 = tw[u * 64 + 12], w49 = tw[u * 64 + 13];
+                    const float b = q == 0 ? s_bias32[l * 64 + 48 + u] : 0.0f;
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+                        float p = b;
+                        p = __builtin_fmaf(w48, ptl[j][0], p);
+                        p = __builtin_fmaf(w49, ptl[j][1], p);
+#pragma unroll
+                        for (int tk = 0; tk < 3; ++tk)
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) p = __builtin_fmaf(wk[tk][i], prev[tk][j][i], p);
+                        ctl[j][u] = tail_act(p);
                     }
-            cur[t][0] = act(acc0, t);
-            cur[t][1] = act(acc1, t);
+                }
+            }
+            cur[t][0] = act(acc0);
+            cur[t][1] = act(acc1);
         }
     }
-    // ---------------- linear output layer in fp64
+    // ---------------- linear output layer in fp64; the tail neurons' terms last, as rows 48 and 49 of the fourth tile were
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         double part = 0.0;
 #pragma unroll
-        for (int t = 0; t < 4; ++t)
+        for (int t = 0; t < 3; ++t)
 #pragma unroll
             for (int i = 0; i < 4; ++i) part = fma((double)cur[t][j][i], s_wout[16 * t + 4 * q + i], part);
+#pragma unroll
+        for (int u = 0; u < 2; ++u) part = fma((double)ctl[j][u], s_wout[48 + u], part);
         part = xor_add16(part);
         part = xor_add32(part);
         yraw[j] = part;
@@ -482,9 +586,7 @@ __device__ __forceinline__ void score_mfma_body(const ScoreArgs A, LDS &S, const
         if constexpr (NT > 0)
             for (int i = threadIdx.x; i < NH * 4 * 64; i += 256) s_wtail[i] = net.wtail[i];
         if (threadIdx.x < 64) s_wout[threadIdx.x] = net.wout[threadIdx.x];
-        if constexpr (FILTER) {
-            if (threadIdx.x < NH * 64) S.s_bias32[threadIdx.x] = net.f32_bias[threadIdx.x];
-        }
+        if constexpr (FILTER) filter_lds_fill<NH>(net, S.s_f32);
         __syncthreads();
     }
 #endif
@@ -823,7 +925,7 @@ __device__ __forceinline__ void score_mfma_body(const ScoreArgs A, LDS &S, const
                 // stale slots and are not live); the survivors are appended to ring 2 in ring-1 order
                 auto filter_round = [&](const int cnt) __attribute__((always_inline)) {
                     double yr[2];
-                    filter_pass_f32<K, H, NH>(net, S.s_bias32, s_wout,
+                    filter_pass_f32<K, H, NH>(net, S.s_f32, s_wout,
                                               [&](const int row, const int col) { return S.f_feat[wave][row][f_head + col]; }, lane, yr);
                     if (q == 0) { S.f_y[wave][c16] = yr[0]; S.f_y[wave][16 + c16] = yr[1]; }
                     wave_lds_sync();
@@ -1037,12 +1139,12 @@ __global__ __launch_bounds__(256) void filter_audit_kernel(ScoreArgs A, double *
 {
     constexpr int DIN = K + K * (K + 1) / 2;
     __shared__ double s_feat[4][DIN][32];
-    __shared__ alignas(16) float s_bias32[NH * 64];
+    __shared__ FilterLds<NH> s_f32;
     __shared__ double s_wout[64];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int q = lane >> 4, c16 = lane & 15;
     const NetDev &net = A.net;
-    if (threadIdx.x < NH * 64) s_bias32[threadIdx.x] = net.f32_bias[threadIdx.x];
+    filter_lds_fill<NH>(net, s_f32);
     if (threadIdx.x < 64) s_wout[threadIdx.x] = net.wout[threadIdx.x];
     __syncthreads();
     for (int64_t base = ((int64_t)blockIdx.x * 4 + wave) * 32; base < A.n; base += (int64_t)gridDim.x * 4 * 32) {
@@ -1060,7 +1162,7 @@ __global__ __launch_bounds__(256) void filter_audit_kernel(ScoreArgs A, double *
         }
         wave_lds_sync();
         double yr[2];
-        filter_pass_f32<K, H, NH>(net, s_bias32, s_wout, [&](const int row, const int col) { return s_feat[wave][row][col]; }, lane, yr);
+        filter_pass_f32<K, H, NH>(net, s_f32, s_wout, [&](const int row, const int col) { return s_feat[wave][row][col]; }, lane, yr);
         if (q == 0) {
 #pragma clang fp contract(off)
 #pragma unroll

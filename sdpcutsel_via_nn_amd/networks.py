@@ -135,8 +135,21 @@ def filter_margin(k, widths, params):
                     cnt += len(live)
         wt = (c * W).astype(np.float32).astype(np.float64)
         bt = (c * b).astype(np.float32).astype(np.float64)
-        acc = np.abs(bt) * gamma(fan) + np.abs(bt - c * b)
-        acc = acc + (np.abs(wt) * (A * gamma(fan - before)) + np.abs(wt - c * W) * A + np.abs(c * W) * e).sum(axis=1)
+        H = W.shape[0]
+        m = np.tile(fan - before, (H, 1))      # roundings term j sees in row i
+        mb = np.full(H, fan)                   # ... and the bias
+        if 48 < H <= 52:                       # tail rows 48 .. H - 1: a lane chain and a two-level tree on the VALU
+            nt = H - 48
+            if l == 0:                         # lane q chains inputs q, 4 + q, ..: `live` of them
+                mt = (fan - j % 4 + 3) // 4 - j // 4 + 2
+                mbt = (fan + 3) // 4 + 2
+            else:                              # b, the tail neurons of the layer in front, then links 4 tk + i of twelve
+                mt = np.where(j < 48, 12 - (4 * (j // 16) + j % 4) + 2, nt - (j - 48) + 12 + 2)
+                mbt = nt + 12 + 2
+            m[48:] = mt
+            mb[48:] = mbt
+        acc = np.abs(bt) * gamma(mb) + np.abs(bt - c * b)
+        acc = acc + (np.abs(wt) * (A * gamma(m)) + np.abs(wt - c * W) * A + np.abs(c * W) * e).sum(axis=1)
         e = acc / abs(c) + 13.0 * u
         A = np.full(W.shape[0], 1.0 + 8.0 * u)
     return float((np.abs(Ws[-1][0]) * e).sum() / abs(y_gain) * (1.0 + 2.0 ** -10))
