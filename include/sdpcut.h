@@ -62,7 +62,10 @@ enum { SDPCUT_PART_STRONG = 104 };
  * third field of the record (the merge's secondary key: the second stable sort of :625 keeps the order of the first, :601). */
 enum { SDPCUT_PART_COMBALL = 105 };
 
-/* kernel variants for sdpcut_set_option(SDPCUT_OPT_KERNEL, ...) */
+/* kernel variants for sdpcut_set_option(SDPCUT_OPT_KERNEL, ...).  The variants agree on the optimality measure to rounding, not to
+ * the bit: CHANGING the variant invalidates the optimality scores of the current list at the current point, as replacing a network
+ * does (the next call that needs them computes them again; lambda_min and the exact measure are kept), and is refused with
+ * SDPCUT_ESTATE while a round is pending. */
 enum { SDPCUT_KERNEL_MFMA = 0, SDPCUT_KERNEL_SIMPLE = 1, SDPCUT_KERNEL_VALU = 2 };
 /* SDPCUT_OPT_FUSE_KEYS (default 1): sdpcut_select_round lets the score kernels count their scores by
  * the leading radix digit of the selection keys (per workgroup in LDS, flushed with no-return atomics)
@@ -411,7 +414,10 @@ int sdpcut_rank_device(sdpcut_handle h, int strat, int64_t sel_size, int64_t max
 
 /* Read entries [offset, offset+count) of the ranking produced by the last sdpcut_rank /
  * sdpcut_rank_device call (the reference hands back the whole sorted list; callers normally
- * consume only its head, so the tail stays on the device until asked for). */
+ * consume only its head, so the tail stays on the device until asked for).  A ranking whose head came from the top-k selection
+ * (max_out <= 16384 and no void selection) has no tail on the device: the call then fails with SDPCUT_ESTATE, as it does before
+ * the first ranking and after sdpcut_set_point, sdpcut_set_candidates, sdpcut_set_box, sdpcut_tri_separate and a batched call.
+ * Which of the two a ranking is depends on the list, the scores, the options and the arguments alone, not on earlier calls. */
 int sdpcut_rank_fetch(sdpcut_handle h, int64_t offset, int64_t count, int64_t *idx_out,
                       double *score_out);
 

@@ -131,6 +131,12 @@ int sdpcut_set_option(sdpcut_handle h, int option, int64_t value)
     case SDPCUT_OPT_KERNEL:
         if (value != SDPCUT_KERNEL_MFMA && value != SDPCUT_KERNEL_SIMPLE && value != SDPCUT_KERNEL_VALU)
             return sdpcut_fail(h, SDPCUT_EINVAL, "unknown kernel variant");
+        if ((int)value != h->kernel_variant) {
+            // the variants agree on the optimality measure to rounding, not to the bit: like the scores of a replaced network
+            // (sdpcut_set_network) those of the old variant are not what the next call would compute -- it scores again
+            SDPCUT_NO_PENDING(h);
+            h->scored &= ~(uint32_t)SDPCUT_NN; h->obj_partial = false;
+        }
         h->kernel_variant = (int)value;
         return SDPCUT_OK;
     case SDPCUT_OPT_FUSE_KEYS:
