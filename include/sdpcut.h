@@ -355,8 +355,9 @@ int sdpcut_set_point_device(sdpcut_handle h, const void *d_vars_values);
  * amplifies rounding by ~ 8 eps / (d_i d_j) absolute on X'), else SDPCUT_EINVAL: fixed and nearly fixed variables are a limitation.
  * Both NULL clears the box.  Clears the SDPCUT_NN and SDPCUT_SDP bits of the scores at the current point and keeps SDPCUT_EIG; a
  * current point is transformed again.  sdpcut_set_instance clears the box.
- * Refused while a box is set (SDPCUT_ESTATE, handle unchanged): sdpcut_score_points and sdpcut_round_csr_points (their kernels
- * have one Q for all points), the sharded entry points (sdpcut_shard_*), and switching SDPCUT_OPT_EXACT_HEAD on (reference-exact
+ * Refused while a box is set (SDPCUT_ESTATE, handle unchanged): sdpcut_score_points and sdpcut_round_csr_points (one Q for all
+ * points) and their boxed forms sdpcut_score_points_boxed / sdpcut_round_csr_points_boxed (a box per point, passed with the
+ * call: the handle's own would be lost), the sharded entry points (sdpcut_shard_*), and switching SDPCUT_OPT_EXACT_HEAD on (reference-exact
  * bits have no meaning where the reference has no boxes); sdpcut_set_box refuses a box while that option is on.
  */
 #define SDPCUT_BOX_MIN_WIDTH 0.0009765625 /* 2^-10 */
@@ -570,6 +571,31 @@ int sdpcut_score_points(sdpcut_handle h, int32_t n_points, const double *points,
                         double *obj_out);
 int sdpcut_round_csr_points(sdpcut_handle h, int32_t n_points, const double *points, int64_t point_ld, int strat, int64_t sel_size,
                             sdpcut_round_csr_t *out /* [n_points] */);
+
+/*
+ * The same two calls with a NODE BOX PER POINT (sdpcut_set_box): the open nodes of a tree search, each with its own LP point and
+ * its own variable bounds.  Row p of lb / ub (row p at lb + p * box_ld, box_ld >= n) is the box of point p; a [P][2][n] array is
+ * passed as lb = boxes, ub = boxes + n, box_ld = 2 n.
+ *   Row p of the result is, bit for bit, what sdpcut_set_box(h, lb_p, ub_p) followed by the single-point call at point p returns
+ *   on a fresh handle: scores, heads, every CSR array, n_total, new_strat and the counters.
+ *   Every box is checked with sdpcut_set_box's rule before any state changes (SDPCUT_EINVAL; the message names the point and the
+ *   variable).  A handle that has a box of its own is refused (SDPCUT_ESTATE) and keeps it, like the unboxed calls;
+ *   SDPCUT_OPT_EXACT_HEAD on is refused as sdpcut_set_box refuses it (SDPCUT_ESTATE), a pending round as everywhere.  Flags,
+ *   strategies and n_points are those of the unboxed calls.  After either call the handle has NO CURRENT POINT AND NO BOX,
+ *   whichever way the call returns.
+ *   One-wait route: under the conditions of sdpcut_round_csr_points, and while the per-point tables -- n_points (2 L + n) doubles:
+ *   Q' and the transformed point of every point -- fit 256 MiB.  The (l | d) rows travel with the points; one launch with a point
+ *   axis writes every Q'_p and transformed point (csrc/box.hip: box_points_kernel); lambda_min is scored on the original points,
+ *   the measure by the MFMA launch on the transformed ones with a Q stride of L; the combined strategy's strong class is counted
+ *   per point by a small kernel (neither launch sees both measures); selection and row assembly are the unboxed batch's.  A scan
+ *   that asks for SDPCUT_EIG alone, and a strategy-1 batch, need no box table at all.  A point whose selection declared itself
+ *   void goes through sdpcut_set_box and the single-point round inside the call.
+ *   Everything else loops inside the call: sdpcut_set_box and the single-point round per point, the box cleared at the end.
+ */
+int sdpcut_score_points_boxed(sdpcut_handle h, int32_t n_points, const double *points, int64_t point_ld, const double *lb, const double *ub,
+                              int64_t box_ld, uint32_t flags, double *eig_out, double *obj_out);
+int sdpcut_round_csr_points_boxed(sdpcut_handle h, int32_t n_points, const double *points, int64_t point_ld, const double *lb, const double *ub,
+                                  int64_t box_ld, int strat, int64_t sel_size, sdpcut_round_csr_t *out /* [n_points] */);
 
 /*
  * Diverse selection: a parallelism filter on the ranked head.  A round takes the first sel_size entries of its ranking however

@@ -136,6 +136,8 @@ SIGNATURES = {
     "sdpcut_round_csr_end": [_vp, _c.POINTER(RoundCsr)],
     "sdpcut_score_points": [_vp, _c.c_int32, _dp, _c.c_int64, _c.c_uint32, _dp, _dp],
     "sdpcut_round_csr_points": [_vp, _c.c_int32, _dp, _c.c_int64, _c.c_int, _c.c_int64, _c.POINTER(RoundCsr)],
+    "sdpcut_score_points_boxed": [_vp, _c.c_int32, _dp, _c.c_int64, _dp, _dp, _c.c_int64, _c.c_uint32, _dp, _dp],
+    "sdpcut_round_csr_points_boxed": [_vp, _c.c_int32, _dp, _c.c_int64, _dp, _dp, _c.c_int64, _c.c_int, _c.c_int64, _c.POINTER(RoundCsr)],
     "sdpcut_round_csr_diverse": [_vp, _dp, _c.c_int, _c.c_int64, _c.c_int64, _c.c_double, _c.POINTER(RoundCsr), _c.POINTER(DiverseInfo)],
     "sdpcut_filter_parallel": [_vp, _c.c_int64, _i64p, _c.c_int64, _c.c_double, _c.POINTER(_c.c_uint8), _c.POINTER(DiverseInfo)],
     "sdpcut_round_csr_multi": [_vp, _dp, _c.c_int, _c.c_int64, _c.c_int32, _c.c_int64, _c.POINTER(RoundMulti)],
@@ -1000,34 +1002,59 @@ class Scorer(object):
             raise ValueError("1 .. %d points per call" % BATCH_MAX_POINTS)
         return pts
 
-    def score_points(self, points, eig=True, obj=True):
+    def _boxes_arg(self, pts, boxes):
+        """boxes [P, 2, n] of a boxed batch, checked (nodebox.check_boxes) -> contiguous float64, and the pointers (lb, ub, box_ld)
+        the boxed entry points take"""
+        from .nodebox import check_boxes
+        bx = check_boxes(self.nb_vars, boxes, n_points=pts.shape[0])
+        n = int(self.nb_vars)
+        ub = _c.cast(_c.c_void_p(bx.ctypes.data + 8 * n), _dp)
+        return bx, bx.ctypes.data_as(_dp), ub, 2 * n
+
+    def score_points(self, points, eig=True, obj=True, boxes=None):
         """Scores of the candidate list at P LP points in one call (sdpcut_score_points): points [P, n(n+1)/2 + n] ->
         (eig [P, N] | None, obj [P, N] | None), row p = what set_point(points[p]), score, get_scores return.  Leaves the Scorer
-        without a current point."""
+        without a current point.
+        boxes [P, 2, n]: (lb, ub) of the node of every point (sdpcut_score_points_boxed); row p is then what set_box(*boxes[p]),
+        set_point, score, get_scores return.  The Scorer must have no box of its own and has none afterwards."""
         pts = self._points_arg(points)
         if not (eig or obj):
             raise ValueError("nothing asked for")
         P = pts.shape[0]
         e = np.empty((P, self.N)) if eig else None
         o = np.empty((P, self.N)) if obj else None
-        self._check(self._lib.sdpcut_score_points(self._h, P, _ptr(pts, _dp), pts.shape[1], (EIG if eig else 0) | (NN if obj else 0),
-                                                  _ptr(e, _dp), _ptr(o, _dp)))
+        flags = (EIG if eig else 0) | (NN if obj else 0)
+        if boxes is None:
+            self._check(self._lib.sdpcut_score_points(self._h, P, _ptr(pts, _dp), pts.shape[1], flags, _ptr(e, _dp), _ptr(o, _dp)))
+        else:
+            bx, lb, ub, box_ld = self._boxes_arg(pts, boxes)
+            self._check(self._lib.sdpcut_score_points_boxed(self._h, P, _ptr(pts, _dp), pts.shape[1], lb, ub, box_ld, flags,
+                                                            _ptr(e, _dp), _ptr(o, _dp)))
         return e, o
 
-    def round_csr_points(self, points, strat, sel_size, copy=False):
+    def round_csr_points(self, points, strat, sel_size, copy=False, boxes=None):
         """P rounds with the cuts assembled, one LP point each, in one call (sdpcut_round_csr_points): points [P, n(n+1)/2 + n] ->
         list of P dicts, entry p = what round_csr(strat, sel_size, point=points[p]) returns (same keys, dtypes and values).  The
         arrays are numpy views of the handle's pinned batch block, valid until the next call on this Scorer; copy=True detaches
-        them.  Strategies 1, 2 and 4.  Leaves the Scorer without a current point."""
+        them.  Strategies 1, 2 and 4.  Leaves the Scorer without a current point.
+        boxes [P, 2, n]: (lb, ub) of the node of every point (sdpcut_round_csr_points_boxed); entry p is then what set_box(*boxes[p])
+        followed by round_csr(strat, sel_size, point=points[p]) returns.  The Scorer must have no box of its own and has none
+        afterwards."""
         pts = self._points_arg(points)
         P = pts.shape[0]
+        if boxes is not None:
+            bx, lb, ub, box_ld = self._boxes_arg(pts, boxes)
         self._open()
         self.round_count += 1
         recs =getattr(self, "_csr_points_recs", None)
         if recs is None or recs.shape[0] < P:
             recs = self._csr_points_recs = np.zeros(max(P, 8), dtype=_ROUND_CSR_DTYPE)
-        self._check(self._lib.sdpcut_round_csr_points(self._h, P, _ptr(pts, _dp), pts.shape[1], int(strat), int(sel_size),
-                                                      recs.ctypes.data_as(_c.POINTER(RoundCsr))))
+        if boxes is None:
+            self._check(self._lib.sdpcut_round_csr_points(self._h, P, _ptr(pts, _dp), pts.shape[1], int(strat), int(sel_size),
+                                                          recs.ctypes.data_as(_c.POINTER(RoundCsr))))
+        else:
+            self._check(self._lib.sdpcut_round_csr_points_boxed(self._h, P, _ptr(pts, _dp), pts.shape[1], lb, ub, box_ld, int(strat),
+                                                                int(sel_size), recs.ctypes.data_as(_c.POINTER(RoundCsr))))
         r = recs[:P]
         base = int(r["idx"].min())
         if base:

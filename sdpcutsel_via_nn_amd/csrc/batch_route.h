@@ -38,6 +38,23 @@ static inline int batch_route(int64_t N, int64_t cap, int strat, bool exact_head
     return (p.err == 0 && p.route == TK_ROUTE_SMALLSORT) ? BATCH_FAST : BATCH_LOOP;
 }
 
+// A boxed batch (sdpcut_round_csr_points_boxed): every point has a Q' [L] and a transformed point [L + n] of its own on the device,
+// n_points (2 L + n) doubles.  n = 125 at 256 points is 33 MB; the budget only keeps a large-n instance from allocating gigabytes.
+#define BATCH_BOX_BUDGET_BYTES ((int64_t)256 << 20)
+static inline int64_t batch_box_table_bytes(int64_t nb_vars, int64_t n_points)
+{
+    const int64_t L = nb_vars * (nb_vars + 1) / 2;
+    return n_points * (2 * L + nb_vars) * 8;
+}
+
+// BATCH_FAST under batch_route's conditions plus one: the box tables fit the budget.  Everything else loops -- sdpcut_set_box and
+// the single-point round once per point inside the call.
+static inline int batch_route_boxed(int64_t N, int64_t cap, int strat, bool exact_head, bool shard, int64_t nb_vars, int64_t n_points)
+{
+    if (batch_route(N, cap, strat, exact_head, shard) != BATCH_FAST) return BATCH_LOOP;
+    return batch_box_table_bytes(nb_vars, n_points) <= BATCH_BOX_BUDGET_BYTES ? BATCH_FAST : BATCH_LOOP;
+}
+
 // The batch block: n_points slices of `slice` bytes, slice p at offset p * slice.  A slice is one CSR round block (csr_layout:
 // 128 bytes of header, then the arrays) padded to a multiple of 64 bytes, so that every point's header starts a cache line of
 // its own.

@@ -4,7 +4,9 @@
 // run on those tables as they are (gather.h recomputes max_elem and Q_slice from whatever table it is handed).
 //   box_q_kernel       Q'_ij = Q_ij (d_i d_j)
 //   box_point_kernel   X'_ij = (((X_ij - l_i x_j) - l_j x_i) + l_i l_j) / (d_i d_j),  x'_i = (x_i - l_i) / d_i
-// fp64 in exactly this order, no contraction: on the unit box every entry is the original's bits.
+//   box_points_kernel  both tables at the P points of a boxed batch (points.hip), every point inside a box of its own
+// fp64 in exactly this order, no contraction: on the unit box every entry is the original's bits.  Each formula is written once
+// (box_q_entry, box_X_entry, box_x_entry) and every kernel calls it.
 #include <cmath>
 
 #include "common.h"
@@ -23,30 +25,79 @@ __device__ __forceinline__ void box_unpack(int64_t p, int32_t n, int32_t &i, int
     j = (int32_t)(r + (p - (r * n - r * (r - 1) / 2)));
 }
 
-__global__ __launch_bounds__(256) void box_q_kernel(const double *Q, const double *ld, int32_t n, int64_t L, double *Qb)
+// the three formulas (their callers inline them: the pragma travels with the operations)
+__device__ __forceinline__ double box_q_entry(double q, double di, double dj)
 {
 #pragma clang fp contract(off)
+    return q * (di * dj);
+}
+
+__device__ __forceinline__ double box_X_entry(double X, double xi, double xj, double li, double lj, double di, double dj)
+{
+#pragma clang fp contract(off)
+    return (((X - li * xj) - lj * xi) + li * lj) / (di * dj);
+}
+
+__device__ __forceinline__ double box_x_entry(double x, double l, double d)
+{
+#pragma clang fp contract(off)
+    return (x - l) / d;
+}
+
+__global__ __launch_bounds__(256) void box_q_kernel(const double *Q, const double *ld, int32_t n, int64_t L, double *Qb)
+{
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= L) return;
     int32_t i, j;
     box_unpack(p, n, i, j);
-    Qb[p] = Q[p] * (ld[n + i] * ld[n + j]);
+    Qb[p] = box_q_entry(Q[p], ld[n + i], ld[n + j]);
 }
 
 __global__ __launch_bounds__(256) void box_point_kernel(const double *vars, const double *ld, int32_t n, int64_t L, double *vb)
 {
-#pragma clang fp contract(off)
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= L + n) return;
     if (p >= L) {
         const int64_t i = p - L;
-        vb[p] = (vars[p] - ld[i]) / ld[n + i];
+        vb[p] = box_x_entry(vars[p], ld[i], ld[n + i]);
         return;
     }
     int32_t i, j;
     box_unpack(p, n, i, j);
-    const double li = ld[i], lj = ld[j];
-    vb[p] = (((vars[p] - li * vars[L + j]) - lj * vars[L + i]) + li * lj) / (ld[n + i] * ld[n + j]);
+    vb[p] = box_X_entry(vars[p], vars[L + i], vars[L + j], ld[i], ld[j], ld[n + i], ld[n + j]);
+}
+
+// The tables of a boxed batch: workgroup row y = point y.  Q'_y [L] (row y of Qb) and vars'_y [L + n] (row y of vb) from the shared
+// Q, point y of the device point table (rows of pts_stride doubles) and row y of the [P][2 n] (l | d) table.  One box_unpack per
+// thread serves both tables; the entries are the ones box_q_kernel / box_point_kernel write for that box and that point.
+__global__ __launch_bounds__(256) void box_points_kernel(const double *Q, const double *pts, int64_t pts_stride, const double *ld, int32_t n,
+                                                         int64_t L, double *Qb, double *vb)
+{
+    const int64_t y = (int64_t)blockIdx.y;
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= L + n) return;
+    const double *vars = pts + y * pts_stride;
+    ld += y * 2 * (int64_t)n;
+    vb += y * (L + n);
+    if (p >= L) {
+        const int64_t i = p - L;
+        vb[p] = box_x_entry(vars[p], ld[i], ld[n + i]);
+        return;
+    }
+    int32_t i, j;
+    box_unpack(p, n, i, j);
+    const double di = ld[n + i], dj = ld[n + j];
+    Qb[y * L + p] = box_q_entry(Q[p], di, dj);
+    vb[p] = box_X_entry(vars[p], vars[L + i], vars[L + j], ld[i], ld[j], di, dj);
+}
+
+int launch_box_points(sdpcut_ctx *h, int n_points, const double *d_pts, int64_t pts_stride, const double *d_ld, double *d_Qb, double *d_vb)
+{
+    const int64_t m = h->L + h->nb_vars;
+    hipLaunchKernelGGL(box_points_kernel, dim3((unsigned)((m + 255) / 256), (unsigned)n_points), dim3(256), 0, h->stream, (const double *)h->d_Q,
+                       d_pts, pts_stride, d_ld, h->nb_vars, h->L, d_Qb, d_vb);
+    HIP_TRY(h, hipGetLastError());
+    return 0;
 }
 
 int box_after_point(sdpcut_ctx *h)
@@ -56,6 +107,17 @@ int box_after_point(sdpcut_ctx *h)
     hipLaunchKernelGGL(box_point_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, h->stream, (const double *)h->d_vars,
                        (const double *)h->d_box_ld, h->nb_vars, h->L, h->d_vars_box);
     HIP_TRY(h, hipGetLastError());
+    return 0;
+}
+
+// the rule of a box (include/sdpcut.h: sdpcut_set_box); point >= 0: the box of that point of a batch
+int box_check(sdpcut_ctx *h, const char *what, int point, const double *lb, const double *ub)
+{
+    for (int32_t i = 0; i < h->nb_vars; ++i)      // (written so that a NaN fails)
+        if (!(lb[i] >= 0.0 && ub[i] <= 1.0 && ub[i] - lb[i] >= SDPCUT_BOX_MIN_WIDTH))
+            return sdpcut_fail(h, SDPCUT_EINVAL, std::string(what) + ": " + (point >= 0 ? "point " + std::to_string(point) + ", " : std::string()) +
+                                                 "variable " + std::to_string(i) + ": a box needs 0 <= lb, ub <= 1 and ub - lb >= "
+                                                 "SDPCUT_BOX_MIN_WIDTH (2^-10)");
     return 0;
 }
 
@@ -78,10 +140,8 @@ int sdpcut_set_box(sdpcut_handle h, const double *lb, const double *ub)
     const int32_t n = h->nb_vars;
     if (lb) {
         if (h->exact_head) return sdpcut_fail(h, SDPCUT_ESTATE, "set_box: SDPCUT_OPT_EXACT_HEAD is on (reference-exact heads have no node box)");
-        for (int32_t i = 0; i < n; ++i)      // (written so that a NaN fails)
-            if (!(lb[i] >= 0.0 && ub[i] <= 1.0 && ub[i] - lb[i] >= SDPCUT_BOX_MIN_WIDTH))
-                return sdpcut_fail(h, SDPCUT_EINVAL, "set_box: variable " + std::to_string(i) + ": a box needs 0 <= lb, ub <= 1 and ub - lb >= "
-                                                     "SDPCUT_BOX_MIN_WIDTH (2^-10)");
+        const int rc = box_check(h, "set_box", -1, lb, ub);
+        if (rc) return rc;
     } else if (!h->box_set) {
         return SDPCUT_OK;      // nothing to clear: the scores stand
     }

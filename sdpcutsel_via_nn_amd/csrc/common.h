@@ -106,6 +106,11 @@ struct PointsBufs {
     int agg_points = 0;
     void *pinned = nullptr, *pinned_dev = nullptr;  // the batch block (batch_route.h: batch_layout)
     size_t pinned_bytes = 0;
+    // a boxed batch (sdpcut_*_points_boxed): its (l | d) rows travel behind the points in the staging block
+    double *d_box_ld = nullptr;                     // [P][2 n]
+    size_t box_ld_doubles = 0;
+    double *d_Q_box = nullptr, *d_vars_box = nullptr;   // [P][L] Q' and [P][L + n] transformed points (box.hip: box_points_kernel)
+    size_t box_q_doubles = 0, box_vars_doubles = 0;
 };
 
 struct sdpcut_ctx {
@@ -352,7 +357,7 @@ int launch_eig_only(sdpcut_ctx *h, void *tk, hipEvent_t ev_start, hipEvent_t ev_
 int launch_eig_only_points(sdpcut_ctx *h, int n_points, const double *d_pts, int64_t pts_stride, double *d_eig, int64_t eig_stride);
 bool score_points_served(const sdpcut_ctx *h, uint32_t flags);
 int launch_score_points(sdpcut_ctx *h, uint32_t flags, int n_points, const double *d_pts, int64_t pts_stride, double *d_eig, double *d_obj,
-                        int64_t score_stride, int64_t *d_strong, int64_t strong_stride);
+                        int64_t score_stride, int64_t *d_strong, int64_t strong_stride, const double *d_Q = nullptr, int64_t Q_stride = 0);
 int launch_round_csr_points(sdpcut_ctx *h, int p_first, int n_points, int64_t cap, int ld, const int64_t *d_c4, int64_t c4_stride,
                             const int64_t *d_idx, const double *d_score, const double *d_pts, int64_t pts_stride, const double *d_eig,
                             int64_t eig_stride, uint64_t *d_agg, int64_t agg_stride, void *block, int64_t block_stride, int64_t serial);
@@ -418,6 +423,11 @@ static inline const double *score_Q(const sdpcut_ctx *h, uint32_t flags)
 }
 int box_after_point(sdpcut_ctx *h);   // the transformed point from d_vars, behind its copy on the handle's stream; nothing without a box
 void box_clear(sdpcut_ctx *h);        // drop the box and its tables (the caller has waited for the stream)
+// sdpcut_set_box's rule on one box, the failure recorded in the name of `what` (point >= 0: "point <point>, variable <i>")
+int box_check(sdpcut_ctx *h, const char *what, int point, const double *lb, const double *ub);
+// box_points_kernel: Q' (rows of L) and the transformed points (rows of L + n) of n_points points, each in the box of its row of
+// the [n_points][2 n] (l | d) table d_ld
+int launch_box_points(sdpcut_ctx *h, int n_points, const double *d_pts, int64_t pts_stride, const double *d_ld, double *d_Qb, double *d_vb);
 #define SDPCUT_NO_BOX(h, what)                                                                                            \
     do {                                                                                                                  \
         if ((h)->box_set)                                                                                                 \

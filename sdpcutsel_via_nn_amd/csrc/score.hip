@@ -259,21 +259,23 @@ bool score_points_served(const sdpcut_ctx *h, uint32_t flags)
 // The scores of the handle's list at n_points LP points, rows of d_pts (stride pts_stride), into rows of d_eig / d_obj (stride
 // score_stride): ONE launch with a point axis for an eigenvalue-only scan, else one per size class (every class with the plan -- and
 // so the scores -- of its single-point launch).  d_strong (optional, needs both flags): point p's launches add its strong
-// candidates to the eight replicas at d_strong + p * strong_stride.
+// candidates to the eight replicas at d_strong + p * strong_stride.  d_Q (optional; a boxed batch, points.hip): the MFMA launches
+// read point p's instance table at d_Q + p * Q_stride instead of the handle's one Q.
 int launch_score_points(sdpcut_ctx *h, uint32_t flags, int n_points, const double *d_pts, int64_t pts_stride, double *d_eig, double *d_obj,
-                        int64_t score_stride, int64_t *d_strong, int64_t strong_stride)
+                        int64_t score_stride, int64_t *d_strong, int64_t strong_stride, const double *d_Q, int64_t Q_stride)
 {
     const ScoreFormIn in = form_in(h, flags, nullptr);
     const ScoreForm f = score_form(in);
     if (f.err) return sdpcut_fail(h, f.err, score_form_msg(f.msg));
     if (!score_points_served(h, flags)) return sdpcut_fail(h, SDPCUT_ESTATE, "score: this kernel variant has no point axis");
     if (f.form == SCORE_FORM_EIG) return launch_eig_only_points(h, n_points, d_pts, pts_stride, d_eig, score_stride);
-    const ScorePointStrides ps = {pts_stride, score_stride, strong_stride};
+    const ScorePointStrides ps = {pts_stride, score_stride, strong_stride, d_Q ? Q_stride : 0};
     for (int k = 2; k <= SDPCUT_MAX_K; ++k) {
         if (h->bucket[k].n == 0) continue;
         const ScorePlan p = plan_class(h, k, nullptr);
         ScoreArgs A = fill_score_args(h, k, flags, nullptr, d_strong, p);
         A.vars = d_pts; A.eig_out = d_eig; A.obj_out = d_obj;
+        if (d_Q) A.Q = d_Q;
         score_mfma_points_launch(k, A, ps, p.grid, n_points, h->stream);
     }
     HIP_TRY(h, hipGetLastError());

@@ -75,9 +75,10 @@ static inline ScoreArgs fill_score_args(const sdpcut_ctx *h, int K, uint32_t fla
 }
 
 // A batch of LP points (points.hip): what workgroup row y of score_mfma_points_kernel adds to the pointers of its ScoreArgs, in
-// elements: vars += y * vars, eig_out / obj_out += y * scores, strong_out (if set) += y * strong.
+// elements: vars += y * vars, eig_out / obj_out += y * scores, strong_out (if set) += y * strong, Q += y * Q (0: one Q for all
+// points; L: every point has a Q' of its own, a boxed batch).
 struct ScorePointStrides {
-    int64_t vars, scores, strong;
+    int64_t vars, scores, strong, Q;
 };
 
 // With SDPCUT_OPT_TIMING the kernel's own dispatch carries the two events (hipExtLaunchKernelGGL):

@@ -1179,7 +1179,8 @@ __global__ __launch_bounds__(256) void filter_audit_kernel(ScoreArgs A, double *
 }
 
 // The same kernel at the P = gridDim.y LP points of a batch (sdpcut_score_points / sdpcut_round_csr_points, points.hip): workgroup
-// row y reads point y and writes row y of the batch's score arrays (and adds to point y's strong counter).  The offsets are applied
+// row y reads point y (and, in a boxed batch, the Q' of point y: ps.Q = L, else 0) and writes row y of the batch's score arrays (and
+// adds to point y's strong counter).  The offsets are applied
 // to the kernel ARGUMENT -- blockIdx.y and the strides are scalars, the sums stay in scalar registers -- and the unchanged body runs
 // on the copy: the same code per candidate, the same scores.  No histogram variants (FUSE = 0): the batched selection builds its
 // own keys.
@@ -1189,6 +1190,7 @@ __global__ __launch_bounds__(256, (JK == 1 ? SDPCUT_MFMA_J1_WAVES : 2)) void sco
     __shared__ MfmaLds<K, H, NH> S;
     const int64_t p = (int64_t)blockIdx.y;
     A.vars += p * ps.vars;
+    A.Q += p * ps.Q;
     A.eig_out += p * ps.scores;
     A.obj_out += p * ps.scores;
     if (A.strong_out) A.strong_out += p * ps.strong;

@@ -524,10 +524,11 @@ class GpuCutSelectionMixin(object):
         :meth:`_gpu_add_csr` takes -- the caller adds each node's cuts to that node's LP -- and the rest is what the single-point
         selection reports (length of the ranking, the combined strategy's switch, its counters).  The arrays are views of the
         scorer's batch block, good until its next call; the scorer holds no current LP point afterwards.
-        ``boxes`` [P, 2, n]: the variable bounds (lb, ub) of each point's node.  The points are then served one by one inside the
-        call -- ``set_box``, the single-point round -- because the point-axis kernels have one Q for all points (a one-launch route
-        for boxed batches is a later step); the arrays are copies, and the solver's own node box
-        (:meth:`set_node_box`) is in place again afterwards."""
+        ``boxes`` [P, 2, n]: the variable bounds (lb, ub) of each point's node; entry p is then what ``set_box(*boxes[p])`` and
+        the single-point round at ``points[p]`` give.  Still one device call (sdpcut_round_csr_points_boxed: every point's tables
+        in its own box by one launch, one host wait for the batch -- DESIGN.md section 5 "Batched points"); the arrays are copies,
+        and the solver's own node box (:meth:`set_node_box`), which the call cannot coexist with, is taken off the scorer before
+        it and is in place again afterwards."""
         b = self._gpu_bind()
         b.drain()
         if boxes is not None:
@@ -535,16 +536,13 @@ class GpuCutSelectionMixin(object):
             bx = np.asarray(boxes, dtype=np.float64)
             if pts.ndim != 2 or bx.shape != (pts.shape[0], 2, self._nb_vars):
                 raise ValueError("boxes must be [P, 2, n]: (lb, ub) per point")
-            out = []
             try:
-                for p in range(pts.shape[0]):
-                    b.scorer.set_box(bx[p, 0], bx[p, 1])
-                    r = b.scorer.round_csr(strat, sel_size, point=pts[p], copy=True)
-                    out.append(((r["indptr"], r["indices"], r["values"], r["rhs"]), r["n_total"], r["new_strat"], r["counters"]))
+                b.scorer.clear_box()
+                rounds = b.scorer.round_csr_points(pts, strat, sel_size, copy=True, boxes=bx)
             finally:
                 b.point_copy, b.scored, b.point_token = None, 0, None
                 self._gpu_apply_box(b, self._gpu_node_box)
-            return out
+            return [((r["indptr"], r["indices"], r["values"], r["rhs"]), r["n_total"], r["new_strat"], r["counters"]) for r in rounds]
         rounds = b.scorer.round_csr_points(points, strat, sel_size)
         b.point_copy, b.scored, b.point_token = None, 0, None      # (the next single-point selection uploads its point)
         return [((r["indptr"], r["indices"], r["values"], r["rhs"]), r["n_total"], r["new_strat"], r["counters"]) for r in rounds]

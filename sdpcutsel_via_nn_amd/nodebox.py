@@ -35,6 +35,22 @@ def check_box(nb_vars, lb, ub):
     return lb, ub
 
 
+def check_boxes(nb_vars, boxes, n_points=None):
+    """check_box's rule on every box of a batch: boxes [P, 2, n] = (lb, ub) per point (``n_points``: the P it must have) ->
+    contiguous float64 [P, 2, n].  The ValueError names the point."""
+    bx = np.ascontiguousarray(boxes, dtype=np.float64)
+    n = int(nb_vars)
+    if bx.ndim != 3 or bx.shape[1:] != (2, n) or bx.shape[0] < 1 or (n_points is not None and bx.shape[0] != int(n_points)):
+        raise ValueError("boxes must be [P, 2, nb_vars]: (lb, ub) per point%s, not %s"
+                         % ("" if n_points is None else " of the %d points" % int(n_points), bx.shape))
+    for p in range(bx.shape[0]):
+        try:
+            check_box(n, bx[p, 0], bx[p, 1])
+        except ValueError as e:
+            raise ValueError("point %d: %s" % (p, e)) from None
+    return bx
+
+
 def _pairs(nb_vars):
     """(i, j) of the packed positions: row-major upper triangle"""
     return np.triu_indices(int(nb_vars))
@@ -57,6 +73,24 @@ def transform_tables(Q_arr, vars_values, lb, ub):
     Xb = (((X - lb[i] * x[j]) - lb[j] * x[i]) + lb[i] * lb[j]) / dd
     xb = (x - lb) / d
     return Qb, np.concatenate([Xb, xb])
+
+
+def transform_tables_points(Q_arr, points, boxes):
+    """The tables of a boxed batch (numpy twin of box_points_kernel, csrc/box.hip): points [P, L + n], boxes [P, 2, n] ->
+    (Q' [P, L], vars' [P, L + n]), row p = transform_tables(Q_arr, points[p], *boxes[p]) bit for bit (the same expressions in
+    the same order, with a point axis)."""
+    bx, pts, Q = np.asarray(boxes), np.asarray(points), np.asarray(Q_arr)
+    lb, ub = bx[:, 0, :], bx[:, 1, :]
+    n = lb.shape[1]
+    L = n * (n + 1) // 2
+    i, j = _pairs(n)
+    d = ub - lb
+    dd = d[:, i] * d[:, j]
+    Qb = Q[None, :] * dd
+    X, x = pts[:, :L], pts[:, L:]
+    Xb = (((X - lb[:, i] * x[:, j]) - lb[:, j] * x[:, i]) + lb[:, i] * lb[:, j]) / dd
+    xb = (x - lb) / d
+    return Qb, np.concatenate([Xb, xb], axis=1)
 
 
 def inverse_tables(Q_box, vars_box, lb, ub):

@@ -10,9 +10,16 @@ Method: both forms are warmed up at every shape (first launches load code object
 batched form and the loop form one after the other (alternating, so that drift of the box hits both), `--calls` calls per timing.
 Reported: the median over the blocks and their min .. max (the run-to-run spread on this box during this run).
 
-usage: tools/batch_points.py [--repeats R] [--calls C] [--loop-only] [--out [FILE]]
+--boxes: every point lies in a node box of its own (a tree search's open nodes).  batched = round_csr_points(P points, boxes=),
+loop = P x (set_box, round_csr(point=p)) on the same handle -- what separate_points(..., boxes=) did before the boxed entry points
+existed.  Lists: the dim-3 covers of spar020-100-1 and spar040-030-1; P in {8, 64, 256}; strategies 2 and 4 (strategy 1 reads no
+box).  Boxes: per variable a seeded interval of width 0.05 .. 1 inside [0, 1]; points: McCormick-feasible points of the unit box
+carried into the box (nodebox.inverse_tables).
+
+usage: tools/batch_points.py [--boxes] [--repeats R] [--calls C] [--loop-only] [--out [FILE]]
+  --boxes       the boxed batch against the loop of set_box + single-point rounds
   --loop-only   time the single-point loop only (runs on a library without the batched entry points: the parent commit's)
-  --out         also write the table to FILE (default profiles/batch_points.txt)"""
+  --out         also write the table to FILE (default profiles/batch_points.txt; with --boxes profiles/boxed_points.txt)"""
 import argparse
 import gc
 import os
@@ -24,11 +31,21 @@ import numpy as np
 ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 sys.path.insert(0, ROOT)
 import sdpcutsel_via_nn_amd as pkg  # noqa: E402
-from sdpcutsel_via_nn_amd import _capi, harness, networks  # noqa: E402
+from sdpcutsel_via_nn_amd import _capi, harness, networks, nodebox  # noqa: E402
 
 INST = os.path.join(ROOT, "tests", "golden", "instances")
 LISTS = (("spar020-100-1 dim 3", "spar020-100-1.in", 3), ("spar040-030-1 dim 5", "spar040-030-1.in", 5))
 POINTS = (1, 8, 64, 256)
+BOXED_LISTS = (("spar020-100-1 dim 3", "spar020-100-1.in", 3), ("spar040-030-1 dim 3", "spar040-030-1.in", 3))
+BOXED_POINTS = (8, 64, 256)
+
+
+def seeded_box(n, seed):
+    """-> [2, n]: per variable an interval of width 0.05 .. 1 inside the unit interval"""
+    rng = np.random.default_rng(7000 + seed)
+    w = rng.uniform(0.05, 1.0, n)
+    lb = rng.uniform(0.0, 1.0, n) * (1.0 - w)
+    return np.stack([lb, np.minimum(lb + w, 1.0)])
 
 
 def timed(fn, calls):
@@ -43,14 +60,18 @@ def main():
     ap.add_argument("--repeats", type=int, default=9)
     ap.add_argument("--calls", type=int, default=0, help="calls per timing (default: about 4096 points' worth, at least 8)")
     ap.add_argument("--loop-only", action="store_true")
-    ap.add_argument("--out", nargs="?", const=os.path.join(ROOT, "profiles", "batch_points.txt"), default=None)
+    ap.add_argument("--boxes", action="store_true")
+    ap.add_argument("--out", nargs="?", const="", default=None)
     args = ap.parse_args()
-    lines = ["# tools/batch_points.py --repeats %d%s: ms per call, us per point; median over the blocks (min .. max)"
-             % (args.repeats, " --loop-only" if args.loop_only else ""),
-             "# batched = round_csr_points(P points); loop = P x round_csr(point=p); sel_size = 10 % of the list"]
+    if args.out == "":
+        args.out = os.path.join(ROOT, "profiles", "boxed_points.txt" if args.boxes else "batch_points.txt")
+    lines = ["# tools/batch_points.py%s --repeats %d%s: ms per call, us per point; median over the blocks (min .. max)"
+             % (" --boxes" if args.boxes else "", args.repeats, " --loop-only" if args.loop_only else ""),
+             "# batched = round_csr_points(P points, boxes=); loop = P x (set_box, round_csr(point=p)); sel_size = 10 % of the list"
+             if args.boxes else "# batched = round_csr_points(P points); loop = P x round_csr(point=p); sel_size = 10 % of the list"]
     gc.collect()
     gc.freeze()
-    for title, fname, dim in LISTS:
+    for title, fname, dim in (BOXED_LISTS if args.boxes else LISTS):
         inst = harness.parse_boxqp(os.path.join(INST, fname))
         S, ks, N = _capi.enumerate_cover(inst["adj"], dim)
         n = inst["nb_vars"]
@@ -61,22 +82,33 @@ def main():
         sc.set_candidates(S, ks)
         sel = max(1, int(0.1 * N))
         pts_all = np.stack([harness.random_mccormick_point(n, np.random.default_rng(100 + i)) for i in range(max(POINTS))])
+        boxes_all = None
+        if args.boxes:
+            boxes_all = np.stack([seeded_box(n, i) for i in range(max(POINTS))])
+            pts_all = np.stack([nodebox.inverse_tables(None, pts_all[i], boxes_all[i, 0], boxes_all[i, 1])[1] for i in range(max(POINTS))])
         sizes = ", ".join("%d of %d" % (int((ks == k).sum()), k) for k in (2, 3, 4, 5) if (ks == k).any())
         lines.append("")
         lines.append("%s: %d candidates (%s), head %d" % (title, N, sizes, sel))
         lines.append("  strat    P | batched ms/call          us/point | loop ms/call             us/point | loop / batched")
-        for strat in (1, 4):
-            for P in POINTS:
+        for strat in ((2, 4) if args.boxes else (1, 4)):
+            for P in (BOXED_POINTS if args.boxes else POINTS):
                 pts = np.ascontiguousarray(pts_all[:P])
                 rows = [pts[p] for p in range(P)]
+                bx = np.ascontiguousarray(boxes_all[:P]) if args.boxes else None
                 calls = args.calls or max(8, 4096 // P)
 
                 def loop():
-                    for v in rows:
-                        sc.round_csr(strat, sel, point=v)
+                    if bx is None:
+                        for v in rows:
+                            sc.round_csr(strat, sel, point=v)
+                    else:
+                        for p, v in enumerate(rows):
+                            sc.set_box(bx[p, 0], bx[p, 1])
+                            sc.round_csr(strat, sel, point=v)
+                        sc.clear_box()
 
                 def batched():
-                    sc.round_csr_points(pts, strat, sel)
+                    sc.round_csr_points(pts, strat, sel, boxes=bx)
 
                 forms = [loop] if args.loop_only else [batched, loop]
                 for f in forms:                      # warm-up at this shape
