@@ -139,7 +139,7 @@ def row_matrix(coef, rhs, k):
     return B
 
 
-def check_rows(set_inds, ks, point, nb_vars, cuts_per_set, row_entry, row_rank, row_lam, coef, rhs, row_quota=None, tol=1e-12):
+def check_rows(set_inds, ks, point, nb_vars, cuts_per_set, row_entry, row_rank, row_lam, coef, rhs, row_quota=None, tol=1e-12, spectrum=None):
     """Invariants of an answer (rows in (entry, eigenvalue) order over the P entries given; coef [R, >= row length]) that hold even
     where eigenvalues tie.  With B the matrix of a row (:func:`row_matrix`) and M the entry's lifted matrix:
       * row_entry ascends, row_rank counts 0, 1, .. inside an entry and stays below cuts_per_set;
@@ -150,6 +150,8 @@ def check_rows(set_inds, ks, point, nb_vars, cuts_per_set, row_entry, row_rank, 
       * completeness: every eigenvalue of M below -tol that is among the first cuts_per_set of its entry has its row, unless the
         quota cut it -- then the rows are exactly the first row_quota of the walk and the first entry without all its rows is the
         last one that has any.
+    The eigenvalues of M are numpy.linalg.eigvalsh's unless ``spectrum`` gives them: one ascending sequence per entry (floats or
+    Fractions), for callers that know the exact ones.
     Raises AssertionError naming the first violation; returns True."""
     m = _check_m(cuts_per_set)
     S = np.asarray(set_inds)
@@ -178,7 +180,8 @@ def check_rows(set_inds, ks, point, nb_vars, cuts_per_set, row_entry, row_rank, 
     for i in range(P):
         k = int(ks[i])
         M, _ = lifted(S[i, :k], point, nb_vars)
-        w = np.linalg.eigvalsh(M)
+        w = np.linalg.eigvalsh(M) if spectrum is None else np.array([float(t) for t in spectrum[i]], dtype=np.float64)
+        assert w.shape == (k + 1,) and np.all(np.diff(w) >= 0), "entry %d: the spectrum must hold k + 1 ascending eigenvalues" % i
         rows = list(range(first, first + int(have[i])))
         first += int(have[i])
         Bs = []

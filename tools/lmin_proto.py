@@ -205,6 +205,8 @@ def lambda_min(A, stats=None):
         stats["evals"] = nev
         stats["notdone"] = int((~done).sum())
         stats["split"] = int(has_split.sum())
+        # per lane: deflated by the relative rule, iterated block by block (either rule), converged
+        stats["relative_split"], stats["blocks"], stats["done"] = has_split.copy(), cold.copy(), done.copy()
     return lam, done
 
 
