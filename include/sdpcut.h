@@ -45,12 +45,23 @@ enum {
     SDPCUT_ENOMEM = -5
 };
 
-/* score flags (SDPCUT_SDP: the exact optimum of the small SDP the MLP of SDPCUT_NN estimates, see sdpcut_score) */
-enum { SDPCUT_EIG = 1, SDPCUT_NN = 2, SDPCUT_SDP = 4 };
+/* score flags (SDPCUT_SDP: the exact optimum of the small SDP the MLP of SDPCUT_NN estimates; SDPCUT_EFF: the efficacy of the cut
+ * row a round would emit; see sdpcut_score) */
+enum { SDPCUT_EIG = 1, SDPCUT_NN = 2, SDPCUT_SDP = 4, SDPCUT_EFF = 8 };
 
 /* selection strategies, numbering of cut_select_algo (cut_select_qp.py:79-80); SDPCUT_STRAT_EXACT is accepted only while
  * SDPCUT_OPT_EXACT_SDP is on */
 enum { SDPCUT_STRAT_FEAS = 1, SDPCUT_STRAT_OPT = 2, SDPCUT_STRAT_EXACT = 3, SDPCUT_STRAT_COMB = 4 };
+/* Strategy 6, efficacy: all N candidates by the score of SDPCUT_EFF descending (the first criterion of a MIP solver's cut selector,
+ * optionally plus w times the objective parallelism), ties by ascending candidate index -- strategy 2's semantics on another array:
+ * n_total = N, *new_strat = 6, nb_positive counts escore > 0 (= nb_violated).  Not a strategy of the reference (its numbering ends
+ * at 5).  Accepted by sdpcut_rank / sdpcut_rank_device (which need a preceding sdpcut_score(SDPCUT_EFF); sdpcut_rank_fetch after
+ * them), sdpcut_select_round, sdpcut_select_round_view, sdpcut_round_view, sdpcut_round_csr, sdpcut_round_csr_begin / _end,
+ * sdpcut_round_csr_diverse and sdpcut_round_csr_multi: the fused calls score the measure themselves if it is missing, then run
+ * the selection strategy 2 runs on scores that exist already; `score` of every head is escore, and the rows are computed from the
+ * lambda_min the score was computed from.  No networks needed.  SDPCUT_OPT_EXACT_HEAD ignores it.  Refused with SDPCUT_EINVAL: by
+ * the batched-points calls (sdpcut_score_points*, sdpcut_round_csr_points*) and the sharded entry points (sdpcut_shard_*). */
+enum { SDPCUT_STRAT_EFF = 6 };
 /* Partial ranking for candidate sets sharded over several GPUs (SURVEY.md section 8 e): only
  * the "strong" class of the combined scan (cut_select_qp.py:607-613: obj_improve > 0 and
  * violated), by obj_improve.  Its merged per-shard heads give the global position at which
@@ -163,7 +174,7 @@ enum { SDPCUT_OPT_KERNEL = 1, SDPCUT_OPT_TIMING = 2, SDPCUT_OPT_FUSE_KEYS = 3, S
  * SDPCUT_STAT_SELECT_FALLBACKS = rounds whose radix selection declared itself void (a grid barrier
  * timed out because other work kept its workgroups from starting) and were answered by the full-sort
  * path instead -- same result, ~1 ms instead of ~0.1 ms.
- * SDPCUT_STAT_SCORED = the measures (SDPCUT_EIG | SDPCUT_NN) scored at the current point.
+ * SDPCUT_STAT_SCORED = the measures (SDPCUT_EIG | SDPCUT_NN | SDPCUT_SDP | SDPCUT_EFF) scored at the current point.
  * SDPCUT_STAT_TIE_SPLITS (r4) = every-entry-visited combined rankings whose threshold group of EQUAL new scores
  * did not fit the sort buffers (structured LP vertices) and was cut by its secondary key -- obj_improve, then index,
  * cut_select_qp.py:601 under :625 -- with two more radix selections; until round 3 these rounds were fallbacks.
@@ -390,6 +401,35 @@ int sdpcut_get_box_tables(sdpcut_handle h, double *Q_box, double *vars_box);
  */
 int sdpcut_score(sdpcut_handle h, uint32_t flags);
 int sdpcut_get_scores(sdpcut_handle h, double *eigmin, double *obj_improve); /* either may be NULL */
+
+/*
+ * SDPCUT_EFF: efficacy of the eigen-cut a round would emit for candidate i at the current point (csrc/efficacy.hip; efficacy.py is
+ * the numpy twin).  lam = eigmin[i], the lambda_min the handle holds -- scoring SDPCUT_EFF scores SDPCUT_EIG first if it is missing
+ * -- and coef[0 .. M), cols[0 .. M), M = k + k(k+1)/2, exactly what sdpcut_cut_rows returns for i (the same device function with the
+ * same lam: the row a round emits, not another vector of the eigenspace).  In fp64, sums in column order m = 0 .. M-1, no
+ * contraction, IEEE square root and division:
+ *     nrm       = sqrt(sum coef[m]^2)
+ *     violated  : lam < -1e-15 and nrm > 0
+ *     eff[i]    = -lam / nrm                 (violated)       the Euclidean distance by which the row cuts off the LP point
+ *               = min(-lam, +0.0)            (otherwise; such a candidate costs no eigenvector)      => eff > 0 <=> violated
+ *     objpar[i] = |sum coef[m] obj[cols[m]]| / (nrm ||obj||_2)   (violated, an objective vector set), else 0.0
+ *     escore[i] = eff[i] + w objpar[i]       (violated), else eff[i]
+ * Like lambda_min and the rows the measure is computed from the ORIGINAL point: a node box (sdpcut_set_box) does not change it, and
+ * sdpcut_set_box leaves its scored bit alone.  No networks needed.  Whatever clears SDPCUT_EIG clears SDPCUT_EFF.
+ *
+ * sdpcut_set_objective: the LP objective in the column layout of vars_values, n_cols = n(n+1)/2 + n entries; obj == NULL clears it.
+ *   ||obj||_2 is computed once here, on the host: squares summed in index order without contraction, IEEE square root.
+ *   SDPCUT_EINVAL (the handle unchanged): a length mismatch, a non-finite entry, an all-zero vector.  Needs sdpcut_set_instance, which
+ *   also clears the vector.
+ * sdpcut_set_efficacy_weight: w, finite and >= 0 (SDPCUT_EINVAL otherwise); the default 0 ranks by pure efficacy, SCIP's default
+ *   weights correspond to w = 0.1.
+ * Both clear SDPCUT_EFF only and are refused with SDPCUT_ESTATE while a round is pending.
+ * sdpcut_get_efficacy: eff, objpar, escore [N] each in caller order, any may be NULL; SDPCUT_ESTATE unless SDPCUT_EFF is scored at
+ *   the current point.
+ */
+int sdpcut_set_objective(sdpcut_handle h, int64_t n_cols, const double *obj);
+int sdpcut_set_efficacy_weight(sdpcut_handle h, double w);
+int sdpcut_get_efficacy(sdpcut_handle h, double *eff, double *objpar, double *escore);
 /* the exact measure and its duality gap (either may be NULL); SDPCUT_ESTATE unless SDPCUT_SDP has been scored at the current point */
 int sdpcut_get_sdp_scores(sdpcut_handle h, double *obj_exact, double *gap);
 
@@ -399,6 +439,7 @@ int sdpcut_get_sdp_scores(sdpcut_handle h, double *obj_exact, double *gap);
  *   strat 2: all candidates by obj_improve descending
  *   strat 3: all candidates by the exact measure of SDPCUT_SDP descending (only with SDPCUT_OPT_EXACT_SDP, see there)
  *   strat 4: combined scan with BIG_M, using sel_size; *new_strat = 1 or 4 (:630-631)
+ *   strat 6: all candidates by the efficacy score of SDPCUT_EFF descending (SDPCUT_STRAT_EFF, see there)
  * Ties keep ascending candidate index (Python's stable sort).  Writes the first
  * min(max_out, length) entries: idx_out = global candidate index, score_out = ranking score.
  * *n_total = full length of the reference's list (N, or nb_violated for strat 1).
@@ -550,13 +591,13 @@ int sdpcut_round_csr_end(sdpcut_handle h, sdpcut_round_csr_t *out);
  * single-point call that follows needs its own sdpcut_set_point (sdpcut_score, sdpcut_rank ... fail with SDPCUT_ESTATE until
  * then; sdpcut_round_csr with a point is fine).  The handle's single-point arrays are scratch of the per-point fallback.
  *
- * sdpcut_score_points: flags = any combination of SDPCUT_EIG | SDPCUT_NN (SDPCUT_SDP is refused in this version).  eig_out /
+ * sdpcut_score_points: flags = any combination of SDPCUT_EIG | SDPCUT_NN (SDPCUT_SDP and SDPCUT_EFF are refused in this version).  eig_out /
  * obj_out: host arrays [n_points][N], row p = what sdpcut_set_point(point p), sdpcut_score(flags), sdpcut_get_scores returns, bit
  * for bit; the array of a measure that is not asked for may be NULL (one that is asked for may not).  One point copy and one
  * score launch with a point axis per size class (an eigenvalue-only scan: one launch).
  *
  * sdpcut_round_csr_points: out[p] is what sdpcut_round_csr(h, points + p * point_ld, strat, sel_size, &o) returns -- every field
- * and every array, bit for bit.  Strategies 1, 2 and 4 are served; 0, 3, -1, 5 and the SDPCUT_PART_* codes are refused with
+ * and every array, bit for bit.  Strategies 1, 2 and 4 are served; 0, 3, -1, 5, 6 and the SDPCUT_PART_* codes are refused with
  * SDPCUT_EINVAL.  All pointers of out[0 .. n_points) point into ONE pinned block of the handle (point p's slice starts with its
  * own header and is 64-byte aligned); they stay valid until the next call on the handle.
  *   Lists of at most 4096 candidates with a head of 1 .. 512 entries (SDPCUT_OPT_EXACT_HEAD off, no shard base): one point copy,
@@ -613,7 +654,7 @@ int sdpcut_round_csr_points_boxed(sdpcut_handle h, int32_t n_points, const doubl
  * skipped_nonviolated = those that were not eligible, rejected_parallel = eligible ones refused as parallel
  * (examined = accepted + skipped_nonviolated + rejected_parallel).
  *
- * sdpcut_round_csr_diverse: one round as sdpcut_round_csr (vars_values NULL keeps the current point), strategies 1, 2 and 4.  The
+ * sdpcut_round_csr_diverse: one round as sdpcut_round_csr (vars_values NULL keeps the current point), strategies 1, 2, 4 and 6.  The
  * pool is the first min(pool_size, length) entries of what sdpcut_rank(h, strat, sel_size, max_out = pool_size, ...) returns --
  * sel_size stays the combined strategy's quota; n_total, new_strat and counters are those of that call; SDPCUT_OPT_EXACT_HEAD is
  * honoured as that call honours it.  *out is the block of sdpcut_round_csr for the ACCEPTED entries in rank order: cap =
@@ -624,7 +665,7 @@ int sdpcut_round_csr_points_boxed(sdpcut_handle h, int32_t n_points, const doubl
  * sdpcut_filter_parallel: the same walk over `count` candidates in an order the CALLER supplies (local ids; a QCQP caller's
  * concatenated list, a merged sharded head, a ranking of one's own) at the current point: keep_out[i] = 1 iff entry i is accepted.
  *
- * SDPCUT_EINVAL: a strategy outside {1, 2, 4}, max_parallel outside [0, 1] or NaN, sel_size / quota < 1, pool_size < sel_size, a
+ * SDPCUT_EINVAL: a strategy outside {1, 2, 4, 6}, max_parallel outside [0, 1] or NaN, sel_size / quota < 1, pool_size < sel_size, a
  * pool or count above SDPCUT_DIVERSE_MAX_POOL, an id outside the list.  SDPCUT_ESTATE: no instance, candidates or point; a round
  * pending.  Device memory: per pool entry 250 bytes, and -- only when max_parallel < 1 -- the lower-triangular bit matrix of the pair
  * test, 16.8 MB at a pool of 16384 (4 KB at 256); allocated by the first call, grown to the largest pool, freed with the handle.
@@ -655,7 +696,7 @@ int sdpcut_filter_parallel(sdpcut_handle h, int64_t count, const int64_t *idx, i
  * csrc/jacobi.h): they are an orthonormal set even inside a multiple eigenvalue, lam_min of an entry is that decomposition's
  * smallest eigenvalue, and row 0 of an entry may differ from sdpcut_round_csr's row in the last bits (another solver).
  *
- * sdpcut_round_csr_multi: strategies 1, 2, 4, and 3 under SDPCUT_OPT_EXACT_SDP; vars_values NULL keeps the current point;
+ * sdpcut_round_csr_multi: strategies 1, 2, 4, 6, and 3 under SDPCUT_OPT_EXACT_SDP; vars_values NULL keeps the current point;
  * synchronous.  out->csr is the block of sdpcut_round_csr with the row arrays (row_entry, indptr, indices, values, rhs) sized for
  * row_cap = min(row_quota, max_per_set * cap) rows, plus
  *   n_neg[n_out]      violated eigenvalues of the entry (before max_per_set and before the quota)

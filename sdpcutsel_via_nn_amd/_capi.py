@@ -18,6 +18,8 @@ EIG, NN = 1, 2
 SDP = 4                  # exact optimum of the small SDP the MLP estimates (sdpcut_score, include/sdpcut.h)
 STRAT_FEAS, STRAT_OPT, STRAT_COMB = 1, 2, 4
 STRAT_EXACT = 3          # strategy 2 on the exact measure; accepted only with OPT_EXACT_SDP
+EFF = 8                  # efficacy of the cut row a round would emit, its objective parallelism and their score (sdpcut_score, include/sdpcut.h)
+STRAT_EFF = 6            # strategy 2's ranking on the efficacy score
 PART_STRONG = 104
 PART_COMBALL = 105
 KERNEL_MFMA, KERNEL_SIMPLE, KERNEL_VALU = 0, 1, 2
@@ -122,6 +124,9 @@ SIGNATURES = {
     "sdpcut_score": [_vp, _c.c_uint32],
     "sdpcut_get_scores": [_vp, _dp, _dp],
     "sdpcut_get_sdp_scores": [_vp, _dp, _dp],
+    "sdpcut_set_objective": [_vp, _c.c_int64, _dp],
+    "sdpcut_set_efficacy_weight": [_vp, _c.c_double],
+    "sdpcut_get_efficacy": [_vp, _dp, _dp, _dp],
     "sdpcut_rank": [_vp, _c.c_int, _c.c_int64, _c.c_int64, _i64p, _dp, _i64p, _i32p, _i64p],
     "sdpcut_rank_device": [_vp, _c.c_int, _c.c_int64, _c.c_int64, _vp, _vp, _i64p, _i64p, _i32p, _i64p],
     "sdpcut_rank_fetch": [_vp, _c.c_int64, _c.c_int64, _i64p, _dp],
@@ -261,8 +266,8 @@ def check_diverse_args(max_parallel, quota, pool_size=None, strat=None):
     quota = int(quota)
     if quota < 1:
         raise ValueError("the quota (sel_size) must be >= 1")
-    if strat is not None and strat not in (STRAT_FEAS, STRAT_OPT, STRAT_COMB):
-        raise ValueError("diverse selection serves strategies 1 (feasibility), 2 (optimality) and 4 (combined)")
+    if strat is not None and strat not in (STRAT_FEAS, STRAT_OPT, STRAT_COMB, STRAT_EFF):
+        raise ValueError("diverse selection serves strategies 1 (feasibility), 2 (optimality), 4 (combined) and 6 (efficacy)")
     if pool_size is None:
         pool_size = min(4 * quota, DIVERSE_MAX_POOL)
         if quota > DIVERSE_MAX_POOL:
@@ -282,8 +287,8 @@ def check_multi_args(cuts_per_set, row_quota, sel_size=None, strat=None):
     m = int(cuts_per_set)
     if m != cuts_per_set or not 1 <= m <= MULTI_MAX_PER_SET:
         raise ValueError("cuts_per_set must be an integer in 1 .. %d" % MULTI_MAX_PER_SET)
-    if strat is not None and strat not in (STRAT_FEAS, STRAT_OPT, STRAT_EXACT, STRAT_COMB):
-        raise ValueError("multi-cut rounds serve strategies 1 (feasibility), 2 (optimality), 3 (exact, with OPT_EXACT_SDP) and 4 (combined)")
+    if strat is not None and strat not in (STRAT_FEAS, STRAT_OPT, STRAT_EXACT, STRAT_COMB, STRAT_EFF):
+        raise ValueError("multi-cut rounds serve strategies 1 (feasibility), 2 (optimality), 3 (exact, with OPT_EXACT_SDP), 4 (combined) and 6 (efficacy)")
     if row_quota is None or (isinstance(row_quota, str) and row_quota == "sets"):
         if sel_size is None:
             raise ValueError("row_quota needs a number where there is no sel_size")
@@ -660,6 +665,28 @@ class Scorer(object):
         o, g = np.empty(self.N), np.empty(self.N)
         self._check(self._lib.sdpcut_get_sdp_scores(self._h, _ptr(o, _dp), _ptr(g, _dp)))
         return o, g
+
+    def set_objective(self, obj):
+        """The LP objective vector in the column layout of an LP point, n(n+1)/2 + n entries (sdpcut_set_objective): what the
+        objective parallelism of the efficacy measure is taken against.  None clears it.  A wrong length, a non-finite entry or an
+        all-zero vector is a ValueError."""
+        if obj is None:
+            self._check(self._lib.sdpcut_set_objective(self._h, 0, None))
+            return
+        obj = _f64(obj)
+        if obj.ndim != 1:
+            raise ValueError("obj must be a vector in the layout of vars_values, n(n+1)/2 + n entries")
+        self._check(self._lib.sdpcut_set_objective(self._h, obj.shape[0], _ptr(obj, _dp)))
+
+    def set_efficacy_weight(self, w):
+        """w >= 0 of escore = eff + w objpar (sdpcut_set_efficacy_weight); 0, the default, ranks by pure efficacy"""
+        self._check(self._lib.sdpcut_set_efficacy_weight(self._h, float(w)))
+
+    def get_efficacy(self):
+        """-> (eff, objpar, escore), float64 [N] each, of the last score(EFF) at the current point (:mod:`efficacy` is the twin)"""
+        e, p, s = np.empty(self.N), np.empty(self.N), np.empty(self.N)
+        self._check(self._lib.sdpcut_get_efficacy(self._h, _ptr(e, _dp), _ptr(p, _dp), _ptr(s, _dp)))
+        return e, p, s
 
     def rank(self, strat, sel_size=0, max_out=None):
         """-> (idx int64[w], score float64[w], n_total, new_strat, counters dict)"""

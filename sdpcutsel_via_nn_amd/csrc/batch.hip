@@ -16,8 +16,9 @@ int sdpcut_score(sdpcut_handle h, uint32_t flags)
 {
     if (!h) return SDPCUT_EINVAL;
     SDPCUT_NO_PENDING(h);
-    if (!(flags & (SDPCUT_EIG | SDPCUT_NN | SDPCUT_SDP)) || (flags & ~(uint32_t)(SDPCUT_EIG | SDPCUT_NN | SDPCUT_SDP)))
-        return sdpcut_fail(h, SDPCUT_EINVAL, "flags must be a combination of SDPCUT_EIG, SDPCUT_NN and SDPCUT_SDP");
+    if (!(flags & (SDPCUT_EIG | SDPCUT_NN | SDPCUT_SDP | SDPCUT_EFF)) || (flags & ~(uint32_t)(SDPCUT_EIG | SDPCUT_NN | SDPCUT_SDP | SDPCUT_EFF)))
+        return sdpcut_fail(h, SDPCUT_EINVAL, "flags must be a combination of SDPCUT_EIG, SDPCUT_NN, SDPCUT_SDP and SDPCUT_EFF");
+    if ((flags & SDPCUT_EFF) && !(h->scored & SDPCUT_EIG)) flags |= SDPCUT_EIG;      // the efficacy is that of the row of the lambda_min the handle holds
     if (!h->have_point) return sdpcut_fail(h, SDPCUT_ESTATE, "set_point first");
     if (!h->d_eig) return sdpcut_fail(h, SDPCUT_ESTATE, "set_candidates first");
     HIP_TRY(h, hipSetDevice(h->device));
@@ -28,6 +29,10 @@ int sdpcut_score(sdpcut_handle h, uint32_t flags)
     }
     if (flags & SDPCUT_SDP) {      // its own kernels and arrays (exact_sdp.hip): no network needed, d_eig / d_obj untouched
         rc = launch_exact_sdp(h);
+        if (rc) return rc;
+    }
+    if (flags & SDPCUT_EFF) {      // after SDPCUT_EIG on the stream; its own kernel and arrays (efficacy.hip), no network needed
+        rc = launch_efficacy(h);
         if (rc) return rc;
     }
     h->scored |= flags;
@@ -68,11 +73,11 @@ int sdpcut_rank_device(sdpcut_handle h, int strat, int64_t sel_size, int64_t max
 {
     if (!h) return SDPCUT_EINVAL;
     SDPCUT_NO_PENDING(h);
-    if (strat_is_sdp(h, strat)) {      // strategy 2 on the exact measure
-        if (!(h->scored & SDPCUT_SDP)) return sdpcut_fail(h, SDPCUT_ESTATE, "sdpcut_score with the needed flags first");
-        SdpAsObj view(h);
+    if (const uint32_t measure = strat_view(h, strat)) {      // strategy 2 on the exact measure (3) / on the efficacy score (6)
+        if (!(h->scored & measure)) return sdpcut_fail(h, SDPCUT_ESTATE, "sdpcut_score with the needed flags first");
+        MeasureAsObj view(h, measure);
         const int rc3 = sdpcut_rank_device(h, SDPCUT_STRAT_OPT, sel_size, max_out, d_idx_out, d_score_out, n_written, n_total, new_strat, counters);
-        if (!rc3 && new_strat) *new_strat = SDPCUT_STRAT_EXACT;
+        if (!rc3 && new_strat) *new_strat = view_strat(measure);
         return rc3;
     }
     int rc = check_rank_args(h, strat);

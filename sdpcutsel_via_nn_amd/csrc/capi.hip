@@ -106,6 +106,7 @@ int sdpcut_destroy(sdpcut_handle h)
     free_multi_ws(h);
     free_pool_ws(h);
     box_clear(h);
+    free_lpobj(h);
     (void)hipFree(h->d_sdp_unconverged);
     (void)hipFree(h->d_tri); (void)hipFree(h->d_tri_dense3);
     if (h->pinned) (void)hipHostFree(h->pinned);

@@ -72,7 +72,7 @@ struct PendingRound {
     bool active = false, csr = false, fast_tried = false;
     bool skipped = false;          // its scoring launch ran the MLP for violated candidates only (SDPCUT_OPT_SKIP_NONVIOLATED)
     int strat = 0;
-    bool by_sdp = false;           // strategy 3: the round was begun inside an SdpAsObj view and is ended inside one
+    uint32_t view = 0;             // strategies 3 and 6: the measure (SDPCUT_SDP / SDPCUT_EFF) whose MeasureAsObj view the round was begun in and is ended in
     int32_t ld = 0;
     int64_t sel_size = 0, cap = 0, serial = 0;
     int64_t exact_band = 0;        // > 0: the enqueued head is an exact one (SDPCUT_OPT_EXACT_HEAD) through a band of this many entries
@@ -175,6 +175,12 @@ struct sdpcut_ctx {
     // SDPCUT_SDP (exact_sdp.hip): exact optimality measure and its duality gap, [N] caller order, allocated by the first scoring
     double *d_sdp = nullptr, *d_sdp_gap = nullptr;
     unsigned long long *d_sdp_unconverged = nullptr;   // candidates of the last exact solve that stopped at the iteration cap
+    // SDPCUT_EFF (efficacy.hip): efficacy of the emitted row, its objective parallelism and the ranking score eff + w objpar, [N]
+    // caller order, one allocation made by the first scoring and freed with the candidates
+    double *d_eff = nullptr, *d_objpar = nullptr, *d_escore = nullptr;
+    double *d_lpobj = nullptr;     // [L + n] LP objective vector (sdpcut_set_objective) or NULL; belongs to the instance
+    double lpobj_norm = 0.0;       // its 2-norm, computed once when it is set
+    double eff_w = 0.0;            // sdpcut_set_efficacy_weight
     bool exact_sdp = false;        // SDPCUT_OPT_EXACT_SDP: strategy 3 is accepted
     uint32_t scored = 0;
     // SDPCUT_OPT_SKIP_NONVIOLATED (score_mfma_skip_kernel): 0 never, 1 lists score_plan cuts into strips of 64, 2 every list
@@ -449,37 +455,48 @@ void free_pool_ws(sdpcut_ctx *h);
 int launch_exact_sdp(sdpcut_ctx *h);                 // d_sdp / d_sdp_gap of every candidate at the current point
 int sdp_unconverged(sdpcut_ctx *h, int64_t *value);  // SDPCUT_STAT_SDP_UNCONVERGED (waits for the handle's stream)
 void free_sdp_ws(sdpcut_ctx *h);
-// Strategy 3 = strategy 2 on the exact measure (cut_select_qp.py:584-601: the same list, the same sort, another obj_improve).
-// The non-fused selection reads the handle's optimality array wherever it ranks (rank.hip, topk.hip); for the lifetime of this
-// object that array IS d_sdp and its `scored` bit is SDPCUT_SDP's, and SDPCUT_OPT_EXACT_HEAD -- which re-scores the MLP -- is
-// off.  Nothing scores inside a view: its scope begins after SDPCUT_SDP has been scored.  The exact measure is whole whatever a
-// skipped round left of the MLP's (obj_partial): inside the view that flag is down -- obj_complete has nothing to do there and
-// must not, its launch would write the MLP's scores into d_sdp -- and the real array's state comes back with the array.
-struct SdpAsObj {
+// Strategies 3 and 6 = strategy 2 on another measure (3: the exact measure of SDPCUT_SDP, cut_select_qp.py:584-601 -- the same list,
+// the same sort, another obj_improve; 6: the efficacy score of SDPCUT_EFF).  The non-fused selection reads the handle's optimality
+// array wherever it ranks (rank.hip, topk.hip); for the lifetime of this object that array IS the measure's (d_sdp / d_escore) and
+// its `scored` bit is the measure's, and SDPCUT_OPT_EXACT_HEAD -- which re-scores the MLP -- is off.  Nothing scores inside a view:
+// its scope begins after the measure has been scored.  The measure is whole whatever a skipped round left of the MLP's
+// (obj_partial): inside the view that flag is down -- obj_complete has nothing to do there and must not, its launch would write the
+// MLP's scores into the measure's array -- and the real array's state comes back with the array.
+struct MeasureAsObj {
     sdpcut_ctx *h;
     double *obj;
     uint32_t scored;
     bool exact_head, obj_partial;
-    explicit SdpAsObj(sdpcut_ctx *ctx)
+    MeasureAsObj(sdpcut_ctx *ctx, uint32_t measure)
         : h(ctx), obj(ctx->d_obj), scored(ctx->scored), exact_head(ctx->exact_head), obj_partial(ctx->obj_partial)
     {
-        h->d_obj = h->d_sdp;
-        h->scored = (scored & SDPCUT_EIG) | ((scored & SDPCUT_SDP) ? (uint32_t)SDPCUT_NN : 0u);
+        h->d_obj = measure == SDPCUT_EFF ? h->d_escore : h->d_sdp;
+        h->scored = (scored & SDPCUT_EIG) | ((scored & measure) ? (uint32_t)SDPCUT_NN : 0u);
         h->exact_head = false;
         h->obj_partial = false;
     }
-    ~SdpAsObj()
+    ~MeasureAsObj()
     {
         h->d_obj = obj;
         h->scored = scored;
         h->exact_head = exact_head;
         h->obj_partial = obj_partial;
     }
-    SdpAsObj(const SdpAsObj &) = delete;
-    SdpAsObj &operator=(const SdpAsObj &) = delete;
+    MeasureAsObj(const MeasureAsObj &) = delete;
+    MeasureAsObj &operator=(const MeasureAsObj &) = delete;
 };
-// strategy 3 where it is accepted: the option on (else the caller's own refusal of an unknown strategy stands)
-static inline bool strat_is_sdp(const sdpcut_ctx *h, int strat) { return strat == SDPCUT_STRAT_EXACT && h->exact_sdp; }
+// the measure a strategy ranks by through such a view, 0 for the strategies with a selection of their own: strategy 3 where it is
+// accepted (the option on, else the caller's own refusal of an unknown strategy stands) and strategy 6
+static inline uint32_t strat_view(const sdpcut_ctx *h, int strat)
+{
+    return (strat == SDPCUT_STRAT_EXACT && h->exact_sdp) ? (uint32_t)SDPCUT_SDP : strat == SDPCUT_STRAT_EFF ? (uint32_t)SDPCUT_EFF : 0u;
+}
+static inline int view_strat(uint32_t measure) { return measure == SDPCUT_EFF ? SDPCUT_STRAT_EFF : SDPCUT_STRAT_EXACT; }
+
+// efficacy.hip (SDPCUT_EFF)
+int launch_efficacy(sdpcut_ctx *h);                  // d_eff / d_objpar / d_escore of every candidate at the current point; needs d_eig
+void free_eff_ws(sdpcut_ctx *h);
+void free_lpobj(sdpcut_ctx *h);
 
 // tri.hip
 int tri_preprocess(sdpcut_ctx *h, const uint8_t *adjacency, int64_t *n_triples);

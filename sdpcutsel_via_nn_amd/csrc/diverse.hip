@@ -376,8 +376,9 @@ int sdpcut_round_csr_diverse(sdpcut_handle h, const double *vars_values, int str
     if (!out) return sdpcut_fail(h, SDPCUT_EINVAL, "out is NULL");
     std::memset(out, 0, sizeof(*out));
     if (info) std::memset(info, 0, sizeof(*info));
-    int rc = check_round_strategy(h, strat);
-    if (rc) return rc;
+    int rc;
+    const bool by_eff = strat == SDPCUT_STRAT_EFF;      // ranks through a view inside the ranking calls (common.h: MeasureAsObj)
+    if (!by_eff && (rc = check_round_strategy(h, strat))) return rc;
     rc = div_check_common(h, max_parallel);
     if (rc) return rc;
     if (sel_size < 1) return sdpcut_fail(h, SDPCUT_EINVAL, "sel_size must be >= 1");
@@ -389,7 +390,7 @@ int sdpcut_round_csr_diverse(sdpcut_handle h, const double *vars_values, int str
     if (vars_values && (rc = sdpcut_set_point(h, vars_values))) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     // 1. the pool: the head of the strategy's ranking, by the existing ranking call (SDPCUT_OPT_EXACT_HEAD included)
-    const uint32_t need = strat_need(strat);
+    const uint32_t need = by_eff ? (uint32_t)SDPCUT_EFF : strat_need(strat);
     if ((rc = obj_complete(h))) return rc;      // a measure a skipped round left partial: whole before this round counts by it
     if ((h->scored & need) != need && (rc = sdpcut_score(h, need & ~h->scored))) return rc;
     const int64_t want = pool_size < h->N ? pool_size : h->N;

@@ -39,6 +39,7 @@ void free_candidates(sdpcut_ctx *h)
     }
     hipFree(h->d_set_orig); hipFree(h->d_k); hipFree(h->d_eig); hipFree(h->d_obj);
     free_sdp_ws(h);
+    free_eff_ws(h);
     h->d_set_orig = nullptr; h->d_k = nullptr; h->d_eig = nullptr; h->d_obj = nullptr;
     h->N = 0; h->scored = 0; h->obj_partial = false; h->last_total = -1;
     h->stat_nn_skipped = 0; h->nn_skipped_on_device = false;
@@ -101,6 +102,7 @@ int sdpcut_set_instance(sdpcut_handle h, int32_t nb_vars, const double *Q_arr)
     const int64_t L = (int64_t)nb_vars * (nb_vars + 1) / 2;
     hipFree(h->d_Q); hipFree(h->d_vars);
     box_clear(h);      // (a box belongs to the instance it was set for)
+    free_lpobj(h);     // (so does an LP objective vector: its length is the instance's)
     h->d_Q = nullptr; h->d_vars = nullptr; h->have_point = false; h->scored = 0; h->obj_partial = false;
     HIP_TRY(h, hipMalloc((void **)&h->d_Q, L * sizeof(double)));
     HIP_TRY(h, hipMalloc((void **)&h->d_vars, (L + nb_vars) * sizeof(double)));

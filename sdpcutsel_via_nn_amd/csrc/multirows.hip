@@ -374,8 +374,8 @@ int sdpcut_round_csr_multi(sdpcut_handle h, const double *vars_values, int strat
     if (max_per_set < 1 || max_per_set > SDPCUT_MULTI_MAX_PER_SET)
         return sdpcut_fail(h, SDPCUT_EINVAL, "max_per_set must lie in 1 .. SDPCUT_MULTI_MAX_PER_SET");
     if (row_quota < 1) return sdpcut_fail(h, SDPCUT_EINVAL, "row_quota must be >= 1");
-    const bool by_sdp = strat_is_sdp(h, strat);
-    if (!by_sdp && (rc = check_round_strategy(h, strat))) return rc;
+    const uint32_t measure = strat_view(h, strat);      // strategies 3 and 6 rank through a view (common.h: MeasureAsObj)
+    if (!measure && (rc = check_round_strategy(h, strat))) return rc;
     if (sel_size < 0) return sdpcut_fail(h, SDPCUT_EINVAL, "bad round_csr_multi arguments");
     if (h->nb_vars == 0 || !h->d_eig || !(h->have_point || vars_values))
         return sdpcut_fail(h, SDPCUT_ESTATE, "set_instance, set_candidates and a point first");
@@ -386,9 +386,9 @@ int sdpcut_round_csr_multi(sdpcut_handle h, const double *vars_values, int strat
     const int64_t cap = sel_size < h->N ? sel_size : h->N;
     if (cap > MULTI_MAX_HEAD) return sdpcut_fail(h, SDPCUT_EINVAL, "round_csr_multi: head too long");
     // the head: the strategy's ranking by the existing ranking call, as the plain round's general path ranks it
-    if (!by_sdp && cap > 0 && exact_head_applies(h, strat) && exact_first_band(h, cap) > TK_LDSK)
+    if (!measure && cap > 0 && exact_head_applies(h, strat) && exact_first_band(h, cap) > TK_LDSK)
         return sdpcut_fail(h, SDPCUT_EINVAL, "SDPCUT_OPT_EXACT_HEAD: the head plus its band (min(N, sel_size + max(256, sel_size / 8))) must not exceed 8192 entries");
-    const uint32_t need = by_sdp ? (uint32_t)SDPCUT_SDP : strat_need(strat);
+    const uint32_t need = measure ? measure : strat_need(strat);
     if ((rc = obj_complete(h))) return rc;      // a measure a skipped round left partial: whole before this round counts by it
     if ((h->scored & need) != need && (rc = sdpcut_score(h, need & ~h->scored))) return rc;
     sdpcut_round_csr_t &o = out->csr;

@@ -347,6 +347,7 @@ static int score_points_impl(sdpcut_ctx *h, const char *what, int32_t n_points, 
     int rc = check_points_args(h, n_points, points, point_ld);
     if (rc) return rc;
     if (flags & SDPCUT_SDP) return sdpcut_fail(h, SDPCUT_EINVAL, std::string(what) + ": SDPCUT_SDP is not served over several points; flags = SDPCUT_EIG | SDPCUT_NN");
+    if (flags & SDPCUT_EFF) return sdpcut_fail(h, SDPCUT_EINVAL, std::string(what) + ": SDPCUT_EFF is not served over several points; flags = SDPCUT_EIG | SDPCUT_NN");
     if (!(flags & (SDPCUT_EIG | SDPCUT_NN)) || (flags & ~(uint32_t)(SDPCUT_EIG | SDPCUT_NN)))
         return sdpcut_fail(h, SDPCUT_EINVAL, "flags must be a combination of SDPCUT_EIG and SDPCUT_NN");
     if (((flags & SDPCUT_EIG) && !eig_out) || ((flags & SDPCUT_NN) && !obj_out))
@@ -385,6 +386,8 @@ static int round_csr_points_impl(sdpcut_ctx *h, const char *what, int32_t n_poin
     if (!out) return sdpcut_fail(h, SDPCUT_EINVAL, "out is NULL");
     int rc = check_points_args(h, n_points, points, point_ld);
     if (rc) return rc;
+    if (strat == SDPCUT_STRAT_EFF)
+        return sdpcut_fail(h, SDPCUT_EINVAL, std::string(what) + ": strategy 6 (efficacy) is not served over several points; strategies 1, 2 and 4 are");
     if (!batch_mode(strat))
         return sdpcut_fail(h, SDPCUT_EINVAL, std::string(what) + " serves strategies 1 (feasibility), 2 (optimality) and 4 (combined)");
     if (sel_size < 0) return sdpcut_fail(h, SDPCUT_EINVAL, "sel_size is negative");

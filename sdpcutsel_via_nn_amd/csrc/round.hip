@@ -88,15 +88,16 @@ static int round_begin_exact_again(sdpcut_ctx *h, PendingRound &P);
 static int round_begin(sdpcut_ctx *h, int strat, int64_t sel_size, int32_t coef_ld, bool csr)
 {
     int rc;
-    if (strat_is_sdp(h, strat)) {
-        // strategy 3: the exact measure is scored here if it is missing, then the round is strategy 2's on that array -- already
-        // scored, so the selection is the non-fused one (score_for_selection) -- and round_end runs inside the same view
+    if (const uint32_t measure = strat_view(h, strat)) {
+        // strategies 3 and 6: the measure is scored here if it is missing, then the round is strategy 2's on that array -- already
+        // scored, so the selection is the non-fused one (score_for_selection) -- and round_end runs inside the same view.  (Strategy
+        // 6 has scored SDPCUT_EIG with its measure: the rows kernel receives d_eig, the rows are those the score was computed from.)
         if (!h->have_point || !h->d_eig) return sdpcut_fail(h, SDPCUT_ESTATE, "set_candidates and set_point first");
         SDPCUT_NO_PENDING(h);
-        if (!(h->scored & SDPCUT_SDP) && (rc = sdpcut_score(h, SDPCUT_SDP))) return rc;
-        SdpAsObj view(h);
+        if (!(h->scored & measure) && (rc = sdpcut_score(h, measure))) return rc;
+        MeasureAsObj view(h, measure);
         rc = round_begin(h, SDPCUT_STRAT_OPT, sel_size, coef_ld, csr);
-        if (!rc) h->pend.by_sdp = true;
+        if (!rc) h->pend.view = measure;
         return rc;
     }
     rc = check_round_strategy(h, strat);
@@ -248,11 +249,11 @@ static int round_end(sdpcut_ctx *h, const void **block, int64_t *cap_out, int64_
 {
     if (!block || !cap_out || !n_out) return sdpcut_fail(h, SDPCUT_EINVAL, "bad select_round arguments");
     if (!h->pend.active) return sdpcut_fail(h, SDPCUT_ESTATE, "no round pending on this handle");
-    if (h->pend.by_sdp) {
-        h->pend.by_sdp = false;
-        SdpAsObj view(h);
+    if (const uint32_t measure = h->pend.view) {
+        h->pend.view = 0;
+        MeasureAsObj view(h, measure);
         const int rc3 = round_end(h, block, cap_out, n_out, n_total, new_strat, counters);
-        if (!rc3 && new_strat) *new_strat = SDPCUT_STRAT_EXACT;
+        if (!rc3 && new_strat) *new_strat = view_strat(measure);
         return rc3;
     }
     PendingRound P = h->pend;

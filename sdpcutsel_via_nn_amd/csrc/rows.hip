@@ -11,62 +11,7 @@
 #include "topk_dev.h"
 
 // ------------------------------------------------------------------------------------------
-// Eigen-cut rows of selected candidates (cut_select_qp.py:737-750), one lane per cut.
-template <int K>
-__device__ __forceinline__ void cut_row_one(const int32_t *s5, const double *vars, int32_t nv, int64_t L,
-                                            double *lam_out, double *coef, double *rhs, int64_t *cols, const double *lam_known = nullptr)
-{
-    constexpr int M = K * (K + 1) / 2;
-    constexpr int D = K + 1;
-    double x[K], X[M];
-    gather_lifted<K>(s5, vars, nv, L, x, X, cols);
-    double a[D][D];
-    fill_lifted<K>(a, x, X);
-    double lam = 0.0;
-    double ev[D];
-    bool have = false;
-#ifndef SDPCUT_ROWS_INVERSE_ITERATION
-#define SDPCUT_ROWS_INVERSE_ITERATION 1
-#endif
-    if (SDPCUT_ROWS_INVERSE_ITERATION && (lam_known || SDPCUT_LMIN)) {
-        // the scoring pass has computed lambda_min of this candidate (the value the selection ranked by): its eigenvector by
-        // inverse iteration (jacobi.h: ~700 instead of ~6700 instructions of a wave that has its SIMD to itself).  (r4) A round
-        // that ranked without eigenvalues (optimality; explicit sdpcut_cut_rows on an unscored list) computes lambda_min here
-        // with the solver the scoring kernels use (lmin.h) instead of running Jacobi with vectors for the whole spectrum.
-        bool ok = true;
-        if (lam_known) {
-            lam = *lam_known;
-        } else {
-            double b[D][D];
-#pragma unroll
-            for (int i = 0; i < D; ++i)
-#pragma unroll
-                for (int j = 0; j < D; ++j) b[i][j] = a[i][j];
-            lam = lmin_laguerre<D>(b, ok);
-        }
-        have = ok && min_eigvec_known<D>(a, lam, ev) <= 1e-12;
-#ifdef SDPCUT_ABL_NOFALLBACK      // timing experiment (tools/build_ablation.sh, ABL_SRC=rows): wrong on multiple eigenvalues
-        have = true;
-#endif
-    }
-    if (!have) {      // no lambda_min at hand (optimality rounds, explicit sdpcut_cut_rows) -- or, never observed, a residual too large
-        double v[D][D];
-        jacobi_eig<D, true>(a, v);
-        // eigenvector of the smallest eigenvalue (first minimum, like LAPACK's ascending order)
-        lam = a[0][0];
-#pragma unroll
-        for (int i = 0; i < D; ++i) ev[i] = v[i][0];
-#pragma unroll
-        for (int j = 1; j < D; ++j) {
-            const bool less = a[j][j] < lam;
-            lam = less ? a[j][j] : lam;
-#pragma unroll
-            for (int i = 0; i < D; ++i) ev[i] = less ? v[i][j] : ev[i];
-        }
-    }
-    eigcut_row<K>(ev, coef, rhs);
-    *lam_out = lam;
-}
+// Eigen-cut rows of selected candidates (cut_select_qp.py:737-750), one lane per cut: cut_row_one of rows_dev.h.
 
 // count may be an upper bound: if d_limit != NULL only min(count, *d_limit) rows exist (the
 // device-side length of a ranking that the host has not read yet).  coef rows have stride

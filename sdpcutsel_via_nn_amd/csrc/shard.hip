@@ -99,6 +99,7 @@ extern "C" int sdpcut_shard_head_device(sdpcut_handle h, int strat, int64_t coun
     SDPCUT_NO_BOX(h, "sharded rounds");
     if (count < 1 || count > TK_MAXK || !d_record) return sdpcut_fail(h, SDPCUT_EINVAL, "shard head: count must be 1.." + std::to_string(TK_MAXK));
     const bool comball = strat == SDPCUT_PART_COMBALL;
+    if (strat == SDPCUT_STRAT_EFF) return sdpcut_fail(h, SDPCUT_EINVAL, "shard head: strategy 6 (efficacy) is not served by the sharded rounds");
     if (strat != SDPCUT_STRAT_FEAS && strat != SDPCUT_STRAT_OPT && strat != SDPCUT_PART_STRONG && !comball)
         return sdpcut_fail(h, SDPCUT_EINVAL, "shard head: strategy must be 1, 2, SDPCUT_PART_STRONG or SDPCUT_PART_COMBALL");
     const uint32_t need = strat_need(strat);

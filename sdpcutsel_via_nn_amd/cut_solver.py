@@ -30,9 +30,11 @@ from .rank_list import (AggArrays, DeviceAgg, FeasEntry, RankList, RankListHead,
 _THRES_NEG_EIGVAL = -10 ** (-15)      # cut_select_qp.py:24
 _HEAD = 5000                          # _SDP_CUTS_PER_ROUND_MAX (:37): rank-list head fetched eagerly
 _FUSED_HEAD_MAX = 16384               # longest head the fused round (sdpcut_round_csr) assembles
-# what each selecting strategy has the device score: feasibility, optimality (MLP), exact optimality, combined
-_MEASURES = {1: _capi.EIG, 2: _capi.NN, 3: _capi.SDP, 4: _capi.EIG | _capi.NN}
-_OPT_STRATS = (2, 3, 4, -1)           # strategies whose rank-list entries are optimality tuples (cut_select_qp.py:599)
+# what each selecting strategy has the device score: feasibility, optimality (MLP), exact optimality, combined, efficacy (which
+# scores lambda_min with it)
+_MEASURES = {1: _capi.EIG, 2: _capi.NN, 3: _capi.SDP, 4: _capi.EIG | _capi.NN, 6: _capi.EIG | _capi.EFF}
+_OPT_STRATS = (2, 3, 4, -1, 6)        # strategies whose rank-list entries are optimality tuples (cut_select_qp.py:599); 6 ranks as 2 does
+_STRONG_STRATS = (2, 3, 4, -1)        # ... and for which strong_only cuts the head at the first non-positive score (:725-726)
 
 
 def _lp_point(vars_values):
@@ -222,7 +224,8 @@ class GpuCutSelectionMixin(object):
     # ------------------------------------------------------------------ a7-a9 selection
     def _sel_eigcut_by_ordering_on_measure(self, strat, vars_values, cut_round, sel_size=0):
         """Strategies 1 (feasibility), 2 (optimality via MLP), 4 (combined), 5 (random); same returns as
-        cut_select_qp.py:543-703.  With ``_gpu_exact_sdp`` also 3 (optimality via the exact SDP solution: the layout of strategy 2)
+        cut_select_qp.py:543-703.  Strategy 6 (efficacy of the emitted row, ``Scorer.score(EFF)``; not the reference's) returns
+        the layout of strategy 2 with the efficacy score in place of obj_improve.  With ``_gpu_exact_sdp`` also 3 (optimality via the exact SDP solution: the layout of strategy 2)
         and -1 (figure 8: ``(rank_list, overlap, std_dev_exact, this_round_cuts)`` of :660-702)."""
         if strat == 5:
             # random order, in place, like :634-637; the device twin of the old order is dropped
@@ -235,7 +238,7 @@ class GpuCutSelectionMixin(object):
                 np.random.shuffle(agg)
             getattr(self, "_gpu_bindings", {}).pop(id(agg), None)
             return agg
-        if strat not in (1, 2, 4) and not (self._gpu_exact_sdp and strat in (3, -1)):
+        if strat not in (1, 2, 4, 6) and not (self._gpu_exact_sdp and strat in (3, -1)):
             raise NotImplementedError("exact-SDP strategies (3, -1) are not part of the GPU path unless exact_sdp is switched on")
         b = self._gpu_bind()
         N = len(self._agg_list)
@@ -422,7 +425,9 @@ class GpuCutSelectionMixin(object):
 
     def _gen_eigcuts_selected(self, strat, sel_size, rank_list, strong_only=False, vars_values=None):
         """Eigen-cuts of the first ``sel_size`` ranked candidates, appended to
-        ``self._my_prob.linear_constraints`` (cut_select_qp.py:705-755)."""
+        ``self._my_prob.linear_constraints`` (cut_select_qp.py:705-755).  ``strong_only`` has no meaning under strategy 6 (a
+        non-positive score there is a candidate that yields no cut anyway) and is ignored."""
+        strong_only = strong_only and strat in _STRONG_STRATS
         if int(self.cuts_per_set) > 1 and sel_size > 0 and len(rank_list) > 0:
             return self._gen_eigcuts_multi(strat, sel_size, rank_list, strong_only, vars_values)
         sel_size = min(sel_size, len(rank_list))
@@ -753,7 +758,7 @@ class CutSolver(GpuCutSelectionMixin):
         if cur == 4:
             run.strat = r["new_strat"]            # the switch takes effect next round (:181 vs :188)
         entries = int(r["idx"].shape[0])
-        csr = csr_prefix(r, strong_prefix(r["score"], entries) if run.strong_only and cur in _OPT_STRATS else entries)      # :725-726
+        csr = csr_prefix(r, strong_prefix(r["score"], entries) if run.strong_only and cur in _STRONG_STRATS else entries)      # :725-726
         if multi:
             rows = csr[3].shape[0]
             used = r["row_entry"][:rows]
@@ -783,7 +788,8 @@ class CutSolver(GpuCutSelectionMixin):
     def cut_select_algo(self, filename, dim, sel_size, strat=2, nb_rounds_cuts=20, term_on=False,
                         triangle_on=False, strong_only=False, max_subs=_THRES_MAX_SUBS, on_round=None, plots=False, sol=0,
                         ch_ext=0, max_parallel=None, pool_factor=4, cuts_per_set=1, row_quota=None,
-                        pool_max_age=None, pool_drop_age=10, pool_return=None, pool_tight_tol=1e-9, pool_viol_tol=1e-6, box=None):
+                        pool_max_age=None, pool_drop_age=10, pool_return=None, pool_tight_tol=1e-9, pool_viol_tol=1e-6, box=None,
+                        objpar_weight=0.0):
         """Cutting-plane rounds on a BoxQP ``.in`` file, same arguments and default return tuple as
         the reference's entry point (cut_select_qp.py:73-221), with HiGHS as LP solver, the native
         cover enumeration and the GPU selection / generation / triangle separation in between.
@@ -799,7 +805,13 @@ class CutSolver(GpuCutSelectionMixin):
         (optimality via the exact SDP solution) and -1 (figure 8); with ``strat=-1, plots=True`` the return is the reference's
         ``(gap_closed_percent, rounds_stats, round_std_devs, rounds_all_cuts)`` with the gap closed measured against ``sol``
         (:209-215).  ``plots`` with another strategy is out of scope.
-        ``max_parallel`` (off by default; strategies 1, 2 and 4 only): a parallelism filter on the ranked head
+        Strategy 6 (not the reference's) ranks all candidates by the EFFICACY of the eigen-cut they would emit -- the distance by
+        which the row cuts off the LP point, the first criterion of a MIP solver's cut selector -- plus ``objpar_weight`` (>= 0,
+        default 0; SCIP's default weights correspond to 0.1) times the row's parallelism to the LP objective (``Scorer.score(EFF)``,
+        DESIGN.md section 5 "Efficacy ranking"); with a positive weight the run hands its LP's objective vector to the handle.  No
+        networks are loaded; ``strong_only`` has no meaning there and is ignored; ``max_parallel`` and ``cuts_per_set`` work with it.
+        ``CutSolver(exact_sdp=True)`` refuses it as before: that opt-in's strategy set is unchanged.
+        ``max_parallel`` (off by default; strategies 1, 2, 4 and 6 only): a parallelism filter on the ranked head
         (``Scorer.round_csr_diverse``, DESIGN.md section 5 "Diverse selection").  Each round walks the first
         ``min(pool_factor * quota, 16384)`` ranked candidates and adds a cut only while fewer than the quota are added and its
         ``|cos|`` with every cut added before it in the round is at most ``max_parallel``; the walk's counts of every round are
@@ -826,16 +838,22 @@ class CutSolver(GpuCutSelectionMixin):
         round, number of candidates)."""
         from timeit import default_timer as clock
         from . import harness
-        if strat not in (0, 1, 2, 4, 5) and not (self._gpu_exact_sdp and strat in (3, -1)):
-            raise AssertionError("strategies on the GPU path: 0 dense, 1 feasibility, 2 optimality, 4 combined, 5 random "
+        if strat == 6 and self._gpu_exact_sdp:      # the opt-in's strategy set stays what it was: 6 was refused there and still is
+            raise AssertionError("strategy 6 (efficacy) is offered by the default solver only: CutSolver(exact_sdp=True) keeps its strategies "
+                                 "0, 1, 2, 3, 4, 5 and -1")
+        if strat not in (0, 1, 2, 4, 5, 6) and not (self._gpu_exact_sdp and strat in (3, -1)):
+            raise AssertionError("strategies on the GPU path: 0 dense, 1 feasibility, 2 optimality, 4 combined, 5 random, 6 efficacy "
                                  "(3 exact optimality and -1 figure 8 with exact_sdp=True)")
+        objpar_weight = float(objpar_weight)
+        assert 0.0 <= objpar_weight < float("inf"), "objpar_weight is the weight of the objective parallelism in strategy 6's score: finite, >= 0"
+        assert objpar_weight == 0.0 or strat == 6, "objpar_weight belongs to strategy 6 (efficacy)"
         assert not plots or strat == -1, "plots=True returns the figure-8 tuple: strat=-1 only"
         assert 0 < sel_size, "The selection size must be a % or number (of cuts) >0!"
         assert dim <= 5, "Keep SDP vertex cover low-dimensional (<=5)!"
         assert (ch_ext in [0, 1, 2]), "Chordal extension flags: 0-P^E_3, 1-P^bar(E)_3, 2-bar(P*_3)!"      # :94
         if max_parallel is not None:
-            if strat not in (1, 2, 4):
-                raise AssertionError("max_parallel filters the ranked head of strategies 1 (feasibility), 2 (optimality) and 4 (combined) only")
+            if strat not in (1, 2, 4, 6):
+                raise AssertionError("max_parallel filters the ranked head of strategies 1 (feasibility), 2 (optimality), 4 (combined) and 6 (efficacy) only")
             assert 0.0 <= max_parallel <= 1.0, "max_parallel is a bound on |cos| between two cuts: 0 .. 1"
             assert pool_factor >= 1, "the pool is pool_factor times the quota: pool_factor >= 1"
             self.diverse_log = []
@@ -879,6 +897,10 @@ class CutSolver(GpuCutSelectionMixin):
         t_model = clock()
         self._my_prob = lp = harness.boxqp_relaxation(inst, *(node_box or ()))
         t_model = clock() - t_model
+        if strat == 6:
+            sc.set_efficacy_weight(objpar_weight)
+            if objpar_weight > 0.0:
+                sc.set_objective(lp.obj)      # [Q_arr | c]: the LP's columns are the LP point's
         if triangle_on:
             self._preprocess_triangle_ineq()
         rounds_stats, round_std_devs, rounds_all_cuts = [], [], []      # figure 8 (:144)
@@ -974,6 +996,8 @@ class CutSolverQCQP(CutSolver):
         (``self.multi_log`` has one record per round).
         -> (objective value per solve, sel_size, PSD cuts per round, optimality cuts per round)."""
         from . import harness
+        if strat == 6:
+            raise AssertionError("strategy 6 (efficacy) is not offered for QCQP: ranking the two covers of a round by one efficacy scale is not built")
         if strat not in (1, 2, 4, 5) and not (self._gpu_exact_sdp and strat == 3):      # cut_select_qcqp.py:26 allows 3
             raise AssertionError("strategies on the GPU path: 1 feasibility, 2 optimality, 4 combined, 5 random (3 exact optimality with exact_sdp=True)")
         assert 0 < sel_size, "The selection size must be a % or number (of cuts) >0!"
