@@ -12,7 +12,7 @@
 //   V, so a rotation combines two contiguous rows, coalesced); 128 KB that one CU reads and writes, resident in its caches.
 //   A sweep starts only while off(A) = sqrt(2 sum_{i<j} a_ij^2) > 2^-52 * 1e-3 * ||A||_F (one workgroup reduction per sweep, in a
 //   fixed order: the same point gives the same bits), at most DN_MAX_SWEEPS times.  Then a rank sort of the diagonal (ascending, ties
-//   by index), the vectors copied out in that order, and n_rows = #{r < n : lambda_r < -1e-15} (:773-774; the negatives are a prefix).
+//   by index), the vectors copied out in that order, each scaled to unit length, and n_rows = #{r < n : lambda_r < -1e-15} (:773-774; the negatives are a prefix).
 // dn_rows_kernel -- grid (row r, tile of 8 matrix rows); a workgroup whose r is not below the n_rows it reads from device memory
 //   retires (no host round trip between the two kernels).  Values [2 v0 v1 .. 2 v0 vn | v1^2, 2 v1 v2, .., vn^2], rhs -v0^2 (:776-780,
 //   nothing zeroed), stored straight into the handle's pinned host block; the column list [L .. L+n-1 | 0 .. L-1] is the same for
@@ -221,8 +221,18 @@ __global__ __launch_bounds__(DN_THREADS) void dn_eig_kernel(const double *__rest
         eig_out[rank] = mine;
     }
     __syncthreads();
+    // every vector leaves with unit length: the rotations leave ||v|^2 - 1| of the order of D eps (1.4e-14 seen at D = 41), and a cut
+    // row is v v^T written out -- it is the row of a unit vector only as far as v is one.  (rc .. rt are free once the sweeps are over.)
+    double *scale = rc;                       // [D] <= 3 * (DN_MAX_D / 2) doubles
+    if (tid < D) {
+        const double *src = vt + ord[tid] * D;
+        double ss = 0.0;
+        for (int c = 0; c < D; ++c) ss = fma(src[c], src[c], ss);
+        scale[tid] = ss > 0.0 ? 1.0 / sqrt(ss) : 1.0;      // (a NaN spectrum is copied out as it is)
+    }
+    __syncthreads();
     if (col < D)
-        for (int r = row0; r < D; r += DN_THREADS / DN_MAX_D) vs[r * D + col] = vt[ord[r] * D + col];
+        for (int r = row0; r < D; r += DN_THREADS / DN_MAX_D) vs[r * D + col] = vt[ord[r] * D + col] * scale[r];
     if (tid == 0) {
         int cnt = 0;
         for (int r = 0; r < n; ++r) cnt += lam[ord[r]] < SDPCUT_NEG_EIGVAL ? 1 : 0;      // (the largest eigenvalue is never a cut, :773)

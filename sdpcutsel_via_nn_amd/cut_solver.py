@@ -851,6 +851,8 @@ class CutSolver(GpuCutSelectionMixin):
         assert 0 < sel_size, "The selection size must be a % or number (of cuts) >0!"
         assert dim <= 5, "Keep SDP vertex cover low-dimensional (<=5)!"
         assert (ch_ext in [0, 1, 2]), "Chordal extension flags: 0-P^E_3, 1-P^bar(E)_3, 2-bar(P*_3)!"      # :94
+        if ch_ext == 2 and dim != 3:      # (with the other argument checks: before the file is read and a handle is made)
+            raise ValueError("ch_ext = 2 is a cover of dimension 3 only")
         if max_parallel is not None:
             if strat not in (1, 2, 4, 6):
                 raise AssertionError("max_parallel filters the ranked head of strategies 1 (feasibility), 2 (optimality), 4 (combined) and 6 (efficacy) only")

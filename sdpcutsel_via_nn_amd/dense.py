@@ -90,6 +90,7 @@ def jacobi_twin(A):
         sweeps += 1
     lam = np.diag(A).copy()
     order = np.argsort(lam, kind="stable")
+    V = V / np.sqrt(np.sum(V * V, axis=0))      # every vector leaves with unit length (the rotations leave |v|^2 - 1 ~ D eps)
     return lam[order], V[:, order], sweeps
 
 
