@@ -60,7 +60,9 @@ enum { SDPCUT_STRAT_FEAS = 1, SDPCUT_STRAT_OPT = 2, SDPCUT_STRAT_EXACT = 3, SDPC
  * sdpcut_round_csr_diverse and sdpcut_round_csr_multi: the fused calls score the measure themselves if it is missing, then run
  * the selection strategy 2 runs on scores that exist already; `score` of every head is escore, and the rows are computed from the
  * lambda_min the score was computed from.  No networks needed.  SDPCUT_OPT_EXACT_HEAD ignores it.  Refused with SDPCUT_EINVAL: by
- * the batched-points calls (sdpcut_score_points*, sdpcut_round_csr_points*) and the sharded entry points (sdpcut_shard_*). */
+ * the plain batched-points calls (sdpcut_score_points, sdpcut_round_csr_points and their _boxed forms; over many LP points the
+ * measure and the strategy come through sdpcut_efficacy_points and sdpcut_round_csr_points_diverse) and the sharded entry points
+ * (sdpcut_shard_*). */
 enum { SDPCUT_STRAT_EFF = 6 };
 /* Partial ranking for candidate sets sharded over several GPUs (SURVEY.md section 8 e): only
  * the "strong" class of the combined scan (cut_select_qp.py:607-613: obj_improve > 0 and
@@ -198,12 +200,15 @@ enum { SDPCUT_OPT_KERNEL = 1, SDPCUT_OPT_TIMING = 2, SDPCUT_OPT_FUSE_KEYS = 3, S
  * SDPCUT_STAT_NN_COMPLETIONS = NN scoring launches since the handle was made that completed a measure such a launch left partial.
  * SDPCUT_STAT_NN_EVALUATED = fp64 MLP evaluations of the handle's last scoring launch that ran the network: the list length after a
  *   launch that scored everybody, nb_violated after a skipping launch, the survivors of the fp32 filter after a filtering one (read
- *   from the device: the call waits for the handle's stream); 0 after a new list. */
+ *   from the device: the call waits for the handle's stream); 0 after a new list.
+ * SDPCUT_STAT_DIVERSE_POINTS_FAST = points of sdpcut_round_csr_points_diverse answered by its one-wait route since the handle was made
+ *   (points served by the loop inside the call, or redone, do not count). */
 enum { SDPCUT_STAT_ROUNDS = 1, SDPCUT_STAT_SELECT_FALLBACKS = 2, SDPCUT_STAT_SCORED = 3, SDPCUT_STAT_TIE_SPLITS = 4,
        SDPCUT_STAT_DIRECT_SELECTIONS = 5, SDPCUT_STAT_PF_BIN = 6, SDPCUT_STAT_PF_FLOOR = 7, SDPCUT_STAT_PF_COUNT = 8,
        SDPCUT_STAT_EXACT_HEAD = 9, SDPCUT_STAT_EXACT_GAVE_UP = 10, SDPCUT_STAT_EXACT_RETRIES = 11,
        SDPCUT_STAT_SDP_UNCONVERGED = 12, SDPCUT_STAT_POINTS_REDONE = 13,
-       SDPCUT_STAT_NN_SKIPPED = 14, SDPCUT_STAT_NN_COMPLETIONS = 15, SDPCUT_STAT_NN_EVALUATED = 16 };
+       SDPCUT_STAT_NN_SKIPPED = 14, SDPCUT_STAT_NN_COMPLETIONS = 15, SDPCUT_STAT_NN_EVALUATED = 16,
+       SDPCUT_STAT_DIVERSE_POINTS_FAST = 17 };
 int sdpcut_get_stat(sdpcut_handle h, int which, int64_t *value);
 
 /* The fp32 filter (SDPCUT_OPT_FP32_FILTER) of the network set for k-variable candidates: *margin = the proven bound on
@@ -676,6 +681,36 @@ int sdpcut_round_csr_diverse(sdpcut_handle h, const double *vars_values, int str
                              double max_parallel, sdpcut_round_csr_t *out, sdpcut_diverse_info_t *info);
 int sdpcut_filter_parallel(sdpcut_handle h, int64_t count, const int64_t *idx, int64_t quota, double max_parallel, uint8_t *keep_out,
                            sdpcut_diverse_info_t *info);
+
+/*
+ * Efficacy and the filtered round over MANY LP POINTS (points, point_ld, n_points, the refusals and the state afterwards as for
+ * sdpcut_score_points / sdpcut_round_csr_points: no current point, nothing scored -- SDPCUT_EFF included -- and no box).
+ *
+ * sdpcut_efficacy_points: row p of eff_out / objpar_out / escore_out ([n_points][N] each; any may be NULL, not all) is what
+ * sdpcut_set_point(point p), sdpcut_score(SDPCUT_EIG | SDPCUT_EFF), sdpcut_get_efficacy returns, bit for bit, with the handle's
+ * objective and weight.  One point copy, the eigenvalue launch and one efficacy launch with a point axis.  Efficacy knows no box.
+ *
+ * sdpcut_round_csr_points_diverse: out[p] and info[p] (info may be NULL) are what sdpcut_round_csr_diverse(h, point p, strat,
+ * sel_size, pool_size, max_parallel, &o, &i) returns -- every field, every array, n_total, new_strat and the counters, bit for bit;
+ * strategies 1, 2, 4 and 6.  lb / ub (both NULL: no boxes; else rows of box_ld >= n doubles as for sdpcut_round_csr_points_boxed):
+ * the comparison call then follows sdpcut_set_box(h, lb_p, ub_p) on a fresh handle; the boxes are checked before any state changes,
+ * a handle with a box of its own or SDPCUT_OPT_EXACT_HEAD on is refused.  Strategies 1 and 6 read no box.  All pointers point into
+ * one pinned block of the handle (slices of the layout for cap = min(sel_size, pool)), valid until the next call on the handle.
+ * SDPCUT_EINVAL: the cases of sdpcut_round_csr_diverse and those of sdpcut_round_csr_points for n_points and point_ld.
+ *   One-wait route (SDPCUT_STAT_DIVERSE_POINTS_FAST counts its points): lists of at most 4096 candidates, pool = min(pool_size, N)
+ *   of 1 .. 512 entries, SDPCUT_OPT_EXACT_HEAD off, no shard base, boxed: the box tables within 256 MiB; strategy 4 only with
+ *   min(sel_size, N) == pool (its ranking depends on the quota; csrc/batch_route.h: batch_route_diverse).  One point copy, the score
+ *   launches of the batched round (strategy 6: eigenvalues, then the efficacy launch), one selection launch with k = pool, one row
+ *   launch for the pools, ONE filter launch -- a workgroup per point holds the pool's rows, index sets and pair bits in LDS and walks
+ *   it (csrc/diverse.hip: div_points_kernel) -- one row assembly over the accepted heads, ONE host wait.  A point whose selection
+ *   declared itself void goes through the single-point call (SDPCUT_STAT_POINTS_REDONE).
+ *   Everything else loops inside the call: sdpcut_set_box where there are boxes, then sdpcut_round_csr_diverse per point.
+ */
+int sdpcut_efficacy_points(sdpcut_handle h, int32_t n_points, const double *points, int64_t point_ld, double *eff_out, double *objpar_out,
+                           double *escore_out /* each [n_points][N], may be NULL */);
+int sdpcut_round_csr_points_diverse(sdpcut_handle h, int32_t n_points, const double *points, int64_t point_ld, const double *lb, const double *ub,
+                                    int64_t box_ld, int strat, int64_t sel_size, int64_t pool_size, double max_parallel,
+                                    sdpcut_round_csr_t *out /* [n_points] */, sdpcut_diverse_info_t *info /* [n_points] */);
 
 /*
  * All violated eigen-cuts of a selected set: multi-cut rounds.  A round emits ONE cut per selected index set, the eigenvector of

@@ -35,6 +35,7 @@ STAT_NN_SKIPPED, STAT_NN_COMPLETIONS = 14, 15   # candidates the last such launc
 OPT_FP32_FILTER = 16     # the skipping launch filters the violated candidates in fp32 ahead of the fp64 pass (include/sdpcut.h); default on
 STAT_NN_EVALUATED = 16   # fp64 MLP evaluations of the last scoring launch that ran the network
 STAT_POINTS_REDONE = 13   # points of batched rounds served by the single-point round inside the call (include/sdpcut.h)
+STAT_DIVERSE_POINTS_FAST = 17   # points of round_csr_points_diverse answered by its one-wait route (include/sdpcut.h)
 BATCH_MAX_POINTS = 256   # SDPCUT_BATCH_MAX_POINTS: most LP points of one score_points / round_csr_points call
 DIVERSE_MAX_POOL = 16384   # SDPCUT_DIVERSE_MAX_POOL: longest pool of round_csr_diverse / list of filter_parallel
 MULTI_MAX_PER_SET = 5      # SDPCUT_MULTI_MAX_PER_SET: most eigen-cuts one index set offers (round_csr_multi / cut_rows_all)
@@ -145,6 +146,9 @@ SIGNATURES = {
     "sdpcut_round_csr_points_boxed": [_vp, _c.c_int32, _dp, _c.c_int64, _dp, _dp, _c.c_int64, _c.c_int, _c.c_int64, _c.POINTER(RoundCsr)],
     "sdpcut_round_csr_diverse": [_vp, _dp, _c.c_int, _c.c_int64, _c.c_int64, _c.c_double, _c.POINTER(RoundCsr), _c.POINTER(DiverseInfo)],
     "sdpcut_filter_parallel": [_vp, _c.c_int64, _i64p, _c.c_int64, _c.c_double, _c.POINTER(_c.c_uint8), _c.POINTER(DiverseInfo)],
+    "sdpcut_efficacy_points": [_vp, _c.c_int32, _dp, _c.c_int64, _dp, _dp, _dp],
+    "sdpcut_round_csr_points_diverse": [_vp, _c.c_int32, _dp, _c.c_int64, _dp, _dp, _c.c_int64, _c.c_int, _c.c_int64, _c.c_int64, _c.c_double,
+                                        _c.POINTER(RoundCsr), _c.POINTER(DiverseInfo)],
     "sdpcut_round_csr_multi": [_vp, _dp, _c.c_int, _c.c_int64, _c.c_int32, _c.c_int64, _c.POINTER(RoundMulti)],
     "sdpcut_cut_rows_all": [_vp, _c.c_int64, _i64p, _c.c_int32, _i64p, _dp, _dp, _dp, _i64p, _i32p],
     "sdpcut_pool_create": [_vp, _c.c_int64],
@@ -1082,8 +1086,13 @@ class Scorer(object):
         else:
             self._check(self._lib.sdpcut_round_csr_points_boxed(self._h, P, _ptr(pts, _dp), pts.shape[1], lb, ub, box_ld, int(strat),
                                                                 int(sel_size), recs.ctypes.data_as(_c.POINTER(RoundCsr))))
+        return self._points_unpack(recs, P, copy)
+
+    def _points_unpack(self, recs, P, copy):
+        """the P records of a batched round -> list of P round dicts (views of the batch block, or copies)"""
         r = recs[:P]
-        base = int(r["idx"].min())
+        held = r["idx"][r["idx"] != 0]      # (a point without a head has no arrays)
+        base = int(held.min()) if held.size else 0
         if base:
             # ONE byte view over the batch block (cached while the block stays where it is); every array is a slice of it
             c_max, ld = int(r["cap"].max()), int(r["row_ld"][0])
@@ -1110,6 +1119,41 @@ class Scorer(object):
                 d = _empty_round()
             d.update(n_total=cols["n_total"][p], new_strat=cols["new_strat"][p], counters=_counters(cols["counters"][p]))
             res.append(d)
+        return res
+
+    def efficacy_points(self, points):
+        """Efficacy of the candidate list at P LP points in one call (sdpcut_efficacy_points): points [P, n(n+1)/2 + n] ->
+        (eff, objpar, escore), each [P, N]; row p = what set_point(points[p]), score(EIG | EFF), get_efficacy return, with the
+        Scorer's objective and weight.  Leaves the Scorer without a current point."""
+        pts = self._points_arg(points)
+        P = pts.shape[0]
+        e, o, s = np.empty((P, self.N)), np.empty((P, self.N)), np.empty((P, self.N))
+        self._check(self._lib.sdpcut_efficacy_points(self._h, P, _ptr(pts, _dp), pts.shape[1], _ptr(e, _dp), _ptr(o, _dp), _ptr(s, _dp)))
+        return e, o, s
+
+    def round_csr_points_diverse(self, points, strat, sel_size, max_parallel, pool_size=None, copy=False, boxes=None):
+        """P filtered rounds, one LP point each, in one call (sdpcut_round_csr_points_diverse): -> list of P dicts, entry p = what
+        round_csr_diverse(points[p], strat, sel_size, max_parallel, pool_size) returns, ``info`` included; strategies 1, 2, 4 and 6.
+        boxes [P, 2, n]: entry p is what set_box(*boxes[p]) followed by that call returns.  Views of the pinned batch block, valid
+        until the next call on this Scorer (copy=True detaches them).  Leaves the Scorer without a current point and without a box."""
+        mp, sel_size, pool_size = check_diverse_args(max_parallel, sel_size, pool_size, strat)
+        pts = self._points_arg(points)
+        P = pts.shape[0]
+        lb = ub = None
+        box_ld = 0
+        if boxes is not None:
+            bx, lb, ub, box_ld = self._boxes_arg(pts, boxes)
+        self._open()
+        self.round_count += 1
+        recs = getattr(self, "_csr_points_recs", None)
+        if recs is None or recs.shape[0] < P:
+            recs = self._csr_points_recs = np.zeros(max(P, 8), dtype=_ROUND_CSR_DTYPE)
+        infos = (DiverseInfo * P)()
+        self._check(self._lib.sdpcut_round_csr_points_diverse(self._h, P, _ptr(pts, _dp), pts.shape[1], lb, ub, box_ld, int(strat), sel_size,
+                                                              pool_size, mp, recs.ctypes.data_as(_c.POINTER(RoundCsr)), infos))
+        res = self._points_unpack(recs, P, copy)
+        for p in range(P):
+            res[p]["info"] = self._diverse_info(infos[p])
         return res
 
     # ------------------------------------------------------------------ dense eigen-cuts (strategy 0)

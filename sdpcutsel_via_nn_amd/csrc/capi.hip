@@ -252,6 +252,7 @@ int sdpcut_get_stat(sdpcut_handle h, int which, int64_t *value)
         return SDPCUT_OK;
     case SDPCUT_STAT_TIE_SPLITS: *value = h->stat_tie_splits; return SDPCUT_OK;
     case SDPCUT_STAT_POINTS_REDONE: *value = h->stat_points_redone; return SDPCUT_OK;
+    case SDPCUT_STAT_DIVERSE_POINTS_FAST: *value = h->stat_diverse_points_fast; return SDPCUT_OK;
     case SDPCUT_STAT_EXACT_HEAD: *value = h->stat_exact_last; return SDPCUT_OK;
     case SDPCUT_STAT_EXACT_GAVE_UP: *value = h->stat_exact_gave_up; return SDPCUT_OK;
     case SDPCUT_STAT_EXACT_RETRIES: *value = h->stat_exact_retries; return SDPCUT_OK;

@@ -111,6 +111,15 @@ struct PointsBufs {
     size_t box_ld_doubles = 0;
     double *d_Q_box = nullptr, *d_vars_box = nullptr;   // [P][L] Q' and [P][L + n] transformed points (box.hip: box_points_kernel)
     size_t box_q_doubles = 0, box_vars_doubles = 0;
+    // efficacy over a batch (sdpcut_efficacy_points, the batched strategy-6 round): eff | objpar | escore, [P][N] each
+    double *d_eff = nullptr;
+    size_t eff_doubles = 0;
+    // the filtered batch (sdpcut_round_csr_points_diverse): pool rows, accepted heads and walk counts of every point in one device
+    // allocation; the selection counters of every point in mapped host memory
+    void *d_div = nullptr;
+    size_t div_bytes = 0;
+    void *div_sel = nullptr, *div_sel_dev = nullptr;   // [P][8] int64
+    int div_sel_points = 0;
 };
 
 struct sdpcut_ctx {
@@ -135,6 +144,7 @@ struct sdpcut_ctx {
     bool coop_launch = false;      // SDPCUT_OPT_COOP_LAUNCH: cooperative launch of the kernels with grid barriers (+20 us per round)
     int64_t stat_rounds = 0, stat_fallbacks = 0, stat_tie_splits = 0;   // sdpcut_get_stat
     int64_t stat_points_redone = 0;   // SDPCUT_STAT_POINTS_REDONE
+    int64_t stat_diverse_points_fast = 0;   // SDPCUT_STAT_DIVERSE_POINTS_FAST
     PointsBufs pts;                   // sdpcut_score_points / sdpcut_round_csr_points
     // SDPCUT_OPT_EXACT_HEAD (exact_head.hip): NN-ranked heads ordered and reported by reference-order obj_improve
     bool exact_head = false;
@@ -446,6 +456,35 @@ void free_dense_ws(sdpcut_ctx *h);
 void free_train_ws(sdpcut_ctx *h);
 // diverse.hip
 void free_diverse_ws(sdpcut_ctx *h);
+// The filter of a batch of points (div_rows_points_kernel, div_points_kernel): point p reads the head its selection emitted (row p
+// of idx / score, `pool` entries per row, its length and void flag in sel_c4 + p * c4_stride) and its LP point, and writes the
+// accepted entries into row p of acc_idx / acc_score (`cap` entries per row), the walk's counts into info + 8 p, and the
+// selection's counters into sel_out + 8 p (host memory).  row_*: scratch for the pool's rows, [n_points][pool].
+#define DIVP_MAX_POOL 512      // = BATCH_DIVERSE_MAX_POOL of batch_route.h: the rows of a pool fit the LDS of one workgroup
+#define DIVP_THREADS 512
+struct DivPointsArgs {
+    int64_t pool, cap, quota;
+    double max_parallel;
+    int compare;               // max_parallel < 1
+    const int64_t *sel_c4;
+    int64_t c4_stride;
+    const int64_t *idx;
+    const double *score;
+    int64_t idx_base, n_local;
+    const int32_t *set5, *ks;
+    const double *vars;
+    int64_t vars_ld;
+    int32_t nv;
+    int64_t L;
+    const double *eig;         // [n_points][eig_ld] lambda_min where the scoring computed it, else NULL
+    int64_t eig_ld;
+    double *row_coef, *row_lam;
+    int32_t *row_ks;
+    int64_t *acc_idx;
+    double *acc_score;
+    int64_t *info, *sel_out;
+};
+int launch_div_points(sdpcut_ctx *h, int n_points, const DivPointsArgs &A);
 // multirows.hip
 void free_multi_ws(sdpcut_ctx *h);
 // pool.hip
@@ -495,6 +534,8 @@ static inline int view_strat(uint32_t measure) { return measure == SDPCUT_EFF ? 
 
 // efficacy.hip (SDPCUT_EFF)
 int launch_efficacy(sdpcut_ctx *h);                  // d_eff / d_objpar / d_escore of every candidate at the current point; needs d_eig
+int launch_efficacy_points(sdpcut_ctx *h, int n_points, const double *d_pts, int64_t pts_stride, const double *d_eig, int64_t score_stride,
+                           double *d_eff, double *d_objpar, double *d_escore);   // the same at every point of a batch
 void free_eff_ws(sdpcut_ctx *h);
 void free_lpobj(sdpcut_ctx *h);
 

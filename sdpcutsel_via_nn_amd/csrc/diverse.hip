@@ -4,11 +4,14 @@
 //   div_prepare_kernel  one lane per pool entry: norm of its row, eligibility, its index set
 //   div_pairs_kernel    one bit per pair s < t of the pool: |<a_s, a_t>| > max_parallel |a_s| |a_t|  (lower-triangular bit matrix)
 //   div_greedy_kernel   ONE workgroup walks the pool in rank order, 64 entries at a time, accepted mask in LDS
+// and, for a batch of LP points (sdpcut_round_csr_points_diverse), the three in one kernel with a workgroup per point:
+//   div_rows_points_kernel / div_points_kernel   pools of at most 512 entries, rows, bits and sets in LDS
 // The walk is the definition of DESIGN.md section 5 "Diverse selection"; diversity.py is its numpy twin.
 #include <cstring>
 #include <new>
 
 #include "common.h"
+#include "rows_dev.h"
 
 #define DIV_MAX_POOL SDPCUT_DIVERSE_MAX_POOL
 #define DIV_WORDS (DIV_MAX_POOL / 64)
@@ -326,6 +329,227 @@ static int div_filter_enqueue(sdpcut_ctx *h, DiverseWs *w, int64_t P, int64_t id
     }
     hipLaunchKernelGGL(div_greedy_kernel, dim3(1), dim3(256), 0, h->stream, P, quota, w->elig, compare ? w->bits : nullptr, w->ids,
                        w->score, w->keep, w->acc_ids, w->acc_score, w->info);
+    HIP_TRY(h, hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// The filter over a batch of LP points (sdpcut_round_csr_points_diverse, points.hip): the same three steps, ONE workgroup per
+// point, everything between the pool's rows and the accepted head in LDS.  No workgroup reads what another writes.
+
+// Row y of the grid: the rows of the pool of point y, as cut_rows_kernel writes them (stride SDPCUT_ROW_LD, zero beyond the row's
+// length), built with the lambda_min the point's score row holds (eig NULL: the row computes it).  The pool's length is what the
+// point's selection left in its counters (k_eff; a void selection has no pool).
+__global__ __launch_bounds__(64) void div_rows_points_kernel(DivPointsArgs A)
+{
+    const int64_t p = blockIdx.y;
+    const int64_t *c4 = A.sel_c4 + p * A.c4_stride;
+    int64_t P = c4[4] ? 0 : c4[3];
+    if (P > A.pool) P = A.pool;
+    const int64_t t = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (t >= P) return;
+    const int64_t e = p * A.pool + t;
+    const int64_t c = A.idx[e] - A.idx_base;
+    double co[SDPCUT_ROW_LD];
+    int64_t cl[SDPCUT_ROW_LD];
+#pragma unroll
+    for (int m = 0; m < SDPCUT_ROW_LD; ++m) { co[m] = 0.0; cl[m] = -1; }
+    double lam = __builtin_nan(""), rhs = 0.0;
+    int k = 0;
+    if (c >= 0 && c < A.n_local) {
+        k = A.ks[c];
+        const int32_t *s5 = A.set5 + c * 5;
+        CALL_FOR_SET_SIZE(k, cut_row_one, s5, A.vars + p * A.vars_ld, A.nv, A.L, &lam, co, &rhs, cl, A.eig ? A.eig + p * A.eig_ld + c : nullptr);
+    }
+    A.row_ks[e] = k;
+    A.row_lam[e] = lam;
+#pragma unroll
+    for (int m = 0; m < SDPCUT_ROW_LD; ++m) A.row_coef[e * SDPCUT_ROW_LD + m] = co[m];
+}
+
+// Workgroup p filters the pool of point p.  (1) rows -> LDS; (2) norm, eligibility, index set of every entry as
+// div_prepare_kernel; (3) the lower-triangular pair bits as div_pairs_kernel, tile (row block, column word) by tile, the tiles dealt
+// to the eight waves in turn; (4) the walk of div_greedy_kernel, eight threads per entry over the words in front; (5) the accepted
+// entries compacted in rank order into the point's head row, the walk's counts into info[p] (the selection counters of the row
+// assembly: word 3 = accepted) and the selection's own counters to the host.  compare == 0 (max_parallel >= 1): no (3), no bit
+// is read.  LDS: rows 80 KB + bits 18 KB + sets 10 KB + norms, sizes, flags 8 KB + the walk's words.
+__global__ __launch_bounds__(DIVP_THREADS) void div_points_kernel(DivPointsArgs A)
+{
+    __shared__ double s_coef[DIVP_MAX_POOL * SDPCUT_ROW_LD];
+    __shared__ unsigned long long s_bits[32 * (DIVP_MAX_POOL / 64) * (DIVP_MAX_POOL / 64 + 1)];
+    __shared__ int32_t s_set[DIVP_MAX_POOL * 5];
+    __shared__ double s_norm[DIVP_MAX_POOL];
+    __shared__ int32_t s_k[DIVP_MAX_POOL];
+    __shared__ int32_t s_elig[DIVP_MAX_POOL];
+    __shared__ unsigned long long s_acc[DIVP_MAX_POOL / 64];
+    __shared__ unsigned long long s_diag[64];
+    __shared__ int32_t s_conf[DIVP_THREADS];
+    __shared__ unsigned long long s_word;
+    __shared__ int64_t s_cnt[4];      // accepted, examined, skipped, rejected
+    const int tid = threadIdx.x;
+    const int l = tid & 63, q = tid >> 6;
+    const int64_t p = blockIdx.x;
+    const int64_t *c4 = A.sel_c4 + p * A.c4_stride;
+    int P = c4[4] ? 0 : (int)(c4[3] < A.pool ? c4[3] : A.pool);      // (uniform)
+    if (tid < 8) A.sel_out[p * 8 + tid] = tid < 7 ? c4[tid] : 0;
+    const int64_t *ids = A.idx + p * A.pool;
+    const double *score = A.score + p * A.pool;
+    if (tid < 4) s_cnt[tid] = 0;
+    // (1), (2)
+    {
+        const double *g = A.row_coef + p * A.pool * SDPCUT_ROW_LD;
+        for (int i = tid; i < P * SDPCUT_ROW_LD; i += DIVP_THREADS) s_coef[i] = g[i];
+    }
+    __syncthreads();
+    for (int t = tid; t < DIVP_MAX_POOL; t += DIVP_THREADS) {
+        double nr = 0.0;
+        int el = 0, k = 0;
+        int64_t c = -1;
+        bool in_list = false;
+        if (t < P) {
+            k = A.row_ks[p * A.pool + t];
+            c = ids[t] - A.idx_base;
+            in_list = c >= 0 && c < A.n_local && k >= 2 && k <= SDPCUT_MAX_K;
+            double ss = 0.0;
+            {
+#pragma clang fp contract(off)
+                for (int m = 0; m < SDPCUT_ROW_LD; ++m) {
+                    const double v = s_coef[t * SDPCUT_ROW_LD + m];
+                    ss = ss + v * v;
+                }
+            }
+            nr = in_list ? sqrt(ss) : 0.0;
+            el = (in_list && A.row_lam[p * A.pool + t] < SDPCUT_NEG_EIGVAL && nr > 0.0) ? 1 : 0;
+        }
+        s_norm[t] = nr;
+        s_k[t] = k;
+        s_elig[t] = el;
+        for (int a = 0; a < 5; ++a) s_set[t * 5 + a] = (in_list && a < k) ? A.set5[c * 5 + a] : -1;
+    }
+    __syncthreads();
+    const int nblk = (P + 63) / 64;
+    // (3)
+    if (A.compare) {
+        int tile = 0;
+        for (int by = 0; by < nblk; ++by) {
+            for (int bx = 0; bx <= by; ++bx, ++tile) {
+                if ((tile & (DIVP_THREADS / 64 - 1)) != q) continue;      // (uniform in the wave)
+                const int t = by * 64 + l;
+                if (t >= P) continue;
+                unsigned long long word = 0ull;
+                if (s_elig[t]) {
+                    int32_t st[5];
+#pragma unroll
+                    for (int a = 0; a < 5; ++a) st[a] = s_set[t * 5 + a];
+                    const double *ct = s_coef + t * SDPCUT_ROW_LD;
+                    const int kt = s_k[t];
+                    const double nt = s_norm[t];
+                    const int jmax = (bx == by) ? l : 64;      // pairs s < t only
+                    for (int j = 0; j < jmax; ++j) {
+                        const int s = bx * 64 + j;
+                        if (!s_elig[s]) continue;
+                        const int kj = s_k[s];
+                        int m[5];
+                        bool any = false;
+#pragma unroll
+                        for (int a = 0; a < 5; ++a) {
+                            m[a] = -1;
+#pragma unroll
+                            for (int b = 0; b < 5; ++b)
+                                if (st[a] >= 0 && s_set[s * 5 + b] == st[a]) m[a] = b;
+                            any = any || m[a] >= 0;
+                        }
+                        if (!any) continue;
+                        const double dot = div_dot(ct, kt, s_coef + s * SDPCUT_ROW_LD, kj, m);
+                        bool hit;
+                        {
+#pragma clang fp contract(off)
+                            hit = fabs(dot) > A.max_parallel * s_norm[s] * nt;
+                        }
+                        if (hit) word |= 1ull << j;
+                    }
+                }
+                s_bits[div_bits_offset(t) + bx] = word;
+            }
+        }
+    }
+    __syncthreads();
+    // (4), (5)
+    int64_t *acc_ids = A.acc_idx + p * A.cap;
+    double *acc_score = A.acc_score + p * A.cap;
+    for (int b = 0; b < nblk; ++b) {
+        const int t = b * 64 + l;
+        const bool live = t < P;
+        int conf = 0;
+        if (A.compare && live && s_elig[t]) {
+            const unsigned long long *row = s_bits + div_bits_offset(t);
+            for (int w = q; w < b; w += DIVP_THREADS / 64) {
+                const unsigned long long a = s_acc[w];
+                if (a && (row[w] & a)) conf = 1;
+            }
+            if (q == 0) s_diag[l] = row[b];
+        } else if (q == 0) {
+            s_diag[l] = 0ull;
+        }
+        s_conf[tid] = conf;
+        __syncthreads();
+        if (q == 0) {
+            int cf = 0;
+#pragma unroll
+            for (int w = 0; w < DIVP_THREADS / 64; ++w) cf |= s_conf[w * 64 + l];
+            const bool el = live && s_elig[t];
+            const bool ok = el && !cf;
+            const unsigned long long d = s_diag[l];
+            unsigned long long acc = 0ull;
+            int64_t n_acc = s_cnt[0];
+            const int nlive = (P - b * 64 < 64) ? (P - b * 64) : 64;
+            int j = 0;
+            for (; j < nlive && n_acc < A.quota; ++j) {
+                const unsigned long long m = __ballot(ok && !(d & acc));
+                if ((m >> j) & 1ull) { acc |= 1ull << j; ++n_acc; }
+            }
+            // (the walk ends WITH the entry that fills the quota: what follows it in the block was not examined)
+            const unsigned long long seen = j >= 64 ? ~0ull : ((1ull << j) - 1ull);
+            const unsigned long long elm = __ballot(el);
+            if (l == 0) {
+                s_word = acc;
+                s_acc[b] = acc;
+                s_cnt[1] += j;
+                s_cnt[2] += __popcll(~elm & seen);
+                s_cnt[3] += __popcll(elm & seen & ~acc);
+            }
+        }
+        __syncthreads();
+        const unsigned long long acc = s_word;
+        const int64_t base = s_cnt[0];
+        if (q == 0 && live && ((acc >> l) & 1ull)) {
+            const int64_t pos = base + __popcll(acc & ((1ull << l) - 1ull));
+            acc_ids[pos] = ids[t];
+            acc_score[pos] = score[t];
+        }
+        __syncthreads();
+        if (tid == 0) s_cnt[0] = base + __popcll(acc);
+        __syncthreads();
+        if (s_cnt[0] >= A.quota) break;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int64_t *info = A.info + p * 8;
+        info[0] = s_cnt[1];
+        info[1] = s_cnt[2];
+        info[2] = s_cnt[3];
+        info[3] = s_cnt[0];
+        info[4] = info[5] = info[6] = info[7] = 0;
+    }
+}
+
+int launch_div_points(sdpcut_ctx *h, int n_points, const DivPointsArgs &A)
+{
+    if (n_points <= 0) return 0;
+    if (A.pool < 1 || A.pool > DIVP_MAX_POOL || A.cap < 1 || A.cap > A.pool) return sdpcut_fail(h, SDPCUT_EINVAL, "div_points: pool out of range");
+    hipLaunchKernelGGL(div_rows_points_kernel, dim3((unsigned)((A.pool + 63) / 64), (unsigned)n_points), dim3(64), 0, h->stream, A);
+    HIP_TRY(h, hipGetLastError());
+    hipLaunchKernelGGL(div_points_kernel, dim3((unsigned)n_points), dim3(DIVP_THREADS), 0, h->stream, A);
     HIP_TRY(h, hipGetLastError());
     return 0;
 }

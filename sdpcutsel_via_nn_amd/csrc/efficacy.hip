@@ -34,14 +34,12 @@ __device__ __forceinline__ void eff_row_one(const int32_t *s5, const double *var
     }
 }
 
-// A workgroup is one wave.  Lanes that are not violated leave before the eigenvector; a wave without a violated lane branches over
-// the whole row computation (the `if (viol)` below is a branch on EXEC == 0).
-__global__ __launch_bounds__(64) void efficacy_kernel(int64_t n, const int32_t *set5, const int32_t *ks, const double *vars, int32_t nv,
-                                                      int64_t L, const double *eig, const double *lpobj, double obj_norm, double w,
-                                                      double *eff, double *objpar, double *escore)
+// Candidate i at one LP point: lanes that are not violated leave before the eigenvector; a wave without a violated lane branches
+// over the whole row computation (the `if (viol)` below is a branch on EXEC == 0).  The body of both kernels below.
+__device__ __forceinline__ void efficacy_one(int64_t i, const int32_t *set5, const int32_t *ks, const double *vars, int32_t nv, int64_t L,
+                                             const double *eig, const double *lpobj, double obj_norm, double w, double *eff, double *objpar,
+                                             double *escore)
 {
-    const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
-    if (i >= n) return;
     const double lam = eig[i];
     const double neg = -lam;
     // min(-lam, +0.0) with +0 for lam = 0 (the twin's bits).  Chosen among bit patterns: written as a floating-point select it
@@ -66,6 +64,30 @@ __global__ __launch_bounds__(64) void efficacy_kernel(int64_t n, const int32_t *
     eff[i] = e;
     objpar[i] = p;
     escore[i] = sc;
+}
+
+// A workgroup is one wave.
+__global__ __launch_bounds__(64) void efficacy_kernel(int64_t n, const int32_t *set5, const int32_t *ks, const double *vars, int32_t nv,
+                                                      int64_t L, const double *eig, const double *lpobj, double obj_norm, double w,
+                                                      double *eff, double *objpar, double *escore)
+{
+    const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    efficacy_one(i, set5, ks, vars, nv, L, eig, lpobj, obj_norm, w, eff, objpar, escore);
+}
+
+// The same with a point axis (sdpcut_efficacy_points, the batched strategy-6 round; points.hip): row blockIdx.y of the grid is LP
+// point blockIdx.y -- its row of the point table (stride vars_ld), of the lambda_min array and of the three outputs (stride score_ld).
+__global__ __launch_bounds__(64) void efficacy_points_kernel(int64_t n, const int32_t *set5, const int32_t *ks, const double *vars,
+                                                             int64_t vars_ld, int32_t nv, int64_t L, const double *eig, int64_t score_ld,
+                                                             const double *lpobj, double obj_norm, double w, double *eff, double *objpar,
+                                                             double *escore)
+{
+    const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const int64_t p = blockIdx.y;
+    efficacy_one(i, set5, ks, vars + p * vars_ld, nv, L, eig + p * score_ld, lpobj, obj_norm, w, eff + p * score_ld, objpar + p * score_ld,
+                 escore + p * score_ld);
 }
 
 void free_eff_ws(sdpcut_ctx *h)
@@ -97,6 +119,19 @@ int launch_efficacy(sdpcut_ctx *h)
     // the ORIGINAL point: like lambda_min and the rows this measure knows no node box
     hipLaunchKernelGGL(efficacy_kernel, dim3(grid), dim3(64), 0, h->stream, h->N, h->d_set_orig, h->d_k, score_vars(h, SDPCUT_EFF), h->nb_vars,
                        h->L, h->d_eig, (const double *)h->d_lpobj, h->lpobj_norm, h->eff_w, h->d_eff, h->d_objpar, h->d_escore);
+    HIP_TRY(h, hipGetLastError());
+    return 0;
+}
+
+// eff / objpar / escore of every candidate at n_points points: rows of d_pts (stride pts_stride), lambda_min in rows of d_eig, the
+// outputs in rows of the three arrays (all with stride score_stride); objective and weight are the handle's
+int launch_efficacy_points(sdpcut_ctx *h, int n_points, const double *d_pts, int64_t pts_stride, const double *d_eig, int64_t score_stride,
+                           double *d_eff, double *d_objpar, double *d_escore)
+{
+    if (h->N == 0 || n_points <= 0) return 0;
+    const unsigned grid = (unsigned)((h->N + 63) / 64);
+    hipLaunchKernelGGL(efficacy_points_kernel, dim3(grid, (unsigned)n_points), dim3(64), 0, h->stream, h->N, h->d_set_orig, h->d_k, d_pts, pts_stride,
+                       h->nb_vars, h->L, d_eig, score_stride, (const double *)h->d_lpobj, h->lpobj_norm, h->eff_w, d_eff, d_objpar, d_escore);
     HIP_TRY(h, hipGetLastError());
     return 0;
 }

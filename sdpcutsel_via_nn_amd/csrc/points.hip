@@ -16,6 +16,12 @@
 //   strong_points_kernel      combined strategy: neither launch saw both measures, so the strong class is counted here
 // and the selection and the assembly run as they are -- they read scores, heads and the original points, never Q.  The split is
 // the one launch_score makes for a single point with a box (score.hip); still ONE host wait.
+// The filtered batch (sdpcut_round_csr_points_diverse; strategies 1, 2, 4 and 6) is the same chain with a longer head and a filter:
+//   efficacy_points_kernel    (efficacy.hip) strategy 6: the efficacy score of every point, behind the eigenvalue launch
+//   tk_points_kernel          k = the pool, the quota as `sel`
+//   div_rows_points_kernel, div_points_kernel   (diverse.hip) the pool's rows, then one workgroup per point filters its pool in LDS
+//   round_csr_points_kernel   over the accepted heads, their lengths read from the walk's counts
+// and sdpcut_efficacy_points is the eigenvalue launch and the efficacy launch alone.
 #include <cstring>
 #include <vector>
 
@@ -98,6 +104,8 @@ void free_points_ws(sdpcut_ctx *h)
     (void)hipFree(b.d_pts); (void)hipFree(b.d_eig); (void)hipFree(b.d_obj); (void)hipFree(b.d_ws); (void)hipFree(b.d_idx);
     (void)hipFree(b.d_score); (void)hipFree(b.d_agg);
     (void)hipFree(b.d_box_ld); (void)hipFree(b.d_Q_box); (void)hipFree(b.d_vars_box);
+    (void)hipFree(b.d_eff); (void)hipFree(b.d_div);
+    if (b.div_sel) (void)hipHostFree(b.div_sel);
     b = PointsBufs();
 }
 
@@ -482,7 +490,285 @@ static int round_csr_points_impl(sdpcut_ctx *h, const char *what, int32_t n_poin
     return SDPCUT_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// Efficacy and the filtered round over a batch (sdpcut_efficacy_points, sdpcut_round_csr_points_diverse)
+
+static int ensure_points_eff(sdpcut_ctx *h, int P)
+{
+    PointsBufs &b = h->pts;
+    const size_t doubles = 3 * (size_t)P * (size_t)h->N;
+    if (b.eff_doubles >= doubles) return 0;
+    (void)hipFree(b.d_eff);
+    b.d_eff = nullptr;
+    b.eff_doubles = 0;
+    HIP_TRY(h, hipMalloc((void **)&b.d_eff, doubles * 8));
+    b.eff_doubles = doubles;
+    return 0;
+}
+
+static_assert(DIVP_MAX_POOL == BATCH_DIVERSE_MAX_POOL && BATCH_DIVERSE_MAX_POOL <= TK_TILE, "the route's pool limit is the filter kernel's and fits a head of the selection");
+
+// where the filter's arrays of a batch of P points lie inside pts.d_div
+struct DivPointsLayout { size_t coef, lam, ks, info, acc_idx, acc_score, bytes; };
+static DivPointsLayout div_points_layout(int P, int64_t pool, int64_t cap)
+{
+    DivPointsLayout y;
+    const size_t e = (size_t)P * (size_t)pool, a = (size_t)P * (size_t)cap;
+    size_t o = 0;
+    y.coef = o; o += e * SDPCUT_ROW_LD * 8;
+    y.lam = o; o += e * 8;
+    y.ks = o; o += (e * 4 + 7) & ~(size_t)7;
+    y.info = o; o += (size_t)P * 64;
+    y.acc_idx = o; o += a * 8;
+    y.acc_score = o; o += a * 8;
+    y.bytes = o;
+    return y;
+}
+
+static int ensure_points_div(sdpcut_ctx *h, int P, size_t bytes)
+{
+    PointsBufs &b = h->pts;
+    if (b.div_bytes < bytes) {
+        (void)hipFree(b.d_div);
+        b.d_div = nullptr;
+        b.div_bytes = 0;
+        HIP_TRY(h, hipMalloc(&b.d_div, bytes));
+        // (the row assembly reads an accepted head up to its capacity and uses its length only: never uninitialised memory)
+        HIP_TRY(h, hipMemsetAsync(b.d_div, 0, bytes, h->stream));
+        b.div_bytes = bytes;
+    }
+    if (b.div_sel_points < P) {
+        HIP_TRY(h, sdpcut_sync(h));
+        if (b.div_sel) (void)hipHostFree(b.div_sel);
+        b.div_sel = b.div_sel_dev = nullptr;
+        b.div_sel_points = 0;
+        HIP_TRY(h, hipHostMalloc(&b.div_sel, (size_t)P * 64, hipHostMallocMapped));
+        HIP_TRY(h, hipHostGetDevicePointer(&b.div_sel_dev, b.div_sel, 0));
+        b.div_sel_points = P;
+    }
+    return 0;
+}
+
+// A block of csr_layout(from, ld) with n_out entries, n_rows rows and nnz non-zeros in use becomes one of csr_layout(to, ld), to <
+// from, in place: every array moves towards the header, in the order they lie in.
+static void csr_block_shrink(char *block, int64_t from, int64_t to, int ld, int64_t n_out, int64_t n_rows, int64_t nnz)
+{
+    const CsrLayout a = csr_layout(from, ld), z = csr_layout(to, ld);
+    const size_t w = (size_t)n_out, r = (size_t)n_rows, nz = (size_t)nnz;
+    std::memmove(block + z.idx, block + a.idx, w * 8);
+    std::memmove(block + z.score, block + a.score, w * 8);
+    std::memmove(block + z.lam, block + a.lam, w * 8);
+    std::memmove(block + z.rhs, block + a.rhs, r * 8);
+    std::memmove(block + z.values, block + a.values, nz * 8);
+    std::memmove(block + z.ks, block + a.ks, w * 4);
+    std::memmove(block + z.sets, block + a.sets, w * 20);
+    std::memmove(block + z.row_entry, block + a.row_entry, r * 4);
+    std::memmove(block + z.indptr, block + a.indptr, (r + 1) * 4);
+    std::memmove(block + z.indices, block + a.indices, nz * 4);
+}
+
+static int efficacy_points_impl(sdpcut_ctx *h, int32_t n_points, const double *points, int64_t point_ld, double *eff_out, double *objpar_out,
+                                double *escore_out)
+{
+    int rc = check_points_args(h, n_points, points, point_ld);
+    if (rc) return rc;
+    if (!eff_out && !objpar_out && !escore_out) return sdpcut_fail(h, SDPCUT_EINVAL, "sdpcut_efficacy_points: every output array is NULL");
+    SDPCUT_NO_PENDING(h);
+    SDPCUT_NO_BOX(h, "sdpcut_efficacy_points");
+    HIP_TRY(h, hipSetDevice(h->device));
+    NoPointAfter leave(h);
+    const int P = n_points;
+    const size_t N = (size_t)h->N;
+    if (!score_points_served(h, SDPCUT_EIG)) {      // a kernel variant without a point axis: point by point
+        for (int p = 0; p < P; ++p) {
+            if ((rc = sdpcut_set_point(h, points + (size_t)p * point_ld))) return rc;
+            if ((rc = sdpcut_score(h, SDPCUT_EIG | SDPCUT_EFF))) return rc;
+            if ((rc = sdpcut_get_efficacy(h, eff_out ? eff_out + p * N : nullptr, objpar_out ? objpar_out + p * N : nullptr,
+                                          escore_out ? escore_out + p * N : nullptr)))
+                return rc;
+        }
+        return SDPCUT_OK;
+    }
+    if ((rc = ensure_points_scores(h, P))) return rc;
+    if ((rc = ensure_points_eff(h, P))) return rc;
+    if ((rc = upload_points(h, P, points, point_ld, nullptr))) return rc;
+    PointsBufs &b = h->pts;
+    const int64_t n = h->L + h->nb_vars;
+    if ((rc = score_batch(h, SDPCUT_EIG, P, false, nullptr, 0))) return rc;
+    double *d_e = b.d_eff, *d_p = d_e + (size_t)P * N, *d_s = d_p + (size_t)P * N;
+    if ((rc = launch_efficacy_points(h, P, b.d_pts, n, b.d_eig, h->N, d_e, d_p, d_s))) return rc;
+    if (eff_out) HIP_TRY(h, hipMemcpyAsync(eff_out, d_e, (size_t)P * N * 8, hipMemcpyDeviceToHost, h->stream));
+    if (objpar_out) HIP_TRY(h, hipMemcpyAsync(objpar_out, d_p, (size_t)P * N * 8, hipMemcpyDeviceToHost, h->stream));
+    if (escore_out) HIP_TRY(h, hipMemcpyAsync(escore_out, d_s, (size_t)P * N * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, sdpcut_sync(h));
+    return SDPCUT_OK;
+}
+
+static int round_csr_points_diverse_impl(sdpcut_ctx *h, int32_t n_points, const double *points, int64_t point_ld, const BoxRows *bx, int strat,
+                                         int64_t sel_size, int64_t pool_size, double max_parallel, sdpcut_round_csr_t *out,
+                                         sdpcut_diverse_info_t *info)
+{
+    const char *what = "sdpcut_round_csr_points_diverse";
+    if (!out) return sdpcut_fail(h, SDPCUT_EINVAL, "out is NULL");
+    int rc = check_points_args(h, n_points, points, point_ld);
+    if (rc) return rc;
+    if (!batch_mode_diverse(strat))
+        return sdpcut_fail(h, SDPCUT_EINVAL, std::string(what) + " serves strategies 1 (feasibility), 2 (optimality), 4 (combined) and 6 (efficacy)");
+    if (!(max_parallel >= 0.0 && max_parallel <= 1.0)) return sdpcut_fail(h, SDPCUT_EINVAL, "max_parallel must lie in [0, 1]");
+    if (sel_size < 1) return sdpcut_fail(h, SDPCUT_EINVAL, "sel_size must be >= 1");
+    if (pool_size < sel_size) return sdpcut_fail(h, SDPCUT_EINVAL, "pool_size must be >= sel_size");
+    if (pool_size > SDPCUT_DIVERSE_MAX_POOL) return sdpcut_fail(h, SDPCUT_EINVAL, "pool_size must not exceed SDPCUT_DIVERSE_MAX_POOL");
+    SDPCUT_NO_PENDING(h);
+    SDPCUT_NO_BOX(h, what);
+    if (bx && (rc = check_box_rows(h, what, n_points, *bx))) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    NoPointAfter leave(h);
+    NoBoxAfter unboxed(h);
+    const int P = n_points;
+    std::memset(out, 0, (size_t)P * sizeof(*out));
+    if (info) std::memset(info, 0, (size_t)P * sizeof(*info));
+    const bool by_eff = strat == SDPCUT_STRAT_EFF;
+    const int64_t pool = pool_size < h->N ? pool_size : h->N;
+    const int64_t cap = sel_size < pool ? sel_size : pool;
+    const int ld = h->row_len_max;
+    const uint32_t need = by_eff ? (uint32_t)SDPCUT_EIG : strat_need(strat);      // what score_batch computes; the efficacy launch follows it
+    const bool shard = h->base != 0 || h->shard_rec != nullptr;
+    int route = bx ? batch_route_diverse_boxed(h->N, sel_size, pool_size, strat, h->exact_head, shard, h->nb_vars, P)
+                   : batch_route_diverse(h->N, sel_size, pool_size, strat, h->exact_head, shard);
+    const BoxRows *bx_dev = (need & SDPCUT_NN) ? bx : nullptr;
+    if (route == BATCH_FAST && (!batch_score_served(h, need, bx_dev != nullptr) || (strat == SDPCUT_STRAT_COMB && !h->auto_regime) || h->timing))
+        route = BATCH_LOOP;
+    const BatchLayout y = batch_layout(cap, ld, P);
+    if ((rc = ensure_points_block(h, y.bytes))) return rc;
+    char *block = (char *)h->pts.pinned;
+    // one point through the single-point filtered round, in its box where the batch has boxes
+    auto single = [&](int p) -> int {
+        int rc1;
+        if (bx && (rc1 = sdpcut_set_box(h, bx->lb + (size_t)p * bx->ld, bx->ub + (size_t)p * bx->ld))) return rc1;
+        sdpcut_round_csr_t *o = out + p;
+        rc1 = sdpcut_round_csr_diverse(h, points + (size_t)p * point_ld, strat, sel_size, pool_size, max_parallel, o, info ? info + p : nullptr);
+        if (rc1) return rc1;
+        if (o->cap > 0 && o->idx) {
+            char *slot = block + batch_point_offset(y, p);
+            std::memcpy(slot, h->pinned, csr_layout(o->cap, o->row_ld).bytes);
+            csr_out_from_block(slot, o);
+        }
+        return SDPCUT_OK;
+    };
+    if (route == BATCH_LOOP) {
+        for (int p = 0; p < P; ++p)
+            if ((rc = single(p))) return rc;
+        return SDPCUT_OK;
+    }
+
+    const DivPointsLayout dy = div_points_layout(P, pool, cap);
+    if ((rc = ensure_points_scores(h, P))) return rc;
+    if ((rc = ensure_points_select(h, P, pool))) return rc;
+    if ((rc = ensure_points_div(h, P, dy.bytes))) return rc;
+    if (by_eff && (rc = ensure_points_eff(h, P))) return rc;
+    PointsBufs &b = h->pts;
+    TopkWs *ws = (TopkWs *)b.d_ws;
+    const int64_t ws_words = (int64_t)(sizeof(TopkWs) / 8), n = h->L + h->nb_vars;
+    if ((rc = upload_points(h, P, points, point_ld, ws, bx_dev))) return rc;
+    int64_t *strong = need == (SDPCUT_EIG | SDPCUT_NN) ? ws->strong_rep : nullptr;
+    if ((rc = score_batch(h, need, P, bx_dev != nullptr, strong, ws_words))) return rc;
+    const double *eig = (need & SDPCUT_EIG) ? b.d_eig : nullptr, *obj = (need & SDPCUT_NN) ? b.d_obj : nullptr;
+    if (by_eff) {      // strategy 2 on the efficacy score, as the single-point ranking runs it (common.h: MeasureAsObj)
+        double *d_e = b.d_eff, *d_p = d_e + (size_t)P * (size_t)h->N, *d_s = d_p + (size_t)P * (size_t)h->N;
+        if ((rc = launch_efficacy_points(h, P, b.d_pts, n, b.d_eig, h->N, d_e, d_p, d_s))) return rc;
+        obj = d_s;
+    }
+    const int64_t sel = sel_size < h->N ? sel_size : h->N;
+    hipLaunchKernelGGL(tk_points_kernel, dim3((unsigned)P), dim3(TK_SMALLSEL_THREADS), 0, h->stream, batch_mode_diverse(strat), sel, (int)h->N, (int)pool,
+                       eig, obj, h->N, ws, strat == SDPCUT_STRAT_COMB ? SDPCUT_BIG_M : 0.0, b.d_idx, b.d_score);
+    HIP_TRY(h, hipGetLastError());
+    char *dv = (char *)b.d_div;
+    DivPointsArgs A;
+    A.pool = pool; A.cap = cap; A.quota = sel_size; A.max_parallel = max_parallel; A.compare = max_parallel < 1.0 ? 1 : 0;
+    A.sel_c4 = ws->counters; A.c4_stride = ws_words; A.idx = b.d_idx; A.score = b.d_score; A.idx_base = h->base; A.n_local = h->N;
+    A.set5 = h->d_set_orig; A.ks = h->d_k; A.vars = b.d_pts; A.vars_ld = n; A.nv = h->nb_vars; A.L = h->L; A.eig = eig; A.eig_ld = h->N;
+    A.row_coef = (double *)(dv + dy.coef); A.row_lam = (double *)(dv + dy.lam); A.row_ks = (int32_t *)(dv + dy.ks);
+    A.acc_idx = (int64_t *)(dv + dy.acc_idx); A.acc_score = (double *)(dv + dy.acc_score); A.info = (int64_t *)(dv + dy.info);
+    A.sel_out = (int64_t *)b.div_sel_dev;
+    if ((rc = launch_div_points(h, P, A))) return rc;
+    for (int p = 0; p < P; ++p) std::memset(block + batch_point_offset(y, p), 0, 128);
+    // the accepted entries are a head like any other: the assembly reads its length from word 3 of the point's walk counts and
+    // copies them into the slice's header
+    auto assemble = [&](int p_first, int count) -> int {
+        return launch_round_csr_points(h, p_first, count, cap, ld, A.info, 8, A.acc_idx, A.acc_score, b.d_pts, n, eig, h->N, b.d_agg, BATCH_AGG_WORDS,
+                                       b.pinned_dev, (int64_t)y.slice, ++h->round_serial);
+    };
+    if ((rc = assemble(0, P))) return rc;
+    HIP_TRY(h, sdpcut_sync(h));      // the one wait of the batch
+
+    std::vector<int> redo, again;
+    const int64_t *selc = (const int64_t *)b.div_sel;
+    for (int p = 0; p < P; ++p) {
+        const int64_t *hdr = (const int64_t *)(block + batch_point_offset(y, p));
+        sdpcut_round_csr_t &o = out[p];
+        int64_t n_pool = 0;
+        o.row_ld = ld;
+        if (!rank_fast_finish(h, by_eff ? SDPCUT_STRAT_OPT : strat, sel_size, pool, selc + 8 * p, &n_pool, &o.n_total, &o.new_strat, o.counters)) {
+            redo.push_back(p);      // a void selection: the single-point call resolves it
+            continue;
+        }
+        if (by_eff) o.new_strat = SDPCUT_STRAT_EFF;
+        if (info) info[p].pool = n_pool;
+        if (n_pool <= 0) continue;      // an empty ranking: an empty block
+        ++h->stat_rounds;
+        if (info) { info[p].examined = hdr[0]; info[p].skipped_nonviolated = hdr[1]; info[p].rejected_parallel = hdr[2]; }
+        o.cap = sel_size < n_pool ? sel_size : n_pool;
+        o.n_out = hdr[3];
+        if (hdr[10] && o.n_out > 0) again.push_back(p);
+    }
+    for (int p : again) {
+        int64_t *hdr = (int64_t *)(block + batch_point_offset(y, p));
+        hdr[8] = hdr[9] = hdr[10] = 0;
+        ++h->stat_fallbacks;
+        if ((rc = assemble(p, 1))) return rc;
+    }
+    if (!again.empty()) {
+        HIP_TRY(h, sdpcut_sync(h));
+        for (int p : again)
+            if (((const int64_t *)(block + batch_point_offset(y, p)))[10])
+                return sdpcut_fail(h, SDPCUT_EHIP, "round_csr_points_diverse: look-back of the row assembly timed out twice");
+    }
+    for (int p = 0; p < P; ++p) {
+        sdpcut_round_csr_t &o = out[p];
+        if (o.cap <= 0) continue;
+        char *slot = block + batch_point_offset(y, p);
+        const int64_t *hdr = (const int64_t *)slot;
+        // (a ranking shorter than sel_size -- few violated candidates under strategy 1 -- has the block of its own length)
+        if (o.cap < cap) csr_block_shrink(slot, cap, o.cap, ld, o.n_out, o.n_out > 0 ? hdr[8] : 0, o.n_out > 0 ? hdr[9] : 0);
+        csr_out_from_block(slot, &o);
+    }
+    h->stat_diverse_points_fast += P - (int64_t)redo.size();
+    for (int p : redo) {
+        ++h->stat_points_redone;
+        std::memset(out + p, 0, sizeof(*out));
+        if (info) std::memset(info + p, 0, sizeof(*info));
+        if ((rc = single(p))) return rc;
+    }
+    return SDPCUT_OK;
+}
+
 extern "C" {
+
+int sdpcut_efficacy_points(sdpcut_handle h, int32_t n_points, const double *points, int64_t point_ld, double *eff_out, double *objpar_out,
+                           double *escore_out)
+{
+    if (!h) return SDPCUT_EINVAL;
+    return efficacy_points_impl(h, n_points, points, point_ld, eff_out, objpar_out, escore_out);
+}
+
+int sdpcut_round_csr_points_diverse(sdpcut_handle h, int32_t n_points, const double *points, int64_t point_ld, const double *lb, const double *ub,
+                                    int64_t box_ld, int strat, int64_t sel_size, int64_t pool_size, double max_parallel, sdpcut_round_csr_t *out,
+                                    sdpcut_diverse_info_t *info)
+{
+    if (!h) return SDPCUT_EINVAL;
+    const BoxRows bx = {lb, ub, box_ld};
+    return round_csr_points_diverse_impl(h, n_points, points, point_ld, (lb || ub) ? &bx : nullptr, strat, sel_size, pool_size, max_parallel, out, info);
+}
 
 int sdpcut_score_points(sdpcut_handle h, int32_t n_points, const double *points, int64_t point_ld, uint32_t flags, double *eig_out,
                         double *obj_out)

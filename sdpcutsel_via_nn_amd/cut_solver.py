@@ -521,7 +521,7 @@ class GpuCutSelectionMixin(object):
     # the reference's loop reaches it through the name-mangled private name (cut_select_qp.py:166)
     _CutSolver__gen_dense_eigcuts = _gen_dense_eigcuts
 
-    def separate_points(self, strat, points, sel_size, boxes=None):
+    def separate_points(self, strat, points, sel_size, boxes=None, max_parallel=None, pool_factor=4):
         """One separation round at EACH of several LP points of the bound instance in one device call (sdpcut_round_csr_points):
         the open nodes of a tree search, the children of a dive.  points [P, L + n]; strat 1, 2 or 4; sel_size as
         ``_sel_eigcut_by_ordering_on_measure`` takes it (a number of cuts).
@@ -533,9 +533,22 @@ class GpuCutSelectionMixin(object):
         the single-point round at ``points[p]`` give.  Still one device call (sdpcut_round_csr_points_boxed: every point's tables
         in its own box by one launch, one host wait for the batch -- DESIGN.md section 5 "Batched points"); the arrays are copies,
         and the solver's own node box (:meth:`set_node_box`), which the call cannot coexist with, is taken off the scorer before
-        it and is in place again afterwards."""
+        it and is in place again afterwards.
+        ``max_parallel`` (None: the plain round above, unchanged): every point's round goes through the parallelism filter of
+        :meth:`Scorer.round_csr_diverse` on a pool of ``min(pool_factor * sel_size, 16384)`` ranked candidates, still in one device
+        call (sdpcut_round_csr_points_diverse); strat 1, 2, 4 or 6 (6 ranks by the efficacy score with the scorer's objective and
+        weight).  Same hand-over form."""
         b = self._gpu_bind()
         b.drain()
+        if max_parallel is not None:
+            pool = int(min(max(int(pool_factor * int(sel_size)), int(sel_size)), _capi.DIVERSE_MAX_POOL))
+            _capi.check_diverse_args(max_parallel, sel_size, pool, strat)
+
+            def rounds_of(pts, copy, bx=None):
+                return b.scorer.round_csr_points_diverse(pts, strat, sel_size, max_parallel, pool_size=pool, copy=copy, boxes=bx)
+        else:
+            def rounds_of(pts, copy, bx=None):
+                return b.scorer.round_csr_points(pts, strat, sel_size, copy=copy, boxes=bx)
         if boxes is not None:
             pts = np.asarray(points, dtype=np.float64)
             bx = np.asarray(boxes, dtype=np.float64)
@@ -543,12 +556,12 @@ class GpuCutSelectionMixin(object):
                 raise ValueError("boxes must be [P, 2, n]: (lb, ub) per point")
             try:
                 b.scorer.clear_box()
-                rounds = b.scorer.round_csr_points(pts, strat, sel_size, copy=True, boxes=bx)
+                rounds = rounds_of(pts, True, bx)
             finally:
                 b.point_copy, b.scored, b.point_token = None, 0, None
                 self._gpu_apply_box(b, self._gpu_node_box)
             return [((r["indptr"], r["indices"], r["values"], r["rhs"]), r["n_total"], r["new_strat"], r["counters"]) for r in rounds]
-        rounds = b.scorer.round_csr_points(points, strat, sel_size)
+        rounds = rounds_of(points, False)
         b.point_copy, b.scored, b.point_token = None, 0, None      # (the next single-point selection uploads its point)
         return [((r["indptr"], r["indices"], r["values"], r["rhs"]), r["n_total"], r["new_strat"], r["counters"]) for r in rounds]
 

@@ -16,10 +16,19 @@ existed.  Lists: the dim-3 covers of spar020-100-1 and spar040-030-1; P in {8, 6
 box).  Boxes: per variable a seeded interval of width 0.05 .. 1 inside [0, 1]; points: McCormick-feasible points of the unit box
 carried into the box (nodebox.inverse_tables).
 
-usage: tools/batch_points.py [--boxes] [--repeats R] [--calls C] [--loop-only] [--out [FILE]]
+--diverse: the filtered round (max_parallel 0.5, sel 100, pool 400; strategies 1, 4 and 6) over P in {8, 64, 256} points of the dim-3
+covers of spar020-100-1 and spar040-030-1, without and with a box per point.  batched = round_csr_points_diverse(P points[, boxes=]),
+loop = P x ([set_box,] round_csr_diverse(point p)) on the same handle.  Strategy 4 with sel < pool is served by the loop inside the
+call (csrc/batch_route.h); a further row times it with sel = pool = 400, where it takes the one-wait route.  Behind each list: the
+plain round_csr_points at P = 64 and sel 100, the price of the filter; --plain-only times that alone, and --root DIR takes the
+package from another checkout (the parent commit's, built), so that the same tool gives the value before and after a change.
+
+usage: tools/batch_points.py [--boxes | --diverse] [--repeats R] [--calls C] [--loop-only] [--plain-only] [--root DIR] [--out [FILE]]
   --boxes       the boxed batch against the loop of set_box + single-point rounds
+  --diverse     the filtered batch against the loop of single-point filtered rounds (default --repeats 5)
   --loop-only   time the single-point loop only (runs on a library without the batched entry points: the parent commit's)
-  --out         also write the table to FILE (default profiles/batch_points.txt; with --boxes profiles/boxed_points.txt)"""
+  --out         also write the table to FILE (default profiles/batch_points.txt; with --boxes profiles/boxed_points.txt; with
+                --diverse profiles/diverse_points.txt)"""
 import argparse
 import gc
 import os
@@ -29,7 +38,8 @@ import time
 import numpy as np
 
 ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-sys.path.insert(0, ROOT)
+PKG_ROOT = os.path.abspath(sys.argv[sys.argv.index("--root") + 1]) if "--root" in sys.argv[1:-1] else ROOT
+sys.path.insert(0, PKG_ROOT)
 import sdpcutsel_via_nn_amd as pkg  # noqa: E402
 from sdpcutsel_via_nn_amd import _capi, harness, networks, nodebox  # noqa: E402
 
@@ -55,16 +65,107 @@ def timed(fn, calls):
     return (time.perf_counter() - t0) / calls
 
 
+def median_cell(times, P):
+    a = np.array(times) * 1e3
+    return "%8.4f (%7.4f .. %7.4f) %8.2f" % (np.median(a), a.min(), a.max(), np.median(a) * 1e3 / P)
+
+
+def diverse_main(args):
+    """--diverse / --plain-only: see the module's docstring"""
+    sel, pool, mp = 100, 400, 0.5
+    lines = ["# tools/batch_points.py --diverse%s --repeats %d: ms per call, us per point; median over the blocks (min .. max)"
+             % (" --plain-only" if args.plain_only else "", args.repeats),
+             "# batched = round_csr_points_diverse(P points[, boxes=]); loop = P x ([set_box,] round_csr_diverse(point=p)); sel %d, pool %d, "
+             "max_parallel %.1f" % (sel, pool, mp),
+             "# package: %s" % ("this checkout" if PKG_ROOT == ROOT else "another checkout (--root)")]
+    for title, fname, dim in BOXED_LISTS:
+        inst = harness.parse_boxqp(os.path.join(INST, fname))
+        S, ks, N = _capi.enumerate_cover(inst["adj"], dim)
+        n = inst["nb_vars"]
+        sc = pkg.Scorer(0)
+        for k in (2, 3, 4, 5):
+            sc.set_network(k, *networks.load_network(k))
+        sc.set_instance(n, inst["Q_arr"])
+        sc.set_candidates(S, ks)
+        pts_all = np.stack([harness.random_mccormick_point(n, np.random.default_rng(100 + i)) for i in range(max(BOXED_POINTS))])
+        boxes_all = np.stack([seeded_box(n, i) for i in range(max(BOXED_POINTS))])
+        bpts_all = np.stack([nodebox.inverse_tables(None, pts_all[i], boxes_all[i, 0], boxes_all[i, 1])[1] for i in range(max(BOXED_POINTS))])
+        lines.append("")
+        lines.append("%s: %d candidates" % (title, N))
+        if not args.plain_only:
+            sc.set_objective(np.concatenate([np.asarray(inst["Q_arr"], dtype=np.float64), np.asarray(inst["c"], dtype=np.float64)]))
+            sc.set_efficacy_weight(0.1)
+            lines.append("  strat  sel boxed    P | batched ms/call          us/point | loop ms/call             us/point | loop / batched | one-wait points")
+            for strat, q in ((1, sel), (4, sel), (4, pool), (6, sel)):
+                for boxed in (False, True):
+                    for P in BOXED_POINTS:
+                        pts = np.ascontiguousarray((bpts_all if boxed else pts_all)[:P])
+                        rows = [pts[p] for p in range(P)]
+                        bx = np.ascontiguousarray(boxes_all[:P]) if boxed else None
+                        calls = args.calls or max(4, 1024 // P)
+
+                        def loop():
+                            for p, v in enumerate(rows):
+                                if bx is not None:
+                                    sc.set_box(bx[p, 0], bx[p, 1])
+                                sc.round_csr_diverse(v, strat, q, mp, pool_size=pool)
+                            if bx is not None:
+                                sc.clear_box()
+
+                        def batched():
+                            sc.round_csr_points_diverse(pts, strat, q, mp, pool_size=pool, boxes=bx)
+
+                        f0 = sc.get_stat(_capi.STAT_DIVERSE_POINTS_FAST)
+                        batched()
+                        fast = sc.get_stat(_capi.STAT_DIVERSE_POINTS_FAST) - f0
+                        for f in (batched, loop):
+                            timed(f, max(2, calls // 4))
+                        t = {"batched": [], "loop": []}
+                        for _ in range(args.repeats):
+                            for f in (batched, loop):
+                                t[f.__name__].append(timed(f, calls))
+                        lines.append("  %5d %4d %5s %4d | %s | %s | %14.2f | %d of %d" % (strat, q, "yes" if boxed else "no", P, median_cell(t["batched"], P),
+                                                                                 median_cell(t["loop"], P), np.median(t["loop"]) / np.median(t["batched"]), fast, P))
+                        print(lines[-1], flush=True)
+            lines.append("  points redone through the single-point round: %d" % sc.get_stat(_capi.STAT_POINTS_REDONE))
+            sc.set_objective(None)
+        # the price of the filter: the plain batched round of the same points
+        lines.append("  plain round_csr_points, P = 64, sel %d:" % sel)
+        pts = np.ascontiguousarray(pts_all[:64])
+        for strat in (1, 4):
+            def plain():
+                sc.round_csr_points(pts, strat, sel)
+            timed(plain, 16)
+            t = [timed(plain, 64) for _ in range(args.repeats)]
+            lines.append("  %5d %4d %5s %4d | %s" % (strat, sel, "no", 64, median_cell(t, 64)))
+            print(lines[-1], flush=True)
+        sc.close()
+    text = "\n".join(lines) + "\n"
+    print(text)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=9)
+    ap.add_argument("--repeats", type=int, default=0)
+    ap.add_argument("--diverse", action="store_true")
+    ap.add_argument("--plain-only", action="store_true")
+    ap.add_argument("--root", default=None)
     ap.add_argument("--calls", type=int, default=0, help="calls per timing (default: about 4096 points' worth, at least 8)")
     ap.add_argument("--loop-only", action="store_true")
     ap.add_argument("--boxes", action="store_true")
     ap.add_argument("--out", nargs="?", const="", default=None)
     args = ap.parse_args()
+    diverse = args.diverse or args.plain_only
+    args.repeats = args.repeats or (5 if diverse else 9)
     if args.out == "":
-        args.out = os.path.join(ROOT, "profiles", "boxed_points.txt" if args.boxes else "batch_points.txt")
+        args.out = os.path.join(ROOT, "profiles", "diverse_points.txt" if diverse else "boxed_points.txt" if args.boxes else "batch_points.txt")
+    if diverse:
+        gc.collect()
+        gc.freeze()
+        return diverse_main(args)
     lines = ["# tools/batch_points.py%s --repeats %d%s: ms per call, us per point; median over the blocks (min .. max)"
              % (" --boxes" if args.boxes else "", args.repeats, " --loop-only" if args.loop_only else ""),
              "# batched = round_csr_points(P points, boxes=); loop = P x (set_box, round_csr(point=p)); sel_size = 10 % of the list"
