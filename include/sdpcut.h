@@ -130,7 +130,9 @@ enum { SDPCUT_KERNEL_MFMA = 0, SDPCUT_KERNEL_SIMPLE = 1, SDPCUT_KERNEL_VALU = 2 
  * scores are within 1e-9 max(|obj|, 1e-3 max_elem) of the exact ones; measured 2e-11).  A band that does not is retried once with
  * 8192 entries; if that fails too (masses of equal scores at the threshold; more than 1024 candidates whose sign the fast score
  * cannot decide) the call GIVES UP: it returns exactly what it returns with the option off -- never a half-exact head -- and
- * SDPCUT_STAT_EXACT_GAVE_UP counts it.
+ * SDPCUT_STAT_EXACT_GAVE_UP counts it.  A band selection that is void because one of its bounded waits expired is neither exact
+ * nor a reason to retry with the widest band: the call gives up in the same way (SDPCUT_STAT_EXACT_GAVE_UP + 1,
+ * SDPCUT_STAT_EXACT_HEAD = 0, SDPCUT_STAT_SELECT_FALLBACKS unchanged) and the round is the option-off round, bit for bit.
  * Affects sdpcut_select_round*, sdpcut_round_view, sdpcut_round_csr*, and sdpcut_rank / sdpcut_rank_device when the head asked for
  * is within the limit below (strategy 4: and max_out <= sel_size); strategies 1 and SDPCUT_PART_* ignore it.
  * Head limit: min(N, cap + max(256, cap / 8)) <= 8192 (the reference's cap is 5000); a fused round with a longer head fails with
@@ -170,12 +172,30 @@ enum { SDPCUT_KERNEL_MFMA = 0, SDPCUT_KERNEL_SIMPLE = 1, SDPCUT_KERNEL_VALU = 2 
 enum { SDPCUT_OPT_KERNEL = 1, SDPCUT_OPT_TIMING = 2, SDPCUT_OPT_FUSE_KEYS = 3, SDPCUT_OPT_AUTO_REGIME = 4,
        SDPCUT_OPT_FUSED_TAIL = 5, SDPCUT_OPT_COOP_LAUNCH = 6, SDPCUT_OPT_EIG_KERNEL = 7, SDPCUT_OPT_STREAM_PRIORITY = 8,
        SDPCUT_OPT_SIDE_STREAMS = 9, SDPCUT_OPT_ONE_LAUNCH = 10, SDPCUT_OPT_PREFILTER = 11, SDPCUT_OPT_EXACT_HEAD = 12, SDPCUT_OPT_EXACT_SDP = 13,
-       SDPCUT_OPT_COUNT_RANK = 14, SDPCUT_OPT_SKIP_NONVIOLATED = 15, SDPCUT_OPT_FP32_FILTER = 16 };
+       SDPCUT_OPT_COUNT_RANK = 14, SDPCUT_OPT_SKIP_NONVIOLATED = 15, SDPCUT_OPT_FP32_FILTER = 16, SDPCUT_OPT_INJECT_GIVEUP = 17 };
+/* SDPCUT_OPT_INJECT_GIVEUP (default 0) -- TEST ONLY.  Makes the bounded device waits of the library give up without waiting, so that
+ * the recovery paths behind them can be tested on an idle device.  value = SDPCUT_INJECT_GIVEUP(site, first, count):
+ *   site   1 the top-k selection of more than one workgroup (the fused kernel with its grid barriers and its wait for a published
+ *            digit, and the launch-per-digit route that stands in for it, which the hook hits in the same way),
+ *          2 the look-back of the ordered CSR row assembly (plain, multi-cut, diverse and batched-points rounds);
+ *   first  0 .. 255 launches of that site pass untouched, then
+ *   count  1 .. 255 launches of that site are hit.
+ * The option disarms itself with the last hit; 0 disarms it by hand.  SDPCUT_ESTATE while a round is pending.
+ * A hit selection ends with its void mark raised (as after an expired wait: workgroups that reach a wait leave, the head of the
+ * others is discarded) and the host answers through its path without waits.  In a hit assembly launch every workgroup behind the
+ * first gives up its look-back before the first poll, whether or not the word it would wait for has arrived; the host launches
+ * the assembly again and fails with SDPCUT_EHIP after the second give-up.  Launches without a bounded wait are no site and consume
+ * nothing: the one-workgroup selections (lists of a few thousand candidates, the batched points), an assembly of one workgroup (a
+ * head of <= 64 entries).
+ * The hook never waits, never spins and launches nothing of its own.  With the option at 0 every call does what it did before. */
+#define SDPCUT_INJECT_GIVEUP(site, first, count) (((int64_t)(site) << 16) | ((int64_t)(first) << 8) | (int64_t)(count))
 
 /* Counters of a handle: SDPCUT_STAT_ROUNDS = fused rounds served (sdpcut_select_round*),
  * SDPCUT_STAT_SELECT_FALLBACKS = rounds whose radix selection declared itself void (a grid barrier
  * timed out because other work kept its workgroups from starting) and were answered by the full-sort
- * path instead -- same result, ~1 ms instead of ~0.1 ms.
+ * path instead -- same result, ~1 ms instead of ~0.1 ms; also: skipped rounds begun again for that reason, sdpcut_tri_separate
+ * calls that ran their selection once more, and row assemblies launched once more because their look-back gave up (one per
+ * launch; per point in the batched rounds).  The table is DESIGN.md section 5 "Give-up paths".
  * SDPCUT_STAT_SCORED = the measures (SDPCUT_EIG | SDPCUT_NN | SDPCUT_SDP | SDPCUT_EFF) scored at the current point.
  * SDPCUT_STAT_TIE_SPLITS (r4) = every-entry-visited combined rankings whose threshold group of EQUAL new scores
  * did not fit the sort buffers (structured LP vertices) and was cut by its secondary key -- obj_improve, then index,
@@ -202,13 +222,14 @@ enum { SDPCUT_OPT_KERNEL = 1, SDPCUT_OPT_TIMING = 2, SDPCUT_OPT_FUSE_KEYS = 3, S
  *   launch that scored everybody, nb_violated after a skipping launch, the survivors of the fp32 filter after a filtering one (read
  *   from the device: the call waits for the handle's stream); 0 after a new list.
  * SDPCUT_STAT_DIVERSE_POINTS_FAST = points of sdpcut_round_csr_points_diverse answered by its one-wait route since the handle was made
- *   (points served by the loop inside the call, or redone, do not count). */
+ *   (points served by the loop inside the call, or redone, do not count).
+ * SDPCUT_STAT_INJECTED -- TEST ONLY: launches SDPCUT_OPT_INJECT_GIVEUP has hit since the handle was made. */
 enum { SDPCUT_STAT_ROUNDS = 1, SDPCUT_STAT_SELECT_FALLBACKS = 2, SDPCUT_STAT_SCORED = 3, SDPCUT_STAT_TIE_SPLITS = 4,
        SDPCUT_STAT_DIRECT_SELECTIONS = 5, SDPCUT_STAT_PF_BIN = 6, SDPCUT_STAT_PF_FLOOR = 7, SDPCUT_STAT_PF_COUNT = 8,
        SDPCUT_STAT_EXACT_HEAD = 9, SDPCUT_STAT_EXACT_GAVE_UP = 10, SDPCUT_STAT_EXACT_RETRIES = 11,
        SDPCUT_STAT_SDP_UNCONVERGED = 12, SDPCUT_STAT_POINTS_REDONE = 13,
        SDPCUT_STAT_NN_SKIPPED = 14, SDPCUT_STAT_NN_COMPLETIONS = 15, SDPCUT_STAT_NN_EVALUATED = 16,
-       SDPCUT_STAT_DIVERSE_POINTS_FAST = 17 };
+       SDPCUT_STAT_DIVERSE_POINTS_FAST = 17, SDPCUT_STAT_INJECTED = 18 };
 int sdpcut_get_stat(sdpcut_handle h, int which, int64_t *value);
 
 /* The fp32 filter (SDPCUT_OPT_FP32_FILTER) of the network set for k-variable candidates: *margin = the proven bound on

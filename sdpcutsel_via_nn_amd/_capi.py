@@ -36,6 +36,18 @@ OPT_FP32_FILTER = 16     # the skipping launch filters the violated candidates i
 STAT_NN_EVALUATED = 16   # fp64 MLP evaluations of the last scoring launch that ran the network
 STAT_POINTS_REDONE = 13   # points of batched rounds served by the single-point round inside the call (include/sdpcut.h)
 STAT_DIVERSE_POINTS_FAST = 17   # points of round_csr_points_diverse answered by its one-wait route (include/sdpcut.h)
+OPT_INJECT_GIVEUP = 17   # TEST ONLY: the bounded device waits give up unasked (include/sdpcut.h); value = inject_giveup(site, first, count)
+STAT_INJECTED = 18       # TEST ONLY: launches the option has hit
+INJECT_SELECT, INJECT_LOOKBACK = 1, 2
+
+
+def inject_giveup(site, first=0, count=1):
+    """SDPCUT_INJECT_GIVEUP(site, first, count) of include/sdpcut.h: the value of OPT_INJECT_GIVEUP."""
+    if site not in (INJECT_SELECT, INJECT_LOOKBACK) or not 0 <= first <= 255 or not 1 <= count <= 255:
+        raise ValueError("inject_giveup: site 1..2, first 0..255, count 1..255")
+    return (site << 16) | (first << 8) | count
+
+
 BATCH_MAX_POINTS = 256   # SDPCUT_BATCH_MAX_POINTS: most LP points of one score_points / round_csr_points call
 DIVERSE_MAX_POOL = 16384   # SDPCUT_DIVERSE_MAX_POOL: longest pool of round_csr_diverse / list of filter_parallel
 MULTI_MAX_PER_SET = 5      # SDPCUT_MULTI_MAX_PER_SET: most eigen-cuts one index set offers (round_csr_multi / cut_rows_all)

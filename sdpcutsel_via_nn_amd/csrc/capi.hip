@@ -185,6 +185,16 @@ int sdpcut_set_option(sdpcut_handle h, int option, int64_t value)
         SDPCUT_NO_PENDING(h);
         h->exact_sdp = value != 0;
         return SDPCUT_OK;
+    case SDPCUT_OPT_INJECT_GIVEUP: {
+        SDPCUT_NO_PENDING(h);
+        const int64_t site = value >> 16, first = (value >> 8) & 255, count = value & 255;
+        if (value != 0 && (value < 0 || (site != 1 && site != 2) || count < 1))
+            return sdpcut_fail(h, SDPCUT_EINVAL, "SDPCUT_OPT_INJECT_GIVEUP: 0, or SDPCUT_INJECT_GIVEUP(site 1..2, first 0..255, count 1..255)");
+        h->inject_site = (int)site;
+        h->inject_skip = (int)first;
+        h->inject_count = (int)count;
+        return SDPCUT_OK;
+    }
     case SDPCUT_OPT_SIDE_STREAMS:
         if (value < 0 || value > 2) return sdpcut_fail(h, SDPCUT_EINVAL, "SDPCUT_OPT_SIDE_STREAMS: 0 off, 1 on, 2 measured");
         h->side_streams = (int)value;
@@ -251,6 +261,7 @@ int sdpcut_get_stat(sdpcut_handle h, int which, int64_t *value)
         *value = h->stat_nn_skipped;
         return SDPCUT_OK;
     case SDPCUT_STAT_TIE_SPLITS: *value = h->stat_tie_splits; return SDPCUT_OK;
+    case SDPCUT_STAT_INJECTED: *value = h->stat_injected; return SDPCUT_OK;
     case SDPCUT_STAT_POINTS_REDONE: *value = h->stat_points_redone; return SDPCUT_OK;
     case SDPCUT_STAT_DIVERSE_POINTS_FAST: *value = h->stat_diverse_points_fast; return SDPCUT_OK;
     case SDPCUT_STAT_EXACT_HEAD: *value = h->stat_exact_last; return SDPCUT_OK;

@@ -143,6 +143,10 @@ struct sdpcut_ctx {
     unsigned long long *d_stats = nullptr;   // device counters that outlive a round: [0] direct selections, [1..3] its diagnostics, [4] nb_violated of a skipped sharded head, [5] fp64 evaluations of a filtering launch
     bool coop_launch = false;      // SDPCUT_OPT_COOP_LAUNCH: cooperative launch of the kernels with grid barriers (+20 us per round)
     int64_t stat_rounds = 0, stat_fallbacks = 0, stat_tie_splits = 0;   // sdpcut_get_stat
+    // SDPCUT_OPT_INJECT_GIVEUP (tests): launches of inject_site (1 selection, 2 row-assembly look-back) -- inject_skip of them pass,
+    // the inject_count after them are hit (inject_take below); stat_injected counts the hits
+    int inject_site = 0, inject_skip = 0, inject_count = 0;
+    int64_t stat_injected = 0;        // SDPCUT_STAT_INJECTED
     int64_t stat_points_redone = 0;   // SDPCUT_STAT_POINTS_REDONE
     int64_t stat_diverse_points_fast = 0;   // SDPCUT_STAT_DIVERSE_POINTS_FAST
     PointsBufs pts;                   // sdpcut_score_points / sdpcut_round_csr_points
@@ -274,6 +278,18 @@ static inline hipError_t sdpcut_sync(sdpcut_ctx *h)
     const hipError_t e = hipStreamSynchronize(h->stream);
     if (e == hipSuccess) h->point_inflight = false;
     return e;
+}
+
+// SDPCUT_OPT_INJECT_GIVEUP: called by the launcher of every launch that holds a bounded wait of `site` -- topk_run of topk.hip (1), the
+// launchers of the CSR assemblies in rows.hip and multirows.hip (2); eligible = the launch has a wait to give up (an assembly of two workgroups at least).
+// -> true: this launch is to be hit (counted; the option disarms itself with the last one).  Disarmed: one compare.
+static inline bool inject_take(sdpcut_ctx *h, int site, bool eligible = true)
+{
+    if (h->inject_site != site || !eligible) return false;
+    if (h->inject_skip > 0) { --h->inject_skip; return false; }
+    if (--h->inject_count <= 0) h->inject_site = 0;
+    ++h->stat_injected;
+    return true;
 }
 
 int sdpcut_fail(sdpcut_ctx *h, int code, const std::string &msg);

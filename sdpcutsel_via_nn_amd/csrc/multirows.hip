@@ -124,6 +124,7 @@ struct MultiCsrArgs {
     int64_t serial;
     uint32_t *done_ticket;
     uint64_t *agg;             // [gridDim.x] look-back words
+    int inject;                // SDPCUT_OPT_INJECT_GIVEUP: the look-back gives up unasked (rows_dev.h); 0 outside tests
 };
 
 __global__ __launch_bounds__(64) void multi_csr_kernel(MultiCsrArgs R)
@@ -175,7 +176,7 @@ __global__ __launch_bounds__(64) void multi_csr_kernel(MultiCsrArgs R)
     const int wg_rows = __shfl(incl_r, 63), wg_nnz = __shfl(incl_z, 63);
     // publish this workgroup's aggregate (BEFORE the quota: a workgroup behind the quota must see it passed), then sum those in front
     int64_t pre_rows, pre_nnz;
-    const int gave_up = csr_lookback(R.agg, (uint32_t)R.serial, wg_rows, wg_nnz, pre_rows, pre_nnz);
+    const int gave_up = csr_lookback(R.agg, (uint32_t)R.serial, wg_rows, wg_nnz, pre_rows, pre_nnz, R.inject);
     if (gave_up && lane == 0) R.o_hdr[10] = 1;      // the block is void; the host launches the assembly once more
     // The rows, now that their global numbers are known.  Row g of the round is kept iff g < row_cap; the row numbered row_cap
     // itself -- the first one dropped -- says where the block ends.  With a give-up the numbers are wrong but stay inside the
@@ -328,6 +329,7 @@ static int launch_multi_csr(sdpcut_ctx *h, MultiWs *w, int64_t cap, int64_t limi
     R.o_rhs = (double *)(b + y.rhs); R.o_row_lam = (double *)(b + y.row_lam); R.o_indices = (int32_t *)(b + y.indices);
     R.o_values = (double *)(b + y.values);
     R.serial = serial; R.done_ticket = h->d_done_ticket; R.agg = round_agg_words(h);
+    R.inject = inject_take(h, 2, grid > 1);
     hipLaunchKernelGGL(multi_csr_kernel, dim3(grid), dim3(64), 0, h->stream, R);
     HIP_TRY(h, hipGetLastError());
     return 0;

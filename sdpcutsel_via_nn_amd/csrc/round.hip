@@ -299,6 +299,9 @@ static int round_end(sdpcut_ctx *h, const void **block, int64_t *cap_out, int64_
             const int64_t *c = (const int64_t *)h->pinned;
             keep = !c[4] && c[6] == TK_MODE_STRONG && c[0] >= (P.sel_size < h->N ? P.sel_size : h->N);
             h->stat_nn_skipped = h->N - c[1];
+            // a selection that gave up is a fallback whichever road answers it (until the give-up tests this one went uncounted:
+            // the round begun again below finds a clean header)
+            if (c[4] == 1) ++h->stat_fallbacks;      // (2, the tie group, is no fallback: the round begun again splits it)
         }
         if (!keep) {
             int rc = obj_complete(h);
@@ -355,7 +358,8 @@ static int round_end(sdpcut_ctx *h, const void **block, int64_t *cap_out, int64_
     }
     if (!have) {
         // general path (full sorts; the combined scan visiting every entry, or heads > 8192)
-        // (the fast attempt above already counted the strong candidates: no second attempt)
+        // (the fast attempt above already counted the strong candidates: with its count as hint there is no second attempt; a VOID
+        // attempt has no count to hand on -- hint -1 -- and rank_on_device makes its own, which answers unless it is void as well)
         if (P.exact_band > 0 && h->stat_exact_last) {      // (never seen: an exact head's counters always answer) nothing half-exact
             h->stat_exact_last = 0;
             ++h->stat_exact_gave_up;

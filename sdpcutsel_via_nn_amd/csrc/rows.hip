@@ -162,6 +162,7 @@ struct RoundCsrArgs {
     int64_t serial;
     uint32_t *done_ticket;
     uint64_t *agg;             // [gridDim.x] look-back words
+    int inject;                // SDPCUT_OPT_INJECT_GIVEUP: the look-back gives up unasked (rows_dev.h); 0 outside tests
 };
 
 #ifndef ROUND_MIN_BLOCKS
@@ -223,7 +224,7 @@ __device__ __forceinline__ void round_csr_body(const RoundCsrArgs &R)
     const int wg_nnz = __shfl(incl, 63);
     // publish this workgroup's aggregate, then sum those of the workgroups in front
     int64_t pre_rows, pre_nnz;
-    const int gave_up = csr_lookback(R.agg, (uint32_t)R.serial, wg_rows, wg_nnz, pre_rows, pre_nnz);
+    const int gave_up = csr_lookback(R.agg, (uint32_t)R.serial, wg_rows, wg_nnz, pre_rows, pre_nnz, R.inject);
     if (gave_up && lane == 0) R.o_hdr[10] = 1;      // the block is void; the host launches the assembly once more (round.hip: csr_assemble_wait)
     if (keep) {
         const int64_t r = pre_rows + my_row;
@@ -383,6 +384,7 @@ int launch_round_csr(sdpcut_ctx *h, int64_t cap, const int64_t *d_c4, int64_t li
     rc = topk_alt_ws(h, &R.zero_ptr, &R.zero_words);
     if (rc) return rc;
     R.serial = serial; R.done_ticket = h->d_done_ticket; R.agg = round_agg_words(h);
+    R.inject = inject_take(h, 2, cap > 64);
     hipLaunchKernelGGL(round_csr_kernel, dim3(grid), dim3(64), 0, h->stream, R);
     HIP_TRY(h, hipGetLastError());
     h->topk_alt_clean = true;
@@ -406,6 +408,7 @@ int launch_round_csr_points(sdpcut_ctx *h, int p_first, int n_points, int64_t ca
     csr_args_out(R, block, cap, ld);
     R.zero_ptr = nullptr; R.zero_words = 0;
     R.serial = serial; R.done_ticket = nullptr; R.agg = d_agg;
+    R.inject = inject_take(h, 2, cap > 64);
     RoundCsrPointStrides ps;
     ps.p_first = p_first; ps.c4 = c4_stride; ps.head = cap; ps.vars = pts_stride; ps.eig = eig_stride; ps.block = block_stride;
     ps.agg = agg_stride;

@@ -151,7 +151,10 @@ static_assert(64 * SDPCUT_MULTI_MAX_PER_SET * SDPCUT_ROW_LD <= 0xffff, "non-zero
 // 0 .. blockIdx.x - 1 into pre_rows / pre_nnz (the same values in every lane).  -> non-zero in every lane if some lane gave
 // up: the sums are then wrong, the caller marks the block void (header word 10) and the host launches the assembly once more
 // (round.hip: csr_assemble_wait).
-__device__ __forceinline__ int csr_lookback(uint64_t *agg, uint32_t tag, int wg_rows, int wg_nnz, int64_t &pre_rows, int64_t &pre_nnz)
+// inject (SDPCUT_OPT_INJECT_GIVEUP, uniform over the launch; 0 outside tests): every lane with a word to wait for gives up before its
+// first poll, whether or not the word has arrived -- what an expired limit looks like, without the wait.
+__device__ __forceinline__ int csr_lookback(uint64_t *agg, uint32_t tag, int wg_rows, int wg_nnz, int64_t &pre_rows, int64_t &pre_nnz,
+                                            int inject)
 {
     const int lane = threadIdx.x;
     if (lane == 0)
@@ -159,7 +162,7 @@ __device__ __forceinline__ int csr_lookback(uint64_t *agg, uint32_t tag, int wg_
                            __HIP_MEMORY_SCOPE_AGENT);
     pre_rows = 0;
     pre_nnz = 0;
-    int gave_up = 0;
+    int gave_up = (inject && lane < (int)blockIdx.x) ? 1 : 0;
     for (int b = lane; b < (int)blockIdx.x && !gave_up; b += 64) {
         uint64_t w = __hip_atomic_load(&agg[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         uint32_t it = 0;

@@ -127,6 +127,15 @@ bool topk_fuse_ok(const sdpcut_ctx *h, int64_t k, bool comb)
 static int topk_run(sdpcut_ctx *h, const TkPlan &p, const TkJob &j, bool prekeys)
 {
     int rc = 0;
+    // SDPCUT_OPT_INJECT_GIVEUP (tests), site 1: the void mark of an expired wait stands in the workspace before the route's kernels
+    // start -- behind the zeroing of the workspace (topk_begin, stream order); neither the score kernels nor the key pass touch the
+    // word.  Workgroups of tk_refine_kernel that reach a wait find the selection gone and leave, everything else runs to its end,
+    // the sort tail emits nothing and the host discards the head: no kernel knows about the option.  The one-workgroup routes have
+    // no bounded wait and no path behind one: they are no site.
+    if (p.route > TK_ROUTE_SMALL && inject_take(h, 1)) {
+        static const int64_t one = 1;
+        HIP_TRY(h, hipMemcpyAsync(&j.ws->counters[4], &one, sizeof(one), hipMemcpyHostToDevice, h->stream));
+    }
     switch (p.route) {
     case TK_ROUTE_SMALLSORT:
     case TK_ROUTE_SMALLSEL:

@@ -15,6 +15,8 @@ operations run a selection round; every ordered pair of families with a round-li
 
 Left out on purpose: the sharded calls (sdpcut_shard_*, rank_device, merge / gather on device buffers -- they need a second
 runtime's buffers and a process group), set_stream (a caller's stream changes ordering, not results, and needs torch),
+SDPCUT_OPT_INJECT_GIVEUP (test only; it changes no result either, and giveup_cases.py / test_gpu_giveup.py run it against fresh
+handles in the same way -- LEFT_OUT_OPTIONS below names it, and the model's statistics list knows SDPCUT_STAT_INJECTED),
 SDPCUT_OPT_COOP_LAUNCH (another way to launch the same selection kernel: it changes no result and no state a later call reads) and
 SDPCUT_OPT_SIDE_STREAMS = 2, which picks a code path from a timing.
 
@@ -53,6 +55,11 @@ OPTIONS = {
     "prefilter": (_capi.OPT_PREFILTER, 1, (0, 1)),
     "exact_sdp": (_capi.OPT_EXACT_SDP, 0, (0, 1)),
 }
+# options of the header that the alphabet leaves out on purpose (the docstring says why), and the statistics a comparison skips
+LEFT_OUT_OPTIONS = {"inject_giveup": _capi.OPT_INJECT_GIVEUP, "coop_launch": _capi.OPT_COOP_LAUNCH, "side_streams": _capi.OPT_SIDE_STREAMS,
+                    "timing": _capi.OPT_TIMING, "eig_kernel": _capi.OPT_EIG_KERNEL, "stream_priority": _capi.OPT_STREAM_PRIORITY}
+HISTORY_STATS = {"rounds": _capi.STAT_ROUNDS, "select_fallbacks": _capi.STAT_SELECT_FALLBACKS, "tie_splits": _capi.STAT_TIE_SPLITS,
+                 "nn_completions": _capi.STAT_NN_COMPLETIONS, "injected": _capi.STAT_INJECTED}
 # name -> global_base (Fixtures.list says what each list is for)
 LISTS = {"A": 0, "B": 7, "C": 0, "D": 10 ** 9, "E": 0}
 LIST_LENGTHS = {"A": 130, "B": 6000, "C": 9880, "D": 40000, "E": 5000}

@@ -86,7 +86,8 @@ def test_abi_carries_the_entry_points():
     enums = " ".join(re.findall(r"enum\s*\{([^}]*)\}", hdr))
     stats = dict((k, int(v)) for k, v in re.findall(r"(SDPCUT_STAT_\w+)\s*=\s*(-?\d+)", enums))
     assert stats["SDPCUT_STAT_DIVERSE_POINTS_FAST"] == _capi.STAT_DIVERSE_POINTS_FAST == 17
-    assert sorted(stats.values()) == list(range(1, 18))      # a new code, nothing renumbered
+    assert stats["SDPCUT_STAT_INJECTED"] == _capi.STAT_INJECTED == 18      # (the test-only statistic of SDPCUT_OPT_INJECT_GIVEUP came after it)
+    assert sorted(stats.values()) == list(range(1, 19))      # new codes, nothing renumbered
     assert (stats["SDPCUT_STAT_POINTS_REDONE"], stats["SDPCUT_STAT_NN_EVALUATED"]) == (13, 16)
     so = build.build(verbose=False)
     exported = set(ln.split()[-1] for ln in subprocess.check_output(["nm", "-D", "--defined-only", so], text=True).splitlines() if ln.strip())

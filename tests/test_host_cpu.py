@@ -45,9 +45,9 @@ def test_header_constants_match_binding():
     # (option / statistic codes: from the enum bodies only -- the comments around them quote values too)
     enums = " ".join(re.findall(r"enum\s*\{([^}]*)\}", hdr))
     vals = dict((k, int(v)) for k, v in re.findall(r"(SDPCUT_\w+)\s*=\s*(-?\d+)", enums))
-    for name in ("KERNEL", "TIMING", "FUSE_KEYS", "AUTO_REGIME", "FUSED_TAIL", "COOP_LAUNCH"):
+    for name in ("KERNEL", "TIMING", "FUSE_KEYS", "AUTO_REGIME", "FUSED_TAIL", "COOP_LAUNCH", "INJECT_GIVEUP"):
         assert vals["SDPCUT_OPT_" + name] == getattr(_capi, "OPT_" + name), name
-    for name in ("ROUNDS", "SELECT_FALLBACKS", "SCORED"):
+    for name in ("ROUNDS", "SELECT_FALLBACKS", "SCORED", "INJECTED"):
         assert vals["SDPCUT_STAT_" + name] == getattr(_capi, "STAT_" + name), name
     assert (vals["SDPCUT_KERNEL_MFMA"], vals["SDPCUT_KERNEL_SIMPLE"], vals["SDPCUT_KERNEL_VALU"]) == (
         _capi.KERNEL_MFMA, _capi.KERNEL_SIMPLE, _capi.KERNEL_VALU)
