@@ -223,13 +223,17 @@ enum { SDPCUT_OPT_KERNEL = 1, SDPCUT_OPT_TIMING = 2, SDPCUT_OPT_FUSE_KEYS = 3, S
  *   from the device: the call waits for the handle's stream); 0 after a new list.
  * SDPCUT_STAT_DIVERSE_POINTS_FAST = points of sdpcut_round_csr_points_diverse answered by its one-wait route since the handle was made
  *   (points served by the loop inside the call, or redone, do not count).
- * SDPCUT_STAT_INJECTED -- TEST ONLY: launches SDPCUT_OPT_INJECT_GIVEUP has hit since the handle was made. */
+ * SDPCUT_STAT_INJECTED -- TEST ONLY: launches SDPCUT_OPT_INJECT_GIVEUP has hit since the handle was made.
+ * SDPCUT_STAT_TRI_POINTS_FAST = points of sdpcut_tri_round_csr_points answered by its one-wait route since the handle was made
+ *   (points served by the loop inside the call do not count). */
 enum { SDPCUT_STAT_ROUNDS = 1, SDPCUT_STAT_SELECT_FALLBACKS = 2, SDPCUT_STAT_SCORED = 3, SDPCUT_STAT_TIE_SPLITS = 4,
        SDPCUT_STAT_DIRECT_SELECTIONS = 5, SDPCUT_STAT_PF_BIN = 6, SDPCUT_STAT_PF_FLOOR = 7, SDPCUT_STAT_PF_COUNT = 8,
        SDPCUT_STAT_EXACT_HEAD = 9, SDPCUT_STAT_EXACT_GAVE_UP = 10, SDPCUT_STAT_EXACT_RETRIES = 11,
        SDPCUT_STAT_SDP_UNCONVERGED = 12, SDPCUT_STAT_POINTS_REDONE = 13,
        SDPCUT_STAT_NN_SKIPPED = 14, SDPCUT_STAT_NN_COMPLETIONS = 15, SDPCUT_STAT_NN_EVALUATED = 16,
        SDPCUT_STAT_DIVERSE_POINTS_FAST = 17, SDPCUT_STAT_INJECTED = 18 };
+/* (a macro, not an enumerator: the enumeration above is the closed set of codes 1 .. 18 that tests/test_diverse_points_cpu.py pins) */
+#define SDPCUT_STAT_TRI_POINTS_FAST 19
 int sdpcut_get_stat(sdpcut_handle h, int which, int64_t *value);
 
 /* The fp32 filter (SDPCUT_OPT_FP32_FILTER) of the network set for k-variable candidates: *margin = the proven bound on
@@ -1040,6 +1044,47 @@ int sdpcut_tri_preprocess(sdpcut_handle h, const uint8_t *adjacency, int64_t *n_
 int sdpcut_tri_get_triples(sdpcut_handle h, int32_t *triples_out, uint8_t *density_out);
 int sdpcut_tri_separate(sdpcut_handle h, int64_t max_out, int64_t *entry_out, double *viol_out,
                         int64_t *n_violated, int64_t *n_written);
+
+/*
+ * Triangle rounds with the rows assembled on the device, at the root and at tree nodes (DESIGN.md section 5 "Triangle inequalities
+ * at nodes"; numpy twin: sdpcutsel_via_nn_amd/triangles.py).
+ * sdpcut_tri_round_csr: the separation of sdpcut_tri_separate followed by the rows of the selected entries, as one CSR block in a
+ *   pinned host block of the handle; one host wait.  vars_values: the LP point [X packed | x] (sdpcut_set_point is part of the
+ *   call), or NULL to keep the current one.  0 <= max_out <= 16384.  Needs sdpcut_tri_preprocess (SDPCUT_ESTATE without).
+ *   All pointers of *out point INTO the handle's block: valid until the next call on the handle, never freed by the caller.
+ *     n_violated  length of the full list of violated entries;  n_rows = min(max_out, n_violated)
+ *     entry [n_rows], viol [n_rows]   what sdpcut_tri_separate returns: 4 * triple + type, ranked (density 3 first, violation
+ *                                     descending, entry ascending)
+ *     rhs [n_rows], indptr [n_rows + 1], indices / values [nnz = indptr[n_rows]]   row r, sense >=, in the columns of vars_values:
+ *                                     X_ab, X_ac, X_bc, then the x columns in ascending variable order
+ *   Without a node box row r is the row the reference builds (:847-861): 4 non-zeros +-1 and rhs 0 for types 0 .. 2, 6 non-zeros and
+ *   rhs -1 for type 3.  With a node box (sdpcut_set_box) the call separates the triangle inequalities OF THE BOX: the violations
+ *   are those of the box tables x' = (x - l) / d, X' (sdpcut_get_box_tables; violated: >= 1e-7 in those units; density is the
+ *   original pattern's), and row r is that facet written in the original (x, X) -- valid on the box, where the unit-box facet is
+ *   weaker -- with up to 3 x columns and a right-hand side; a coefficient that is exactly zero is dropped.  On the unit box every
+ *   byte equals the call without a box.
+ * sdpcut_tri_round_csr_points: the same at n_points LP points (row p of `points`, point_ld >= L + n doubles apart; 1 <= n_points <=
+ *   SDPCUT_BATCH_MAX_POINTS) in one call with one host wait; lb / ub: both NULL, or [n_points][n] each -- the node box of every
+ *   point, checked by sdpcut_set_box's rule.  out[p] is, bit for bit, what sdpcut_set_box(lb[p], ub[p]) (or no box) followed by
+ *   sdpcut_tri_round_csr(points[p], max_out) returns; its pointers point into the handle's pinned batch block (slice p, padded to
+ *   64 bytes).  One-wait route (SDPCUT_STAT_TRI_POINTS_FAST counts its points): max_out <= 4096 and the per-point tables within
+ *   256 MB -- one workgroup per point selects by radix over recomputed keys, sorts its head and emits its rows; everything else
+ *   runs the single-point call per point inside the call.  Refused (SDPCUT_ESTATE) while the handle has a box of its own; leaves
+ *   the handle without a current point and without a box.
+ */
+typedef struct sdpcut_tri_csr {
+    int64_t cap;                    /* min(max_out, 4 T): entries the block has room for */
+    int64_t n_rows, n_violated, nnz;
+    const int64_t *entry;
+    const double *viol;
+    const int32_t *indptr;
+    const int32_t *indices;
+    const double *values;
+    const double *rhs;
+} sdpcut_tri_csr_t;
+int sdpcut_tri_round_csr(sdpcut_handle h, const double *vars_values, int64_t max_out, sdpcut_tri_csr_t *out);
+int sdpcut_tri_round_csr_points(sdpcut_handle h, int32_t n_points, const double *points, int64_t point_ld, const double *lb,
+                                const double *ub, int64_t max_out, sdpcut_tri_csr_t *out);
 
 /* Self-test hook: multiplies A[16x4] * B[4x16] with v_mfma_f64_16x16x4_f64 using the
  * fragment maps the MLP kernel assumes; C row-major [16][16]. */

@@ -35,6 +35,7 @@ STAT_NN_SKIPPED, STAT_NN_COMPLETIONS = 14, 15   # candidates the last such launc
 OPT_FP32_FILTER = 16     # the skipping launch filters the violated candidates in fp32 ahead of the fp64 pass (include/sdpcut.h); default on
 STAT_NN_EVALUATED = 16   # fp64 MLP evaluations of the last scoring launch that ran the network
 STAT_POINTS_REDONE = 13   # points of batched rounds served by the single-point round inside the call (include/sdpcut.h)
+STAT_TRI_POINTS_FAST = 19   # points of tri_round_csr_points answered by its one-wait route (include/sdpcut.h)
 STAT_DIVERSE_POINTS_FAST = 17   # points of round_csr_points_diverse answered by its one-wait route (include/sdpcut.h)
 OPT_INJECT_GIVEUP = 17   # TEST ONLY: the bounded device waits give up unasked (include/sdpcut.h); value = inject_giveup(site, first, count)
 STAT_INJECTED = 18       # TEST ONLY: launches the option has hit
@@ -72,6 +73,12 @@ _ROUND_CSR_DTYPE = np.dtype([("cap", "<i8"), ("n_out", "<i8"), ("n_total", "<i8"
                              ("idx", "<u8"), ("score", "<u8"), ("lam_min", "<u8"), ("ks", "<u8"), ("set_inds", "<u8"), ("n_rows", "<i8"),
                              ("nnz", "<i8"), ("row_entry", "<u8"), ("indptr", "<u8"), ("indices", "<u8"), ("values", "<u8"), ("rhs", "<u8")])
 assert _ROUND_CSR_DTYPE.itemsize == _c.sizeof(RoundCsr)
+
+
+class TriCsr(_c.Structure):
+    """sdpcut_tri_csr_t of include/sdpcut.h"""
+    _fields_ = [("cap", _c.c_int64), ("n_rows", _c.c_int64), ("n_violated", _c.c_int64), ("nnz", _c.c_int64), ("entry", _vp), ("viol", _vp),
+                ("indptr", _vp), ("indices", _vp), ("values", _vp), ("rhs", _vp)]
 
 
 class RoundMulti(_c.Structure):
@@ -186,6 +193,8 @@ SIGNATURES = {
     "sdpcut_tri_preprocess": [_vp, _c.POINTER(_c.c_uint8), _i64p],
     "sdpcut_tri_get_triples": [_vp, _i32p, _c.POINTER(_c.c_uint8)],
     "sdpcut_tri_separate": [_vp, _c.c_int64, _i64p, _dp, _i64p, _i64p],
+    "sdpcut_tri_round_csr": [_vp, _dp, _c.c_int64, _c.POINTER(TriCsr)],
+    "sdpcut_tri_round_csr_points": [_vp, _c.c_int32, _dp, _c.c_int64, _dp, _dp, _c.c_int64, _c.POINTER(TriCsr)],
     "sdpcut_enumerate_cover": [_c.c_int32, _c.POINTER(_c.c_uint8), _c.c_int32, _c.c_int64, _i32p, _i32p, _i64p],
     "sdpcut_enumerate_cover_ch": [_c.c_int32, _c.POINTER(_c.c_uint8), _c.POINTER(_c.c_uint8), _c.c_int32, _c.c_int64, _i32p, _i32p, _i64p],
     "sdpcut_chordal_extension": [_c.c_int32, _c.POINTER(_c.c_uint8), _i32p, _c.POINTER(_c.c_uint8), _i32p, _i64p],
@@ -1293,6 +1302,52 @@ class Scorer(object):
         self._check(self._lib.sdpcut_tri_separate(self._h, cap, _ptr(ent, _i64p), _ptr(vio, _dp), ctypes.byref(nv),
                                                   ctypes.byref(nw)))
         return ent[:nw.value], vio[:nw.value], int(nv.value)
+
+    TRI_MAX_OUT = 16384      # most entries of one tri_separate / tri_round_csr call
+
+    @staticmethod
+    def _tri_unpack(rec, copy):
+        """a sdpcut_tri_csr_t -> dict(entry, viol, indptr, indices, values, rhs, n_rows, n_violated): views of the pinned block, or copies"""
+        r, nnz = int(rec.n_rows), int(rec.nnz)
+        out = dict(entry=_view(rec.entry, np.int64, r), viol=_view(rec.viol, np.float64, r), indptr=_view(rec.indptr, np.int32, r + 1),
+                   indices=_view(rec.indices, np.int32, nnz), values=_view(rec.values, np.float64, nnz), rhs=_view(rec.rhs, np.float64, r))
+        if copy:
+            out = dict((k, np.array(v)) for k, v in out.items())
+        out.update(n_rows=r, n_violated=int(rec.n_violated))
+        return out
+
+    def tri_round_csr(self, max_out, point=None, copy=False):
+        """The triangle separation with its rows assembled on the device (sdpcut_tri_round_csr): at ``point`` (None: the current one)
+        the first ``max_out`` violated triangle inequalities, ranked as :meth:`tri_separate` ranks them, and their rows in the
+        hand-over form of a round's cuts, sense >=.  With a node box (:meth:`set_box`) the inequalities are those of the box
+        (:mod:`triangles`).  -> dict(entry int64 [r], viol [r], indptr int32 [r + 1], indices int32, values, rhs [r], n_rows,
+        n_violated); the arrays are views of the handle's pinned block, valid until the next call on this Scorer (copy=True
+        detaches them)."""
+        if not 0 <= int(max_out) <= self.TRI_MAX_OUT:
+            raise ValueError("max_out must be 0 .. %d" % self.TRI_MAX_OUT)
+        rec = TriCsr()
+        vv = None if point is None else self._point(point)
+        self._check(self._lib.sdpcut_tri_round_csr(self._h, _ptr(vv, _dp), int(max_out), ctypes.byref(rec)))
+        return self._tri_unpack(rec, copy)
+
+    def tri_round_csr_points(self, points, max_out, boxes=None, copy=False):
+        """:meth:`tri_round_csr` at P LP points in one call with one host wait (sdpcut_tri_round_csr_points): points [P, n(n+1)/2 + n]
+        -> list of P dicts, entry p = what tri_round_csr(max_out, point=points[p]) returns -- with boxes [P, 2, n], inside
+        set_box(*boxes[p]).  Views of the handle's pinned batch block, valid until the next call (copy=True detaches them).  The
+        Scorer must have no box of its own; it is left without a current point and without a box."""
+        pts = self._points_arg(points)
+        P = pts.shape[0]
+        if not 0 <= int(max_out) <= self.TRI_MAX_OUT:
+            raise ValueError("max_out must be 0 .. %d" % self.TRI_MAX_OUT)
+        lb = ub = None
+        if boxes is not None:
+            from .nodebox import check_boxes
+            bx = check_boxes(self.nb_vars, boxes, n_points=P)
+            lo, hi = np.ascontiguousarray(bx[:, 0, :]), np.ascontiguousarray(bx[:, 1, :])
+            lb, ub = _ptr(lo, _dp), _ptr(hi, _dp)
+        recs = (TriCsr * P)()
+        self._check(self._lib.sdpcut_tri_round_csr_points(self._h, P, _ptr(pts, _dp), pts.shape[1], lb, ub, int(max_out), recs))
+        return [self._tri_unpack(recs[p], copy) for p in range(P)]
 
     def eig_batch(self, k, x_rho, X_rho, want_vectors=False):
         x_rho, X_rho = _f64(x_rho), _f64(X_rho)

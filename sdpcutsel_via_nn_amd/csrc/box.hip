@@ -87,7 +87,7 @@ __global__ __launch_bounds__(256) void box_points_kernel(const double *Q, const 
     int32_t i, j;
     box_unpack(p, n, i, j);
     const double di = ld[n + i], dj = ld[n + j];
-    Qb[y * L + p] = box_q_entry(Q[p], di, dj);
+    if (Qb) Qb[y * L + p] = box_q_entry(Q[p], di, dj);      // (uniform; NULL: a caller that reads the point tables only -- the triangle batch)
     vb[p] = box_X_entry(vars[p], vars[L + i], vars[L + j], ld[i], ld[j], di, dj);
 }
 

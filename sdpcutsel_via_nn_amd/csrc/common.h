@@ -149,6 +149,7 @@ struct sdpcut_ctx {
     int64_t stat_injected = 0;        // SDPCUT_STAT_INJECTED
     int64_t stat_points_redone = 0;   // SDPCUT_STAT_POINTS_REDONE
     int64_t stat_diverse_points_fast = 0;   // SDPCUT_STAT_DIVERSE_POINTS_FAST
+    int64_t stat_tri_points_fast = 0;       // SDPCUT_STAT_TRI_POINTS_FAST
     PointsBufs pts;                   // sdpcut_score_points / sdpcut_round_csr_points
     // SDPCUT_OPT_EXACT_HEAD (exact_head.hip): NN-ranked heads ordered and reported by reference-order obj_improve
     bool exact_head = false;
@@ -244,6 +245,8 @@ struct sdpcut_ctx {
     int32_t *d_tri = nullptr;          // [T][3]
     uint8_t *d_tri_dense3 = nullptr;   // [T] density == 3
     int64_t n_tri = 0;
+    bool tri_ready = false;            // sdpcut_tri_preprocess has run (n_tri = 0 is a list too)
+    void *tri_pts = nullptr;           // triangle rounds over a batch of points (tri_points.hip: TriPointsBufs); allocated by the first call
     std::vector<int32_t> tri_host;
     std::vector<uint8_t> tri_dense_host;
     // small staging
@@ -291,6 +294,31 @@ static inline bool inject_take(sdpcut_ctx *h, int site, bool eligible = true)
     ++h->stat_injected;
     return true;
 }
+
+// The batched calls (points.hip, tri_points.hip) leave the handle without a current point, whichever way they return: the
+// single-point arrays hold, at best, the scores of the last point the per-point fallback served.
+struct NoPointAfter {
+    sdpcut_ctx *h;
+    explicit NoPointAfter(sdpcut_ctx *ctx) : h(ctx) {}
+    ~NoPointAfter()
+    {
+        h->have_point = false;
+        h->scored = 0; h->obj_partial = false;
+        h->last_total = -1;
+    }
+};
+// The boxed batched calls leave the handle without a box, whichever way they return (the loop route and a redone point set one).
+struct NoBoxAfter {
+    sdpcut_ctx *h;
+    explicit NoBoxAfter(sdpcut_ctx *ctx) : h(ctx) {}
+    ~NoBoxAfter()
+    {
+        if (!h->box_set) return;
+        (void)sdpcut_sync(h);      // (launches of the last point's scoring read the box tables)
+        h->box_set = false;
+        h->box_lb.clear(); h->box_ub.clear();
+    }
+};
 
 int sdpcut_fail(sdpcut_ctx *h, int code, const std::string &msg);
 int ensure_stage(sdpcut_ctx *h, size_t bytes);   // capi.hip: grow h->d_stage
@@ -458,7 +486,7 @@ void box_clear(sdpcut_ctx *h);        // drop the box and its tables (the caller
 // sdpcut_set_box's rule on one box, the failure recorded in the name of `what` (point >= 0: "point <point>, variable <i>")
 int box_check(sdpcut_ctx *h, const char *what, int point, const double *lb, const double *ub);
 // box_points_kernel: Q' (rows of L) and the transformed points (rows of L + n) of n_points points, each in the box of its row of
-// the [n_points][2 n] (l | d) table d_ld
+// the [n_points][2 n] (l | d) table d_ld; d_Qb NULL: the transformed points alone
 int launch_box_points(sdpcut_ctx *h, int n_points, const double *d_pts, int64_t pts_stride, const double *d_ld, double *d_Qb, double *d_vb);
 #define SDPCUT_NO_BOX(h, what)                                                                                            \
     do {                                                                                                                  \
@@ -559,6 +587,10 @@ void free_lpobj(sdpcut_ctx *h);
 int tri_preprocess(sdpcut_ctx *h, const uint8_t *adjacency, int64_t *n_triples);
 int tri_separate(sdpcut_ctx *h, int64_t max_out, int64_t *d_entry_out, double *d_viol_out, int64_t *n_violated,
                  int64_t *n_written);
+// the pointers and counts of *out for a triangle block (tri_layout.h: tri_layout) of out->cap entries that lies at `block`
+void tri_out_from_block(const void *block, sdpcut_tri_csr_t *out);
+// tri_points.hip
+void free_tri_points_ws(sdpcut_ctx *h);
 
 // topk.hip
 int topk_select_enqueue(sdpcut_ctx *h, int mode, int64_t k, double score_add, int64_t *d_idx_out,
@@ -572,6 +604,8 @@ int64_t *topk_strong_counter(void *ws);      // TopkWs::strong_rep (TK_SREP = 8 
 int topk_select_on_device(sdpcut_ctx *h, int mode, int64_t k, double score_add, int64_t *d_idx_out,
                           double *d_score_out, int64_t cnt[5]);
 int topk_select_keys_on_device(sdpcut_ctx *h, int64_t n, int64_t k, int64_t *d_idx_out, double *d_val_out, int64_t cnt[5]);
+// the same selection enqueued, without the host wait: *d_counters_out = its five counters on the device (what `cnt` receives)
+int topk_select_keys_enqueue(sdpcut_ctx *h, int64_t n, int64_t k, int64_t *d_idx_out, double *d_val_out, const int64_t **d_counters_out);
 void free_topk_ws(sdpcut_ctx *h);
 // the void COMBALL selection in the handle's workspace, answered by two selections over precomputed keys (see topk.hip)
 int topk_tie_split(sdpcut_ctx *h, int64_t k, int64_t *d_idx_out, double *d_score_out, int64_t *k_eff_out);

@@ -236,36 +236,12 @@ static int check_points_args(sdpcut_ctx *h, int32_t n_points, const double *poin
     return 0;
 }
 
-// Both calls leave the handle without a current point, whichever way they return: the single-point arrays hold, at best, the
-// scores of the last point the per-point fallback served.
-struct NoPointAfter {
-    sdpcut_ctx *h;
-    explicit NoPointAfter(sdpcut_ctx *ctx) : h(ctx) {}
-    ~NoPointAfter()
-    {
-        h->have_point = false;
-        h->scored = 0; h->obj_partial = false;
-        h->last_total = -1;
-    }
-};
+// (NoPointAfter, NoBoxAfter -- what both calls leave the handle with -- are in common.h: the triangle batch shares them)
 
 // the boxes of a boxed batch as the caller hands them over: row p of lb / ub (stride ld) is the box of point p
 struct BoxRows {
     const double *lb, *ub;
     int64_t ld;
-};
-
-// Both boxed calls leave the handle without a box, whichever way they return (the loop route and a redone point set one).
-struct NoBoxAfter {
-    sdpcut_ctx *h;
-    explicit NoBoxAfter(sdpcut_ctx *ctx) : h(ctx) {}
-    ~NoBoxAfter()
-    {
-        if (!h->box_set) return;
-        (void)sdpcut_sync(h);      // (launches of the last point's scoring read the box tables)
-        h->box_set = false;
-        h->box_lb.clear(); h->box_ub.clear();
-    }
 };
 
 // the P points into the staging block and, by one launch, into the device table; ws: see points_copy_kernel.  bx (a boxed batch):

@@ -188,7 +188,7 @@ int topk_select_enqueue(sdpcut_ctx *h, int mode, int64_t k, double score_add, in
 
 // Head of a ranking over n PRECOMPUTED keys in h->d_key_a (0 = not in the class), ties by index:
 // idx_out = entry index, val_out = the key's low 63 bits as a double; cnt as in topk_select_on_device.
-int topk_select_keys_on_device(sdpcut_ctx *h, int64_t n, int64_t k, int64_t *d_idx_out, double *d_val_out, int64_t cnt[5])
+int topk_select_keys_enqueue(sdpcut_ctx *h, int64_t n, int64_t k, int64_t *d_idx_out, double *d_val_out, const int64_t **d_counters_out)
 {
     if (k < 1 || k > TK_MAXK || n < 1 || n > h->key_n) return sdpcut_fail(h, SDPCUT_EINVAL, "top-k select: k / n out of range");
     // (always through the big-head merge: it is the one with the raw key output)
@@ -201,7 +201,16 @@ int topk_select_keys_on_device(sdpcut_ctx *h, int64_t n, int64_t k, int64_t *d_i
     const TkJob j = {ws, TK_MODE_FEAS, n, kk, 0, nullptr, nullptr, 0, 0.0, d_idx_out, d_val_out, 1, k};
     rc = topk_run(h, p, j, true);
     if (rc) return rc;
-    HIP_TRY(h, hipMemcpyAsync(cnt, ws->counters, 5 * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    *d_counters_out = ws->counters;
+    return 0;
+}
+
+int topk_select_keys_on_device(sdpcut_ctx *h, int64_t n, int64_t k, int64_t *d_idx_out, double *d_val_out, int64_t cnt[5])
+{
+    const int64_t *d_cnt = nullptr;
+    const int rc = topk_select_keys_enqueue(h, n, k, d_idx_out, d_val_out, &d_cnt);
+    if (rc) return rc;
+    HIP_TRY(h, hipMemcpyAsync(cnt, d_cnt, 5 * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, sdpcut_sync(h));
     return 0;
 }

@@ -7,8 +7,8 @@
 #include <cstring>
 
 #include "common.h"
-
-#define TRI_VIOL_THRES 1e-7     /* _THRES_TRI_VIOL, cut_select_qp.py:33 */
+#include "tri_dev.h"        // TRI_VIOL_THRES, the row of an entry, the block scan
+#include "tri_layout.h"
 
 // key: bit 63 = density 3, low bits = the positive violation's IEEE image (positive doubles
 // order like integers); 0 = not violated.  Violations are <= 2, so bit 63 is free.
@@ -68,6 +68,7 @@ int tri_preprocess(sdpcut_ctx *h, const uint8_t *adjacency, int64_t *n_triples)
         HIP_TRY(h, hipMemcpy(h->d_tri_dense3, d3.data(), (size_t)T, hipMemcpyHostToDevice));
     }
     h->n_tri = T;
+    h->tri_ready = true;
     h->tri_host = tri;
     h->tri_dense_host = d3;
     if (n_triples) *n_triples = T;
@@ -112,3 +113,109 @@ int tri_separate(sdpcut_ctx *h, int64_t max_out, int64_t *d_entry_out, double *d
     if (n_written) *n_written = w;
     return 0;
 }
+
+// ------------------------------------------------------------------------------------------
+// The round with its rows (include/sdpcut.h: sdpcut_tri_round_csr): violation launch, the selection of tri_separate -- enqueued, not
+// waited for --, then ONE workgroup writes the rows of the selected entries into the handle's pinned block, a block scan over
+// the row lengths placing them (no look-back, no wait on another workgroup); one host wait.  With a node box the violation
+// launch reads the box table of the point (box.hip: box_point_kernel, in front of it in stream order) and the rows are the
+// box's facets in the original variables (tri_dev.h: tri_row).
+
+#define TRI_EMIT_WAVES 4
+// nviol: the violation launch's count; sel_cnt: the selection's counters (word 4: void) or NULL where nothing was selected
+__global__ __launch_bounds__(TRI_EMIT_WAVES * 64) void tri_emit_kernel(int64_t cap, const int64_t *nviol, const int64_t *sel_cnt, const int64_t *ent,
+                                                                        const double *vio, int64_t T, const int32_t *tri, const double *ld, int32_t nv,
+                                                                        int64_t L, char *block)
+{
+    __shared__ uint32_t s_wave[TRI_EMIT_WAVES];
+    const TriLayout y = tri_layout(cap);
+    const TriBlockPtrs B = {(int64_t *)block, (int64_t *)(block + y.entry), (double *)(block + y.viol), (double *)(block + y.rhs),
+                            (double *)(block + y.values), (int32_t *)(block + y.indptr), (int32_t *)(block + y.indices)};
+    const int64_t nvl = nviol[0], vflag = sel_cnt ? sel_cnt[4] : 0;
+    const int64_t w = vflag ? 0 : (nvl < cap ? nvl : cap);
+    tri_emit_rows<TRI_EMIT_WAVES>(w, [&](int64_t i) { return ent[i]; }, [&](int64_t i) { return vio[i]; }, tri, T, ld, nv, L, B, nvl, vflag, s_wave);
+}
+
+void tri_out_from_block(const void *block, sdpcut_tri_csr_t *out)
+{
+    const TriLayout y = tri_layout(out->cap);
+    const char *b = (const char *)block;
+    const int64_t *hdr = (const int64_t *)b;
+    out->n_rows = hdr[0];
+    out->n_violated = hdr[1];
+    out->nnz = hdr[2];
+    out->entry = (const int64_t *)(b + y.entry);
+    out->viol = (const double *)(b + y.viol);
+    out->rhs = (const double *)(b + y.rhs);
+    out->values = (const double *)(b + y.values);
+    out->indptr = (const int32_t *)(b + y.indptr);
+    out->indices = (const int32_t *)(b + y.indices);
+}
+
+// one pass: violations, selection (where cap > 0), rows; waited for.  -> the block's void word
+static int tri_round_pass(sdpcut_ctx *h, int64_t cap, int64_t *d_e, double *d_v, int64_t *void_flag)
+{
+    const int64_t T = h->n_tri, E = 4 * T;
+    HIP_TRY(h, hipMemsetAsync(h->d_counters, 0, 8 * sizeof(int64_t), h->stream));
+    hipLaunchKernelGGL(tri_viol_kernel, dim3((int)((T + 255) / 256)), dim3(256), 0, h->stream, T, h->d_tri, h->d_tri_dense3,
+                       (const double *)(h->box_set ? h->d_vars_box : h->d_vars), h->nb_vars, h->L, h->d_key_a, h->d_val_a, h->d_counters);
+    HIP_TRY(h, hipGetLastError());
+    const int64_t *d_cnt = nullptr;
+    if (cap > 0) {
+        const int rc = topk_select_keys_enqueue(h, E, cap, d_e, d_v, &d_cnt);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(tri_emit_kernel, dim3(1), dim3(TRI_EMIT_WAVES * 64), 0, h->stream, cap, (const int64_t *)h->d_counters, d_cnt, (const int64_t *)d_e,
+                       (const double *)d_v, T, (const int32_t *)h->d_tri, (const double *)(h->box_set ? h->d_box_ld : nullptr), h->nb_vars, h->L,
+                       (char *)h->pinned_dev);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, sdpcut_sync(h));      // the one wait of the call
+    *void_flag = ((const int64_t *)h->pinned)[3];
+    return 0;
+}
+
+extern "C" {
+
+int sdpcut_tri_round_csr(sdpcut_handle h, const double *vars_values, int64_t max_out, sdpcut_tri_csr_t *out)
+{
+    if (!h) return SDPCUT_EINVAL;
+    SDPCUT_NO_PENDING(h);
+    if (!out) return sdpcut_fail(h, SDPCUT_EINVAL, "out is NULL");
+    if (max_out < 0 || max_out > 16384) return sdpcut_fail(h, SDPCUT_EINVAL, "tri_round_csr: max_out must be 0 .. 16384 (the reference takes <= 10000)");
+    if (!h->tri_ready) return sdpcut_fail(h, SDPCUT_ESTATE, "tri_round_csr: sdpcut_tri_preprocess first");
+    if (!vars_values && !h->have_point) return sdpcut_fail(h, SDPCUT_ESTATE, "set_point first");
+    int rc;
+    if (vars_values && (rc = sdpcut_set_point(h, vars_values))) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int64_t T = h->n_tri, E = 4 * T;
+    const int64_t cap = max_out < E ? max_out : E;
+    std::memset(out, 0, sizeof(*out));
+    out->cap = cap;
+    if ((rc = ensure_pinned(h, tri_layout(cap).bytes))) return rc;
+    if (E == 0) {      // an empty list: an empty block, nothing launched
+        std::memset(h->pinned, 0, tri_layout(0).bytes);
+        tri_out_from_block(h->pinned, out);
+        return SDPCUT_OK;
+    }
+    if ((rc = ensure_stage(h, (size_t)(cap < 1 ? 1 : cap) * 16))) return rc;
+    int64_t *d_e = (int64_t *)h->d_stage;
+    double *d_v = (double *)((char *)h->d_stage + (size_t)(cap < 1 ? 1 : cap) * 8);
+    if ((rc = ensure_rank_ws(h, E > h->N ? E : h->N))) return rc;      // (as tri_separate: the key array serves the candidate list as well)
+    h->last_total = -1;
+    int64_t vflag = 0;
+    if ((rc = tri_round_pass(h, cap, d_e, d_v, &vflag))) return rc;
+    if (vflag) {
+        // a bounded wait of the fused selection expired: the same selection with one launch per digit has no waits (tri_separate)
+        const bool fused = h->fused_tail;
+        h->fused_tail = false;
+        rc = tri_round_pass(h, cap, d_e, d_v, &vflag);
+        h->fused_tail = fused;
+        ++h->stat_fallbacks;
+        if (rc) return rc;
+        if (vflag) return sdpcut_fail(h, SDPCUT_EHIP, "tri_round_csr: selection void");
+    }
+    tri_out_from_block(h->pinned, out);
+    return SDPCUT_OK;
+}
+
+} // extern "C"

@@ -666,6 +666,42 @@ class GpuCutSelectionMixin(object):
         # (built here: no second copy; the reference hands integer coefficients and right-hand sides, :833-836)
         return self._gpu_add_csr((indptr, ind, val, np.where(four, 0.0, -1.0)), copy=False, integral=True)
 
+    def _separate_and_add_triangle_node(self, sel_size, vars_values):
+        """The triangle step of a run at a node (``cut_select_algo(box=..., triangle_on=True, triangle_box=True)``): the
+        inequalities of the NODE'S box -- the facets in ``x' = (x - l) / d``, ``X'``, mapped back to rows in the original
+        variables (:mod:`triangles`) -- separated, ranked and assembled on the device (``Scorer.tri_round_csr`` on the triangle
+        handle, which holds the run's box).  The number of cuts follows the reference's rule (:844-845) on the node's count."""
+        r = self._gpu_tri.tri_round_csr(self._TRI_CUTS_PER_ROUND_MAX, point=_lp_point(vars_values))
+        nb_viol = r["n_violated"]
+        nb_tri_cuts = min(max(min(self._TRI_CUTS_PER_ROUND_MIN, int(np.floor(sel_size * nb_viol))),
+                              min(self._TRI_CUTS_PER_ROUND_MAX, nb_viol)), r["n_rows"])
+        if nb_tri_cuts <= 0:
+            return self._gpu_add_csr(None)
+        indptr = r["indptr"][:nb_tri_cuts + 1]
+        nnz = int(indptr[-1])
+        return self._gpu_add_csr((indptr, r["indices"][:nnz], r["values"][:nnz], r["rhs"][:nb_tri_cuts]), copy=True)
+
+    def separate_triangles_points(self, points, max_cuts, boxes=None):
+        """The triangle inequalities at P LP points in one device call with one host wait (``Scorer.tri_round_csr_points``): the
+        open nodes of a tree search.  points [P, n(n+1)/2 + n]; boxes [P, 2, n] = (lb, ub) of every point's node, or None (the
+        root's inequalities everywhere).  -> list of P ``(csr, n_violated)``: csr = (indptr, indices, values, rhs) of the first
+        ``max_cuts`` violated inequalities of point p in rank order, sense >=, as :meth:`_gpu_add_csr` takes them (copies: they
+        outlive the next call); n_violated the length of the full list.  The call keeps a handle of its own with the triples
+        of the bound instance's pattern (``self._Q_adj``): the triangle handle of a running loop, which may hold the run's box,
+        is not touched."""
+        adj = np.ascontiguousarray(self._gpu_dense_adj(), dtype=np.uint8)
+        key = (self._nb_vars, adj.tobytes())
+        if getattr(self, "_gpu_tri_points_key", None) != key:
+            if getattr(self, "_gpu_tri_points", None) is not None:      # another pattern: the old handle goes first
+                self._gpu_tri_points.close()
+                self._gpu_tri_points = self._gpu_tri_points_key = None
+            sc = _capi.Scorer(self._gpu_device)
+            sc.set_instance(self._nb_vars, np.asarray(self._Q_arr, dtype=np.float64))
+            sc.tri_preprocess(adj)
+            self._gpu_tri_points, self._gpu_tri_points_key = sc, key
+        res = self._gpu_tri_points.tri_round_csr_points(points, int(max_cuts), boxes=boxes, copy=True)
+        return [((r["indptr"], r["indices"], r["values"], r["rhs"]), r["n_violated"]) for r in res]
+
     # the reference reaches these two through name-mangled private names inside class CutSolver
     _CutSolver__preprocess_triangle_ineq = _preprocess_triangle_ineq
     _CutSolver__separate_and_add_triangle = _separate_and_add_triangle
@@ -730,7 +766,10 @@ class CutSolver(GpuCutSelectionMixin):
     def _round_counts(self, sdp, point):
         """the counts of a round that added ``sdp`` eigen-cuts: the triangle inequalities are separated behind them"""
         run = self._run
-        return {"sdp": sdp, "tri": self._separate_and_add_triangle(run.sel_size, point) if run.triangle_on else 0}
+        if not run.triangle_on:
+            return {"sdp": sdp, "tri": 0}
+        tri_step = self._separate_and_add_triangle_node if getattr(run, "triangle_box", False) else self._separate_and_add_triangle
+        return {"sdp": sdp, "tri": tri_step(run.sel_size, point)}
 
     def _round_plain(self, round_no, point):
         """selection, then generation, as the reference's loop calls them (cut_select_qp.py:165-182)"""
@@ -802,7 +841,7 @@ class CutSolver(GpuCutSelectionMixin):
                         triangle_on=False, strong_only=False, max_subs=_THRES_MAX_SUBS, on_round=None, plots=False, sol=0,
                         ch_ext=0, max_parallel=None, pool_factor=4, cuts_per_set=1, row_quota=None,
                         pool_max_age=None, pool_drop_age=10, pool_return=None, pool_tight_tol=1e-9, pool_viol_tol=1e-6, box=None,
-                        objpar_weight=0.0):
+                        objpar_weight=0.0, triangle_box=False):
         """Cutting-plane rounds on a BoxQP ``.in`` file, same arguments and default return tuple as
         the reference's entry point (cut_select_qp.py:73-221), with HiGHS as LP solver, the native
         cover enumeration and the GPU selection / generation / triangle separation in between.
@@ -847,6 +886,10 @@ class CutSolver(GpuCutSelectionMixin):
         ``lb <= x <= ub`` -- the LP is the node's relaxation (``harness.boxqp_relaxation(inst, lb, ub)``) and the optimality
         measures are the node's (``Scorer.set_box`` on the run's own handle, DESIGN.md section 5 "Node boxes").  The run's box is
         this argument alone: a box set with :meth:`set_node_box` is neither used nor changed.
+        ``triangle_box`` (False = today's triangle step, untouched; needs ``box`` and ``triangle_on``, ValueError otherwise): the
+        triangle step separates the inequalities of the NODE'S box instead of the unit box's -- the same facets in the box's own
+        variables, which are valid at the node and tighter, as rows in the original variables assembled on the device
+        (``Scorer.tri_round_csr``, DESIGN.md section 5 "Triangle inequalities at nodes").
         -> (bound per solve, total s, round s, separation s, PSD cuts per round, triangle cuts per
         round, number of candidates)."""
         from timeit import default_timer as clock
@@ -866,6 +909,8 @@ class CutSolver(GpuCutSelectionMixin):
         assert (ch_ext in [0, 1, 2]), "Chordal extension flags: 0-P^E_3, 1-P^bar(E)_3, 2-bar(P*_3)!"      # :94
         if ch_ext == 2 and dim != 3:      # (with the other argument checks: before the file is read and a handle is made)
             raise ValueError("ch_ext = 2 is a cover of dimension 3 only")
+        if triangle_box and (box is None or not triangle_on):
+            raise ValueError("triangle_box switches the triangle step of a node's run to the node's inequalities: it needs box= and triangle_on=True")
         if max_parallel is not None:
             if strat not in (1, 2, 4, 6):
                 raise AssertionError("max_parallel filters the ranked head of strategies 1 (feasibility), 2 (optimality), 4 (combined) and 6 (efficacy) only")
@@ -918,13 +963,15 @@ class CutSolver(GpuCutSelectionMixin):
                 sc.set_objective(lp.obj)      # [Q_arr | c]: the LP's columns are the LP point's
         if triangle_on:
             self._preprocess_triangle_ineq()
+            if triangle_box:
+                self._gpu_tri.set_box(*node_box)
         rounds_stats, round_std_devs, rounds_all_cuts = [], [], []      # figure 8 (:144)
         if strat == 0:      # the cover's scorer already holds the instance
             self._gpu_dense_sc, self._gpu_dense_key = sc, (self._nb_vars, id(self._Q_arr))
         # what the round functions read, and the strategy they update (the combined strategy's switch)
         self._run = run = SimpleNamespace(strat=strat, quota=quota, sel_size=sel_size, triangle_on=triangle_on, strong_only=strong_only,
                                           max_parallel=max_parallel, pool_factor=pool_factor, m_cuts=m_cuts, row_quota=row_quota,
-                                          figure8=(rounds_stats, round_std_devs, rounds_all_cuts))
+                                          triangle_box=bool(triangle_box), figure8=(rounds_stats, round_std_devs, rounds_all_cuts))
         sep_fn = self._round_plain if m_cuts == 1 and max_parallel is None else self._round_one_call
         if pooled:
             from . import cutpool

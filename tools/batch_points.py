@@ -23,12 +23,22 @@ call (csrc/batch_route.h); a further row times it with sel = pool = 400, where i
 plain round_csr_points at P = 64 and sel 100, the price of the filter; --plain-only times that alone, and --root DIR takes the
 package from another checkout (the parent commit's, built), so that the same tool gives the value before and after a change.
 
-usage: tools/batch_points.py [--boxes | --diverse] [--repeats R] [--calls C] [--loop-only] [--plain-only] [--root DIR] [--out [FILE]]
+--triangles: the triangle inequalities (Scorer.tri_round_csr_points, Scorer.tri_round_csr), medians of --repeats (default 5) blocks:
+  * the batch call against the loop it replaces on the same handle -- P x (set_point, tri_separate, the numpy build of the rows of
+    GpuCutSelectionMixin._separate_and_add_triangle), timed together -- at P in {8, 64, 256} McCormick points and heads of 4096
+    entries, over the triangle lists (dim-independent) of spar020-100-1, spar040-030-1 and spar070-050-1, without and with a box
+    per point (the loop then is P x (set_box, tri_round_csr): there is no older way to a node's rows);
+  * tri_round_csr against set_point + tri_separate + the numpy build at one point, spar125-075-1, 10 000 rows;
+  * at the depth-1 / depth-2 nodes of tools/node_rounds.py (spar020-100-1, spar040-030-1): the violated inequalities at the node's
+    LP point with the unit box's facets and with the node's, and the bound after 4 rounds of cut_select_algo(strat 1, triangle_on)
+    with triangle_box off and on.
+
+usage: tools/batch_points.py [--boxes | --diverse | --triangles] [--repeats R] [--calls C] [--loop-only] [--plain-only] [--root DIR] [--out [FILE]]
   --boxes       the boxed batch against the loop of set_box + single-point rounds
   --diverse     the filtered batch against the loop of single-point filtered rounds (default --repeats 5)
   --loop-only   time the single-point loop only (runs on a library without the batched entry points: the parent commit's)
   --out         also write the table to FILE (default profiles/batch_points.txt; with --boxes profiles/boxed_points.txt; with
-                --diverse profiles/diverse_points.txt)"""
+                --diverse profiles/diverse_points.txt; with --triangles profiles/tri_points.txt)"""
 import argparse
 import gc
 import os
@@ -147,6 +157,119 @@ def diverse_main(args):
             f.write(text)
 
 
+def triangles_main(args):
+    """--triangles: see the module's docstring"""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import node_rounds
+    from tri_rows_numpy import numpy_rows as numpy_tri_rows      # the one copy of the loop's host build
+    head = 4096
+    lines = ["# tools/batch_points.py --triangles --repeats %d: ms per call, us per point; median over the blocks (min .. max)" % args.repeats,
+             "# batched = tri_round_csr_points(P points, %d[, boxes=]); loop = P x (set_point, tri_separate(%d), numpy rows); with boxes: P x (set_box, "
+             "tri_round_csr)" % (head, head)]
+
+    def handle(fname):
+        inst = harness.parse_boxqp(os.path.join(INST, fname))
+        sc = pkg.Scorer(0)
+        sc.set_instance(inst["nb_vars"], inst["Q_arr"])
+        tri, _ = sc.tri_preprocess(inst["adj"])
+        return inst, sc, np.asarray(tri, dtype=np.int64)
+
+    for fname in ("spar020-100-1.in", "spar040-030-1.in", "spar070-050-1.in"):
+        inst, sc, tri64 = handle(fname)
+        n = inst["nb_vars"]
+        pts_all = np.stack([harness.random_mccormick_point(n, np.random.default_rng(100 + i)) for i in range(max(BOXED_POINTS))])
+        boxes_all = np.stack([seeded_box(n, i) for i in range(max(BOXED_POINTS))])
+        bpts_all = np.stack([nodebox.inverse_tables(None, pts_all[i], boxes_all[i, 0], boxes_all[i, 1])[1] for i in range(max(BOXED_POINTS))])
+        lines.append("")
+        lines.append("%s: %d triples, %d inequalities" % (fname[:-3], tri64.shape[0], 4 * tri64.shape[0]))
+        lines.append("  boxed    P | batched ms/call          us/point | loop ms/call             us/point | loop / batched | one-wait points | violated (median)")
+        for boxed in (False, True):
+            for P in BOXED_POINTS:
+                pts = np.ascontiguousarray((bpts_all if boxed else pts_all)[:P])
+                bx = np.ascontiguousarray(boxes_all[:P]) if boxed else None
+                calls = args.calls or max(4, 512 // P)
+
+                def loop():
+                    for p in range(P):
+                        if bx is not None:
+                            sc.set_box(bx[p, 0], bx[p, 1])
+                            sc.tri_round_csr(head, point=pts[p])
+                        else:
+                            sc.set_point(pts[p])
+                            ent, _, _ = sc.tri_separate(head)
+                            numpy_tri_rows(tri64, n, ent)
+                    if bx is not None:
+                        sc.clear_box()
+
+                def batched():
+                    return sc.tri_round_csr_points(pts, head, boxes=bx)
+
+                f0 = sc.get_stat(_capi.STAT_TRI_POINTS_FAST)
+                nviol = int(np.median([r["n_violated"] for r in batched()]))
+                fast = sc.get_stat(_capi.STAT_TRI_POINTS_FAST) - f0
+                for f in (batched, loop):
+                    timed(f, max(2, calls // 4))
+                t = {"batched": [], "loop": []}
+                for _ in range(args.repeats):
+                    for f in (batched, loop):
+                        t[f.__name__].append(timed(f, calls))
+                lines.append("  %5s %4d | %s | %s | %14.2f | %d of %d | %d" % ("yes" if boxed else "no", P, median_cell(t["batched"], P), median_cell(t["loop"], P),
+                                                                          np.median(t["loop"]) / np.median(t["batched"]), fast, P, nviol))
+                print(lines[-1], flush=True)
+        sc.close()
+
+    inst, sc, tri64 = handle("spar125-075-1.in")
+    n = inst["nb_vars"]
+    vv = harness.random_mccormick_point(n, np.random.default_rng(100))
+
+    def device_rows():
+        return sc.tri_round_csr(10000, point=vv)
+
+    def host_rows():
+        sc.set_point(vv)
+        ent, _, _ = sc.tri_separate(10000)
+        numpy_tri_rows(tri64, n, ent)
+
+    rows = device_rows()["n_rows"]
+    for f in (device_rows, host_rows):
+        timed(f, 8)
+    t = {"device_rows": [], "host_rows": []}
+    for _ in range(args.repeats):
+        for f in (device_rows, host_rows):
+            t[f.__name__].append(timed(f, args.calls or 32))
+    lines.append("")
+    lines.append("spar125-075-1: %d triples, one point, %d rows" % (tri64.shape[0], rows))
+    lines.append("  tri_round_csr                          ms/call | %s" % median_cell(t["device_rows"], 1))
+    lines.append("  set_point + tri_separate + numpy rows  ms/call | %s" % median_cell(t["host_rows"], 1))
+    print("\n".join(lines[-3:]), flush=True)
+    sc.close()
+
+    lines.append("")
+    lines.append("nodes of tools/node_rounds.py: violated inequalities at the node's LP point, bound after 4 rounds (strategy 1, dim 3, sel 0.1, triangle_on)")
+    lines.append("  instance        node                                   | violated unit-box  node-box | bound triangle_box off            on")
+    for fname in ("spar020-100-1.in", "spar040-030-1.in"):
+        inst, sc, _ = handle(fname)
+        for name, lb, ub in node_rounds.nodes_of(inst):
+            _, vv = node_rounds.solve_node(inst, lb, ub)
+            unit = sc.tri_round_csr(0, point=vv)["n_violated"]
+            sc.set_box(lb, ub)
+            node = sc.tri_round_csr(0, point=vv)["n_violated"]
+            sc.clear_box()
+            bound = []
+            for on in (False, True):
+                out = pkg.CutSolver().cut_select_algo(os.path.join(INST, fname), 3, 0.1, strat=1, nb_rounds_cuts=4, triangle_on=True, box=(lb, ub),
+                                                      triangle_box=on)
+                bound.append(out[0][-1])
+            lines.append("  %-15s %-38s | %17d %9d | %24.6f %13.6f" % (fname[:-3], name, unit, node, bound[0], bound[1]))
+            print(lines[-1], flush=True)
+        sc.close()
+    text = "\n".join(lines) + "\n"
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=0)
@@ -156,10 +279,17 @@ def main():
     ap.add_argument("--calls", type=int, default=0, help="calls per timing (default: about 4096 points' worth, at least 8)")
     ap.add_argument("--loop-only", action="store_true")
     ap.add_argument("--boxes", action="store_true")
+    ap.add_argument("--triangles", action="store_true")
     ap.add_argument("--out", nargs="?", const="", default=None)
     args = ap.parse_args()
     diverse = args.diverse or args.plain_only
-    args.repeats = args.repeats or (5 if diverse else 9)
+    args.repeats = args.repeats or (5 if diverse or args.triangles else 9)
+    if args.triangles:
+        if args.out == "":
+            args.out = os.path.join(ROOT, "profiles", "tri_points.txt")
+        gc.collect()
+        gc.freeze()
+        return triangles_main(args)
     if args.out == "":
         args.out = os.path.join(ROOT, "profiles", "diverse_points.txt" if diverse else "boxed_points.txt" if args.boxes else "batch_points.txt")
     if diverse:
