@@ -189,6 +189,16 @@ enum { SDPCUT_OPT_KERNEL = 1, SDPCUT_OPT_TIMING = 2, SDPCUT_OPT_FUSE_KEYS = 3, S
  * head of <= 64 entries).
  * The hook never waits, never spins and launches nothing of its own.  With the option at 0 every call does what it did before. */
 #define SDPCUT_INJECT_GIVEUP(site, first, count) (((int64_t)(site) << 16) | ((int64_t)(first) << 8) | (int64_t)(count))
+/* SDPCUT_OPT_EMIT_HEAD (default 1): the scoring launch of a fused combined round under SDPCUT_OPT_SKIP_NONVIOLATED also appends every
+ * candidate it finds strong -- its selection key and its index -- to a list in the selection's workspace, and a round that resolves
+ * to its strong regime selects its head from that list instead of rebuilding the key of every candidate from the score arrays
+ * (csrc/topk_route.h: TK_ROUTE_EMITTED).  Same head, scores, rows, counters and new_strat, bit for bit; a round in the other regime,
+ * or one whose list overflowed, scans the scores as with the option off.  0: nothing is appended, the selection is the one of
+ * TK_ROUTE_ONFLY (A/B, tests).  SDPCUT_ESTATE while a round is pending.
+ * SDPCUT_OPT_EMIT_CAP (default 0) -- TEST ONLY: > 0 caps the list at that many entries, so that the overflow path can be run on a
+ * short list; 0: the capacity the workspace gives (half the list length). */
+#define SDPCUT_OPT_EMIT_HEAD 18
+#define SDPCUT_OPT_EMIT_CAP 19
 
 /* Counters of a handle: SDPCUT_STAT_ROUNDS = fused rounds served (sdpcut_select_round*),
  * SDPCUT_STAT_SELECT_FALLBACKS = rounds whose radix selection declared itself void (a grid barrier
@@ -234,6 +244,10 @@ enum { SDPCUT_STAT_ROUNDS = 1, SDPCUT_STAT_SELECT_FALLBACKS = 2, SDPCUT_STAT_SCO
        SDPCUT_STAT_DIVERSE_POINTS_FAST = 17, SDPCUT_STAT_INJECTED = 18 };
 /* (a macro, not an enumerator: the enumeration above is the closed set of codes 1 .. 18 that tests/test_diverse_points_cpu.py pins) */
 #define SDPCUT_STAT_TRI_POINTS_FAST 19
+/* SDPCUT_STAT_EMITTED_SELECTIONS = selections since the handle was made whose head came from the list the scoring launch emitted
+ * (SDPCUT_OPT_EMIT_HEAD; TK_ROUTE_EMITTED in its strong regime without an overflow).  Read from the device: the call waits for the
+ * handle's stream. */
+#define SDPCUT_STAT_EMITTED_SELECTIONS 20
 int sdpcut_get_stat(sdpcut_handle h, int which, int64_t *value);
 
 /* The fp32 filter (SDPCUT_OPT_FP32_FILTER) of the network set for k-variable candidates: *margin = the proven bound on

@@ -39,6 +39,9 @@ STAT_TRI_POINTS_FAST = 19   # points of tri_round_csr_points answered by its one
 STAT_DIVERSE_POINTS_FAST = 17   # points of round_csr_points_diverse answered by its one-wait route (include/sdpcut.h)
 OPT_INJECT_GIVEUP = 17   # TEST ONLY: the bounded device waits give up unasked (include/sdpcut.h); value = inject_giveup(site, first, count)
 STAT_INJECTED = 18       # TEST ONLY: launches the option has hit
+OPT_EMIT_HEAD = 18       # the skipping score launch emits its strong members, the strong regime selects from that list (include/sdpcut.h); default on
+OPT_EMIT_CAP = 19        # TEST ONLY: capacity of that list in entries (0: what the workspace gives)
+STAT_EMITTED_SELECTIONS = 20   # selections whose head came from the emitted list
 INJECT_SELECT, INJECT_LOOKBACK = 1, 2
 
 

@@ -79,8 +79,8 @@ int sdpcut_create(int device_id, sdpcut_handle *out)
     h->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     if (hipSetDevice(device_id) != hipSuccess || hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess ||
         hipMalloc((void **)&h->d_counters, 8 * sizeof(int64_t)) != hipSuccess ||
-        hipMalloc((void **)&h->d_stats, 6 * sizeof(unsigned long long)) != hipSuccess ||
-        hipMemset(h->d_stats, 0, 6 * sizeof(unsigned long long)) != hipSuccess) {
+        hipMalloc((void **)&h->d_stats, 8 * sizeof(unsigned long long)) != hipSuccess ||
+        hipMemset(h->d_stats, 0, 8 * sizeof(unsigned long long)) != hipSuccess) {
         delete h;
         return sdpcut_fail(nullptr, SDPCUT_EHIP, "stream / counter allocation failed");
     }
@@ -177,6 +177,15 @@ int sdpcut_set_option(sdpcut_handle h, int option, int64_t value)
         SDPCUT_NO_PENDING(h);
         h->fp32_filter = value != 0;
         return SDPCUT_OK;
+    case SDPCUT_OPT_EMIT_HEAD:
+        SDPCUT_NO_PENDING(h);
+        h->emit_head = value != 0;
+        return SDPCUT_OK;
+    case SDPCUT_OPT_EMIT_CAP:
+        SDPCUT_NO_PENDING(h);
+        if (value < 0) return sdpcut_fail(h, SDPCUT_EINVAL, "SDPCUT_OPT_EMIT_CAP: 0, or the capacity in entries");
+        h->emit_cap_opt = value;
+        return SDPCUT_OK;
     case SDPCUT_OPT_EXACT_HEAD:
         SDPCUT_NO_PENDING(h);
         if (value != 0) SDPCUT_NO_BOX(h, "SDPCUT_OPT_EXACT_HEAD");      // (the reference has no boxes: no reference-exact bits at a node)
@@ -270,6 +279,14 @@ int sdpcut_get_stat(sdpcut_handle h, int which, int64_t *value)
     case SDPCUT_STAT_EXACT_GAVE_UP: *value = h->stat_exact_gave_up; return SDPCUT_OK;
     case SDPCUT_STAT_EXACT_RETRIES: *value = h->stat_exact_retries; return SDPCUT_OK;
     case SDPCUT_STAT_SDP_UNCONVERGED: return sdp_unconverged(h, value);
+    case SDPCUT_STAT_EMITTED_SELECTIONS: {
+        unsigned long long v = 0;
+        HIP_TRY(h, hipSetDevice(h->device));
+        HIP_TRY(h, hipMemcpyAsync(&v, h->d_stats + 6, sizeof(v), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, sdpcut_sync(h));
+        *value = (int64_t)v;
+        return SDPCUT_OK;
+    }
     case SDPCUT_STAT_DIRECT_SELECTIONS:
     case SDPCUT_STAT_PF_BIN:
     case SDPCUT_STAT_PF_FLOOR:

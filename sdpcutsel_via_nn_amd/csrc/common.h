@@ -140,7 +140,7 @@ struct sdpcut_ctx {
     bool eig_kernel = true;        // SDPCUT_OPT_EIG_KERNEL: eigenvalue-only launches run eig_only_kernel (eig.hip)
     bool pf_counted = false;       // the scoring launches of the current round all counted the fine histogram (launch_score)
     bool prefilter = true;         // SDPCUT_OPT_PREFILTER: fine histogram in the score kernels, direct selection (topk_dev.h)
-    unsigned long long *d_stats = nullptr;   // device counters that outlive a round: [0] direct selections, [1..3] its diagnostics, [4] nb_violated of a skipped sharded head, [5] fp64 evaluations of a filtering launch
+    unsigned long long *d_stats = nullptr;   // device counters that outlive a round: [0] direct selections, [1..3] its diagnostics, [4] nb_violated of a skipped sharded head, [5] fp64 evaluations of a filtering launch, [6] selections from the emitted list
     bool coop_launch = false;      // SDPCUT_OPT_COOP_LAUNCH: cooperative launch of the kernels with grid barriers (+20 us per round)
     int64_t stat_rounds = 0, stat_fallbacks = 0, stat_tie_splits = 0;   // sdpcut_get_stat
     // SDPCUT_OPT_INJECT_GIVEUP (tests): launches of inject_site (1 selection, 2 row-assembly look-back) -- inject_skip of them pass,
@@ -204,6 +204,12 @@ struct sdpcut_ctx {
     // SDPCUT_OPT_FP32_FILTER (score_mfma_filter_kernel): the skipping launch filters in fp32 where the network qualifies
     bool fp32_filter = true;
     bool filter_launched = false;  // ... and it was the filtering one
+    // SDPCUT_OPT_EMIT_HEAD: the skipping launch of a round whose regime the device resolves appends its strong members (key, index)
+    // to a list in d_key_a -- a stage-3 selection has no key array -- and the selection reads that list (TK_ROUTE_EMITTED)
+    bool emit_head = true;
+    int64_t emit_cap_opt = 0;      // SDPCUT_OPT_EMIT_CAP (tests): > 0 caps the list
+    bool emit_launched = false;    // the last launch_score emitted ...
+    int64_t emit_cap = 0;          // ... into a list of this many entries in d_key_a: (key, index) pairs of two 64-bit words
     // SDPCUT_STAT_NN_EVALUATED of the last launch that ran the network: 0 everybody (nn_eval_n), 1 the violated candidates
     // (nn_eval_n - SDPCUT_STAT_NN_SKIPPED), 2 the filter's survivors (d_stats[5], left there by the selection's first kernel)
     int nn_eval_mode = 0;
@@ -389,6 +395,7 @@ struct ScoreFuse {
     void *ws;
     int mode;      // TK_MODE_FEAS / OPT / STRONG of topk_route.h: whose keys to count
     int64_t k;     // head size of the selection (the streaming prefilter's bound rises to the k-th largest key); 0: no fine histogram
+    bool emit = false;   // a skipping launch appends its strong members to the handle's emitted list (sdpcut_ctx::emit_cap)
 };
 // strong_out (optional, device, 8 int64 replicas): the launches add the number of candidates with
 // obj_improve > 0 and lambda_min < -1e-15 to strong_out[workgroup % 8] (needs both flags; used by the device-resolved combined selection)

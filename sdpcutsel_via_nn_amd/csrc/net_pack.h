@@ -53,15 +53,19 @@ static inline bool filter_shape(int k, int H, int nh) { return k == 3 && H == 50
 //                    + |c| sum_j |W_ij| e_j                               the inputs' own error
 // The k-steps of a hidden layer hold neurons {16 t + 4 q + i, q = 0..3} for (t, i) in order -- the C/D fragment of one layer is the
 // B fragment of the next -- and those of the input layer inputs 4 s .. 4 s + 3.  That is the chain of rows 0 .. 47, the three
-// row tiles on the matrix core; k-steps (3, 0) and (3, 1), their last, hold neurons 48 and 49 alone.
+// row tiles on the matrix core; ONE k-step, their last, holds the tail neurons of the layer in front: neuron 48 + v on its slot
+// q = v (the kernel merges components 0 and 1 of the q = 0 lanes of fragment (t, 3) into that A operand; the packed blob keeps
+// them apart), exact zeros on q >= NT.  Terms 48 and 49 both count from the first term of that shared k-step: 2 roundings each.
 // TAIL ROWS.  A last row tile with NT = H - 48 <= 4 live rows (two at H = 50) does not run on the matrix core: each of its rows
 // is summed on the VALU, by the four lanes q = 0..3 of the candidate's column (score_mfma.hip: filter_pass_f32).  Lane q chains
-//   p_q = fma-chain( [q = 0: b~_i, then w~_i,48 a^_48, w~_i,49 a^_49 (the tail neurons of the layer in front)],
+//   p_q = fma-chain( [q = 0: b~_i, else 0], then ONE head link w~_i,48+q a^_(48+q) (the tail neuron of the layer in front that
+//                    lane q holds; on q >= NT the activation is an exact zero and the link adds it to an exact zero),
 //                    then its twelve terms j = 16 tk + 4 q + i' in the order of 4 tk + i' = 0 .. 11 ),
-// one rounding per fma (on q >= 1 the head of the chain adds exact zeros to an exact zero), and the lanes are summed as
+// one rounding per fma, and the lanes are summed as
 //   z_i = (p_q + p_(q^1)) + (p_(q^2) + p_(q^3)):  two more roundings for every term.
 // So in a tail row term j < 48 sees m_j = 12 - (4 tk + i') + 2 roundings (its own fma, the later ones of its lane, the tree),
-// tail term 48 + v sees NT - v + 12 + 2 and the bias NT + 12 + 2; these replace gamma(fan - before[j]) and gamma(fan) above.
+// every tail term 48 + v sees 1 + 12 + 2 (its head link, the twelve behind it, the tree) and so does the bias, which enters
+// that head link as its addend; these replace gamma(fan - before[j]) and gamma(fan) above.
 // In the input layer lane q chains the inputs q, 4 + q, 8 + q .. below the fan-in (`live` of them; a padded term adds an exact
 // zero) behind the bias on q = 0:  m_j = live - j / 4 + 2, and the bias sees the ceil(fan / 4) links of lane 0 and the tree.
 // Every other term of the bound -- conversion, inputs' error, tansig -- is that of the other rows.  (Widths whose last tile
@@ -110,6 +114,8 @@ static inline double net_filter_margin(int k, int nh, int H, int d_in, const dou
                     }
                     cnt += live;
                 }
+            if (NT > 0)
+                for (int j = 48; j < fan; ++j) before[j] = 48;      // the tail neurons share one k-step: 48 + v on q = v
         }
         // the tail rows' own count: roundings seen by term j, and by the bias
         int mtail[MAX_HIDDEN], mtail_bias = 0;
@@ -122,8 +128,8 @@ static inline double net_filter_margin(int k, int nh, int H, int d_in, const dou
                 mtail_bias = (fan + 3) / 4 + 2;
             } else {
                 for (int j = 0; j < 48; ++j) mtail[j] = 12 - (4 * (j / 16) + j % 4) + 2;      // j = 16 tk + 4 q + i: link 4 tk + i of 12
-                for (int j = 48; j < fan; ++j) mtail[j] = NT - (j - 48) + 12 + 2;
-                mtail_bias = NT + 12 + 2;
+                for (int j = 48; j < fan; ++j) mtail[j] = 1 + 12 + 2;      // lane q = j - 48: one head link, then its twelve
+                mtail_bias = 1 + 12 + 2;
             }
         }
         for (int i = 0; i < H; ++i) {

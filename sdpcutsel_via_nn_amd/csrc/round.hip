@@ -40,6 +40,7 @@ int score_for_selection(sdpcut_ctx *h, int strat, int64_t sel_size, int64_t cap,
     *stage = 0;
     *auto_out = false;
     h->skip_launched = false;
+    h->emit_launched = false;
     int rc;
     // a measure a skipped round left partial (same point, another selection): whole before anything ranks or counts by it -- a
     // feasibility selection too, whose nb_positive reads it
@@ -64,6 +65,7 @@ int score_for_selection(sdpcut_ctx *h, int strat, int64_t sel_size, int64_t cap,
             fuse.ws = ws;
             fuse.mode = fast_mode;
             fuse.k = (h->prefilter && h->N >= SDPCUT_PF_MIN_N) ? cap : 0;
+            fuse.emit = want_auto && h->emit_head;      // only a regime resolved on the device reads the list (TK_ROUTE_EMITTED)
             rc = launch_score(h, need, &fuse, &counted, strong);
         } else {
             rc = launch_score(h, need, nullptr, nullptr, strong);

@@ -29,9 +29,20 @@ static int launch_score_k(sdpcut_ctx *h, int K, uint32_t flags, hipEvent_t ev_st
                       h->kernel_variant == SDPCUT_KERNEL_MFMA && h->bucket[K].n == h->N && score_mfma_skip_built(K) &&
                       score_skip_applies(h->bucket[K].n, h->n_cu, K, h->skip_nonviolated);
     const ScorePlan p = skip ? score_plan_skip(h->bucket[K].n, h->n_cu, K, h->N, fuse->k, h->skip_nonviolated == 2) : plan_class(h, K, fuse);
-    const ScoreArgs A = fill_score_args(h, K, flags, fuse, strong_out, p);
+    ScoreArgs A = fill_score_args(h, K, flags, fuse, strong_out, p);
     if (skip) {
         if (A.pf_mloc == 0) h->pf_counted = false;
+        // SDPCUT_OPT_EMIT_HEAD: the strong members go to a list in the key array, which a selection that starts from this launch's
+        // histograms (stage 3) does not use: 16 bytes per entry, the key and the index
+        int64_t ecap = fuse->emit && A.strong_out && h->d_key_a ? h->key_n / 2 : 0;
+        if (ecap > 0xffffffffll) ecap = 0xffffffffll;
+        if (h->emit_cap_opt > 0 && h->emit_cap_opt < ecap) ecap = h->emit_cap_opt;
+        if (ecap > 0) {
+            A.emit = h->d_key_a;
+            A.emit_cap = (uint32_t)ecap;
+            h->emit_launched = true;
+            h->emit_cap = ecap;
+        }
         // SDPCUT_OPT_FP32_FILTER: an fp32 pass with a proven error bound in front of the fp64 one (NetDev::filter_ok)
         const bool filter = h->fp32_filter && A.net.filter_ok && score_mfma_filter_built(K);
         if (filter) score_mfma_filter_launch(K, A, p.grid, st, ev_start, ev_stop);
@@ -185,6 +196,7 @@ static int launch_score_form(sdpcut_ctx *h, uint32_t flags, const ScoreFuse *fus
     // (r5) did EVERY launch of this round count the fine histogram of the selection's class?  (The selection reads the table only then.)
     h->pf_counted = fuse != nullptr && fuse->k > 0;
     h->skip_launched = false;      // set by the launch that skips (launch_score_k)
+    h->emit_launched = false;      // ... and emits
     h->filter_launched = false;
     const ScoreFormIn in = form_in(h, flags, fuse);
     const ScoreForm f = score_form(in);

@@ -43,6 +43,11 @@ struct ScoreArgs {
     // of the combined strategy, cut_select_qp.py:607-613); lets the selection that follows pick its
     // regime on the device.  Needs both flags.
     int64_t *strong_out;
+    // SKIP / FILTER kernels, optional (NULL: off): every candidate the launch finds strong is appended to this list -- its selection
+    // key into emit[2 slot], its output index into emit[2 slot + 1], slot from one returning atomic per pass on tk->emit_n; entries
+    // beyond emit_cap are dropped and raise tk->emit_over.  Append order is not deterministic.
+    uint64_t *emit;
+    uint32_t emit_cap;
     NetDev net;
 };
 
@@ -70,6 +75,7 @@ static inline ScoreArgs fill_score_args(const sdpcut_ctx *h, int K, uint32_t fla
     A.spread = p.spread;
     A.pf_mloc = p.pf_mloc;
     A.strong_out = ((flags & SDPCUT_EIG) && (flags & SDPCUT_NN)) ? strong_out : nullptr;
+    A.emit = nullptr; A.emit_cap = 0;      // (set by the launch that skips: launch_score_k)
     A.net = h->net[K].dev;
     return A;
 }

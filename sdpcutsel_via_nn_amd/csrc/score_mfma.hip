@@ -333,14 +333,17 @@ __device__ __forceinline__ void filter_lds_fill(const NetDev &net, FilterLds<NH>
 //    4 (l >> 4) + i.  So register i of row tile tk IS the B operand of a k-step that multiplies neurons {16 tk + 4 q + i}: the
 //    host packs the A-fragments in that k-order (net_pack.h) and the activations never leave registers.
 //  * Row tiles 0..2 (neurons 0..47) run on the matrix core.  Their accumulator starts as the (scaled) bias and the k-steps follow
-//    in order -- (0, 0) .. (2, 3), then (3, 0) and (3, 1), whose B operand holds the tail neurons 48 and 49 on the q = 0 lanes and
-//    an exact 0.0f on the others: the chain the margin's derivation counts.
+//    in order -- (0, 0) .. (2, 3), then ONE k-step for the tail neurons: its B operand holds neuron 48 on the q = 0 lanes, 49 on
+//    q = 1 and an exact 0.0f on q >= 2; its A operand is c W[row][48] on q = 0 and c W[row][49] on q = 1, merged here from
+//    components 0 and 1 of the q = 0 lanes of the packed fragment (t, 3) by one v_permlane16_swap (rows q >= 1 of that fragment
+//    are packed zeros, which is what lands on q = 2, 3).  The chain the margin's derivation counts.
 //  * Neurons 48 and 49 (a fourth row tile would be 14 rows of padding) run on the VALU.  Lane (q, c) chains
-//        p = (q == 0 ? bias : 0);  p = fma(w[48], a48, p);  p = fma(w[49], a49, p);  p = fma(w[16 tk + 4 q + i], a, p), (tk, i) in order
-//    over the two tail activations of the layer in front (0 on q >= 1: the bias and these two terms enter on the q = 0 lane
-//    only, at the HEAD of its chain) and the twelve activations it holds; the four q-lanes of the column are then summed as
-//    (p_q + p_(q^1)) + (the same of q^2), and every lane takes the tansig.  The input layer's tail chains the lane's S0 inputs
-//    4 s + q the same way.  This order, too, is what net_filter_margin counts.
+//        p = (q == 0 ? bias : 0);  p = fma(w[48 + q], a_(48 + q), p);  p = fma(w[16 tk + 4 q + i], a, p), (tk, i) in order
+//    over the tail activation of the layer in front that it holds (neuron 48 + q on q = 0, 1; an exact 0 on q >= 2), at the HEAD
+//    of its chain, and the twelve activations it holds; the four q-lanes of the column are then summed as
+//    (p_q + p_(q^1)) + (the same of q^2) -- every lane then holds both neurons' sums, takes the one of neuron q & 1 and ONE
+//    tansig of it.  The input layer's tail chains the lane's S0 inputs 4 s + q the same way.  This order, too, is what
+//    net_filter_margin counts.
 //  * The output layer is a fp64 dot product of the fp32 activations with the fp64 output weights (13 fma per lane and tile) and the
 //    cross-lane sum of the fp64 pass: no fp32 rounding behind the last tansig.
 // Columns are independent: the tail's sums go across the q-lanes of ONE column, so a stale or padding column (NaN included)
@@ -370,21 +373,22 @@ __device__ __forceinline__ void filter_pass_f32(const NetDev &net, const FilterL
         for (int i = 0; i < 4; ++i) a[i] = tansig_f32_z(z[i]);
         return a;
     };
-    // a tail neuron from its lane chain: the column's four q-lanes summed, tansig, and the value kept on q = 0 only
-    auto tail_act = [&](float p) __attribute__((always_inline)) {
-        p = xor_add16f(p);
-        p = xor_add32f(p);
-        const float a = tansig_f32_z(p);
-        return q == 0 ? a : 0.0f;
+    // the two tail neurons from their lane chains: the column's four q-lanes summed, then neuron 48 + u kept on lane q = u
+    auto tail_act = [&](float p48, float p49) __attribute__((always_inline)) {
+        p48 = xor_add32f(xor_add16f(p48));
+        p49 = xor_add32f(xor_add16f(p49));
+        const float a = tansig_f32_z(q == 0 ? p48 : p49);
+        return q < 2 ? a : 0.0f;
     };
     f4 cur[3][2], prev[3][2];
-    float ctl[2][2], ptl[2][2];      // [column tile][u]: neurons 48 + u
+    float ctl[2], ptl[2];            // [column tile]: neuron 48 + q on the lanes q = 0, 1
     // ---------------- input layer
     {
         const f4 *w_in = (const f4 *)net.f32_in;
         f4 w[3];
 #pragma unroll
         for (int t = 0; t < 3; ++t) w[t] = w_in[t * 64 + lane];
+        float pt[2][2];
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const f4 wt = *(const f4 *)&s_tail32[(u * 4 + q) * 16];
@@ -394,9 +398,11 @@ __device__ __forceinline__ void filter_pass_f32(const NetDev &net, const FilterL
                 float p = b;
 #pragma unroll
                 for (int s = 0; s < S0; ++s) p = __builtin_fmaf(wt[s], bin[s][j], p);
-                ctl[j][u] = tail_act(p);
+                pt[j][u] = p;
             }
         }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) ctl[j] = tail_act(pt[j][0], pt[j][1]);
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
             const f4 bias = *(const f4 *)&s_bias32[16 * t + 4 * q];
@@ -416,7 +422,7 @@ __device__ __forceinline__ void filter_pass_f32(const NetDev &net, const FilterL
 #pragma unroll
         for (int t = 0; t < 3; ++t) { prev[t][0] = cur[t][0]; prev[t][1] = cur[t][1]; }
 #pragma unroll
-        for (int j = 0; j < 2; ++j) { ptl[j][0] = ctl[j][0]; ptl[j][1] = ctl[j][1]; }
+        for (int j = 0; j < 2; ++j) ptl[j] = ctl[j];
         const f4 *wh = (const f4 *)net.f32_hid + (size_t)(l - 1) * 4 * 4 * 64 + lane;
         f4 wnx[4];
 #pragma unroll
@@ -440,33 +446,35 @@ __device__ __forceinline__ void filter_pass_f32(const NetDev &net, const FilterL
                     acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w[tk][i], prev[tk][0][i], acc0, 0, 0, 0);
                     acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w[tk][i], prev[tk][1][i], acc1, 0, 0, 0);
                 }
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {      // k-steps (3, 0) and (3, 1): neurons 48 + u on q = 0, zeros elsewhere
-                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w[3][u], ptl[0][u], acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w[3][u], ptl[1][u], acc1, 0, 0, 0);
+            {      // the tail k-step: neuron 48 + q on q = 0, 1, zeros elsewhere.  Odd rows of w[3][0] <- even rows of w[3][1]
+                const float w3 = __uint_as_float(
+                    __builtin_amdgcn_permlane16_swap(__float_as_uint(w[3][0]), __float_as_uint(w[3][1]), false, false)[0]);
+                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w3, ptl[0], acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w3, ptl[1], acc1, 0, 0, 0);
             }
             if (t == 0) {
                 // the layer's two tail neurons, in the region of tile 0: everything they read is the layer in front
                 const float *tw = &s_tail32[((l * 2) * 4 + q) * 16];
+                float pt[2][2];
 #pragma unroll
                 for (int u = 0; u < 2; ++u) {
                     f4 wk[3];
 #pragma unroll
                     for (int tk = 0; tk < 3; ++tk) wk[tk] = *(const f4 *)&tw[u * 64 + 4 * tk];
-                    const float w48 = tw[u * 64 + 12], w49 = tw[u * 64 + 13];
+                    const float wq = tw[u * 64 + 12 + (q & 1)];      // the weight of the tail neuron this lane holds (a 0 on q >= 2)
                     const float b = q == 0 ? s_bias32[l * 64 + 48 + u] : 0.0f;
 #pragma unroll
                     for (int j = 0; j < 2; ++j) {
-                        float p = b;
-                        p = __builtin_fmaf(w48, ptl[j][0], p);
-                        p = __builtin_fmaf(w49, ptl[j][1], p);
+                        float p = __builtin_fmaf(wq, ptl[j], b);
 #pragma unroll
                         for (int tk = 0; tk < 3; ++tk)
 #pragma unroll
                             for (int i = 0; i < 4; ++i) p = __builtin_fmaf(wk[tk][i], prev[tk][j][i], p);
-                        ctl[j][u] = tail_act(p);
+                        pt[j][u] = p;
                     }
                 }
+#pragma unroll
+                for (int j = 0; j < 2; ++j) ctl[j] = tail_act(pt[j][0], pt[j][1]);
             }
             cur[t][0] = act(acc0);
             cur[t][1] = act(acc1);
@@ -480,8 +488,7 @@ __device__ __forceinline__ void filter_pass_f32(const NetDev &net, const FilterL
         for (int t = 0; t < 3; ++t)
 #pragma unroll
             for (int i = 0; i < 4; ++i) part = fma((double)cur[t][j][i], s_wout[16 * t + 4 * q + i], part);
-#pragma unroll
-        for (int u = 0; u < 2; ++u) part = fma((double)ctl[j][u], s_wout[48 + u], part);
+        part = fma((double)ctl[j], s_wout[48 + (q & 1)], part);      // neuron 48 + q on q = 0, 1; an exact zero on q >= 2
         part = xor_add16(part);
         part = xor_add32(part);
         yraw[j] = part;
@@ -919,6 +926,27 @@ __device__ __forceinline__ void score_mfma_body(const ScoreArgs A, LDS &S, const
                 const uint64_t key = key_of(obj);
                 hist_add_few(tk_hist, (uint32_t)(key >> 56), pos);
                 if (PF && pos) { const int f = pf_code(key, false); atomicAdd(&pf_tab[f >> 1], (f & 1) ? 0x10000u : 1u); }
+                // the strong members of the pass go to the emitted list (ScoreArgs::emit): ONE returning atomic reserves their
+                // slots; the selection of a round in its strong regime reads (key, index) from there (TK_ROUTE_EMITTED)
+                if (A.emit) {      // uniform
+                    const unsigned long long pm = __ballot(pos);
+                    if (pm) {      // uniform per wave
+                        const int leader = __ffsll((long long)pm) - 1;
+                        uint32_t base = 0;
+                        if (lane == leader)
+                            base = __hip_atomic_fetch_add(&A.tk->emit_n, (uint32_t)__popcll(pm), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        base = (uint32_t)__builtin_amdgcn_readlane((int)base, leader);
+                        const uint32_t slot = base + __builtin_amdgcn_mbcnt_hi((unsigned)(pm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)pm, 0u));
+                        if (pos) {
+                            if (slot < A.emit_cap) {
+                                A.emit[2 * (size_t)slot] = key;
+                                A.emit[2 * (size_t)slot + 1] = (uint64_t)(uint32_t)S.q_out[wave][s];
+                            } else {
+                                __hip_atomic_store(&A.tk->emit_over, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            }
+                        }
+                    }
+                }
             };
             if constexpr (FILTER) {
                 // one fp32 pass over the cnt <= 32 oldest entries of ring 1 (always two column tiles: padding columns compute on

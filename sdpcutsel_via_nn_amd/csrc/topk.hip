@@ -29,8 +29,8 @@
 // launchers of topk_launch.h:
 //   route (TkRoute)                         file              kernels
 //   SMALLSORT, SMALLSEL, SMALL              topk_small.hip    tk_smallsel_kernel<SORT>, tk_small_kernel
-//   ONFLY, COOP, FUSED, DIGITS              topk_passes.hip   tk_keys_kernel / tk_prekeys_kernel (key pass of COOP, FUSED, DIGITS),
-//                                                             tk_refine_kernel<ONFLY>, tk_hist_kernel (DIGITS)
+//   ONFLY, EMITTED, COOP, FUSED, DIGITS     topk_passes.hip   tk_keys_kernel / tk_prekeys_kernel (key pass of COOP, FUSED, DIGITS),
+//                                                             tk_refine_kernel<ONFLY, EMIT>, tk_hist_kernel (DIGITS)
 //   DIGITS, its compaction                  topk_compact.hip  tk_count_kernel, tk_write_kernel
 //   the sort tail of all but SMALLSORT      topk_sort.hip     tk_countrank_kernel<TIE>, or tk_tilesort_kernel<TIE> and
 //                                                             tk_mergerank_kernel<TIE> / tk_mergerank_big_kernel<TIE>
@@ -109,6 +109,7 @@ static TkPlan plan_for(const sdpcut_ctx *h, int64_t n, int64_t k, int mode, int 
     in.fused_tail = h->fused_tail; in.coop_launch = h->coop_launch; in.shard_rec = h->shard_rec != nullptr;
     in.prefilter = h->prefilter; in.pf_counted = h->pf_counted; in.tk_coresident = h->tk_coresident;
     in.prekeys = prekeys; in.raw = raw; in.count_rank = h->count_rank;
+    in.emitted = h->emit_launched;
     return tk_route(in);
 }
 
@@ -143,6 +144,7 @@ static int topk_run(sdpcut_ctx *h, const TkPlan &p, const TkJob &j, bool prekeys
         tk_small_launch(h, p, j);
         break;
     case TK_ROUTE_ONFLY:
+    case TK_ROUTE_EMITTED:
         rc = tk_refine_launch(h, p, j);
         break;
     case TK_ROUTE_COOP:

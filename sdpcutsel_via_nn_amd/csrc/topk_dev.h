@@ -93,7 +93,7 @@ struct TopkWs {
     int64_t n_sel;           // entries compacted by tk_write_kernel (>= k_eff after an early stop)
     int64_t mode;            // TK_MODE_* of the running selection (written by its pass 0)
     uint32_t ready[9];       // tk_refine_kernel: state[p] has been published inside the launch
-    uint32_t pad_[1];
+    uint32_t emit_n;         // strong members the skipping score launch appended to its emitted list (ScoreArgs::emit), overflowing ones included
     int64_t strong_rep[TK_SREP];   // strong candidates counted by the score kernels, replicated by workgroup
                                    // (same-address device atomics are serialised, see TK_HREP)
     uint32_t bar[8];               // one-shot grid barriers of the fused kernels (arrival counters)
@@ -104,6 +104,8 @@ struct TopkWs {
     int64_t pos_rep[TK_SHREP];            // ONE counter each would queue thousands of retiring workgroups on one address (~15 ns
                                           // apiece: 58 us for the eigenvalue kernel's 3907 workgroups -- longer than the kernel runs)
     int64_t eval_rep[TK_SHREP];           // fp64 MLP evaluations of a filtering score launch (score_mfma_filter_kernel), the same way
+    uint32_t emit_over;                   // != 0: the emitted list overflowed its capacity (the selection scans the scores instead)
+    uint32_t pad2_[3];                    // (keeps the fine histogram below on a 16-byte boundary)
     // (r5) the FINE histogram the score / eigenvalue kernels leave for the selection (see above); LAST in the struct: lists too
     // short for it zero only what lies in front (offsetof(TopkWs, pf_floor))
     uint32_t pf_floor[PF_FLOOR_REP][32];  // max over the reporting units of the lowest bin they reported (replicas in separate lines)

@@ -144,12 +144,25 @@ static __device__ bool grid_barrier(TopkWs *ws, int b, uint32_t nblocks)
 // ONE pass over the scores and handed to the sort exactly like an early stop of the digit passes: no histogram pass, no grid
 // barrier, no wait.  pf_k = 0, a workgroup rich in head members, a fat bin, or the every-entry-visited regime: the passes below
 // run as before.
-template <bool ONFLY>
+// EMIT (with ONFLY; TK_ROUTE_EMITTED): the skipping score launch of this round appended every strong candidate -- selection key and
+// index -- to a list of at most emit_cap pairs of 64-bit words in `keys`; TopkWs::emit_n counts them, emit_over says that
+// some did not fit.  What only the device knows decides first: mode COMBAUTO resolved to STRONG, no overflow, the count equal to
+// the strong count.  Then the strong class IS the list: workgroup b takes entries 1024 b .. 1024 b + 1023 (and every gridDim.x-th
+// block of 1024 behind), the others leave (at once if the class fits the sort buffers, else once the table says that its threshold serves), and nobody
+// reads a score.  The threshold is the direct one of the fine
+// histogram; without one (pf_k = 0, e* below the floor, a fat bin) a class that fits the sort buffers is taken whole, which is what
+// resolve_digit would close digit 0 with.  The list's order is not deterministic and nothing depends on it: the compacted superset is
+// handed to the sort in whatever order the slices are reserved, as on the direct path.  In every other case -- the other regime, an
+// overflow, a class beyond the sort buffers without a direct threshold -- the scores of the first batch are requested late, once
+// that is known, and the launch is TK_ROUTE_ONFLY's from there on.
+#define TK_EMIT_PER (4 * TK_THREADS)
+template <bool ONFLY, bool EMIT = false>
 __global__ __launch_bounds__(TK_THREADS) void tk_refine_kernel(int64_t n, int64_t k, int64_t chunk, const uint64_t *keys,
                                                                TopkWs *ws, uint64_t *sel_key, uint32_t *sel_idx, int mode,
                                                                int64_t sel, const double *eig, const double *obj, int64_t pf_k,
-                                                               unsigned long long *d_stats)
+                                                               unsigned long long *d_stats, int64_t emit_cap)
 {
+    static_assert(!EMIT || ONFLY, "the emitted list belongs to a selection that starts from the score launch's histograms");
     __shared__ uint32_t hist[256];
     __shared__ int go;
     __shared__ uint32_t red_gt[TK_THREADS], red_eq[TK_THREADS], all_gt[TK_THREADS], all_eq[TK_THREADS];
@@ -175,6 +188,8 @@ __global__ __launch_bounds__(TK_THREADS) void tk_refine_kernel(int64_t n, int64_
     double pre_e[TK_UNROLL], pre_o[TK_UNROLL], pre_e2[TK_UNROLL], pre_o2[TK_UNROLL];
     uint32_t pf_q[2 * (PF_BINS / 1024)][4];      // (r5) this thread's words of the fine table, both replicas, and of the floor
     uint32_t pf_fl = 0;
+    [[maybe_unused]] int list_mode = 0;             // (EMIT) 1: the list's entries at or above the direct threshold; 2: all of them
+    [[maybe_unused]] uint32_t emit_n = 0;
     if constexpr (ONFLY) {
         if (pf_k > 0) {      // uniform; coalesced 16-byte loads, independent of everything else the kernel reads
             static_assert(PF_REP == 2 && PF_BINS % 1024 == 0, "two replicas of 1024-word blocks");
@@ -188,6 +203,7 @@ __global__ __launch_bounds__(TK_THREADS) void tk_refine_kernel(int64_t n, int64_
                 }
             if ((threadIdx.x & 63) < PF_FLOOR_REP) pf_fl = ws->pf_floor[threadIdx.x & 63][0];
         }
+        auto issue_pre = [&]() __attribute__((always_inline)) {
         if (lo < hi) {
             // (r5) only the measure the mode ranks by: a feasibility / optimality selection reads 8 bytes per candidate, not 16 -- the
             // scan of the scores is what this kernel waits for longest (phase stamps: table 3.2 us, scores 3.5-4.3 more)
@@ -230,12 +246,27 @@ __global__ __launch_bounds__(TK_THREADS) void tk_refine_kernel(int64_t n, int64_
                 }
             }
         }
+        };
+        if constexpr (!EMIT) issue_pre();
         const bool both = mode == TK_MODE_COMBAUTO;
         // (everything read here was written by earlier launches: plain loads)
         int64_t strong = 0;
 #pragma unroll
         for (int r = 0; r < TK_SREP; ++r) strong += ws->strong_rep[r];
         if (both) mode = strong >= sel ? TK_MODE_STRONG : TK_MODE_COMBALL;      // uniform over the grid
+        [[maybe_unused]] bool use_list = false;     // uniform over the grid
+        if constexpr (EMIT) {
+            emit_n = ws->emit_n;
+            // a class that fits the sort buffers is served from the list whatever the fine histogram says; a larger one needs the
+            // direct threshold, which exists only where the table was counted (pf_k > 0) and is known only once it is resolved
+            const bool fits = (int64_t)emit_n <= (k <= TK_LDSK ? TK_LDSK : TK_MAXK);
+            use_list = both && mode == TK_MODE_STRONG && ws->emit_over == 0u && (int64_t)emit_n == strong && (int64_t)emit_n <= emit_cap &&
+                       (fits || pf_k > 0);
+            if (!use_list) issue_pre();
+            // no entry of the list is this workgroup's, and the list is certain to serve: leave.  (A larger class keeps every
+            // workgroup until the table is resolved: without a direct threshold all of them scan their chunks of the scores.)
+            else if (fits && blockIdx.x != 0 && (int64_t)blockIdx.x * TK_EMIT_PER >= (int64_t)emit_n) return;
+        }
         int64_t nviol = 0, npos = 0;      // counted by the score / eigenvalue kernels, replicated by workgroup
 #pragma unroll 4
         for (int r = 0; r < TK_SHREP; ++r) { nviol += ws->viol_rep[r]; npos += ws->pos_rep[r]; }
@@ -322,8 +353,72 @@ __global__ __launch_bounds__(TK_THREADS) void tk_refine_kernel(int64_t n, int64_
                 }
             }
             if (!direct) resolve_digit(ws, 0, k, ws->hist_score, cls, &st1, blockIdx.x == 0, mode, true, TK_SHREP);
+            if constexpr (EMIT) {
+                if (use_list) {
+                    if (direct) list_mode = 1;
+                    else if ((int64_t)emit_n <= (k <= TK_LDSK ? TK_LDSK : TK_MAXK)) list_mode = 2;
+                    else issue_pre();      // a class beyond the sort buffers and no direct threshold: the passes below scan the scores
+                }
+            }
         }
         __syncthreads();
+    }
+    if constexpr (EMIT) {
+        if (list_mode) {      // uniform over the workgroups that are still here
+            const uint64_t T0 = list_mode == 1 ? st1.prefix : 1ull;      // (key 0 = not in the class; the list holds members only)
+            const ulonglong2 *elist = (const ulonglong2 *)keys;
+            const int ln = threadIdx.x & 63, wv = threadIdx.x >> 6;
+            for (int64_t base = (int64_t)blockIdx.x * TK_EMIT_PER; base < (int64_t)emit_n; base += (int64_t)gridDim.x * TK_EMIT_PER) {
+                uint64_t ek[TK_EMIT_PER / TK_THREADS];
+                uint32_t ei[TK_EMIT_PER / TK_THREADS], mask = 0;
+#pragma unroll
+                for (int u = 0; u < TK_EMIT_PER / TK_THREADS; ++u) {
+                    const int64_t i = base + (int64_t)u * TK_THREADS + threadIdx.x;
+                    const int64_t ic = i < (int64_t)emit_n ? i : (int64_t)emit_n - 1;
+                    const ulonglong2 e = elist[ic];
+                    ek[u] = e.x;
+                    ei[u] = (uint32_t)e.y;
+                }
+#pragma unroll
+                for (int u = 0; u < TK_EMIT_PER / TK_THREADS; ++u)
+                    mask |= (uint32_t)(base + (int64_t)u * TK_THREADS + threadIdx.x < (int64_t)emit_n && ek[u] >= T0) << u;
+                const uint32_t cnt = (uint32_t)__popc(mask);
+                uint32_t incl = cnt;
+#pragma unroll
+                for (int off = 1; off < 64; off <<= 1) {
+                    const uint32_t o = (uint32_t)__shfl_up((int)incl, off);
+                    if (ln >= off) incl += o;
+                }
+                if (ln == 63) wave_cnt[wv] = incl;
+                __syncthreads();
+                uint32_t wbase = 0, total = 0;
+#pragma unroll
+                for (int w = 0; w < TK_THREADS / 64; ++w) {
+                    if (w < wv) wbase += wave_cnt[w];
+                    total += wave_cnt[w];
+                }
+                if (threadIdx.x == 0 && total)
+                    slice = __hip_atomic_fetch_add((unsigned long long *)&ws->n_sel, (unsigned long long)total, __ATOMIC_RELAXED,
+                                                   __HIP_MEMORY_SCOPE_AGENT);
+                __syncthreads();
+                int64_t slot = (int64_t)slice + wbase + incl - cnt;
+#pragma unroll
+                for (int u = 0; u < TK_EMIT_PER / TK_THREADS; ++u) {
+                    if ((mask >> u) & 1u) {
+                        if (slot < (int64_t)TK_MAXK) {
+                            sel_key[slot] = ek[u];
+                            sel_idx[slot] = ei[u];
+                        } else {
+                            st_i64(&ws->counters[4], 1);      // cannot happen (see the direct path below): the selection is void
+                        }
+                        ++slot;
+                    }
+                }
+                __syncthreads();      // wave_cnt and slice are rewritten by the next round
+            }
+            if (d_stats && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&d_stats[6], 1ull);
+            return;
+        }
     }
     TkState st;
     if constexpr (ONFLY) {
@@ -723,6 +818,9 @@ int tk_refine_coresident(sdpcut_ctx *h, int64_t *coresident)
     int b_on = 0, b_off = 0;
     HIP_TRY(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&b_on, tk_refine_kernel<true>, TK_THREADS, 0));
     HIP_TRY(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&b_off, tk_refine_kernel<false>, TK_THREADS, 0));
+    int b_emit = 0;
+    HIP_TRY(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&b_emit, tk_refine_kernel<true, true>, TK_THREADS, 0));
+    b_on = b_emit < b_on ? b_emit : b_on;
     *coresident = (int64_t)(b_on < b_off ? b_on : b_off) * h->n_cu;
     return 0;
 }
@@ -730,9 +828,12 @@ int tk_refine_coresident(sdpcut_ctx *h, int64_t *coresident)
 int tk_refine_launch(sdpcut_ctx *h, const TkPlan &p, const TkJob &j)
 {
     const dim3 grid(p.grid_pass), blk(TK_THREADS);
-    if (p.route == TK_ROUTE_ONFLY) {      // (a measure the mode does not use is never looked at: any readable array of n doubles will do)
+    if (p.route == TK_ROUTE_EMITTED) {      // the list the score launch emitted lies in the key array (launch_score_k)
+        hipLaunchKernelGGL((tk_refine_kernel<true, true>), grid, blk, 0, h->stream, j.n, j.k, p.chunk, h->d_key_a, j.ws, h->d_sel_key,
+                           h->d_sel_idx, j.mode, j.sel, j.eig ? j.eig : j.obj, j.obj ? j.obj : j.eig, p.pf_k, h->d_stats, h->emit_cap);
+    } else if (p.route == TK_ROUTE_ONFLY) {      // (a measure the mode does not use is never looked at: any readable array of n doubles will do)
         hipLaunchKernelGGL(tk_refine_kernel<true>, grid, blk, 0, h->stream, j.n, j.k, p.chunk, nullptr, j.ws, h->d_sel_key, h->d_sel_idx,
-                           j.mode, j.sel, j.eig ? j.eig : j.obj, j.obj ? j.obj : j.eig, p.pf_k, h->d_stats);
+                           j.mode, j.sel, j.eig ? j.eig : j.obj, j.obj ? j.obj : j.eig, p.pf_k, h->d_stats, (int64_t)0);
     } else if (p.route == TK_ROUTE_COOP) {      // the runtime guarantees the co-residency (+20 us per launch)
         const uint64_t *keys_arg = h->d_key_a;
         TopkWs *ws_arg = j.ws;
@@ -742,11 +843,13 @@ int tk_refine_launch(sdpcut_ctx *h, const TkPlan &p, const TkJob &j)
         int mode_arg = j.mode;
         const double *eig_arg = j.eig, *obj_arg = j.obj;
         unsigned long long *stats_arg = nullptr;
-        void *args[] = {&n_arg, &k_arg, &chunk_arg, &keys_arg, &ws_arg, &sk_arg, &si_arg, &mode_arg, &sel_arg, &eig_arg, &obj_arg, &pf_arg, &stats_arg};
+        int64_t ecap_arg = 0;
+        void *args[] = {&n_arg, &k_arg, &chunk_arg, &keys_arg, &ws_arg, &sk_arg, &si_arg, &mode_arg, &sel_arg, &eig_arg, &obj_arg, &pf_arg, &stats_arg,
+                        &ecap_arg};
         HIP_TRY(h, hipLaunchCooperativeKernel((const void *)tk_refine_kernel<false>, grid, blk, args, 0, h->stream));
     } else {
         hipLaunchKernelGGL(tk_refine_kernel<false>, grid, blk, 0, h->stream, j.n, j.k, p.chunk, h->d_key_a, j.ws, h->d_sel_key, h->d_sel_idx,
-                           j.mode, j.sel, j.eig, j.obj, (int64_t)0, (unsigned long long *)nullptr);
+                           j.mode, j.sel, j.eig, j.obj, (int64_t)0, (unsigned long long *)nullptr, (int64_t)0);
     }
     return 0;
 }

@@ -57,7 +57,12 @@ enum TkRoute {
     TK_ROUTE_ONFLY = 4,       // tk_refine_kernel<true>: digit 0 counted by the score kernels, no key array         (topk_passes.hip)
     TK_ROUTE_COOP = 5,        // key pass, tk_refine_kernel<false> launched cooperatively, sort tail               (topk_passes.hip)
     TK_ROUTE_FUSED = 6,       // key pass, tk_refine_kernel<false>, sort tail                                      (topk_passes.hip)
-    TK_ROUTE_DIGITS = 7       // key pass, tk_hist_kernel x 7, tk_count_kernel, tk_write_kernel, sort tail (topk_passes.hip, topk_compact.hip)
+    TK_ROUTE_DIGITS = 7,      // key pass, tk_hist_kernel x 7, tk_count_kernel, tk_write_kernel, sort tail (topk_passes.hip, topk_compact.hip)
+    // tk_refine_kernel<true, true>: TK_ROUTE_ONFLY whose launch first looks at what the device alone knows -- the regime and the
+    // overflow flag of the emitted list -- and, in the strong regime without an overflow, compacts the head's superset from the
+    // (key, index) pairs the skipping score launch appended instead of rebuilding 10^6 keys from the scores; otherwise it is
+    // TK_ROUTE_ONFLY's code from there on, same result                                                              (topk_passes.hip)
+    TK_ROUTE_EMITTED = 8
 };
 
 struct TkRouteIn {
@@ -74,6 +79,7 @@ struct TkRouteIn {
     bool raw = false;                                 // the head's scores are emitted as raw key images (big-head merge only)
     bool smallsel = TK_SMALLSEL != 0, smallsort = TK_SMALLSORT != 0;
     bool count_rank = true;                           // SDPCUT_OPT_COUNT_RANK
+    bool emitted = false;                             // this round's (skipping) score launch appended its strong members to the emitted list
 };
 
 struct TkPlan {
@@ -143,6 +149,9 @@ static inline TkPlan tk_route(const TkRouteIn &in)
         if (!in.fused_tail) return tk_refuse(p, SDPCUT_ESTATE, "top-k select: no key pass to continue from");
         p.route = TK_ROUTE_ONFLY;
         p.pf_k = (in.prefilter && in.pf_counted && n >= SDPCUT_PF_MIN_N) ? k : 0;
+        // the list holds the strong class and nothing else: only a selection that may resolve to it reads it, and the sort behind
+        // must be the one that takes any superset in any order (heads that fit TK_LDSK, no shard record)
+        if (in.emitted && in.mode == TK_MODE_COMBAUTO && !in.shard_rec && k <= TK_LDSK) p.route = TK_ROUTE_EMITTED;
     } else if (in.fused_tail)
         p.route = in.coop_launch ? TK_ROUTE_COOP : TK_ROUTE_FUSED;      // cooperative: the runtime guarantees the co-residency (+20 us per launch)
     else      // one launch per digit, no wait anywhere inside a kernel: the path that always answers

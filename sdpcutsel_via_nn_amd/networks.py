@@ -136,16 +136,18 @@ def filter_margin(k, widths, params):
         wt = (c * W).astype(np.float32).astype(np.float64)
         bt = (c * b).astype(np.float32).astype(np.float64)
         H = W.shape[0]
+        tail = 48 < H <= 52                    # tail rows 48 .. H - 1: a lane chain and a two-level tree on the VALU
+        if tail and l > 0:                     # the tail neurons of the layer in front share ONE k-step, neuron 48 + v on q = v
+            before[48:] = 48
         m = np.tile(fan - before, (H, 1))      # roundings term j sees in row i
         mb = np.full(H, fan)                   # ... and the bias
-        if 48 < H <= 52:                       # tail rows 48 .. H - 1: a lane chain and a two-level tree on the VALU
-            nt = H - 48
+        if tail:
             if l == 0:                         # lane q chains inputs q, 4 + q, ..: `live` of them
                 mt = (fan - j % 4 + 3) // 4 - j // 4 + 2
                 mbt = (fan + 3) // 4 + 2
-            else:                              # b, the tail neurons of the layer in front, then links 4 tk + i of twelve
-                mt = np.where(j < 48, 12 - (4 * (j // 16) + j % 4) + 2, nt - (j - 48) + 12 + 2)
-                mbt = nt + 12 + 2
+            else:                              # b on q = 0, tail neuron 48 + v of the layer in front on q = v, then links 4 tk + i of twelve
+                mt = np.where(j < 48, 12 - (4 * (j // 16) + j % 4) + 2, 1 + 12 + 2)
+                mbt = 1 + 12 + 2
             m[48:] = mt
             mb[48:] = mbt
         acc = np.abs(bt) * gamma(mb) + np.abs(bt - c * b)
