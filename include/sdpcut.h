@@ -164,7 +164,9 @@ enum { SDPCUT_KERNEL_MFMA = 0, SDPCUT_KERNEL_SIMPLE = 1, SDPCUT_KERNEL_VALU = 2 
 /* SDPCUT_OPT_FP32_FILTER (default 1): where a launch under SDPCUT_OPT_SKIP_NONVIOLATED runs and the class's network qualifies
  * (sdpcut_get_filter_margin), the violated candidates first go through the network in fp32 on the matrix cores; the fp64 pass
  * then runs only for those whose fp32 measure exceeds -margin * max_elem, margin a PROVEN bound on the difference of the two network
- * outputs (csrc/net_pack.h), and for candidates with an input outside the domain the bound was derived on.  Every violated
+ * outputs (csrc/net_pack.h), and for candidates with an input outside the domain the bound was derived on.  The margin is PER
+ * CANDIDATE -- it follows the slopes of the last hidden layer's activations at that candidate -- and never above
+ * sdpcut_get_filter_margin (sdpcut_filter_audit_margins returns it).  Every violated
  * candidate with a positive measure is among them: same head, scores, rows, new_strat and counters as with the option off, bit for
  * bit; the others keep their fp32 measure, which is not positive, until the measure is completed on demand exactly as under
  * SDPCUT_OPT_SKIP_NONVIOLATED (no call returns it before).
@@ -229,8 +231,9 @@ enum { SDPCUT_OPT_KERNEL = 1, SDPCUT_OPT_TIMING = 2, SDPCUT_OPT_FUSE_KEYS = 3, S
  *   sdpcut_shard_head_device it is read from the device: the call waits for the handle's stream;
  * SDPCUT_STAT_NN_COMPLETIONS = NN scoring launches since the handle was made that completed a measure such a launch left partial.
  * SDPCUT_STAT_NN_EVALUATED = fp64 MLP evaluations of the handle's last scoring launch that ran the network: the list length after a
- *   launch that scored everybody, nb_violated after a skipping launch, the survivors of the fp32 filter after a filtering one (read
- *   from the device: the call waits for the handle's stream); 0 after a new list.
+ *   launch that scored everybody, nb_violated after a skipping launch, the survivors of the fp32 filter after a filtering one --
+ *   the violated candidates whose fp32 measure exceeds -margin * max_elem with their OWN margin, which is never above
+ *   sdpcut_get_filter_margin -- (read from the device: the call waits for the handle's stream); 0 after a new list.
  * SDPCUT_STAT_DIVERSE_POINTS_FAST = points of sdpcut_round_csr_points_diverse answered by its one-wait route since the handle was made
  *   (points served by the loop inside the call, or redone, do not count).
  * SDPCUT_STAT_INJECTED -- TEST ONLY: launches SDPCUT_OPT_INJECT_GIVEUP has hit since the handle was made.
@@ -251,13 +254,17 @@ enum { SDPCUT_STAT_ROUNDS = 1, SDPCUT_STAT_SELECT_FALLBACKS = 2, SDPCUT_STAT_SCO
 int sdpcut_get_stat(sdpcut_handle h, int which, int64_t *value);
 
 /* The fp32 filter (SDPCUT_OPT_FP32_FILTER) of the network set for k-variable candidates: *margin = the proven bound on
- * |y32 - y64| of the unmapped network output the filter decides by, or NaN if that network does not filter (not clamp-free, not
+ * |y32 - y64| of the unmapped network output that holds for every candidate -- the filter decides by a margin per candidate that
+ * is never above it (sdpcut_filter_audit_margins) --, or NaN if that network does not filter (not clamp-free, not
  * the shipped 3-variable shape, or a bound above the cut-off).  SDPCUT_ESTATE without a network for k. */
 int sdpcut_get_filter_margin(sdpcut_handle h, int k, double *margin);
 /* Audit of that bound on the device: runs the filter's fp32 pass -- the device function the scoring kernel runs -- for EVERY
  * candidate of the handle's list at the current point and returns the fp32 network output, unmapped, in y32_out [N] (caller
  * order).  The list must hold 3-variable candidates only and their network must filter; no node box.  Not a hot path. */
 int sdpcut_filter_audit(sdpcut_handle h, double *y32_out);
+/* The same audit, and in m_out [N] (caller order) the margin the filter decides by for each candidate: a proven bound on
+ * |y32 - y64| of THAT candidate, computed by the same device function from the same pass, <= sdpcut_get_filter_margin. */
+int sdpcut_filter_audit_margins(sdpcut_handle h, double *y32_out, double *m_out);
 
 /* Maximum sub-problem size (assert dim <= 5, cut_select_qp.py:93) */
 #define SDPCUT_MAX_K 5

@@ -127,6 +127,7 @@ SIGNATURES = {
     "sdpcut_get_stat": [_vp, _c.c_int, _i64p],
     "sdpcut_get_filter_margin": [_vp, _c.c_int, _dp],
     "sdpcut_filter_audit": [_vp, _dp],
+    "sdpcut_filter_audit_margins": [_vp, _dp, _dp],
     "sdpcut_synchronize": [_vp],
     "sdpcut_wake": [_vp],
     "sdpcut_set_network": [_vp, _c.c_int, _c.c_int, _i32p, _dp, _c.c_int64],
@@ -525,8 +526,9 @@ class Scorer(object):
         return int(v.value)
 
     def filter_margin(self, k):
-        """the proven bound on |y32 - y64| the fp32 filter of the k-variable network decides by (sdpcut_get_filter_margin); NaN if
-        that network does not filter"""
+        """the proven bound on |y32 - y64| of the fp32 filter of the k-variable network that holds for every candidate
+        (sdpcut_get_filter_margin; the filter decides by a margin per candidate that is never above it); NaN if that network does
+        not filter"""
         v = _c.c_double(0.0)
         self._check(self._lib.sdpcut_get_filter_margin(self._h, int(k), ctypes.byref(v)))
         return float(v.value)
@@ -537,6 +539,14 @@ class Scorer(object):
         y = np.empty(self.N, dtype=np.float64)
         self._check(self._lib.sdpcut_filter_audit(self._h, _ptr(y, _dp)))
         return y
+
+    def filter_audit_margins(self):
+        """filter_audit, and the margin the filter decides by for every candidate, each a proven bound on that candidate's
+        |y32 - y64| and never above filter_margin(3) (sdpcut_filter_audit_margins) -> (y32, m), float64 [N] each"""
+        y = np.empty(self.N, dtype=np.float64)
+        m = np.empty(self.N, dtype=np.float64)
+        self._check(self._lib.sdpcut_filter_audit_margins(self._h, _ptr(y, _dp), _ptr(m, _dp)))
+        return y, m
 
     def wake(self):
         """an empty kernel on the handle's stream (sdpcut_wake): poke an idle device while the LP solution is still being extracted"""

@@ -311,23 +311,39 @@ int sdpcut_get_filter_margin(sdpcut_handle h, int k, double *margin)
     return SDPCUT_OK;
 }
 
-int sdpcut_filter_audit(sdpcut_handle h, double *y32_out)
+// y32_out and (if not null) m_out: the filter's fp32 pass and the margin it decides by, for every candidate of the list
+static int filter_audit(sdpcut_handle h, double *y32_out, double *m_out)
 {
-    if (!h || !y32_out) return SDPCUT_EINVAL;
     SDPCUT_NO_PENDING(h);
     SDPCUT_NO_BOX(h, "sdpcut_filter_audit");
     if (h->N < 1 || h->bucket[3].n != h->N) return sdpcut_fail(h, SDPCUT_ESTATE, "filter audit: the list must hold 3-variable candidates only");
     if (!h->have_point) return sdpcut_fail(h, SDPCUT_ESTATE, "set_point first");
     if (!h->net[3].set || !h->net[3].dev.filter_ok) return sdpcut_fail(h, SDPCUT_ESTATE, "filter audit: the network of 3-variable candidates does not filter");
     HIP_TRY(h, hipSetDevice(h->device));
+    const size_t n = (size_t)h->N;
     double *d_y = nullptr;
-    HIP_TRY(h, hipMalloc((void **)&d_y, (size_t)h->N * sizeof(double)));
-    int rc = launch_filter_audit(h, d_y);
-    if (!rc && hipMemcpyAsync(y32_out, d_y, (size_t)h->N * sizeof(double), hipMemcpyDeviceToHost, h->stream) != hipSuccess)
+    HIP_TRY(h, hipMalloc((void **)&d_y, (m_out ? 2 : 1) * n * sizeof(double)));
+    double *d_m = m_out ? d_y + n : nullptr;
+    int rc = launch_filter_audit(h, d_y, d_m);
+    if (!rc && hipMemcpyAsync(y32_out, d_y, n * sizeof(double), hipMemcpyDeviceToHost, h->stream) != hipSuccess)
+        rc = sdpcut_fail(h, SDPCUT_EHIP, "filter audit: copy failed");
+    if (!rc && m_out && hipMemcpyAsync(m_out, d_m, n * sizeof(double), hipMemcpyDeviceToHost, h->stream) != hipSuccess)
         rc = sdpcut_fail(h, SDPCUT_EHIP, "filter audit: copy failed");
     if (!rc && sdpcut_sync(h) != hipSuccess) rc = sdpcut_fail(h, SDPCUT_EHIP, "filter audit: the kernel failed");
     (void)hipFree(d_y);
     return rc;
+}
+
+int sdpcut_filter_audit(sdpcut_handle h, double *y32_out)
+{
+    if (!h || !y32_out) return SDPCUT_EINVAL;
+    return filter_audit(h, y32_out, nullptr);
+}
+
+int sdpcut_filter_audit_margins(sdpcut_handle h, double *y32_out, double *m_out)
+{
+    if (!h || !y32_out || !m_out) return SDPCUT_EINVAL;
+    return filter_audit(h, y32_out, m_out);
 }
 
 int sdpcut_set_stream(sdpcut_handle h, void *hip_stream)

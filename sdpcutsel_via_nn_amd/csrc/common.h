@@ -46,6 +46,10 @@ struct NetDev {
     const float *f32_in;       // (x -2 log2 e) input-layer A-fragments of v_mfma_f32_16x16x4_f32: [t][lane] float4, component = k-step
     const float *f32_hid;      // (x -2 log2 e) hidden-layer A-fragments: [layer - 1][t][tk][lane] float4, component i = k-step (tk, i)
     const float *f32_bias;     // (x -2 log2 e) [n_hidden][64] zero padded
+    // the margin per candidate, min(filter_margin, (S (1 + 2^-9) + filter_c0) (1 + 2^-10)) with S = sum_j f32_g[j] (1 - a_j^2) over
+    // the last hidden layer's fp32 activations (net_pack.h: net_filter_slope_terms)
+    const float *f32_g;        // [64] zero padded, neuron order
+    double filter_c0;
 };
 
 struct Bucket {
@@ -401,7 +405,7 @@ struct ScoreFuse {
 // obj_improve > 0 and lambda_min < -1e-15 to strong_out[workgroup % 8] (needs both flags; used by the device-resolved combined selection)
 int launch_score(sdpcut_ctx *h, uint32_t flags, const ScoreFuse *fuse = nullptr, bool *fused = nullptr,
                  int64_t *strong_out = nullptr);
-int launch_filter_audit(sdpcut_ctx *h, double *d_y32);   // score.hip: sdpcut_filter_audit's kernel over the (single) class 3, enqueued
+int launch_filter_audit(sdpcut_ctx *h, double *d_y32, double *d_m);   // score.hip: sdpcut_filter_audit's kernel over the (single) class 3, enqueued
 int launch_cut_rows(sdpcut_ctx *h, int64_t count, const int64_t *d_limit, const int64_t *d_idx, int64_t idx_base,
                     double *d_lam, double *d_coef, int coef_ld, double *d_rhs, int64_t *d_cols, int32_t *d_ks);
 // Epilogue of a fused round: rows of the ranking head + its ids, scores and the four counters,

@@ -65,15 +65,17 @@ int sdpcut_set_network(sdpcut_handle h, int k, int n_layers, const int32_t *widt
     nh_.d_blob = nullptr;
     nh_.set = false;
     h->scored &= ~(uint32_t)SDPCUT_NN; h->obj_partial = false;      // the list's optimality scores were the old network's: a round scores again
-    // one allocation: the blob | filter_box [d_in][2] | the fp32 forms of the filter (floats; empty unless filter_ok)
+    // one allocation: the blob | filter_box [d_in][2] | the fp32 forms of the filter (floats; empty unless filter_ok) | filter_g [64]
     const size_t n_box = 2 * (size_t)pk.d_in;
     const size_t n_pre = (pk.blob.size() + n_box + 1) & ~(size_t)1;      // (an even number of doubles: the float4 loads stay aligned)
-    HIP_TRY(h, hipMalloc((void **)&nh_.d_blob, n_pre * sizeof(double) + pk.f32.size() * sizeof(float)));
+    HIP_TRY(h, hipMalloc((void **)&nh_.d_blob, n_pre * sizeof(double) + (pk.f32.size() + MAX_HIDDEN) * sizeof(float)));
     HIP_TRY(h, hipMemcpy(nh_.d_blob, pk.blob.data(), pk.blob.size() * sizeof(double), hipMemcpyHostToDevice));
     double *d_box = nh_.d_blob + pk.blob.size();
     float *d_f32 = (float *)(nh_.d_blob + n_pre);
     HIP_TRY(h, hipMemcpy(d_box, &pk.filter_box[0][0], n_box * sizeof(double), hipMemcpyHostToDevice));
     if (!pk.f32.empty()) HIP_TRY(h, hipMemcpy(d_f32, pk.f32.data(), pk.f32.size() * sizeof(float), hipMemcpyHostToDevice));
+    float *d_g = d_f32 + pk.f32.size();      // (a multiple of four floats behind d_f32: the float4 loads stay aligned)
+    HIP_TRY(h, hipMemcpy(d_g, pk.filter_g, MAX_HIDDEN * sizeof(float), hipMemcpyHostToDevice));
     NetDev &d = nh_.dev;
     d = NetDev{};
     d.d_in = pk.d_in; d.n_hidden = pk.n_hidden; d.width = pk.width; d.s0 = pk.s0; d.sh = pk.sh;
@@ -88,7 +90,8 @@ int sdpcut_set_network(sdpcut_handle h, int k, int n_layers, const int32_t *widt
     d.ymin = pk.ymin; d.b_out = pk.b_out; d.y_ymin = pk.y_ymin; d.y_gain = pk.y_gain; d.y_xoffset = pk.y_xoffset;
     d.unclamped_ok = pk.unclamped_ok;
     d.filter_ok = pk.filter_ok; d.filter_margin = pk.filter_margin; d.filter_box = d_box;
-    if (pk.filter_ok) { d.f32_in = d_f32 + pk.o32_in; d.f32_hid = d_f32 + pk.o32_hid; d.f32_bias = d_f32 + pk.o32_bias; }
+    if (pk.filter_ok) { d.f32_in = d_f32 + pk.o32_in; d.f32_hid = d_f32 + pk.o32_hid; d.f32_bias = d_f32 + pk.o32_bias; d.f32_g = d_g; }
+    d.filter_c0 = pk.filter_c0;
     nh_.set = true;
     return SDPCUT_OK;
 }

@@ -31,6 +31,9 @@ struct NetPack {
     int filter_ok;
     double filter_margin;                 // bound on |y32 - y64| of the unmapped output for mapped inputs inside filter_box
     double filter_box[MAX_DIN][2];        // [lo, hi] of every mapped input the bound was derived on
+    float filter_g[MAX_HIDDEN];           // the per-candidate margin (net_filter_slope_terms): the last hidden layer's slope weights ..
+    double filter_g64[MAX_HIDDEN];        // .. before they were rounded up to float (tests) ..
+    double filter_c0;                     // .. and its constant term
 };
 
 // the networks the fp32 filter is instantiated for: the shipped 3-variable class (NetShape<3> of score_plan.h)
@@ -82,13 +85,15 @@ static inline bool filter_shape(int k, int H, int nh) { return k == 3 && H == 50
 // filter_box: the image of the input domain (x in [0, 1], |q| <= 1/k) under the network's mapping, 1e-9 wider at both ends so
 // that a contracted (v - xoffset) gain + ymin on the device and a quotient one ulp above 1/k stay inside.
 // networks.filter_margin restates this in numpy (tests/test_filter_margin_cpu.py).
-static inline double net_filter_margin(int k, int nh, int H, int d_in, const double *const *W, const double *const *B,
-                                       const double *xoffset, const double *gain, double ymin, double y_gain, double (*box)[2])
+// The layers of that derivation: -> e[j] of the LAST hidden layer's activations, and in delta[j] (if asked for) their
+// pre-activations' share of it, |z_j / c - n_j| <= delta_j = e_j - 13 u, which net_filter_slope_terms below starts from.
+static inline void net_filter_layers(int k, int nh, int H, int d_in, const double *const *W, const double *const *B,
+                                     const double *xoffset, const double *gain, double ymin, double (*box)[2], double *e, double *delta)
 {
     const double u = 0x1p-24, c = FILTER_EXP_SCALE;
     auto gamma = [&](int m) { return m * u / (1.0 - m * u); };
     const int NT = (H > 48 && H <= 52) ? H - 48 : 0;      // tail rows 48 .. H - 1 (two at the width that filters, 50)
-    double e[MAX_HIDDEN], A[MAX_HIDDEN], en[MAX_HIDDEN];
+    double A[MAX_HIDDEN], en[MAX_HIDDEN];
     for (int i = 0; i < d_in; ++i) {
         const double lo = i < k ? 0.0 : -1.0 / (double)k, hi = i < k ? 1.0 : 1.0 / (double)k;
         const double a = (lo - xoffset[i]) * gain[i] + ymin, b = (hi - xoffset[i]) * gain[i] + ymin;
@@ -141,13 +146,66 @@ static inline double net_filter_margin(int k, int nh, int H, int d_in, const dou
                 acc += std::fabs(wt) * A[j] * gamma(tail ? mtail[j] : fan - before[j]) + std::fabs(wt - c * w) * A[j] + std::fabs(c * w) * e[j];
             }
             en[i] = acc / std::fabs(c) + 13.0 * u;
+            if (delta) delta[i] = acc / std::fabs(c);
         }
         for (int i = 0; i < H; ++i) { e[i] = en[i]; A[i] = 1.0 + 8.0 * u; }
         fan = H;
     }
+}
+
+static inline double net_filter_margin(int k, int nh, int H, int d_in, const double *const *W, const double *const *B,
+                                       const double *xoffset, const double *gain, double ymin, double y_gain, double (*box)[2])
+{
+    double e[MAX_HIDDEN];
+    net_filter_layers(k, nh, H, d_in, W, B, xoffset, gain, ymin, box, e, nullptr);
     double out = 0.0;
     for (int j = 0; j < H; ++j) out += std::fabs(W[nh][j]) * e[j];
     return out / std::fabs(y_gain) * (1.0 + 0x1p-10);
+}
+
+// ---- The margin PER CANDIDATE: the same bound with the last hidden layer's tansig taken at its slope instead of as 1-Lipschitz.
+// Neuron j of the LAST hidden layer: n_j its exact pre-activation, n^_j = z_j / c what the fp32 pass holds, |n^_j - n_j| <= delta_j
+// (the a-priori bound of the derivation above, e'_j without its 13 u: net_filter_layers), a_j = tansig(n_j), t_j = tansig(n^_j)
+// exactly and a^_j the hardware's value, |a^_j - t_j| <= 13 u (above).  The mean value theorem on the segment between n_j and n^_j:
+//   |t_j - a_j| = tansig'(xi) |n^_j - n_j|,   tansig'(xi) <= tansig'(n^_j) + L2 |xi - n^_j| <= 1 - t_j^2 + L2 delta_j
+// with tansig' = 1 - tansig^2 and L2 = max |tansig''| = max |2 t (1 - t^2)| = 4 / (3 sqrt 3) (at t^2 = 1/3).  The pass holds a^_j,
+// not t_j:  |t_j^2 - a^_j^2| = |t_j - a^_j| |t_j + a^_j| <= 13 u (2 + 8 u) <= 27 u.  So
+//   |a^_j - a_j| <= (1 - a^_j^2 + 27 u + L2 delta_j) delta_j + 13 u
+// The output layer is fp64 on the fp32 activations and the mapping divides by its gain, as above:
+//   |y32 - y64| <= S + C,   S = sum_j G_j (1 - a^_j^2),   G_j = |Wout_j| delta_j / |y_gain|,
+//                           C = sum_j |Wout_j| ((27 u + L2 delta_j) delta_j + 13 u) / |y_gain|
+// S is evaluated by the fp32 pass itself (score_mfma.hip: filter_pass_f32), with G_j rounded UP to float (Gf_j >= G_j):
+//   s_j = fma(-a^_j, a^_j, 1)                       one rounding of a value in [-17 u, 1] (|a^_j| <= 1 + 8 u):  |s_j - (1 - a^_j^2)| <= u
+//   lane q:  p = fma(Gf_j, s_j, p) over its 13 terms    13 links (the tail term is its last; forced to 0 on q >= 2, where the lane
+//                                                   holds an exact 0 whose slope would count as 1)
+//   S~ = (p_q + p_(q^1)) + (p_(q^2) + p_(q^3))      2 more roundings for every term
+// A term sees at most 13 + 2 = 15 roundings of the sum and |s_j| <= 1:  |S~ - sum_j Gf_j (1 - a^_j^2)| <= (gamma(15) + u) sum_j Gf_j,
+// 16 roundings counted in all, charged in ABSOLUTE terms:
+//   C0 = C + (gamma(15) + u) sum_j Gf_j
+// (An s_j below zero, >= -17 u, makes Gf_j s_j smaller than G_j s_j by at most 17 u (Gf_j - G_j) <= 17 u^2 G_j: second order.)
+//   M(cand) = min( filter_margin, (S~ (1 + 2^-9) + C0) (1 + 2^-10) )
+// Both arguments of the min are bounds on |y32 - y64|.  1 + 2^-10 is the factor of the a-priori margin, for the same fp64 roundings
+// and second-order terms; 1 + 2^-9 on S~ is slack on top of the counted terms (gamma(15) is 9e-7), none of which depends on it.
+// -> Gd[64] = G_j, Gf[64] = the floats the kernel multiplies (zeros from H on in both), *C0.  networks.filter_margin_terms restates it.
+static inline void net_filter_slope_terms(int k, int nh, int H, int d_in, const double *const *W, const double *const *B,
+                                          const double *xoffset, const double *gain, double ymin, double y_gain, double *Gd, float *Gf,
+                                          double *C0)
+{
+    const double u = 0x1p-24, L2 = 4.0 / (3.0 * std::sqrt(3.0)), g15 = 15.0 * u / (1.0 - 15.0 * u);
+    double e[MAX_HIDDEN], delta[MAX_HIDDEN], box[MAX_DIN][2];
+    net_filter_layers(k, nh, H, d_in, W, B, xoffset, gain, ymin, box, e, delta);
+    double c = 0.0, gsum = 0.0;
+    for (int j = 0; j < MAX_HIDDEN; ++j) { Gd[j] = 0.0; Gf[j] = 0.0f; }
+    for (int j = 0; j < H; ++j) {
+        const double w = std::fabs(W[nh][j]);
+        Gd[j] = w * delta[j] / std::fabs(y_gain);
+        float g = (float)Gd[j];
+        if ((double)g < Gd[j]) g = std::nextafterf(g, INFINITY);
+        Gf[j] = g;
+        gsum += (double)g;
+        c += w * ((27.0 * u + L2 * delta[j]) * delta[j] + 13.0 * u);
+    }
+    *C0 = c / std::fabs(y_gain) + (g15 + u) * gsum;
 }
 
 // What the library accepts as a network description (sdpcut_set_network, and sdpcut_train_loss_grad through the same lines):
@@ -305,6 +363,7 @@ static inline int net_pack(int k, int n_layers, const int32_t *widths, const dou
     }
     // ---- the fp32 filter (stage F of the skipping kernel): its margin, and -- where the network qualifies -- its weights
     out->filter_margin = net_filter_margin(k, nh, H, d_in, W, B, xoffset, gain, out->ymin, out->y_gain, out->filter_box);
+    net_filter_slope_terms(k, nh, H, d_in, W, B, xoffset, gain, out->ymin, out->y_gain, out->filter_g64, out->filter_g, &out->filter_c0);
     // (written so that a NaN margin fails)
     out->filter_ok = (out->unclamped_ok && filter_shape(k, H, nh) && out->filter_margin < FILTER_MARGIN_CUTOFF) ? 1 : 0;
     out->f32.clear();

@@ -295,7 +295,7 @@ int launch_score_points(sdpcut_ctx *h, uint32_t flags, int n_points, const doubl
 }
 
 // sdpcut_filter_audit: the filter's fp32 pass for every candidate of a list of 3-variable candidates (the caller has checked that)
-int launch_filter_audit(sdpcut_ctx *h, double *d_y32)
+int launch_filter_audit(sdpcut_ctx *h, double *d_y32, double *d_m)
 {
     const int K = 3;
     const uint32_t flags = SDPCUT_EIG | SDPCUT_NN;
@@ -303,7 +303,7 @@ int launch_filter_audit(sdpcut_ctx *h, double *d_y32)
     const ScoreArgs A = fill_score_args(h, K, flags, nullptr, nullptr, p);
     const int64_t rounds = (h->bucket[K].n + 127) / 128;      // a workgroup takes 128 candidates at a time
     const int grid = (int)(rounds < 4 * (int64_t)h->n_cu ? (rounds < 1 ? 1 : rounds) : 4 * (int64_t)h->n_cu);
-    score_filter_audit_launch(K, A, grid, d_y32, h->stream);
+    score_filter_audit_launch(K, A, grid, d_y32, d_m, h->stream);
     HIP_TRY(h, hipGetLastError());
     return 0;
 }

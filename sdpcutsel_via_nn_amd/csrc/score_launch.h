@@ -109,8 +109,9 @@ void score_mfma_skip_launch(int K, const ScoreArgs &A, int grid, hipStream_t st,
 // score_mfma_filter_built(K) and A.net.filter_ok: the arguments and the work split of score_mfma_skip_launch
 bool score_mfma_filter_built(int K);
 void score_mfma_filter_launch(int K, const ScoreArgs &A, int grid, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop);
-// filter_audit_kernel: the filter's fp32 pass for every candidate of class K, unmapped outputs into d_y32 [N] (caller order)
-void score_filter_audit_launch(int K, const ScoreArgs &A, int grid, double *d_y32, hipStream_t st);
+// filter_audit_kernel: the filter's fp32 pass for every candidate of class K, unmapped outputs into d_y32 [N] and, if d_m is not
+// null, the candidates' margins into d_m [N] (caller order)
+void score_filter_audit_launch(int K, const ScoreArgs &A, int grid, double *d_y32, double *d_m, hipStream_t st);
 void score_mfma_all_launch(const ScoreArgsAll &AA, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop);            // score_mfma_all_kernel over AA.bend[nclasses - 1] workgroups
 // score_mfma_points_kernel over class K at n_points points: grid x n_points workgroups, A.tk must be NULL
 void score_mfma_points_launch(int K, const ScoreArgs &A, const ScorePointStrides &ps, int grid, int n_points, hipStream_t st);

@@ -253,11 +253,12 @@ struct MfmaLdsSkip {
 // the lanes of the VALU tail read them, [layer][u][q][16]: for a hidden layer entries 4 tk + i = c W[48 + u][16 tk + 4 q + i]
 // (tk < 3: the twelve activations lane (q, c) holds), entries 12, 13 = c W[48 + u][48], c W[48 + u][49]; for the input layer
 // entries s = c W0[48 + u][4 s + q].  All of them are read out of the packed A-fragments of row tile 3 (net_pack.h: lane
-// u + 16 q of fragment (3, tk)), the same fl32(c W) values the matrix core used to multiply (filter_lds_fill below).
+// u + 16 q of fragment (3, tk)), the same fl32(c W) values the matrix core used to multiply (filter_lds_fill below).  Then the
+// slope weights G of the margin per candidate, 64 floats in neuron order (NetDev::f32_g).
 template <int NH>
 struct FilterLds {
-    static constexpr int BIAS = NH * 64, TAIL = NH * 2 * 4 * 16;
-    alignas(16) float v[BIAS + TAIL];
+    static constexpr int BIAS = NH * 64, TAIL = NH * 2 * 4 * 16, SLOPE = 64;
+    alignas(16) float v[BIAS + TAIL + SLOPE];
 };
 
 // LDS of one workgroup of the skipping kernel with the fp32 filter (FILTER, see score_mfma_body): TWO rings per wave.  Ring 1 (f_*,
@@ -323,12 +324,21 @@ __device__ __forceinline__ void filter_lds_fill(const NetDev &net, FilterLds<NH>
         }
         F.v[FilterLds<NH>::BIAS + i] = w;
     }
+    for (int i = threadIdx.x; i < FilterLds<NH>::SLOPE; i += blockDim.x) F.v[FilterLds<NH>::BIAS + FilterLds<NH>::TAIL + i] = net.f32_g[i];
+}
+
+// The margin of ONE candidate from the slope sum S its fp32 pass returned (net_pack.h: net_filter_slope_terms has the derivation):
+// never above the a-priori margin, and the a-priori margin itself where S is a NaN.
+__device__ __forceinline__ double filter_cand_margin(const NetDev &net, const float S)
+{
+    const double m = ((double)S * (1.0 + 0x1p-9) + net.filter_c0) * (1.0 + 0x1p-10);
+    return m < net.filter_margin ? m : net.filter_margin;
 }
 
 // The fp32 pass of the filter (stage F of the skipping kernel, and all of filter_audit_kernel): the MLP of 32 candidates on
 // v_mfma_f32_16x16x4_f32, two column tiles of 16 = two independent accumulator chains.  feat_at(row, col) is the staged (mapped,
 // fp64) input `row` of column col = 0..31.  Returns in yraw[j], on every lane of column c16 of tile j, the output layer's sum
-// (without b_out) as a double.
+// (without b_out) as a double, and in slope[j] the sum S = sum_i G_i (1 - a_i^2) over the last hidden layer's activations in fp32.
 //  * Layouts: A lane l = A[row l & 15][k l >> 4], B lane l = B[k l >> 4][col l & 15], C/D register i of lane l = row
 //    4 (l >> 4) + i.  So register i of row tile tk IS the B operand of a k-step that multiplies neurons {16 tk + 4 q + i}: the
 //    host packs the A-fragments in that k-order (net_pack.h) and the activations never leave registers.
@@ -346,11 +356,14 @@ __device__ __forceinline__ void filter_lds_fill(const NetDev &net, FilterLds<NH>
 //    net_filter_margin counts.
 //  * The output layer is a fp64 dot product of the fp32 activations with the fp64 output weights (13 fma per lane and tile) and the
 //    cross-lane sum of the fp64 pass: no fp32 rounding behind the last tansig.
+//  * The slope sum, beside it (the layer in front is dead there): per lane and tile thirteen links s = fma(G_i, fma(-a_i, a_i, 1), s)
+//    in the order of the lane's activations, the tail neuron's last -- forced to zero on q >= 2, whose exact 0 is no neuron --
+//    then the two-level lane sum of the tail rows.  This order is what net_filter_slope_terms counts.
 // Columns are independent: the tail's sums go across the q-lanes of ONE column, so a stale or padding column (NaN included)
 // changes no other column's result, and the select behind the tansig puts a finite zero on q >= 1 whatever the sum was.
 template <int K, int H, int NH, class FeatAt>
 __device__ __forceinline__ void filter_pass_f32(const NetDev &net, const FilterLds<NH> &F, const double *s_wout, FeatAt feat_at,
-                                                const int lane, double (&yraw)[2])
+                                                const int lane, double (&yraw)[2], float (&slope)[2])
 {
     constexpr int DIN = K + K * (K + 1) / 2;
     constexpr int S0 = (DIN + 3) / 4;
@@ -493,6 +506,25 @@ __device__ __forceinline__ void filter_pass_f32(const NetDev &net, const FilterL
         part = xor_add32(part);
         yraw[j] = part;
     }
+    // ---------------- the slope sum of the margin per candidate (behind the output layer: its weights are dead, G takes their place)
+    {
+        const float *s_g32 = F.v + FilterLds<NH>::BIAS + FilterLds<NH>::TAIL;
+        f4 g[3];
+#pragma unroll
+        for (int t = 0; t < 3; ++t) g[t] = *(const f4 *)&s_g32[16 * t + 4 * q];
+        const float gq = s_g32[48 + (q & 1)];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            float s = 0.0f;
+#pragma unroll
+            for (int t = 0; t < 3; ++t)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) s = __builtin_fmaf(g[t][i], __builtin_fmaf(-cur[t][j][i], cur[t][j][i], 1.0f), s);
+            const float st = __builtin_fmaf(-ctl[j], ctl[j], 1.0f);
+            s = __builtin_fmaf(gq, q < 2 ? st : 0.0f, s);
+            slope[j] = xor_add32f(xor_add16f(s));
+        }
+    }
 }
 
 // bid / nblk: this workgroup's index among the nblk workgroups that serve the class (blockIdx.x / gridDim.x of a launch over
@@ -505,8 +537,9 @@ __device__ __forceinline__ void filter_pass_f32(const NetDev &net, const FilterL
 // a violated candidate gets the bits the plain kernel gives it.  Non-violated candidates get NO obj_out store.
 // FILTER (SKIP with LDS = MfmaLdsFilter; NetDev::filter_ok): a stage F between the two.  The violated lanes append to ring 1; while
 // it holds 32 entries an fp32 pass (filter_pass_f32) evaluates the network for them, and an entry moves on to ring 2 -- the queue of
-// the fp64 pass, which is unchanged -- iff  obj32 = negSM + y32 max_elem > -filter_margin max_elem,  or it carries the bypass bit
-// (a mapped input outside filter_box, where the margin was not derived).  |y32 - y64| <= filter_margin is proven (net_pack.h), so
+// the fp64 pass, which is unchanged -- iff  obj32 = negSM + y32 max_elem > -M max_elem,  or it carries the bypass bit
+// (a mapped input outside filter_box, where the margin was not derived).  M <= filter_margin is the margin of THIS candidate, from
+// the slopes of its last hidden layer (filter_cand_margin);  |y32 - y64| <= M is proven (net_pack.h), so
 // every violated candidate with a positive measure survives and gets the bits the plain kernel gives it; the others are not strong
 // whatever their measure, and store their (non-positive) fp32 measure so that the selection, which reads obj_out of every violated
 // candidate, sees them as what they are.  The strong count, the histograms and the head are the plain kernel's.
@@ -953,9 +986,13 @@ __device__ __forceinline__ void score_mfma_body(const ScoreArgs A, LDS &S, const
                 // stale slots and are not live); the survivors are appended to ring 2 in ring-1 order
                 auto filter_round = [&](const int cnt) __attribute__((always_inline)) {
                     double yr[2];
+                    float sl[2];
                     filter_pass_f32<K, H, NH>(net, S.s_f32, s_wout,
-                                              [&](const int row, const int col) { return S.f_feat[wave][row][f_head + col]; }, lane, yr);
+                                              [&](const int row, const int col) { return S.f_feat[wave][row][f_head + col]; }, lane, yr, sl);
                     if (q == 0) { S.f_y[wave][c16] = yr[0]; S.f_y[wave][16 + c16] = yr[1]; }
+                    // (no staging for the slope sums: every lane of a column holds them, and lane s < 32 decides entry s = 16 q + c16,
+                    // which is column c16 of tile q)
+                    const float sv = q & 1 ? sl[1] : sl[0];
                     wave_lds_sync();
                     {
 #pragma clang fp contract(off)
@@ -969,7 +1006,8 @@ __device__ __forceinline__ void score_mfma_body(const ScoreArgs A, LDS &S, const
                         double obj = S.f_negsm[wave][s];
                         obj = obj + y * me;
                         // (written so that a NaN survives)
-                        const bool surv = live && (S.f_byp[wave][s] != 0 || !(obj <= -(net.filter_margin * me)));
+                        const double mc = filter_cand_margin(net, sv);
+                        const bool surv = live && (S.f_byp[wave][s] != 0 || !(obj <= -(mc * me)));
                         // The selection that follows reads obj_out of every violated candidate to tell the strong ones: an entry that
                         // stops here stores its fp32 measure, which is <= -margin max_elem <= 0 -- not strong, as proven.  (The
                         // array counts as not scored after such a launch; a completion overwrites the value.)
@@ -1160,10 +1198,10 @@ __global__ __launch_bounds__(256, 2) void score_mfma_filter_kernel(ScoreArgs A)
 }
 
 // sdpcut_filter_audit: the fp32 pass of the filter -- the same device function as stage F -- for EVERY candidate of the class, its
-// output unmapped into y32_out (caller order).  Not on the hot path: a wave takes 32 candidates at a time, stages their mapped
+// output unmapped into y32_out and, where asked for, its margin (filter_cand_margin) into m_out (caller order).  Not on the hot path: a wave takes 32 candidates at a time, stages their mapped
 // inputs exactly as the scoring kernel does (clamp-free form) and runs one pass.
 template <int K, int H, int NH>
-__global__ __launch_bounds__(256) void filter_audit_kernel(ScoreArgs A, double *y32_out)
+__global__ __launch_bounds__(256) void filter_audit_kernel(ScoreArgs A, double *y32_out, double *m_out)
 {
     constexpr int DIN = K + K * (K + 1) / 2;
     __shared__ double s_feat[4][DIN][32];
@@ -1190,7 +1228,8 @@ __global__ __launch_bounds__(256) void filter_audit_kernel(ScoreArgs A, double *
         }
         wave_lds_sync();
         double yr[2];
-        filter_pass_f32<K, H, NH>(net, s_f32, s_wout, [&](const int row, const int col) { return s_feat[wave][row][col]; }, lane, yr);
+        float sl[2];
+        filter_pass_f32<K, H, NH>(net, s_f32, s_wout, [&](const int row, const int col) { return s_feat[wave][row][col]; }, lane, yr, sl);
         if (q == 0) {
 #pragma clang fp contract(off)
 #pragma unroll
@@ -1199,7 +1238,10 @@ __global__ __launch_bounds__(256) void filter_audit_kernel(ScoreArgs A, double *
                 double acc = yr[j];
                 acc = acc + net.b_out;
                 const double y = (acc - net.y_ymin) / net.y_gain + net.y_xoffset;
-                if (cj < A.n) y32_out[A.orig[cj]] = y;
+                if (cj < A.n) {
+                    y32_out[A.orig[cj]] = y;
+                    if (m_out) m_out[A.orig[cj]] = filter_cand_margin(net, sl[j]);
+                }
             }
         }
         wave_lds_sync();      // s_feat is rewritten by the next round
@@ -1333,9 +1375,9 @@ void score_mfma_filter_launch(int K, const ScoreArgs &A, int grid, hipStream_t s
     if (K == 3) SCORE_LAUNCH((score_mfma_filter_kernel<3, NetShape<3>::H, NetShape<3>::NH>), grid, 256);
 }
 
-void score_filter_audit_launch(int K, const ScoreArgs &A, int grid, double *d_y32, hipStream_t st)
+void score_filter_audit_launch(int K, const ScoreArgs &A, int grid, double *d_y32, double *d_m, hipStream_t st)
 {
-    if (K == 3) hipLaunchKernelGGL((filter_audit_kernel<3, NetShape<3>::H, NetShape<3>::NH>), dim3(grid), dim3(256), 0, st, A, d_y32);
+    if (K == 3) hipLaunchKernelGGL((filter_audit_kernel<3, NetShape<3>::H, NetShape<3>::NH>), dim3(grid), dim3(256), 0, st, A, d_y32, d_m);
 }
 
 template <int K>

@@ -112,6 +112,50 @@ def filter_margin(k, widths, params):
     per layer  e' = (|w~| A gamma(m) + |b~| gamma(n) + |w~ - c W| A + |b~ - c b| + |c| |W| e) / |c| + 13 u,  the output layer in
     fp64, the output mapping's gain, and 1 + 2^-10."""
     p = np.asarray(params, dtype=np.float64)
+    _, _, _, Ws, _, (_, y_gain, _) = split_params(k, widths, p)
+    e = _filter_layers(k, widths, p)
+    return float((np.abs(Ws[-1][0]) * e).sum() / abs(y_gain) * (1.0 + 2.0 ** -10))
+
+
+def filter_margin_terms(k, widths, params):
+    """net_filter_slope_terms of csrc/net_pack.h, restated: the terms of the margin PER CANDIDATE,
+    M = min(filter_margin, (S (1 + 2^-9) + C0) (1 + 2^-10)),  S = sum_j G_j (1 - a_j^2) over the last hidden layer's activations.
+    -> (G float64 [64], G rounded up to float32 [64] -- what the kernel multiplies --, C0, e [H]: the a-priori bound on the error of
+    those activations).  With delta = e - 13 u the bound on the pre-activations:  G_j = |Wout_j| delta_j / |y_gain|,
+    C0 = sum_j |Wout_j| ((27 u + L2 delta_j) delta_j + 13 u) / |y_gain| + (gamma(15) + u) sum_j Gf_j,  L2 = 4 / (3 sqrt 3)."""
+    p = np.asarray(params, dtype=np.float64)
+    _, _, _, Ws, _, (_, y_gain, _) = split_params(k, widths, p)
+    u, L2 = 2.0 ** -24, 4.0 / (3.0 * np.sqrt(3.0))
+    e = _filter_layers(k, widths, p)
+    delta = e - 13.0 * u
+    w = np.abs(Ws[-1][0])
+    H = w.shape[0]
+    G = np.zeros(64)
+    G[:H] = w * delta / abs(y_gain)
+    Gf = G.astype(np.float32)
+    Gf = np.where(Gf.astype(np.float64) < G, np.nextafter(Gf, np.float32(np.inf)), Gf).astype(np.float32)
+    C0 = (w * ((27.0 * u + L2 * delta) * delta + 13.0 * u)).sum() / abs(y_gain)
+    C0 += (15.0 * u / (1.0 - 15.0 * u) + u) * float(Gf.astype(np.float64).sum())
+    return G, Gf, float(C0), e
+
+
+def filter_margin_at(k, widths, params, inputs):
+    """M of filter_margin_terms for every row of inputs [count, d_in] (the network's own, unmapped inputs), with the last hidden
+    layer's activations taken in float64 and G unrounded -> float64 [count].  The device's value (sdpcut_filter_audit_margins)
+    differs by what its fp32 activations differ: at most 2 sum_j G_j e_j, and the fp32 sum's 2^-9."""
+    p = np.asarray(params, dtype=np.float64)
+    xoffset, gain, ymin, Ws, Bs, _ = split_params(k, widths, p)
+    G, _, C0, _ = filter_margin_terms(k, widths, p)
+    a = (np.asarray(inputs, dtype=np.float64) - xoffset) * gain + ymin
+    for W, b in zip(Ws[:-1], Bs[:-1]):
+        a = _tansig(a @ W.T + b)
+    S = (1.0 - a * a) @ G[:a.shape[1]]
+    return np.minimum(filter_margin(k, widths, p), (S * (1.0 + 2.0 ** -9) + C0) * (1.0 + 2.0 ** -10))
+
+
+def _filter_layers(k, widths, params):
+    """net_filter_layers of csrc/net_pack.h: the a-priori bound e [H] on the error of the last hidden layer's fp32 activations"""
+    p = np.asarray(params, dtype=np.float64)
     xoffset, gain, ymin, Ws, Bs, (y_ymin, y_gain, y_xoffset) = split_params(k, widths, p)
     u, c = 2.0 ** -24, FILTER_EXP_SCALE
 
@@ -154,7 +198,7 @@ def filter_margin(k, widths, params):
         acc = acc + (np.abs(wt) * (A * gamma(m)) + np.abs(wt - c * W) * A + np.abs(c * W) * e).sum(axis=1)
         e = acc / abs(c) + 13.0 * u
         A = np.full(W.shape[0], 1.0 + 8.0 * u)
-    return float((np.abs(Ws[-1][0]) * e).sum() / abs(y_gain) * (1.0 + 2.0 ** -10))
+    return e
 
 
 def filter_ok(k, widths, params):
