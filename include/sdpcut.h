@@ -871,6 +871,47 @@ int sdpcut_pool_get(sdpcut_handle h, int64_t max_rows, int64_t *n_rows, int64_t 
                     int32_t *age, int32_t *nnz, int32_t *sense, double *rhs, double *norm, int32_t *cols, double *vals);
 
 /*
+ * The pool at tree nodes: separated at many LP points per call, read-only, and rows removed by serial -- what a GLOBAL pool needs
+ * (a branch-and-cut code separates from the pool of cuts found elsewhere in the tree before it runs its separators).  The rule
+ * ("Cut pool"; cutpool.py is the twin), for n_points points v_p of nb_lifted + nb_vars entries (point p at
+ * points + p * point_ld):
+ *   act, d = sense * (act - rhs) and norm are exactly the step's.  Row r is EXAMINED at every point iff (1 << state[r]) & state_mask
+ *   (SDPCUT_POOL_SEP_LP: the rows in the LP, SDPCUT_POOL_SEP_PARKED: the parked ones; both: all rows, what a global pool uses).  An
+ *   examined row is violated at p iff -d > viol_tol * norm, key (-d) / norm: the step's test and key of a parked row.  Per point:
+ *   n_violated (before the cap) and the first n_rows = min(max_return, n_violated) violated rows by (key descending, serial
+ *   ascending) in CSR form with their serials and keys.  max_return = 0 returns the counts only.
+ * NOTHING changes: the pool (states and ages included), the handle's LP point, scores, candidate list and box are what they were.
+ * One kernel launch -- a workgroup per point -- and ONE host wait per call (csrc/pool_points.hip); select_passes = 0 where every
+ * violated row fitted the workgroup's list of 4096 entries, else the number of radix digit passes the selection ran (8).
+ * All pointers of out[p] point into a pinned block of the pool: valid until the next pool call.  An empty pool returns zeros.
+ * SDPCUT_ESTATE: no pool, a pool made for another nb_vars, a round pending.  SDPCUT_EINVAL, nothing changed: n_points outside
+ * 1 .. SDPCUT_BATCH_MAX_POINTS, point_ld < nb_lifted + nb_vars, points or out NULL, state_mask 0 or with bits beyond 3, viol_tol
+ * negative or not finite, max_return outside 0 .. SDPCUT_POOL_SEP_MAX_RETURN, a result block above 256 MiB (n_points slices, each
+ * sized for min(max_return, rows of the pool) rows of SDPCUT_ROW_LD entries: about 272 bytes per row).
+ *
+ * sdpcut_pool_drop: every row whose serial is among serials[0 .. n-1] (any order; duplicates count once; serials not in the pool are
+ *   ignored; n = 0 is fine) leaves the pool by the step's stable compaction: the rows behind it move up, order kept, serials are
+ *   never reused.  *n_dropped (may be NULL) = the number removed.  One host wait.
+ */
+#define SDPCUT_POOL_SEP_LP 1u
+#define SDPCUT_POOL_SEP_PARKED 2u
+#define SDPCUT_POOL_SEP_MAX_RETURN 4096
+typedef struct sdpcut_pool_sep {     /* one per point; pointers into a pinned block of the pool, valid until the next pool call */
+    int64_t n_violated, n_rows, nnz;
+    int32_t select_passes;           /* 0: every violated row fitted the workgroup's LDS list; else radix digit passes run */
+    const int64_t *serial;           /* n_rows, rank order */
+    const double *key;               /* n_rows, rank order */
+    const int32_t *indptr;           /* n_rows + 1 */
+    const int32_t *indices;          /* nnz */
+    const double *values;            /* nnz */
+    const double *rhs;               /* n_rows */
+    const int32_t *sense;            /* n_rows */
+} sdpcut_pool_sep_t;
+int sdpcut_pool_separate_points(sdpcut_handle h, int32_t n_points, const double *points, int64_t point_ld, uint32_t state_mask,
+                                double viol_tol, int64_t max_return, sdpcut_pool_sep_t *out /* [n_points] */);
+int sdpcut_pool_drop(sdpcut_handle h, int64_t n, const int64_t *serials, int64_t *n_dropped);
+
+/*
  * Dense eigen-cuts: strategy 0 of cut_select_algo, the paper's baseline (replaces __gen_dense_eigcuts, cut_select_qp.py:757-786:
  * numpy.linalg.eigh of the whole lifted matrix [[1, x^T],[x, X]] of order dim = nb_vars + 1 and the per-entry Python comprehension
  * that builds one fully dense cut for every negative eigenvalue but the largest).  Both calls need sdpcut_set_instance and a point

@@ -57,6 +57,9 @@ DIVERSE_MAX_POOL = 16384   # SDPCUT_DIVERSE_MAX_POOL: longest pool of round_csr_
 MULTI_MAX_PER_SET = 5      # SDPCUT_MULTI_MAX_PER_SET: most eigen-cuts one index set offers (round_csr_multi / cut_rows_all)
 POOL_MAX_ROWS = 4194304    # SDPCUT_POOL_MAX_ROWS: largest capacity of a cut pool (pool_create)
 ROW_LD = 20
+POOL_SEP_LP, POOL_SEP_PARKED = 1, 2     # SDPCUT_POOL_SEP_*: the rows pool_separate_points examines, by state
+POOL_SEP_MAX_RETURN = 4096              # SDPCUT_POOL_SEP_MAX_RETURN: most rows a point gets back from pool_separate_points
+POOL_SEP_MAX_BLOCK_BYTES = 256 << 20    # largest result block of one pool_separate_points call (csrc/pool_points_layout.h)
 
 _c = ctypes
 _i32p = _c.POINTER(_c.c_int32)
@@ -107,6 +110,12 @@ class PoolStep(_c.Structure):
                 ("n_leave", _c.c_int64), ("n_enter", _c.c_int64), ("enter_nnz", _c.c_int64), ("leave", _vp), ("enter", _vp),
                 ("dropped", _vp), ("enter_indptr", _vp), ("enter_indices", _vp), ("enter_values", _vp), ("enter_rhs", _vp),
                 ("enter_sense", _vp), ("enter_key", _vp)]
+
+
+class PoolSep(_c.Structure):
+    """sdpcut_pool_sep_t of include/sdpcut.h"""
+    _fields_ = [("n_violated", _c.c_int64), ("n_rows", _c.c_int64), ("nnz", _c.c_int64), ("select_passes", _c.c_int32),
+                ("serial", _vp), ("key", _vp), ("indptr", _vp), ("indices", _vp), ("values", _vp), ("rhs", _vp), ("sense", _vp)]
 
 
 class DenseRound(_c.Structure):
@@ -179,6 +188,8 @@ SIGNATURES = {
     "sdpcut_pool_add_csr": [_vp, _c.c_int64, _i32p, _i32p, _dp, _dp, _i32p, _i64p],
     "sdpcut_pool_step": [_vp, _dp, _c.POINTER(PoolParams), _c.POINTER(PoolStep)],
     "sdpcut_pool_get": [_vp, _c.c_int64, _i64p, _i64p, _i64p, _i32p, _i32p, _i32p, _i32p, _dp, _dp, _i32p, _dp],
+    "sdpcut_pool_separate_points": [_vp, _c.c_int32, _dp, _c.c_int64, _c.c_uint32, _c.c_double, _c.c_int64, _c.POINTER(PoolSep)],
+    "sdpcut_pool_drop": [_vp, _c.c_int64, _i64p, _i64p],
     "sdpcut_dense_round": [_vp, _dp, _c.POINTER(DenseRound)],
     "sdpcut_dense_eig": [_vp, _dp, _dp],
     "sdpcut_shard_head_device": [_vp, _c.c_int, _c.c_int64, _vp],
@@ -343,6 +354,45 @@ def check_pool_params(tight_tol, viol_tol, max_age, drop_age, max_return):
     if mr != max_return or mr < 0:
         raise ValueError("max_return must be an integer >= 0")
     return tt, vt, ma, da, mr
+
+
+_POOL_SEP_STATES = {"all": POOL_SEP_LP | POOL_SEP_PARKED, "lp": POOL_SEP_LP, "parked": POOL_SEP_PARKED}
+
+
+def pool_sep_slice_bytes(cap):
+    """bytes of one point's slice of the block pool_separate_points returns, for ``cap`` rows (csrc/pool_points_layout.h)"""
+    cap = int(cap)
+    o = 64 + cap * 8 * 3 + cap * 8 * ROW_LD + (cap + 1) * 4 + cap * 4 + cap * 4 * ROW_LD
+    return (o + 63) & ~63
+
+
+def check_pool_sep_args(n_points, max_return, viol_tol, states, n_rows):
+    """The refusals of pool_separate_points that need no device (the library repeats them); n_rows: the rows of the pool
+    -> (max_return, viol_tol, state_mask)."""
+    vt = check_pool_params(0.0, viol_tol, 1, 1, 0)[1]
+    mr = int(max_return)
+    if mr != max_return or not 0 <= mr <= POOL_SEP_MAX_RETURN:
+        raise ValueError("max_return must be an integer in 0 .. %d" % POOL_SEP_MAX_RETURN)
+    if not isinstance(states, str) or states not in _POOL_SEP_STATES:
+        raise ValueError('states must be "all", "parked" or "lp"')
+    if not 1 <= int(n_points) <= BATCH_MAX_POINTS:
+        raise ValueError("1 .. %d points per call" % BATCH_MAX_POINTS)
+    cap = min(mr, int(n_rows))
+    total = int(n_points) * pool_sep_slice_bytes(cap)
+    if total > POOL_SEP_MAX_BLOCK_BYTES:
+        raise ValueError("the result block of %d points x %d bytes (%d rows each) = %d bytes exceeds the limit of %d bytes (256 MiB)"
+                         % (n_points, pool_sep_slice_bytes(cap), cap, total, POOL_SEP_MAX_BLOCK_BYTES))
+    return mr, vt, _POOL_SEP_STATES[states]
+
+
+def check_pool_serials(serials):
+    """the serials of a pool_drop -> contiguous int64 [m] (ValueError for anything but a flat list of integers)"""
+    a = np.asarray(serials)
+    if a.size == 0:
+        return np.zeros(0, dtype=np.int64)
+    if a.ndim != 1 or a.dtype.kind not in "iu":
+        raise ValueError("serials must be a flat list of integers")
+    return np.ascontiguousarray(a, dtype=np.int64)
 
 
 def check_pool_rows(indptr, indices, values, rhs, sense, ncols, room):
@@ -1057,6 +1107,49 @@ class Scorer(object):
                                                   _ptr(a["cols"], _i32p), _ptr(a["vals"], _dp)))
         a.update(n=m, next_serial=int(nxt.value))
         return a
+
+    def pool_separate_points(self, points, max_return, viol_tol=1e-6, states="all", copy=False):
+        """The pool separated at P LP points in one call with one host wait, READ-ONLY (sdpcut_pool_separate_points): points
+        [P, n(n+1)/2 + n] (a view whose rows lie further apart than their length is passed as it is).  ``states``: the rows examined
+        -- "all" (a global pool), "parked" or "lp".  -> list of P dicts: the first min(max_return, n_violated) rows violated by
+        more than ``viol_tol * ||row||`` at the point, by (key descending, serial ascending): serial, key, indptr, indices, values,
+        rhs, sense; n_violated (before the cap; max_return = 0 returns the counts alone) and select_passes (0: the violated rows
+        fitted the workgroup's list).  The pool, the Scorer's point, scores and box stay as they were.  Views of the pool's pinned
+        block, valid until the next pool call (copy=True detaches them)."""
+        self._pool_open()
+        pts = np.asarray(points)
+        n = self._point_len()
+        if not (pts.dtype == np.float64 and pts.ndim == 2 and pts.shape[1] == n and pts.shape[0] >= 1 and pts.strides[1] == 8
+                and (pts.shape[0] == 1 or (pts.strides[0] % 8 == 0 and pts.strides[0] >= 8 * n))):
+            pts = _f64(points)
+        if pts.ndim != 2 or pts.shape[1] != n:
+            raise ValueError("points must be [P, n(n+1)/2 + n]: one LP point [X packed | x] per row")
+        P = pts.shape[0]
+        mr, vt, mask = check_pool_sep_args(P, max_return, viol_tol, states, self._pool_rows)
+        recs = (PoolSep * P)()
+        self._check(self._lib.sdpcut_pool_separate_points(self._h, P, _ptr(pts, _dp), pts.strides[0] // 8 if P > 1 else n, mask, vt, mr, recs))
+        res = []
+        for o in recs:
+            w, nnz = int(o.n_rows), int(o.nnz)
+            d = dict(serial=_view(o.serial, np.int64, w), key=_view(o.key, np.float64, w),
+                     indptr=_view(o.indptr, np.int32, w + 1) if o.indptr else np.zeros(1, np.int32),
+                     indices=_view(o.indices, np.int32, nnz), values=_view(o.values, np.float64, nnz),
+                     rhs=_view(o.rhs, np.float64, w), sense=_view(o.sense, np.int32, w))
+            if copy:
+                d = {k: a.copy() for k, a in d.items()}
+            d.update(n_violated=int(o.n_violated), select_passes=int(o.select_passes))
+            res.append(d)
+        return res
+
+    def pool_drop(self, serials):
+        """The rows with these serials leave the pool (sdpcut_pool_drop): any order, duplicates count once, serials not in the pool
+        are ignored; the rows behind a removed row move up, serials are never reused -> the number removed."""
+        self._pool_open()
+        ser = check_pool_serials(serials)
+        gone = _c.c_int64(0)
+        self._check(self._lib.sdpcut_pool_drop(self._h, ser.shape[0], _ptr(ser, _i64p), ctypes.byref(gone)))
+        self._pool_rows -= int(gone.value)
+        return int(gone.value)
 
     # ------------------------------------------------------------------ many LP points per call
     def _points_arg(self, points):

@@ -9,6 +9,8 @@
 //   pool_emit_kernel     the three serial lists, the CSR of the entering rows and the counts into the pinned block
 //   pool_compact_kernel  stable compaction of the surviving rows, out of place into the second set of arrays
 // Rows are stored slot-major (cols[slot * cap + row]): a wave's 64 rows read 64 consecutive words per slot.
+// The arrays, the workspace and the row-distance function are pool_dev.h's: pool_points.hip (the read-only separation at many
+// points, the eviction by serial) shares them and ends its eviction with this file's scan and compaction (pool_compact_enqueue).
 #include <cmath>
 #include <cstring>
 #include <new>
@@ -17,43 +19,7 @@
 #include <rocprim/functional.hpp>
 
 #include "common.h"
-
-#define POOL_LD SDPCUT_ROW_LD
-#define POOL_MAX_CAP SDPCUT_POOL_MAX_ROWS
-
-// marks of a step (PoolWs::mark)
-enum { PM_LP = 0, PM_LEAVE = 1, PM_PARKED = 2, PM_VIOLATED = 3, PM_ENTER = 4, PM_DROP = 5 };
-// device counters of a step (PoolWs::cnt)
-enum { PC_VIOLATED = 0, PC_LEAVE = 1, PC_DROP = 2, PC_WORDS = 4 };
-
-struct PoolArrays {
-    int32_t *cols = nullptr;    // [POOL_LD][cap]
-    double *vals = nullptr;     // [POOL_LD][cap]
-    int32_t *nnz = nullptr, *sense = nullptr, *state = nullptr, *age = nullptr;   // [cap]
-    double *rhs = nullptr, *norm = nullptr;                                       // [cap]
-    int64_t *serial = nullptr;                                                    // [cap]
-};
-
-struct PoolWs {
-    int64_t cap = 0, n = 0, next_serial = 0, n_lp = 0, n_parked = 0;
-    int64_t ncols = 0;            // nb_lifted + nb_vars of the instance the columns were checked against
-    PoolArrays a[2];              // the live set and the target of the next compaction
-    int cur = 0;
-    double *key = nullptr;        // [cap] ranking key of a violated parked row, -inf otherwise
-    int64_t *rowid = nullptr;     // [cap] 0 .. n-1 (ascending row = ascending serial)
-    double *key_out = nullptr;    // [cap] keys of the ranked head
-    int64_t *row_out = nullptr;   // [cap] rows of the ranked head
-    int32_t *mark = nullptr;      // [cap] PM_*
-    unsigned long long *flags = nullptr, *scan = nullptr;   // [cap + 1] leave | dropped << 32 and its exclusive scan
-    int32_t *ennz = nullptr, *eptr = nullptr;               // [cap + 1] nnz of the entering rows in rank order and its exclusive scan
-    unsigned long long *cnt = nullptr;                      // [PC_WORDS]
-    void *scan_tmp = nullptr;
-    size_t scan_tmp_bytes = 0;
-    void *stage = nullptr, *stage_dev = nullptr;            // pinned staging of sdpcut_pool_add_csr
-    size_t stage_bytes = 0;
-    void *out = nullptr, *out_dev = nullptr;                // pinned block of sdpcut_pool_step
-    size_t out_bytes = 0;
-};
+#include "pool_dev.h"
 
 // the step's pinned block for n rows of which at most w return
 struct PoolOutLayout {
@@ -91,7 +57,7 @@ void free_pool_ws(sdpcut_ctx *h)
     pool_free_arrays(&w->a[1]);
     (void)hipFree(w->key); (void)hipFree(w->rowid); (void)hipFree(w->key_out); (void)hipFree(w->row_out); (void)hipFree(w->mark);
     (void)hipFree(w->flags); (void)hipFree(w->scan); (void)hipFree(w->ennz); (void)hipFree(w->eptr); (void)hipFree(w->cnt);
-    (void)hipFree(w->scan_tmp);
+    (void)hipFree(w->scan_tmp); (void)hipFree(w->d_pts); (void)hipFree(w->d_drop);
     if (w->stage) (void)hipHostFree(w->stage);
     if (w->out) (void)hipHostFree(w->out);
     delete w;
@@ -112,7 +78,7 @@ static int pool_alloc_arrays(sdpcut_ctx *h, PoolArrays *a, size_t c)
     return 0;
 }
 
-static int pool_ensure_host(sdpcut_ctx *h, void **host, void **dev, size_t *have, size_t bytes)
+int pool_ensure_host(sdpcut_ctx *h, void **host, void **dev, size_t *have, size_t bytes)
 {
     if (*have >= bytes) return 0;
     HIP_TRY(h, sdpcut_sync(h));
@@ -169,18 +135,12 @@ __global__ __launch_bounds__(256) void pool_eval_kernel(int64_t n, int64_t cap, 
     const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
     int viol = 0, leave = 0;
     if (r < n) {
-        const int len = a.nnz[r];
-        double act = 0.0, d, k = -__builtin_huge_val();
+        double k = -__builtin_huge_val();
         const double nr = a.norm[r];
         int m;
         {
 #pragma clang fp contract(off)
-            for (int s = 0; s < len; ++s) {
-                const int32_t c = a.cols[(int64_t)s * cap + r];
-                const double x = (c >= 0 && c < ncols) ? v[c] : 0.0;     // (checked when the row was added)
-                act = act + a.vals[(int64_t)s * cap + r] * x;
-            }
-            d = (double)a.sense[r] * (act - a.rhs[r]);
+            const double d = pool_row_distance(a, cap, r, ncols, v);
             if (a.state[r] == 0) {
                 const int32_t g = (d > tight_tol * nr) ? a.age[r] + 1 : 0;
                 leave = g >= max_age;
@@ -316,13 +276,24 @@ __global__ __launch_bounds__(256) void pool_compact_kernel(int64_t n, int64_t ca
 }
 
 // ------------------------------------------------------------------------------------------
-static int pool_get_ws(sdpcut_ctx *h, PoolWs **out)
+int pool_get_ws(sdpcut_ctx *h, PoolWs **out)
 {
     PoolWs *w = (PoolWs *)h->pool;
     if (!w) return sdpcut_fail(h, SDPCUT_ESTATE, "sdpcut_pool_create first");
     if (w->ncols != h->L + h->nb_vars)
         return sdpcut_fail(h, SDPCUT_ESTATE, "the instance changed since sdpcut_pool_create: destroy the pool and create it again");
     *out = w;
+    return 0;
+}
+
+int pool_compact_enqueue(sdpcut_ctx *h, PoolWs *w, int64_t n)
+{
+    size_t tb = w->scan_tmp_bytes;
+    HIP_TRY(h, rocprim::exclusive_scan(w->scan_tmp, tb, w->flags, w->scan, 0ull, (size_t)(n + 1), rocprim::plus<unsigned long long>(),
+                                       h->stream));
+    hipLaunchKernelGGL(pool_compact_kernel, dim3(pool_grid(n + 1)), dim3(256), 0, h->stream, n, w->cap, w->a[w->cur], w->a[1 - w->cur],
+                       w->mark, w->scan);
+    HIP_TRY(h, hipGetLastError());
     return 0;
 }
 

@@ -702,6 +702,28 @@ class GpuCutSelectionMixin(object):
         res = self._gpu_tri_points.tri_round_csr_points(points, int(max_cuts), boxes=boxes, copy=True)
         return [((r["indptr"], r["indices"], r["values"], r["rhs"]), r["n_violated"]) for r in res]
 
+    def separate_pool_points(self, points, max_cuts, viol_tol=1e-6, pool=None):
+        """A cut pool separated at P LP points in one device call with one host wait, read-only
+        (``Scorer.pool_separate_points`` with ``states="all"``): the open nodes of a tree search ask a GLOBAL pool first, before
+        their own separators run.  points [P, n(n+1)/2 + n]; ``pool``: a ``Scorer`` with a pool or a :class:`cutpool.CutPoolTwin`,
+        by default ``self.pool_loop.pool`` -- the pool a ``cut_select_algo(pool_max_age=...)`` run leaves behind, with the
+        eigen-cuts of that run.  -> list of P ``(csr, sense, serials, n_violated)``: csr = (indptr, indices, values, rhs) of the
+        first ``max_cuts`` rows point p violates by more than ``viol_tol * ||row||``, most violated first, as
+        :meth:`_gpu_add_csr` takes them; sense +1 (>=) / -1 (<=) per row (``_gpu_add_csr`` adds >= rows: a <= row is negated by
+        the caller); the rows' serials (what ``pool_drop`` takes); n_violated the length of the full list.  The arrays are copies.
+        The pool, its states and ages, and the scorer's LP point are left as they were.
+
+        Only GLOBALLY valid rows belong in a pool that is asked at other nodes: eigen-cuts and the root's triangle inequalities
+        are; rows valid only inside a node's box -- the rows of ``triangle_box=True`` -- must not be pooled globally.  Nothing
+        checks that."""
+        if pool is None:
+            loop = getattr(self, "pool_loop", None)
+            if loop is None:
+                raise ValueError("no pool: pass pool= or run cut_select_algo(pool_max_age=...) first")
+            pool = loop.pool
+        res = pool.pool_separate_points(points, int(max_cuts), viol_tol=viol_tol, states="all", copy=True)
+        return [((r["indptr"], r["indices"], r["values"], r["rhs"]), r["sense"], r["serial"], r["n_violated"]) for r in res]
+
     # the reference reaches these two through name-mangled private names inside class CutSolver
     _CutSolver__preprocess_triangle_ineq = _preprocess_triangle_ineq
     _CutSolver__separate_and_add_triangle = _separate_and_add_triangle

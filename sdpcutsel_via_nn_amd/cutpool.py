@@ -13,7 +13,13 @@ added, each in the LP (state 0) or parked (state 1), in ascending order of a ser
 
 :class:`CutPoolTwin` restates the device's arithmetic operation by operation (Python floats where the order of a sum matters), so
 the two agree bit for bit; it has the methods of ``Scorer.pool_*`` and serves loops that run without a device.
-:func:`check_step` checks the invariants of one step from the outside, with its own arithmetic.  :class:`PoolLoop` is the pool's
+:func:`check_step` checks the invariants of one step from the outside, with its own arithmetic.
+
+The pool at tree nodes (include/sdpcut.h: sdpcut_pool_separate_points, sdpcut_pool_drop).  ``pool_separate_points`` asks which rows P
+LP points violate and changes nothing: row r is examined iff ``(1 << state[r]) & state_mask`` ("all" = 3, "lp" = 1, "parked" = 2), an
+examined row is violated iff ``-d > viol_tol * norm`` with the key ``(-d) / norm`` -- the step's test and key of a parked row -- and
+a point gets its count and the first ``max_return`` violated rows by (key descending, serial ascending).  ``pool_drop`` removes rows
+by serial with the step's stable compaction.  :func:`check_separation` checks a separation's invariants from the outside.  :class:`PoolLoop` is the pool's
 side of a cutting-plane loop (``CutSolver.cut_select_algo(pool_max_age=...)``): it moves rows between the LP and either pool.
 """
 import math
@@ -21,7 +27,7 @@ from timeit import default_timer
 
 import numpy as np
 
-from ._capi import POOL_MAX_ROWS, ROW_LD, check_pool_params, check_pool_rows
+from ._capi import POOL_MAX_ROWS, ROW_LD, check_pool_params, check_pool_rows, check_pool_sep_args, check_pool_serials
 
 _STATE_FIELDS = ("serial", "state", "age", "nnz", "sense", "rhs", "norm", "cols", "vals")
 
@@ -147,6 +153,41 @@ class CutPoolTwin(object):
         out.update(n_in_lp=int(np.sum(self.state == 0)), n_parked=int(np.sum(self.state == 1)), n_violated=len(viol),
                    n_dropped=int(drop.sum()))
         return out
+
+    def pool_separate_points(self, points, max_return, viol_tol=1e-6, states="all", copy=False):
+        """``Scorer.pool_separate_points`` on the host, bit for bit (without ``select_passes``, which describes the kernel)."""
+        pts = np.asarray(points, dtype=np.float64)
+        if pts.ndim != 2 or pts.shape[1] != self.ncols:
+            raise ValueError("points must be [P, n(n+1)/2 + n]: one LP point [X packed | x] per row")
+        n = self.n
+        mr, vt, mask = check_pool_sep_args(pts.shape[0], max_return, viol_tol, states, n)
+        examined = [r for r in range(n) if (1 << int(self.state[r])) & mask]
+        res = []
+        for v in pts:
+            viol = []
+            for r in examined:
+                d = row_distance(self.cols[r], self.vals[r], self.nnz[r], self.rhs[r], self.sense[r], v)
+                nr = float(self.norm[r])
+                if -d > vt * nr:
+                    viol.append((-_key(d, nr), r))      # key descending, row (= serial) ascending
+            viol.sort()
+            take = [r for _, r in viol[:mr]]
+            lens = self.nnz[take].astype(np.int64)
+            res.append(dict(
+                serial=self.serial[take].copy(), key=np.array([-k for k, _ in viol[:mr]], dtype=np.float64),
+                indptr=np.concatenate([[0], np.cumsum(lens)]).astype(np.int32),
+                indices=(np.concatenate([self.cols[r, :self.nnz[r]] for r in take]) if take else np.zeros(0)).astype(np.int32),
+                values=(np.concatenate([self.vals[r, :self.nnz[r]] for r in take]) if take else np.zeros(0)).astype(np.float64),
+                rhs=self.rhs[take].copy(), sense=self.sense[take].copy(), n_violated=len(viol)))
+        return res
+
+    def pool_drop(self, serials):
+        ser = check_pool_serials(serials)
+        keep = ~np.isin(self.serial, ser)
+        gone = int(self.n - keep.sum())
+        for f in _STATE_FIELDS:
+            setattr(self, f, getattr(self, f)[keep])
+        return gone
 
     def pool_state(self):
         a = {f: getattr(self, f).copy() for f in _STATE_FIELDS}
@@ -297,4 +338,64 @@ def check_step(before, params, point, out, after):
             d, nr = dist(j), float(before["norm"][j])
             if nr > 0.0 and -d > vt * nr * (1.0 + 1e-12) + 1e-300:
                 assert (-d) / nr <= last + 1e-12 * max(1.0, abs(last)), "a parked row left out beats the last one taken"
+    return True
+
+
+def check_separation(state, points, viol_tol, states, max_return, out):
+    """Invariants of one ``pool_separate_points`` call, recomputed independently (numpy dot products: another summation order, so a
+    violation or a key within 1e-12 relative of its threshold is not judged).
+
+    state: ``pool_state()`` at the call; points [P, ncols]; out: the list the call returned.  Checks that every returned row is
+    examined and violated, that keys do not increase and equal keys ascend in serial, that no examined row left out beats the last
+    one returned, the counts, and that the CSR equals the stored row.  Raises AssertionError."""
+    mr, vt, mask = check_pool_sep_args(len(out), max_return, viol_tol, states, state["n"])
+    points = np.asarray(points, dtype=np.float64)
+    assert points.shape[0] == len(out)
+    ser = state["serial"]
+    assert np.all(np.diff(ser) > 0), "serials must ascend"
+    pos = {int(s): i for i, s in enumerate(ser)}
+    examined = ((1 << state["state"].astype(np.int64)) & mask) != 0
+    n = int(state["n"])
+    # d and the key of every row at every point, by numpy: rows padded with zero values contribute nothing
+    lens = state["nnz"]
+    live = np.arange(state["cols"].shape[1])[None, :] < lens[:, None]
+    vals = np.where(live, state["vals"], 0.0)
+    for v, o in zip(points, out):
+        act = np.sum(vals * np.where(live, v[state["cols"]], 0.0), axis=1) if n else np.zeros(0)
+        d = state["sense"] * (act - state["rhs"])
+        nr = state["norm"]
+        surely = examined & (-d > vt * nr * (1.0 + 1e-12) + 1e-300)
+        maybe = examined & (-d > vt * nr * (1.0 - 1e-12) - 1e-300)
+        assert int(surely.sum()) <= o["n_violated"] <= int(maybe.sum()), "n_violated"
+        w = int(o["serial"].shape[0])
+        assert w == min(mr, o["n_violated"]), "the number of returned rows"
+        keys, ip = np.asarray(o["key"], dtype=np.float64), o["indptr"]
+        assert keys.shape == (w,) and ip.shape == (w + 1,) and ip[0] == 0
+        assert o["rhs"].shape == (w,) and o["sense"].shape == (w,)
+        assert o["indices"].shape == o["values"].shape == (int(ip[-1]),)
+        assert len(set(int(s) for s in o["serial"])) == w, "a row returned twice"
+        taken = np.zeros(n, bool)
+        for t, s in enumerate(o["serial"]):
+            assert int(s) in pos, "a returned serial is not in the pool"
+            j = pos[int(s)]
+            taken[j] = True
+            assert examined[j], "a returned row was not examined"
+            assert maybe[j], "a returned row is not violated"
+            if nr[j] > 0.0:
+                assert abs(keys[t] - (-d[j]) / nr[j]) <= 1e-12 * max(1.0, abs(keys[t])), "key of a returned row"
+            else:
+                assert keys[t] == math.inf, "key of a zero-norm row"
+            ln = int(lens[j])
+            assert ip[t + 1] - ip[t] == ln
+            assert np.array_equal(o["indices"][ip[t]:ip[t + 1]], state["cols"][j, :ln])
+            assert np.array_equal(o["values"][ip[t]:ip[t + 1]], state["vals"][j, :ln])
+            assert o["rhs"][t] == state["rhs"][j] and o["sense"][t] == state["sense"][j]
+        for t in range(1, w):
+            assert keys[t - 1] > keys[t] or (keys[t - 1] == keys[t] and o["serial"][t - 1] < o["serial"][t]), "not in rank order"
+        if w:
+            last = keys[-1]
+            rest = surely & ~taken & (nr > 0.0)
+            if rest.any():
+                assert np.max(-d[rest] / nr[rest]) <= last + 1e-12 * max(1.0, abs(last)), "a row left out beats the last one returned"
+            assert not np.any(surely & ~taken & (nr == 0.0)) or last == math.inf, "a zero-norm row left out beats the last one returned"
     return True
