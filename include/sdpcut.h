@@ -251,6 +251,8 @@ enum { SDPCUT_STAT_ROUNDS = 1, SDPCUT_STAT_SELECT_FALLBACKS = 2, SDPCUT_STAT_SCO
  * (SDPCUT_OPT_EMIT_HEAD; TK_ROUTE_EMITTED in its strong regime without an overflow).  Read from the device: the call waits for the
  * handle's stream. */
 #define SDPCUT_STAT_EMITTED_SELECTIONS 20
+/* SDPCUT_STAT_NODE_EVAL_POINTS = points evaluated by sdpcut_node_eval_points since the handle was made. */
+#define SDPCUT_STAT_NODE_EVAL_POINTS 21
 int sdpcut_get_stat(sdpcut_handle h, int which, int64_t *value);
 
 /* The fp32 filter (SDPCUT_OPT_FP32_FILTER) of the network set for k-variable candidates: *margin = the proven bound on
@@ -1147,6 +1149,44 @@ typedef struct sdpcut_tri_csr {
 int sdpcut_tri_round_csr(sdpcut_handle h, const double *vars_values, int64_t max_out, sdpcut_tri_csr_t *out);
 int sdpcut_tri_round_csr_points(sdpcut_handle h, int32_t n_points, const double *points, int64_t point_ld, const double *lb,
                                 const double *ub, int64_t max_out, sdpcut_tri_csr_t *out);
+
+/*
+ * Node evaluation: what a tree node needs after its LP solves and separation rounds, at n_points LP points in one launch with one
+ * host wait (DESIGN.md section 5 "Node evaluation"; numpy twin, equal bit for bit: sdpcutsel_via_nn_amd/nodeeval.py).
+ * The objective is the handle's LP objective (sdpcut_set_objective) over [X packed | x]: a_ij = obj[pos(i, j)] for i <= j,
+ * c_i = obj[L + i], f(x) = sum_{i <= j} a_ij x_i x_j + sum_i c_i x_i.  Per point p, with its box lb[p], ub[p] or the unit box:
+ *   projection   x <- min(max(x, l), u); everything below uses this x and the point's own X
+ *   f_point      f at the projected x
+ *   local search Gauss-Seidel coordinate descent inside the box, i ascending, at most max_sweeps sweeps: s = c_i + sum_{j != i}
+ *                a_ij x_j, a = a_ii; a > 0: t = clamp(-s / (2 a), l_i, u_i), else t = the endpoint with the smaller
+ *                phi(t) = (a t + s) t, a tie going to l_i; x_i <- t only if phi(t) < phi(x_i) strictly; a sweep without a move
+ *                ends the search (it is counted in `sweeps`).  x_local [n], f_local = f(x_local), sweeps, moves
+ *   branching    candidates: u_i - l_i >= 4 SDPCUT_BOX_MIN_WIDTH.  branch_rule 0: g_i = X_ii - x_i^2; 1: g_i = sum_j |a_ij|
+ *                |X_ij - x_i x_j|, j = i included.  branch_var = the largest g, lowest index on ties (-1 and score 0 without a
+ *                candidate), branch_score = that g, branch_val = clamp(x_i, l_i + m, u_i - m), m = max(rho (u_i - l_i),
+ *                SDPCUT_BOX_MIN_WIDTH), then moved by single ulps where the rounding of l_i + m or u_i - m would leave a child
+ *                narrower than SDPCUT_BOX_MIN_WIDTH: both children keep a width sdpcut_set_box accepts
+ * The orders of the sums are documented in csrc/node_eval.hip; nothing is contracted.
+ * READ-ONLY: the handle's point, scores, box, pending round and pool stay as they were; the call is allowed while a box is set (it
+ * does not use it) and between the halves of a round.  Needs sdpcut_set_instance and sdpcut_set_objective (SDPCUT_ESTATE without);
+ * the first call after a sdpcut_set_objective builds the objective's dense n x n table on the device (one more launch in front of
+ * the evaluation, the same single wait) and the handle keeps it until the objective changes.
+ * SDPCUT_EINVAL, the handle unchanged: n_points outside 1 .. SDPCUT_BATCH_MAX_POINTS, more than 1024 variables, point_ld < L + n,
+ * a non-finite entry of a point or a bound, only one of lb / ub, a bound outside 0 <= l < u <= 1, max_sweeps < 0, branch_rule not
+ * 0 or 1, rho outside (0, 0.5].  Widths below SDPCUT_BOX_MIN_WIDTH are NOT refused: such a variable is never a candidate.
+ * x_local points INTO a pinned block of the handle (slice p: a 64-byte header, then n doubles, padded to 64 bytes): valid until
+ * the next call of this function on the handle.  SDPCUT_STAT_NODE_EVAL_POINTS counts the points evaluated.
+ */
+typedef struct sdpcut_node_eval {
+    double f_point, f_local;
+    double branch_score, branch_val;
+    int32_t sweeps, moves;
+    int32_t branch_var, reserved;
+    const double *x_local;          /* [n] */
+} sdpcut_node_eval_t;
+int sdpcut_node_eval_points(sdpcut_handle h, int32_t n_points, const double *points, int64_t point_ld, const double *lb /* [n_points][n] */,
+                            const double *ub /* [n_points][n] */, int32_t max_sweeps, int32_t branch_rule, double rho,
+                            sdpcut_node_eval_t *out /* [n_points] */);
 
 /* Self-test hook: multiplies A[16x4] * B[4x16] with v_mfma_f64_16x16x4_f64 using the
  * fragment maps the MLP kernel assumes; C row-major [16][16]. */

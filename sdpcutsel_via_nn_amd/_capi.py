@@ -42,6 +42,7 @@ STAT_INJECTED = 18       # TEST ONLY: launches the option has hit
 OPT_EMIT_HEAD = 18       # the skipping score launch emits its strong members, the strong regime selects from that list (include/sdpcut.h); default on
 OPT_EMIT_CAP = 19        # TEST ONLY: capacity of that list in entries (0: what the workspace gives)
 STAT_EMITTED_SELECTIONS = 20   # selections whose head came from the emitted list
+STAT_NODE_EVAL_POINTS = 21     # points evaluated by node_eval_points since the handle was made
 INJECT_SELECT, INJECT_LOOKBACK = 1, 2
 
 
@@ -118,6 +119,12 @@ class PoolSep(_c.Structure):
                 ("serial", _vp), ("key", _vp), ("indptr", _vp), ("indices", _vp), ("values", _vp), ("rhs", _vp), ("sense", _vp)]
 
 
+class NodeEval(_c.Structure):
+    """sdpcut_node_eval_t of include/sdpcut.h"""
+    _fields_ = [("f_point", _c.c_double), ("f_local", _c.c_double), ("branch_score", _c.c_double), ("branch_val", _c.c_double),
+                ("sweeps", _c.c_int32), ("moves", _c.c_int32), ("branch_var", _c.c_int32), ("reserved", _c.c_int32), ("x_local", _vp)]
+
+
 class DenseRound(_c.Structure):
     """sdpcut_dense_round_t of include/sdpcut.h"""
     _fields_ = [("dim", _c.c_int32), ("n_rows", _c.c_int32), ("sweeps", _c.c_int32), ("reserved", _c.c_int32), ("row_len", _c.c_int64),
@@ -190,6 +197,7 @@ SIGNATURES = {
     "sdpcut_pool_get": [_vp, _c.c_int64, _i64p, _i64p, _i64p, _i32p, _i32p, _i32p, _i32p, _dp, _dp, _i32p, _dp],
     "sdpcut_pool_separate_points": [_vp, _c.c_int32, _dp, _c.c_int64, _c.c_uint32, _c.c_double, _c.c_int64, _c.POINTER(PoolSep)],
     "sdpcut_pool_drop": [_vp, _c.c_int64, _i64p, _i64p],
+    "sdpcut_node_eval_points": [_vp, _c.c_int32, _dp, _c.c_int64, _dp, _dp, _c.c_int32, _c.c_int32, _c.c_double, _c.POINTER(NodeEval)],
     "sdpcut_dense_round": [_vp, _dp, _c.POINTER(DenseRound)],
     "sdpcut_dense_eig": [_vp, _dp, _dp],
     "sdpcut_shard_head_device": [_vp, _c.c_int, _c.c_int64, _vp],
@@ -616,6 +624,7 @@ class Scorer(object):
         Q_arr = _f64(Q_arr)
         if Q_arr.shape != (nb_vars * (nb_vars + 1) // 2,):
             raise ValueError("Q_arr must hold the packed upper triangle, n(n+1)/2 entries")
+        self.objective_key = None      # (an objective vector belongs to the instance it was set for: the library drops it)
         self._check(self._lib.sdpcut_set_instance(self._h, int(nb_vars), _ptr(Q_arr, _dp)))
         self.nb_vars = int(nb_vars)
 
@@ -758,6 +767,7 @@ class Scorer(object):
         """The LP objective vector in the column layout of an LP point, n(n+1)/2 + n entries (sdpcut_set_objective): what the
         objective parallelism of the efficacy measure is taken against.  None clears it.  A wrong length, a non-finite entry or an
         all-zero vector is a ValueError."""
+        self.objective_key = None      # (what the handle holds is unknown while the call can still fail)
         if obj is None:
             self._check(self._lib.sdpcut_set_objective(self._h, 0, None))
             return
@@ -765,6 +775,9 @@ class Scorer(object):
         if obj.ndim != 1:
             raise ValueError("obj must be a vector in the layout of vars_values, n(n+1)/2 + n entries")
         self._check(self._lib.sdpcut_set_objective(self._h, obj.shape[0], _ptr(obj, _dp)))
+        self.objective_key = obj.tobytes()
+
+    objective_key = None      # the bytes of the objective vector the handle holds (set_objective), None: none, or not known
 
     def set_efficacy_weight(self, w):
         """w >= 0 of escore = eff + w objpar (sdpcut_set_efficacy_weight); 0, the default, ranks by pure efficacy"""
@@ -1150,6 +1163,41 @@ class Scorer(object):
         self._check(self._lib.sdpcut_pool_drop(self._h, ser.shape[0], _ptr(ser, _i64p), ctypes.byref(gone)))
         self._pool_rows -= int(gone.value)
         return int(gone.value)
+
+    def node_eval_points(self, points, boxes=None, max_sweeps=50, branch_rule=1, rho=0.2, copy=True):
+        """What a tree node needs after its LP solves, at P LP points in one launch with one host wait, READ-ONLY
+        (sdpcut_node_eval_points; :mod:`nodeeval` states the rule and is the numpy twin, equal bit for bit): points
+        [P, n(n+1)/2 + n], boxes [P, 2, n] = (lb, ub) of every point's node or None (the unit box).  Needs :meth:`set_objective`.
+        -> dict of x_local [P, n], f_point, f_local, branch_score, branch_val (float64 [P]), sweeps, moves, branch_var (int32 [P];
+        -1: no variable is wide enough to branch on).  The Scorer's point, scores, box, pending round and pool stay as they were.
+        copy=False: x_local is a strided view of the handle's pinned block, valid until the next call of this method."""
+        pts = _f64(points)
+        if pts.ndim != 2 or pts.shape[1] != self._point_len():
+            raise ValueError("points must be [P, n(n+1)/2 + n]: one LP point [X packed | x] per row")
+        n, P = int(self.nb_vars), pts.shape[0]
+        if not 1 <= P <= BATCH_MAX_POINTS:
+            raise ValueError("1 .. %d points per call" % BATCH_MAX_POINTS)
+        lb = ub = None
+        if boxes is not None:
+            bx = _f64(boxes)
+            if bx.shape != (P, 2, n):
+                raise ValueError("boxes must be [P, 2, n]: (lb, ub) per point")
+            lb, ub = _f64(bx[:, 0, :]), _f64(bx[:, 1, :])
+        if int(max_sweeps) != max_sweeps or not 0 <= max_sweeps <= 2 ** 31 - 1:
+            raise ValueError("max_sweeps must be an integer >= 0")
+        if int(branch_rule) != branch_rule or abs(int(branch_rule)) > 2 ** 30:
+            raise ValueError("branch_rule must be 0 or 1")
+        recs = (NodeEval * P)()
+        self._check(self._lib.sdpcut_node_eval_points(self._h, P, _ptr(pts, _dp), pts.shape[1], _ptr(lb, _dp), _ptr(ub, _dp), int(max_sweeps),
+                                                      int(branch_rule), float(rho), recs))
+        slice_d = ((64 + 8 * n + 63) // 64) * 8      # doubles of a point's slice: a 64-byte header, x_local [n], padded to 64 bytes
+        xl = _view(recs[0].x_local, np.float64, (P - 1) * slice_d + n)
+        xl = np.lib.stride_tricks.as_strided(xl, shape=(P, n), strides=(8 * slice_d, 8), writeable=False)
+        return dict(x_local=xl.copy() if copy else xl,
+                    f_point=np.array([o.f_point for o in recs]), f_local=np.array([o.f_local for o in recs]),
+                    sweeps=np.array([o.sweeps for o in recs], np.int32), moves=np.array([o.moves for o in recs], np.int32),
+                    branch_var=np.array([o.branch_var for o in recs], np.int32),
+                    branch_score=np.array([o.branch_score for o in recs]), branch_val=np.array([o.branch_val for o in recs]))
 
     # ------------------------------------------------------------------ many LP points per call
     def _points_arg(self, points):

@@ -106,6 +106,7 @@ int sdpcut_destroy(sdpcut_handle h)
     free_multi_ws(h);
     free_pool_ws(h);
     free_tri_points_ws(h);
+    free_node_eval_ws(h);
     box_clear(h);
     free_lpobj(h);
     (void)hipFree(h->d_sdp_unconverged);
@@ -275,6 +276,7 @@ int sdpcut_get_stat(sdpcut_handle h, int which, int64_t *value)
     case SDPCUT_STAT_POINTS_REDONE: *value = h->stat_points_redone; return SDPCUT_OK;
     case SDPCUT_STAT_DIVERSE_POINTS_FAST: *value = h->stat_diverse_points_fast; return SDPCUT_OK;
     case SDPCUT_STAT_TRI_POINTS_FAST: *value = h->stat_tri_points_fast; return SDPCUT_OK;
+    case SDPCUT_STAT_NODE_EVAL_POINTS: *value = h->stat_node_eval_points; return SDPCUT_OK;
     case SDPCUT_STAT_EXACT_HEAD: *value = h->stat_exact_last; return SDPCUT_OK;
     case SDPCUT_STAT_EXACT_GAVE_UP: *value = h->stat_exact_gave_up; return SDPCUT_OK;
     case SDPCUT_STAT_EXACT_RETRIES: *value = h->stat_exact_retries; return SDPCUT_OK;

@@ -154,6 +154,7 @@ struct sdpcut_ctx {
     int64_t stat_points_redone = 0;   // SDPCUT_STAT_POINTS_REDONE
     int64_t stat_diverse_points_fast = 0;   // SDPCUT_STAT_DIVERSE_POINTS_FAST
     int64_t stat_tri_points_fast = 0;       // SDPCUT_STAT_TRI_POINTS_FAST
+    int64_t stat_node_eval_points = 0;      // SDPCUT_STAT_NODE_EVAL_POINTS
     PointsBufs pts;                   // sdpcut_score_points / sdpcut_round_csr_points
     // SDPCUT_OPT_EXACT_HEAD (exact_head.hip): NN-ranked heads ordered and reported by reference-order obj_improve
     bool exact_head = false;
@@ -199,6 +200,8 @@ struct sdpcut_ctx {
     double *d_eff = nullptr, *d_objpar = nullptr, *d_escore = nullptr;
     double *d_lpobj = nullptr;     // [L + n] LP objective vector (sdpcut_set_objective) or NULL; belongs to the instance
     double lpobj_norm = 0.0;       // its 2-norm, computed once when it is set
+    double *d_lpobj_dense = nullptr;   // [n][n] the objective's a_ij in both triangles (node_eval.hip), n <= 1024; freed with d_lpobj
+    bool lpobj_dense_ok = false;       // ... and it is the table of the vector in d_lpobj (built by the first node evaluation after a set_objective)
     double eff_w = 0.0;            // sdpcut_set_efficacy_weight
     bool exact_sdp = false;        // SDPCUT_OPT_EXACT_SDP: strategy 3 is accepted
     uint32_t scored = 0;
@@ -257,6 +260,7 @@ struct sdpcut_ctx {
     int64_t n_tri = 0;
     bool tri_ready = false;            // sdpcut_tri_preprocess has run (n_tri = 0 is a list too)
     void *tri_pts = nullptr;           // triangle rounds over a batch of points (tri_points.hip: TriPointsBufs); allocated by the first call
+    void *node_eval = nullptr;         // node evaluation (node_eval.hip: NodeEvalBufs): staging and result block; allocated by the first call
     std::vector<int32_t> tri_host;
     std::vector<uint8_t> tri_dense_host;
     // small staging
@@ -602,6 +606,7 @@ int tri_separate(sdpcut_ctx *h, int64_t max_out, int64_t *d_entry_out, double *d
 void tri_out_from_block(const void *block, sdpcut_tri_csr_t *out);
 // tri_points.hip
 void free_tri_points_ws(sdpcut_ctx *h);
+void free_node_eval_ws(sdpcut_ctx *h);               // node_eval.hip
 
 // topk.hip
 int topk_select_enqueue(sdpcut_ctx *h, int mode, int64_t k, double score_add, int64_t *d_idx_out,

@@ -100,7 +100,10 @@ void free_eff_ws(sdpcut_ctx *h)
 void free_lpobj(sdpcut_ctx *h)
 {
     (void)hipFree(h->d_lpobj);
+    (void)hipFree(h->d_lpobj_dense);
     h->d_lpobj = nullptr;
+    h->d_lpobj_dense = nullptr;
+    h->lpobj_dense_ok = false;
     h->lpobj_norm = 0.0;
     h->scored &= ~(uint32_t)SDPCUT_EFF;
 }
@@ -164,6 +167,7 @@ int sdpcut_set_objective(sdpcut_handle h, int64_t n_cols, const double *obj)
     if (!(nrm > 0.0) || !std::isfinite(nrm)) return sdpcut_fail(h, SDPCUT_EINVAL, "set_objective: the vector is all zero (or its norm overflows)");
     HIP_TRY(h, sdpcut_sync(h));
     if (!h->d_lpobj) HIP_TRY(h, hipMalloc((void **)&h->d_lpobj, (size_t)len * sizeof(double)));
+    h->lpobj_dense_ok = false;      // (sdpcut_node_eval_points builds its dense table of the new vector when it is first called)
     HIP_TRY(h, hipMemcpy(h->d_lpobj, obj, (size_t)len * sizeof(double), hipMemcpyHostToDevice));
     h->lpobj_norm = nrm;
     h->scored &= ~(uint32_t)SDPCUT_EFF;

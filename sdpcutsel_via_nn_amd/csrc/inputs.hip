@@ -99,7 +99,8 @@ int sdpcut_set_instance(sdpcut_handle h, int32_t nb_vars, const double *Q_arr)
 {
     if (!h) return SDPCUT_EINVAL;
     SDPCUT_NO_PENDING(h);
-    if (nb_vars < 2 || nb_vars > 40000 || !Q_arr) return sdpcut_fail(h, SDPCUT_EINVAL, "bad instance");
+    // (one variable: no candidate set fits, but sdpcut_node_eval_points serves it)
+    if (nb_vars < 1 || nb_vars > 40000 || !Q_arr) return sdpcut_fail(h, SDPCUT_EINVAL, "bad instance");
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, sdpcut_sync(h));
     const int64_t L = (int64_t)nb_vars * (nb_vars + 1) / 2;

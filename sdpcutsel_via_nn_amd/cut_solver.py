@@ -724,6 +724,26 @@ class GpuCutSelectionMixin(object):
         res = pool.pool_separate_points(points, int(max_cuts), viol_tol=viol_tol, states="all", copy=True)
         return [((r["indptr"], r["indices"], r["values"], r["rhs"]), r["sense"], r["serial"], r["n_violated"]) for r in res]
 
+    def evaluate_points(self, points, boxes=None, obj=None, **kw):
+        """Node evaluation at P LP points of the bound instance in one device call with one host wait, read-only
+        (``Scorer.node_eval_points``, :mod:`nodeeval`): per point an incumbent by coordinate descent from the projected LP point,
+        the true objective there and a branching variable with its value.  points [P, n(n+1)/2 + n]; boxes [P, 2, n] = (lb, ub)
+        of every point's node or None; ``kw``: max_sweeps, branch_rule, rho.  The objective is the bound LP's own vector
+        ``self._my_prob.obj`` = [Q_arr | c] -- handed to the handle the way strategy 6 hands it over, once per vector -- or ``obj``.
+        -> the dict of arrays ``Scorer.node_eval_points`` returns (copies).  The scorer's point, scores and box stay as they were."""
+        b = self._gpu_bind()
+        if obj is None:
+            lp = getattr(self, "_my_prob", None)
+            if lp is None or getattr(lp, "obj", None) is None:
+                raise ValueError("evaluate_points: no LP is bound (self._my_prob) and no obj= is given")
+            obj = lp.obj
+        obj = np.ascontiguousarray(obj, dtype=np.float64)
+        if b.scorer.objective_key != obj.tobytes():      # (the Scorer knows what it holds, whoever set or cleared it)
+            b.drain()
+            b.scorer.set_objective(obj)
+            b.scored &= ~_capi.EFF      # (the library drops the efficacy scores of the old vector)
+        return b.scorer.node_eval_points(points, boxes=boxes, copy=True, **kw)
+
     # the reference reaches these two through name-mangled private names inside class CutSolver
     _CutSolver__preprocess_triangle_ineq = _preprocess_triangle_ineq
     _CutSolver__separate_and_add_triangle = _separate_and_add_triangle
@@ -1024,6 +1044,40 @@ class CutSolver(GpuCutSelectionMixin):
             return gap_closed_percent, rounds_stats, round_std_devs, rounds_all_cuts
         return ([-v for v in log.bounds], clock() - t_start, [a + b for a, b in zip(log.solve_s, [0.0] + log.separation_s)],
                 sep, [0] + log.column("sdp"), log.column("tri"), n_cand)
+
+    def branch_and_cut(self, filename, dim, sel_size, strat=2, triangles=True, triangle_box=True, boxes=True, max_subs=_THRES_MAX_SUBS,
+                       tri_cuts=1000, wrap=None, **kw):
+        """Best-first branch and cut on a BoxQP ``.in`` file with the device's batched node calls (:func:`tree.branch_and_cut` with
+        :func:`tree.gpu_backends`): per iteration one ``separate_points`` round of strategy ``strat`` (1, 2, 4; ``sel_size`` as
+        ``cut_select_algo`` takes it) and, with ``triangles``, one ``separate_triangles_points`` call per separation round, and one
+        ``evaluate_points`` call, for all nodes of the batch.  ``boxes``: the optimality measure of every node in its own box;
+        ``triangle_box``: the triangle inequalities of every node's box; at most ``tri_cuts`` triangle rows per node and round.
+        ``kw``: batch, rounds, gap_tol, max_nodes, time_limit, branch_rule, rho, max_sweeps.  ``wrap(separate, evaluate)`` may
+        return the pair the driver is to call instead (tools and tests that record what passes through).
+        -> ``tree.TreeResult`` (values in the LP's minimising form, ``sign = -1``: the file maximises) with ``n_candidates``."""
+        from . import harness, tree
+        if strat not in (1, 2, 4):
+            raise AssertionError("branch_and_cut separates with strategies 1 (feasibility), 2 (optimality) and 4 (combined)")
+        inst = harness.parse_boxqp(filename)
+        self._dim = dim
+        self._nb_vars, self._nb_lifted, self._Q_arr, self._Q_adj = (inst[k] for k in ("nb_vars", "nb_lifted", "Q_arr", "adj"))
+        self._gpu_nets = {}
+        if strat in (2, 4):
+            self._load_neural_nets()
+        sc = self._gpu_new_scorer()
+        sc.set_instance(self._nb_vars, np.asarray(self._Q_arr, dtype=np.float64))
+        n_cand = sc.set_candidates_cover(inst["adj"], dim, max_subs=max_subs or 0)
+        self._agg_list = DeviceAgg(sc, n_cand, self._nb_vars, self._Q_arr)
+        self._my_prob = harness.boxqp_relaxation(inst)      # (its objective vector is what evaluate_points hands to the handle)
+        quota = self.selection_size(sel_size, n_cand, minimum=1)
+        ev = {k: kw[k] for k in ("branch_rule", "rho", "max_sweeps") if k in kw}
+        separate, evaluate = tree.gpu_backends(self, strat=strat, sel_size=quota, triangles=triangles, triangle_box=triangle_box,
+                                               boxes=boxes, tri_cuts=tri_cuts, **ev)
+        if wrap is not None:
+            separate, evaluate = wrap(separate, evaluate)
+        res = tree.branch_and_cut(inst, separate, evaluate, sign=-1.0, **kw)
+        res.n_candidates = n_cand
+        return res
 
 
 class CutSolverQCQP(CutSolver):
