@@ -24,7 +24,7 @@ NNS_SRC = "nns_compat.cpp"
 STAMP = os.path.join(HERE, ".buildhash")
 SOURCES = ["score.hip", "score_mfma.hip", "score_alt.hip", "batch_kernels.hip", "eig.hip", "rows.hip", "rank.hip", "topk.hip", "topk_passes.hip", "topk_compact.hip", "topk_small.hip", "topk_sort.hip", "tri.hip", "shard.hip", "capi.hip", "inputs.hip", "batch.hip", "round.hip", "points.hip", "exact_head.hip", "exact_sdp.hip", "dense.hip", "cover.cpp", "chordal.cpp", "covergen.hip", "coversplit.hip",
            "philox.hip", "compat.hip", "train.hip", "diverse.hip", "multirows.hip", "pool.hip", "box.hip", "efficacy.hip", "tri_points.hip", "pool_points.hip", "node_eval.hip"]
-HEADERS = ["common.h", "net_pack.h", "round_layout.h", "jacobi.h", "lmin.h", "libm_exp.h", "tansig.h", "score_plan.h", "score_launch.h", "gather.h", "rows_dev.h", "keys.h", "topk_dev.h", "topk_route.h", "topk_launch.h", "topk_small_dev.h", "batch_route.h", "exact_band.h", "exact_sdp.h", "philox.h", "tri_dev.h", "tri_layout.h", "tri_route.h", "pool_dev.h", "pool_points_layout.h", os.path.join("..", "..", "include", "sdpcut.h"),
+HEADERS = ["common.h", "bufs.h", "net_pack.h", "round_layout.h", "jacobi.h", "lmin.h", "libm_exp.h", "tansig.h", "score_plan.h", "score_launch.h", "gather.h", "rows_dev.h", "keys.h", "topk_dev.h", "topk_route.h", "topk_launch.h", "topk_small_dev.h", "batch_route.h", "exact_band.h", "exact_sdp.h", "philox.h", "tri_dev.h", "tri_layout.h", "tri_route.h", "pool_dev.h", "pool_points_layout.h", os.path.join("..", "..", "include", "sdpcut.h"),
            os.path.join("..", "..", "include", "sdpcut_nns.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -fvisibility=hidden: the libraries export what include/sdpcut.h / include/sdpcut_nns.h declare (visibility pragma there) and

@@ -20,7 +20,7 @@ int sdpcut_score(sdpcut_handle h, uint32_t flags)
         return sdpcut_fail(h, SDPCUT_EINVAL, "flags must be a combination of SDPCUT_EIG, SDPCUT_NN, SDPCUT_SDP and SDPCUT_EFF");
     if ((flags & SDPCUT_EFF) && !(h->scored & SDPCUT_EIG)) flags |= SDPCUT_EIG;      // the efficacy is that of the row of the lambda_min the handle holds
     if (!h->have_point) return sdpcut_fail(h, SDPCUT_ESTATE, "set_point first");
-    if (!h->d_eig) return sdpcut_fail(h, SDPCUT_ESTATE, "set_candidates first");
+    if (!h->d_eig.get()) return sdpcut_fail(h, SDPCUT_ESTATE, "set_candidates first");
     HIP_TRY(h, hipSetDevice(h->device));
     int rc;
     if (flags & (SDPCUT_EIG | SDPCUT_NN)) {
@@ -48,7 +48,7 @@ int sdpcut_get_scores(sdpcut_handle h, double *eigmin, double *obj_improve)
     if (obj_improve && (rc = obj_complete(h))) return rc;
     if (eigmin) {
         if (!(h->scored & SDPCUT_EIG)) return sdpcut_fail(h, SDPCUT_ESTATE, "eigenvalues not scored");
-        HIP_TRY(h, hipMemcpyAsync(eigmin, h->d_eig, h->N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(eigmin, h->d_eig.get(), h->N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     }
     if (obj_improve) {
         if (!(h->scored & SDPCUT_NN)) return sdpcut_fail(h, SDPCUT_ESTATE, "optimality measure not scored");
@@ -129,8 +129,8 @@ int sdpcut_rank(sdpcut_handle h, int strat, int64_t sel_size, int64_t max_out, i
     int64_t cap = max_out < h->N ? max_out : h->N;
     int rc = ensure_stage(h, (size_t)(cap < 1 ? 1 : cap) * 16);
     if (rc) return rc;
-    int64_t *d_idx = (int64_t *)h->d_stage;
-    double *d_sc = (double *)((char *)h->d_stage + (size_t)(cap < 1 ? 1 : cap) * 8);
+    int64_t *d_idx = (int64_t *)h->d_stage.get();
+    double *d_sc = (double *)((char *)h->d_stage.get() + (size_t)(cap < 1 ? 1 : cap) * 8);
     int64_t w = 0;
     rc = sdpcut_rank_device(h, strat, sel_size, cap, d_idx, d_sc, &w, n_total, new_strat, counters);
     if (rc) return rc;
@@ -153,8 +153,8 @@ int sdpcut_rank_fetch(sdpcut_handle h, int64_t offset, int64_t count, int64_t *i
     HIP_TRY(h, hipSetDevice(h->device));
     int rc = ensure_stage(h, (size_t)count * 16);
     if (rc) return rc;
-    int64_t *d_idx = (int64_t *)h->d_stage;
-    double *d_sc = (double *)((char *)h->d_stage + (size_t)count * 8);
+    int64_t *d_idx = (int64_t *)h->d_stage.get();
+    double *d_sc = (double *)((char *)h->d_stage.get() + (size_t)count * 8);
     rc = rank_fetch_on_device(h, offset, count, d_idx, d_sc);
     if (rc) return rc;
     HIP_TRY(h, hipMemcpyAsync(idx_out, d_idx, count * 8, hipMemcpyDeviceToHost, h->stream));
@@ -194,7 +194,7 @@ int sdpcut_cut_rows(sdpcut_handle h, int64_t count, const int64_t *idx, double *
 {
     if (!h) return SDPCUT_EINVAL;
     SDPCUT_NO_PENDING(h);
-    if (!h->have_point || !h->d_set_orig) return sdpcut_fail(h, SDPCUT_ESTATE, "set_candidates and set_point first");
+    if (!h->have_point || !h->d_set_orig.get()) return sdpcut_fail(h, SDPCUT_ESTATE, "set_candidates and set_point first");
     if (count < 0 || (count > 0 && (!idx || !lam_min || !coef || !rhs || !cols || !ks)))
         return sdpcut_fail(h, SDPCUT_EINVAL, "bad cut_rows arguments");
     if (count == 0) return SDPCUT_OK;
@@ -206,7 +206,7 @@ int sdpcut_cut_rows(sdpcut_handle h, int64_t count, const int64_t *idx, double *
     const size_t bytes = c * 8 * (3 + 2 * SDPCUT_ROW_LD) + c * 4;
     int rc = ensure_stage(h, bytes);
     if (rc) return rc;
-    char *p = (char *)h->d_stage;
+    char *p = (char *)h->d_stage.get();
     int64_t *d_idx = (int64_t *)p; p += c * 8;
     double *d_lam = (double *)p; p += c * 8;
     double *d_rhs = (double *)p; p += c * 8;
@@ -238,7 +238,7 @@ int sdpcut_eig_batch(sdpcut_handle h, int k, int64_t count, const double *x_rho,
     const size_t bytes = c * 8 * (k + m + D + D * D);
     int rc = ensure_stage(h, bytes);
     if (rc) return rc;
-    double *d_x = (double *)h->d_stage, *d_X = d_x + c * k, *d_w = d_X + c * m, *d_v = d_w + c * D;
+    double *d_x = (double *)h->d_stage.get(), *d_X = d_x + c * k, *d_w = d_X + c * m, *d_v = d_w + c * D;
     HIP_TRY(h, hipMemcpyAsync(d_x, x_rho, c * k * 8, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(d_X, X_rho, c * m * 8, hipMemcpyHostToDevice, h->stream));
     rc = launch_eig_batch(h, k, count, d_x, d_X, d_w, evecs ? d_v : nullptr);
@@ -261,7 +261,7 @@ int sdpcut_nn_batch(sdpcut_handle h, int k, int64_t count, const double *inputs,
     const size_t c = (size_t)count, d = (size_t)k * (k + 3) / 2;
     int rc = ensure_stage(h, c * 8 * (d + 1));
     if (rc) return rc;
-    double *d_in = (double *)h->d_stage, *d_out = d_in + c * d;
+    double *d_in = (double *)h->d_stage.get(), *d_out = d_in + c * d;
     HIP_TRY(h, hipMemcpyAsync(d_in, inputs, c * d * 8, hipMemcpyHostToDevice, h->stream));
     rc = launch_nn_batch(h, k, count, d_in, d_out);
     if (rc) return rc;
@@ -302,8 +302,8 @@ int sdpcut_tri_separate(sdpcut_handle h, int64_t max_out, int64_t *entry_out, do
     int64_t cap = max_out < 4 * h->n_tri ? max_out : 4 * h->n_tri;
     int rc = ensure_stage(h, (size_t)(cap < 1 ? 1 : cap) * 16);
     if (rc) return rc;
-    int64_t *d_e = (int64_t *)h->d_stage;
-    double *d_v = (double *)((char *)h->d_stage + (size_t)(cap < 1 ? 1 : cap) * 8);
+    int64_t *d_e = (int64_t *)h->d_stage.get();
+    double *d_v = (double *)((char *)h->d_stage.get() + (size_t)(cap < 1 ? 1 : cap) * 8);
     int64_t w = 0;
     rc = tri_separate(h, cap, d_e, d_v, n_violated, &w);
     if (rc) return rc;

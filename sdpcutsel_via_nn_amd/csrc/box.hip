@@ -94,7 +94,7 @@ __global__ __launch_bounds__(256) void box_points_kernel(const double *Q, const 
 int launch_box_points(sdpcut_ctx *h, int n_points, const double *d_pts, int64_t pts_stride, const double *d_ld, double *d_Qb, double *d_vb)
 {
     const int64_t m = h->L + h->nb_vars;
-    hipLaunchKernelGGL(box_points_kernel, dim3((unsigned)((m + 255) / 256), (unsigned)n_points), dim3(256), 0, h->stream, (const double *)h->d_Q,
+    hipLaunchKernelGGL(box_points_kernel, dim3((unsigned)((m + 255) / 256), (unsigned)n_points), dim3(256), 0, h->stream, (const double *)h->d_Q.get(),
                        d_pts, pts_stride, d_ld, h->nb_vars, h->L, d_Qb, d_vb);
     HIP_TRY(h, hipGetLastError());
     return 0;
@@ -104,8 +104,8 @@ int box_after_point(sdpcut_ctx *h)
 {
     if (!h->box_set) return 0;
     const int64_t m = h->L + h->nb_vars;
-    hipLaunchKernelGGL(box_point_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, h->stream, (const double *)h->d_vars,
-                       (const double *)h->d_box_ld, h->nb_vars, h->L, h->d_vars_box);
+    hipLaunchKernelGGL(box_point_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, h->stream, (const double *)h->d_vars.get(),
+                       (const double *)h->d_box_ld.get(), h->nb_vars, h->L, h->d_vars_box.get());
     HIP_TRY(h, hipGetLastError());
     return 0;
 }
@@ -123,8 +123,7 @@ int box_check(sdpcut_ctx *h, const char *what, int point, const double *lb, cons
 
 void box_clear(sdpcut_ctx *h)
 {
-    (void)hipFree(h->d_box_ld); (void)hipFree(h->d_Q_box); (void)hipFree(h->d_vars_box);
-    h->d_box_ld = h->d_Q_box = h->d_vars_box = nullptr;
+    h->d_box_ld.release(); h->d_Q_box.release(); h->d_vars_box.release();
     h->box_set = false;
     h->box_lb.clear(); h->box_ub.clear();
 }
@@ -135,7 +134,7 @@ int sdpcut_set_box(sdpcut_handle h, const double *lb, const double *ub)
 {
     if (!h) return SDPCUT_EINVAL;
     SDPCUT_NO_PENDING(h);
-    if (!h->d_Q) return sdpcut_fail(h, SDPCUT_ESTATE, "set_instance first");
+    if (!h->d_Q.get()) return sdpcut_fail(h, SDPCUT_ESTATE, "set_instance first");
     if ((lb == nullptr) != (ub == nullptr)) return sdpcut_fail(h, SDPCUT_EINVAL, "set_box: lb and ub must both be given or both be NULL");
     const int32_t n = h->nb_vars;
     if (lb) {
@@ -147,9 +146,9 @@ int sdpcut_set_box(sdpcut_handle h, const double *lb, const double *ub)
     }
     HIP_TRY(h, hipSetDevice(h->device));
     if (lb) {      // the tables first: a failed allocation leaves box, scores and tables as they were
-        if (!h->d_box_ld) HIP_TRY(h, hipMalloc((void **)&h->d_box_ld, (size_t)2 * n * sizeof(double)));
-        if (!h->d_Q_box) HIP_TRY(h, hipMalloc((void **)&h->d_Q_box, (size_t)h->L * sizeof(double)));
-        if (!h->d_vars_box) HIP_TRY(h, hipMalloc((void **)&h->d_vars_box, (size_t)(h->L + n) * sizeof(double)));
+        if (!h->d_box_ld.get()) HIP_TRY(h, h->d_box_ld.reset((size_t)2 * n));
+        if (!h->d_Q_box.get()) HIP_TRY(h, h->d_Q_box.reset((size_t)h->L));
+        if (!h->d_vars_box.get()) HIP_TRY(h, h->d_vars_box.reset((size_t)(h->L + n)));
     }
     HIP_TRY(h, sdpcut_sync(h));      // (the launches of an earlier scoring read the tables rewritten below)
     h->scored &= ~(uint32_t)(SDPCUT_NN | SDPCUT_SDP);      // the measures of the old box; lambda_min knows no box
@@ -160,11 +159,11 @@ int sdpcut_set_box(sdpcut_handle h, const double *lb, const double *ub)
     if (!lb) return SDPCUT_OK;
     std::vector<double> ld((size_t)2 * n);
     for (int32_t i = 0; i < n; ++i) { ld[i] = lb[i]; ld[(size_t)n + i] = ub[i] - lb[i]; }
-    HIP_TRY(h, hipMemcpy(h->d_box_ld, ld.data(), ld.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->d_box_ld.get(), ld.data(), ld.size() * sizeof(double), hipMemcpyHostToDevice));
     h->box_lb.assign(lb, lb + n);
     h->box_ub.assign(ub, ub + n);
-    hipLaunchKernelGGL(box_q_kernel, dim3((unsigned)((h->L + 255) / 256)), dim3(256), 0, h->stream, (const double *)h->d_Q,
-                       (const double *)h->d_box_ld, n, h->L, h->d_Q_box);
+    hipLaunchKernelGGL(box_q_kernel, dim3((unsigned)((h->L + 255) / 256)), dim3(256), 0, h->stream, (const double *)h->d_Q.get(),
+                       (const double *)h->d_box_ld.get(), n, h->L, h->d_Q_box.get());
     HIP_TRY(h, hipGetLastError());
     h->box_set = true;
     return h->have_point ? box_after_point(h) : SDPCUT_OK;
@@ -173,7 +172,7 @@ int sdpcut_set_box(sdpcut_handle h, const double *lb, const double *ub)
 int sdpcut_get_box(sdpcut_handle h, double *lb, double *ub, int *is_set)
 {
     if (!h) return SDPCUT_EINVAL;
-    if (!h->d_Q) return sdpcut_fail(h, SDPCUT_ESTATE, "set_instance first");
+    if (!h->d_Q.get()) return sdpcut_fail(h, SDPCUT_ESTATE, "set_instance first");
     for (int32_t i = 0; i < h->nb_vars; ++i) {
         if (lb) lb[i] = h->box_set ? h->box_lb[i] : 0.0;
         if (ub) ub[i] = h->box_set ? h->box_ub[i] : 1.0;
@@ -189,9 +188,9 @@ int sdpcut_get_box_tables(sdpcut_handle h, double *Q_box, double *vars_box)
     if (!h->box_set) return sdpcut_fail(h, SDPCUT_ESTATE, "get_box_tables: no node box is set");
     if (vars_box && !h->have_point) return sdpcut_fail(h, SDPCUT_ESTATE, "get_box_tables: set_point first");
     HIP_TRY(h, hipSetDevice(h->device));
-    if (Q_box) HIP_TRY(h, hipMemcpyAsync(Q_box, h->d_Q_box, (size_t)h->L * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (Q_box) HIP_TRY(h, hipMemcpyAsync(Q_box, h->d_Q_box.get(), (size_t)h->L * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (vars_box)
-        HIP_TRY(h, hipMemcpyAsync(vars_box, h->d_vars_box, (size_t)(h->L + h->nb_vars) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(vars_box, h->d_vars_box.get(), (size_t)(h->L + h->nb_vars) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, sdpcut_sync(h));
     return SDPCUT_OK;
 }

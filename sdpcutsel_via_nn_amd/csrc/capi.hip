@@ -20,30 +20,15 @@ int sdpcut_fail(sdpcut_ctx *h, int code, const std::string &msg)
     return code;
 }
 
-int ensure_stage(sdpcut_ctx *h, size_t bytes)
-{
-    if (bytes <= h->stage_bytes) return 0;
-    hipFree(h->d_stage);
-    h->d_stage = nullptr;
-    h->stage_bytes = 0;
-    HIP_TRY(h, hipMalloc(&h->d_stage, bytes));
-    h->stage_bytes = bytes;
-    return 0;
-}
+int ensure_stage(sdpcut_ctx *h, size_t bytes) { return grow(h, h->d_stage, bytes); }
 
 // Pinned host block the device can also write (kernel stores = the device-to-host transfer).
 int ensure_pinned(sdpcut_ctx *h, size_t bytes)
 {
-    if (h->pinned_bytes >= bytes) return 0;
-    HIP_TRY(h, sdpcut_sync(h));
-    if (h->pinned) (void)hipHostFree(h->pinned);
-    h->pinned = nullptr;
-    h->pinned_dev = nullptr;
-    h->pinned_bytes = 0;
-    HIP_TRY(h, hipHostMalloc(&h->pinned, bytes, hipHostMallocMapped));
-    HIP_TRY(h, hipHostGetDevicePointer(&h->pinned_dev, h->pinned, 0));
-    std::memset(h->pinned, 0, bytes < 64 ? bytes : 64);     // header incl. the completion word of wait_round_done
-    h->pinned_bytes = bytes;
+    bool grew = false;
+    const int rc = grow(h, h->pinned, bytes, &grew);
+    if (rc) return rc;
+    if (grew) std::memset(h->pinned.get(), 0, bytes < 64 ? bytes : 64);     // header incl. the completion word of wait_round_done
     return 0;
 }
 
@@ -78,9 +63,8 @@ int sdpcut_create(int device_id, sdpcut_handle *out)
     h->device = device_id;
     h->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     if (hipSetDevice(device_id) != hipSuccess || hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc((void **)&h->d_counters, 8 * sizeof(int64_t)) != hipSuccess ||
-        hipMalloc((void **)&h->d_stats, 8 * sizeof(unsigned long long)) != hipSuccess ||
-        hipMemset(h->d_stats, 0, 8 * sizeof(unsigned long long)) != hipSuccess) {
+        h->d_counters.reset(8) != hipSuccess || h->d_stats.reset(8) != hipSuccess ||
+        hipMemset(h->d_stats.get(), 0, 8 * sizeof(unsigned long long)) != hipSuccess) {
         delete h;
         return sdpcut_fail(nullptr, SDPCUT_EHIP, "stream / counter allocation failed");
     }
@@ -95,27 +79,12 @@ int sdpcut_destroy(sdpcut_handle h)
     if (!h) return SDPCUT_OK;
     hipSetDevice(h->device);
     sdpcut_sync(h);
-    free_candidates(h);
-    free_rank_ws(h);
-    free_topk_ws(h);
-    free_exact_ws(h);
-    free_dense_ws(h);
-    free_train_ws(h);
-    free_points_ws(h);
+    // the workspaces behind opaque members; everything else the handle owns frees itself with it
     free_diverse_ws(h);
     free_multi_ws(h);
     free_pool_ws(h);
     free_tri_points_ws(h);
     free_node_eval_ws(h);
-    box_clear(h);
-    free_lpobj(h);
-    (void)hipFree(h->d_sdp_unconverged);
-    (void)hipFree(h->d_tri); (void)hipFree(h->d_tri_dense3);
-    if (h->pinned) (void)hipHostFree(h->pinned);
-    if (h->point_stage) (void)hipHostFree(h->point_stage);
-    (void)hipFree(h->d_done_ticket);
-    for (int k = 0; k <= SDPCUT_MAX_K; ++k) hipFree(h->net[k].d_blob);
-    hipFree(h->d_Q); hipFree(h->d_vars); hipFree(h->d_counters); hipFree(h->d_stage); hipFree(h->d_stats);
     for (int i = 0; i < 4; ++i) if (h->ev[i]) hipEventDestroy(h->ev[i]);
     for (int i = 0; i < 3; ++i) {
         if (h->side_stream[i]) hipStreamDestroy(h->side_stream[i]);
@@ -246,7 +215,7 @@ int sdpcut_get_stat(sdpcut_handle h, int which, int64_t *value)
         if (h->nn_eval_mode == 2) {
             unsigned long long v = 0;
             HIP_TRY(h, hipSetDevice(h->device));
-            HIP_TRY(h, hipMemcpyAsync(&v, h->d_stats + 5, sizeof(v), hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(h, hipMemcpyAsync(&v, h->d_stats.get() + 5, sizeof(v), hipMemcpyDeviceToHost, h->stream));
             HIP_TRY(h, sdpcut_sync(h));
             *value = (int64_t)v;
             return SDPCUT_OK;
@@ -264,7 +233,7 @@ int sdpcut_get_stat(sdpcut_handle h, int which, int64_t *value)
         if (h->nn_skipped_on_device) {      // a sharded head: its violated count was copied to d_stats[4] behind the selection
             unsigned long long nviol = 0;
             HIP_TRY(h, hipSetDevice(h->device));
-            HIP_TRY(h, hipMemcpyAsync(&nviol, h->d_stats + 4, sizeof(nviol), hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(h, hipMemcpyAsync(&nviol, h->d_stats.get() + 4, sizeof(nviol), hipMemcpyDeviceToHost, h->stream));
             HIP_TRY(h, sdpcut_sync(h));
             h->stat_nn_skipped = h->nn_skipped_n - (int64_t)nviol;
             h->nn_skipped_on_device = false;
@@ -284,7 +253,7 @@ int sdpcut_get_stat(sdpcut_handle h, int which, int64_t *value)
     case SDPCUT_STAT_EMITTED_SELECTIONS: {
         unsigned long long v = 0;
         HIP_TRY(h, hipSetDevice(h->device));
-        HIP_TRY(h, hipMemcpyAsync(&v, h->d_stats + 6, sizeof(v), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(&v, h->d_stats.get() + 6, sizeof(v), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(h, sdpcut_sync(h));
         *value = (int64_t)v;
         return SDPCUT_OK;
@@ -295,7 +264,7 @@ int sdpcut_get_stat(sdpcut_handle h, int which, int64_t *value)
     case SDPCUT_STAT_PF_COUNT: {
         unsigned long long v = 0;
         HIP_TRY(h, hipSetDevice(h->device));
-        HIP_TRY(h, hipMemcpyAsync(&v, h->d_stats + (which - SDPCUT_STAT_DIRECT_SELECTIONS), sizeof(v), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(&v, h->d_stats.get() + (which - SDPCUT_STAT_DIRECT_SELECTIONS), sizeof(v), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(h, sdpcut_sync(h));
         *value = (int64_t)v;
         return SDPCUT_OK;
@@ -323,16 +292,15 @@ static int filter_audit(sdpcut_handle h, double *y32_out, double *m_out)
     if (!h->net[3].set || !h->net[3].dev.filter_ok) return sdpcut_fail(h, SDPCUT_ESTATE, "filter audit: the network of 3-variable candidates does not filter");
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t n = (size_t)h->N;
-    double *d_y = nullptr;
-    HIP_TRY(h, hipMalloc((void **)&d_y, (m_out ? 2 : 1) * n * sizeof(double)));
-    double *d_m = m_out ? d_y + n : nullptr;
+    DevBuf<double> y;
+    HIP_TRY(h, y.reset((m_out ? 2 : 1) * n));
+    double *d_y = y.get(), *d_m = m_out ? d_y + n : nullptr;
     int rc = launch_filter_audit(h, d_y, d_m);
     if (!rc && hipMemcpyAsync(y32_out, d_y, n * sizeof(double), hipMemcpyDeviceToHost, h->stream) != hipSuccess)
         rc = sdpcut_fail(h, SDPCUT_EHIP, "filter audit: copy failed");
     if (!rc && m_out && hipMemcpyAsync(m_out, d_m, n * sizeof(double), hipMemcpyDeviceToHost, h->stream) != hipSuccess)
         rc = sdpcut_fail(h, SDPCUT_EHIP, "filter audit: copy failed");
     if (!rc && sdpcut_sync(h) != hipSuccess) rc = sdpcut_fail(h, SDPCUT_EHIP, "filter audit: the kernel failed");
-    (void)hipFree(d_y);
     return rc;
 }
 
@@ -397,7 +365,7 @@ int sdpcut_mfma_probe(sdpcut_handle h, const double *A, const double *B, double 
     HIP_TRY(h, hipSetDevice(h->device));
     int rc = ensure_stage(h, 8 * (64 + 64 + 256));
     if (rc) return rc;
-    double *dA = (double *)h->d_stage, *dB = dA + 64, *dC = dB + 64;
+    double *dA = (double *)h->d_stage.get(), *dB = dA + 64, *dC = dB + 64;
     HIP_TRY(h, hipMemcpyAsync(dA, A, 64 * 8, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(dB, B, 64 * 8, hipMemcpyHostToDevice, h->stream));
     rc = launch_mfma_probe(h, dA, dB, dC);

@@ -2,11 +2,13 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 #include <functional>
 #include <string>
 #include <vector>
 
 #include "../../include/sdpcut.h"
+#include "bufs.h"          // DevBuf, HostBuf: the owners of every device and pinned allocation
 #include "net_pack.h"      // MAX_HIDDEN, MAX_LAYERS, SDPCUT_INPUT_CLAMP, net_pack
 #include "round_layout.h"  // RowsLayout, CsrLayout
 
@@ -54,21 +56,21 @@ struct NetDev {
 
 struct Bucket {
     int64_t n = 0;
-    int32_t *d_set = nullptr;   // SoA [k][n]
-    int32_t *d_orig = nullptr;  // [n] local candidate index (position in caller's list)
+    DevBuf<int32_t> d_set;      // SoA [k][n]
+    DevBuf<int32_t> d_orig;     // [n] local candidate index (position in caller's list)
 };
 
 struct NetHost {
     bool set = false;
     NetDev dev{};
-    double *d_blob = nullptr;   // one allocation behind all device pointers of dev
+    DevBuf<char> d_blob;        // one allocation behind all device pointers of dev (doubles, then the filter's floats)
 };
 
 // the resident training set of one candidate size and the workspace of its gradient evaluations (train.hip)
 struct TrainData {
     int64_t count = 0;
-    double *d_in = nullptr;     // [count][k(k+3)/2], the layout of sdpcut_nn_batch
-    double *d_t = nullptr;      // [count]
+    DevBuf<double> d_in;        // [count][k(k+3)/2], the layout of sdpcut_nn_batch
+    DevBuf<double> d_t;         // [count]
 };
 
 // a fused round between its two halves (round.hip: round_begin / round_end)
@@ -95,35 +97,23 @@ struct PendingRound {
 
 // what a batch of LP points needs beside the handle's single-point state (points.hip); everything grows on demand
 struct PointsBufs {
-    void *stage = nullptr, *stage_dev = nullptr;   // pinned staging of the points [P][L + n], as the host / the device sees it
-    size_t stage_bytes = 0;
-    double *d_pts = nullptr;                        // [P][L + n]
-    size_t pts_doubles = 0;
-    double *d_eig = nullptr, *d_obj = nullptr;      // [P][N]
-    size_t score_doubles = 0;
-    void *d_ws = nullptr;                           // TopkWs[P]: selection state and counters of every point
-    int ws_points = 0;
-    int64_t *d_idx = nullptr;                       // [P][cap] heads
-    double *d_score = nullptr;
-    size_t head_entries = 0;
-    uint64_t *d_agg = nullptr;                      // [P][BATCH_AGG_WORDS] look-back words of the row assembly
-    int agg_points = 0;
-    void *pinned = nullptr, *pinned_dev = nullptr;  // the batch block (batch_route.h: batch_layout)
-    size_t pinned_bytes = 0;
+    HostBuf stage{true};                            // mapped staging of the points [P][L + n] (a boxed batch: and its (l | d) rows behind them)
+    DevBuf<double> d_pts;                           // [P][L + n]
+    DevBuf<double> d_eig, d_obj;                    // [P][N]; grown together
+    DevBuf<char> d_ws;                              // TopkWs[P]: selection state and counters of every point
+    DevBuf<int64_t> d_idx;                          // [P][cap] heads; grown together with d_score
+    DevBuf<double> d_score;
+    DevBuf<uint64_t> d_agg;                         // [P][BATCH_AGG_WORDS] look-back words of the row assembly
+    HostBuf pinned{true};                           // the batch block (batch_route.h: batch_layout)
     // a boxed batch (sdpcut_*_points_boxed): its (l | d) rows travel behind the points in the staging block
-    double *d_box_ld = nullptr;                     // [P][2 n]
-    size_t box_ld_doubles = 0;
-    double *d_Q_box = nullptr, *d_vars_box = nullptr;   // [P][L] Q' and [P][L + n] transformed points (box.hip: box_points_kernel)
-    size_t box_q_doubles = 0, box_vars_doubles = 0;
+    DevBuf<double> d_box_ld;                        // [P][2 n]
+    DevBuf<double> d_Q_box, d_vars_box;             // [P][L] Q' and [P][L + n] transformed points (box.hip: box_points_kernel); grown together
     // efficacy over a batch (sdpcut_efficacy_points, the batched strategy-6 round): eff | objpar | escore, [P][N] each
-    double *d_eff = nullptr;
-    size_t eff_doubles = 0;
+    DevBuf<double> d_eff;
     // the filtered batch (sdpcut_round_csr_points_diverse): pool rows, accepted heads and walk counts of every point in one device
     // allocation; the selection counters of every point in mapped host memory
-    void *d_div = nullptr;
-    size_t div_bytes = 0;
-    void *div_sel = nullptr, *div_sel_dev = nullptr;   // [P][8] int64
-    int div_sel_points = 0;
+    DevBuf<char> d_div;
+    HostBuf div_sel{true};                          // [P][8] int64
 };
 
 struct sdpcut_ctx {
@@ -144,7 +134,7 @@ struct sdpcut_ctx {
     bool eig_kernel = true;        // SDPCUT_OPT_EIG_KERNEL: eigenvalue-only launches run eig_only_kernel (eig.hip)
     bool pf_counted = false;       // the scoring launches of the current round all counted the fine histogram (launch_score)
     bool prefilter = true;         // SDPCUT_OPT_PREFILTER: fine histogram in the score kernels, direct selection (topk_dev.h)
-    unsigned long long *d_stats = nullptr;   // device counters that outlive a round: [0] direct selections, [1..3] its diagnostics, [4] nb_violated of a skipped sharded head, [5] fp64 evaluations of a filtering launch, [6] selections from the emitted list
+    DevBuf<unsigned long long> d_stats;      // device counters that outlive a round: [0] direct selections, [1..3] its diagnostics, [4] nb_violated of a skipped sharded head, [5] fp64 evaluations of a filtering launch, [6] selections from the emitted list
     bool coop_launch = false;      // SDPCUT_OPT_COOP_LAUNCH: cooperative launch of the kernels with grid barriers (+20 us per round)
     int64_t stat_rounds = 0, stat_fallbacks = 0, stat_tie_splits = 0;   // sdpcut_get_stat
     // SDPCUT_OPT_INJECT_GIVEUP (tests): launches of inject_site (1 selection, 2 row-assembly look-back) -- inject_skip of them pass,
@@ -161,9 +151,8 @@ struct sdpcut_ctx {
     bool exact_suspended = false;  // a round that gave up is being served by the ordinary path
     int64_t stat_exact_last = 0, stat_exact_gave_up = 0, stat_exact_retries = 0;
     double q_absmax = 0.0;         // max |Q_arr| of the instance (bound on every candidate's max_elem, exact_band.h)
-    void *d_exact = nullptr;       // zero band, band ids and exact scores (exact_head.hip: ExactBufs)
-    double *d_obj_exact = nullptr; // [N] exact obj_improve of the band's members by candidate: tie key of the every-entry-visited sort
-    int64_t obj_exact_n = 0;
+    DevBuf<char> d_exact;          // zero band, band ids and exact scores (exact_head.hip: ExactBufs)
+    DevBuf<double> d_obj_exact;    // [N] exact obj_improve of the band's members by candidate: tie key of the every-entry-visited sort
     int timing = 0;                // 0 off, 1 events around the score kernel, 2 also around the ranking
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     bool timed_score = false;      // ev[0] / ev[1] were attached to the last score launch
@@ -172,8 +161,8 @@ struct sdpcut_ctx {
 
     int32_t nb_vars = 0;
     int64_t L = 0;
-    double *d_Q = nullptr;      // [L]
-    double *d_vars = nullptr;   // [L + n]
+    DevBuf<double> d_Q;         // [L]
+    DevBuf<double> d_vars;      // [L + n]
     // set by sdpcut_shard_head_device around its selection: the sort's last kernel also writes the
     // record header and the padding (topk_sort.hip, tk_mergerank_kernel)
     int64_t *shard_rec = nullptr;
@@ -181,26 +170,30 @@ struct sdpcut_ctx {
     bool have_point = false;
     // node box (box.hip, sdpcut_set_box): the tables SDPCUT_NN / SDPCUT_SDP are computed from while a box is set
     bool box_set = false;
-    double *d_box_ld = nullptr;    // [2 n]: l | d = u - l
-    double *d_Q_box = nullptr;     // [L] Q'
-    double *d_vars_box = nullptr;  // [L + n] the transformed point; follows d_vars in stream order (box_after_point)
+    DevBuf<double> d_box_ld;       // [2 n]: l | d = u - l
+    DevBuf<double> d_Q_box;        // [L] Q'
+    DevBuf<double> d_vars_box;     // [L + n] the transformed point; follows d_vars in stream order (box_after_point)
     std::vector<double> box_lb, box_ub;
 
     int64_t N = 0, base = 0;
     int32_t row_len_max = 5;       // k + k(k+1)/2 of the largest candidate size present
     Bucket bucket[SDPCUT_MAX_K + 1];
-    int32_t *d_set_orig = nullptr; // [N][5] padded, caller order
-    int32_t *d_k = nullptr;        // [N]
-    double *d_eig = nullptr, *d_obj = nullptr; // [N] caller order
+    DevBuf<int32_t> d_set_orig;    // [N][5] padded, caller order
+    DevBuf<int32_t> d_k;           // [N]
+    DevBuf<double> d_eig;          // [N] caller order
+    // the optimality array every ranking reads, [N] caller order: obj_own's, or -- inside a MeasureAsObj view -- a measure's
+    double *d_obj = nullptr;
+    DevBuf<double> obj_own;
     // SDPCUT_SDP (exact_sdp.hip): exact optimality measure and its duality gap, [N] caller order, allocated by the first scoring
-    double *d_sdp = nullptr, *d_sdp_gap = nullptr;
-    unsigned long long *d_sdp_unconverged = nullptr;   // candidates of the last exact solve that stopped at the iteration cap
+    DevBuf<double> d_sdp, d_sdp_gap;
+    DevBuf<unsigned long long> d_sdp_unconverged;      // candidates of the last exact solve that stopped at the iteration cap
     // SDPCUT_EFF (efficacy.hip): efficacy of the emitted row, its objective parallelism and the ranking score eff + w objpar, [N]
     // caller order, one allocation made by the first scoring and freed with the candidates
-    double *d_eff = nullptr, *d_objpar = nullptr, *d_escore = nullptr;
-    double *d_lpobj = nullptr;     // [L + n] LP objective vector (sdpcut_set_objective) or NULL; belongs to the instance
+    DevBuf<double> d_eff;          // the allocation; d_objpar and d_escore point into it
+    double *d_objpar = nullptr, *d_escore = nullptr;
+    DevBuf<double> d_lpobj;        // [L + n] LP objective vector (sdpcut_set_objective) or NULL; belongs to the instance
     double lpobj_norm = 0.0;       // its 2-norm, computed once when it is set
-    double *d_lpobj_dense = nullptr;   // [n][n] the objective's a_ij in both triangles (node_eval.hip), n <= 1024; freed with d_lpobj
+    DevBuf<double> d_lpobj_dense;      // [n][n] the objective's a_ij in both triangles (node_eval.hip), n <= 1024; freed with d_lpobj
     bool lpobj_dense_ok = false;       // ... and it is the table of the vector in d_lpobj (built by the first node evaluation after a set_objective)
     double eff_w = 0.0;            // sdpcut_set_efficacy_weight
     bool exact_sdp = false;        // SDPCUT_OPT_EXACT_SDP: strategy 3 is accepted
@@ -237,26 +230,25 @@ struct sdpcut_ctx {
     NetHost net[SDPCUT_MAX_K + 1];
 
     // ranking workspace (sized to N by ensure_rank_ws)
-    int64_t ws_n = 0;              // entries the full-list arrays hold (ensure_rank_ws)
-    int64_t key_n = 0;             // entries d_key_a holds (ensure_key_ws)
-    uint64_t *d_key_a = nullptr, *d_key_b = nullptr;
-    uint32_t *d_val_a = nullptr, *d_val_b = nullptr;
-    int32_t *d_flag = nullptr, *d_scan = nullptr;
-    int64_t *d_counters = nullptr; // [8]
-    void *d_tmp = nullptr;
+    int64_t ws_n = 0;              // entries the full-list arrays (all but d_key_a) hold (ensure_rank_ws)
+    DevBuf<uint64_t> d_key_a, d_key_b;   // d_key_a grows on its own (ensure_key_ws)
+    DevBuf<uint32_t> d_val_a, d_val_b;   // 2 n entries: 8 B per entry of the list, also used as u64 by the merge
+    DevBuf<int32_t> d_flag, d_scan;
+    DevBuf<int64_t> d_counters;    // [8]
+    DevBuf<char> d_tmp;            // rocPRIM's temporary storage; tmp_bytes of it are what the primitives asked for
     size_t tmp_bytes = 0;
     // top-k select workspace (topk.hip)
-    void *d_topk_ws = nullptr;
+    DevBuf<char> d_topk_ws;
     int64_t tk_coresident = 256;   // workgroups of tk_refine_kernel resident at once (occupancy x CUs), set with the workspace
-    void *d_topk_ws_alt = nullptr; // second workspace: zeroed by the epilogue of a round for the next one
+    DevBuf<char> d_topk_ws_alt;    // second workspace: zeroed by the epilogue of a round for the next one
     bool topk_alt_clean = false;   // d_topk_ws_alt has been (stream-ordered) zeroed and may be swapped in
-    uint64_t *d_sel_key = nullptr;
-    uint32_t *d_sel_idx = nullptr;
+    DevBuf<uint64_t> d_sel_key;
+    DevBuf<uint32_t> d_sel_idx;
     bool count_rank = true;        // SDPCUT_OPT_COUNT_RANK: the sort tail ranks by counting in one launch (tk_countrank_kernel)
-    unsigned long long *d_rank_acc = nullptr;   // [TK_LDSK] rank sum | arrivals of every compacted entry; zero between launches
+    DevBuf<unsigned long long> d_rank_acc;      // [TK_LDSK] rank sum | arrivals of every compacted entry; zero between launches
     // triangle inequalities (tri.hip)
-    int32_t *d_tri = nullptr;          // [T][3]
-    uint8_t *d_tri_dense3 = nullptr;   // [T] density == 3
+    DevBuf<int32_t> d_tri;             // [T][3]
+    DevBuf<uint8_t> d_tri_dense3;      // [T] density == 3
     int64_t n_tri = 0;
     bool tri_ready = false;            // sdpcut_tri_preprocess has run (n_tri = 0 is a list too)
     void *tri_pts = nullptr;           // triangle rounds over a batch of points (tri_points.hip: TriPointsBufs); allocated by the first call
@@ -264,22 +256,17 @@ struct sdpcut_ctx {
     std::vector<int32_t> tri_host;
     std::vector<uint8_t> tri_dense_host;
     // small staging
-    void *d_stage = nullptr;
-    size_t stage_bytes = 0;
-    void *pinned = nullptr;        // host block of sdpcut_select_round (written by the device, one sync per round)
-    void *pinned_dev = nullptr;    // the same memory as the device sees it
-    size_t pinned_bytes = 0;
+    DevBuf<char> d_stage;
+    HostBuf pinned{true};          // host block of sdpcut_select_round (written by the device, one sync per round)
     // sdpcut_set_point: pinned staging copy of the caller's LP point and the event of its transfer
-    void *point_stage = nullptr, *point_stage_dev = nullptr;
-    size_t point_stage_bytes = 0;
+    HostBuf point_stage{true};
     bool point_inflight = false;   // a transfer out of point_stage may still be running
     int64_t round_serial = 0;      // completion word of the fused round (round_rows_kernel -> pinned header)
-    uint32_t *d_done_ticket = nullptr;   // completion ticket, then the look-back words of the row assemblies (ensure_round_sync)
+    DevBuf<uint32_t> d_done_ticket;      // completion ticket, then the look-back words of the row assemblies (ensure_round_sync)
     PendingRound pend;
     TrainData train[SDPCUT_MAX_K + 1];   // sdpcut_train_set_data; independent of instance, candidates, point and networks
-    double *d_train_ws = nullptr;  // parameters | per-workgroup partial sums | reduced loss and gradient (train.hip)
-    size_t train_ws_doubles = 0;
-    void *d_dense = nullptr;       // dense eigen-cuts (dense.hip): V^T, sorted vectors, eigenvalues, n_rows; allocated by the first call
+    DevBuf<double> d_train_ws;     // parameters | per-workgroup partial sums | reduced loss and gradient (train.hip)
+    DevBuf<char> d_dense;          // dense eigen-cuts (dense.hip): V^T, sorted vectors, eigenvalues, n_rows; allocated by the first call
     void *diverse = nullptr;       // diverse selection (diverse.hip: DiverseWs): pool rows, pair bits, accepted head; allocated by the first call
     void *multi = nullptr;         // multi-cut rounds (multirows.hip: MultiWs): head, host arrays; allocated by the first call
     void *pool = nullptr;          // cut pool (pool.hip: PoolWs): the rows of a loop, in the LP or parked; sdpcut_pool_create
@@ -396,6 +383,49 @@ static inline void csr_out_from_block(const void *block, sdpcut_round_csr_t *out
                                std::string(#expr) + ": " + hipGetErrorString(e__));        \
     } while (0)
 
+// The one way a buffer of the handle grows (B: DevBuf<T> or HostBuf, count in its units).  Large enough: nothing is touched.
+// Else the handle's stream is waited for -- whatever was launched may still read the old block, also behind an error return that
+// skipped its call's own wait -- and the buffer is reallocated: its contents are gone, *grew tells who has to fill it again.
+template <class B> static inline int grow(sdpcut_ctx *h, B &buf, size_t count, bool *grew = nullptr)
+{
+    if (buf.size() >= count) return 0;
+    HIP_TRY(h, sdpcut_sync(h));
+    HIP_TRY(h, buf.reset(count));
+    if (grew) *grew = true;
+    return 0;
+}
+
+// The intake of a batch of LP points (n_points, points, point_ld[, lb, ub]), shared by the seven calls that take one; `prefix`
+// goes in front of the texts (only sdpcut_node_eval_points has one).
+static inline int check_point_batch(sdpcut_ctx *h, const char *prefix, int32_t n_points, const double *points, int64_t point_ld, int64_t min_ld)
+{
+    const std::string pre(prefix);
+    if (n_points < 1 || n_points > SDPCUT_BATCH_MAX_POINTS)
+        return sdpcut_fail(h, SDPCUT_EINVAL, pre + "n_points must be 1 .. SDPCUT_BATCH_MAX_POINTS (" + std::to_string(SDPCUT_BATCH_MAX_POINTS) + ")");
+    if (!points) return sdpcut_fail(h, SDPCUT_EINVAL, pre + "points is NULL");
+    if (point_ld < min_ld) return sdpcut_fail(h, SDPCUT_EINVAL, pre + "point_ld must be at least L + n");
+    return 0;
+}
+static inline int check_box_pair(sdpcut_ctx *h, const char *prefix, const double *lb, const double *ub)
+{
+    if ((lb == nullptr) != (ub == nullptr)) return sdpcut_fail(h, SDPCUT_EINVAL, std::string(prefix) + "lb and ub must both be given or both be NULL");
+    return 0;
+}
+// rows of m doubles, packed, from P rows of stride point_ld
+static inline void pack_points(double *dst, int P, const double *points, int64_t point_ld, int64_t m)
+{
+    for (int p = 0; p < P; ++p) memcpy(dst + (size_t)p * (size_t)m, points + (size_t)p * (size_t)point_ld, (size_t)m * 8);
+}
+// the (l | d = u - l) rows of P boxes as sdpcut_set_box forms them, [P][2 nv] packed
+static inline void pack_box_ld(double *dst, int P, int64_t nv, const double *lb, int64_t lb_ld, const double *ub, int64_t ub_ld)
+{
+    for (int p = 0; p < P; ++p) {
+        const double *l = lb + (size_t)p * (size_t)lb_ld, *u = ub + (size_t)p * (size_t)ub_ld;
+        double *d = dst + (size_t)p * 2 * (size_t)nv;
+        for (int64_t i = 0; i < nv; ++i) { d[i] = l[i]; d[nv + i] = u[i] - l[i]; }
+    }
+}
+
 // score.hip
 // Optional: the score kernels count their scores by the leading radix digit of the selection keys
 // (ScoreArgs::tk): ws = zeroed TopkWs of the selection that follows (topk_begin).
@@ -425,7 +455,7 @@ int launch_round_csr(sdpcut_ctx *h, int64_t cap, const int64_t *d_c4, int64_t li
 #define ROUND_TICKET_BYTES 64
 #define ROUND_AGG_WORDS 512
 int ensure_round_sync(sdpcut_ctx *h);
-static inline uint64_t *round_agg_words(sdpcut_ctx *h) { return (uint64_t *)((char *)h->d_done_ticket + ROUND_TICKET_BYTES); }
+static inline uint64_t *round_agg_words(sdpcut_ctx *h) { return (uint64_t *)((char *)h->d_done_ticket.get() + ROUND_TICKET_BYTES); }
 // eig.hip: lambda_min of every candidate, one launch over all size classes; tk = TopkWs of a feasibility selection or NULL
 int launch_eig_only(sdpcut_ctx *h, void *tk, hipEvent_t ev_start, hipEvent_t ev_stop, int64_t pf_k = 0);
 // the point-axis forms of the scoring and of the CSR assembly (a batch of LP points, points.hip): eig.hip, score.hip, rows.hip
@@ -436,7 +466,6 @@ int launch_score_points(sdpcut_ctx *h, uint32_t flags, int n_points, const doubl
 int launch_round_csr_points(sdpcut_ctx *h, int p_first, int n_points, int64_t cap, int ld, const int64_t *d_c4, int64_t c4_stride,
                             const int64_t *d_idx, const double *d_score, const double *d_pts, int64_t pts_stride, const double *d_eig,
                             int64_t eig_stride, uint64_t *d_agg, int64_t agg_stride, void *block, int64_t block_stride, int64_t serial);
-void free_points_ws(sdpcut_ctx *h);              // points.hip
 int wait_round_done(sdpcut_ctx *h, const int64_t *word, int64_t serial);   // round.hip
 // round.hip: a CSR assembly into the handle's pinned block, launched here and waited for, once more if its look-back gave up
 int csr_assemble_wait(sdpcut_ctx *h, int last_word, int launches, bool count_failure, const char *what,
@@ -459,7 +488,6 @@ int merge_topk_on_device(sdpcut_ctx *h, int64_t count, const double *d_scores, c
                          const int64_t *d_ids, int64_t max_out, double *d_score_out, int64_t *d_id_out);
 int gather_scores_on_device(sdpcut_ctx *h, int64_t count, const int64_t *d_ids, double *d_eig_out, double *d_obj_out);
 int rank_fetch_on_device(sdpcut_ctx *h, int64_t offset, int64_t count, int64_t *d_idx_out, double *d_score_out);
-void free_rank_ws(sdpcut_ctx *h);
 
 // stage: see topk_select_enqueue; auto_regime: the combined strategy's regime is resolved on the device
 // from the strong count the score kernels of this round left in the selection workspace
@@ -477,7 +505,6 @@ int64_t exact_widest_band(const sdpcut_ctx *h);
 int exact_head_enqueue(sdpcut_ctx *h, int strat, int64_t sel_size, int64_t cap, int64_t band, int64_t *d_idx_out, double *d_score_out,
                        const int64_t **d_c4);
 int exact_head_verdict(sdpcut_ctx *h, const int64_t c4[7], int64_t band);   // 0 exact, 1 retry with the widest band, 2 give up
-void free_exact_ws(sdpcut_ctx *h);
 // the sharded entry points have no exact merge
 #define SDPCUT_NO_EXACT(h)                                                                                                \
     do {                                                                                                                  \
@@ -490,11 +517,11 @@ void free_exact_ws(sdpcut_ctx *h);
 // (never together with SDPCUT_EIG: launch_score splits such a call), else the originals
 static inline const double *score_vars(const sdpcut_ctx *h, uint32_t flags)
 {
-    return (h->box_set && (flags & (SDPCUT_NN | SDPCUT_SDP)) && !(flags & SDPCUT_EIG)) ? h->d_vars_box : h->d_vars;
+    return (h->box_set && (flags & (SDPCUT_NN | SDPCUT_SDP)) && !(flags & SDPCUT_EIG)) ? h->d_vars_box.get() : h->d_vars.get();
 }
 static inline const double *score_Q(const sdpcut_ctx *h, uint32_t flags)
 {
-    return (h->box_set && (flags & (SDPCUT_NN | SDPCUT_SDP)) && !(flags & SDPCUT_EIG)) ? h->d_Q_box : h->d_Q;
+    return (h->box_set && (flags & (SDPCUT_NN | SDPCUT_SDP)) && !(flags & SDPCUT_EIG)) ? h->d_Q_box.get() : h->d_Q.get();
 }
 int box_after_point(sdpcut_ctx *h);   // the transformed point from d_vars, behind its copy on the handle's stream; nothing without a box
 void box_clear(sdpcut_ctx *h);        // drop the box and its tables (the caller has waited for the stream)
@@ -509,10 +536,6 @@ int launch_box_points(sdpcut_ctx *h, int n_points, const double *d_pts, int64_t 
             return sdpcut_fail((h), SDPCUT_ESTATE, std::string(what) + ": a node box is set (sdpcut_set_box); clear it first"); \
     } while (0)
 
-// dense.hip
-void free_dense_ws(sdpcut_ctx *h);
-// train.hip
-void free_train_ws(sdpcut_ctx *h);
 // diverse.hip
 void free_diverse_ws(sdpcut_ctx *h);
 // The filter of a batch of points (div_rows_points_kernel, div_points_kernel): point p reads the head its selection emitted (row p
@@ -568,7 +591,7 @@ struct MeasureAsObj {
     MeasureAsObj(sdpcut_ctx *ctx, uint32_t measure)
         : h(ctx), obj(ctx->d_obj), scored(ctx->scored), exact_head(ctx->exact_head), obj_partial(ctx->obj_partial)
     {
-        h->d_obj = measure == SDPCUT_EFF ? h->d_escore : h->d_sdp;
+        h->d_obj = measure == SDPCUT_EFF ? h->d_escore : h->d_sdp.get();
         h->scored = (scored & SDPCUT_EIG) | ((scored & measure) ? (uint32_t)SDPCUT_NN : 0u);
         h->exact_head = false;
         h->obj_partial = false;
@@ -622,7 +645,6 @@ int topk_select_on_device(sdpcut_ctx *h, int mode, int64_t k, double score_add, 
 int topk_select_keys_on_device(sdpcut_ctx *h, int64_t n, int64_t k, int64_t *d_idx_out, double *d_val_out, int64_t cnt[5]);
 // the same selection enqueued, without the host wait: *d_counters_out = its five counters on the device (what `cnt` receives)
 int topk_select_keys_enqueue(sdpcut_ctx *h, int64_t n, int64_t k, int64_t *d_idx_out, double *d_val_out, const int64_t **d_counters_out);
-void free_topk_ws(sdpcut_ctx *h);
 // the void COMBALL selection in the handle's workspace, answered by two selections over precomputed keys (see topk.hip)
 int topk_tie_split(sdpcut_ctx *h, int64_t k, int64_t *d_idx_out, double *d_score_out, int64_t *k_eff_out);
 // the workspace NOT used by the selection enqueued last, and its size in 8-byte words: a later

@@ -267,54 +267,46 @@ int run_cover(sdpcut_ctx *h, const std::vector<uint64_t> &adj_host, const std::v
               int64_t max_subs, int64_t *count_out)
 {
     const int64_t E = (int64_t)(edges.size() / 2);
-    uint64_t *d_adj = nullptr;
-    int32_t *d_edges = nullptr, *d_per = nullptr;
-    int64_t *d_off = nullptr;
-    auto cleanup = [&]() { hipFree(d_adj); hipFree(d_edges); hipFree(d_per); hipFree(d_off); };
-#define COVER_TRY(expr)                                                                         \
-    do {                                                                                        \
-        hipError_t e__ = (expr);                                                                \
-        if (e__ != hipSuccess) {                                                                \
-            cleanup();                                                                          \
-            return sdpcut_fail(h, SDPCUT_EHIP, std::string(#expr) + ": " + hipGetErrorString(e__)); \
-        }                                                                                       \
-    } while (0)
-    COVER_TRY(hipMalloc((void **)&d_adj, adj_host.size() * 8));
-    COVER_TRY(hipMalloc((void **)&d_edges, (size_t)(E < 1 ? 1 : E) * 8));
-    COVER_TRY(hipMalloc((void **)&d_per, (size_t)(E < 1 ? 1 : E) * 20));
-    COVER_TRY(hipMalloc((void **)&d_off, (size_t)(E + 1) * 40));
-    COVER_TRY(hipMemcpy(d_adj, adj_host.data(), adj_host.size() * 8, hipMemcpyHostToDevice));
-    if (E > 0) COVER_TRY(hipMemcpy(d_edges, edges.data(), (size_t)E * 8, hipMemcpyHostToDevice));
+    DevBuf<uint64_t> adj;
+    DevBuf<int32_t> edg, per;
+    DevBuf<int64_t> off;      // (temporaries of this call: freed on every way out)
+    HIP_TRY(h, adj.reset(adj_host.size()));
+    HIP_TRY(h, edg.reset((size_t)(E < 1 ? 1 : E) * 2));
+    HIP_TRY(h, per.reset((size_t)(E < 1 ? 1 : E) * 5));
+    HIP_TRY(h, off.reset((size_t)(E + 1) * 5));
+    uint64_t *const d_adj = adj.get();
+    int32_t *const d_edges = edg.get(), *const d_per = per.get();
+    int64_t *const d_off = off.get();
+    HIP_TRY(h, hipMemcpy(d_adj, adj_host.data(), adj_host.size() * 8, hipMemcpyHostToDevice));
+    if (E > 0) HIP_TRY(h, hipMemcpy(d_edges, edges.data(), (size_t)E * 8, hipMemcpyHostToDevice));
     const unsigned grid = (unsigned)((E + 3) / 4);
     Sink sk{};
     if (E > 0) hipLaunchKernelGGL((cover_kernel<W, false>), dim3(grid), dim3(256), 0, h->stream, d_adj, d_edges, E, dim, d_per,
                                   (const int64_t *)nullptr, sk);
     hipLaunchKernelGGL(cover_scan_kernel, dim3(1), dim3(1024), 0, h->stream, d_per, E, d_off);
-    COVER_TRY(hipGetLastError());
+    HIP_TRY(h, hipGetLastError());
     int64_t totals[5] = {0, 0, 0, 0, 0};
-    COVER_TRY(hipMemcpyAsync(totals, d_off + 5 * E, 40, hipMemcpyDeviceToHost, h->stream));
-    COVER_TRY(sdpcut_sync(h));
+    HIP_TRY(h, hipMemcpyAsync(totals, d_off + 5 * E, 40, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, sdpcut_sync(h));
     *count_out = totals[0];
-    if (totals[0] > 0x7fffffffLL) { cleanup(); return sdpcut_fail(h, SDPCUT_EINVAL, "cover has more than 2^31 - 1 candidates"); }
-    if (max_subs > 0 && totals[0] >= max_subs) { cleanup(); return SDPCUT_OK; }     // count only (the reference's guard)
+    if (totals[0] > 0x7fffffffLL) return sdpcut_fail(h, SDPCUT_EINVAL, "cover has more than 2^31 - 1 candidates");
+    if (max_subs > 0 && totals[0] >= max_subs) return SDPCUT_OK;     // count only (the reference's guard)
     int64_t cnt[SDPCUT_MAX_K + 1] = {0, 0, totals[1], totals[2], totals[3], totals[4]};
     int rc = alloc_candidates(h, totals[0], cnt, 0);
-    if (rc) { cleanup(); return rc; }
+    if (rc) return rc;
     if (totals[0] > 0) {
-        sk.set5 = h->d_set_orig;
-        sk.ks = h->d_k;
+        sk.set5 = h->d_set_orig.get();
+        sk.ks = h->d_k.get();
         for (int s = 2; s <= SDPCUT_MAX_K; ++s) {
-            sk.soa[s] = h->bucket[s].d_set;
-            sk.orig[s] = h->bucket[s].d_orig;
+            sk.soa[s] = h->bucket[s].d_set.get();
+            sk.orig[s] = h->bucket[s].d_orig.get();
             sk.cls_n[s] = cnt[s];
         }
         hipLaunchKernelGGL((cover_kernel<W, true>), dim3(grid), dim3(256), 0, h->stream, d_adj, d_edges, E, dim, d_per,
                            (const int64_t *)d_off, sk);
-        COVER_TRY(hipGetLastError());
-        COVER_TRY(sdpcut_sync(h));
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, sdpcut_sync(h));
     }
-    cleanup();
-#undef COVER_TRY
     return SDPCUT_OK;
 }
 
@@ -382,56 +374,48 @@ int run_cover_ch(sdpcut_ctx *h, const std::vector<uint64_t> &ext_host, const std
                  const std::vector<int32_t> &edges, int64_t max_subs, int64_t *count_out)
 {
     const int64_t E = (int64_t)(edges.size() / 2);
-    uint64_t *d_ext = nullptr, *d_orig = nullptr;
-    int32_t *d_edges = nullptr, *d_per = nullptr;
-    int64_t *d_off = nullptr;
-    auto cleanup = [&]() { hipFree(d_ext); hipFree(d_orig); hipFree(d_edges); hipFree(d_per); hipFree(d_off); };
-#define COVER_TRY(expr)                                                                         \
-    do {                                                                                        \
-        hipError_t e__ = (expr);                                                                \
-        if (e__ != hipSuccess) {                                                                \
-            cleanup();                                                                          \
-            return sdpcut_fail(h, SDPCUT_EHIP, std::string(#expr) + ": " + hipGetErrorString(e__)); \
-        }                                                                                       \
-    } while (0)
-    COVER_TRY(hipMalloc((void **)&d_ext, ext_host.size() * 8));
-    COVER_TRY(hipMalloc((void **)&d_orig, orig_host.size() * 8));
-    COVER_TRY(hipMalloc((void **)&d_edges, (size_t)(E < 1 ? 1 : E) * 8));
-    COVER_TRY(hipMalloc((void **)&d_per, (size_t)(E < 1 ? 1 : E) * 20));
-    COVER_TRY(hipMalloc((void **)&d_off, (size_t)(E + 1) * 40));
-    COVER_TRY(hipMemcpy(d_ext, ext_host.data(), ext_host.size() * 8, hipMemcpyHostToDevice));
-    COVER_TRY(hipMemcpy(d_orig, orig_host.data(), orig_host.size() * 8, hipMemcpyHostToDevice));
-    if (E > 0) COVER_TRY(hipMemcpy(d_edges, edges.data(), (size_t)E * 8, hipMemcpyHostToDevice));
+    DevBuf<uint64_t> ext, orig;
+    DevBuf<int32_t> edg, per;
+    DevBuf<int64_t> off;      // (temporaries of this call: freed on every way out)
+    HIP_TRY(h, ext.reset(ext_host.size()));
+    HIP_TRY(h, orig.reset(orig_host.size()));
+    HIP_TRY(h, edg.reset((size_t)(E < 1 ? 1 : E) * 2));
+    HIP_TRY(h, per.reset((size_t)(E < 1 ? 1 : E) * 5));
+    HIP_TRY(h, off.reset((size_t)(E + 1) * 5));
+    uint64_t *const d_ext = ext.get(), *const d_orig = orig.get();
+    int32_t *const d_edges = edg.get(), *const d_per = per.get();
+    int64_t *const d_off = off.get();
+    HIP_TRY(h, hipMemcpy(d_ext, ext_host.data(), ext_host.size() * 8, hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(d_orig, orig_host.data(), orig_host.size() * 8, hipMemcpyHostToDevice));
+    if (E > 0) HIP_TRY(h, hipMemcpy(d_edges, edges.data(), (size_t)E * 8, hipMemcpyHostToDevice));
     const unsigned grid = (unsigned)((E + 3) / 4);
     Sink sk{};
     if (E > 0) hipLaunchKernelGGL((cover3_ch_kernel<W, false>), dim3(grid), dim3(256), 0, h->stream, d_ext, d_orig, d_edges, E, d_per,
                                   (const int64_t *)nullptr, sk);
     hipLaunchKernelGGL(cover_scan_kernel, dim3(1), dim3(1024), 0, h->stream, d_per, E, d_off);
-    COVER_TRY(hipGetLastError());
+    HIP_TRY(h, hipGetLastError());
     int64_t totals[5] = {0, 0, 0, 0, 0};
-    COVER_TRY(hipMemcpyAsync(totals, d_off + 5 * E, 40, hipMemcpyDeviceToHost, h->stream));
-    COVER_TRY(sdpcut_sync(h));
+    HIP_TRY(h, hipMemcpyAsync(totals, d_off + 5 * E, 40, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, sdpcut_sync(h));
     *count_out = totals[0];
-    if (totals[0] > 0x7fffffffLL) { cleanup(); return sdpcut_fail(h, SDPCUT_EINVAL, "cover has more than 2^31 - 1 candidates"); }
-    if (max_subs > 0 && totals[0] >= max_subs) { cleanup(); return SDPCUT_OK; }     // count only (the reference's guard)
+    if (totals[0] > 0x7fffffffLL) return sdpcut_fail(h, SDPCUT_EINVAL, "cover has more than 2^31 - 1 candidates");
+    if (max_subs > 0 && totals[0] >= max_subs) return SDPCUT_OK;     // count only (the reference's guard)
     int64_t cnt[SDPCUT_MAX_K + 1] = {0, 0, totals[1], totals[2], 0, 0};
     int rc = alloc_candidates(h, totals[0], cnt, 0);
-    if (rc) { cleanup(); return rc; }
+    if (rc) return rc;
     if (totals[0] > 0) {
-        sk.set5 = h->d_set_orig;
-        sk.ks = h->d_k;
+        sk.set5 = h->d_set_orig.get();
+        sk.ks = h->d_k.get();
         for (int s = 2; s <= SDPCUT_MAX_K; ++s) {
-            sk.soa[s] = h->bucket[s].d_set;
-            sk.orig[s] = h->bucket[s].d_orig;
+            sk.soa[s] = h->bucket[s].d_set.get();
+            sk.orig[s] = h->bucket[s].d_orig.get();
             sk.cls_n[s] = cnt[s];
         }
         hipLaunchKernelGGL((cover3_ch_kernel<W, true>), dim3(grid), dim3(256), 0, h->stream, d_ext, d_orig, d_edges, E, d_per,
                            (const int64_t *)d_off, sk);
-        COVER_TRY(hipGetLastError());
-        COVER_TRY(sdpcut_sync(h));
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, sdpcut_sync(h));
     }
-    cleanup();
-#undef COVER_TRY
     return SDPCUT_OK;
 }
 

@@ -12,6 +12,7 @@
 // never exists on the host.
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/functional.hpp>
+#include <utility>
 
 #include "common.h"
 
@@ -105,50 +106,48 @@ extern "C" int sdpcut_set_candidates_cover_split(sdpcut_handle h_in, sdpcut_hand
     rc = sdpcut_set_candidates_cover(h_out, adjacency_all, dim, 0, &N_a);
     if (rc) return rc;
     HIP_TRY(h, sdpcut_sync(h_in));
-    int32_t *d_obj = nullptr, *d_all = h->d_set_orig, *d_kall = h->d_k;
-    uint8_t *d_flag = nullptr;
-    uint64_t *d_v = nullptr, *d_p = nullptr;
-    void *d_tmp = nullptr;
-    // the all-cover's arrays are the source of the split: take them out of the handle before its list is replaced
-    h->d_set_orig = nullptr;
-    h->d_k = nullptr;
-    auto cleanup = [&]() { hipFree(d_obj); hipFree(d_all); hipFree(d_kall); hipFree(d_flag); hipFree(d_v); hipFree(d_p); hipFree(d_tmp); };
-    // an error exit leaves BOTH handles without a list (N = 0, nothing scored): h_out's arrays have been taken out of it above
-    // and h_in still holds the whole objective cover -- a later round on either would run on half-built state
-    auto fail_cleanup = [&]() { cleanup(); free_candidates(h_in); free_candidates(h_out); };
-#define SPLIT_TRY(expr)                                                                         \
-    do {                                                                                        \
-        hipError_t e__ = (expr);                                                                \
-        if (e__ != hipSuccess) {                                                                \
-            fail_cleanup();                                                                     \
-            return sdpcut_fail(h, SDPCUT_EHIP, std::string(#expr) + ": " + hipGetErrorString(e__)); \
-        }                                                                                       \
-    } while (0)
+    // an error exit leaves BOTH handles without a list (N = 0, nothing scored): h_out's arrays are taken out of it below and h_in
+    // still holds the whole objective cover -- a later round on either would run on half-built state
+    struct DropLists {
+        sdpcut_ctx *a, *b;
+        bool armed;
+        ~DropLists() { if (armed) { free_candidates(a); free_candidates(b); } }
+    } on_failure = {h_in, h_out, true};
+    // the all-cover's arrays are the source of the split: moved out of the handle before its list is replaced.  They and the
+    // temporaries are freed on every way out (before on_failure acts)
+    DevBuf<int32_t> all = std::move(h->d_set_orig), kall = std::move(h->d_k), obj;
+    DevBuf<uint8_t> flag;
+    DevBuf<uint64_t> v, pre;
+    DevBuf<char> tmp;
     const size_t na = (size_t)(N_a < 1 ? 1 : N_a), no = (size_t)(N_o < 1 ? 1 : N_o);
-    SPLIT_TRY(hipMalloc((void **)&d_obj, no * 5 * sizeof(int32_t)));
-    if (N_o > 0) SPLIT_TRY(hipMemcpyAsync(d_obj, h_in->d_set_orig, (size_t)N_o * 5 * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
-    SPLIT_TRY(hipMalloc((void **)&d_flag, na));
-    SPLIT_TRY(hipMalloc((void **)&d_v, na * 5 * sizeof(uint64_t)));
-    SPLIT_TRY(hipMalloc((void **)&d_p, na * 5 * sizeof(uint64_t)));
+    HIP_TRY(h, obj.reset(no * 5));
+    HIP_TRY(h, flag.reset(na));
+    HIP_TRY(h, v.reset(na * 5));
+    HIP_TRY(h, pre.reset(na * 5));
+    int32_t *const d_obj = obj.get(), *const d_all = all.get(), *const d_kall = kall.get();
+    uint8_t *const d_flag = flag.get();
+    uint64_t *const d_v = v.get(), *const d_p = pre.get();
+    if (N_o > 0) HIP_TRY(h, hipMemcpyAsync(d_obj, h_in->d_set_orig.get(), (size_t)N_o * 5 * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
     int64_t cnt[2][SDPCUT_MAX_K + 1] = {{0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0}};
     int64_t tot[2] = {0, 0};
     if (N_a > 0) {
         const unsigned grid = (unsigned)((N_a + 255) / 256);
         hipLaunchKernelGGL(split_flag_kernel, dim3(grid), dim3(256), 0, h->stream, N_a, d_all, d_kall, N_o, d_obj, d_flag, d_v, N_a);
-        SPLIT_TRY(hipGetLastError());
+        HIP_TRY(h, hipGetLastError());
         size_t tb = 0;
-        SPLIT_TRY(rocprim::exclusive_scan(nullptr, tb, d_v, d_p, 0ull, (size_t)N_a, rocprim::plus<uint64_t>(), h->stream));
-        SPLIT_TRY(hipMalloc(&d_tmp, tb < 256 ? 256 : tb));
+        HIP_TRY(h, rocprim::exclusive_scan(nullptr, tb, d_v, d_p, 0ull, (size_t)N_a, rocprim::plus<uint64_t>(), h->stream));
+        HIP_TRY(h, tmp.reset(tb < 256 ? 256 : tb));
+        void *const d_tmp = tmp.get();
         for (int c = 0; c < 5; ++c)
-            SPLIT_TRY(rocprim::exclusive_scan(d_tmp, tb, d_v + (size_t)c * N_a, d_p + (size_t)c * N_a, 0ull, (size_t)N_a,
+            HIP_TRY(h, rocprim::exclusive_scan(d_tmp, tb, d_v + (size_t)c * N_a, d_p + (size_t)c * N_a, 0ull, (size_t)N_a,
                                               rocprim::plus<uint64_t>(), h->stream));
         // totals = prefix of the last element + its own contribution
         uint64_t lastp[5], lastv[5];
         for (int c = 0; c < 5; ++c) {
-            SPLIT_TRY(hipMemcpyAsync(&lastp[c], d_p + (size_t)c * N_a + (N_a - 1), 8, hipMemcpyDeviceToHost, h->stream));
-            SPLIT_TRY(hipMemcpyAsync(&lastv[c], d_v + (size_t)c * N_a + (N_a - 1), 8, hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(h, hipMemcpyAsync(&lastp[c], d_p + (size_t)c * N_a + (N_a - 1), 8, hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(h, hipMemcpyAsync(&lastv[c], d_v + (size_t)c * N_a + (N_a - 1), 8, hipMemcpyDeviceToHost, h->stream));
         }
-        SPLIT_TRY(sdpcut_sync(h));
+        HIP_TRY(h, sdpcut_sync(h));
         uint64_t t5[5];
         for (int c = 0; c < 5; ++c) t5[c] = lastp[c] + lastv[c];
         tot[0] = (int64_t)(t5[0] & 0xffffffffull); tot[1] = (int64_t)(t5[0] >> 32);
@@ -158,30 +157,29 @@ extern "C" int sdpcut_set_candidates_cover_split(sdpcut_handle h_in, sdpcut_hand
         }
     }
     // 2. the two lists
-    SPLIT_TRY(sdpcut_sync(h));      // (the objective cover has left h_in's arrays)
+    HIP_TRY(h, sdpcut_sync(h));      // (the objective cover has left h_in's arrays)
     rc = alloc_candidates(h_in, tot[0], cnt[0], 0);
-    if (rc) { fail_cleanup(); return sdpcut_fail(h, rc, std::string("cover_split: ") + sdpcut_last_error(h_in)); }
+    if (rc) return sdpcut_fail(h, rc, std::string("cover_split: ") + sdpcut_last_error(h_in));
     rc = alloc_candidates(h_out, tot[1], cnt[1], 0);
-    if (rc) { fail_cleanup(); return rc; }
+    if (rc) return rc;
     if (N_a > 0) {
         SplitSink sk{};
         sdpcut_ctx *hh[2] = {h_in, h_out};
         for (int part = 0; part < 2; ++part) {
-            sk.set5[part] = hh[part]->d_set_orig;
-            sk.ks[part] = hh[part]->d_k;
+            sk.set5[part] = hh[part]->d_set_orig.get();
+            sk.ks[part] = hh[part]->d_k.get();
             for (int s = 2; s <= SDPCUT_MAX_K; ++s) {
-                sk.soa[part][s] = hh[part]->bucket[s].d_set;
-                sk.orig[part][s] = hh[part]->bucket[s].d_orig;
+                sk.soa[part][s] = hh[part]->bucket[s].d_set.get();
+                sk.orig[part][s] = hh[part]->bucket[s].d_orig.get();
                 sk.cls_n[part][s] = cnt[part][s];
             }
         }
         hipLaunchKernelGGL(split_write_kernel, dim3((unsigned)((N_a + 255) / 256)), dim3(256), 0, h->stream, N_a, d_all, d_kall, d_flag, d_p,
                            N_a, sk);
-        SPLIT_TRY(hipGetLastError());
-        SPLIT_TRY(sdpcut_sync(h));
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, sdpcut_sync(h));
     }
-    cleanup();
-#undef SPLIT_TRY
+    on_failure.armed = false;
     *n_in = tot[0];
     *n_out = tot[1];
     return SDPCUT_OK;

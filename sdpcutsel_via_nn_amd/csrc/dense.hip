@@ -273,15 +273,9 @@ __global__ __launch_bounds__(DN_ROW_THREADS) void dn_rows_kernel(const double *_
     }
 }
 
-void free_dense_ws(sdpcut_ctx *h)
-{
-    (void)hipFree(h->d_dense);
-    h->d_dense = nullptr;
-}
-
 static int dense_check(sdpcut_ctx *h)
 {
-    if (!h->d_vars || !h->have_point) return sdpcut_fail(h, SDPCUT_ESTATE, "set_instance and set_point first");
+    if (!h->d_vars.get() || !h->have_point) return sdpcut_fail(h, SDPCUT_ESTATE, "set_instance and set_point first");
     if (h->nb_vars > SDPCUT_DENSE_MAX_VARS)
         return sdpcut_fail(h, SDPCUT_EINVAL, "dense eigen-cuts: nb_vars must not exceed 127 (SDPCUT_DENSE_MAX_VARS: the lifted matrix of order "
                                              "nb_vars + 1 stays in the LDS of one workgroup)");
@@ -292,15 +286,15 @@ static int dense_check(sdpcut_ctx *h)
 static int dense_eig_enqueue(sdpcut_ctx *h, DenseWs *ws)
 {
     HIP_TRY(h, hipSetDevice(h->device));
-    if (!h->d_dense) HIP_TRY(h, hipMalloc(&h->d_dense, DN_WS_BYTES));
-    *ws = dense_ws(h->d_dense);
+    if (!h->d_dense.get()) HIP_TRY(h, h->d_dense.reset(DN_WS_BYTES));
+    *ws = dense_ws(h->d_dense.get());
     const int D = h->nb_vars + 1;
     const size_t lds = (size_t)(D * (D | 1) + 3 * (DN_MAX_D / 2) + DN_MAX_D + DN_THREADS / 64) * sizeof(double)
                        + (size_t)(2 * (DN_MAX_D / 2) + DN_MAX_D) * sizeof(int);
     // (more than the default 64 KB of dynamic LDS from order 90 on)
     HIP_TRY(h, hipFuncSetAttribute((const void *)dn_eig_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
     if (h->timing) HIP_TRY(h, hipEventRecord(h->ev[0], h->stream));
-    hipLaunchKernelGGL(dn_eig_kernel, dim3(1), dim3(DN_THREADS), lds, h->stream, h->d_vars, (int)h->nb_vars, h->L, ws->vt, ws->vs, ws->eig,
+    hipLaunchKernelGGL(dn_eig_kernel, dim3(1), dim3(DN_THREADS), lds, h->stream, h->d_vars.get(), (int)h->nb_vars, h->L, ws->vt, ws->vs, ws->eig,
                        ws->meta);
     HIP_TRY(h, hipGetLastError());
     if (h->timing) HIP_TRY(h, hipEventRecord(h->ev[1], h->stream));
@@ -324,7 +318,7 @@ int sdpcut_dense_round(sdpcut_handle h, const double *vars_values, sdpcut_dense_
     if ((rc = ensure_pinned(h, y.bytes))) return rc;
     DenseWs ws;
     if ((rc = dense_eig_enqueue(h, &ws))) return rc;
-    char *dev = (char *)h->pinned_dev;
+    char *dev = (char *)h->pinned.dev();
     if (h->timing > 1) HIP_TRY(h, hipEventRecord(h->ev[2], h->stream));
     hipLaunchKernelGGL(dn_rows_kernel, dim3(n, (n + 1 + DN_ROW_TILE - 1) / DN_ROW_TILE), dim3(DN_ROW_THREADS), 0, h->stream, ws.vs, ws.eig,
                        ws.meta, n, h->L, (int32_t *)dev, (double *)(dev + y.eig), (double *)(dev + y.rhs), (int32_t *)(dev + y.cols),
@@ -332,7 +326,7 @@ int sdpcut_dense_round(sdpcut_handle h, const double *vars_values, sdpcut_dense_
     HIP_TRY(h, hipGetLastError());
     if (h->timing > 1) HIP_TRY(h, hipEventRecord(h->ev[3], h->stream));
     HIP_TRY(h, sdpcut_sync(h));      // the round's one host wait
-    const char *b = (const char *)h->pinned;
+    const char *b = (const char *)h->pinned.get();
     const int32_t *hdr = (const int32_t *)b;
     out->dim = n + 1;
     out->n_rows = hdr[0];

@@ -18,20 +18,18 @@
 
 // everything the filter keeps on the device, sized for `cap` pool entries (grown on demand, freed with the handle)
 struct DiverseWs {
-    int64_t cap = 0;           // pool entries the arrays hold
-    int64_t bit_blocks = 0;    // 64-row blocks the bit matrix holds
-    int64_t *ids = nullptr;    // [cap] candidate ids of the pool in rank order (global for a ranked pool, local for a caller's list)
-    double *score = nullptr;   // [cap]
-    double *lam = nullptr, *rhs = nullptr, *norm = nullptr;   // [cap]
-    double *coef = nullptr;    // [cap][SDPCUT_ROW_LD]
-    int32_t *ks = nullptr;     // [cap]
-    int32_t *sets = nullptr;   // [cap][5] padded with -1
-    uint8_t *elig = nullptr;   // [cap]
-    uint8_t *keep = nullptr;   // [cap]
-    int64_t *acc_ids = nullptr;    // [cap] accepted entries, compacted in rank order: the head the CSR assembly reads
-    double *acc_score = nullptr;   // [cap]
-    int64_t *info = nullptr;       // [8]: examined, skipped (not eligible), rejected (parallel), accepted, 0, 0, 0
-    unsigned long long *bits = nullptr;   // lower-triangular bit matrix, see div_bits_offset
+    DevBuf<int64_t> ids;       // [cap] candidate ids of the pool in rank order (global for a ranked pool, local for a caller's list)
+    DevBuf<double> score;      // [cap]
+    DevBuf<double> lam, rhs, norm;   // [cap]
+    DevBuf<double> coef;       // [cap][SDPCUT_ROW_LD]
+    DevBuf<int32_t> ks;        // [cap]
+    DevBuf<int32_t> sets;      // [cap][5] padded with -1
+    DevBuf<uint8_t> elig;      // [cap]
+    DevBuf<uint8_t> keep;      // [cap]
+    DevBuf<int64_t> acc_ids;   // [cap] accepted entries, compacted in rank order: the head the CSR assembly reads
+    DevBuf<double> acc_score;  // [cap]
+    DevBuf<int64_t> info;      // [8]: examined, skipped (not eligible), rejected (parallel), accepted, 0, 0, 0; kept when the others grow
+    DevBuf<unsigned long long> bits;   // lower-triangular bit matrix, see div_bits_offset; grows on its own
 };
 
 // Rows 64 b .. 64 b + 63 of the bit matrix hold b + 1 words each (columns 0 .. 64 b + 63); the blocks follow one another.
@@ -43,23 +41,9 @@ static __host__ __device__ __forceinline__ int64_t div_bits_offset(int64_t t)
 }
 static inline int64_t div_bits_words(int64_t blocks) { return 32 * blocks * (blocks + 1); }
 
-static void div_free(DiverseWs *w)
-{
-    (void)hipFree(w->ids); (void)hipFree(w->score); (void)hipFree(w->lam); (void)hipFree(w->rhs); (void)hipFree(w->norm);
-    (void)hipFree(w->coef); (void)hipFree(w->ks); (void)hipFree(w->sets); (void)hipFree(w->elig); (void)hipFree(w->keep);
-    (void)hipFree(w->acc_ids); (void)hipFree(w->acc_score); (void)hipFree(w->bits);
-    const auto info = w->info;
-    *w = DiverseWs();
-    w->info = info;
-}
-
 void free_diverse_ws(sdpcut_ctx *h)
 {
-    DiverseWs *w = (DiverseWs *)h->diverse;
-    if (!w) return;
-    div_free(w);
-    (void)hipFree(w->info);
-    delete w;
+    delete (DiverseWs *)h->diverse;
     h->diverse = nullptr;
 }
 
@@ -71,35 +55,16 @@ static int div_ensure(sdpcut_ctx *h, int64_t P, bool with_bits, DiverseWs **out)
         w = new (std::nothrow) DiverseWs();
         if (!w) return sdpcut_fail(h, SDPCUT_ENOMEM, "out of host memory");
         h->diverse = w;
-        HIP_TRY(h, hipMalloc((void **)&w->info, 8 * sizeof(int64_t)));
     }
-    if (P > w->cap) {
-        HIP_TRY(h, sdpcut_sync(h));
-        div_free(w);
-        const size_t c = (size_t)((P + 63) & ~(int64_t)63);
-        HIP_TRY(h, hipMalloc((void **)&w->ids, c * 8));
-        HIP_TRY(h, hipMalloc((void **)&w->score, c * 8));
-        HIP_TRY(h, hipMalloc((void **)&w->lam, c * 8));
-        HIP_TRY(h, hipMalloc((void **)&w->rhs, c * 8));
-        HIP_TRY(h, hipMalloc((void **)&w->norm, c * 8));
-        HIP_TRY(h, hipMalloc((void **)&w->coef, c * 8 * SDPCUT_ROW_LD));
-        HIP_TRY(h, hipMalloc((void **)&w->ks, c * 4));
-        HIP_TRY(h, hipMalloc((void **)&w->sets, c * 20));
-        HIP_TRY(h, hipMalloc((void **)&w->elig, c));
-        HIP_TRY(h, hipMalloc((void **)&w->keep, c));
-        HIP_TRY(h, hipMalloc((void **)&w->acc_ids, c * 8));
-        HIP_TRY(h, hipMalloc((void **)&w->acc_score, c * 8));
-        w->cap = (int64_t)c;
-    }
-    const int64_t blocks = (P + 63) / 64;
-    if (with_bits && blocks > w->bit_blocks) {
-        HIP_TRY(h, sdpcut_sync(h));
-        (void)hipFree(w->bits);
-        w->bits = nullptr;
-        w->bit_blocks = 0;
-        HIP_TRY(h, hipMalloc((void **)&w->bits, (size_t)div_bits_words(blocks) * 8));
-        w->bit_blocks = blocks;
-    }
+    int rc;
+    if ((rc = grow(h, w->info, 8))) return rc;
+    // the twelve arrays of the pool are all asked for c entries, a multiple of 64: they grow together
+    const size_t c = (size_t)((P + 63) & ~(int64_t)63);
+    if ((rc = grow(h, w->ids, c)) || (rc = grow(h, w->score, c)) || (rc = grow(h, w->lam, c)) || (rc = grow(h, w->rhs, c)) ||
+        (rc = grow(h, w->norm, c)) || (rc = grow(h, w->coef, c * SDPCUT_ROW_LD)) || (rc = grow(h, w->ks, c)) || (rc = grow(h, w->sets, c * 5)) ||
+        (rc = grow(h, w->elig, c)) || (rc = grow(h, w->keep, c)) || (rc = grow(h, w->acc_ids, c)) || (rc = grow(h, w->acc_score, c)))
+        return rc;
+    if (with_bits && (rc = grow(h, w->bits, (size_t)div_bits_words((P + 63) / 64)))) return rc;
     *out = w;
     return 0;
 }
@@ -315,20 +280,20 @@ __global__ __launch_bounds__(256) void div_greedy_kernel(int64_t P, int64_t quot
 // rows -> norms -> pair bits -> walk, for the P ids in w->ids (minus idx_base = local candidate index); all on the handle's stream
 static int div_filter_enqueue(sdpcut_ctx *h, DiverseWs *w, int64_t P, int64_t idx_base, int64_t quota, double max_parallel)
 {
-    int rc = launch_cut_rows(h, P, nullptr, w->ids, idx_base, w->lam, w->coef, SDPCUT_ROW_LD, w->rhs, nullptr, w->ks);
+    int rc = launch_cut_rows(h, P, nullptr, w->ids.get(), idx_base, w->lam.get(), w->coef.get(), SDPCUT_ROW_LD, w->rhs.get(), nullptr, w->ks.get());
     if (rc) return rc;
     const int grid = (int)((P + 63) / 64);
-    hipLaunchKernelGGL(div_prepare_kernel, dim3(grid), dim3(64), 0, h->stream, P, w->ids, idx_base, h->N, h->d_set_orig, w->lam, w->coef,
-                       w->ks, w->norm, w->elig, w->sets);
+    hipLaunchKernelGGL(div_prepare_kernel, dim3(grid), dim3(64), 0, h->stream, P, w->ids.get(), idx_base, h->N, h->d_set_orig.get(), w->lam.get(), w->coef.get(),
+                       w->ks.get(), w->norm.get(), w->elig.get(), w->sets.get());
     HIP_TRY(h, hipGetLastError());
     const bool compare = max_parallel < 1.0;
     if (compare) {
-        hipLaunchKernelGGL(div_pairs_kernel, dim3(grid, grid), dim3(64), 0, h->stream, P, max_parallel, w->coef, w->ks, w->sets, w->norm,
-                           w->elig, w->bits);
+        hipLaunchKernelGGL(div_pairs_kernel, dim3(grid, grid), dim3(64), 0, h->stream, P, max_parallel, w->coef.get(), w->ks.get(), w->sets.get(), w->norm.get(),
+                           w->elig.get(), w->bits.get());
         HIP_TRY(h, hipGetLastError());
     }
-    hipLaunchKernelGGL(div_greedy_kernel, dim3(1), dim3(256), 0, h->stream, P, quota, w->elig, compare ? w->bits : nullptr, w->ids,
-                       w->score, w->keep, w->acc_ids, w->acc_score, w->info);
+    hipLaunchKernelGGL(div_greedy_kernel, dim3(1), dim3(256), 0, h->stream, P, quota, w->elig.get(), compare ? w->bits.get() : nullptr, w->ids.get(),
+                       w->score.get(), w->keep.get(), w->acc_ids.get(), w->acc_score.get(), w->info.get());
     HIP_TRY(h, hipGetLastError());
     return 0;
 }
@@ -571,7 +536,7 @@ int sdpcut_filter_parallel(sdpcut_handle h, int64_t count, const int64_t *idx, i
     if (count < 0 || count > DIV_MAX_POOL) return sdpcut_fail(h, SDPCUT_EINVAL, "count must lie in 0 .. SDPCUT_DIVERSE_MAX_POOL");
     if (quota < 1) return sdpcut_fail(h, SDPCUT_EINVAL, "quota must be >= 1");
     if (count > 0 && (!idx || !keep_out)) return sdpcut_fail(h, SDPCUT_EINVAL, "bad filter_parallel arguments");
-    if (!h->have_point || !h->d_set_orig) return sdpcut_fail(h, SDPCUT_ESTATE, "set_candidates and set_point first");
+    if (!h->have_point || !h->d_set_orig.get()) return sdpcut_fail(h, SDPCUT_ESTATE, "set_candidates and set_point first");
     SDPCUT_NO_PENDING(h);
     for (int64_t i = 0; i < count; ++i)
         if (idx[i] < 0 || idx[i] >= h->N) return sdpcut_fail(h, SDPCUT_EINVAL, "candidate index out of range");
@@ -581,13 +546,13 @@ int sdpcut_filter_parallel(sdpcut_handle h, int64_t count, const int64_t *idx, i
     DiverseWs *w = nullptr;
     rc = div_ensure(h, count, max_parallel < 1.0, &w);
     if (rc) return rc;
-    HIP_TRY(h, hipMemcpyAsync(w->ids, idx, (size_t)count * 8, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemsetAsync(w->score, 0, (size_t)count * 8, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(w->ids.get(), idx, (size_t)count * 8, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemsetAsync(w->score.get(), 0, (size_t)count * 8, h->stream));
     rc = div_filter_enqueue(h, w, count, 0, quota, max_parallel);
     if (rc) return rc;
     int64_t c8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    HIP_TRY(h, hipMemcpyAsync(keep_out, w->keep, (size_t)count, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(c8, w->info, sizeof(c8), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(keep_out, w->keep.get(), (size_t)count, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(c8, w->info.get(), sizeof(c8), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, sdpcut_sync(h));
     if (info) { info->examined = c8[0]; info->skipped_nonviolated = c8[1]; info->rejected_parallel = c8[2]; }
     return SDPCUT_OK;
@@ -608,7 +573,7 @@ int sdpcut_round_csr_diverse(sdpcut_handle h, const double *vars_values, int str
     if (sel_size < 1) return sdpcut_fail(h, SDPCUT_EINVAL, "sel_size must be >= 1");
     if (pool_size < sel_size) return sdpcut_fail(h, SDPCUT_EINVAL, "pool_size must be >= sel_size");
     if (pool_size > DIV_MAX_POOL) return sdpcut_fail(h, SDPCUT_EINVAL, "pool_size must not exceed SDPCUT_DIVERSE_MAX_POOL");
-    if (h->nb_vars == 0 || !h->d_eig || !(h->have_point || vars_values))
+    if (h->nb_vars == 0 || !h->d_eig.get() || !(h->have_point || vars_values))
         return sdpcut_fail(h, SDPCUT_ESTATE, "set_instance, set_candidates and a point first");
     SDPCUT_NO_PENDING(h);
     if (vars_values && (rc = sdpcut_set_point(h, vars_values))) return rc;
@@ -624,7 +589,7 @@ int sdpcut_round_csr_diverse(sdpcut_handle h, const double *vars_values, int str
     rc = div_ensure(h, want, max_parallel < 1.0, &w);
     if (rc) return rc;
     int64_t P = 0;
-    rc = sdpcut_rank_device(h, strat, sel_size, want, w->ids, w->score, &P, &out->n_total, &out->new_strat, out->counters);
+    rc = sdpcut_rank_device(h, strat, sel_size, want, w->ids.get(), w->score.get(), &P, &out->n_total, &out->new_strat, out->counters);
     if (rc) return rc;
     if (info) info->pool = P;
     if (P <= 0) return SDPCUT_OK;      // an empty ranking (no violated candidate): an empty block
@@ -637,16 +602,16 @@ int sdpcut_round_csr_diverse(sdpcut_handle h, const double *vars_values, int str
     const int32_t ld = h->row_len_max;
     rc = ensure_pinned(h, csr_layout(cap, ld).bytes);
     if (rc) return rc;
-    const int64_t *hdr = (const int64_t *)h->pinned;
+    const int64_t *hdr = (const int64_t *)h->pinned.get();
     rc = csr_assemble_wait(h, 10, 2, true, "round_csr_diverse", [&](int64_t serial) {
-        return launch_round_csr(h, cap, w->info, cap, w->acc_ids, w->acc_score, ld, h->pinned_dev, serial);
+        return launch_round_csr(h, cap, w->info.get(), cap, w->acc_ids.get(), w->acc_score.get(), ld, h->pinned.dev(), serial);
     });
     if (rc) return rc;
     ++h->stat_rounds;
     if (info) { info->examined = hdr[0]; info->skipped_nonviolated = hdr[1]; info->rejected_parallel = hdr[2]; }
     out->cap = cap;
     out->n_out = hdr[3];
-    csr_out_from_block(h->pinned, out);
+    csr_out_from_block(h->pinned.get(), out);
     return SDPCUT_OK;
 }
 

@@ -92,17 +92,15 @@ __global__ __launch_bounds__(64) void efficacy_points_kernel(int64_t n, const in
 
 void free_eff_ws(sdpcut_ctx *h)
 {
-    (void)hipFree(h->d_eff);      // one allocation: eff | objpar | escore
-    h->d_eff = h->d_objpar = h->d_escore = nullptr;
+    h->d_eff.release();      // one allocation: eff | objpar | escore
+    h->d_objpar = h->d_escore = nullptr;
     h->scored &= ~(uint32_t)SDPCUT_EFF;
 }
 
 void free_lpobj(sdpcut_ctx *h)
 {
-    (void)hipFree(h->d_lpobj);
-    (void)hipFree(h->d_lpobj_dense);
-    h->d_lpobj = nullptr;
-    h->d_lpobj_dense = nullptr;
+    h->d_lpobj.release();
+    h->d_lpobj_dense.release();
     h->lpobj_dense_ok = false;
     h->lpobj_norm = 0.0;
     h->scored &= ~(uint32_t)SDPCUT_EFF;
@@ -111,17 +109,17 @@ void free_lpobj(sdpcut_ctx *h)
 // d_eff / d_objpar / d_escore of every candidate at the current point; SDPCUT_EIG has been scored (sdpcut_score sees to it)
 int launch_efficacy(sdpcut_ctx *h)
 {
-    if (!h->d_eff) {      // allocated by the first scoring of a list, as d_sdp is
+    if (!h->d_eff.get()) {      // allocated by the first scoring of a list, as d_sdp is
         const size_t nn = (size_t)(h->N < 1 ? 1 : h->N);
-        HIP_TRY(h, hipMalloc((void **)&h->d_eff, 3 * nn * sizeof(double)));
-        h->d_objpar = h->d_eff + nn;
+        HIP_TRY(h, h->d_eff.reset(3 * nn));
+        h->d_objpar = h->d_eff.get() + nn;
         h->d_escore = h->d_objpar + nn;
     }
     if (h->N == 0) return 0;
     const unsigned grid = (unsigned)((h->N + 63) / 64);
     // the ORIGINAL point: like lambda_min and the rows this measure knows no node box
-    hipLaunchKernelGGL(efficacy_kernel, dim3(grid), dim3(64), 0, h->stream, h->N, h->d_set_orig, h->d_k, score_vars(h, SDPCUT_EFF), h->nb_vars,
-                       h->L, h->d_eig, (const double *)h->d_lpobj, h->lpobj_norm, h->eff_w, h->d_eff, h->d_objpar, h->d_escore);
+    hipLaunchKernelGGL(efficacy_kernel, dim3(grid), dim3(64), 0, h->stream, h->N, h->d_set_orig.get(), h->d_k.get(), score_vars(h, SDPCUT_EFF), h->nb_vars,
+                       h->L, h->d_eig.get(), (const double *)h->d_lpobj.get(), h->lpobj_norm, h->eff_w, h->d_eff.get(), h->d_objpar, h->d_escore);
     HIP_TRY(h, hipGetLastError());
     return 0;
 }
@@ -133,8 +131,8 @@ int launch_efficacy_points(sdpcut_ctx *h, int n_points, const double *d_pts, int
 {
     if (h->N == 0 || n_points <= 0) return 0;
     const unsigned grid = (unsigned)((h->N + 63) / 64);
-    hipLaunchKernelGGL(efficacy_points_kernel, dim3(grid, (unsigned)n_points), dim3(64), 0, h->stream, h->N, h->d_set_orig, h->d_k, d_pts, pts_stride,
-                       h->nb_vars, h->L, d_eig, score_stride, (const double *)h->d_lpobj, h->lpobj_norm, h->eff_w, d_eff, d_objpar, d_escore);
+    hipLaunchKernelGGL(efficacy_points_kernel, dim3(grid, (unsigned)n_points), dim3(64), 0, h->stream, h->N, h->d_set_orig.get(), h->d_k.get(), d_pts, pts_stride,
+                       h->nb_vars, h->L, d_eig, score_stride, (const double *)h->d_lpobj.get(), h->lpobj_norm, h->eff_w, d_eff, d_objpar, d_escore);
     HIP_TRY(h, hipGetLastError());
     return 0;
 }
@@ -166,9 +164,9 @@ int sdpcut_set_objective(sdpcut_handle h, int64_t n_cols, const double *obj)
     const double nrm = std::sqrt(s);
     if (!(nrm > 0.0) || !std::isfinite(nrm)) return sdpcut_fail(h, SDPCUT_EINVAL, "set_objective: the vector is all zero (or its norm overflows)");
     HIP_TRY(h, sdpcut_sync(h));
-    if (!h->d_lpobj) HIP_TRY(h, hipMalloc((void **)&h->d_lpobj, (size_t)len * sizeof(double)));
+    if (!h->d_lpobj.get()) HIP_TRY(h, h->d_lpobj.reset((size_t)len));
     h->lpobj_dense_ok = false;      // (sdpcut_node_eval_points builds its dense table of the new vector when it is first called)
-    HIP_TRY(h, hipMemcpy(h->d_lpobj, obj, (size_t)len * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->d_lpobj.get(), obj, (size_t)len * sizeof(double), hipMemcpyHostToDevice));
     h->lpobj_norm = nrm;
     h->scored &= ~(uint32_t)SDPCUT_EFF;
     return SDPCUT_OK;
@@ -191,7 +189,7 @@ int sdpcut_get_efficacy(sdpcut_handle h, double *eff, double *objpar, double *es
     if (!h->have_point || !(h->scored & SDPCUT_EFF)) return sdpcut_fail(h, SDPCUT_ESTATE, "efficacy not scored at the current point");
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t bytes = (size_t)h->N * sizeof(double);
-    if (eff) HIP_TRY(h, hipMemcpyAsync(eff, h->d_eff, bytes, hipMemcpyDeviceToHost, h->stream));
+    if (eff) HIP_TRY(h, hipMemcpyAsync(eff, h->d_eff.get(), bytes, hipMemcpyDeviceToHost, h->stream));
     if (objpar) HIP_TRY(h, hipMemcpyAsync(objpar, h->d_objpar, bytes, hipMemcpyDeviceToHost, h->stream));
     if (escore) HIP_TRY(h, hipMemcpyAsync(escore, h->d_escore, bytes, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, sdpcut_sync(h));

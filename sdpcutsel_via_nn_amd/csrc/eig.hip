@@ -301,13 +301,13 @@ static int fill_eig_args(const sdpcut_ctx *h, EigArgs &A)
     int64_t acc = 0;
     for (int k = SDPCUT_MAX_K; k >= 2; --k) {
         const Bucket &b = h->bucket[k];
-        A.set[k] = b.d_set; A.orig[k] = b.d_orig; A.n[k] = b.n;
+        A.set[k] = b.d_set.get(); A.orig[k] = b.d_orig.get(); A.n[k] = b.n;
         acc += (b.n + 255) / 256;
         A.tile_end[k] = acc;
         if (b.n > 0 && k > kmax) kmax = k;
     }
     A.set[0] = A.set[1] = nullptr; A.orig[0] = A.orig[1] = nullptr; A.n[0] = A.n[1] = 0; A.tile_end[0] = A.tile_end[1] = acc;
-    A.vars = h->d_vars; A.nv = h->nb_vars; A.L = h->L; A.eig_out = h->d_eig; A.tk = nullptr;
+    A.vars = h->d_vars.get(); A.nv = h->nb_vars; A.L = h->L; A.eig_out = h->d_eig.get(); A.tk = nullptr;
     A.pf_mloc = 0;      // (set with the grid: eig_launch)
     A.spread = 0;
     return kmax;

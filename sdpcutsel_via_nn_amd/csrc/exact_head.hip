@@ -259,25 +259,11 @@ int64_t exact_widest_band(const sdpcut_ctx *h) { return h->N < EB_LDSK ? h->N : 
 
 static int ensure_exact_ws(sdpcut_ctx *h, bool full)
 {
-    if (!h->d_exact) {
-        HIP_TRY(h, hipMalloc(&h->d_exact, exact_bytes()));
-        HIP_TRY(h, hipMemsetAsync(h->d_exact, 0, exact_bytes(), h->stream));
+    if (!h->d_exact.get()) {
+        HIP_TRY(h, h->d_exact.reset(exact_bytes()));
+        HIP_TRY(h, hipMemsetAsync(h->d_exact.get(), 0, exact_bytes(), h->stream));
     }
-    if (full && h->obj_exact_n < h->N) {
-        HIP_TRY(h, sdpcut_sync(h));
-        (void)hipFree(h->d_obj_exact);
-        h->d_obj_exact = nullptr;
-        h->obj_exact_n = 0;
-        HIP_TRY(h, hipMalloc((void **)&h->d_obj_exact, (size_t)h->N * 8));
-        h->obj_exact_n = h->N;
-    }
-    return 0;
-}
-
-void free_exact_ws(sdpcut_ctx *h)
-{
-    (void)hipFree(h->d_exact); (void)hipFree(h->d_obj_exact);
-    h->d_exact = nullptr; h->d_obj_exact = nullptr; h->obj_exact_n = 0;
+    return full ? grow(h, h->d_obj_exact, (size_t)h->N) : 0;
 }
 
 // Enqueue the exact head of `cap` entries (strategy 2 or 4; the measures are scored already) through a band of `band` entries into
@@ -293,14 +279,14 @@ int exact_head_enqueue(sdpcut_ctx *h, int strat, int64_t sel_size, int64_t cap, 
         if (h->bucket[k].n && !h->net[k].set) return sdpcut_fail(h, SDPCUT_ESTATE, "exact head: no network for a size class of the list");
     int rc = ensure_exact_ws(h, comb);
     if (rc) return rc;
-    const ExactBufs B = exact_bufs(h->d_exact);
+    const ExactBufs B = exact_bufs(h->d_exact.get());
     void *wsv = nullptr;
     rc = topk_begin(h, &wsv, nullptr);
     if (rc) return rc;
     TopkWs *ws = (TopkWs *)wsv;
     int64_t *strong = comb ? topk_strong_counter(wsv) : nullptr;
     const double me = eb_max_elem_bound(h->q_absmax);
-    const double *eig = comb ? h->d_eig : nullptr;
+    const double *eig = comb ? h->d_eig.get() : nullptr;
     ExactNets nets;
     for (int k = 0; k <= SDPCUT_MAX_K; ++k) nets.net[k] = h->net[k].dev;
     const int mode = comb ? TK_MODE_COMBAUTO : TK_MODE_OPT;
@@ -318,7 +304,7 @@ int exact_head_enqueue(sdpcut_ctx *h, int strat, int64_t sel_size, int64_t cap, 
         const int g_scan = (int)(nb < 4 * h->n_cu ? nb : 4 * h->n_cu);
         hipLaunchKernelGGL(exact_zb_scan_kernel, dim3(g_scan), dim3(256), 0, h->stream, n, h->base, h->d_obj, eig, me, B.xw, B.zb_ids, strong);
         hipLaunchKernelGGL(exact_rescore_kernel, dim3(EB_ZB_MAX), dim3(64), 0, h->stream, nets, B.zb_ids, h->base, &B.xw->zb_n,
-                           (int64_t)EB_ZB_MAX, (const int64_t *)nullptr, n, h->d_set_orig, h->d_k, h->d_vars, h->d_Q, h->nb_vars, h->L,
+                           (int64_t)EB_ZB_MAX, (const int64_t *)nullptr, n, h->d_set_orig.get(), h->d_k.get(), h->d_vars.get(), h->d_Q.get(), h->nb_vars, h->L,
                            B.zb_exact, (double *)nullptr);
         hipLaunchKernelGGL(exact_zb_patch_kernel, dim3(1), dim3(256), 0, h->stream, h->base, h->d_obj, eig, B.xw, B.zb_ids, B.zb_exact,
                            B.zb_old, strong);
@@ -334,17 +320,17 @@ int exact_head_enqueue(sdpcut_ctx *h, int strat, int64_t sel_size, int64_t cap, 
     if (rc) return undo(rc);
     // ---- re-score, re-rank
     hipLaunchKernelGGL(exact_rescore_kernel, dim3((unsigned)(band < 4096 ? band : 4096)), dim3(64), 0, h->stream, nets, B.band_idx, h->base, &ws->counters[3], band,
-                       &ws->counters[4], n, h->d_set_orig, h->d_k, h->d_vars, h->d_Q, h->nb_vars, h->L, B.band_obj,
-                       comb ? h->d_obj_exact : (double *)nullptr);
+                       &ws->counters[4], n, h->d_set_orig.get(), h->d_k.get(), h->d_vars.get(), h->d_Q.get(), h->nb_vars, h->L, B.band_obj,
+                       comb ? h->d_obj_exact.get() : (double *)nullptr);
     hipLaunchKernelGGL(exact_keys_kernel, dim3((unsigned)((band + 255) / 256)), dim3(256), 0, h->stream, ws, B.band_idx, h->base, n, eig,
-                       B.band_obj, h->d_sel_key, h->d_sel_idx);
+                       B.band_obj, h->d_sel_key.get(), h->d_sel_idx.get());
     if (hipGetLastError() != hipSuccess) return undo(sdpcut_fail(h, SDPCUT_EHIP, "exact head: launch of the re-score failed"));
     hipLaunchKernelGGL(exact_finish_kernel, dim3(1), dim3(256), 0, h->stream, ws, comb ? B.xw : (ExactWs *)nullptr, cap, band, n, h->base,
                        B.band_idx, h->d_obj, eig, me, B.zb_ids, B.zb_old);
     HIP_TRY(h, hipGetLastError());
     // (a void head has n_sel = 0: the tail emits nothing)
     const TkJob j = {ws, mode, band, cap, sel, eig, h->d_obj, h->base, comb ? SDPCUT_BIG_M : 0.0, d_idx_out, d_score_out, 0, TK_MAXK,
-                     h->d_obj_exact};
+                     h->d_obj_exact.get()};
     tk_sort_launch(h, p, j);
     HIP_TRY(h, hipGetLastError());
     return 0;

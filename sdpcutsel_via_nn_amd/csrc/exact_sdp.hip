@@ -65,15 +65,14 @@ __global__ __launch_bounds__(64) void exact_sdp_batch_kernel(int64_t count, cons
 
 void free_sdp_ws(sdpcut_ctx *h)
 {
-    (void)hipFree(h->d_sdp);
-    (void)hipFree(h->d_sdp_gap);
-    h->d_sdp = h->d_sdp_gap = nullptr;
+    h->d_sdp.release();
+    h->d_sdp_gap.release();
     h->scored &= ~(uint32_t)SDPCUT_SDP;
 }
 
 static int ensure_sdp_counter(sdpcut_ctx *h)
 {
-    if (!h->d_sdp_unconverged) HIP_TRY(h, hipMalloc((void **)&h->d_sdp_unconverged, sizeof(unsigned long long)));
+    if (!h->d_sdp_unconverged.get()) HIP_TRY(h, h->d_sdp_unconverged.reset(1));
     return 0;
 }
 
@@ -82,17 +81,17 @@ int launch_exact_sdp(sdpcut_ctx *h)
 {
     int rc = ensure_sdp_counter(h);
     if (rc) return rc;
-    if (!h->d_sdp) {      // allocated by the first scoring of a list: lists that never ask for the exact measure pay nothing
+    if (!h->d_sdp.get()) {      // allocated by the first scoring of a list: lists that never ask for the exact measure pay nothing
         const size_t nn = (size_t)(h->N < 1 ? 1 : h->N);
-        HIP_TRY(h, hipMalloc((void **)&h->d_sdp, nn * sizeof(double)));
-        HIP_TRY(h, hipMalloc((void **)&h->d_sdp_gap, nn * sizeof(double)));
+        HIP_TRY(h, h->d_sdp.reset(nn));
+        HIP_TRY(h, h->d_sdp_gap.reset(nn));
     }
-    HIP_TRY(h, hipMemsetAsync(h->d_sdp_unconverged, 0, sizeof(unsigned long long), h->stream));
+    HIP_TRY(h, hipMemsetAsync(h->d_sdp_unconverged.get(), 0, sizeof(unsigned long long), h->stream));
     const double *vars = score_vars(h, SDPCUT_SDP), *Q = score_Q(h, SDPCUT_SDP);      // (the box tables at a node, common.h)
 #define ESDP_LAUNCH(KK)                                                                                                            \
     if (h->bucket[KK].n > 0)                                                                                                         \
-        hipLaunchKernelGGL((exact_sdp_kernel<KK>), dim3((unsigned)((h->bucket[KK].n + 63) / 64)), dim3(64), 0, h->stream, h->bucket[KK].d_set, \
-                           h->bucket[KK].d_orig, h->bucket[KK].n, vars, Q, h->nb_vars, h->L, h->d_sdp, h->d_sdp_gap, h->d_sdp_unconverged)
+        hipLaunchKernelGGL((exact_sdp_kernel<KK>), dim3((unsigned)((h->bucket[KK].n + 63) / 64)), dim3(64), 0, h->stream, h->bucket[KK].d_set.get(), \
+                           h->bucket[KK].d_orig.get(), h->bucket[KK].n, vars, Q, h->nb_vars, h->L, h->d_sdp.get(), h->d_sdp_gap.get(), h->d_sdp_unconverged.get())
     ESDP_LAUNCH(5);
     ESDP_LAUNCH(4);
     ESDP_LAUNCH(3);
@@ -105,9 +104,9 @@ int launch_exact_sdp(sdpcut_ctx *h)
 int sdp_unconverged(sdpcut_ctx *h, int64_t *value)
 {
     unsigned long long v = 0;
-    if (h->d_sdp_unconverged) {
+    if (h->d_sdp_unconverged.get()) {
         HIP_TRY(h, hipSetDevice(h->device));
-        HIP_TRY(h, hipMemcpyAsync(&v, h->d_sdp_unconverged, sizeof(v), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(&v, h->d_sdp_unconverged.get(), sizeof(v), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(h, sdpcut_sync(h));
     }
     *value = (int64_t)v;
@@ -122,8 +121,8 @@ int sdpcut_get_sdp_scores(sdpcut_handle h, double *obj_exact, double *gap)
     SDPCUT_NO_PENDING(h);
     if (!(h->scored & SDPCUT_SDP)) return sdpcut_fail(h, SDPCUT_ESTATE, "exact optimality measure not scored");
     HIP_TRY(h, hipSetDevice(h->device));
-    if (obj_exact) HIP_TRY(h, hipMemcpyAsync(obj_exact, h->d_sdp, h->N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (gap) HIP_TRY(h, hipMemcpyAsync(gap, h->d_sdp_gap, h->N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (obj_exact) HIP_TRY(h, hipMemcpyAsync(obj_exact, h->d_sdp.get(), h->N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (gap) HIP_TRY(h, hipMemcpyAsync(gap, h->d_sdp_gap.get(), h->N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, sdpcut_sync(h));
     return SDPCUT_OK;
 }
@@ -143,10 +142,10 @@ int sdpcut_sdp_batch(sdpcut_handle h, int k, int64_t count, const double *inputs
     const size_t c = (size_t)count, m = (size_t)k * (k + 1) / 2, d = (size_t)k + m;
     rc = ensure_stage(h, c * 8 * (d + 2 + k + m) + c * 4);
     if (rc) return rc;
-    double *d_in = (double *)h->d_stage, *d_val = d_in + c * d, *d_gap = d_val + c, *d_lam = d_gap + c, *d_Y = d_lam + c * k;
+    double *d_in = (double *)h->d_stage.get(), *d_val = d_in + c * d, *d_gap = d_val + c, *d_lam = d_gap + c, *d_Y = d_lam + c * k;
     int32_t *d_it = (int32_t *)(d_Y + c * m);
     HIP_TRY(h, hipMemcpyAsync(d_in, inputs, c * d * 8, hipMemcpyHostToDevice, h->stream));
-    unsigned long long *d_cnt = h->d_sdp_unconverged;      // SDPCUT_STAT_SDP_UNCONVERGED: of the last solve, scoring or batch
+    unsigned long long *d_cnt = h->d_sdp_unconverged.get();      // SDPCUT_STAT_SDP_UNCONVERGED: of the last solve, scoring or batch
     HIP_TRY(h, hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long), h->stream));
     const unsigned grid = (unsigned)((count + 63) / 64);
 #define ESDP_BATCH(KK)                                                                                                                   \

@@ -13,18 +13,19 @@ int alloc_candidates(sdpcut_ctx *h, int64_t N, const int64_t cnt[SDPCUT_MAX_K + 
     free_candidates(h);
     h->base = global_base;
     const size_t nn = (size_t)(N < 1 ? 1 : N);
-    HIP_TRY(h, hipMalloc((void **)&h->d_set_orig, nn * 5 * sizeof(int32_t)));
-    HIP_TRY(h, hipMalloc((void **)&h->d_k, nn * sizeof(int32_t)));
-    HIP_TRY(h, hipMalloc((void **)&h->d_eig, nn * sizeof(double)));
-    HIP_TRY(h, hipMalloc((void **)&h->d_obj, nn * sizeof(double)));
+    HIP_TRY(h, h->d_set_orig.reset(nn * 5));
+    HIP_TRY(h, h->d_k.reset(nn));
+    HIP_TRY(h, h->d_eig.reset(nn));
+    HIP_TRY(h, h->obj_own.reset(nn));
+    h->d_obj = h->obj_own.get();
     h->row_len_max = 5;
     for (int k = 2; k <= SDPCUT_MAX_K; ++k) {
         Bucket &b = h->bucket[k];
         b.n = cnt[k];
         if (!cnt[k]) continue;
         h->row_len_max = k * (k + 3) / 2;
-        HIP_TRY(h, hipMalloc((void **)&b.d_set, (size_t)cnt[k] * k * sizeof(int32_t)));
-        HIP_TRY(h, hipMalloc((void **)&b.d_orig, (size_t)cnt[k] * sizeof(int32_t)));
+        HIP_TRY(h, b.d_set.reset((size_t)cnt[k] * k));
+        HIP_TRY(h, b.d_orig.reset((size_t)cnt[k]));
     }
     h->N = N;
     return 0;      // (the ranking workspaces are allocated by whoever first needs them: ensure_key_ws / ensure_rank_ws)
@@ -32,15 +33,11 @@ int alloc_candidates(sdpcut_ctx *h, int64_t N, const int64_t cnt[SDPCUT_MAX_K + 
 
 void free_candidates(sdpcut_ctx *h)
 {
-    for (int k = 0; k <= SDPCUT_MAX_K; ++k) {
-        hipFree(h->bucket[k].d_set);
-        hipFree(h->bucket[k].d_orig);
-        h->bucket[k] = Bucket();
-    }
-    hipFree(h->d_set_orig); hipFree(h->d_k); hipFree(h->d_eig); hipFree(h->d_obj);
+    for (int k = 0; k <= SDPCUT_MAX_K; ++k) h->bucket[k] = Bucket();
+    h->d_set_orig.release(); h->d_k.release(); h->d_eig.release(); h->obj_own.release();
+    h->d_obj = nullptr;
     free_sdp_ws(h);
     free_eff_ws(h);
-    h->d_set_orig = nullptr; h->d_k = nullptr; h->d_eig = nullptr; h->d_obj = nullptr;
     h->N = 0; h->scored = 0; h->obj_partial = false; h->last_total = -1;
     h->stat_nn_skipped = 0; h->nn_skipped_on_device = false;
     h->nn_eval_mode = 0; h->nn_eval_n = 0;
@@ -61,17 +58,17 @@ int sdpcut_set_network(sdpcut_handle h, int k, int n_layers, const int32_t *widt
     HIP_TRY(h, hipSetDevice(h->device));
     NetHost &nh_ = h->net[k];
     HIP_TRY(h, sdpcut_sync(h));
-    hipFree(nh_.d_blob);
-    nh_.d_blob = nullptr;
+    nh_.d_blob.release();
     nh_.set = false;
     h->scored &= ~(uint32_t)SDPCUT_NN; h->obj_partial = false;      // the list's optimality scores were the old network's: a round scores again
     // one allocation: the blob | filter_box [d_in][2] | the fp32 forms of the filter (floats; empty unless filter_ok) | filter_g [64]
     const size_t n_box = 2 * (size_t)pk.d_in;
     const size_t n_pre = (pk.blob.size() + n_box + 1) & ~(size_t)1;      // (an even number of doubles: the float4 loads stay aligned)
-    HIP_TRY(h, hipMalloc((void **)&nh_.d_blob, n_pre * sizeof(double) + (pk.f32.size() + MAX_HIDDEN) * sizeof(float)));
-    HIP_TRY(h, hipMemcpy(nh_.d_blob, pk.blob.data(), pk.blob.size() * sizeof(double), hipMemcpyHostToDevice));
-    double *d_box = nh_.d_blob + pk.blob.size();
-    float *d_f32 = (float *)(nh_.d_blob + n_pre);
+    HIP_TRY(h, nh_.d_blob.reset(n_pre * sizeof(double) + (pk.f32.size() + MAX_HIDDEN) * sizeof(float)));
+    double *const blob = (double *)nh_.d_blob.get();
+    HIP_TRY(h, hipMemcpy(blob, pk.blob.data(), pk.blob.size() * sizeof(double), hipMemcpyHostToDevice));
+    double *d_box = blob + pk.blob.size();
+    float *d_f32 = (float *)(blob + n_pre);
     HIP_TRY(h, hipMemcpy(d_box, &pk.filter_box[0][0], n_box * sizeof(double), hipMemcpyHostToDevice));
     if (!pk.f32.empty()) HIP_TRY(h, hipMemcpy(d_f32, pk.f32.data(), pk.f32.size() * sizeof(float), hipMemcpyHostToDevice));
     float *d_g = d_f32 + pk.f32.size();      // (a multiple of four floats behind d_f32: the float4 loads stay aligned)
@@ -79,14 +76,14 @@ int sdpcut_set_network(sdpcut_handle h, int k, int n_layers, const int32_t *widt
     NetDev &d = nh_.dev;
     d = NetDev{};
     d.d_in = pk.d_in; d.n_hidden = pk.n_hidden; d.width = pk.width; d.s0 = pk.s0; d.sh = pk.sh;
-    d.inmap = nh_.d_blob + pk.o_inmap;
-    d.bias = nh_.d_blob + pk.o_bias;
-    d.bias_q = nh_.d_blob + pk.o_bias_q;
-    d.wout = nh_.d_blob + pk.o_wout;
-    d.wfrag = nh_.d_blob + pk.o_frag;
-    d.wvalu = nh_.d_blob + pk.o_wvalu;
-    d.wtail = nh_.d_blob + pk.o_wtail;
-    for (int l = 0; l < n_layers; ++l) { d.raw_w[l] = nh_.d_blob + pk.o_rw[l]; d.raw_b[l] = nh_.d_blob + pk.o_rb[l]; }
+    d.inmap = blob + pk.o_inmap;
+    d.bias = blob + pk.o_bias;
+    d.bias_q = blob + pk.o_bias_q;
+    d.wout = blob + pk.o_wout;
+    d.wfrag = blob + pk.o_frag;
+    d.wvalu = blob + pk.o_wvalu;
+    d.wtail = blob + pk.o_wtail;
+    for (int l = 0; l < n_layers; ++l) { d.raw_w[l] = blob + pk.o_rw[l]; d.raw_b[l] = blob + pk.o_rb[l]; }
     d.ymin = pk.ymin; d.b_out = pk.b_out; d.y_ymin = pk.y_ymin; d.y_gain = pk.y_gain; d.y_xoffset = pk.y_xoffset;
     d.unclamped_ok = pk.unclamped_ok;
     d.filter_ok = pk.filter_ok; d.filter_margin = pk.filter_margin; d.filter_box = d_box;
@@ -104,13 +101,13 @@ int sdpcut_set_instance(sdpcut_handle h, int32_t nb_vars, const double *Q_arr)
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, sdpcut_sync(h));
     const int64_t L = (int64_t)nb_vars * (nb_vars + 1) / 2;
-    hipFree(h->d_Q); hipFree(h->d_vars);
+    h->d_Q.release(); h->d_vars.release();
     box_clear(h);      // (a box belongs to the instance it was set for)
     free_lpobj(h);     // (so does an LP objective vector: its length is the instance's)
-    h->d_Q = nullptr; h->d_vars = nullptr; h->have_point = false; h->scored = 0; h->obj_partial = false;
-    HIP_TRY(h, hipMalloc((void **)&h->d_Q, L * sizeof(double)));
-    HIP_TRY(h, hipMalloc((void **)&h->d_vars, (L + nb_vars) * sizeof(double)));
-    HIP_TRY(h, hipMemcpy(h->d_Q, Q_arr, L * sizeof(double), hipMemcpyHostToDevice));
+    h->have_point = false; h->scored = 0; h->obj_partial = false;
+    HIP_TRY(h, h->d_Q.reset((size_t)L));
+    HIP_TRY(h, h->d_vars.reset((size_t)(L + nb_vars)));
+    HIP_TRY(h, hipMemcpy(h->d_Q.get(), Q_arr, L * sizeof(double), hipMemcpyHostToDevice));
     h->nb_vars = nb_vars;
     h->L = L;
     h->q_absmax = 0.0;
@@ -159,41 +156,32 @@ int sdpcut_set_candidates(sdpcut_handle h, int64_t N, const int32_t *set_inds, i
     int rc = alloc_candidates(h, N, cnt, global_base);
     if (rc) return rc;
     if (N > 0) {
-        HIP_TRY(h, hipMemcpy(h->d_set_orig, pad.data(), (size_t)N * 5 * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMemcpy(h->d_k, kk.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIP_TRY(h, hipMemcpy(h->d_set_orig.get(), pad.data(), (size_t)N * 5 * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIP_TRY(h, hipMemcpy(h->d_k.get(), kk.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice));
     }
     for (int k = 2; k <= SDPCUT_MAX_K; ++k) {
         Bucket &b = h->bucket[k];
         if (!cnt[k]) continue;
-        HIP_TRY(h, hipMemcpy(b.d_set, soa[k].data(), soa[k].size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMemcpy(b.d_orig, orig[k].data(), orig[k].size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIP_TRY(h, hipMemcpy(b.d_set.get(), soa[k].data(), soa[k].size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIP_TRY(h, hipMemcpy(b.d_orig.get(), orig[k].data(), orig[k].size() * sizeof(int32_t), hipMemcpyHostToDevice));
     }
     return SDPCUT_OK;
 }
 
 static int ensure_point_stage(sdpcut_ctx *h)
 {
-    const size_t bytes = (size_t)(h->L + h->nb_vars) * sizeof(double);
-    if (h->point_stage_bytes >= bytes) return 0;
-    HIP_TRY(h, sdpcut_sync(h));
-    if (h->point_stage) (void)hipHostFree(h->point_stage);
-    h->point_stage = nullptr;
-    h->point_stage_bytes = 0;
-    HIP_TRY(h, hipHostMalloc(&h->point_stage, bytes, hipHostMallocMapped));
-    HIP_TRY(h, hipHostGetDevicePointer(&h->point_stage_dev, h->point_stage, 0));
-    h->point_stage_bytes = bytes;
-    return 0;
+    return grow(h, h->point_stage, (size_t)(h->L + h->nb_vars) * sizeof(double));
 }
 
 int sdpcut_point_buffer(sdpcut_handle h, double **buf)
 {
     if (!h) return SDPCUT_EINVAL;
     if (!buf) return sdpcut_fail(h, SDPCUT_EINVAL, "buf is NULL");
-    if (!h->d_vars) return sdpcut_fail(h, SDPCUT_ESTATE, "set_instance first");
+    if (!h->d_vars.get()) return sdpcut_fail(h, SDPCUT_ESTATE, "set_instance first");
     HIP_TRY(h, hipSetDevice(h->device));
     int rc = ensure_point_stage(h);
     if (rc) return rc;
-    *buf = (double *)h->point_stage;
+    *buf = (double *)h->point_stage.get();
     return SDPCUT_OK;
 }
 
@@ -201,7 +189,7 @@ int sdpcut_set_point(sdpcut_handle h, const double *vars_values)
 {
     if (!h) return SDPCUT_EINVAL;
     SDPCUT_NO_PENDING(h);
-    if (!h->d_vars) return sdpcut_fail(h, SDPCUT_ESTATE, "set_instance first");
+    if (!h->d_vars.get()) return sdpcut_fail(h, SDPCUT_ESTATE, "set_instance first");
     if (!vars_values) return sdpcut_fail(h, SDPCUT_EINVAL, "vars_values is NULL");
     HIP_TRY(h, hipSetDevice(h->device));
     // The caller's (pageable) buffer is copied into a pinned staging block and sent from there: the
@@ -212,16 +200,16 @@ int sdpcut_set_point(sdpcut_handle h, const double *vars_values)
     const size_t bytes = (size_t)(h->L + h->nb_vars) * sizeof(double);
     int rc = ensure_point_stage(h);
     if (rc) return rc;
-    if (vars_values != (const double *)h->point_stage) {
+    if (vars_values != (const double *)h->point_stage.get()) {
         // (every round ends in a host wait on the device, so this one is normally skipped; an event per
         // transfer would put a barrier packet -- ~10 us -- in front of every score launch)
         if (h->point_inflight) HIP_TRY(h, sdpcut_sync(h));
-        std::memcpy(h->point_stage, vars_values, bytes);
+        std::memcpy(h->point_stage.get(), vars_values, bytes);
     }
     // a kernel of the compute queue pulls the block over PCIe (mapped host memory): the score launch
     // follows it in queue order, whereas a copy-engine transfer costs a cross-queue hand-off (~10 us)
     // in front of every round
-    rc = launch_point_copy(h, (const double *)h->point_stage_dev, h->L + h->nb_vars);
+    rc = launch_point_copy(h, (const double *)h->point_stage.dev(), h->L + h->nb_vars);
     if (rc) return rc;
     if ((rc = box_after_point(h))) return rc;
     h->point_inflight = true;
@@ -235,10 +223,10 @@ int sdpcut_set_point_device(sdpcut_handle h, const void *d_vars_values)
 {
     if (!h) return SDPCUT_EINVAL;
     SDPCUT_NO_PENDING(h);
-    if (!h->d_vars) return sdpcut_fail(h, SDPCUT_ESTATE, "set_instance first");
+    if (!h->d_vars.get()) return sdpcut_fail(h, SDPCUT_ESTATE, "set_instance first");
     if (!d_vars_values) return sdpcut_fail(h, SDPCUT_EINVAL, "d_vars_values is NULL");
     HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipMemcpyAsync(h->d_vars, d_vars_values, (h->L + h->nb_vars) * sizeof(double),
+    HIP_TRY(h, hipMemcpyAsync(h->d_vars.get(), d_vars_values, (h->L + h->nb_vars) * sizeof(double),
                               hipMemcpyDeviceToDevice, h->stream));
     int rc = box_after_point(h);
     if (rc) return rc;

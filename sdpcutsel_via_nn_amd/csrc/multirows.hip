@@ -273,9 +273,8 @@ __global__ __launch_bounds__(64) void cut_rows_all_kernel(int64_t count, int32_t
 // ------------------------------------------------------------------------------------------
 // what the multi-cut calls keep on the handle
 struct MultiWs {
-    int64_t cap = 0;                 // head entries ids / score hold
-    int64_t *ids = nullptr;          // [cap] the ranked head (sdpcut_rank_device)
-    double *score = nullptr;
+    DevBuf<int64_t> ids;             // [cap] the ranked head (sdpcut_rank_device); grows together with score
+    DevBuf<double> score;
     // max_per_set = 1 forwards to the plain round, whose block has no room for the per-row extras: they live here
     std::vector<int32_t> h_nneg, h_rank;
     std::vector<double> h_rlam;
@@ -283,10 +282,7 @@ struct MultiWs {
 
 void free_multi_ws(sdpcut_ctx *h)
 {
-    MultiWs *w = (MultiWs *)h->multi;
-    if (!w) return;
-    (void)hipFree(w->ids); (void)hipFree(w->score);
-    delete w;
+    delete (MultiWs *)h->multi;
     h->multi = nullptr;
 }
 
@@ -298,14 +294,8 @@ static int multi_ensure(sdpcut_ctx *h, int64_t cap, MultiWs **out)
         if (!w) return sdpcut_fail(h, SDPCUT_ENOMEM, "out of host memory");
         h->multi = w;
     }
-    if (cap > w->cap) {
-        HIP_TRY(h, sdpcut_sync(h));
-        (void)hipFree(w->ids); (void)hipFree(w->score);
-        w->ids = nullptr; w->score = nullptr; w->cap = 0;
-        HIP_TRY(h, hipMalloc((void **)&w->ids, (size_t)cap * 8));
-        HIP_TRY(h, hipMalloc((void **)&w->score, (size_t)cap * 8));
-        w->cap = cap;
-    }
+    int rc;
+    if ((rc = grow(h, w->ids, (size_t)(cap < 0 ? 0 : cap))) || (rc = grow(h, w->score, (size_t)(cap < 0 ? 0 : cap)))) return rc;
     *out = w;
     return 0;
 }
@@ -318,8 +308,8 @@ static int launch_multi_csr(sdpcut_ctx *h, MultiWs *w, int64_t cap, int64_t limi
     const int rc = ensure_round_sync(h);
     if (rc) return rc;
     MultiCsrArgs R;
-    R.cap = cap; R.limit = limit; R.row_cap = row_cap; R.m = m; R.idx = w->ids; R.score = w->score; R.idx_base = h->base;
-    R.n_local = h->N; R.set5 = h->d_set_orig; R.ks = h->d_k; R.vars = h->d_vars; R.nv = h->nb_vars; R.L = h->L;
+    R.cap = cap; R.limit = limit; R.row_cap = row_cap; R.m = m; R.idx = w->ids.get(); R.score = w->score.get(); R.idx_base = h->base;
+    R.n_local = h->N; R.set5 = h->d_set_orig.get(); R.ks = h->d_k.get(); R.vars = h->d_vars.get(); R.nv = h->nb_vars; R.L = h->L;
     const CsrMultiLayout y = csr_multi_layout(cap, row_cap, ld);
     char *b = (char *)block;
     R.o_hdr = (int64_t *)b;
@@ -328,7 +318,7 @@ static int launch_multi_csr(sdpcut_ctx *h, MultiWs *w, int64_t cap, int64_t limi
     R.o_row_entry = (int32_t *)(b + y.row_entry); R.o_row_rank = (int32_t *)(b + y.row_rank); R.o_indptr = (int32_t *)(b + y.indptr);
     R.o_rhs = (double *)(b + y.rhs); R.o_row_lam = (double *)(b + y.row_lam); R.o_indices = (int32_t *)(b + y.indices);
     R.o_values = (double *)(b + y.values);
-    R.serial = serial; R.done_ticket = h->d_done_ticket; R.agg = round_agg_words(h);
+    R.serial = serial; R.done_ticket = h->d_done_ticket.get(); R.agg = round_agg_words(h);
     R.inject = inject_take(h, 2, grid > 1);
     hipLaunchKernelGGL(multi_csr_kernel, dim3(grid), dim3(64), 0, h->stream, R);
     HIP_TRY(h, hipGetLastError());
@@ -379,7 +369,7 @@ int sdpcut_round_csr_multi(sdpcut_handle h, const double *vars_values, int strat
     const uint32_t measure = strat_view(h, strat);      // strategies 3 and 6 rank through a view (common.h: MeasureAsObj)
     if (!measure && (rc = check_round_strategy(h, strat))) return rc;
     if (sel_size < 0) return sdpcut_fail(h, SDPCUT_EINVAL, "bad round_csr_multi arguments");
-    if (h->nb_vars == 0 || !h->d_eig || !(h->have_point || vars_values))
+    if (h->nb_vars == 0 || !h->d_eig.get() || !(h->have_point || vars_values))
         return sdpcut_fail(h, SDPCUT_ESTATE, "set_instance, set_candidates and a point first");
     SDPCUT_NO_PENDING(h);
     if (max_per_set == 1) return multi_forward_one(h, vars_values, strat, sel_size, row_quota, out);
@@ -400,7 +390,7 @@ int sdpcut_round_csr_multi(sdpcut_handle h, const double *vars_values, int strat
     rc = multi_ensure(h, cap, &w);
     if (rc) return rc;
     int64_t P = 0;
-    rc = sdpcut_rank_device(h, strat, sel_size, cap, w->ids, w->score, &P, &o.n_total, &o.new_strat, o.counters);
+    rc = sdpcut_rank_device(h, strat, sel_size, cap, w->ids.get(), w->score.get(), &P, &o.n_total, &o.new_strat, o.counters);
     if (rc) return rc;
     if (P > cap) P = cap;
     const int64_t all_rows = (int64_t)max_per_set * cap;
@@ -409,13 +399,13 @@ int sdpcut_round_csr_multi(sdpcut_handle h, const double *vars_values, int strat
     const CsrMultiLayout y = csr_multi_layout(cap, row_cap, ld);
     rc = ensure_pinned(h, y.bytes);
     if (rc) return rc;
-    const int64_t *hdr = (const int64_t *)h->pinned;
+    const int64_t *hdr = (const int64_t *)h->pinned.get();
     rc = csr_assemble_wait(h, 11, 2, true, "round_csr_multi", [&](int64_t serial) {
-        return launch_multi_csr(h, w, cap, P, row_cap, max_per_set, ld, h->pinned_dev, serial);
+        return launch_multi_csr(h, w, cap, P, row_cap, max_per_set, ld, h->pinned.dev(), serial);
     });
     if (rc) return rc;
     ++h->stat_rounds;
-    const char *b = (const char *)h->pinned;
+    const char *b = (const char *)h->pinned.get();
     o.cap = cap;
     o.n_out = P;
     o.idx = (const int64_t *)(b + y.idx);
@@ -446,7 +436,7 @@ int sdpcut_cut_rows_all(sdpcut_handle h, int64_t count, const int64_t *idx, int3
     SDPCUT_NO_PENDING(h);
     if (max_per_set < 1 || max_per_set > SDPCUT_MULTI_MAX_PER_SET)
         return sdpcut_fail(h, SDPCUT_EINVAL, "max_per_set must lie in 1 .. SDPCUT_MULTI_MAX_PER_SET");
-    if (!h->have_point || !h->d_set_orig) return sdpcut_fail(h, SDPCUT_ESTATE, "set_candidates and set_point first");
+    if (!h->have_point || !h->d_set_orig.get()) return sdpcut_fail(h, SDPCUT_ESTATE, "set_candidates and set_point first");
     if (count < 0 || !row_ptr || (count > 0 && (!idx || !row_lam || !coef || !rhs || !cols || !ks)))
         return sdpcut_fail(h, SDPCUT_EINVAL, "bad cut_rows_all arguments");
     row_ptr[0] = 0;
@@ -478,7 +468,7 @@ int sdpcut_cut_rows_all(sdpcut_handle h, int64_t count, const int64_t *idx, int3
     const size_t bytes = c * 8 + c * m * 8 * (2 + LD) + c * 8 * LD + c * 8;
     int rc = ensure_stage(h, bytes);
     if (rc) return rc;
-    char *p = (char *)h->d_stage;
+    char *p = (char *)h->d_stage.get();
     int64_t *d_idx = (int64_t *)p; p += c * 8;
     double *d_lam = (double *)p; p += c * m * 8;
     double *d_rhs = (double *)p; p += c * m * 8;
@@ -496,8 +486,8 @@ int sdpcut_cut_rows_all(sdpcut_handle h, int64_t count, const int64_t *idx, int3
     // slots an entry does not fill are never read back as rows, but they travel: keep them defined
     HIP_TRY(h, hipMemsetAsync(d_lam, 0, c * m * 8 * (2 + LD), h->stream));
     const int grid = (int)((count + 63) / 64);
-    hipLaunchKernelGGL(cut_rows_all_kernel, dim3(grid), dim3(64), 0, h->stream, count, max_per_set, d_idx, h->N, h->d_set_orig, h->d_k,
-                       h->d_vars, h->nb_vars, h->L, d_off, d_lam, d_coef, d_rhs, d_cols, d_ks);
+    hipLaunchKernelGGL(cut_rows_all_kernel, dim3(grid), dim3(64), 0, h->stream, count, max_per_set, d_idx, h->N, h->d_set_orig.get(), h->d_k.get(),
+                       h->d_vars.get(), h->nb_vars, h->L, d_off, d_lam, d_coef, d_rhs, d_cols, d_ks);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipMemcpyAsync(row_lam, d_lam, c * m * 8, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipMemcpyAsync(rhs, d_rhs, c * m * 8, hipMemcpyDeviceToHost, h->stream));

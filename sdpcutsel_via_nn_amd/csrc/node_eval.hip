@@ -25,12 +25,9 @@
 #define NODE_EVAL_HDR_BYTES 64      /* doubles 0 f_point, 1 f_local, 2 branch_score, 3 branch_val; int32 at byte 32: sweeps, moves, branch_var */
 
 struct NodeEvalBufs {
-    void *stage = nullptr;                          // pinned staging: the points [P][L + n], then lb [P][n], ub [P][n]
-    size_t stage_bytes = 0;
-    double *d_in = nullptr;                         // the same on the device
-    size_t in_doubles = 0;
-    void *pinned = nullptr, *pinned_dev = nullptr;  // the result block: slice p = header | x_local [n], padded to 64 bytes
-    size_t pinned_bytes = 0;
+    HostBuf stage{false};                           // pinned staging (default memory: the source of a hipMemcpyAsync): the points [P][L + n], then lb [P][n], ub [P][n]
+    DevBuf<double> d_in;                            // the same on the device
+    HostBuf pinned{true};                           // the result block: slice p = header | x_local [n], padded to 64 bytes
 };
 
 struct NodeEvalArgs {
@@ -203,12 +200,7 @@ __global__ __launch_bounds__(64) void node_eval_kernel(NodeEvalArgs A)
 // ------------------------------------------------------------------------------------------
 void free_node_eval_ws(sdpcut_ctx *h)
 {
-    NodeEvalBufs *b = (NodeEvalBufs *)h->node_eval;
-    if (!b) return;
-    if (b->stage) (void)hipHostFree(b->stage);
-    if (b->pinned) (void)hipHostFree(b->pinned);
-    (void)hipFree(b->d_in);
-    delete b;
+    delete (NodeEvalBufs *)h->node_eval;
     h->node_eval = nullptr;
 }
 
@@ -218,47 +210,15 @@ static int node_eval_build_table(sdpcut_ctx *h)
 {
     if (h->lpobj_dense_ok) return 0;
     const int64_t n = h->nb_vars;
-    if (!h->d_lpobj_dense) HIP_TRY(h, hipMalloc((void **)&h->d_lpobj_dense, (size_t)(n * n) * sizeof(double)));
-    hipLaunchKernelGGL(node_eval_table_kernel, dim3((unsigned)((n * n + 255) / 256)), dim3(256), 0, h->stream, (int32_t)n, (const double *)h->d_lpobj,
-                       h->d_lpobj_dense);
+    if (!h->d_lpobj_dense.get()) HIP_TRY(h, h->d_lpobj_dense.reset((size_t)(n * n)));
+    hipLaunchKernelGGL(node_eval_table_kernel, dim3((unsigned)((n * n + 255) / 256)), dim3(256), 0, h->stream, (int32_t)n, (const double *)h->d_lpobj.get(),
+                       h->d_lpobj_dense.get());
     HIP_TRY(h, hipGetLastError());
     h->lpobj_dense_ok = true;
     return 0;
 }
 
 static size_t node_eval_slice(int64_t n) { return ((size_t)NODE_EVAL_HDR_BYTES + (size_t)n * 8 + 63) & ~(size_t)63; }
-
-static int node_eval_ensure(sdpcut_ctx *h, size_t in_doubles, size_t block_bytes)
-{
-    if (!h->node_eval) h->node_eval = new NodeEvalBufs();
-    NodeEvalBufs &b = *(NodeEvalBufs *)h->node_eval;
-    if (b.pinned_bytes < block_bytes) {
-        HIP_TRY(h, sdpcut_sync(h));
-        if (b.pinned) (void)hipHostFree(b.pinned);
-        b.pinned = b.pinned_dev = nullptr;
-        b.pinned_bytes = 0;
-        HIP_TRY(h, hipHostMalloc(&b.pinned, block_bytes, hipHostMallocMapped));
-        HIP_TRY(h, hipHostGetDevicePointer(&b.pinned_dev, b.pinned, 0));
-        b.pinned_bytes = block_bytes;
-    }
-    if (b.stage_bytes < in_doubles * 8) {
-        HIP_TRY(h, sdpcut_sync(h));
-        if (b.stage) (void)hipHostFree(b.stage);
-        b.stage = nullptr;
-        b.stage_bytes = 0;
-        HIP_TRY(h, hipHostMalloc(&b.stage, in_doubles * 8, hipHostMallocDefault));
-        b.stage_bytes = in_doubles * 8;
-    }
-    if (b.in_doubles < in_doubles) {
-        HIP_TRY(h, sdpcut_sync(h));
-        (void)hipFree(b.d_in);
-        b.d_in = nullptr;
-        b.in_doubles = 0;
-        HIP_TRY(h, hipMalloc((void **)&b.d_in, in_doubles * 8));
-        b.in_doubles = in_doubles;
-    }
-    return 0;
-}
 
 extern "C" {
 
@@ -268,15 +228,13 @@ int sdpcut_node_eval_points(sdpcut_handle h, int32_t n_points, const double *poi
     if (!h) return SDPCUT_EINVAL;
     const std::string what = "sdpcut_node_eval_points: ";
     if (!out) return sdpcut_fail(h, SDPCUT_EINVAL, what + "out is NULL");
-    if (n_points < 1 || n_points > SDPCUT_BATCH_MAX_POINTS)
-        return sdpcut_fail(h, SDPCUT_EINVAL, what + "n_points must be 1 .. SDPCUT_BATCH_MAX_POINTS (" + std::to_string(SDPCUT_BATCH_MAX_POINTS) + ")");
-    if (!points) return sdpcut_fail(h, SDPCUT_EINVAL, what + "points is NULL");
-    if (!h->d_vars || h->nb_vars == 0) return sdpcut_fail(h, SDPCUT_ESTATE, what + "set_instance first");
-    if (!h->d_lpobj) return sdpcut_fail(h, SDPCUT_ESTATE, what + "set_objective first");
+    if (!h->d_vars.get() || h->nb_vars == 0) return sdpcut_fail(h, SDPCUT_ESTATE, what + "set_instance first");
+    if (!h->d_lpobj.get()) return sdpcut_fail(h, SDPCUT_ESTATE, what + "set_objective first");
     const int64_t n = h->nb_vars, L = h->L, m = L + n;
     if (n > NODE_EVAL_MAX_N) return sdpcut_fail(h, SDPCUT_EINVAL, what + "instances of at most " + std::to_string(NODE_EVAL_MAX_N) + " variables are served");
-    if (point_ld < m) return sdpcut_fail(h, SDPCUT_EINVAL, what + "point_ld must be at least L + n");
-    if ((lb == nullptr) != (ub == nullptr)) return sdpcut_fail(h, SDPCUT_EINVAL, what + "lb and ub must both be given or both be NULL");
+    int rc;
+    if ((rc = check_point_batch(h, what.c_str(), n_points, points, point_ld, m))) return rc;
+    if ((rc = check_box_pair(h, what.c_str(), lb, ub))) return rc;
     if (max_sweeps < 0) return sdpcut_fail(h, SDPCUT_EINVAL, what + "max_sweeps must be >= 0");
     if (branch_rule != 0 && branch_rule != 1) return sdpcut_fail(h, SDPCUT_EINVAL, what + "branch_rule must be 0 (X_ii - x_i^2) or 1 (weighted by the objective)");
     if (!(rho > 0.0 && rho <= 0.5)) return sdpcut_fail(h, SDPCUT_EINVAL, what + "rho must lie in (0, 0.5]");
@@ -295,35 +253,37 @@ int sdpcut_node_eval_points(sdpcut_handle h, int32_t n_points, const double *poi
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t slice = node_eval_slice(n);
     const size_t pts = (size_t)P * (size_t)m, bx = lb ? (size_t)P * (size_t)n : 0;
-    int rc;
-    if ((rc = node_eval_ensure(h, pts + 2 * bx, slice * (size_t)P))) return rc;
+    if (!h->node_eval) h->node_eval = new NodeEvalBufs();
     NodeEvalBufs &b = *(NodeEvalBufs *)h->node_eval;
-    double *st = (double *)b.stage;
-    for (int p = 0; p < P; ++p) std::memcpy(st + (size_t)p * m, points + (size_t)p * point_ld, (size_t)m * 8);
+    if ((rc = grow(h, b.pinned, slice * (size_t)P))) return rc;
+    if ((rc = grow(h, b.stage, (pts + 2 * bx) * 8))) return rc;
+    if ((rc = grow(h, b.d_in, pts + 2 * bx))) return rc;
+    double *st = (double *)b.stage.get();
+    pack_points(st, P, points, point_ld, m);
     if (lb) {
         std::memcpy(st + pts, lb, bx * 8);
         std::memcpy(st + pts + bx, ub, bx * 8);
     }
-    HIP_TRY(h, hipMemcpyAsync(b.d_in, st, (pts + 2 * bx) * 8, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(b.d_in.get(), st, (pts + 2 * bx) * 8, hipMemcpyHostToDevice, h->stream));
     if ((rc = node_eval_build_table(h))) return rc;      // (the first call after a set_objective: one more launch on the stream)
     NodeEvalArgs A;
     A.n = (int32_t)n;
     A.L = L;
-    A.pts = b.d_in;
+    A.pts = b.d_in.get();
     A.pts_stride = m;
-    A.lb = lb ? b.d_in + pts : nullptr;
-    A.ub = lb ? b.d_in + pts + bx : nullptr;
-    A.obj = h->d_lpobj;
-    A.tab = h->d_lpobj_dense;
+    A.lb = lb ? b.d_in.get() + pts : nullptr;
+    A.ub = lb ? b.d_in.get() + pts + bx : nullptr;
+    A.obj = h->d_lpobj.get();
+    A.tab = h->d_lpobj_dense.get();
     A.max_sweeps = max_sweeps;
     A.rule = branch_rule;
     A.rho = rho;
-    A.block = (char *)b.pinned_dev;
+    A.block = (char *)b.pinned.dev();
     A.slice = (int64_t)slice;
     hipLaunchKernelGGL(node_eval_kernel, dim3((unsigned)P), dim3(64), (size_t)n * 8, h->stream, A);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, sdpcut_sync(h));      // the one wait of the call
-    const char *blk = (const char *)b.pinned;
+    const char *blk = (const char *)b.pinned.get();
     for (int p = 0; p < P; ++p) {
         const char *s = blk + slice * (size_t)p;
         const double *hd = (const double *)s;

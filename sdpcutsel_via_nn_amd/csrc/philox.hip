@@ -33,7 +33,7 @@ extern "C" int sdpcut_set_candidates_philox(sdpcut_handle h, int32_t k, int64_t 
     if (N == 0) return SDPCUT_OK;
     const Bucket &b = h->bucket[k];
     hipLaunchKernelGGL(philox_sets_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, seed,
-                       (uint64_t)first_id, N, (int)h->nb_vars, (int)k, b.d_set, b.d_orig, h->d_set_orig, h->d_k);
+                       (uint64_t)first_id, N, (int)h->nb_vars, (int)k, b.d_set.get(), b.d_orig.get(), h->d_set_orig.get(), h->d_k.get());
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, sdpcut_sync(h));
     return SDPCUT_OK;
@@ -60,17 +60,17 @@ extern "C" int sdpcut_get_candidates(sdpcut_handle h, int64_t count, const int64
     SDPCUT_NO_PENDING(h);
     if (count < 0 || (count > 0 && (!idx || !set_inds_out || !ks_out)))
         return sdpcut_fail(h, SDPCUT_EINVAL, "bad get_candidates arguments");
-    if (!h->d_set_orig) return sdpcut_fail(h, SDPCUT_ESTATE, "no candidate list");
+    if (!h->d_set_orig.get()) return sdpcut_fail(h, SDPCUT_ESTATE, "no candidate list");
     if (count == 0) return SDPCUT_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t c = (size_t)count;
     int rc = ensure_stage(h, c * (8 + 20 + 4));
     if (rc) return rc;
-    int64_t *d_idx = (int64_t *)h->d_stage;
+    int64_t *d_idx = (int64_t *)h->d_stage.get();
     int32_t *d_out = (int32_t *)(d_idx + c), *d_k = d_out + c * 5;
     HIP_TRY(h, hipMemcpyAsync(d_idx, idx, c * 8, hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(gather_sets_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, h->stream, count, d_idx,
-                       h->N, h->d_set_orig, h->d_k, d_out, d_k);
+                       h->N, h->d_set_orig.get(), h->d_k.get(), d_out, d_k);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipMemcpyAsync(set_inds_out, d_out, c * 20, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipMemcpyAsync(ks_out, d_k, c * 4, hipMemcpyDeviceToHost, h->stream));

@@ -94,20 +94,7 @@ __global__ __launch_bounds__(256) void strong_points_kernel(const double *eig, c
 }
 
 // ------------------------------------------------------------------------------------------
-// buffers (grown on demand; both calls are synchronous, so nothing is in flight when one is replaced)
-
-void free_points_ws(sdpcut_ctx *h)
-{
-    PointsBufs &b = h->pts;
-    if (b.stage) (void)hipHostFree(b.stage);
-    if (b.pinned) (void)hipHostFree(b.pinned);
-    (void)hipFree(b.d_pts); (void)hipFree(b.d_eig); (void)hipFree(b.d_obj); (void)hipFree(b.d_ws); (void)hipFree(b.d_idx);
-    (void)hipFree(b.d_score); (void)hipFree(b.d_agg);
-    (void)hipFree(b.d_box_ld); (void)hipFree(b.d_Q_box); (void)hipFree(b.d_vars_box);
-    (void)hipFree(b.d_eff); (void)hipFree(b.d_div);
-    if (b.div_sel) (void)hipHostFree(b.div_sel);
-    b = PointsBufs();
-}
+// buffers (grown on demand through grow, common.h: the stream is waited for before a block is replaced)
 
 // staging (pinned, mapped) and device table for P points; boxed: the staging block also holds the [P][2 n] (l | d) rows behind the
 // points, and the device has a table for them
@@ -116,44 +103,18 @@ static int ensure_points_table(sdpcut_ctx *h, int P, bool boxed)
     PointsBufs &b = h->pts;
     const size_t doubles = (size_t)P * (size_t)(h->L + h->nb_vars);
     const size_t box_doubles = boxed ? (size_t)P * 2 * (size_t)h->nb_vars : 0;
-    if (b.stage_bytes < (doubles + box_doubles) * 8) {
-        HIP_TRY(h, sdpcut_sync(h));
-        if (b.stage) (void)hipHostFree(b.stage);
-        b.stage = b.stage_dev = nullptr;
-        b.stage_bytes = 0;
-        HIP_TRY(h, hipHostMalloc(&b.stage, (doubles + box_doubles) * 8, hipHostMallocMapped));
-        HIP_TRY(h, hipHostGetDevicePointer(&b.stage_dev, b.stage, 0));
-        b.stage_bytes = (doubles + box_doubles) * 8;
-    }
-    if (b.box_ld_doubles < box_doubles) {
-        (void)hipFree(b.d_box_ld);
-        b.d_box_ld = nullptr;
-        b.box_ld_doubles = 0;
-        HIP_TRY(h, hipMalloc((void **)&b.d_box_ld, box_doubles * 8));
-        b.box_ld_doubles = box_doubles;
-    }
-    if (b.pts_doubles < doubles) {
-        (void)hipFree(b.d_pts);
-        b.d_pts = nullptr;
-        b.pts_doubles = 0;
-        HIP_TRY(h, hipMalloc((void **)&b.d_pts, doubles * 8));
-        b.pts_doubles = doubles;
-    }
-    return 0;
+    int rc;
+    if ((rc = grow(h, b.stage, (doubles + box_doubles) * 8))) return rc;
+    if ((rc = grow(h, b.d_box_ld, box_doubles))) return rc;
+    return grow(h, b.d_pts, doubles);
 }
 
 static int ensure_points_scores(sdpcut_ctx *h, int P)
 {
     PointsBufs &b = h->pts;
     const size_t doubles = (size_t)P * (size_t)h->N;
-    if (b.score_doubles >= doubles) return 0;
-    (void)hipFree(b.d_eig); (void)hipFree(b.d_obj);
-    b.d_eig = b.d_obj = nullptr;
-    b.score_doubles = 0;
-    HIP_TRY(h, hipMalloc((void **)&b.d_eig, doubles * 8));
-    HIP_TRY(h, hipMalloc((void **)&b.d_obj, doubles * 8));
-    b.score_doubles = doubles;
-    return 0;
+    const int rc = grow(h, b.d_eig, doubles);      // (the two are always asked for the same size: they grow together)
+    return rc ? rc : grow(h, b.d_obj, doubles);
 }
 
 // Q' and the transformed points of a boxed batch of P points (batch_route.h: batch_box_table_bytes)
@@ -161,28 +122,17 @@ static int ensure_box_tables(sdpcut_ctx *h, int P)
 {
     PointsBufs &b = h->pts;
     const size_t q = (size_t)P * (size_t)h->L, v = (size_t)P * (size_t)(h->L + h->nb_vars);
-    if (b.box_q_doubles >= q && b.box_vars_doubles >= v) return 0;
-    (void)hipFree(b.d_Q_box); (void)hipFree(b.d_vars_box);
-    b.d_Q_box = b.d_vars_box = nullptr;
-    b.box_q_doubles = b.box_vars_doubles = 0;
-    HIP_TRY(h, hipMalloc((void **)&b.d_Q_box, q * 8));
-    HIP_TRY(h, hipMalloc((void **)&b.d_vars_box, v * 8));
-    b.box_q_doubles = q;
-    b.box_vars_doubles = v;
-    return 0;
+    const int rc = grow(h, b.d_Q_box, q);
+    return rc ? rc : grow(h, b.d_vars_box, v);
 }
 
-static int ensure_points_block(sdpcut_ctx *h, size_t bytes)
+// grow, and zero-fill what is new on the stream: the kernels that read these arrays rely on zeros where nothing was written yet
+template <class T> static int grow_zeroed(sdpcut_ctx *h, DevBuf<T> &buf, size_t count)
 {
-    PointsBufs &b = h->pts;
-    if (b.pinned_bytes >= bytes) return 0;
-    HIP_TRY(h, sdpcut_sync(h));
-    if (b.pinned) (void)hipHostFree(b.pinned);
-    b.pinned = b.pinned_dev = nullptr;
-    b.pinned_bytes = 0;
-    HIP_TRY(h, hipHostMalloc(&b.pinned, bytes, hipHostMallocMapped));
-    HIP_TRY(h, hipHostGetDevicePointer(&b.pinned_dev, b.pinned, 0));
-    b.pinned_bytes = bytes;
+    bool grew = false;
+    const int rc = grow(h, buf, count, &grew);
+    if (rc) return rc;
+    if (grew) HIP_TRY(h, hipMemsetAsync(buf.get(), 0, count * sizeof(T), h->stream));
     return 0;
 }
 
@@ -190,49 +140,24 @@ static int ensure_points_block(sdpcut_ctx *h, size_t bytes)
 static int ensure_points_select(sdpcut_ctx *h, int P, int64_t cap)
 {
     PointsBufs &b = h->pts;
-    if (b.ws_points < P) {
-        (void)hipFree(b.d_ws);
-        b.d_ws = nullptr;
-        b.ws_points = 0;
-        HIP_TRY(h, hipMalloc(&b.d_ws, (size_t)P * sizeof(TopkWs)));
-        HIP_TRY(h, hipMemsetAsync(b.d_ws, 0, (size_t)P * sizeof(TopkWs), h->stream));
-        b.ws_points = P;
-    }
     const size_t entries = (size_t)P * (size_t)cap;
-    if (b.head_entries < entries) {
-        (void)hipFree(b.d_idx); (void)hipFree(b.d_score);
-        b.d_idx = nullptr; b.d_score = nullptr;
-        b.head_entries = 0;
-        HIP_TRY(h, hipMalloc((void **)&b.d_idx, entries * 8));
-        HIP_TRY(h, hipMalloc((void **)&b.d_score, entries * 8));
-        // (a void selection emits no head, the assembly still reads its rows: never uninitialised memory)
-        HIP_TRY(h, hipMemsetAsync(b.d_idx, 0, entries * 8, h->stream));
-        HIP_TRY(h, hipMemsetAsync(b.d_score, 0, entries * 8, h->stream));
-        b.head_entries = entries;
-    }
-    if (b.agg_points < P) {
-        (void)hipFree(b.d_agg);
-        b.d_agg = nullptr;
-        b.agg_points = 0;
-        HIP_TRY(h, hipMalloc((void **)&b.d_agg, (size_t)P * BATCH_AGG_WORDS * 8));
-        HIP_TRY(h, hipMemsetAsync(b.d_agg, 0, (size_t)P * BATCH_AGG_WORDS * 8, h->stream));
-        b.agg_points = P;
-    }
-    return 0;
+    int rc;
+    if ((rc = grow_zeroed(h, b.d_ws, (size_t)P * sizeof(TopkWs)))) return rc;
+    // (a void selection emits no head, the assembly still reads its rows: never uninitialised memory)
+    if ((rc = grow_zeroed(h, b.d_idx, entries)) || (rc = grow_zeroed(h, b.d_score, entries))) return rc;
+    return grow_zeroed(h, b.d_agg, (size_t)P * BATCH_AGG_WORDS);
 }
 
 // ------------------------------------------------------------------------------------------
 // host side
 
-// the argument checks both calls share (the handle itself has been checked)
-static int check_points_args(sdpcut_ctx *h, int32_t n_points, const double *points, int64_t point_ld)
+// the shared intake checks and the state the batched rounds need (the handle itself has been checked)
+static int check_batch_state(sdpcut_ctx *h, int32_t n_points, const double *points, int64_t point_ld)
 {
-    if (n_points < 1 || n_points > SDPCUT_BATCH_MAX_POINTS)
-        return sdpcut_fail(h, SDPCUT_EINVAL, "n_points must be 1 .. SDPCUT_BATCH_MAX_POINTS (" + std::to_string(SDPCUT_BATCH_MAX_POINTS) + ")");
-    if (!points) return sdpcut_fail(h, SDPCUT_EINVAL, "points is NULL");
-    if (!h->d_vars) return sdpcut_fail(h, SDPCUT_ESTATE, "set_instance first");
-    if (!h->d_eig || h->N < 1) return sdpcut_fail(h, SDPCUT_ESTATE, "set_candidates first");
-    if (point_ld < h->L + h->nb_vars) return sdpcut_fail(h, SDPCUT_EINVAL, "point_ld must be at least L + n");
+    const int rc = check_point_batch(h, "", n_points, points, point_ld, h->L + h->nb_vars);
+    if (rc) return rc;
+    if (!h->d_vars.get()) return sdpcut_fail(h, SDPCUT_ESTATE, "set_instance first");
+    if (!h->d_eig.get() || h->N < 1) return sdpcut_fail(h, SDPCUT_ESTATE, "set_candidates first");
     return 0;
 }
 
@@ -251,19 +176,13 @@ static int upload_points(sdpcut_ctx *h, int P, const double *points, int64_t poi
     int rc = ensure_points_table(h, P, bx != nullptr);
     if (rc) return rc;
     const int64_t n = h->L + h->nb_vars, nv = h->nb_vars;
-    for (int p = 0; p < P; ++p) std::memcpy((double *)h->pts.stage + (size_t)p * n, points + (size_t)p * point_ld, (size_t)n * 8);
+    pack_points((double *)h->pts.stage.get(), P, points, point_ld, n);
     const size_t box_off = (size_t)P * (size_t)n;
-    if (bx) {
-        double *ld = (double *)h->pts.stage + box_off;
-        for (int p = 0; p < P; ++p) {
-            const double *lb = bx->lb + (size_t)p * bx->ld, *ub = bx->ub + (size_t)p * bx->ld;
-            for (int64_t i = 0; i < nv; ++i) { ld[(size_t)p * 2 * nv + i] = lb[i]; ld[(size_t)p * 2 * nv + nv + i] = ub[i] - lb[i]; }
-        }
-    }
+    if (bx) pack_box_ld((double *)h->pts.stage.get() + box_off, P, nv, bx->lb, bx->ld, bx->ub, bx->ld);
     int64_t g = (n + 255) / 256;
     if (g > 64) g = 64;
-    hipLaunchKernelGGL(points_copy_kernel, dim3((unsigned)g, (unsigned)(P + (bx ? 1 : 0))), dim3(256), 0, h->stream, (const double *)h->pts.stage_dev,
-                       h->pts.d_pts, n, ws, P, bx ? (const double *)h->pts.stage_dev + box_off : nullptr, bx ? h->pts.d_box_ld : nullptr,
+    hipLaunchKernelGGL(points_copy_kernel, dim3((unsigned)g, (unsigned)(P + (bx ? 1 : 0))), dim3(256), 0, h->stream, (const double *)h->pts.stage.dev(),
+                       h->pts.d_pts.get(), n, ws, P, bx ? (const double *)h->pts.stage.dev() + box_off : nullptr, bx ? h->pts.d_box_ld.get() : nullptr,
                        bx ? (int64_t)P * 2 * nv : 0);
     HIP_TRY(h, hipGetLastError());
     return 0;
@@ -298,14 +217,14 @@ static int score_batch(sdpcut_ctx *h, uint32_t flags, int P, bool boxed, int64_t
     PointsBufs &b = h->pts;
     const int64_t n = h->L + h->nb_vars;
     int rc;
-    if (!boxed || !(flags & SDPCUT_NN)) return launch_score_points(h, flags, P, b.d_pts, n, b.d_eig, b.d_obj, h->N, strong, strong_stride);
+    if (!boxed || !(flags & SDPCUT_NN)) return launch_score_points(h, flags, P, b.d_pts.get(), n, b.d_eig.get(), b.d_obj.get(), h->N, strong, strong_stride);
     if ((rc = ensure_box_tables(h, P))) return rc;
-    if ((flags & SDPCUT_EIG) && (rc = launch_score_points(h, SDPCUT_EIG, P, b.d_pts, n, b.d_eig, b.d_obj, h->N, nullptr, 0))) return rc;
-    if ((rc = launch_box_points(h, P, b.d_pts, n, b.d_box_ld, b.d_Q_box, b.d_vars_box))) return rc;
-    if ((rc = launch_score_points(h, SDPCUT_NN, P, b.d_vars_box, n, b.d_eig, b.d_obj, h->N, nullptr, 0, b.d_Q_box, h->L))) return rc;
+    if ((flags & SDPCUT_EIG) && (rc = launch_score_points(h, SDPCUT_EIG, P, b.d_pts.get(), n, b.d_eig.get(), b.d_obj.get(), h->N, nullptr, 0))) return rc;
+    if ((rc = launch_box_points(h, P, b.d_pts.get(), n, b.d_box_ld.get(), b.d_Q_box.get(), b.d_vars_box.get()))) return rc;
+    if ((rc = launch_score_points(h, SDPCUT_NN, P, b.d_vars_box.get(), n, b.d_eig.get(), b.d_obj.get(), h->N, nullptr, 0, b.d_Q_box.get(), h->L))) return rc;
     if (strong) {
-        hipLaunchKernelGGL(strong_points_kernel, dim3((unsigned)((h->N + 255) / 256), (unsigned)P), dim3(256), 0, h->stream, (const double *)b.d_eig,
-                           (const double *)b.d_obj, h->N, h->N, (TopkWs *)b.d_ws);
+        hipLaunchKernelGGL(strong_points_kernel, dim3((unsigned)((h->N + 255) / 256), (unsigned)P), dim3(256), 0, h->stream, (const double *)b.d_eig.get(),
+                           (const double *)b.d_obj.get(), h->N, h->N, (TopkWs *)b.d_ws.get());
         HIP_TRY(h, hipGetLastError());
     }
     return 0;
@@ -318,7 +237,7 @@ static int point_through_round(sdpcut_ctx *h, const double *point, int strat, in
     const int rc = sdpcut_round_csr(h, point, strat, sel_size, out);
     if (rc) return rc;
     if (out->cap > 0 && out->idx) {
-        std::memcpy(slot, h->pinned, csr_layout(out->cap, out->row_ld).bytes);
+        std::memcpy(slot, h->pinned.get(), csr_layout(out->cap, out->row_ld).bytes);
         csr_out_from_block(slot, out);
     }
     return SDPCUT_OK;
@@ -328,7 +247,7 @@ static int point_through_round(sdpcut_ctx *h, const double *point, int strat, in
 static int score_points_impl(sdpcut_ctx *h, const char *what, int32_t n_points, const double *points, int64_t point_ld, const BoxRows *bx,
                              uint32_t flags, double *eig_out, double *obj_out)
 {
-    int rc = check_points_args(h, n_points, points, point_ld);
+    int rc = check_batch_state(h, n_points, points, point_ld);
     if (rc) return rc;
     if (flags & SDPCUT_SDP) return sdpcut_fail(h, SDPCUT_EINVAL, std::string(what) + ": SDPCUT_SDP is not served over several points; flags = SDPCUT_EIG | SDPCUT_NN");
     if (flags & SDPCUT_EFF) return sdpcut_fail(h, SDPCUT_EINVAL, std::string(what) + ": SDPCUT_EFF is not served over several points; flags = SDPCUT_EIG | SDPCUT_NN");
@@ -357,8 +276,8 @@ static int score_points_impl(sdpcut_ctx *h, const char *what, int32_t n_points, 
     if ((rc = ensure_points_scores(h, P))) return rc;
     if ((rc = upload_points(h, P, points, point_ld, nullptr, bx))) return rc;
     if ((rc = score_batch(h, flags, P, bx != nullptr, nullptr, 0))) return rc;
-    if (flags & SDPCUT_EIG) HIP_TRY(h, hipMemcpyAsync(eig_out, h->pts.d_eig, (size_t)P * N * 8, hipMemcpyDeviceToHost, h->stream));
-    if (flags & SDPCUT_NN) HIP_TRY(h, hipMemcpyAsync(obj_out, h->pts.d_obj, (size_t)P * N * 8, hipMemcpyDeviceToHost, h->stream));
+    if (flags & SDPCUT_EIG) HIP_TRY(h, hipMemcpyAsync(eig_out, h->pts.d_eig.get(), (size_t)P * N * 8, hipMemcpyDeviceToHost, h->stream));
+    if (flags & SDPCUT_NN) HIP_TRY(h, hipMemcpyAsync(obj_out, h->pts.d_obj.get(), (size_t)P * N * 8, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, sdpcut_sync(h));
     return SDPCUT_OK;
 }
@@ -368,7 +287,7 @@ static int round_csr_points_impl(sdpcut_ctx *h, const char *what, int32_t n_poin
                                  int strat, int64_t sel_size, sdpcut_round_csr_t *out)
 {
     if (!out) return sdpcut_fail(h, SDPCUT_EINVAL, "out is NULL");
-    int rc = check_points_args(h, n_points, points, point_ld);
+    int rc = check_batch_state(h, n_points, points, point_ld);
     if (rc) return rc;
     if (strat == SDPCUT_STRAT_EFF)
         return sdpcut_fail(h, SDPCUT_EINVAL, std::string(what) + ": strategy 6 (efficacy) is not served over several points; strategies 1, 2 and 4 are");
@@ -395,8 +314,8 @@ static int round_csr_points_impl(sdpcut_ctx *h, const char *what, int32_t n_poin
     if (route == BATCH_FAST && (!batch_score_served(h, need, bx_dev != nullptr) || (strat == SDPCUT_STRAT_COMB && !h->auto_regime) || h->timing))
         route = BATCH_LOOP;
     const BatchLayout y = batch_layout(cap, ld, P);
-    if ((rc = ensure_points_block(h, y.bytes))) return rc;
-    char *block = (char *)h->pts.pinned;
+    if ((rc = grow(h, h->pts.pinned, y.bytes))) return rc;
+    char *block = (char *)h->pts.pinned.get();
     // one point through the single-point round, in its box where the batch has boxes
     auto single = [&](int p) -> int {
         int rc1;
@@ -412,20 +331,20 @@ static int round_csr_points_impl(sdpcut_ctx *h, const char *what, int32_t n_poin
     if ((rc = ensure_points_scores(h, P))) return rc;
     if ((rc = ensure_points_select(h, P, cap))) return rc;
     PointsBufs &b = h->pts;
-    TopkWs *ws = (TopkWs *)b.d_ws;
+    TopkWs *ws = (TopkWs *)b.d_ws.get();
     const int64_t ws_words = (int64_t)(sizeof(TopkWs) / 8), n = h->L + h->nb_vars;
     if ((rc = upload_points(h, P, points, point_ld, ws, bx_dev))) return rc;
     // the strong class of the combined strategy: counted by the score launch (a boxed batch: by strong_points_kernel behind its two
     // launches), point p into ws[p].strong_rep
     int64_t *strong = need == (SDPCUT_EIG | SDPCUT_NN) ? ws->strong_rep : nullptr;
     if ((rc = score_batch(h, need, P, bx_dev != nullptr, strong, ws_words))) return rc;
-    const double *eig = (need & SDPCUT_EIG) ? b.d_eig : nullptr, *obj = (need & SDPCUT_NN) ? b.d_obj : nullptr;
+    const double *eig = (need & SDPCUT_EIG) ? b.d_eig.get() : nullptr, *obj = (need & SDPCUT_NN) ? b.d_obj.get() : nullptr;
     hipLaunchKernelGGL(tk_points_kernel, dim3((unsigned)P), dim3(TK_SMALLSEL_THREADS), 0, h->stream, batch_mode(strat), cap, (int)h->N, (int)cap, eig,
-                       obj, h->N, ws, strat == SDPCUT_STRAT_COMB ? SDPCUT_BIG_M : 0.0, b.d_idx, b.d_score);
+                       obj, h->N, ws, strat == SDPCUT_STRAT_COMB ? SDPCUT_BIG_M : 0.0, b.d_idx.get(), b.d_score.get());
     HIP_TRY(h, hipGetLastError());
     for (int p = 0; p < P; ++p) std::memset(block + batch_point_offset(y, p), 0, 128);      // headers: counters, n_rows, nnz, give-up flag
-    rc = launch_round_csr_points(h, 0, P, cap, ld, ws->counters, ws_words, b.d_idx, b.d_score, b.d_pts, n, eig, h->N, b.d_agg, BATCH_AGG_WORDS,
-                                 b.pinned_dev, (int64_t)y.slice, ++h->round_serial);
+    rc = launch_round_csr_points(h, 0, P, cap, ld, ws->counters, ws_words, b.d_idx.get(), b.d_score.get(), b.d_pts.get(), n, eig, h->N, b.d_agg.get(), BATCH_AGG_WORDS,
+                                 b.pinned.dev(), (int64_t)y.slice, ++h->round_serial);
     if (rc) return rc;
     HIP_TRY(h, sdpcut_sync(h));      // the one wait of the batch (a faulted kernel surfaces here as an error)
 
@@ -447,8 +366,8 @@ static int round_csr_points_impl(sdpcut_ctx *h, const char *what, int32_t n_poin
         int64_t *hdr = (int64_t *)(block + batch_point_offset(y, p));
         hdr[8] = hdr[9] = hdr[10] = 0;
         ++h->stat_fallbacks;
-        rc = launch_round_csr_points(h, p, 1, cap, ld, ws->counters, ws_words, b.d_idx, b.d_score, b.d_pts, n, eig, h->N, b.d_agg, BATCH_AGG_WORDS,
-                                     b.pinned_dev, (int64_t)y.slice, ++h->round_serial);
+        rc = launch_round_csr_points(h, p, 1, cap, ld, ws->counters, ws_words, b.d_idx.get(), b.d_score.get(), b.d_pts.get(), n, eig, h->N, b.d_agg.get(), BATCH_AGG_WORDS,
+                                     b.pinned.dev(), (int64_t)y.slice, ++h->round_serial);
         if (rc) return rc;
     }
     if (!again.empty()) {
@@ -469,18 +388,7 @@ static int round_csr_points_impl(sdpcut_ctx *h, const char *what, int32_t n_poin
 // ------------------------------------------------------------------------------------------
 // Efficacy and the filtered round over a batch (sdpcut_efficacy_points, sdpcut_round_csr_points_diverse)
 
-static int ensure_points_eff(sdpcut_ctx *h, int P)
-{
-    PointsBufs &b = h->pts;
-    const size_t doubles = 3 * (size_t)P * (size_t)h->N;
-    if (b.eff_doubles >= doubles) return 0;
-    (void)hipFree(b.d_eff);
-    b.d_eff = nullptr;
-    b.eff_doubles = 0;
-    HIP_TRY(h, hipMalloc((void **)&b.d_eff, doubles * 8));
-    b.eff_doubles = doubles;
-    return 0;
-}
+static int ensure_points_eff(sdpcut_ctx *h, int P) { return grow(h, h->pts.d_eff, 3 * (size_t)P * (size_t)h->N); }
 
 static_assert(DIVP_MAX_POOL == BATCH_DIVERSE_MAX_POOL && BATCH_DIVERSE_MAX_POOL <= TK_TILE, "the route's pool limit is the filter kernel's and fits a head of the selection");
 
@@ -503,26 +411,9 @@ static DivPointsLayout div_points_layout(int P, int64_t pool, int64_t cap)
 
 static int ensure_points_div(sdpcut_ctx *h, int P, size_t bytes)
 {
-    PointsBufs &b = h->pts;
-    if (b.div_bytes < bytes) {
-        (void)hipFree(b.d_div);
-        b.d_div = nullptr;
-        b.div_bytes = 0;
-        HIP_TRY(h, hipMalloc(&b.d_div, bytes));
-        // (the row assembly reads an accepted head up to its capacity and uses its length only: never uninitialised memory)
-        HIP_TRY(h, hipMemsetAsync(b.d_div, 0, bytes, h->stream));
-        b.div_bytes = bytes;
-    }
-    if (b.div_sel_points < P) {
-        HIP_TRY(h, sdpcut_sync(h));
-        if (b.div_sel) (void)hipHostFree(b.div_sel);
-        b.div_sel = b.div_sel_dev = nullptr;
-        b.div_sel_points = 0;
-        HIP_TRY(h, hipHostMalloc(&b.div_sel, (size_t)P * 64, hipHostMallocMapped));
-        HIP_TRY(h, hipHostGetDevicePointer(&b.div_sel_dev, b.div_sel, 0));
-        b.div_sel_points = P;
-    }
-    return 0;
+    // (the row assembly reads an accepted head up to its capacity and uses its length only: never uninitialised memory)
+    const int rc = grow_zeroed(h, h->pts.d_div, bytes);
+    return rc ? rc : grow(h, h->pts.div_sel, (size_t)P * 64);
 }
 
 // A block of csr_layout(from, ld) with n_out entries, n_rows rows and nnz non-zeros in use becomes one of csr_layout(to, ld), to <
@@ -546,7 +437,7 @@ static void csr_block_shrink(char *block, int64_t from, int64_t to, int ld, int6
 static int efficacy_points_impl(sdpcut_ctx *h, int32_t n_points, const double *points, int64_t point_ld, double *eff_out, double *objpar_out,
                                 double *escore_out)
 {
-    int rc = check_points_args(h, n_points, points, point_ld);
+    int rc = check_batch_state(h, n_points, points, point_ld);
     if (rc) return rc;
     if (!eff_out && !objpar_out && !escore_out) return sdpcut_fail(h, SDPCUT_EINVAL, "sdpcut_efficacy_points: every output array is NULL");
     SDPCUT_NO_PENDING(h);
@@ -571,8 +462,8 @@ static int efficacy_points_impl(sdpcut_ctx *h, int32_t n_points, const double *p
     PointsBufs &b = h->pts;
     const int64_t n = h->L + h->nb_vars;
     if ((rc = score_batch(h, SDPCUT_EIG, P, false, nullptr, 0))) return rc;
-    double *d_e = b.d_eff, *d_p = d_e + (size_t)P * N, *d_s = d_p + (size_t)P * N;
-    if ((rc = launch_efficacy_points(h, P, b.d_pts, n, b.d_eig, h->N, d_e, d_p, d_s))) return rc;
+    double *d_e = b.d_eff.get(), *d_p = d_e + (size_t)P * N, *d_s = d_p + (size_t)P * N;
+    if ((rc = launch_efficacy_points(h, P, b.d_pts.get(), n, b.d_eig.get(), h->N, d_e, d_p, d_s))) return rc;
     if (eff_out) HIP_TRY(h, hipMemcpyAsync(eff_out, d_e, (size_t)P * N * 8, hipMemcpyDeviceToHost, h->stream));
     if (objpar_out) HIP_TRY(h, hipMemcpyAsync(objpar_out, d_p, (size_t)P * N * 8, hipMemcpyDeviceToHost, h->stream));
     if (escore_out) HIP_TRY(h, hipMemcpyAsync(escore_out, d_s, (size_t)P * N * 8, hipMemcpyDeviceToHost, h->stream));
@@ -586,7 +477,7 @@ static int round_csr_points_diverse_impl(sdpcut_ctx *h, int32_t n_points, const 
 {
     const char *what = "sdpcut_round_csr_points_diverse";
     if (!out) return sdpcut_fail(h, SDPCUT_EINVAL, "out is NULL");
-    int rc = check_points_args(h, n_points, points, point_ld);
+    int rc = check_batch_state(h, n_points, points, point_ld);
     if (rc) return rc;
     if (!batch_mode_diverse(strat))
         return sdpcut_fail(h, SDPCUT_EINVAL, std::string(what) + " serves strategies 1 (feasibility), 2 (optimality), 4 (combined) and 6 (efficacy)");
@@ -615,8 +506,8 @@ static int round_csr_points_diverse_impl(sdpcut_ctx *h, int32_t n_points, const 
     if (route == BATCH_FAST && (!batch_score_served(h, need, bx_dev != nullptr) || (strat == SDPCUT_STRAT_COMB && !h->auto_regime) || h->timing))
         route = BATCH_LOOP;
     const BatchLayout y = batch_layout(cap, ld, P);
-    if ((rc = ensure_points_block(h, y.bytes))) return rc;
-    char *block = (char *)h->pts.pinned;
+    if ((rc = grow(h, h->pts.pinned, y.bytes))) return rc;
+    char *block = (char *)h->pts.pinned.get();
     // one point through the single-point filtered round, in its box where the batch has boxes
     auto single = [&](int p) -> int {
         int rc1;
@@ -626,7 +517,7 @@ static int round_csr_points_diverse_impl(sdpcut_ctx *h, int32_t n_points, const 
         if (rc1) return rc1;
         if (o->cap > 0 && o->idx) {
             char *slot = block + batch_point_offset(y, p);
-            std::memcpy(slot, h->pinned, csr_layout(o->cap, o->row_ld).bytes);
+            std::memcpy(slot, h->pinned.get(), csr_layout(o->cap, o->row_ld).bytes);
             csr_out_from_block(slot, o);
         }
         return SDPCUT_OK;
@@ -643,42 +534,42 @@ static int round_csr_points_diverse_impl(sdpcut_ctx *h, int32_t n_points, const 
     if ((rc = ensure_points_div(h, P, dy.bytes))) return rc;
     if (by_eff && (rc = ensure_points_eff(h, P))) return rc;
     PointsBufs &b = h->pts;
-    TopkWs *ws = (TopkWs *)b.d_ws;
+    TopkWs *ws = (TopkWs *)b.d_ws.get();
     const int64_t ws_words = (int64_t)(sizeof(TopkWs) / 8), n = h->L + h->nb_vars;
     if ((rc = upload_points(h, P, points, point_ld, ws, bx_dev))) return rc;
     int64_t *strong = need == (SDPCUT_EIG | SDPCUT_NN) ? ws->strong_rep : nullptr;
     if ((rc = score_batch(h, need, P, bx_dev != nullptr, strong, ws_words))) return rc;
-    const double *eig = (need & SDPCUT_EIG) ? b.d_eig : nullptr, *obj = (need & SDPCUT_NN) ? b.d_obj : nullptr;
+    const double *eig = (need & SDPCUT_EIG) ? b.d_eig.get() : nullptr, *obj = (need & SDPCUT_NN) ? b.d_obj.get() : nullptr;
     if (by_eff) {      // strategy 2 on the efficacy score, as the single-point ranking runs it (common.h: MeasureAsObj)
-        double *d_e = b.d_eff, *d_p = d_e + (size_t)P * (size_t)h->N, *d_s = d_p + (size_t)P * (size_t)h->N;
-        if ((rc = launch_efficacy_points(h, P, b.d_pts, n, b.d_eig, h->N, d_e, d_p, d_s))) return rc;
+        double *d_e = b.d_eff.get(), *d_p = d_e + (size_t)P * (size_t)h->N, *d_s = d_p + (size_t)P * (size_t)h->N;
+        if ((rc = launch_efficacy_points(h, P, b.d_pts.get(), n, b.d_eig.get(), h->N, d_e, d_p, d_s))) return rc;
         obj = d_s;
     }
     const int64_t sel = sel_size < h->N ? sel_size : h->N;
     hipLaunchKernelGGL(tk_points_kernel, dim3((unsigned)P), dim3(TK_SMALLSEL_THREADS), 0, h->stream, batch_mode_diverse(strat), sel, (int)h->N, (int)pool,
-                       eig, obj, h->N, ws, strat == SDPCUT_STRAT_COMB ? SDPCUT_BIG_M : 0.0, b.d_idx, b.d_score);
+                       eig, obj, h->N, ws, strat == SDPCUT_STRAT_COMB ? SDPCUT_BIG_M : 0.0, b.d_idx.get(), b.d_score.get());
     HIP_TRY(h, hipGetLastError());
-    char *dv = (char *)b.d_div;
+    char *dv = (char *)b.d_div.get();
     DivPointsArgs A;
     A.pool = pool; A.cap = cap; A.quota = sel_size; A.max_parallel = max_parallel; A.compare = max_parallel < 1.0 ? 1 : 0;
-    A.sel_c4 = ws->counters; A.c4_stride = ws_words; A.idx = b.d_idx; A.score = b.d_score; A.idx_base = h->base; A.n_local = h->N;
-    A.set5 = h->d_set_orig; A.ks = h->d_k; A.vars = b.d_pts; A.vars_ld = n; A.nv = h->nb_vars; A.L = h->L; A.eig = eig; A.eig_ld = h->N;
+    A.sel_c4 = ws->counters; A.c4_stride = ws_words; A.idx = b.d_idx.get(); A.score = b.d_score.get(); A.idx_base = h->base; A.n_local = h->N;
+    A.set5 = h->d_set_orig.get(); A.ks = h->d_k.get(); A.vars = b.d_pts.get(); A.vars_ld = n; A.nv = h->nb_vars; A.L = h->L; A.eig = eig; A.eig_ld = h->N;
     A.row_coef = (double *)(dv + dy.coef); A.row_lam = (double *)(dv + dy.lam); A.row_ks = (int32_t *)(dv + dy.ks);
     A.acc_idx = (int64_t *)(dv + dy.acc_idx); A.acc_score = (double *)(dv + dy.acc_score); A.info = (int64_t *)(dv + dy.info);
-    A.sel_out = (int64_t *)b.div_sel_dev;
+    A.sel_out = (int64_t *)b.div_sel.dev();
     if ((rc = launch_div_points(h, P, A))) return rc;
     for (int p = 0; p < P; ++p) std::memset(block + batch_point_offset(y, p), 0, 128);
     // the accepted entries are a head like any other: the assembly reads its length from word 3 of the point's walk counts and
     // copies them into the slice's header
     auto assemble = [&](int p_first, int count) -> int {
-        return launch_round_csr_points(h, p_first, count, cap, ld, A.info, 8, A.acc_idx, A.acc_score, b.d_pts, n, eig, h->N, b.d_agg, BATCH_AGG_WORDS,
-                                       b.pinned_dev, (int64_t)y.slice, ++h->round_serial);
+        return launch_round_csr_points(h, p_first, count, cap, ld, A.info, 8, A.acc_idx, A.acc_score, b.d_pts.get(), n, eig, h->N, b.d_agg.get(), BATCH_AGG_WORDS,
+                                       b.pinned.dev(), (int64_t)y.slice, ++h->round_serial);
     };
     if ((rc = assemble(0, P))) return rc;
     HIP_TRY(h, sdpcut_sync(h));      // the one wait of the batch
 
     std::vector<int> redo, again;
-    const int64_t *selc = (const int64_t *)b.div_sel;
+    const int64_t *selc = (const int64_t *)b.div_sel.get();
     for (int p = 0; p < P; ++p) {
         const int64_t *hdr = (const int64_t *)(block + batch_point_offset(y, p));
         sdpcut_round_csr_t &o = out[p];

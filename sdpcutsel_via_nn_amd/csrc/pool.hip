@@ -42,52 +42,25 @@ static inline PoolOutLayout pool_out_layout(int64_t n, int64_t w)
     return y;
 }
 
-static void pool_free_arrays(PoolArrays *a)
-{
-    (void)hipFree(a->cols); (void)hipFree(a->vals); (void)hipFree(a->nnz); (void)hipFree(a->sense); (void)hipFree(a->state);
-    (void)hipFree(a->age); (void)hipFree(a->rhs); (void)hipFree(a->norm); (void)hipFree(a->serial);
-    *a = PoolArrays();
-}
-
 void free_pool_ws(sdpcut_ctx *h)
 {
-    PoolWs *w = (PoolWs *)h->pool;
-    if (!w) return;
-    pool_free_arrays(&w->a[0]);
-    pool_free_arrays(&w->a[1]);
-    (void)hipFree(w->key); (void)hipFree(w->rowid); (void)hipFree(w->key_out); (void)hipFree(w->row_out); (void)hipFree(w->mark);
-    (void)hipFree(w->flags); (void)hipFree(w->scan); (void)hipFree(w->ennz); (void)hipFree(w->eptr); (void)hipFree(w->cnt);
-    (void)hipFree(w->scan_tmp); (void)hipFree(w->d_pts); (void)hipFree(w->d_drop);
-    if (w->stage) (void)hipHostFree(w->stage);
-    if (w->out) (void)hipHostFree(w->out);
-    delete w;
+    delete (PoolWs *)h->pool;
     h->pool = nullptr;
 }
 
-static int pool_alloc_arrays(sdpcut_ctx *h, PoolArrays *a, size_t c)
+static int pool_alloc_arrays(sdpcut_ctx *h, PoolArraysOwn *o, PoolArrays *a, size_t c)
 {
-    HIP_TRY(h, hipMalloc((void **)&a->cols, c * 4 * POOL_LD));
-    HIP_TRY(h, hipMalloc((void **)&a->vals, c * 8 * POOL_LD));
-    HIP_TRY(h, hipMalloc((void **)&a->nnz, c * 4));
-    HIP_TRY(h, hipMalloc((void **)&a->sense, c * 4));
-    HIP_TRY(h, hipMalloc((void **)&a->state, c * 4));
-    HIP_TRY(h, hipMalloc((void **)&a->age, c * 4));
-    HIP_TRY(h, hipMalloc((void **)&a->rhs, c * 8));
-    HIP_TRY(h, hipMalloc((void **)&a->norm, c * 8));
-    HIP_TRY(h, hipMalloc((void **)&a->serial, c * 8));
-    return 0;
-}
-
-int pool_ensure_host(sdpcut_ctx *h, void **host, void **dev, size_t *have, size_t bytes)
-{
-    if (*have >= bytes) return 0;
-    HIP_TRY(h, sdpcut_sync(h));
-    if (*host) (void)hipHostFree(*host);
-    *host = *dev = nullptr;
-    *have = 0;
-    HIP_TRY(h, hipHostMalloc(host, bytes, hipHostMallocMapped));
-    HIP_TRY(h, hipHostGetDevicePointer(dev, *host, 0));
-    *have = bytes;
+    HIP_TRY(h, o->cols.reset(c * POOL_LD));
+    HIP_TRY(h, o->vals.reset(c * POOL_LD));
+    HIP_TRY(h, o->nnz.reset(c));
+    HIP_TRY(h, o->sense.reset(c));
+    HIP_TRY(h, o->state.reset(c));
+    HIP_TRY(h, o->age.reset(c));
+    HIP_TRY(h, o->rhs.reset(c));
+    HIP_TRY(h, o->norm.reset(c));
+    HIP_TRY(h, o->serial.reset(c));
+    a->cols = o->cols.get(); a->vals = o->vals.get(); a->nnz = o->nnz.get(); a->sense = o->sense.get(); a->state = o->state.get();
+    a->age = o->age.get(); a->rhs = o->rhs.get(); a->norm = o->norm.get(); a->serial = o->serial.get();
     return 0;
 }
 
@@ -288,11 +261,11 @@ int pool_get_ws(sdpcut_ctx *h, PoolWs **out)
 
 int pool_compact_enqueue(sdpcut_ctx *h, PoolWs *w, int64_t n)
 {
-    size_t tb = w->scan_tmp_bytes;
-    HIP_TRY(h, rocprim::exclusive_scan(w->scan_tmp, tb, w->flags, w->scan, 0ull, (size_t)(n + 1), rocprim::plus<unsigned long long>(),
+    size_t tb = w->scan_tmp.size();
+    HIP_TRY(h, rocprim::exclusive_scan(w->scan_tmp.get(), tb, w->flags.get(), w->scan.get(), 0ull, (size_t)(n + 1), rocprim::plus<unsigned long long>(),
                                        h->stream));
     hipLaunchKernelGGL(pool_compact_kernel, dim3(pool_grid(n + 1)), dim3(256), 0, h->stream, n, w->cap, w->a[w->cur], w->a[1 - w->cur],
-                       w->mark, w->scan);
+                       w->mark.get(), w->scan.get());
     HIP_TRY(h, hipGetLastError());
     return 0;
 }
@@ -312,26 +285,24 @@ int sdpcut_pool_create(sdpcut_handle h, int64_t capacity)
     if (!w) return sdpcut_fail(h, SDPCUT_ENOMEM, "out of host memory");
     h->pool = w;
     const size_t c = (size_t)capacity;
-    int rc = pool_alloc_arrays(h, &w->a[0], c);
-    if (!rc) rc = pool_alloc_arrays(h, &w->a[1], c);
+    int rc = pool_alloc_arrays(h, &w->own[0], &w->a[0], c);
+    if (!rc) rc = pool_alloc_arrays(h, &w->own[1], &w->a[1], c);
     if (rc) { free_pool_ws(h); return rc; }
-    hipError_t e = hipSuccess;
-    if (e == hipSuccess) e = hipMalloc((void **)&w->key, c * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&w->rowid, c * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&w->key_out, c * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&w->row_out, c * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&w->mark, c * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&w->flags, (c + 1) * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&w->scan, (c + 1) * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&w->ennz, (c + 1) * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&w->eptr, (c + 1) * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&w->cnt, PC_WORDS * 8);
+    hipError_t e = w->key.reset(c);
+    if (e == hipSuccess) e = w->rowid.reset(c);
+    if (e == hipSuccess) e = w->key_out.reset(c);
+    if (e == hipSuccess) e = w->row_out.reset(c);
+    if (e == hipSuccess) e = w->mark.reset(c);
+    if (e == hipSuccess) e = w->flags.reset(c + 1);
+    if (e == hipSuccess) e = w->scan.reset(c + 1);
+    if (e == hipSuccess) e = w->ennz.reset(c + 1);
+    if (e == hipSuccess) e = w->eptr.reset(c + 1);
+    if (e == hipSuccess) e = w->cnt.reset(PC_WORDS);
     size_t t1 = 0, t2 = 0;
     if (e == hipSuccess)
-        e = rocprim::exclusive_scan(nullptr, t1, w->flags, w->scan, 0ull, c + 1, rocprim::plus<unsigned long long>(), h->stream);
-    if (e == hipSuccess) e = rocprim::exclusive_scan(nullptr, t2, w->ennz, w->eptr, 0, c + 1, rocprim::plus<int32_t>(), h->stream);
-    w->scan_tmp_bytes = (t1 > t2 ? t1 : t2) + 256;
-    if (e == hipSuccess) e = hipMalloc(&w->scan_tmp, w->scan_tmp_bytes);
+        e = rocprim::exclusive_scan(nullptr, t1, w->flags.get(), w->scan.get(), 0ull, c + 1, rocprim::plus<unsigned long long>(), h->stream);
+    if (e == hipSuccess) e = rocprim::exclusive_scan(nullptr, t2, w->ennz.get(), w->eptr.get(), 0, c + 1, rocprim::plus<int32_t>(), h->stream);
+    if (e == hipSuccess) e = w->scan_tmp.reset((t1 > t2 ? t1 : t2) + 256);
     if (e != hipSuccess) {
         free_pool_ws(h);
         return sdpcut_fail(h, SDPCUT_EHIP, std::string("sdpcut_pool_create: ") + hipGetErrorString(e));
@@ -382,15 +353,15 @@ int sdpcut_pool_add_csr(sdpcut_handle h, int64_t n_rows, const int32_t *indptr, 
     // the staged block: values | rhs | indptr (rebased to 0) | indices | sense
     const size_t o_val = 0, o_rhs = o_val + (size_t)nnz * 8, o_ptr = o_rhs + (size_t)n_rows * 8, o_ind = o_ptr + (size_t)(n_rows + 1) * 4,
                  o_sense = o_ind + (size_t)nnz * 4, bytes = o_sense + (size_t)n_rows * 4;
-    rc = pool_ensure_host(h, &w->stage, &w->stage_dev, &w->stage_bytes, bytes);
+    rc = grow(h, w->stage, bytes);
     if (rc) return rc;
-    char *s = (char *)w->stage;
+    char *s = (char *)w->stage.get();
     std::memcpy(s + o_val, values + lo, (size_t)nnz * 8);
     std::memcpy(s + o_rhs, rhs, (size_t)n_rows * 8);
     for (int64_t i = 0; i <= n_rows; ++i) ((int32_t *)(s + o_ptr))[i] = (int32_t)(indptr[i] - lo);
     std::memcpy(s + o_ind, indices + lo, (size_t)nnz * 4);
     for (int64_t i = 0; i < n_rows; ++i) ((int32_t *)(s + o_sense))[i] = sense ? sense[i] : 1;
-    const char *d = (const char *)w->stage_dev;
+    const char *d = (const char *)w->stage.dev();
     hipLaunchKernelGGL(pool_append_kernel, dim3(pool_grid(n_rows)), dim3(256), 0, h->stream, n_rows, w->n, w->cap, w->next_serial,
                        (const int32_t *)(d + o_ptr), (const int32_t *)(d + o_ind), (const double *)(d + o_val), (const double *)(d + o_rhs),
                        (const int32_t *)(d + o_sense), w->a[w->cur]);
@@ -425,36 +396,36 @@ int sdpcut_pool_step(sdpcut_handle h, const double *vars_values, const sdpcut_po
     HIP_TRY(h, hipSetDevice(h->device));
     const int64_t wmax = params->max_return < n ? params->max_return : n;
     const PoolOutLayout y = pool_out_layout(n, wmax);
-    rc = pool_ensure_host(h, &w->out, &w->out_dev, &w->out_bytes, y.bytes);
+    rc = grow(h, w->out, y.bytes);
     if (rc) return rc;
     if (wmax > 0 && (rc = ensure_rank_ws(h, n))) return rc;      // (may wait for the stream: before anything is enqueued)
     PoolArrays &a = w->a[w->cur], &b = w->a[1 - w->cur];
     const int g = pool_grid(n + 1);
-    HIP_TRY(h, hipMemsetAsync(w->cnt, 0, PC_WORDS * 8, h->stream));
-    hipLaunchKernelGGL(pool_eval_kernel, dim3(g), dim3(256), 0, h->stream, n, w->cap, w->ncols, h->d_vars, params->tight_tol,
-                       params->viol_tol, params->max_age, a, w->key, w->rowid, w->mark, w->cnt);
+    HIP_TRY(h, hipMemsetAsync(w->cnt.get(), 0, PC_WORDS * 8, h->stream));
+    hipLaunchKernelGGL(pool_eval_kernel, dim3(g), dim3(256), 0, h->stream, n, w->cap, w->ncols, h->d_vars.get(), params->tight_tol,
+                       params->viol_tol, params->max_age, a, w->key.get(), w->rowid.get(), w->mark.get(), w->cnt.get());
     HIP_TRY(h, hipGetLastError());
     if (wmax > 0) {
         // (key descending, row ascending) = (key descending, serial ascending): the rows are in ascending serial order
-        rc = merge_topk_on_device(h, n, w->key, nullptr, w->rowid, wmax, w->key_out, w->row_out);
+        rc = merge_topk_on_device(h, n, w->key.get(), nullptr, w->rowid.get(), wmax, w->key_out.get(), w->row_out.get());
         if (rc) return rc;
     }
-    hipLaunchKernelGGL(pool_enter_kernel, dim3(pool_grid(wmax + 1)), dim3(256), 0, h->stream, wmax, n, w->row_out, w->cnt, a, w->mark,
-                       w->ennz);
-    hipLaunchKernelGGL(pool_age_kernel, dim3(g), dim3(256), 0, h->stream, n, params->drop_age, a, w->mark, w->flags, w->cnt);
+    hipLaunchKernelGGL(pool_enter_kernel, dim3(pool_grid(wmax + 1)), dim3(256), 0, h->stream, wmax, n, w->row_out.get(), w->cnt.get(), a, w->mark.get(),
+                       w->ennz.get());
+    hipLaunchKernelGGL(pool_age_kernel, dim3(g), dim3(256), 0, h->stream, n, params->drop_age, a, w->mark.get(), w->flags.get(), w->cnt.get());
     HIP_TRY(h, hipGetLastError());
-    size_t tb = w->scan_tmp_bytes;
-    HIP_TRY(h, rocprim::exclusive_scan(w->scan_tmp, tb, w->flags, w->scan, 0ull, (size_t)(n + 1), rocprim::plus<unsigned long long>(),
+    size_t tb = w->scan_tmp.size();
+    HIP_TRY(h, rocprim::exclusive_scan(w->scan_tmp.get(), tb, w->flags.get(), w->scan.get(), 0ull, (size_t)(n + 1), rocprim::plus<unsigned long long>(),
                                        h->stream));
-    tb = w->scan_tmp_bytes;
-    HIP_TRY(h, rocprim::exclusive_scan(w->scan_tmp, tb, w->ennz, w->eptr, 0, (size_t)(wmax + 1), rocprim::plus<int32_t>(), h->stream));
+    tb = w->scan_tmp.size();
+    HIP_TRY(h, rocprim::exclusive_scan(w->scan_tmp.get(), tb, w->ennz.get(), w->eptr.get(), 0, (size_t)(wmax + 1), rocprim::plus<int32_t>(), h->stream));
     const int64_t lanes = n > wmax ? n : wmax;
-    hipLaunchKernelGGL(pool_emit_kernel, dim3(pool_grid(lanes)), dim3(256), 0, h->stream, n, wmax, w->cap, a, w->mark, w->scan, w->row_out,
-                       w->key_out, w->eptr, w->cnt, (char *)w->out_dev, y);
-    hipLaunchKernelGGL(pool_compact_kernel, dim3(g), dim3(256), 0, h->stream, n, w->cap, a, b, w->mark, w->scan);
+    hipLaunchKernelGGL(pool_emit_kernel, dim3(pool_grid(lanes)), dim3(256), 0, h->stream, n, wmax, w->cap, a, w->mark.get(), w->scan.get(), w->row_out.get(),
+                       w->key_out.get(), w->eptr.get(), w->cnt.get(), (char *)w->out.dev(), y);
+    hipLaunchKernelGGL(pool_compact_kernel, dim3(g), dim3(256), 0, h->stream, n, w->cap, a, b, w->mark.get(), w->scan.get());
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, sdpcut_sync(h));      // the step's one host wait
-    const char *blk = (const char *)w->out;
+    const char *blk = (const char *)w->out.get();
     const int64_t *hdr = (const int64_t *)blk;
     out->n_violated = hdr[0];
     out->n_leave = hdr[1];

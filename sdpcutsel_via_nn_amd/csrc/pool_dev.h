@@ -12,6 +12,7 @@ enum { PM_LP = 0, PM_LEAVE = 1, PM_PARKED = 2, PM_VIOLATED = 3, PM_ENTER = 4, PM
 // device counters of a step (PoolWs::cnt); sdpcut_pool_drop counts the removed LP rows in word 0 and the removed parked rows in word 1
 enum { PC_VIOLATED = 0, PC_LEAVE = 1, PC_DROP = 2, PC_WORDS = 4 };
 
+// one set of the pool's arrays as the kernels take it (by value): views of a PoolArraysOwn
 struct PoolArrays {
     int32_t *cols = nullptr;    // [POOL_LD][cap]
     double *vals = nullptr;     // [POOL_LD][cap]
@@ -20,36 +21,37 @@ struct PoolArrays {
     int64_t *serial = nullptr;                                                    // [cap]
 };
 
+struct PoolArraysOwn {
+    DevBuf<int32_t> cols, nnz, sense, state, age;
+    DevBuf<double> vals, rhs, norm;
+    DevBuf<int64_t> serial;
+};
+
 struct PoolWs {
     int64_t cap = 0, n = 0, next_serial = 0, n_lp = 0, n_parked = 0;
     int64_t ncols = 0;            // nb_lifted + nb_vars of the instance the columns were checked against
-    PoolArrays a[2];              // the live set and the target of the next compaction
+    PoolArraysOwn own[2];         // allocated once by sdpcut_pool_create ...
+    PoolArrays a[2];              // ... and their views: the live set and the target of the next compaction
     int cur = 0;
-    double *key = nullptr;        // [cap] ranking key of a violated parked row, -inf otherwise
-    int64_t *rowid = nullptr;     // [cap] 0 .. n-1 (ascending row = ascending serial)
-    double *key_out = nullptr;    // [cap] keys of the ranked head
-    int64_t *row_out = nullptr;   // [cap] rows of the ranked head
-    int32_t *mark = nullptr;      // [cap] PM_*
-    unsigned long long *flags = nullptr, *scan = nullptr;   // [cap + 1] leave | dropped << 32 and its exclusive scan
-    int32_t *ennz = nullptr, *eptr = nullptr;               // [cap + 1] nnz of the entering rows in rank order and its exclusive scan
-    unsigned long long *cnt = nullptr;                      // [PC_WORDS]
-    void *scan_tmp = nullptr;
-    size_t scan_tmp_bytes = 0;
-    void *stage = nullptr, *stage_dev = nullptr;            // pinned staging of sdpcut_pool_add_csr, sdpcut_pool_separate_points, sdpcut_pool_drop
-    size_t stage_bytes = 0;
-    void *out = nullptr, *out_dev = nullptr;                // pinned block of sdpcut_pool_step / sdpcut_pool_separate_points
-    size_t out_bytes = 0;
+    DevBuf<double> key;           // [cap] ranking key of a violated parked row, -inf otherwise
+    DevBuf<int64_t> rowid;        // [cap] 0 .. n-1 (ascending row = ascending serial)
+    DevBuf<double> key_out;       // [cap] keys of the ranked head
+    DevBuf<int64_t> row_out;      // [cap] rows of the ranked head
+    DevBuf<int32_t> mark;         // [cap] PM_*
+    DevBuf<unsigned long long> flags, scan;   // [cap + 1] leave | dropped << 32 and its exclusive scan
+    DevBuf<int32_t> ennz, eptr;               // [cap + 1] nnz of the entering rows in rank order and its exclusive scan
+    DevBuf<unsigned long long> cnt;           // [PC_WORDS]
+    DevBuf<char> scan_tmp;
+    HostBuf stage{true};          // mapped staging of sdpcut_pool_add_csr, sdpcut_pool_separate_points, sdpcut_pool_drop
+    HostBuf out{true};            // mapped block of sdpcut_pool_step / sdpcut_pool_separate_points
     // pool_points.hip: the points of a separation and the serials of an eviction on the device -- the pool's own, so that neither
     // call touches the handle's LP point (grown on demand, freed with the pool)
-    double *d_pts = nullptr;
-    size_t pts_doubles = 0;
-    int64_t *d_drop = nullptr;
-    size_t drop_words = 0;
+    DevBuf<double> d_pts;
+    DevBuf<int64_t> d_drop;
 };
 
 // pool.hip
 int pool_get_ws(sdpcut_ctx *h, PoolWs **out);      // the handle's pool, or SDPCUT_ESTATE: none / made for another instance
-int pool_ensure_host(sdpcut_ctx *h, void **host, void **dev, size_t *have, size_t bytes);
 // flags[0 .. n] -> its scan, then the stable compaction of the rows not marked PM_DROP into the other set of arrays (enqueued; the
 // caller waits and swaps the sets when scan[n] >> 32 rows went)
 int pool_compact_enqueue(sdpcut_ctx *h, PoolWs *w, int64_t n);

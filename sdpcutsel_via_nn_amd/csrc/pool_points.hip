@@ -245,19 +245,6 @@ __global__ __launch_bounds__(256) void pool_drop_mark_kernel(int64_t n, int64_t 
 }
 
 // ------------------------------------------------------------------------------------------
-template <typename T>
-static int pool_grow_device(sdpcut_ctx *h, T **ptr, size_t *have, size_t want)
-{
-    if (*have >= want) return 0;
-    HIP_TRY(h, sdpcut_sync(h));
-    (void)hipFree(*ptr);
-    *ptr = nullptr;
-    *have = 0;
-    HIP_TRY(h, hipMalloc((void **)ptr, want * sizeof(T)));
-    *have = want;
-    return 0;
-}
-
 extern "C" {
 
 int sdpcut_pool_separate_points(sdpcut_handle h, int32_t n_points, const double *points, int64_t point_ld, uint32_t state_mask,
@@ -269,10 +256,7 @@ int sdpcut_pool_separate_points(sdpcut_handle h, int32_t n_points, const double 
     int rc = pool_get_ws(h, &w);
     if (rc) return rc;
     SDPCUT_NO_PENDING(h);
-    if (n_points < 1 || n_points > SDPCUT_BATCH_MAX_POINTS)
-        return sdpcut_fail(h, SDPCUT_EINVAL, "n_points must be 1 .. SDPCUT_BATCH_MAX_POINTS (" + std::to_string(SDPCUT_BATCH_MAX_POINTS) + ")");
-    if (point_ld < w->ncols) return sdpcut_fail(h, SDPCUT_EINVAL, "point_ld must be at least L + n");
-    if (!points) return sdpcut_fail(h, SDPCUT_EINVAL, "points is NULL");
+    if ((rc = check_point_batch(h, "", n_points, points, point_ld, w->ncols))) return rc;
     if (!out) return sdpcut_fail(h, SDPCUT_EINVAL, "out is NULL");
     if (state_mask == 0 || (state_mask & ~(uint32_t)(SDPCUT_POOL_SEP_LP | SDPCUT_POOL_SEP_PARKED)))
         return sdpcut_fail(h, SDPCUT_EINVAL, std::string(what) + ": state_mask must be SDPCUT_POOL_SEP_LP, SDPCUT_POOL_SEP_PARKED or both");
@@ -291,29 +275,29 @@ int sdpcut_pool_separate_points(sdpcut_handle h, int32_t n_points, const double 
     std::memset(out, 0, (size_t)P * sizeof(*out));
     if (n == 0) return SDPCUT_OK;
     HIP_TRY(h, hipSetDevice(h->device));
-    if ((rc = pool_ensure_host(h, &w->out, &w->out_dev, &w->out_bytes, y.slice * (size_t)P))) return rc;
-    if ((rc = pool_ensure_host(h, &w->stage, &w->stage_dev, &w->stage_bytes, (size_t)P * (size_t)m * 8))) return rc;
-    if ((rc = pool_grow_device(h, &w->d_pts, &w->pts_doubles, (size_t)P * (size_t)m))) return rc;
-    double *st = (double *)w->stage;
-    for (int p = 0; p < P; ++p) std::memcpy(st + (size_t)p * m, points + (size_t)p * point_ld, (size_t)m * 8);
-    HIP_TRY(h, hipMemcpyAsync(w->d_pts, st, (size_t)P * m * 8, hipMemcpyHostToDevice, h->stream));
+    if ((rc = grow(h, w->out, y.slice * (size_t)P))) return rc;
+    if ((rc = grow(h, w->stage, (size_t)P * (size_t)m * 8))) return rc;
+    if ((rc = grow(h, w->d_pts, (size_t)P * (size_t)m))) return rc;
+    double *st = (double *)w->stage.get();
+    pack_points(st, P, points, point_ld, m);
+    HIP_TRY(h, hipMemcpyAsync(w->d_pts.get(), st, (size_t)P * m * 8, hipMemcpyHostToDevice, h->stream));
     PoolPointsArgs A;
     A.n = n;
     A.cap = w->cap;
     A.ncols = m;
     A.a = w->a[w->cur];
-    A.pts = w->d_pts;
+    A.pts = w->d_pts.get();
     A.pts_stride = m;
     A.state_mask = state_mask;
     A.viol_tol = viol_tol;
     A.max_return = max_return;
     A.wcap = wcap;
-    A.block = (char *)w->out_dev;
+    A.block = (char *)w->out.dev();
     A.slice = (int64_t)y.slice;
     hipLaunchKernelGGL(pool_points_kernel, dim3((unsigned)P), dim3(POOL_POINTS_THREADS), 0, h->stream, A);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, sdpcut_sync(h));      // the one wait of the call
-    const char *blk = (const char *)w->out;
+    const char *blk = (const char *)w->out.get();
     for (int p = 0; p < P; ++p) {
         const char *b = blk + y.slice * (size_t)p;
         const int64_t *hdr = (const int64_t *)b;
@@ -353,19 +337,19 @@ int sdpcut_pool_drop(sdpcut_handle h, int64_t n, const int64_t *serials, int64_t
     const int64_t m = (int64_t)list.size(), rows = w->n;
     if (m == 0 || rows == 0) return SDPCUT_OK;
     HIP_TRY(h, hipSetDevice(h->device));
-    if ((rc = pool_ensure_host(h, &w->stage, &w->stage_dev, &w->stage_bytes, (size_t)m * 8))) return rc;
-    if ((rc = pool_ensure_host(h, &w->out, &w->out_dev, &w->out_bytes, 64))) return rc;
-    if ((rc = pool_grow_device(h, &w->d_drop, &w->drop_words, (size_t)m))) return rc;
-    std::memcpy(w->stage, list.data(), (size_t)m * 8);
-    HIP_TRY(h, hipMemcpyAsync(w->d_drop, w->stage, (size_t)m * 8, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemsetAsync(w->cnt, 0, PC_WORDS * 8, h->stream));
-    hipLaunchKernelGGL(pool_drop_mark_kernel, dim3((unsigned)((rows + 1 + 255) / 256)), dim3(256), 0, h->stream, rows, m, w->d_drop, w->a[w->cur],
-                       w->mark, w->flags, w->cnt);
+    if ((rc = grow(h, w->stage, (size_t)m * 8))) return rc;
+    if ((rc = grow(h, w->out, 64))) return rc;
+    if ((rc = grow(h, w->d_drop, (size_t)m))) return rc;
+    std::memcpy(w->stage.get(), list.data(), (size_t)m * 8);
+    HIP_TRY(h, hipMemcpyAsync(w->d_drop.get(), w->stage.get(), (size_t)m * 8, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemsetAsync(w->cnt.get(), 0, PC_WORDS * 8, h->stream));
+    hipLaunchKernelGGL(pool_drop_mark_kernel, dim3((unsigned)((rows + 1 + 255) / 256)), dim3(256), 0, h->stream, rows, m, w->d_drop.get(), w->a[w->cur],
+                       w->mark.get(), w->flags.get(), w->cnt.get());
     HIP_TRY(h, hipGetLastError());
     if ((rc = pool_compact_enqueue(h, w, rows))) return rc;
-    HIP_TRY(h, hipMemcpyAsync(w->out, w->cnt, PC_WORDS * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(w->out.get(), w->cnt.get(), PC_WORDS * 8, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, sdpcut_sync(h));      // the one wait of the call
-    const unsigned long long *c = (const unsigned long long *)w->out;
+    const unsigned long long *c = (const unsigned long long *)w->out.get();
     const int64_t gone_lp = (int64_t)c[0], gone_parked = (int64_t)c[1], gone = gone_lp + gone_parked;
     if (gone > 0) w->cur = 1 - w->cur;
     w->n = rows - gone;

@@ -132,25 +132,11 @@ __global__ void gather_scores_kernel(int64_t count, int64_t base, int64_t n, con
     if (obj_out) obj_out[i] = ok ? obj[c] : __builtin_nan("");
 }
 
-void free_rank_ws(sdpcut_ctx *h)
-{
-    hipFree(h->d_key_a); hipFree(h->d_key_b); hipFree(h->d_val_a); hipFree(h->d_val_b);
-    hipFree(h->d_flag); hipFree(h->d_scan); hipFree(h->d_tmp);
-    h->d_key_a = h->d_key_b = nullptr; h->d_val_a = h->d_val_b = nullptr;
-    h->d_flag = h->d_scan = nullptr; h->d_tmp = nullptr; h->tmp_bytes = 0; h->ws_n = 0; h->key_n = 0;
-}
-
 // the key array alone (8 B per candidate): all that the head selection (topk.hip) may need of this workspace -- a round whose score
 // kernels counted the leading digit does not even read it
 int ensure_key_ws(sdpcut_ctx *h, int64_t n)
 {
-    if (n <= h->key_n) return 0;
-    (void)hipFree(h->d_key_a);
-    h->d_key_a = nullptr;
-    h->key_n = 0;
-    HIP_TRY(h, hipMalloc((void **)&h->d_key_a, (size_t)(n < 1 ? 1 : n) * 8));
-    h->key_n = n;
-    return 0;
+    return grow(h, h->d_key_a, (size_t)(n < 0 ? 0 : n));
 }
 
 // the whole workspace of the FULL-LIST ranking (~50 B per candidate: two key and two payload arrays, flags, scan, rocPRIM's
@@ -163,25 +149,25 @@ int ensure_rank_ws(sdpcut_ctx *h, int64_t n)
     int rc = ensure_key_ws(h, n);
     if (rc) return rc;
     if (n <= h->ws_n) return 0;
-    hipFree(h->d_key_b); hipFree(h->d_val_a); hipFree(h->d_val_b); hipFree(h->d_flag); hipFree(h->d_scan); hipFree(h->d_tmp);
-    h->d_key_b = nullptr; h->d_val_a = h->d_val_b = nullptr; h->d_flag = h->d_scan = nullptr; h->d_tmp = nullptr;
+    HIP_TRY(h, sdpcut_sync(h));
+    h->d_key_b.release(); h->d_val_a.release(); h->d_val_b.release(); h->d_flag.release(); h->d_scan.release(); h->d_tmp.release();
     h->tmp_bytes = 0; h->ws_n = 0;
     const size_t nn = (size_t)(n < 1 ? 1 : n);
-    HIP_TRY(h, hipMalloc((void **)&h->d_key_b, nn * 8));
-    HIP_TRY(h, hipMalloc((void **)&h->d_val_a, nn * 8));   // 8 B/entry: also used as u64 by the merge
-    HIP_TRY(h, hipMalloc((void **)&h->d_val_b, nn * 8));
-    HIP_TRY(h, hipMalloc((void **)&h->d_flag, nn * 4));
-    HIP_TRY(h, hipMalloc((void **)&h->d_scan, nn * 4));
+    HIP_TRY(h, h->d_key_b.reset(nn));
+    HIP_TRY(h, h->d_val_a.reset(2 * nn));   // 8 B/entry: also used as u64 by the merge
+    HIP_TRY(h, h->d_val_b.reset(2 * nn));
+    HIP_TRY(h, h->d_flag.reset(nn));
+    HIP_TRY(h, h->d_scan.reset(nn));
     size_t t1 = 0, t2 = 0, t3 = 0;
-    HIP_TRY(h, rocprim::radix_sort_pairs_desc(nullptr, t1, h->d_key_a, h->d_key_b, h->d_val_a, h->d_val_b, nn,
+    HIP_TRY(h, rocprim::radix_sort_pairs_desc(nullptr, t1, h->d_key_a.get(), h->d_key_b.get(), h->d_val_a.get(), h->d_val_b.get(), nn,
                                               0, 64, h->stream));
-    HIP_TRY(h, rocprim::radix_sort_pairs(nullptr, t2, h->d_key_a, h->d_key_b, (uint64_t *)h->d_val_a,
-                                         (uint64_t *)h->d_val_b, nn, 0, 64, h->stream));
-    HIP_TRY(h, rocprim::exclusive_scan(nullptr, t3, h->d_flag, h->d_scan, 0, nn, rocprim::plus<int32_t>(),
+    HIP_TRY(h, rocprim::radix_sort_pairs(nullptr, t2, h->d_key_a.get(), h->d_key_b.get(), (uint64_t *)h->d_val_a.get(),
+                                         (uint64_t *)h->d_val_b.get(), nn, 0, 64, h->stream));
+    HIP_TRY(h, rocprim::exclusive_scan(nullptr, t3, h->d_flag.get(), h->d_scan.get(), 0, nn, rocprim::plus<int32_t>(),
                                        h->stream));
     size_t t = t1 > t2 ? t1 : t2;
     t = t > t3 ? t : t3;
-    HIP_TRY(h, hipMalloc(&h->d_tmp, t < 256 ? 256 : t));
+    HIP_TRY(h, h->d_tmp.reset(t < 256 ? 256 : t));
     h->tmp_bytes = t;
     h->ws_n = n;
     return 0;
@@ -314,33 +300,33 @@ int rank_on_device(sdpcut_ctx *h, int strat, int64_t sel_size, int64_t max_out, 
             return 0;
         }
     }
-    HIP_TRY(h, hipMemsetAsync(h->d_counters, 0, 8 * sizeof(int64_t), h->stream));
-    const uint64_t *fkey = h->d_key_b;
-    const uint32_t *fval = h->d_val_b;
+    HIP_TRY(h, hipMemsetAsync(h->d_counters.get(), 0, 8 * sizeof(int64_t), h->stream));
+    const uint64_t *fkey = h->d_key_b.get();
+    const uint32_t *fval = h->d_val_b.get();
     if (n > 0) {
-        const double *eig = (h->scored & SDPCUT_EIG) ? h->d_eig : nullptr;
+        const double *eig = (h->scored & SDPCUT_EIG) ? h->d_eig.get() : nullptr;
         hipLaunchKernelGGL(keys_first_kernel, dim3(nblk(n)), dim3(256), 0, h->stream, strat, n, eig, h->d_obj,
-                           h->d_key_a, h->d_val_a, h->d_counters);
+                           h->d_key_a.get(), h->d_val_a.get(), h->d_counters.get());
         size_t tb = h->tmp_bytes;
-        HIP_TRY(h, rocprim::radix_sort_pairs_desc(h->d_tmp, tb, h->d_key_a, h->d_key_b, h->d_val_a, h->d_val_b,
+        HIP_TRY(h, rocprim::radix_sort_pairs_desc(h->d_tmp.get(), tb, h->d_key_a.get(), h->d_key_b.get(), h->d_val_a.get(), h->d_val_b.get(),
                                                   (size_t)n, 0, 64, h->stream));
         if (strat == SDPCUT_STRAT_COMB) {
-            hipLaunchKernelGGL(comb_flag_kernel, dim3(nblk(n)), dim3(256), 0, h->stream, n, h->d_key_b, h->d_val_b,
-                               h->d_eig, h->d_flag);
+            hipLaunchKernelGGL(comb_flag_kernel, dim3(nblk(n)), dim3(256), 0, h->stream, n, h->d_key_b.get(), h->d_val_b.get(),
+                               h->d_eig.get(), h->d_flag.get());
             tb = h->tmp_bytes;
-            HIP_TRY(h, rocprim::exclusive_scan(h->d_tmp, tb, h->d_flag, h->d_scan, 0, (size_t)n,
+            HIP_TRY(h, rocprim::exclusive_scan(h->d_tmp.get(), tb, h->d_flag.get(), h->d_scan.get(), 0, (size_t)n,
                                                rocprim::plus<int32_t>(), h->stream));
-            hipLaunchKernelGGL(comb_keys_kernel, dim3(nblk(n)), dim3(256), 0, h->stream, n, sel_size, h->d_key_b,
-                               h->d_val_b, h->d_flag, h->d_scan, h->d_eig, h->d_key_a, h->d_counters);
+            hipLaunchKernelGGL(comb_keys_kernel, dim3(nblk(n)), dim3(256), 0, h->stream, n, sel_size, h->d_key_b.get(),
+                               h->d_val_b.get(), h->d_flag.get(), h->d_scan.get(), h->d_eig.get(), h->d_key_a.get(), h->d_counters.get());
             // second stable sort: payload keeps first-sort order among equal new scores (:625)
             tb = h->tmp_bytes;
-            HIP_TRY(h, hipMemcpyAsync(h->d_val_a, h->d_val_b, (size_t)n * 4, hipMemcpyDeviceToDevice, h->stream));
-            HIP_TRY(h, rocprim::radix_sort_pairs_desc(h->d_tmp, tb, h->d_key_a, h->d_key_b, h->d_val_a, h->d_val_b,
+            HIP_TRY(h, hipMemcpyAsync(h->d_val_a.get(), h->d_val_b.get(), (size_t)n * 4, hipMemcpyDeviceToDevice, h->stream));
+            HIP_TRY(h, rocprim::radix_sort_pairs_desc(h->d_tmp.get(), tb, h->d_key_a.get(), h->d_key_b.get(), h->d_val_a.get(), h->d_val_b.get(),
                                                       (size_t)n, 0, 64, h->stream));
         }
         HIP_TRY(h, hipGetLastError());
     }
-    HIP_TRY(h, hipMemcpyAsync(cnt, h->d_counters, 8 * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(cnt, h->d_counters.get(), 8 * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, sdpcut_sync(h));
     // :654 rank_list[0:nb_violated]; class-restricted rankings list their class only
     const int64_t total = (strat == SDPCUT_STRAT_FEAS || strat == SDPCUT_PART_STRONG) ? cnt[0] : n;
@@ -369,8 +355,8 @@ int rank_on_device(sdpcut_ctx *h, int strat, int64_t sel_size, int64_t max_out, 
 int rank_fetch_on_device(sdpcut_ctx *h, int64_t offset, int64_t count, int64_t *d_idx_out, double *d_score_out)
 {
     if (count <= 0) return 0;
-    hipLaunchKernelGGL(emit_kernel, dim3(nblk(count)), dim3(256), 0, h->stream, count, h->base, h->d_key_b + offset,
-                       h->d_val_b + offset, d_idx_out, d_score_out);
+    hipLaunchKernelGGL(emit_kernel, dim3(nblk(count)), dim3(256), 0, h->stream, count, h->base, h->d_key_b.get() + offset,
+                       h->d_val_b.get() + offset, d_idx_out, d_score_out);
     HIP_TRY(h, hipGetLastError());
     return 0;
 }
@@ -382,24 +368,24 @@ int merge_topk_on_device(sdpcut_ctx *h, int64_t count, const double *d_scores, c
     h->last_total = -1;   // the merge reuses the ranking workspace
     int rc = ensure_rank_ws(h, count);
     if (rc) return rc;
-    uint64_t *ka = h->d_key_a, *kb = h->d_key_b;
-    uint32_t *pa = h->d_val_a, *pb = h->d_val_b;
+    uint64_t *ka = h->d_key_a.get(), *kb = h->d_key_b.get();
+    uint32_t *pa = h->d_val_a.get(), *pb = h->d_val_b.get();
     const int g = nblk(count);
     size_t tb = h->tmp_bytes;
     // 1) ascending by id
     hipLaunchKernelGGL(merge_idkey_kernel, dim3(g), dim3(256), 0, h->stream, count, d_ids, ka, pa);
-    HIP_TRY(h, rocprim::radix_sort_pairs(h->d_tmp, tb, ka, kb, pa, pb, (size_t)count, 0, 64, h->stream));
+    HIP_TRY(h, rocprim::radix_sort_pairs(h->d_tmp.get(), tb, ka, kb, pa, pb, (size_t)count, 0, 64, h->stream));
     // 2) stable descending by the secondary key (first-sort order of the combined strategy)
     if (d_secondary) {
         hipLaunchKernelGGL(merge_gatherkey_kernel, dim3(g), dim3(256), 0, h->stream, count, d_secondary, pb, ka);
         tb = h->tmp_bytes;
-        HIP_TRY(h, rocprim::radix_sort_pairs_desc(h->d_tmp, tb, ka, kb, pb, pa, (size_t)count, 0, 64, h->stream));
+        HIP_TRY(h, rocprim::radix_sort_pairs_desc(h->d_tmp.get(), tb, ka, kb, pb, pa, (size_t)count, 0, 64, h->stream));
         uint32_t *t = pa; pa = pb; pb = t;
     }
     // 3) stable descending by score
     hipLaunchKernelGGL(merge_gatherkey_kernel, dim3(g), dim3(256), 0, h->stream, count, d_scores, pb, ka);
     tb = h->tmp_bytes;
-    HIP_TRY(h, rocprim::radix_sort_pairs_desc(h->d_tmp, tb, ka, kb, pb, pa, (size_t)count, 0, 64, h->stream));
+    HIP_TRY(h, rocprim::radix_sort_pairs_desc(h->d_tmp.get(), tb, ka, kb, pb, pa, (size_t)count, 0, 64, h->stream));
     const int64_t w = count < max_out ? count : max_out;
     hipLaunchKernelGGL(merge_emit_kernel, dim3(nblk(w)), dim3(256), 0, h->stream, w, pa, d_scores, d_ids,
                        d_score_out, d_id_out);
@@ -411,7 +397,7 @@ int gather_scores_on_device(sdpcut_ctx *h, int64_t count, const int64_t *d_ids, 
 {
     if (count <= 0) return 0;
     hipLaunchKernelGGL(gather_scores_kernel, dim3(nblk(count)), dim3(256), 0, h->stream, count, h->base, h->N, d_ids,
-                       h->d_eig, h->d_obj, d_eig_out, d_obj_out);
+                       h->d_eig.get(), h->d_obj, d_eig_out, d_obj_out);
     HIP_TRY(h, hipGetLastError());
     return 0;
 }

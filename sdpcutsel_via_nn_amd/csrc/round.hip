@@ -94,7 +94,7 @@ static int round_begin(sdpcut_ctx *h, int strat, int64_t sel_size, int32_t coef_
         // strategies 3 and 6: the measure is scored here if it is missing, then the round is strategy 2's on that array -- already
         // scored, so the selection is the non-fused one (score_for_selection) -- and round_end runs inside the same view.  (Strategy
         // 6 has scored SDPCUT_EIG with its measure: the rows kernel receives d_eig, the rows are those the score was computed from.)
-        if (!h->have_point || !h->d_eig) return sdpcut_fail(h, SDPCUT_ESTATE, "set_candidates and set_point first");
+        if (!h->have_point || !h->d_eig.get()) return sdpcut_fail(h, SDPCUT_ESTATE, "set_candidates and set_point first");
         SDPCUT_NO_PENDING(h);
         if (!(h->scored & measure) && (rc = sdpcut_score(h, measure))) return rc;
         MeasureAsObj view(h, measure);
@@ -105,7 +105,7 @@ static int round_begin(sdpcut_ctx *h, int strat, int64_t sel_size, int32_t coef_
     rc = check_round_strategy(h, strat);
     if (rc) return rc;
     if (sel_size < 0) return sdpcut_fail(h, SDPCUT_EINVAL, "bad select_round arguments");
-    if (!h->have_point || !h->d_eig) return sdpcut_fail(h, SDPCUT_ESTATE, "set_candidates and set_point first");
+    if (!h->have_point || !h->d_eig.get()) return sdpcut_fail(h, SDPCUT_ESTATE, "set_candidates and set_point first");
     if (coef_ld < h->row_len_max || coef_ld > SDPCUT_ROW_LD)
         return sdpcut_fail(h, SDPCUT_EINVAL, "coef_ld must hold the longest row (k + k(k+1)/2) and be <= SDPCUT_ROW_LD");
     SDPCUT_NO_PENDING(h);        // a fused round begun, or a sharded round enqueued and not waited for
@@ -142,10 +142,10 @@ static int round_begin(sdpcut_ctx *h, int strat, int64_t sel_size, int32_t coef_
     if (rc) return rc;
     rc = ensure_pinned(h, csr ? csr_layout(cap, coef_ld).bytes : y.bytes);
     if (rc) return rc;
-    int64_t *d_idx = (int64_t *)((char *)h->d_stage + y.idx);
-    double *d_sc = (double *)((char *)h->d_stage + y.score);
+    int64_t *d_idx = (int64_t *)((char *)h->d_stage.get() + y.idx);
+    double *d_sc = (double *)((char *)h->d_stage.get() + y.score);
     if (h->timing > 1) HIP_TRY(h, hipEventRecord(h->ev[2], h->stream));
-    int64_t *hdr = (int64_t *)h->pinned;
+    int64_t *hdr = (int64_t *)h->pinned.get();
     if (csr) hdr[8] = hdr[9] = hdr[10] = 0;
     // fast path: selection and rows are enqueued back to back; the epilogue kernel stores the
     // results directly into the pinned host block (no copy engine); one synchronisation
@@ -164,8 +164,8 @@ static int round_begin(sdpcut_ctx *h, int strat, int64_t sel_size, int32_t coef_
         // the epilogue's last workgroup publishes this round's serial number in the block's header: the
         // host polls that word instead of waiting for the runtime's completion signal (~5 us earlier)
         P.serial = ++h->round_serial;
-        rc = csr ? launch_round_csr(h, cap, d_cnt, cap, d_idx, d_sc, coef_ld, h->pinned_dev, P.serial)
-                 : launch_round_rows(h, cap, d_cnt, d_idx, d_sc, coef_ld, h->pinned_dev, 64, P.serial);
+        rc = csr ? launch_round_csr(h, cap, d_cnt, cap, d_idx, d_sc, coef_ld, h->pinned.dev(), P.serial)
+                 : launch_round_rows(h, cap, d_cnt, d_idx, d_sc, coef_ld, h->pinned.dev(), 64, P.serial);
         if (rc) return rc;
     }
     P.active = true;
@@ -177,17 +177,17 @@ static int round_begin(sdpcut_ctx *h, int strat, int64_t sel_size, int32_t coef_
 static int round_begin_exact_again(sdpcut_ctx *h, PendingRound &P)
 {
     const RowsLayout y = rows_layout(64, P.cap, P.ld);
-    int64_t *d_idx = (int64_t *)((char *)h->d_stage + y.idx);
-    double *d_sc = (double *)((char *)h->d_stage + y.score);
-    int64_t *hdr = (int64_t *)h->pinned;
+    int64_t *d_idx = (int64_t *)((char *)h->d_stage.get() + y.idx);
+    double *d_sc = (double *)((char *)h->d_stage.get() + y.score);
+    int64_t *hdr = (int64_t *)h->pinned.get();
     if (P.csr) hdr[8] = hdr[9] = hdr[10] = 0;
     P.exact_band = exact_widest_band(h);
     const int64_t *d_cnt = nullptr;
     int rc = exact_head_enqueue(h, P.strat, P.sel_size, P.cap, P.exact_band, d_idx, d_sc, &d_cnt);
     if (rc) return rc;
     P.serial = ++h->round_serial;
-    return P.csr ? launch_round_csr(h, P.cap, d_cnt, P.cap, d_idx, d_sc, P.ld, h->pinned_dev, P.serial)
-                 : launch_round_rows(h, P.cap, d_cnt, d_idx, d_sc, P.ld, h->pinned_dev, 64, P.serial);
+    return P.csr ? launch_round_csr(h, P.cap, d_cnt, P.cap, d_idx, d_sc, P.ld, h->pinned.dev(), P.serial)
+                 : launch_round_rows(h, P.cap, d_cnt, d_idx, d_sc, P.ld, h->pinned.dev(), 64, P.serial);
 }
 
 // A CSR assembly into the handle's pinned block, launched here and waited for: header words 8 .. last_word zeroed (10 for the
@@ -202,7 +202,7 @@ static int round_begin_exact_again(sdpcut_ctx *h, PendingRound &P)
 int csr_assemble_wait(sdpcut_ctx *h, int last_word, int launches, bool count_failure, const char *what,
                       const std::function<int(int64_t serial)> &launch)
 {
-    int64_t *hdr = (int64_t *)h->pinned;
+    int64_t *hdr = (int64_t *)h->pinned.get();
     for (;;) {
         for (int w = 8; w <= last_word; ++w) hdr[w] = 0;
         const int64_t serial = ++h->round_serial;
@@ -221,10 +221,10 @@ int csr_assemble_wait(sdpcut_ctx *h, int last_word, int launches, bool count_fai
 static int csr_head_again(sdpcut_ctx *h, const PendingRound &P, int64_t w, int launches)
 {
     const RowsLayout y = rows_layout(64, P.cap, P.ld);
-    const int64_t *d_idx = (const int64_t *)((char *)h->d_stage + y.idx);
-    const double *d_sc = (const double *)((char *)h->d_stage + y.score);
+    const int64_t *d_idx = (const int64_t *)((char *)h->d_stage.get() + y.idx);
+    const double *d_sc = (const double *)((char *)h->d_stage.get() + y.score);
     return csr_assemble_wait(h, 10, launches, false, "round_csr", [&](int64_t serial) {
-        return launch_round_csr(h, P.cap, nullptr, w, d_idx, d_sc, P.ld, h->pinned_dev, serial);
+        return launch_round_csr(h, P.cap, nullptr, w, d_idx, d_sc, P.ld, h->pinned.dev(), serial);
     });
 }
 
@@ -236,12 +236,12 @@ static int emit_head(sdpcut_ctx *h, const PendingRound &P, int64_t w, bool csr_i
     if (P.csr) return (w <= 0 && !csr_if_empty) ? 0 : csr_head_again(h, P, w, 2);
     if (w <= 0) return 0;
     const RowsLayout y = rows_layout(64, P.cap, P.ld);
-    char *st = (char *)h->d_stage;
+    char *st = (char *)h->d_stage.get();
     const int64_t *d_idx = (const int64_t *)(st + y.idx);
     int rc = launch_cut_rows(h, w, nullptr, d_idx, h->base, (double *)(st + y.lam), (double *)(st + y.coef), P.ld, (double *)(st + y.rhs),
                          nullptr, (int32_t *)(st + y.ks));
     if (rc) return rc;
-    HIP_TRY(h, hipMemcpyAsync(h->pinned, h->d_stage, y.bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->pinned.get(), h->d_stage.get(), y.bytes, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, sdpcut_sync(h));
     return 0;
 }
@@ -264,16 +264,16 @@ static int round_end(sdpcut_ctx *h, const void **block, int64_t *cap_out, int64_
     if (P.exact_band > 0 && P.cap > 0) {
         // the verdict of the band rule arrives with the block (hdr[4]): exact -- the ordinary code below finds its round complete;
         // a band that did not prove itself -- once more with the widest one (a second wait); else the ordinary round, whole
-        int rc = wait_round_done(h, (const int64_t *)h->pinned + 7, P.serial);
+        int rc = wait_round_done(h, (const int64_t *)h->pinned.get() + 7, P.serial);
         if (rc) return rc;
-        int v = exact_head_verdict(h, (const int64_t *)h->pinned, P.exact_band);
+        int v = exact_head_verdict(h, (const int64_t *)h->pinned.get(), P.exact_band);
         if (v == 1) {
             ++h->stat_exact_retries;
             rc = round_begin_exact_again(h, P);
             if (rc) return rc;
-            rc = wait_round_done(h, (const int64_t *)h->pinned + 7, P.serial);
+            rc = wait_round_done(h, (const int64_t *)h->pinned.get() + 7, P.serial);
             if (rc) return rc;
-            v = exact_head_verdict(h, (const int64_t *)h->pinned, P.exact_band);
+            v = exact_head_verdict(h, (const int64_t *)h->pinned.get(), P.exact_band);
         }
         if (v != 0) {
             ++h->stat_exact_gave_up;
@@ -296,9 +296,9 @@ static int round_end(sdpcut_ctx *h, const void **block, int64_t *cap_out, int64_
         // head rank_fast_mode serves, which rank_fast_enqueue then enqueues; were they not to, the round is simply begun again)
         bool keep = false;
         if (P.fast_tried && P.cap > 0) {
-            int rc = wait_round_done(h, (const int64_t *)h->pinned + 7, P.serial);
+            int rc = wait_round_done(h, (const int64_t *)h->pinned.get() + 7, P.serial);
             if (rc) return rc;
-            const int64_t *c = (const int64_t *)h->pinned;
+            const int64_t *c = (const int64_t *)h->pinned.get();
             keep = !c[4] && c[6] == TK_MODE_STRONG && c[0] >= (P.sel_size < h->N ? P.sel_size : h->N);
             h->stat_nn_skipped = h->N - c[1];
             // a selection that gave up is a fallback whichever road answers it (until the give-up tests this one went uncounted:
@@ -321,16 +321,16 @@ static int round_end(sdpcut_ctx *h, const void **block, int64_t *cap_out, int64_
     *block = nullptr;
     if (cap == 0) return sdpcut_rank(h, strat, sel_size, 0, nullptr, nullptr, n_total, new_strat, counters);
     const RowsLayout y = rows_layout(64, cap, P.ld);
-    int64_t *d_idx = (int64_t *)((char *)h->d_stage + y.idx);
-    double *d_sc = (double *)((char *)h->d_stage + y.score);
-    int64_t *hdr = (int64_t *)h->pinned;
+    int64_t *d_idx = (int64_t *)((char *)h->d_stage.get() + y.idx);
+    double *d_sc = (double *)((char *)h->d_stage.get() + y.score);
+    int64_t *hdr = (int64_t *)h->pinned.get();
     int rc;
     int64_t w = 0;
     bool have = false;
     if (P.fast_tried) {
         rc = wait_round_done(h, hdr + 7, P.serial);
         if (rc) return rc;
-        have = rank_fast_finish(h, strat, sel_size, cap, (const int64_t *)h->pinned, &w, n_total, new_strat, counters) != 0;
+        have = rank_fast_finish(h, strat, sel_size, cap, (const int64_t *)h->pinned.get(), &w, n_total, new_strat, counters) != 0;
         if (have && P.csr && hdr[10] && w > 0) {      // the enqueued assembly gave up its look-back: once more, see csr_assemble_wait
             ++h->stat_fallbacks;
             rc = csr_head_again(h, P, w, 1);
@@ -366,7 +366,7 @@ static int round_end(sdpcut_ctx *h, const void **block, int64_t *cap_out, int64_
             h->stat_exact_last = 0;
             ++h->stat_exact_gave_up;
         }
-        const int64_t *c5 = (const int64_t *)h->pinned;
+        const int64_t *c5 = (const int64_t *)h->pinned.get();
         const int64_t hint = (P.fast_tried && strat == SDPCUT_STRAT_COMB && !c5[4]) ? c5[0] : -1;
         rc = rank_on_device(h, strat, sel_size, cap, d_idx, d_sc, &w, n_total, new_strat, counters, hint);
         if (rc) return rc;
@@ -375,7 +375,7 @@ static int round_end(sdpcut_ctx *h, const void **block, int64_t *cap_out, int64_
         if (rc) return rc;
     }
     *n_out = w;
-    *block = h->pinned;
+    *block = h->pinned.get();
     return SDPCUT_OK;
 }
 

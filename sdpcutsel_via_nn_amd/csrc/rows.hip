@@ -304,10 +304,10 @@ __global__ __launch_bounds__(256) void point_copy_kernel(const double *src, doub
 // its own assembly before it returns.
 int ensure_round_sync(sdpcut_ctx *h)
 {
-    if (h->d_done_ticket) return 0;
+    if (h->d_done_ticket.get()) return 0;
     const size_t bytes = ROUND_TICKET_BYTES + (size_t)ROUND_AGG_WORDS * 8;
-    HIP_TRY(h, hipMalloc((void **)&h->d_done_ticket, bytes));
-    HIP_TRY(h, hipMemsetAsync(h->d_done_ticket, 0, bytes, h->stream));
+    HIP_TRY(h, h->d_done_ticket.reset(bytes / sizeof(uint32_t)));
+    HIP_TRY(h, hipMemsetAsync(h->d_done_ticket.get(), 0, bytes, h->stream));
     return 0;
 }
 
@@ -328,8 +328,8 @@ int launch_cut_rows(sdpcut_ctx *h, int64_t count, const int64_t *d_limit, const 
     if (count == 0) return 0;
     const int grid = (int)((count + 63) / 64);
     hipLaunchKernelGGL(cut_rows_kernel, dim3(grid), dim3(64), 0, h->stream, count, d_limit, d_idx, idx_base,
-                       h->N, h->d_set_orig, h->d_k, h->d_vars, h->nb_vars, h->L, d_lam, d_coef, coef_ld, d_rhs, d_cols,
-                       d_ks, (h->scored & SDPCUT_EIG) ? (const double *)h->d_eig : (const double *)nullptr);
+                       h->N, h->d_set_orig.get(), h->d_k.get(), h->d_vars.get(), h->nb_vars, h->L, d_lam, d_coef, coef_ld, d_rhs, d_cols,
+                       d_ks, (h->scored & SDPCUT_EIG) ? (const double *)h->d_eig.get() : (const double *)nullptr);
     HIP_TRY(h, hipGetLastError());
     return 0;
 }
@@ -338,7 +338,7 @@ int launch_point_copy(sdpcut_ctx *h, const double *src_mapped, int64_t n)
 {
     int64_t g = (n + 255) / 256;
     if (g > 2048) g = 2048;
-    hipLaunchKernelGGL(point_copy_kernel, dim3((unsigned)(g < 1 ? 1 : g)), dim3(256), 0, h->stream, src_mapped, h->d_vars, n);
+    hipLaunchKernelGGL(point_copy_kernel, dim3((unsigned)(g < 1 ? 1 : g)), dim3(256), 0, h->stream, src_mapped, h->d_vars.get(), n);
     HIP_TRY(h, hipGetLastError());
     return 0;
 }
@@ -356,8 +356,8 @@ int launch_round_rows(sdpcut_ctx *h, int64_t cap, const int64_t *d_c4, const int
     int grid = (int)((cap + 63) / 64);
     if (grid < ROUND_MIN_BLOCKS) grid = ROUND_MIN_BLOCKS;      // (the workspace zeroing, see launch_round_csr)
     hipLaunchKernelGGL(round_rows_kernel, dim3(grid), dim3(64), 0, h->stream, cap, d_c4, d_idx, d_score, h->base, h->N,
-                       h->d_set_orig, h->d_k, h->d_vars, h->nb_vars, h->L, coef_ld, (char *)block, hdr_bytes, zp, zw, done_serial,
-                       h->d_done_ticket, (h->scored & SDPCUT_EIG) ? (const double *)h->d_eig : (const double *)nullptr);
+                       h->d_set_orig.get(), h->d_k.get(), h->d_vars.get(), h->nb_vars, h->L, coef_ld, (char *)block, hdr_bytes, zp, zw, done_serial,
+                       h->d_done_ticket.get(), (h->scored & SDPCUT_EIG) ? (const double *)h->d_eig.get() : (const double *)nullptr);
     HIP_TRY(h, hipGetLastError());
     h->topk_alt_clean = true;
     return 0;
@@ -378,12 +378,12 @@ int launch_round_csr(sdpcut_ctx *h, int64_t cap, const int64_t *d_c4, int64_t li
     if (rc) return rc;
     RoundCsrArgs R;
     R.cap = cap; R.d_c4 = d_c4; R.limit = limit; R.idx = d_idx; R.score = d_score; R.idx_base = h->base; R.n_local = h->N;
-    R.set5 = h->d_set_orig; R.ks = h->d_k; R.vars = h->d_vars; R.nv = h->nb_vars; R.L = h->L;
-    R.eig = (h->scored & SDPCUT_EIG) ? h->d_eig : nullptr;
+    R.set5 = h->d_set_orig.get(); R.ks = h->d_k.get(); R.vars = h->d_vars.get(); R.nv = h->nb_vars; R.L = h->L;
+    R.eig = (h->scored & SDPCUT_EIG) ? h->d_eig.get() : nullptr;
     csr_args_out(R, block, cap, ld);
     rc = topk_alt_ws(h, &R.zero_ptr, &R.zero_words);
     if (rc) return rc;
-    R.serial = serial; R.done_ticket = h->d_done_ticket; R.agg = round_agg_words(h);
+    R.serial = serial; R.done_ticket = h->d_done_ticket.get(); R.agg = round_agg_words(h);
     R.inject = inject_take(h, 2, cap > 64);
     hipLaunchKernelGGL(round_csr_kernel, dim3(grid), dim3(64), 0, h->stream, R);
     HIP_TRY(h, hipGetLastError());
@@ -403,7 +403,7 @@ int launch_round_csr_points(sdpcut_ctx *h, int p_first, int n_points, int64_t ca
     if (grid > agg_stride) return sdpcut_fail(h, SDPCUT_EINVAL, "round_csr_points: head too long");
     RoundCsrArgs R;
     R.cap = cap; R.d_c4 = d_c4; R.limit = cap; R.idx = d_idx; R.score = d_score; R.idx_base = h->base; R.n_local = h->N;
-    R.set5 = h->d_set_orig; R.ks = h->d_k; R.vars = d_pts; R.nv = h->nb_vars; R.L = h->L;
+    R.set5 = h->d_set_orig.get(); R.ks = h->d_k.get(); R.vars = d_pts; R.nv = h->nb_vars; R.L = h->L;
     R.eig = d_eig;
     csr_args_out(R, block, cap, ld);
     R.zero_ptr = nullptr; R.zero_words = 0;

@@ -34,11 +34,11 @@ static int launch_score_k(sdpcut_ctx *h, int K, uint32_t flags, hipEvent_t ev_st
         if (A.pf_mloc == 0) h->pf_counted = false;
         // SDPCUT_OPT_EMIT_HEAD: the strong members go to a list in the key array, which a selection that starts from this launch's
         // histograms (stage 3) does not use: 16 bytes per entry, the key and the index
-        int64_t ecap = fuse->emit && A.strong_out && h->d_key_a ? h->key_n / 2 : 0;
+        int64_t ecap = fuse->emit && A.strong_out && h->d_key_a.get() ? (int64_t)h->d_key_a.size() / 2 : 0;
         if (ecap > 0xffffffffll) ecap = 0xffffffffll;
         if (h->emit_cap_opt > 0 && h->emit_cap_opt < ecap) ecap = h->emit_cap_opt;
         if (ecap > 0) {
-            A.emit = h->d_key_a;
+            A.emit = h->d_key_a.get();
             A.emit_cap = (uint32_t)ecap;
             h->emit_launched = true;
             h->emit_cap = ecap;

@@ -65,11 +65,11 @@ static inline ScoreArgs fill_score_args(const sdpcut_ctx *h, int K, uint32_t fla
 {
     const Bucket &b = h->bucket[K];
     ScoreArgs A;
-    A.set = b.d_set; A.orig = b.d_orig; A.n = b.n;
+    A.set = b.d_set.get(); A.orig = b.d_orig.get(); A.n = b.n;
     A.strip = p.strip;
     A.rr_end = p.rr_end; A.tail_nhi = p.tail_nhi; A.tail_hi = p.tail_hi; A.tail_lo = p.tail_lo;
     A.vars = score_vars(h, flags); A.Q = score_Q(h, flags); A.nv = h->nb_vars; A.L = h->L;      // (a node box: common.h)
-    A.eig_out = h->d_eig; A.obj_out = h->d_obj; A.flags = flags;
+    A.eig_out = h->d_eig.get(); A.obj_out = h->d_obj; A.flags = flags;
     A.tk = fuse ? (TopkWs *)fuse->ws : nullptr;
     A.tk_mode = fuse ? fuse->mode : 0;
     A.spread = p.spread;

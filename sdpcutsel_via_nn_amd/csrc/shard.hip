@@ -103,7 +103,7 @@ extern "C" int sdpcut_shard_head_device(sdpcut_handle h, int strat, int64_t coun
     if (strat != SDPCUT_STRAT_FEAS && strat != SDPCUT_STRAT_OPT && strat != SDPCUT_PART_STRONG && !comball)
         return sdpcut_fail(h, SDPCUT_EINVAL, "shard head: strategy must be 1, 2, SDPCUT_PART_STRONG or SDPCUT_PART_COMBALL");
     const uint32_t need = strat_need(strat);
-    if (h->N > 0 && (!h->have_point || !h->d_eig)) return sdpcut_fail(h, SDPCUT_ESTATE, "set_candidates and set_point first");
+    if (h->N > 0 && (!h->have_point || !h->d_eig.get())) return sdpcut_fail(h, SDPCUT_ESTATE, "set_candidates and set_point first");
     HIP_TRY(h, hipSetDevice(h->device));
     // Not scored at this point yet: the call scores the shard itself, and the score kernels count the leading
     // digit of the selection keys on the way (score_for_selection) -- a sharded round needs no sdpcut_score.
@@ -142,7 +142,7 @@ extern "C" int sdpcut_shard_head_device(sdpcut_handle h, int strat, int64_t coun
         if (rc < 0) return rc;
         if (rc != 1) return sdpcut_fail(h, SDPCUT_EINVAL, "shard head: request not eligible for the select path");
         if (partial.on) {      // SDPCUT_STAT_NN_SKIPPED = N - nb_violated of this selection: no host wait here, the count stays on the device
-            HIP_TRY(h, hipMemcpyAsync(h->d_stats + 4, d_c4 + 1, sizeof(int64_t), hipMemcpyDeviceToDevice, h->stream));
+            HIP_TRY(h, hipMemcpyAsync(h->d_stats.get() + 4, d_c4 + 1, sizeof(int64_t), hipMemcpyDeviceToDevice, h->stream));
             h->nn_skipped_n = h->N;
             h->nn_skipped_on_device = true;
         }
@@ -183,17 +183,17 @@ extern "C" int sdpcut_shard_finish_enqueue(sdpcut_handle h, int32_t world, int64
     if (rc) return rc;
     rc = ensure_pinned(h, rows_layout(hdr_b, sel_size, coef_ld).bytes_pos);      // with int32 pos[sel] of the compacted form
     if (rc) return rc;
-    int64_t *d_mi = (int64_t *)h->d_stage;
+    int64_t *d_mi = (int64_t *)h->d_stage.get();
     double *d_ms = (double *)(d_mi + s);
     const size_t nthr = tot > (size_t)world * SHARD_HDR ? tot : (size_t)world * SHARD_HDR;
     hipLaunchKernelGGL(shard_mergerank_kernel, dim3((int)((nthr + 255) / 256)), dim3(256), 0, h->stream, (int)world,
-                       count, (int)fields, pitch_words, (const int64_t *)d_allrec, sel_size, d_ms, d_mi, (int64_t *)h->pinned_dev);
+                       count, (int)fields, pitch_words, (const int64_t *)d_allrec, sel_size, d_ms, d_mi, (int64_t *)h->pinned.dev());
     // rows of the merged head that live on this shard (the others are marked ks = 0, lam = NaN),
     // stored -- with the merged ids and scores -- straight into the host block
     // (completion: the rows kernel's last workgroup stores the round's serial number into word 7 of the
     // first header -- a pad word of the record -- and the host polls it, see wait_round_done)
     const int64_t serial = ++h->round_serial;
-    rc = launch_round_rows(h, sel_size, nullptr, d_mi, d_ms, coef_ld, h->pinned_dev, (int64_t)hdr_b, serial);
+    rc = launch_round_rows(h, sel_size, nullptr, d_mi, d_ms, coef_ld, h->pinned.dev(), (int64_t)hdr_b, serial);
     if (rc) return rc;
     h->shard_pending_serial = serial;
     h->shard_pending_world = world;
@@ -209,15 +209,15 @@ extern "C" int sdpcut_shard_finish_wait(sdpcut_handle h, int32_t compact_own, co
     if (!h) return SDPCUT_EINVAL;
     if (!block || (compact_own && !n_own)) return sdpcut_fail(h, SDPCUT_EINVAL, "bad shard_finish_wait arguments");
     if (!h->shard_pending_serial) return sdpcut_fail(h, SDPCUT_ESTATE, "no sharded round pending: sdpcut_shard_finish_enqueue first");
-    int rc = wait_round_done(h, (const int64_t *)h->pinned + 7, h->shard_pending_serial);
+    int rc = wait_round_done(h, (const int64_t *)h->pinned.get() + 7, h->shard_pending_serial);
     h->shard_pending_serial = 0;
     if (rc) return rc;
-    ((int64_t *)h->pinned)[7] = 0;      // the caller sees the record's pad word, not the completion mark
-    *block = h->pinned;
+    ((int64_t *)h->pinned.get())[7] = 0;      // the caller sees the record's pad word, not the completion mark
+    *block = h->pinned.get();
     if (!compact_own) return SDPCUT_OK;
     const size_t s = (size_t)h->shard_pending_sel, ld = (size_t)h->shard_pending_ld;
     const RowsLayout y = rows_layout((size_t)h->shard_pending_world * SHARD_HDR * 8, h->shard_pending_sel, h->shard_pending_ld);
-    char *p = (char *)h->pinned;
+    char *p = (char *)h->pinned.get();
     double *lam = (double *)(p + y.lam);
     double *rhs = (double *)(p + y.rhs);
     double *coef = (double *)(p + y.coef);

@@ -38,39 +38,32 @@
 // The one-workgroup select-sort-emit algorithm (smallsel_body) is in topk_small_dev.h: tk_smallsel_kernel and the batched
 // tk_points_kernel (points.hip, a workgroup per LP point) are its two hosts.
 
+#include <utility>
+
 #include "topk_launch.h"
 
 // ------------------------------------------------------------------------------------------
 int ensure_topk_ws(sdpcut_ctx *h)
 {
-    if (h->d_topk_ws) return 0;
-    HIP_TRY(h, hipMalloc(&h->d_topk_ws, sizeof(TopkWs)));
+    if (h->d_topk_ws.get()) return 0;
+    HIP_TRY(h, h->d_topk_ws.reset(sizeof(TopkWs)));
     // first half: compacted selection, second half: the sorted tiles
-    HIP_TRY(h, hipMalloc((void **)&h->d_sel_key, 2 * TK_MAXK * sizeof(uint64_t)));
-    HIP_TRY(h, hipMalloc((void **)&h->d_sel_idx, 2 * TK_MAXK * sizeof(uint32_t)));
+    HIP_TRY(h, h->d_sel_key.reset(2 * TK_MAXK));
+    HIP_TRY(h, h->d_sel_idx.reset(2 * TK_MAXK));
     // tk_countrank_kernel's per-entry words: zeroed once here, the wave that completes a word leaves it zero again
-    HIP_TRY(h, hipMalloc((void **)&h->d_rank_acc, TK_LDSK * sizeof(unsigned long long)));
-    HIP_TRY(h, hipMemsetAsync(h->d_rank_acc, 0, TK_LDSK * sizeof(unsigned long long), h->stream));
+    HIP_TRY(h, h->d_rank_acc.reset(TK_LDSK));
+    HIP_TRY(h, hipMemsetAsync(h->d_rank_acc.get(), 0, TK_LDSK * sizeof(unsigned long long), h->stream));
     const int rc = tk_refine_coresident(h, &h->tk_coresident);
     if (rc) return rc;
     if (h->tk_coresident < 1) h->fused_tail = false;      // (never on gfx950: 4 per CU by LDS) the launch-per-digit path has no waits
     return 0;
 }
 
-void free_topk_ws(sdpcut_ctx *h)
-{
-    (void)hipFree(h->d_topk_ws); (void)hipFree(h->d_topk_ws_alt); (void)hipFree(h->d_sel_key); (void)hipFree(h->d_sel_idx);
-    (void)hipFree(h->d_rank_acc);
-    h->d_rank_acc = nullptr;
-    h->d_topk_ws = nullptr; h->d_topk_ws_alt = nullptr; h->d_sel_key = nullptr; h->d_sel_idx = nullptr;
-    h->topk_alt_clean = false;
-}
-
 int topk_alt_ws(sdpcut_ctx *h, uint64_t **ptr, int *words)
 {
     static_assert(sizeof(TopkWs) % 8 == 0, "TopkWs is zeroed in 8-byte words");
-    if (!h->d_topk_ws_alt) HIP_TRY(h, hipMalloc(&h->d_topk_ws_alt, sizeof(TopkWs)));
-    *ptr = (uint64_t *)h->d_topk_ws_alt;
+    if (!h->d_topk_ws_alt.get()) HIP_TRY(h, h->d_topk_ws_alt.reset(sizeof(TopkWs)));
+    *ptr = (uint64_t *)h->d_topk_ws_alt.get();
     // (r5) lists too short for the fine histogram (it sits at the end of the struct) zero only what lies in front of it: the epilogue
     // of a round with a handful of cuts is a handful of workgroups, and every word is a store on its critical path
     static_assert(offsetof(TopkWs, pf_floor) % 8 == 0 && offsetof(TopkWs, pf_tab) > offsetof(TopkWs, pf_floor), "fine histogram last");
@@ -87,15 +80,15 @@ int topk_begin(sdpcut_ctx *h, void **ws_out, uint64_t **keys_out)
     if (rc) return rc;
     rc = ensure_key_ws(h, h->N);
     if (rc) return rc;
-    if (h->topk_alt_clean && h->d_topk_ws_alt) {
+    if (h->topk_alt_clean && h->d_topk_ws_alt.get()) {
         // the epilogue of the previous round zeroed the other workspace (stream-ordered): swap
-        void *t = h->d_topk_ws; h->d_topk_ws = h->d_topk_ws_alt; h->d_topk_ws_alt = t;
+        std::swap(h->d_topk_ws, h->d_topk_ws_alt);
         h->topk_alt_clean = false;
     } else {
-        HIP_TRY(h, hipMemsetAsync(h->d_topk_ws, 0, sizeof(TopkWs), h->stream));
+        HIP_TRY(h, hipMemsetAsync(h->d_topk_ws.get(), 0, sizeof(TopkWs), h->stream));
     }
-    if (ws_out) *ws_out = h->d_topk_ws;
-    if (keys_out) *keys_out = h->d_key_a;
+    if (ws_out) *ws_out = h->d_topk_ws.get();
+    if (keys_out) *keys_out = h->d_key_a.get();
     return 0;
 }
 
@@ -178,8 +171,8 @@ int topk_select_enqueue(sdpcut_ctx *h, int mode, int64_t k, double score_add, in
         const int rc = topk_begin(h, nullptr, nullptr);
         if (rc) return rc;
     }
-    TopkWs *ws = (TopkWs *)h->d_topk_ws;
-    const double *eig = (h->scored & SDPCUT_EIG) ? h->d_eig : nullptr;
+    TopkWs *ws = (TopkWs *)h->d_topk_ws.get();
+    const double *eig = (h->scored & SDPCUT_EIG) ? h->d_eig.get() : nullptr;
     const double *obj = (h->scored & SDPCUT_NN) ? h->d_obj : nullptr;
     const TkJob j = {ws, mode, n, k, sel, eig, obj, h->base, score_add, d_idx_out, d_score_out, 0, TK_MAXK};
     const int rc = topk_run(h, p, j, false);
@@ -192,14 +185,14 @@ int topk_select_enqueue(sdpcut_ctx *h, int mode, int64_t k, double score_add, in
 // idx_out = entry index, val_out = the key's low 63 bits as a double; cnt as in topk_select_on_device.
 int topk_select_keys_enqueue(sdpcut_ctx *h, int64_t n, int64_t k, int64_t *d_idx_out, double *d_val_out, const int64_t **d_counters_out)
 {
-    if (k < 1 || k > TK_MAXK || n < 1 || n > h->key_n) return sdpcut_fail(h, SDPCUT_EINVAL, "top-k select: k / n out of range");
+    if (k < 1 || k > TK_MAXK || n < 1 || n > (int64_t)h->d_key_a.size()) return sdpcut_fail(h, SDPCUT_EINVAL, "top-k select: k / n out of range");
     // (always through the big-head merge: it is the one with the raw key output)
     const int64_t kk = k <= TK_LDSK ? TK_LDSK + 1 : k;
     const TkPlan p = plan_for(h, n, kk, TK_MODE_FEAS, 0, true, true);
     if (p.err) return sdpcut_fail(h, p.err, p.msg);
     int rc = topk_begin(h, nullptr, nullptr);
     if (rc) return rc;
-    TopkWs *ws = (TopkWs *)h->d_topk_ws;
+    TopkWs *ws = (TopkWs *)h->d_topk_ws.get();
     const TkJob j = {ws, TK_MODE_FEAS, n, kk, 0, nullptr, nullptr, 0, 0.0, d_idx_out, d_val_out, 1, k};
     rc = topk_run(h, p, j, true);
     if (rc) return rc;
@@ -257,7 +250,7 @@ static int select_prekeys_enqueue(sdpcut_ctx *h, int64_t n, int64_t k, bool tie,
     if (p.err) return sdpcut_fail(h, p.err, p.msg);
     const int rc = topk_begin(h, nullptr, nullptr);
     if (rc) return rc;
-    TopkWs *ws = (TopkWs *)h->d_topk_ws;
+    TopkWs *ws = (TopkWs *)h->d_topk_ws.get();
     *d_void = &ws->counters[4];
     const TkJob j = {ws, mode, n, k, 0, nullptr, nullptr, h->base, 0.0, d_idx_out, d_score_out, 0, TK_MAXK};
     return topk_run(h, p, j, true);
@@ -269,8 +262,8 @@ static int select_prekeys_enqueue(sdpcut_ctx *h, int64_t n, int64_t k, bool tie,
 int topk_tie_split(sdpcut_ctx *h, int64_t k, int64_t *d_idx_out, double *d_score_out, int64_t *k_eff_out)
 {
     const int64_t n = h->N;
-    if (!h->d_topk_ws || (h->scored & (SDPCUT_EIG | SDPCUT_NN)) != (SDPCUT_EIG | SDPCUT_NN) || k < 1 || k > TK_MAXK) return 1;
-    const TopkWs *ws = (const TopkWs *)h->d_topk_ws;
+    if (!h->d_topk_ws.get() || (h->scored & (SDPCUT_EIG | SDPCUT_NN)) != (SDPCUT_EIG | SDPCUT_NN) || k < 1 || k > TK_MAXK) return 1;
+    const TopkWs *ws = (const TopkWs *)h->d_topk_ws.get();
     TkState st8;
     int64_t c[8];
     HIP_TRY(h, hipMemcpyAsync(&st8, &ws->state[8], sizeof(st8), hipMemcpyDeviceToHost, h->stream));
@@ -286,12 +279,12 @@ int topk_tie_split(sdpcut_ctx *h, int64_t k, int64_t *d_idx_out, double *d_score
     int64_t void_a = 0, void_b = 0;
     const int64_t *d_void = nullptr;
     if (above > 0) {
-        hipLaunchKernelGGL(tk_tiekeys_kernel, dim3(grid), dim3(TK_THREADS), 0, h->stream, n, T, 0, h->d_eig, h->d_obj, h->d_key_a);
+        hipLaunchKernelGGL(tk_tiekeys_kernel, dim3(grid), dim3(TK_THREADS), 0, h->stream, n, T, 0, h->d_eig.get(), h->d_obj, h->d_key_a.get());
         rc = select_prekeys_enqueue(h, n, above, true, d_idx_out, d_score_out, &d_void);
         if (rc) return rc;
         HIP_TRY(h, hipMemcpyAsync(&void_a, d_void, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
     }
-    hipLaunchKernelGGL(tk_tiekeys_kernel, dim3(grid), dim3(TK_THREADS), 0, h->stream, n, T, 1, h->d_eig, h->d_obj, h->d_key_a);
+    hipLaunchKernelGGL(tk_tiekeys_kernel, dim3(grid), dim3(TK_THREADS), 0, h->stream, n, T, 1, h->d_eig.get(), h->d_obj, h->d_key_a.get());
     rc = select_prekeys_enqueue(h, n, need, false, d_idx_out + above, d_score_out + above, &d_void);
     if (rc) return rc;
     HIP_TRY(h, hipMemcpyAsync(&void_b, d_void, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));

@@ -98,6 +98,6 @@ __global__ __launch_bounds__(TK_THREADS) void tk_write_kernel(int64_t n, int64_t
 void tk_compact_launch(sdpcut_ctx *h, const TkPlan &p, const TkJob &j)
 {
     const dim3 grid(p.grid_pass), blk(TK_THREADS);
-    hipLaunchKernelGGL(tk_count_kernel, grid, blk, 0, h->stream, j.n, p.chunk, h->d_key_a, j.ws);
-    hipLaunchKernelGGL(tk_write_kernel, grid, blk, 0, h->stream, j.n, p.chunk, h->d_key_a, j.ws, h->d_sel_key, h->d_sel_idx);
+    hipLaunchKernelGGL(tk_count_kernel, grid, blk, 0, h->stream, j.n, p.chunk, h->d_key_a.get(), j.ws);
+    hipLaunchKernelGGL(tk_write_kernel, grid, blk, 0, h->stream, j.n, p.chunk, h->d_key_a.get(), j.ws, h->d_sel_key.get(), h->d_sel_idx.get());
 }

@@ -797,19 +797,19 @@ __global__ __launch_bounds__(TK_THREADS) void tk_prekeys_kernel(int64_t n, int64
 
 void tk_keys_launch(sdpcut_ctx *h, const TkPlan &p, const TkJob &j)
 {
-    hipLaunchKernelGGL(tk_keys_kernel, dim3(p.grid_keys), dim3(TK_THREADS), 0, h->stream, j.mode, j.sel, j.n, j.k, j.eig, j.obj, h->d_key_a, j.ws);
+    hipLaunchKernelGGL(tk_keys_kernel, dim3(p.grid_keys), dim3(TK_THREADS), 0, h->stream, j.mode, j.sel, j.n, j.k, j.eig, j.obj, h->d_key_a.get(), j.ws);
 }
 
 void tk_prekeys_launch(sdpcut_ctx *h, const TkPlan &p, const TkJob &j)
 {
-    hipLaunchKernelGGL(tk_prekeys_kernel, dim3(p.grid_keys), dim3(TK_THREADS), 0, h->stream, j.n, j.k, h->d_key_a, j.ws);
+    hipLaunchKernelGGL(tk_prekeys_kernel, dim3(p.grid_keys), dim3(TK_THREADS), 0, h->stream, j.n, j.k, h->d_key_a.get(), j.ws);
 }
 
 // one launch per digit (each returns at once when the selection has been closed by an earlier digit)
 void tk_hist_launch(sdpcut_ctx *h, const TkPlan &p, const TkJob &j)
 {
     for (int d = 1; d < 8; ++d)
-        hipLaunchKernelGGL(tk_hist_kernel, dim3(p.grid_pass), dim3(TK_THREADS), 0, h->stream, d, j.n, j.k, h->d_key_a, j.ws);
+        hipLaunchKernelGGL(tk_hist_kernel, dim3(p.grid_pass), dim3(TK_THREADS), 0, h->stream, d, j.n, j.k, h->d_key_a.get(), j.ws);
 }
 
 // workgroups of the fused selection kernel the device holds at once (its grid barriers rely on it)
@@ -829,16 +829,16 @@ int tk_refine_launch(sdpcut_ctx *h, const TkPlan &p, const TkJob &j)
 {
     const dim3 grid(p.grid_pass), blk(TK_THREADS);
     if (p.route == TK_ROUTE_EMITTED) {      // the list the score launch emitted lies in the key array (launch_score_k)
-        hipLaunchKernelGGL((tk_refine_kernel<true, true>), grid, blk, 0, h->stream, j.n, j.k, p.chunk, h->d_key_a, j.ws, h->d_sel_key,
-                           h->d_sel_idx, j.mode, j.sel, j.eig ? j.eig : j.obj, j.obj ? j.obj : j.eig, p.pf_k, h->d_stats, h->emit_cap);
+        hipLaunchKernelGGL((tk_refine_kernel<true, true>), grid, blk, 0, h->stream, j.n, j.k, p.chunk, h->d_key_a.get(), j.ws, h->d_sel_key.get(),
+                           h->d_sel_idx.get(), j.mode, j.sel, j.eig ? j.eig : j.obj, j.obj ? j.obj : j.eig, p.pf_k, h->d_stats.get(), h->emit_cap);
     } else if (p.route == TK_ROUTE_ONFLY) {      // (a measure the mode does not use is never looked at: any readable array of n doubles will do)
-        hipLaunchKernelGGL(tk_refine_kernel<true>, grid, blk, 0, h->stream, j.n, j.k, p.chunk, nullptr, j.ws, h->d_sel_key, h->d_sel_idx,
-                           j.mode, j.sel, j.eig ? j.eig : j.obj, j.obj ? j.obj : j.eig, p.pf_k, h->d_stats, (int64_t)0);
+        hipLaunchKernelGGL(tk_refine_kernel<true>, grid, blk, 0, h->stream, j.n, j.k, p.chunk, nullptr, j.ws, h->d_sel_key.get(), h->d_sel_idx.get(),
+                           j.mode, j.sel, j.eig ? j.eig : j.obj, j.obj ? j.obj : j.eig, p.pf_k, h->d_stats.get(), (int64_t)0);
     } else if (p.route == TK_ROUTE_COOP) {      // the runtime guarantees the co-residency (+20 us per launch)
-        const uint64_t *keys_arg = h->d_key_a;
+        const uint64_t *keys_arg = h->d_key_a.get();
         TopkWs *ws_arg = j.ws;
-        uint64_t *sk_arg = h->d_sel_key;
-        uint32_t *si_arg = h->d_sel_idx;
+        uint64_t *sk_arg = h->d_sel_key.get();
+        uint32_t *si_arg = h->d_sel_idx.get();
         int64_t n_arg = j.n, k_arg = j.k, chunk_arg = p.chunk, sel_arg = j.sel, pf_arg = 0;
         int mode_arg = j.mode;
         const double *eig_arg = j.eig, *obj_arg = j.obj;
@@ -848,7 +848,7 @@ int tk_refine_launch(sdpcut_ctx *h, const TkPlan &p, const TkJob &j)
                         &ecap_arg};
         HIP_TRY(h, hipLaunchCooperativeKernel((const void *)tk_refine_kernel<false>, grid, blk, args, 0, h->stream));
     } else {
-        hipLaunchKernelGGL(tk_refine_kernel<false>, grid, blk, 0, h->stream, j.n, j.k, p.chunk, h->d_key_a, j.ws, h->d_sel_key, h->d_sel_idx,
+        hipLaunchKernelGGL(tk_refine_kernel<false>, grid, blk, 0, h->stream, j.n, j.k, p.chunk, h->d_key_a.get(), j.ws, h->d_sel_key.get(), h->d_sel_idx.get(),
                            j.mode, j.sel, j.eig, j.obj, (int64_t)0, (unsigned long long *)nullptr, (int64_t)0);
     }
     return 0;

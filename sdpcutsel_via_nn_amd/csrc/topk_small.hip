@@ -88,11 +88,11 @@ void tk_small_launch(sdpcut_ctx *h, const TkPlan &p, const TkJob &j)
 {
     if (p.route == TK_ROUTE_SMALLSORT)      // a short list with a head of one tile at most: selection, sort and emission in ONE launch
         hipLaunchKernelGGL(tk_smallsel_kernel<true>, dim3(1), dim3(TK_SMALLSEL_THREADS), 0, h->stream, j.mode, j.sel, (int)j.n, (int)j.k, j.eig,
-                           j.obj, j.ws, h->d_sel_key, h->d_sel_idx, j.base, j.score_add, j.d_idx_out, j.d_score_out);
+                           j.obj, j.ws, h->d_sel_key.get(), h->d_sel_idx.get(), j.base, j.score_add, j.d_idx_out, j.d_score_out);
     else if (p.route == TK_ROUTE_SMALLSEL)
         hipLaunchKernelGGL(tk_smallsel_kernel<false>, dim3(1), dim3(TK_SMALLSEL_THREADS), 0, h->stream, j.mode, j.sel, (int)j.n, (int)j.k, j.eig,
-                           j.obj, j.ws, h->d_sel_key, h->d_sel_idx, j.base, j.score_add, j.d_idx_out, j.d_score_out);
+                           j.obj, j.ws, h->d_sel_key.get(), h->d_sel_idx.get(), j.base, j.score_add, j.d_idx_out, j.d_score_out);
     else
         hipLaunchKernelGGL(tk_small_kernel, dim3(1), dim3(TK_SMALL_THREADS), 0, h->stream, j.mode, j.sel, j.n, j.k, j.eig, j.obj, j.ws,
-                           h->d_sel_key, h->d_sel_idx);
+                           h->d_sel_key.get(), h->d_sel_idx.get());
 }

@@ -311,17 +311,17 @@ __global__ __launch_bounds__(TK_THREADS) void tk_countrank_kernel(int64_t base, 
 template <int T>
 static void sort_launch(sdpcut_ctx *h, const TkPlan &p, const TkJob &j)
 {
-    uint64_t *tile_key = h->d_sel_key + TK_MAXK;      // first half: compacted selection, second half: the sorted tiles
-    uint32_t *tile_idx = h->d_sel_idx + TK_MAXK;
+    uint64_t *tile_key = h->d_sel_key.get() + TK_MAXK;      // first half: compacted selection, second half: the sorted tiles
+    uint32_t *tile_idx = h->d_sel_idx.get() + TK_MAXK;
     const double *tie_obj = T ? (j.tie_obj ? j.tie_obj : h->d_obj) : nullptr;
     if (p.count_rank) {      // one launch: 64-entry groups x slices, four slices per workgroup; idle groups exit at once
         const dim3 g_count(p.ntiles * (TK_TILE / 64) * (TK_CR_SLICES / (TK_THREADS / 64)));
-        hipLaunchKernelGGL(tk_countrank_kernel<T>, g_count, dim3(TK_THREADS), 0, h->stream, j.base, j.score_add, j.ws, h->d_sel_key,
-                           h->d_sel_idx, h->d_rank_acc, j.d_idx_out, j.d_score_out, tie_obj);
+        hipLaunchKernelGGL(tk_countrank_kernel<T>, g_count, dim3(TK_THREADS), 0, h->stream, j.base, j.score_add, j.ws, h->d_sel_key.get(),
+                           h->d_sel_idx.get(), h->d_rank_acc.get(), j.d_idx_out, j.d_score_out, tie_obj);
         return;
     }
     const dim3 g_sort(p.ntiles), g_merge(p.ntiles * TK_TILE / TK_THREADS), blk(TK_THREADS);      // idle tiles exit at once
-    hipLaunchKernelGGL(tk_tilesort_kernel<T>, g_sort, blk, 0, h->stream, j.ws, h->d_sel_key, h->d_sel_idx, tile_key, tile_idx, tie_obj);
+    hipLaunchKernelGGL(tk_tilesort_kernel<T>, g_sort, blk, 0, h->stream, j.ws, h->d_sel_key.get(), h->d_sel_idx.get(), tile_key, tile_idx, tie_obj);
     if constexpr (T < 2) {
         if (p.big_merge) {
             hipLaunchKernelGGL(tk_mergerank_big_kernel<(T != 0)>, g_merge, blk, 0, h->stream, j.base, j.score_add, j.ws, tile_key, tile_idx,

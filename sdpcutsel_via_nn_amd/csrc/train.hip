@@ -273,18 +273,6 @@ static void train_launch_k(int nh, const TrainArgs &A, int grid, hipStream_t st)
     }
 }
 
-void free_train_ws(sdpcut_ctx *h)
-{
-    for (int k = 0; k <= SDPCUT_MAX_K; ++k) {
-        (void)hipFree(h->train[k].d_in);
-        (void)hipFree(h->train[k].d_t);
-        h->train[k] = TrainData();
-    }
-    (void)hipFree(h->d_train_ws);
-    h->d_train_ws = nullptr;
-    h->train_ws_doubles = 0;
-}
-
 extern "C" {
 
 int sdpcut_train_set_data(sdpcut_handle h, int k, int64_t count, const double *inputs, const double *targets)
@@ -296,15 +284,13 @@ int sdpcut_train_set_data(sdpcut_handle h, int k, int64_t count, const double *i
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, sdpcut_sync(h));
     TrainData &td = h->train[k];
-    (void)hipFree(td.d_in);
-    (void)hipFree(td.d_t);
     td = TrainData();
     if (count == 0) return SDPCUT_OK;      // the set of this size is dropped
     const size_t d = (size_t)k * (k + 3) / 2;
-    HIP_TRY(h, hipMalloc((void **)&td.d_in, (size_t)count * d * sizeof(double)));
-    HIP_TRY(h, hipMalloc((void **)&td.d_t, (size_t)count * sizeof(double)));
-    HIP_TRY(h, hipMemcpy(td.d_in, inputs, (size_t)count * d * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(td.d_t, targets, (size_t)count * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(h, td.d_in.reset((size_t)count * d));
+    HIP_TRY(h, td.d_t.reset((size_t)count));
+    HIP_TRY(h, hipMemcpy(td.d_in.get(), inputs, (size_t)count * d * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(td.d_t.get(), targets, (size_t)count * sizeof(double), hipMemcpyHostToDevice));
     td.count = count;
     return SDPCUT_OK;
 }
@@ -341,17 +327,11 @@ int sdpcut_train_loss_grad(sdpcut_handle h, int k, int n_layers, const int32_t *
     A.pstride = n_grad + 1;
     // workspace: params | reduced gradient and loss | partial sums
     const size_t need = (size_t)n_params + (size_t)A.pstride * ((size_t)grid + 1);
-    if (need > h->train_ws_doubles) {
-        HIP_TRY(h, sdpcut_sync(h));
-        (void)hipFree(h->d_train_ws);
-        h->d_train_ws = nullptr;
-        h->train_ws_doubles = 0;
-        HIP_TRY(h, hipMalloc((void **)&h->d_train_ws, need * sizeof(double)));
-        h->train_ws_doubles = need;
-    }
-    double *d_params = h->d_train_ws, *d_out = d_params + n_params, *d_part = d_out + A.pstride;
+    int rc_ws = grow(h, h->d_train_ws, need);
+    if (rc_ws) return rc_ws;
+    double *d_params = h->d_train_ws.get(), *d_out = d_params + n_params, *d_part = d_out + A.pstride;
     HIP_TRY(h, hipMemcpyAsync(d_params, params, (size_t)n_params * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    A.in = td.d_in; A.tg = td.d_t; A.params = d_params; A.part = d_part;
+    A.in = td.d_in.get(); A.tg = td.d_t.get(); A.params = d_params; A.part = d_part;
     A.first = first; A.count = count;
     A.H = widths[0]; A.want_grad = grad ? 1 : 0;
     switch (k) {

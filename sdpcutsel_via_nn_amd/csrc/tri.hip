@@ -59,13 +59,13 @@ int tri_preprocess(sdpcut_ctx *h, const uint8_t *adjacency, int64_t *n_triples)
             }
     const int64_t T = (int64_t)d3.size();
     if (4 * T > 0x7fffffffLL) return sdpcut_fail(h, SDPCUT_EINVAL, "too many triangle inequalities");
-    (void)hipFree(h->d_tri); (void)hipFree(h->d_tri_dense3);
-    h->d_tri = nullptr; h->d_tri_dense3 = nullptr; h->n_tri = 0;
+    h->d_tri.release(); h->d_tri_dense3.release();
+    h->n_tri = 0;
     if (T > 0) {
-        HIP_TRY(h, hipMalloc((void **)&h->d_tri, (size_t)T * 3 * sizeof(int32_t)));
-        HIP_TRY(h, hipMalloc((void **)&h->d_tri_dense3, (size_t)T));
-        HIP_TRY(h, hipMemcpy(h->d_tri, tri.data(), (size_t)T * 3 * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMemcpy(h->d_tri_dense3, d3.data(), (size_t)T, hipMemcpyHostToDevice));
+        HIP_TRY(h, h->d_tri.reset((size_t)T * 3));
+        HIP_TRY(h, h->d_tri_dense3.reset((size_t)T));
+        HIP_TRY(h, hipMemcpy(h->d_tri.get(), tri.data(), (size_t)T * 3 * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIP_TRY(h, hipMemcpy(h->d_tri_dense3.get(), d3.data(), (size_t)T, hipMemcpyHostToDevice));
     }
     h->n_tri = T;
     h->tri_ready = true;
@@ -85,9 +85,9 @@ int tri_separate(sdpcut_ctx *h, int64_t max_out, int64_t *d_entry_out, double *d
         int rc = ensure_rank_ws(h, E > h->N ? E : h->N);      // (the selection below sizes the key array for the candidate list as well: it must not move)
         if (rc) return rc;
         h->last_total = -1;
-        HIP_TRY(h, hipMemsetAsync(h->d_counters, 0, 8 * sizeof(int64_t), h->stream));
-        hipLaunchKernelGGL(tri_viol_kernel, dim3((int)((T + 255) / 256)), dim3(256), 0, h->stream, T, h->d_tri,
-                           h->d_tri_dense3, h->d_vars, h->nb_vars, h->L, h->d_key_a, h->d_val_a, h->d_counters);
+        HIP_TRY(h, hipMemsetAsync(h->d_counters.get(), 0, 8 * sizeof(int64_t), h->stream));
+        hipLaunchKernelGGL(tri_viol_kernel, dim3((int)((T + 255) / 256)), dim3(256), 0, h->stream, T, h->d_tri.get(),
+                           h->d_tri_dense3.get(), h->d_vars.get(), h->nb_vars, h->L, h->d_key_a.get(), h->d_val_a.get(), h->d_counters.get());
         HIP_TRY(h, hipGetLastError());
         if (max_out > 0) {
             rc = topk_select_keys_on_device(h, E, max_out, d_entry_out, d_viol_out, cnt);
@@ -104,7 +104,7 @@ int tri_separate(sdpcut_ctx *h, int64_t max_out, int64_t *d_entry_out, double *d
                 if (cnt[4]) return sdpcut_fail(h, SDPCUT_EHIP, "tri_separate: selection void");
             }
         } else {
-            HIP_TRY(h, hipMemcpyAsync(cnt, h->d_counters, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(h, hipMemcpyAsync(cnt, h->d_counters.get(), sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
             HIP_TRY(h, sdpcut_sync(h));
         }
     }
@@ -156,21 +156,21 @@ void tri_out_from_block(const void *block, sdpcut_tri_csr_t *out)
 static int tri_round_pass(sdpcut_ctx *h, int64_t cap, int64_t *d_e, double *d_v, int64_t *void_flag)
 {
     const int64_t T = h->n_tri, E = 4 * T;
-    HIP_TRY(h, hipMemsetAsync(h->d_counters, 0, 8 * sizeof(int64_t), h->stream));
-    hipLaunchKernelGGL(tri_viol_kernel, dim3((int)((T + 255) / 256)), dim3(256), 0, h->stream, T, h->d_tri, h->d_tri_dense3,
-                       (const double *)(h->box_set ? h->d_vars_box : h->d_vars), h->nb_vars, h->L, h->d_key_a, h->d_val_a, h->d_counters);
+    HIP_TRY(h, hipMemsetAsync(h->d_counters.get(), 0, 8 * sizeof(int64_t), h->stream));
+    hipLaunchKernelGGL(tri_viol_kernel, dim3((int)((T + 255) / 256)), dim3(256), 0, h->stream, T, h->d_tri.get(), h->d_tri_dense3.get(),
+                       (const double *)(h->box_set ? h->d_vars_box.get() : h->d_vars.get()), h->nb_vars, h->L, h->d_key_a.get(), h->d_val_a.get(), h->d_counters.get());
     HIP_TRY(h, hipGetLastError());
     const int64_t *d_cnt = nullptr;
     if (cap > 0) {
         const int rc = topk_select_keys_enqueue(h, E, cap, d_e, d_v, &d_cnt);
         if (rc) return rc;
     }
-    hipLaunchKernelGGL(tri_emit_kernel, dim3(1), dim3(TRI_EMIT_WAVES * 64), 0, h->stream, cap, (const int64_t *)h->d_counters, d_cnt, (const int64_t *)d_e,
-                       (const double *)d_v, T, (const int32_t *)h->d_tri, (const double *)(h->box_set ? h->d_box_ld : nullptr), h->nb_vars, h->L,
-                       (char *)h->pinned_dev);
+    hipLaunchKernelGGL(tri_emit_kernel, dim3(1), dim3(TRI_EMIT_WAVES * 64), 0, h->stream, cap, (const int64_t *)h->d_counters.get(), d_cnt, (const int64_t *)d_e,
+                       (const double *)d_v, T, (const int32_t *)h->d_tri.get(), (const double *)(h->box_set ? h->d_box_ld.get() : nullptr), h->nb_vars, h->L,
+                       (char *)h->pinned.dev());
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, sdpcut_sync(h));      // the one wait of the call
-    *void_flag = ((const int64_t *)h->pinned)[3];
+    *void_flag = ((const int64_t *)h->pinned.get())[3];
     return 0;
 }
 
@@ -193,13 +193,13 @@ int sdpcut_tri_round_csr(sdpcut_handle h, const double *vars_values, int64_t max
     out->cap = cap;
     if ((rc = ensure_pinned(h, tri_layout(cap).bytes))) return rc;
     if (E == 0) {      // an empty list: an empty block, nothing launched
-        std::memset(h->pinned, 0, tri_layout(0).bytes);
-        tri_out_from_block(h->pinned, out);
+        std::memset(h->pinned.get(), 0, tri_layout(0).bytes);
+        tri_out_from_block(h->pinned.get(), out);
         return SDPCUT_OK;
     }
     if ((rc = ensure_stage(h, (size_t)(cap < 1 ? 1 : cap) * 16))) return rc;
-    int64_t *d_e = (int64_t *)h->d_stage;
-    double *d_v = (double *)((char *)h->d_stage + (size_t)(cap < 1 ? 1 : cap) * 8);
+    int64_t *d_e = (int64_t *)h->d_stage.get();
+    double *d_v = (double *)((char *)h->d_stage.get() + (size_t)(cap < 1 ? 1 : cap) * 8);
     if ((rc = ensure_rank_ws(h, E > h->N ? E : h->N))) return rc;      // (as tri_separate: the key array serves the candidate list as well)
     h->last_total = -1;
     int64_t vflag = 0;
@@ -214,7 +214,7 @@ int sdpcut_tri_round_csr(sdpcut_handle h, const double *vars_values, int64_t max
         if (rc) return rc;
         if (vflag) return sdpcut_fail(h, SDPCUT_EHIP, "tri_round_csr: selection void");
     }
-    tri_out_from_block(h->pinned, out);
+    tri_out_from_block(h->pinned.get(), out);
     return SDPCUT_OK;
 }
 

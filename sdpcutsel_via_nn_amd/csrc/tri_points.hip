@@ -189,66 +189,32 @@ __global__ __launch_bounds__(TRI_POINTS_THREADS) void tri_points_kernel(TriPoint
 }
 
 // ------------------------------------------------------------------------------------------
-// buffers (grown on demand; the call is synchronous, so nothing is in flight when one is replaced)
+// buffers (grown on demand through grow, common.h)
 
 struct TriPointsBufs {
-    void *stage = nullptr;          // pinned staging: the points [P][L + n], then the (l | d) rows [P][2 n]
-    size_t stage_bytes = 0;
-    double *d_pts = nullptr, *d_vb = nullptr, *d_ld = nullptr;
-    size_t pts_doubles = 0, vb_doubles = 0, ld_doubles = 0;
-    void *pinned = nullptr, *pinned_dev = nullptr;   // the batch block (tri_layout.h: tri_batch_layout)
-    size_t pinned_bytes = 0;
+    HostBuf stage{false};           // pinned staging (default memory: the source of a hipMemcpyAsync): the points [P][L + n], then the (l | d) rows [P][2 n]
+    DevBuf<double> d_pts, d_vb, d_ld;
+    HostBuf pinned{true};           // the batch block (tri_layout.h: tri_batch_layout)
 };
 
 void free_tri_points_ws(sdpcut_ctx *h)
 {
-    TriPointsBufs *b = (TriPointsBufs *)h->tri_pts;
-    if (!b) return;
-    if (b->stage) (void)hipHostFree(b->stage);
-    if (b->pinned) (void)hipHostFree(b->pinned);
-    (void)hipFree(b->d_pts); (void)hipFree(b->d_vb); (void)hipFree(b->d_ld);
-    delete b;
+    delete (TriPointsBufs *)h->tri_pts;
     h->tri_pts = nullptr;
-}
-
-static int grow_device(sdpcut_ctx *h, double **ptr, size_t *have, size_t want)
-{
-    if (*have >= want) return 0;
-    (void)hipFree(*ptr);
-    *ptr = nullptr;
-    *have = 0;
-    HIP_TRY(h, hipMalloc((void **)ptr, want * 8));
-    *have = want;
-    return 0;
 }
 
 static int ensure_tri_points(sdpcut_ctx *h, int P, bool boxed, bool tables, size_t block_bytes)
 {
     if (!h->tri_pts) h->tri_pts = new TriPointsBufs();
     TriPointsBufs &b = *(TriPointsBufs *)h->tri_pts;
-    if (b.pinned_bytes < block_bytes) {
-        HIP_TRY(h, sdpcut_sync(h));
-        if (b.pinned) (void)hipHostFree(b.pinned);
-        b.pinned = b.pinned_dev = nullptr;
-        b.pinned_bytes = 0;
-        HIP_TRY(h, hipHostMalloc(&b.pinned, block_bytes, hipHostMallocMapped));
-        HIP_TRY(h, hipHostGetDevicePointer(&b.pinned_dev, b.pinned, 0));
-        b.pinned_bytes = block_bytes;
-    }
+    int rc;
+    if ((rc = grow(h, b.pinned, block_bytes))) return rc;
     if (!tables) return 0;
     const size_t m = (size_t)(h->L + h->nb_vars), pts = (size_t)P * m, lds = boxed ? (size_t)P * 2 * (size_t)h->nb_vars : 0;
-    if (b.stage_bytes < (pts + lds) * 8) {
-        HIP_TRY(h, sdpcut_sync(h));
-        if (b.stage) (void)hipHostFree(b.stage);
-        b.stage = nullptr;
-        b.stage_bytes = 0;
-        HIP_TRY(h, hipHostMalloc(&b.stage, (pts + lds) * 8, hipHostMallocDefault));
-        b.stage_bytes = (pts + lds) * 8;
-    }
-    int rc;
-    if ((rc = grow_device(h, &b.d_pts, &b.pts_doubles, pts))) return rc;
-    if (boxed && (rc = grow_device(h, &b.d_vb, &b.vb_doubles, pts))) return rc;
-    if (boxed && (rc = grow_device(h, &b.d_ld, &b.ld_doubles, lds))) return rc;
+    if ((rc = grow(h, b.stage, (pts + lds) * 8))) return rc;
+    if ((rc = grow(h, b.d_pts, pts))) return rc;
+    if (boxed && (rc = grow(h, b.d_vb, pts))) return rc;
+    if (boxed && (rc = grow(h, b.d_ld, lds))) return rc;
     return 0;
 }
 
@@ -260,12 +226,10 @@ int sdpcut_tri_round_csr_points(sdpcut_handle h, int32_t n_points, const double 
     if (!h) return SDPCUT_EINVAL;
     const char *what = "sdpcut_tri_round_csr_points";
     if (!out) return sdpcut_fail(h, SDPCUT_EINVAL, "out is NULL");
-    if (n_points < 1 || n_points > SDPCUT_BATCH_MAX_POINTS)
-        return sdpcut_fail(h, SDPCUT_EINVAL, "n_points must be 1 .. SDPCUT_BATCH_MAX_POINTS (" + std::to_string(SDPCUT_BATCH_MAX_POINTS) + ")");
-    if (!points) return sdpcut_fail(h, SDPCUT_EINVAL, "points is NULL");
-    if (!h->d_vars) return sdpcut_fail(h, SDPCUT_ESTATE, "set_instance first");
-    if (point_ld < h->L + h->nb_vars) return sdpcut_fail(h, SDPCUT_EINVAL, "point_ld must be at least L + n");
-    if ((lb == nullptr) != (ub == nullptr)) return sdpcut_fail(h, SDPCUT_EINVAL, std::string(what) + ": lb and ub must both be given or both be NULL");
+    int rc;
+    if ((rc = check_point_batch(h, "", n_points, points, point_ld, h->L + h->nb_vars))) return rc;
+    if (!h->d_vars.get()) return sdpcut_fail(h, SDPCUT_ESTATE, "set_instance first");
+    if ((rc = check_box_pair(h, "sdpcut_tri_round_csr_points: ", lb, ub))) return rc;
     if (max_out < 0 || max_out > 16384) return sdpcut_fail(h, SDPCUT_EINVAL, std::string(what) + ": max_out must be 0 .. 16384");
     if (!h->tri_ready) return sdpcut_fail(h, SDPCUT_ESTATE, std::string(what) + ": sdpcut_tri_preprocess first");
     SDPCUT_NO_PENDING(h);
@@ -273,7 +237,6 @@ int sdpcut_tri_round_csr_points(sdpcut_handle h, int32_t n_points, const double 
     const int P = n_points;
     const int32_t nv = h->nb_vars;
     const bool boxed = lb != nullptr;
-    int rc;
     if (boxed) {
         if (h->exact_head) return sdpcut_fail(h, SDPCUT_ESTATE, std::string(what) + ": SDPCUT_OPT_EXACT_HEAD is on (reference-exact heads have no node box)");
         for (int p = 0; p < P; ++p)
@@ -289,42 +252,38 @@ int sdpcut_tri_round_csr_points(sdpcut_handle h, int32_t n_points, const double 
     const TriBatchLayout y = tri_batch_layout(cap, P);
     if ((rc = ensure_tri_points(h, P, boxed, route == TRI_FAST, y.bytes))) return rc;
     TriPointsBufs &b = *(TriPointsBufs *)h->tri_pts;
-    char *block = (char *)b.pinned;
+    char *block = (char *)b.pinned.get();
     if (route == TRI_LOOP) {
         for (int p = 0; p < P; ++p) {
             if (boxed && (rc = sdpcut_set_box(h, lb + (size_t)p * nv, ub + (size_t)p * nv))) return rc;
             if ((rc = sdpcut_tri_round_csr(h, points + (size_t)p * point_ld, max_out, out + p))) return rc;
-            std::memcpy(block + y.slice * (size_t)p, h->pinned, tri_layout(cap).bytes);
+            std::memcpy(block + y.slice * (size_t)p, h->pinned.get(), tri_layout(cap).bytes);
             tri_out_from_block(block + y.slice * (size_t)p, out + p);
         }
         return SDPCUT_OK;
     }
 
-    double *st = (double *)b.stage;
-    for (int p = 0; p < P; ++p) std::memcpy(st + (size_t)p * m, points + (size_t)p * point_ld, (size_t)m * 8);
-    HIP_TRY(h, hipMemcpyAsync(b.d_pts, st, (size_t)P * m * 8, hipMemcpyHostToDevice, h->stream));
+    double *st = (double *)b.stage.get();
+    pack_points(st, P, points, point_ld, m);
+    HIP_TRY(h, hipMemcpyAsync(b.d_pts.get(), st, (size_t)P * m * 8, hipMemcpyHostToDevice, h->stream));
     if (boxed) {
         double *ld = st + (size_t)P * m;      // the (l | d) rows as sdpcut_set_box forms them
-        for (int p = 0; p < P; ++p)
-            for (int32_t i = 0; i < nv; ++i) {
-                ld[(size_t)p * 2 * nv + i] = lb[(size_t)p * nv + i];
-                ld[(size_t)p * 2 * nv + nv + i] = ub[(size_t)p * nv + i] - lb[(size_t)p * nv + i];
-            }
-        HIP_TRY(h, hipMemcpyAsync(b.d_ld, ld, (size_t)P * 2 * nv * 8, hipMemcpyHostToDevice, h->stream));
-        if ((rc = launch_box_points(h, P, b.d_pts, m, b.d_ld, nullptr, b.d_vb))) return rc;
+        pack_box_ld(ld, P, nv, lb, nv, ub, nv);
+        HIP_TRY(h, hipMemcpyAsync(b.d_ld.get(), ld, (size_t)P * 2 * nv * 8, hipMemcpyHostToDevice, h->stream));
+        if ((rc = launch_box_points(h, P, b.d_pts.get(), m, b.d_ld.get(), nullptr, b.d_vb.get()))) return rc;
     }
     TriPointsArgs A;
     A.T = T;
-    A.tri = h->d_tri;
-    A.dense3 = h->d_tri_dense3;
-    A.vars = boxed ? b.d_vb : b.d_pts;
+    A.tri = h->d_tri.get();
+    A.dense3 = h->d_tri_dense3.get();
+    A.vars = boxed ? b.d_vb.get() : b.d_pts.get();
     A.vars_stride = m;
-    A.ld = boxed ? b.d_ld : nullptr;
+    A.ld = boxed ? b.d_ld.get() : nullptr;
     A.nv = nv;
     A.L = h->L;
     A.max_out = max_out;
     A.cap = cap;
-    A.block = (char *)b.pinned_dev;
+    A.block = (char *)b.pinned.dev();
     A.slice = (int64_t)y.slice;
     hipLaunchKernelGGL(tri_points_kernel, dim3((unsigned)P), dim3(TRI_POINTS_THREADS), 0, h->stream, A);
     HIP_TRY(h, hipGetLastError());

@@ -89,7 +89,7 @@ def test_the_consumers_are_where_the_table_says():
     look-back -- a path that moves or goes is a table to revisit"""
     src = {name: _read(CSRC, name) for name in ("round.hip", "rank.hip", "topk.hip", "tri.hip", "points.hip", "shard.hip")}
     assert "keep = !c[4] &&" in src["round.hip"] and "if (c[4] == 1) ++h->stat_fallbacks" in src["round.hip"]
-    assert "exact_head_verdict(h, (const int64_t *)h->pinned, P.exact_band)" in src["round.hip"]
+    assert "exact_head_verdict(h, (const int64_t *)h->pinned.get(), P.exact_band)" in src["round.hip"]
     assert "if (have && P.csr && hdr[10] && w > 0)" in src["round.hip"] and "csr_head_again(h, P, w, 1)" in src["round.hip"]
     assert "if (P.fast_tried && !have && hdr[4]) ++h->stat_fallbacks" in src["round.hip"]
     assert "if (launches > 0 || count_failure) ++h->stat_fallbacks" in src["round.hip"]
