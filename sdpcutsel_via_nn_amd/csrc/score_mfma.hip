@@ -234,6 +234,7 @@ struct MfmaLdsSkip {
     static constexpr int S0 = (K + K * (K + 1) / 2 + 3) / 4;
     static constexpr int T = (H + 15) / 16;
     static constexpr int NT = (H - 16 * (T - 1) <= 4) ? H - 16 * (T - 1) : 0;
+    static constexpr int DIN = K + K * (K + 1) / 2;
     static constexpr int QCAP = 96;
     double feat[4][S0 * 4][QCAP];
     double ynn[4][QCAP];
@@ -243,6 +244,7 @@ struct MfmaLdsSkip {
     double s_bias[NH * 64];
     double s_wtail[NT ? NH * 4 * 64 : 1];
     double s_wout[64];
+    alignas(16) double s_stage[DIN][2];      // launch constants of the staging loop, per feature: xoffset, gain (stage_lds_fill)
     uint32_t tk_hist[256];
     uint32_t tk_cnt[2];
     uint32_t s_strong;
@@ -286,6 +288,7 @@ struct MfmaLdsFilter {
     double s_bias[NH * 64];
     double s_wtail[NT ? NH * 4 * 64 : 1];
     double s_wout[64];
+    alignas(16) double s_stage[DIN][4];      // launch constants of the staging loop, per feature: xoffset, gain, box lo, box hi
     uint32_t tk_hist[256];
     uint32_t tk_cnt[3];
     uint32_t s_strong;
@@ -325,6 +328,20 @@ __device__ __forceinline__ void filter_lds_fill(const NetDev &net, FilterLds<NH>
         F.v[FilterLds<NH>::BIAS + i] = w;
     }
     for (int i = threadIdx.x; i < FilterLds<NH>::SLOPE; i += blockDim.x) F.v[FilterLds<NH>::BIAS + FilterLds<NH>::TAIL + i] = net.f32_g[i];
+}
+
+// The launch constants the strip loop's staging reads per feature, copied next to each other into LDS (s_stage of MfmaLdsSkip /
+// MfmaLdsFilter): the input mapping's xoffset and gain, and with BOX the feature's interval of NetDev::filter_box.  Read through
+// the NetDev pointers inside the strip loop they are vector loads from a uniform address, one L2 round trip each and -- behind
+// the short-circuit of the box test -- one after the other.  Call before a __syncthreads().
+template <int DIN, bool BOX, int W>
+__device__ __forceinline__ void stage_lds_fill(const NetDev &net, double (&C)[DIN][W])
+{
+    static_assert(W == (BOX ? 4 : 2), "xoffset, gain (, lo, hi) per feature");
+    if (threadIdx.x < 2 * DIN) {
+        C[threadIdx.x % DIN][threadIdx.x / DIN] = net.inmap[threadIdx.x];
+        if constexpr (BOX) C[threadIdx.x >> 1][2 + (threadIdx.x & 1)] = net.filter_box[threadIdx.x];
+    }
 }
 
 // The margin of ONE candidate from the slope sum S its fp32 pass returned (net_pack.h: net_filter_slope_terms has the derivation):
@@ -627,6 +644,7 @@ __device__ __forceinline__ void score_mfma_body(const ScoreArgs A, LDS &S, const
             for (int i = threadIdx.x; i < NH * 4 * 64; i += 256) s_wtail[i] = net.wtail[i];
         if (threadIdx.x < 64) s_wout[threadIdx.x] = net.wout[threadIdx.x];
         if constexpr (FILTER) filter_lds_fill<NH>(net, S.s_f32);
+        if constexpr (SKIP) stage_lds_fill<DIN, FILTER>(net, S.s_stage);
         __syncthreads();
     }
 #endif
@@ -734,14 +752,17 @@ __device__ __forceinline__ void score_mfma_body(const ScoreArgs A, LDS &S, const
 #pragma unroll
         for (int i = 0; i < S0 * 4; ++i) {
             double xp = 0.0;
+            [[maybe_unused]] const int ic = i < DIN ? i : 0;
             if (i < DIN) {
                 const double v = (i < K) ? cd.x[i < K ? i : 0] : cd.q[i >= K ? i - K : 0];
-                xp = (v - net.inmap[i]) * net.inmap[DIN + i] + net.ymin;
+                if constexpr (SKIP) xp = (v - S.s_stage[ic][0]) * S.s_stage[ic][1] + net.ymin;
+                else xp = (v - net.inmap[i]) * net.inmap[DIN + i] + net.ymin;
                 if constexpr (!CLAMP) xp = min_f64_raw(max_f64_raw(xp, -SDPCUT_INPUT_CLAMP), SDPCUT_INPUT_CLAMP);
             }
             if constexpr (FILTER) {
                 if (i < DIN) {
-                    f_outside = f_outside || !(xp >= net.filter_box[2 * i] && xp <= net.filter_box[2 * i + 1]);      // (a NaN is outside)
+                    // (a NaN is outside, the bounds are inclusive; no short-circuit: the constants of a strip are requested together)
+                    f_outside = f_outside | !((xp >= S.s_stage[ic][2]) & (xp <= S.s_stage[ic][3]));
                     if (q_viol) S.f_feat[wave][i][q_slot] = xp;
                 }
             } else if constexpr (SKIP) {
@@ -1183,6 +1204,7 @@ template <int K, int H, int NH, bool CLAMP>
 __global__ __launch_bounds__(256, 2) void score_mfma_skip_kernel(ScoreArgs A)
 {
     static_assert(sizeof(MfmaLdsSkip<K, H, NH>) <= 80 * 1024, "two workgroups of the skipping kernel must fit a CU's LDS");
+    static_assert(SDPCUT_SMALL_IN_LDS, "the staging constants (s_stage) are filled with the small weights");
     __shared__ MfmaLdsSkip<K, H, NH> S;
     score_mfma_body<K, H, NH, TK_MODE_STRONG, CLAMP, 2, true>(A, S, (int)blockIdx.x, (int)gridDim.x);
 }
@@ -1193,9 +1215,12 @@ template <int K, int H, int NH>
 __global__ __launch_bounds__(256, 2) void score_mfma_filter_kernel(ScoreArgs A)
 {
     static_assert(sizeof(MfmaLdsFilter<K, H, NH>) <= 80 * 1024, "two workgroups of the filtering kernel must fit a CU's LDS");
+    static_assert(SDPCUT_SMALL_IN_LDS, "the staging constants (s_stage) are filled with the small weights");
     __shared__ MfmaLdsFilter<K, H, NH> S;
     score_mfma_body<K, H, NH, TK_MODE_STRONG, false, 2, true, MfmaLdsFilter<K, H, NH>, true>(A, S, (int)blockIdx.x, (int)gridDim.x);
 }
+
+static_assert(2 * sizeof(MfmaLdsFilter<3, 50, 3>) <= 160 * 1024, "two workgroups of the shipped K = 3 filtering kernel per CU (160 KiB of LDS)");
 
 // sdpcut_filter_audit: the fp32 pass of the filter -- the same device function as stage F -- for EVERY candidate of the class, its
 // output unmapped into y32_out and, where asked for, its margin (filter_cand_margin) into m_out (caller order).  Not on the hot path: a wave takes 32 candidates at a time, stages their mapped
