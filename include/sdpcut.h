@@ -282,7 +282,18 @@ int sdpcut_destroy(sdpcut_handle h);
 int sdpcut_set_option(sdpcut_handle h, int option, int64_t value);
 /* Run all work of this handle on an existing HIP stream (hipStream_t passed as void*).
  * NULL is the HIP null stream (what PyTorch calls its default stream);
- * SDPCUT_OWN_STREAM restores the handle's own non-blocking stream. */
+ * SDPCUT_OWN_STREAM restores the handle's own non-blocking stream.
+ * Order: every launch, copy and event of the library goes to the handle's stream, and device pointers passed to it
+ * (d_vars_values, d_idx_out, d_record, d_allrec, ...) are read and written in that stream's order: produce them on the stream,
+ * consume them on it, and no host synchronisation is needed.  A switch to ANOTHER stream orders the new stream, on the device,
+ * behind everything the handle has enqueued on the old one; the caller need not synchronise first, and the call does not wait on
+ * the host (except for a staged sdpcut_set_point transfer still in flight, whose source is host memory).  That matters after the
+ * entry points that return without a host wait: sdpcut_score, sdpcut_set_point, sdpcut_set_point_device, sdpcut_wake,
+ * sdpcut_round_csr_begin, sdpcut_merge_topk_device, sdpcut_gather_scores_device, sdpcut_shard_head_device and
+ * sdpcut_shard_finish_enqueue (sdpcut_set_box and sdpcut_rank_device wait first and leave only their last launches behind).
+ * With the stream the handle already has the call changes nothing.
+ * Lifetime: the stream stays the caller's.  It must outlive its use by the handle -- until a later sdpcut_set_stream has moved
+ * the handle off it (that call still records an event on it) or sdpcut_destroy. */
 #define SDPCUT_OWN_STREAM ((void *)(intptr_t)-1)
 int sdpcut_set_stream(sdpcut_handle h, void *hip_stream);
 int sdpcut_synchronize(sdpcut_handle h);

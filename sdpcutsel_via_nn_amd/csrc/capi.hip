@@ -91,6 +91,7 @@ int sdpcut_destroy(sdpcut_handle h)
         if (h->ev_join[i]) hipEventDestroy(h->ev_join[i]);
     }
     if (h->ev_fork) hipEventDestroy(h->ev_fork);
+    if (h->ev_switch) hipEventDestroy(h->ev_switch);
     if (h->own_stream) hipStreamDestroy(h->own_stream);
     delete h;
     return SDPCUT_OK;
@@ -319,8 +320,19 @@ int sdpcut_filter_audit_margins(sdpcut_handle h, double *y32_out, double *m_out)
 int sdpcut_set_stream(sdpcut_handle h, void *hip_stream)
 {
     if (!h) return SDPCUT_EINVAL;
-    if (h->point_inflight) (void)sdpcut_sync(h);     // the staging copy's transfer lives on the old stream
-    h->stream = (hip_stream == SDPCUT_OWN_STREAM) ? h->own_stream : (hipStream_t)hip_stream;
+    // the staging copy's transfer lives on the old stream, and its source is host memory the caller may overwrite: a host wait
+    if (h->point_inflight) (void)sdpcut_sync(h);
+    const hipStream_t next = (hip_stream == SDPCUT_OWN_STREAM) ? h->own_stream : (hipStream_t)hip_stream;
+    if (next != h->stream) {
+        // Calls that return without waiting (sdpcut_score, sdpcut_set_point_device, ...) may still have work on the old stream that
+        // the next call reads the results of: the new stream waits, on the device, for everything enqueued there so far.  Two
+        // non-blocking streams are ordered by nothing else.  No host wait; a handle that never switches never comes here.
+        HIP_TRY(h, hipSetDevice(h->device));
+        if (!h->ev_switch) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_switch, hipEventDisableTiming));
+        HIP_TRY(h, hipEventRecord(h->ev_switch, h->stream));
+        HIP_TRY(h, hipStreamWaitEvent(next, h->ev_switch, 0));
+    }
+    h->stream = next;
     h->topk_alt_clean = false;   // its zeroing was ordered on the previous stream only
     return SDPCUT_OK;
 }

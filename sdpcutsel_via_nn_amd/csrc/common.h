@@ -119,6 +119,7 @@ struct PointsBufs {
 struct sdpcut_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr, stream = nullptr;
+    hipEvent_t ev_switch = nullptr;      // sdpcut_set_stream: orders the new stream behind the old one; created by the first switch
     // the small size classes of a mixed cover are scored on side streams next to the largest one (launch_score)
     bool one_launch = true;      // SDPCUT_OPT_ONE_LAUNCH: the size classes of a mixed list in one launch (score_mfma_all_kernel)
     int side_streams = 0;        // SDPCUT_OPT_SIDE_STREAMS: 0 off (default since r4: no code path picked by a timing), 1 on, 2 measured once per candidate list (side_choice)

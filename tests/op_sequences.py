@@ -14,7 +14,8 @@ operations run a selection round; every ordered pair of families with a round-li
 `point` operation in between (adjacent keeps the scored measures of X alive into Y).
 
 Left out on purpose: the sharded calls (sdpcut_shard_*, rank_device, merge / gather on device buffers -- they need a second
-runtime's buffers and a process group), set_stream (a caller's stream changes ordering, not results, and needs torch),
+runtime's buffers and a process group), set_stream (a caller's stream changes ordering, not results, and needs torch:
+stream_cases.py / test_gpu_streams.py run this alphabet on a caller's stream, and the device-pointer calls in stream order),
 SDPCUT_OPT_INJECT_GIVEUP (test only; it changes no result either, and giveup_cases.py / test_gpu_giveup.py run it against fresh
 handles in the same way -- LEFT_OUT_OPTIONS below names it, and the model's statistics list knows SDPCUT_STAT_INJECTED),
 SDPCUT_OPT_COOP_LAUNCH (another way to launch the same selection kernel: it changes no result and no state a later call reads) and
