@@ -16,12 +16,21 @@
 //   strong_points_kernel      combined strategy: neither launch saw both measures, so the strong class is counted here
 // and the selection and the assembly run as they are -- they read scores, heads and the original points, never Q.  The split is
 // the one launch_score makes for a single point with a box (score.hip); still ONE host wait.
-// The filtered batch (sdpcut_round_csr_points_diverse; strategies 1, 2, 4 and 6) is the same chain with a longer head and a filter:
+// The host side of a batched round is ONE driver, round_points, told by a PointsRound what differs between its callers:
+//   intake and refusals, all before any state changes; the route (batch_route.h) and what overrides it; the batch block
+//   BATCH_LOOP: every point through the single-point call, its block copied into the point's slice
+//   BATCH_FAST: upload, scores, selection, row assembly, the one wait; then per point the verdict of its selection --
+//     answered; answered, but the assembly gave up its bounded look-back: assembled once more, a second wait, an error if that
+//     gives up too; void: redone through the single-point call, after everything else, over its slice
+// The filtered batch (sdpcut_round_csr_points_diverse; strategies 1, 2, 4 and 6) is the same chain with a longer head and a filter
+// (PointsFilter):
 //   efficacy_points_kernel    (efficacy.hip) strategy 6: the efficacy score of every point, behind the eigenvalue launch
 //   tk_points_kernel          k = the pool, the quota as `sel`
 //   div_rows_points_kernel, div_points_kernel   (diverse.hip) the pool's rows, then one workgroup per point filters its pool in LDS
 //   round_csr_points_kernel   over the accepted heads, their lengths read from the walk's counts
-// and sdpcut_efficacy_points is the eigenvalue launch and the efficacy launch alone.
+// its verdict reads the selection's counters where the filter left them, a ranking shorter than the quota gets the block of its
+// own length, and the single-point call is sdpcut_round_csr_diverse.  sdpcut_efficacy_points is the eigenvalue launch and the
+// efficacy launch alone.
 #include <cstring>
 #include <vector>
 
@@ -167,6 +176,8 @@ static int check_batch_state(sdpcut_ctx *h, int32_t n_points, const double *poin
 struct BoxRows {
     const double *lb, *ub;
     int64_t ld;
+    const double *lo(int p) const { return lb + (size_t)p * ld; }      // the box of point p
+    const double *hi(int p) const { return ub + (size_t)p * ld; }
 };
 
 // the P points into the staging block and, by one launch, into the device table; ws: see points_copy_kernel.  bx (a boxed batch):
@@ -196,7 +207,7 @@ static int check_box_rows(sdpcut_ctx *h, const char *what, int P, const BoxRows 
     if (bx.ld < h->nb_vars) return sdpcut_fail(h, SDPCUT_EINVAL, std::string(what) + ": box_ld must be at least n");
     if (h->exact_head) return sdpcut_fail(h, SDPCUT_ESTATE, std::string(what) + ": SDPCUT_OPT_EXACT_HEAD is on (reference-exact heads have no node box)");
     for (int p = 0; p < P; ++p) {
-        const int rc = box_check(h, what, p, bx.lb + (size_t)p * bx.ld, bx.ub + (size_t)p * bx.ld);
+        const int rc = box_check(h, what, p, bx.lo(p), bx.hi(p));
         if (rc) return rc;
     }
     return 0;
@@ -230,11 +241,10 @@ static int score_batch(sdpcut_ctx *h, uint32_t flags, int P, bool boxed, int64_t
     return 0;
 }
 
-// One point through the single-point round (sdpcut_round_csr: the handle's single-point arrays and pinned block are its scratch);
-// the block it returns is copied into `slot` and *out points there.
-static int point_through_round(sdpcut_ctx *h, const double *point, int strat, int64_t sel_size, char *slot, sdpcut_round_csr_t *out)
+// One point has gone through a single-point round (rc: what the call returned; the handle's single-point arrays and pinned block
+// are its scratch): the block it returned is copied into `slot` and *out points there.
+static int round_into_slot(sdpcut_ctx *h, int rc, char *slot, sdpcut_round_csr_t *out)
 {
-    const int rc = sdpcut_round_csr(h, point, strat, sel_size, out);
     if (rc) return rc;
     if (out->cap > 0 && out->idx) {
         std::memcpy(slot, h->pinned.get(), csr_layout(out->cap, out->row_ld).bytes);
@@ -266,7 +276,7 @@ static int score_points_impl(sdpcut_ctx *h, const char *what, int32_t n_points, 
     if (!(flags & SDPCUT_NN)) bx = nullptr;      // lambda_min knows no box
     if (!batch_score_served(h, flags, bx != nullptr)) {      // a kernel variant without a point axis: point by point
         for (int p = 0; p < P; ++p) {
-            if (bx && (rc = sdpcut_set_box(h, bx->lb + (size_t)p * bx->ld, bx->ub + (size_t)p * bx->ld))) return rc;
+            if (bx && (rc = sdpcut_set_box(h, bx->lo(p), bx->hi(p)))) return rc;
             if ((rc = sdpcut_set_point(h, points + (size_t)p * point_ld))) return rc;
             if ((rc = sdpcut_score(h, flags))) return rc;
             if ((rc = sdpcut_get_scores(h, (flags & SDPCUT_EIG) ? eig_out + p * N : nullptr, (flags & SDPCUT_NN) ? obj_out + p * N : nullptr))) return rc;
@@ -279,109 +289,6 @@ static int score_points_impl(sdpcut_ctx *h, const char *what, int32_t n_points, 
     if (flags & SDPCUT_EIG) HIP_TRY(h, hipMemcpyAsync(eig_out, h->pts.d_eig.get(), (size_t)P * N * 8, hipMemcpyDeviceToHost, h->stream));
     if (flags & SDPCUT_NN) HIP_TRY(h, hipMemcpyAsync(obj_out, h->pts.d_obj.get(), (size_t)P * N * 8, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, sdpcut_sync(h));
-    return SDPCUT_OK;
-}
-
-// sdpcut_round_csr_points (bx == NULL) and sdpcut_round_csr_points_boxed under the name `what`
-static int round_csr_points_impl(sdpcut_ctx *h, const char *what, int32_t n_points, const double *points, int64_t point_ld, const BoxRows *bx,
-                                 int strat, int64_t sel_size, sdpcut_round_csr_t *out)
-{
-    if (!out) return sdpcut_fail(h, SDPCUT_EINVAL, "out is NULL");
-    int rc = check_batch_state(h, n_points, points, point_ld);
-    if (rc) return rc;
-    if (strat == SDPCUT_STRAT_EFF)
-        return sdpcut_fail(h, SDPCUT_EINVAL, std::string(what) + ": strategy 6 (efficacy) is not served over several points; strategies 1, 2 and 4 are");
-    if (!batch_mode(strat))
-        return sdpcut_fail(h, SDPCUT_EINVAL, std::string(what) + " serves strategies 1 (feasibility), 2 (optimality) and 4 (combined)");
-    if (sel_size < 0) return sdpcut_fail(h, SDPCUT_EINVAL, "sel_size is negative");
-    SDPCUT_NO_PENDING(h);
-    SDPCUT_NO_BOX(h, what);
-    if (bx && (rc = check_box_rows(h, what, n_points, *bx))) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    NoPointAfter leave(h);
-    NoBoxAfter unboxed(h);
-    const int P = n_points;
-    std::memset(out, 0, (size_t)P * sizeof(*out));
-    const int64_t cap = sel_size < h->N ? sel_size : h->N;
-    const int ld = h->row_len_max;
-    const uint32_t need = strat_need(strat);
-    const bool shard = h->base != 0 || h->shard_rec != nullptr;
-    int route = bx ? batch_route_boxed(h->N, cap, strat, h->exact_head, shard, h->nb_vars, P) : batch_route(h->N, cap, strat, h->exact_head, shard);
-    // the boxes reach the device only where the measure is scored (lambda_min knows no box); the per-point rounds always get theirs
-    const BoxRows *bx_dev = (need & SDPCUT_NN) ? bx : nullptr;
-    // what the route function does not see: a kernel variant without a point axis, the combined regime resolved on the host
-    // (SDPCUT_OPT_AUTO_REGIME off), event timing of the single-point launches
-    if (route == BATCH_FAST && (!batch_score_served(h, need, bx_dev != nullptr) || (strat == SDPCUT_STRAT_COMB && !h->auto_regime) || h->timing))
-        route = BATCH_LOOP;
-    const BatchLayout y = batch_layout(cap, ld, P);
-    if ((rc = grow(h, h->pts.pinned, y.bytes))) return rc;
-    char *block = (char *)h->pts.pinned.get();
-    // one point through the single-point round, in its box where the batch has boxes
-    auto single = [&](int p) -> int {
-        int rc1;
-        if (bx && (rc1 = sdpcut_set_box(h, bx->lb + (size_t)p * bx->ld, bx->ub + (size_t)p * bx->ld))) return rc1;
-        return point_through_round(h, points + (size_t)p * point_ld, strat, sel_size, block + batch_point_offset(y, p), out + p);
-    };
-    if (route == BATCH_LOOP) {
-        for (int p = 0; p < P; ++p)
-            if ((rc = single(p))) return rc;
-        return SDPCUT_OK;
-    }
-
-    if ((rc = ensure_points_scores(h, P))) return rc;
-    if ((rc = ensure_points_select(h, P, cap))) return rc;
-    PointsBufs &b = h->pts;
-    TopkWs *ws = (TopkWs *)b.d_ws.get();
-    const int64_t ws_words = (int64_t)(sizeof(TopkWs) / 8), n = h->L + h->nb_vars;
-    if ((rc = upload_points(h, P, points, point_ld, ws, bx_dev))) return rc;
-    // the strong class of the combined strategy: counted by the score launch (a boxed batch: by strong_points_kernel behind its two
-    // launches), point p into ws[p].strong_rep
-    int64_t *strong = need == (SDPCUT_EIG | SDPCUT_NN) ? ws->strong_rep : nullptr;
-    if ((rc = score_batch(h, need, P, bx_dev != nullptr, strong, ws_words))) return rc;
-    const double *eig = (need & SDPCUT_EIG) ? b.d_eig.get() : nullptr, *obj = (need & SDPCUT_NN) ? b.d_obj.get() : nullptr;
-    hipLaunchKernelGGL(tk_points_kernel, dim3((unsigned)P), dim3(TK_SMALLSEL_THREADS), 0, h->stream, batch_mode(strat), cap, (int)h->N, (int)cap, eig,
-                       obj, h->N, ws, strat == SDPCUT_STRAT_COMB ? SDPCUT_BIG_M : 0.0, b.d_idx.get(), b.d_score.get());
-    HIP_TRY(h, hipGetLastError());
-    for (int p = 0; p < P; ++p) std::memset(block + batch_point_offset(y, p), 0, 128);      // headers: counters, n_rows, nnz, give-up flag
-    rc = launch_round_csr_points(h, 0, P, cap, ld, ws->counters, ws_words, b.d_idx.get(), b.d_score.get(), b.d_pts.get(), n, eig, h->N, b.d_agg.get(), BATCH_AGG_WORDS,
-                                 b.pinned.dev(), (int64_t)y.slice, ++h->round_serial);
-    if (rc) return rc;
-    HIP_TRY(h, sdpcut_sync(h));      // the one wait of the batch (a faulted kernel surfaces here as an error)
-
-    std::vector<int> redo, again;
-    for (int p = 0; p < P; ++p) {
-        const int64_t *hdr = (const int64_t *)(block + batch_point_offset(y, p));
-        sdpcut_round_csr_t &o = out[p];
-        o.cap = cap;
-        o.row_ld = ld;
-        if (!rank_fast_finish(h, strat, sel_size, cap, hdr, &o.n_out, &o.n_total, &o.new_strat, o.counters)) {
-            redo.push_back(p);      // a void selection: the single-point round resolves it (tie split or full sort)
-            continue;
-        }
-        ++h->stat_rounds;
-        if (hdr[10] && o.n_out > 0) again.push_back(p);
-    }
-    // a point whose row assembly gave up its bounded look-back (rows.hip): once more over the same head, like csr_assemble_wait (round.hip)
-    for (int p : again) {
-        int64_t *hdr = (int64_t *)(block + batch_point_offset(y, p));
-        hdr[8] = hdr[9] = hdr[10] = 0;
-        ++h->stat_fallbacks;
-        rc = launch_round_csr_points(h, p, 1, cap, ld, ws->counters, ws_words, b.d_idx.get(), b.d_score.get(), b.d_pts.get(), n, eig, h->N, b.d_agg.get(), BATCH_AGG_WORDS,
-                                     b.pinned.dev(), (int64_t)y.slice, ++h->round_serial);
-        if (rc) return rc;
-    }
-    if (!again.empty()) {
-        HIP_TRY(h, sdpcut_sync(h));
-        for (int p : again)
-            if (((const int64_t *)(block + batch_point_offset(y, p)))[10])
-                return sdpcut_fail(h, SDPCUT_EHIP, "round_csr_points: look-back of the row assembly timed out twice");
-    }
-    for (int p = 0; p < P; ++p) csr_out_from_block(block + batch_point_offset(y, p), out + p);      // (the redone ones are overwritten below)
-    for (int p : redo) {
-        ++h->stat_points_redone;
-        std::memset(out + p, 0, sizeof(*out));
-        if ((rc = single(p))) return rc;
-    }
     return SDPCUT_OK;
 }
 
@@ -471,56 +378,85 @@ static int efficacy_points_impl(sdpcut_ctx *h, int32_t n_points, const double *p
     return SDPCUT_OK;
 }
 
-static int round_csr_points_diverse_impl(sdpcut_ctx *h, int32_t n_points, const double *points, int64_t point_ld, const BoxRows *bx, int strat,
-                                         int64_t sel_size, int64_t pool_size, double max_parallel, sdpcut_round_csr_t *out,
-                                         sdpcut_diverse_info_t *info)
+// What the filtered batch adds to the plain one, and what differs between the two batched rounds: all the driver is told.
+struct PointsFilter {
+    int64_t pool_size;
+    double max_parallel;
+    sdpcut_diverse_info_t *info;      // [n_points] or NULL
+};
+struct PointsRound {
+    const char *what;      // the entry point's name, for the refusals
+    const BoxRows *bx;      // a box per point, or NULL
+    int strat;
+    int64_t sel_size;
+    const PointsFilter *filter;      // NULL: sdpcut_round_csr_points[_boxed]
+};
+
+// The one-wait batched round: sdpcut_round_csr_points[_boxed] (R.filter == NULL) and sdpcut_round_csr_points_diverse.
+static int round_points(sdpcut_ctx *h, const PointsRound &R, int32_t n_points, const double *points, int64_t point_ld, sdpcut_round_csr_t *out)
 {
-    const char *what = "sdpcut_round_csr_points_diverse";
+    const PointsFilter *F = R.filter;
+    const BoxRows *bx = R.bx;
+    const int strat = R.strat;
+    const int64_t sel_size = R.sel_size;
+    sdpcut_diverse_info_t *info = F ? F->info : nullptr;
     if (!out) return sdpcut_fail(h, SDPCUT_EINVAL, "out is NULL");
     int rc = check_batch_state(h, n_points, points, point_ld);
     if (rc) return rc;
-    if (!batch_mode_diverse(strat))
-        return sdpcut_fail(h, SDPCUT_EINVAL, std::string(what) + " serves strategies 1 (feasibility), 2 (optimality), 4 (combined) and 6 (efficacy)");
-    if (!(max_parallel >= 0.0 && max_parallel <= 1.0)) return sdpcut_fail(h, SDPCUT_EINVAL, "max_parallel must lie in [0, 1]");
-    if (sel_size < 1) return sdpcut_fail(h, SDPCUT_EINVAL, "sel_size must be >= 1");
-    if (pool_size < sel_size) return sdpcut_fail(h, SDPCUT_EINVAL, "pool_size must be >= sel_size");
-    if (pool_size > SDPCUT_DIVERSE_MAX_POOL) return sdpcut_fail(h, SDPCUT_EINVAL, "pool_size must not exceed SDPCUT_DIVERSE_MAX_POOL");
+    if (F) {
+        if (!batch_mode_diverse(strat))
+            return sdpcut_fail(h, SDPCUT_EINVAL, std::string(R.what) + " serves strategies 1 (feasibility), 2 (optimality), 4 (combined) and 6 (efficacy)");
+        if (!(F->max_parallel >= 0.0 && F->max_parallel <= 1.0)) return sdpcut_fail(h, SDPCUT_EINVAL, "max_parallel must lie in [0, 1]");
+        if (sel_size < 1) return sdpcut_fail(h, SDPCUT_EINVAL, "sel_size must be >= 1");
+        if (F->pool_size < sel_size) return sdpcut_fail(h, SDPCUT_EINVAL, "pool_size must be >= sel_size");
+        if (F->pool_size > SDPCUT_DIVERSE_MAX_POOL) return sdpcut_fail(h, SDPCUT_EINVAL, "pool_size must not exceed SDPCUT_DIVERSE_MAX_POOL");
+    } else {
+        if (strat == SDPCUT_STRAT_EFF)
+            return sdpcut_fail(h, SDPCUT_EINVAL, std::string(R.what) + ": strategy 6 (efficacy) is not served over several points; strategies 1, 2 and 4 are");
+        if (!batch_mode(strat))
+            return sdpcut_fail(h, SDPCUT_EINVAL, std::string(R.what) + " serves strategies 1 (feasibility), 2 (optimality) and 4 (combined)");
+        if (sel_size < 0) return sdpcut_fail(h, SDPCUT_EINVAL, "sel_size is negative");
+    }
     SDPCUT_NO_PENDING(h);
-    SDPCUT_NO_BOX(h, what);
-    if (bx && (rc = check_box_rows(h, what, n_points, *bx))) return rc;
+    SDPCUT_NO_BOX(h, R.what);
+    if (bx && (rc = check_box_rows(h, R.what, n_points, *bx))) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     NoPointAfter leave(h);
     NoBoxAfter unboxed(h);
     const int P = n_points;
     std::memset(out, 0, (size_t)P * sizeof(*out));
     if (info) std::memset(info, 0, (size_t)P * sizeof(*info));
-    const bool by_eff = strat == SDPCUT_STRAT_EFF;
-    const int64_t pool = pool_size < h->N ? pool_size : h->N;
-    const int64_t cap = sel_size < pool ? sel_size : pool;
+    const bool by_eff = strat == SDPCUT_STRAT_EFF;      // (the filtered batch only: strategy 2 on the efficacy score)
+    // the quota, the head the selection emits (the filter's pool, else the quota) and the capacity of a slice of the batch block
+    const int64_t sel = sel_size < h->N ? sel_size : h->N;
+    const int64_t head = !F ? sel : F->pool_size < h->N ? F->pool_size : h->N;
+    const int64_t cap = sel_size < head ? sel_size : head;
     const int ld = h->row_len_max;
     const uint32_t need = by_eff ? (uint32_t)SDPCUT_EIG : strat_need(strat);      // what score_batch computes; the efficacy launch follows it
     const bool shard = h->base != 0 || h->shard_rec != nullptr;
-    int route = bx ? batch_route_diverse_boxed(h->N, sel_size, pool_size, strat, h->exact_head, shard, h->nb_vars, P)
-                   : batch_route_diverse(h->N, sel_size, pool_size, strat, h->exact_head, shard);
+    int route;
+    if (F)
+        route = bx ? batch_route_diverse_boxed(h->N, sel_size, F->pool_size, strat, h->exact_head, shard, h->nb_vars, P)
+                   : batch_route_diverse(h->N, sel_size, F->pool_size, strat, h->exact_head, shard);
+    else
+        route = bx ? batch_route_boxed(h->N, cap, strat, h->exact_head, shard, h->nb_vars, P) : batch_route(h->N, cap, strat, h->exact_head, shard);
+    // the boxes reach the device only where the measure is scored (lambda_min knows no box); the per-point rounds always get theirs
     const BoxRows *bx_dev = (need & SDPCUT_NN) ? bx : nullptr;
+    // what the route function does not see: a kernel variant without a point axis, the combined regime resolved on the host
+    // (SDPCUT_OPT_AUTO_REGIME off), event timing of the single-point launches
     if (route == BATCH_FAST && (!batch_score_served(h, need, bx_dev != nullptr) || (strat == SDPCUT_STRAT_COMB && !h->auto_regime) || h->timing))
         route = BATCH_LOOP;
     const BatchLayout y = batch_layout(cap, ld, P);
     if ((rc = grow(h, h->pts.pinned, y.bytes))) return rc;
     char *block = (char *)h->pts.pinned.get();
-    // one point through the single-point filtered round, in its box where the batch has boxes
+    // one point through the single-point call (which also fills info[p]), in its box where the batch has boxes
     auto single = [&](int p) -> int {
         int rc1;
-        if (bx && (rc1 = sdpcut_set_box(h, bx->lb + (size_t)p * bx->ld, bx->ub + (size_t)p * bx->ld))) return rc1;
-        sdpcut_round_csr_t *o = out + p;
-        rc1 = sdpcut_round_csr_diverse(h, points + (size_t)p * point_ld, strat, sel_size, pool_size, max_parallel, o, info ? info + p : nullptr);
-        if (rc1) return rc1;
-        if (o->cap > 0 && o->idx) {
-            char *slot = block + batch_point_offset(y, p);
-            std::memcpy(slot, h->pinned.get(), csr_layout(o->cap, o->row_ld).bytes);
-            csr_out_from_block(slot, o);
-        }
-        return SDPCUT_OK;
+        if (bx && (rc1 = sdpcut_set_box(h, bx->lo(p), bx->hi(p)))) return rc1;
+        const double *point = points + (size_t)p * point_ld;
+        rc1 = F ? sdpcut_round_csr_diverse(h, point, strat, sel_size, F->pool_size, F->max_parallel, out + p, info ? info + p : nullptr)
+                : sdpcut_round_csr(h, point, strat, sel_size, out + p);
+        return round_into_slot(h, rc1, block + batch_point_offset(y, p), out + p);
     };
     if (route == BATCH_LOOP) {
         for (int p = 0; p < P; ++p)
@@ -528,15 +464,20 @@ static int round_csr_points_diverse_impl(sdpcut_ctx *h, int32_t n_points, const 
         return SDPCUT_OK;
     }
 
-    const DivPointsLayout dy = div_points_layout(P, pool, cap);
     if ((rc = ensure_points_scores(h, P))) return rc;
-    if ((rc = ensure_points_select(h, P, pool))) return rc;
-    if ((rc = ensure_points_div(h, P, dy.bytes))) return rc;
+    if ((rc = ensure_points_select(h, P, head))) return rc;
+    DivPointsLayout dy = {};
+    if (F) {
+        dy = div_points_layout(P, head, cap);
+        if ((rc = ensure_points_div(h, P, dy.bytes))) return rc;
+    }
     if (by_eff && (rc = ensure_points_eff(h, P))) return rc;
     PointsBufs &b = h->pts;
     TopkWs *ws = (TopkWs *)b.d_ws.get();
     const int64_t ws_words = (int64_t)(sizeof(TopkWs) / 8), n = h->L + h->nb_vars;
     if ((rc = upload_points(h, P, points, point_ld, ws, bx_dev))) return rc;
+    // the strong class of the combined strategy: counted by the score launch (a boxed batch: by strong_points_kernel behind its two
+    // launches), point p into ws[p].strong_rep
     int64_t *strong = need == (SDPCUT_EIG | SDPCUT_NN) ? ws->strong_rep : nullptr;
     if ((rc = score_batch(h, need, P, bx_dev != nullptr, strong, ws_words))) return rc;
     const double *eig = (need & SDPCUT_EIG) ? b.d_eig.get() : nullptr, *obj = (need & SDPCUT_NN) ? b.d_obj.get() : nullptr;
@@ -545,49 +486,57 @@ static int round_csr_points_diverse_impl(sdpcut_ctx *h, int32_t n_points, const 
         if ((rc = launch_efficacy_points(h, P, b.d_pts.get(), n, b.d_eig.get(), h->N, d_e, d_p, d_s))) return rc;
         obj = d_s;
     }
-    const int64_t sel = sel_size < h->N ? sel_size : h->N;
-    hipLaunchKernelGGL(tk_points_kernel, dim3((unsigned)P), dim3(TK_SMALLSEL_THREADS), 0, h->stream, batch_mode_diverse(strat), sel, (int)h->N, (int)pool,
+    hipLaunchKernelGGL(tk_points_kernel, dim3((unsigned)P), dim3(TK_SMALLSEL_THREADS), 0, h->stream, batch_mode_diverse(strat), sel, (int)h->N, (int)head,
                        eig, obj, h->N, ws, strat == SDPCUT_STRAT_COMB ? SDPCUT_BIG_M : 0.0, b.d_idx.get(), b.d_score.get());
     HIP_TRY(h, hipGetLastError());
-    char *dv = (char *)b.d_div.get();
-    DivPointsArgs A;
-    A.pool = pool; A.cap = cap; A.quota = sel_size; A.max_parallel = max_parallel; A.compare = max_parallel < 1.0 ? 1 : 0;
-    A.sel_c4 = ws->counters; A.c4_stride = ws_words; A.idx = b.d_idx.get(); A.score = b.d_score.get(); A.idx_base = h->base; A.n_local = h->N;
-    A.set5 = h->d_set_orig.get(); A.ks = h->d_k.get(); A.vars = b.d_pts.get(); A.vars_ld = n; A.nv = h->nb_vars; A.L = h->L; A.eig = eig; A.eig_ld = h->N;
-    A.row_coef = (double *)(dv + dy.coef); A.row_lam = (double *)(dv + dy.lam); A.row_ks = (int32_t *)(dv + dy.ks);
-    A.acc_idx = (int64_t *)(dv + dy.acc_idx); A.acc_score = (double *)(dv + dy.acc_score); A.info = (int64_t *)(dv + dy.info);
-    A.sel_out = (int64_t *)b.div_sel.dev();
-    if ((rc = launch_div_points(h, P, A))) return rc;
-    for (int p = 0; p < P; ++p) std::memset(block + batch_point_offset(y, p), 0, 128);
-    // the accepted entries are a head like any other: the assembly reads its length from word 3 of the point's walk counts and
-    // copies them into the slice's header
+    // what the assembly reads as the head of a point: the selection's, or -- the accepted entries are a head like any other -- the
+    // filter's, its length in word 3 of the point's walk counts, which the assembly copies into the slice's header
+    const int64_t *head_c4 = ws->counters, *head_idx = b.d_idx.get();
+    int64_t head_c4_stride = ws_words;
+    const double *head_score = b.d_score.get();
+    if (F) {
+        char *dv = (char *)b.d_div.get();
+        DivPointsArgs A;
+        A.pool = head; A.cap = cap; A.quota = sel_size; A.max_parallel = F->max_parallel; A.compare = F->max_parallel < 1.0 ? 1 : 0;
+        A.sel_c4 = ws->counters; A.c4_stride = ws_words; A.idx = b.d_idx.get(); A.score = b.d_score.get(); A.idx_base = h->base; A.n_local = h->N;
+        A.set5 = h->d_set_orig.get(); A.ks = h->d_k.get(); A.vars = b.d_pts.get(); A.vars_ld = n; A.nv = h->nb_vars; A.L = h->L; A.eig = eig; A.eig_ld = h->N;
+        A.row_coef = (double *)(dv + dy.coef); A.row_lam = (double *)(dv + dy.lam); A.row_ks = (int32_t *)(dv + dy.ks);
+        A.acc_idx = (int64_t *)(dv + dy.acc_idx); A.acc_score = (double *)(dv + dy.acc_score); A.info = (int64_t *)(dv + dy.info);
+        A.sel_out = (int64_t *)b.div_sel.dev();
+        if ((rc = launch_div_points(h, P, A))) return rc;
+        head_c4 = A.info; head_c4_stride = 8; head_idx = A.acc_idx; head_score = A.acc_score;
+    }
+    for (int p = 0; p < P; ++p) std::memset(block + batch_point_offset(y, p), 0, 128);      // headers: counters, n_rows, nnz, give-up flag
     auto assemble = [&](int p_first, int count) -> int {
-        return launch_round_csr_points(h, p_first, count, cap, ld, A.info, 8, A.acc_idx, A.acc_score, b.d_pts.get(), n, eig, h->N, b.d_agg.get(), BATCH_AGG_WORDS,
-                                       b.pinned.dev(), (int64_t)y.slice, ++h->round_serial);
+        return launch_round_csr_points(h, p_first, count, cap, ld, head_c4, head_c4_stride, head_idx, head_score, b.d_pts.get(), n, eig, h->N, b.d_agg.get(),
+                                       BATCH_AGG_WORDS, b.pinned.dev(), (int64_t)y.slice, ++h->round_serial);
     };
     if ((rc = assemble(0, P))) return rc;
-    HIP_TRY(h, sdpcut_sync(h));      // the one wait of the batch
+    HIP_TRY(h, sdpcut_sync(h));      // the one wait of the batch (a faulted kernel surfaces here as an error)
 
     std::vector<int> redo, again;
-    const int64_t *selc = (const int64_t *)b.div_sel.get();
+    const int64_t *selc = F ? (const int64_t *)b.div_sel.get() : nullptr;      // the filtered batch: the selection's counters of point p at selc + 8 p
     for (int p = 0; p < P; ++p) {
         const int64_t *hdr = (const int64_t *)(block + batch_point_offset(y, p));
         sdpcut_round_csr_t &o = out[p];
-        int64_t n_pool = 0;
+        int64_t n_head = 0;
         o.row_ld = ld;
-        if (!rank_fast_finish(h, by_eff ? SDPCUT_STRAT_OPT : strat, sel_size, pool, selc + 8 * p, &n_pool, &o.n_total, &o.new_strat, o.counters)) {
-            redo.push_back(p);      // a void selection: the single-point call resolves it
+        if (!rank_fast_finish(h, by_eff ? SDPCUT_STRAT_OPT : strat, sel_size, head, F ? selc + 8 * p : hdr, &n_head, &o.n_total, &o.new_strat, o.counters)) {
+            redo.push_back(p);      // a void selection: the single-point call resolves it (tie split or full sort)
             continue;
         }
-        if (by_eff) o.new_strat = SDPCUT_STRAT_EFF;
-        if (info) info[p].pool = n_pool;
-        if (n_pool <= 0) continue;      // an empty ranking: an empty block
+        if (F) {
+            if (by_eff) o.new_strat = SDPCUT_STRAT_EFF;
+            if (info) info[p].pool = n_head;
+            if (n_head <= 0) continue;      // an empty ranking: an empty block
+            if (info) { info[p].examined = hdr[0]; info[p].skipped_nonviolated = hdr[1]; info[p].rejected_parallel = hdr[2]; }
+        }
         ++h->stat_rounds;
-        if (info) { info[p].examined = hdr[0]; info[p].skipped_nonviolated = hdr[1]; info[p].rejected_parallel = hdr[2]; }
-        o.cap = sel_size < n_pool ? sel_size : n_pool;
-        o.n_out = hdr[3];
+        o.cap = F ? (sel_size < n_head ? sel_size : n_head) : cap;
+        o.n_out = F ? hdr[3] : n_head;
         if (hdr[10] && o.n_out > 0) again.push_back(p);
     }
+    // a point whose row assembly gave up its bounded look-back (rows.hip): once more over the same head, like csr_assemble_wait (round.hip)
     for (int p : again) {
         int64_t *hdr = (int64_t *)(block + batch_point_offset(y, p));
         hdr[8] = hdr[9] = hdr[10] = 0;
@@ -598,8 +547,10 @@ static int round_csr_points_diverse_impl(sdpcut_ctx *h, int32_t n_points, const 
         HIP_TRY(h, sdpcut_sync(h));
         for (int p : again)
             if (((const int64_t *)(block + batch_point_offset(y, p)))[10])
-                return sdpcut_fail(h, SDPCUT_EHIP, "round_csr_points_diverse: look-back of the row assembly timed out twice");
+                return sdpcut_fail(h, SDPCUT_EHIP, std::string(F ? "round_csr_points_diverse" : "round_csr_points") + ": look-back of the row assembly timed out twice");
     }
+    // (a redone point and an empty ranking of the filtered batch have no block: cap 0.  An answered point of the plain batch always
+    // has o.cap == cap > 0: cap == 0 takes the loop route, batch_route.h)
     for (int p = 0; p < P; ++p) {
         sdpcut_round_csr_t &o = out[p];
         if (o.cap <= 0) continue;
@@ -609,7 +560,7 @@ static int round_csr_points_diverse_impl(sdpcut_ctx *h, int32_t n_points, const 
         if (o.cap < cap) csr_block_shrink(slot, cap, o.cap, ld, o.n_out, o.n_out > 0 ? hdr[8] : 0, o.n_out > 0 ? hdr[9] : 0);
         csr_out_from_block(slot, &o);
     }
-    h->stat_diverse_points_fast += P - (int64_t)redo.size();
+    if (F) h->stat_diverse_points_fast += P - (int64_t)redo.size();
     for (int p : redo) {
         ++h->stat_points_redone;
         std::memset(out + p, 0, sizeof(*out));
@@ -634,7 +585,9 @@ int sdpcut_round_csr_points_diverse(sdpcut_handle h, int32_t n_points, const dou
 {
     if (!h) return SDPCUT_EINVAL;
     const BoxRows bx = {lb, ub, box_ld};
-    return round_csr_points_diverse_impl(h, n_points, points, point_ld, (lb || ub) ? &bx : nullptr, strat, sel_size, pool_size, max_parallel, out, info);
+    const PointsFilter filter = {pool_size, max_parallel, info};
+    const PointsRound R = {"sdpcut_round_csr_points_diverse", (lb || ub) ? &bx : nullptr, strat, sel_size, &filter};
+    return round_points(h, R, n_points, points, point_ld, out);
 }
 
 int sdpcut_score_points(sdpcut_handle h, int32_t n_points, const double *points, int64_t point_ld, uint32_t flags, double *eig_out,
@@ -648,7 +601,8 @@ int sdpcut_round_csr_points(sdpcut_handle h, int32_t n_points, const double *poi
                             sdpcut_round_csr_t *out)
 {
     if (!h) return SDPCUT_EINVAL;
-    return round_csr_points_impl(h, "sdpcut_round_csr_points", n_points, points, point_ld, nullptr, strat, sel_size, out);
+    const PointsRound R = {"sdpcut_round_csr_points", nullptr, strat, sel_size, nullptr};
+    return round_points(h, R, n_points, points, point_ld, out);
 }
 
 int sdpcut_score_points_boxed(sdpcut_handle h, int32_t n_points, const double *points, int64_t point_ld, const double *lb, const double *ub,
@@ -664,7 +618,8 @@ int sdpcut_round_csr_points_boxed(sdpcut_handle h, int32_t n_points, const doubl
 {
     if (!h) return SDPCUT_EINVAL;
     const BoxRows bx = {lb, ub, box_ld};
-    return round_csr_points_impl(h, "sdpcut_round_csr_points_boxed", n_points, points, point_ld, &bx, strat, sel_size, out);
+    const PointsRound R = {"sdpcut_round_csr_points_boxed", &bx, strat, sel_size, nullptr};
+    return round_points(h, R, n_points, points, point_ld, out);
 }
 
 } // extern "C"

@@ -51,8 +51,8 @@ CONSUMERS = {
     "rank.on_device": ("csrc/rank.hip", "rank_on_device: a void fast attempt, a void every-entry-visited selection -> the full sorts"),
     "topk.tie_split_void": ("csrc/topk.hip", "topk_tie_split: one of its own selections is void -> 1, the general path answers"),
     "tri.relaunch": ("csrc/tri.hip", "tri_separate: once more with fused_tail off, then 'selection void'"),
-    "points.again": ("csrc/points.hip", "round_csr_points[_boxed]: the `again` list and 'timed out twice'"),
-    "points.diverse_again": ("csrc/points.hip", "round_csr_points_diverse: the `again` list and 'timed out twice'"),
+    "points.again": ("csrc/points.hip", "round_points serving round_csr_points[_boxed]: the `again` list and 'timed out twice'"),
+    "points.diverse_again": ("csrc/points.hip", "round_points serving round_csr_points_diverse: the same `again` list, 'timed out twice' under its name"),
     "shard.void_record": ("csrc/shard.hip", "a void head writes nothing behind the record's header, word 4 set"),
     "distributed.unfused": ("sdpcutsel_via_nn_amd/distributed.py", "ShardedSelector.end_round: a void record -> the unfused route"),
 }

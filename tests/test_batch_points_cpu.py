@@ -179,3 +179,20 @@ def test_refusals_without_a_device():
     with pytest.raises(ValueError):
         sc.score_points(np.zeros((2, 9)), eig=False, obj=False)
     sc._h = None
+
+
+def test_one_driver_for_the_plain_and_the_filtered_batch():
+    """csrc/points.hip holds ONE body of the one-wait batched round (round_points; DESIGN.md section 5, "The batched round's
+    driver"): each step of the chain is written once, and the two functions it replaced are gone"""
+    text = open(os.path.join(CSRC, "points.hip")).read()
+    once = ("hipLaunchKernelGGL(tk_points_kernel,", "launch_round_csr_points(", "rank_fast_finish(", "++h->stat_points_redone", "route = BATCH_LOOP",
+            "std::memcpy(slot, h->pinned.get()", '": look-back of the row assembly timed out twice"', "launch_div_points(",
+            "if (hdr[10] && o.n_out > 0) again.push_back(p);", "++h->stat_fallbacks", "static int round_points(")
+    for piece in once:
+        assert text.count(piece) == 1, (piece, text.count(piece))
+    for gone in ("round_csr_points_impl", "round_csr_points_diverse_impl", "point_through_round"):
+        assert not re.search(r"\b%s\b" % gone, text), gone
+    # the three entry points fill in the description and call it
+    assert len(re.findall(r"return round_points\(h, R, n_points, points, point_ld, out\);", text)) == 3
+    # "the box of point p" is BoxRows' own: no caller forms the row addresses
+    assert not re.search(r"(lb|ub) \+ \(size_t\)p \* (bx->|bx\.)?ld", text.replace("return lb + (size_t)p * ld;", "").replace("return ub + (size_t)p * ld;", ""))
